@@ -11,13 +11,17 @@ This file: argument parsing and launch, the timed step (run_workload), the compa
 the timed step — per-phase times, rooflines, the parity legs against the oracle, step_excludes, the extra configs, the CPU baseline, the
 N > 1 plans — lives in bench_sections.py.  What each field of the line means is written in DESIGN.md §7, not on the line.
 
-stdout carries exactly ONE line: the compact JSON (numbers only, < 8 KB; tests/test_bench_line_cpu.py bounds it).  The detailed object
-(every section in full) goes to the side file `--detail-out` (default gpurun_out/bench_detail.json, or ./bench_detail.json).
+A plain run sets up, settles and warms up, times exactly K steps, writes the last step's outputs when `--dump-outputs DIR` is given
+(bench_outputs.py) and prints the line.  `--full` adds every section beside the headline (bench_sections.py).
+
+stdout carries exactly ONE line: the compact JSON (numbers only, < 8 KB; tests/test_bench_line_cpu.py bounds it).  With `--full` the
+detailed object (every section in full) goes to a side file: `--detail-out`, or the default that detail_path() picks.
 
 Headline workload (`value`): BASELINE.json configs[1] — create_n_cubes(10 000) = 120 000 triangles f32/3D and R = 1 000 000 create_ray
 rays PER GPU (weak scaling: rank r traverses rays [r*R, (r+1)*R) of the seed-0 stream).  `extra_configs` carries the other BASELINE
-configs, the reference's whole harness loop and a 12 M-triangle scene as one compact row each.  A run is never downgraded: `--gpus N`
-with no WORLD_SIZE re-executes itself under torch.distributed.run with N ranks; with a WORLD_SIZE that is not N it stops with an error.
+configs, the reference's whole harness loop and a 12 M-triangle scene as one compact row each (--full).  A run is never downgraded:
+`--gpus N` with no WORLD_SIZE re-executes itself under torch.distributed.run with N ranks; with a WORLD_SIZE that is not N it stops
+with an error.
 """
 from __future__ import annotations
 
@@ -55,7 +59,11 @@ def parse(argv=None):
            "(the engine's own folded binary array on first use), all = both arrays, beside = both by a second pass beside the walk; "
            "lazy: on first use (NOT in the step)")
     A("--collective-timeout", type=float, default=60.0, help="N>1: seconds the exchange plan may take before the replicate line is printed")
-    A("--regions", type=int, default=5, help="timed regions of exactly K steps each; `value` is the median region, all are on the line")
+    A("--regions", type=int, default=5, help="the K timed steps run as this many back-to-back regions (at most K); `value` is the "
+      "median region, all are on the line")
+    A("--full", action="store_true", help="also every section beside the headline (phases, rooflines, parity, pipelined, step_excludes, "
+      "extra_configs, cpu_baseline); without it a run times the headline and prints its line")
+    A("--dump-outputs", default=None, metavar="DIR", help="write what the timed step computed in its last step to DIR/<name>.npy")
     A("--settle-steps", type=int, default=300, help="untimed steps before the W warmup steps (clock ramp; at most 20 for big batches)")
     A("--no-cpu-baseline", action="store_true")
     A("--no-extra", action="store_true", help="skip the extra_configs sub-runs")
@@ -221,36 +229,56 @@ def run_workload(wl, args, env, steps, warmup, detailed, force_plan=None, region
     settle = args.settle_steps if (wl.R <= 2_000_000 and state["plan"] in ("single", "replicate")) else min(args.settle_steps, 20)
     for _ in range(settle + warmup):
         step()
-    # EXACTLY K steps between barrier + synchronize, max over ranks — `--regions` times back to back, the MEDIAN region is the figure and
-    # every region is on the line.  (The GPU boxes' host CPUs are shared: the one host thread of a step loop is descheduled for tens of
-    # ms now and then — r6_a: one such stall inside a 7 ms region read 470 instead of 2 900 Mrays/s.  A median over regions of K steps
-    # says what K steps take; a single region says what the neighbours did.)
-    region_s = [timed(steps) for _ in range(max(1, regions))]
-    elapsed = sorted(region_s)[len(region_s) // 2]
-    ms_per_step = elapsed * 1e3 / max(steps, 1)
+    # EXACTLY K steps in one loop between barrier + synchronize (every step ends in a host wait, so the clock read after it is the step's
+    # end), split into `--regions` back-to-back regions, max over ranks; the MEDIAN region's time per step is the figure and every region
+    # is on the line.  (The GPU boxes' host CPUs are shared: the one host thread of a step loop is descheduled for tens of ms now and
+    # then — r6_a: one such stall inside a 7 ms region read 470 instead of 2 900 Mrays/s.  A median over regions says what a step takes;
+    # a single region says what the neighbours did.)
+    k_all = max(steps, 1)
+    nreg = min(max(1, regions), k_all)
+    bounds = [i * k_all // nreg for i in range(nreg + 1)]
+    barrier()
+    stamps = [time.perf_counter()]
+    for _ in range(k_all):
+        step()
+        stamps.append(time.perf_counter())
+    barrier()
+    region_s = [stamps[bounds[i + 1]] - stamps[bounds[i]] for i in range(nreg)]
+    if n_gpus > 1:      # the job's time is the slowest rank's, region by region
+        tt = torch.tensor(region_s, dtype=torch.float64, device=dev)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        region_s = tt.tolist()
+    region_ms = [t * 1e3 / (bounds[i + 1] - bounds[i]) for i, t in enumerate(region_s)]
+    ms_per_step = sorted(region_ms)[len(region_ms) // 2]
     value = wl.total_rays / (ms_per_step * 1e-3) / 1e6   # Mrays/s, whole job (weak: N*R, strong: T)
     # ---- end of the timed region: everything below is reported beside it ----
 
     plan = state["plan"]
     builder = plan not in ("bcast", "bcast-torch") or rank == 0
     tree = bvh if builder else state["peer"]
+    outputs = None
+    if detailed and args.dump_outputs and rank == 0:     # (what a caller of the last step receives: copied to the host untimed)
+        from bench_outputs import step_outputs
+        outputs = step_outputs(wl, tree._hits, tree)
+    out = {
+        "workload": wl.tag, "harness": wl.harness, "config": wl.config_id, "dtype": wl.dtype_name, "value": round(value, 3),
+        "unit": "Mrays/s", "ms_per_step": round(ms_per_step, 4), "steps": steps, "warmup": warmup, "settle_steps": settle,
+        "regions_ms_per_step": [round(t, 4) for t in region_ms],
+        "scaling": wl.scaling, "triangles": wl.n_tri, "rays_this_rank": wl.R, "rays_total": wl.total_rays, "scene_dist": plan,
+        "flat_array": {0: "all", 1: "lazy", 2: "beside", 3: "eager"}[ctx.get_tuning(TUNE_FLATTEN_LAZY)],
+        "scene_dist_probe_ms_per_step": {k: round(v, 4) for k, v in probe_ms.items()} or None,
+    }
+    env["last"] = dict(bvh=bvh, tree=tree, builder=builder, outputs=outputs)
+    if not args.full:        # a plain run: the headline only
+        return out
     extra, phases, stats = sec.phases_and_roofline(wl, env, bvh, tree, builder, mode_flags, steps, detailed)
     hits_all = stats["hits"]
     if n_gpus > 1:   # whole-job hit count (untimed): lets a reader check the shards against one process over all rays
         ht = torch.tensor([hits_all], dtype=torch.int64, device=dev)
         dist.all_reduce(ht, op=dist.ReduceOp.SUM)
         hits_all = int(ht.item())
-    out = {
-        "workload": wl.tag, "harness": wl.harness, "config": wl.config_id, "dtype": wl.dtype_name, "value": round(value, 3),
-        "unit": "Mrays/s", "ms_per_step": round(ms_per_step, 4), "steps": steps, "warmup": warmup, "settle_steps": settle,
-        "regions_ms_per_step": [round(t * 1e3 / max(steps, 1), 4) for t in region_s],
-        "scaling": wl.scaling, "triangles": wl.n_tri, "rays_this_rank": wl.R, "rays_total": wl.total_rays, "scene_dist": plan,
-        "flat_array": {0: "all", 1: "lazy", 2: "beside", 3: "eager"}[ctx.get_tuning(TUNE_FLATTEN_LAZY)],
-        "hits_all_ranks": int(hits_all), "visited_per_ray": round(stats["visited"] / max(wl.R, 1), 2),
-        "scene_dist_probe_ms_per_step": {k: round(v, 4) for k, v in probe_ms.items()} or None,
-    }
-    out.update(extra)
-    env["last"] = dict(bvh=bvh, tree=tree, stats=stats, phases=phases, builder=builder)
+    out.update(extra, hits_all_ranks=int(hits_all), visited_per_ray=round(stats["visited"] / max(wl.R, 1), 2))
+    env["last"].update(stats=stats, phases=phases)
     if state.get("rebroadcasts"):
         out["rebroadcasts"] = state["rebroadcasts"]
     return out
@@ -306,9 +334,10 @@ def compact_line(d):
     out.update(_pick(d, ("phases_ms", "build_levels", "hits_all_ranks", "scene_dist_probe_ms_per_step")))
     if d.get("scene_dist_plans"):
         out["scene_dist_plans"] = _plans(d["scene_dist_plans"])
-    out["roofline"] = _pick(d.get("roofline"), ROOF_KEYS)
-    for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):       # the contract's six keys are always there (null = unmeasured)
-        out["roofline"].setdefault(k, None)
+    if d.get("roofline") is not None:      # (--full: a plain run measures no roofline)
+        out["roofline"] = _pick(d["roofline"], ROOF_KEYS)
+        for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):   # the contract's six keys are always there (null = unmeasured)
+            out["roofline"].setdefault(k, None)
     if d.get("roofline_build"):
         out["roofline_build"] = _pick(d["roofline_build"], ("frac", "ms", "algorithmic_bytes", "achieved", "unit"))
     if d.get("parity"):
@@ -430,13 +459,14 @@ def main():
     dpath = detail_path(args)
 
     def emit(detail):
-        """rank 0: the detailed object to the side file, the compact line — the ONE stdout line — to fd 1"""
-        detail = dict(detail, detail=os.path.relpath(dpath, ROOT))
-        try:
-            with open(dpath, "w") as f:
-                f.write(json.dumps(detail) + "\n")
-        except OSError as e:
-            detail["detail"] = f"not written: {e!r}"
+        """rank 0: the detailed object to the side file (--full or --detail-out), the compact line — the ONE stdout line — to fd 1"""
+        if args.full or args.detail_out:
+            detail = dict(detail, detail=os.path.relpath(dpath, ROOT))
+            try:
+                with open(dpath, "w") as f:
+                    f.write(json.dumps(detail) + "\n")
+            except OSError as e:
+                detail["detail"] = f"not written: {e!r}"
         text = render_line(detail)
         os.write(json_fd, (text + "\n").encode())
 
@@ -449,7 +479,8 @@ def main():
     out.clear()
     out.update(run.compose(res, wl))
 
-    if not args.no_parity and rank == 0:     # the GPU result of the headline batch against the CPU oracle, in-process
+    full = args.full      # every section beside the headline; a plain run prints the headline's line and nothing else
+    if full and not args.no_parity and rank == 0:     # the GPU result of the headline batch against the CPU oracle, in-process
         from oracle import orc
         if wl.harness:
             out["parity"], out["cpu_harness"] = sec.check_parity_harness(wl, env, orc, min(wl.R, args.parity_max_rays))
@@ -457,22 +488,25 @@ def main():
             out["parity"] = sec.check_parity(wl, env, orc, min(wl.R, args.parity_max_rays))
         if out.get("roofline_build") and env["last"].get("oracle_levels"):
             out["roofline_build"] = sec.build_roofline(wl, main_env["phases"], env["last"]["oracle_levels"])
-    if n_gpus == 1 and args.pipeline_streams > 1:
+    if full and n_gpus == 1 and args.pipeline_streams > 1:
         out["pipelined"] = sec.pipelined(wl, args, env, local_rank)
-    if n_gpus == 1 and args.workload == "cubes120k" and args.harness is None and not args.no_excluded:
+    if full and n_gpus == 1 and args.workload == "cubes120k" and args.harness is None and not args.no_excluded:
         try:
             out["step_excludes"] = sec.measure_excluded(wl, args, env, out["ms_per_step"])
         except Exception as e:   # a supplementary figure must never take the headline down
             out["step_excludes"] = {"error": repr(e)}
-    if not args.no_extra and args.workload == "cubes120k" and args.dtype == "f32" and args.harness is None:
+    if full and not args.no_extra and args.workload == "cubes120k" and args.dtype == "f32" and args.harness is None:
         out["extra_configs"] = run.extras(args, rank, dev)
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = sec.cpu_baseline(wl, args)
             out["speedup_vs_cpu_baseline"] = round(out["value"] / out["cpu_baseline"]["value"], 2)
         except Exception as e:
             out["cpu_baseline"] = {"value": None, "unit": "Mrays/s", "cores": None, "kind": "port", "sample": "", "error": repr(e)[:300]}
 
+    if rank == 0 and args.dump_outputs:
+        from bench_outputs import write_outputs
+        write_outputs(main_env["outputs"], args.dump_outputs)
     if rank == 0:
         sys.stdout.flush()
         emit(out)

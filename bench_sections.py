@@ -690,9 +690,9 @@ class Run:
             "config": {"workload": wl.describe(), "triangles": wl.n_tri, "rays_per_gpu": wl.R, "rays_total": wl.total_rays,
                        "scene_dist": res["scene_dist"], "flat_array": res.get("flat_array"),
                        "parallelism": f"rays sharded x{n}" + plan_words[res["scene_dist"]]},
-            "phases_ms": res["phases_ms"], "build_levels": res.get("build_levels"), "hits_all_ranks": res["hits_all_ranks"],
+            "phases_ms": res.get("phases_ms"), "build_levels": res.get("build_levels"), "hits_all_ranks": res.get("hits_all_ranks"),
             "scene_dist_probe_ms_per_step": res.get("scene_dist_probe_ms_per_step"), "scene_dist_plans": res.get("scene_dist_plans"),
-            "roofline": res["roofline"], "roofline_build": res.get("roofline_build"), "launch": self.launch_obj,
+            "roofline": res.get("roofline"), "roofline_build": res.get("roofline_build"), "launch": self.launch_obj,
             # None: no RCCL communicator in this run (N = 1, --backend gloo, --scene-dist replicate, or rccl_comm_error)
             "rccl": env["comm"].info() if env["comm"] is not None else None,
         }

@@ -213,3 +213,35 @@ def test_source_files_keep_their_shape_budget():
         assert len(lines) <= max_lines, (name, len(lines))
         wide = [(i + 1, len(ln)) for i, ln in enumerate(lines) if len(ln) > 140]
         assert not wide, (name, wide[:5])
+
+
+def test_dump_writer_is_finite_lossless_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (bench_outputs.write_outputs): every value written is finite, the non-finite ones (the FlatNode array's
+    Aabb::empty() shape entries, a miss's infinite distance) come back exactly from <name>_nonfinite, outputs that fit stay whole, and a
+    larger one is a seeded row sample within the budget — the same rows in its companion, the same on every call"""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench_outputs as bo
+    monkeypatch.setattr(bo, "DUMP_BUDGET", 1_000_000)
+    bounds = np.ones((2000, 6), np.float32)
+    bounds[::3, :3], bounds[::3, 3:], bounds[5, 0] = np.inf, -np.inf, np.nan
+    big = np.arange(300_000 * 3, dtype=np.float64).reshape(-1, 3)
+    big[::7, 0] = np.inf
+    outs = {"flat_bounds": bounds, "hit_indices": np.arange(100.0), "closest_isect": big}
+    dec = lambda v, c: np.where(c == 1, np.inf, np.where(c == -1, -np.inf, np.where(c == 2, np.nan, v)))
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bo.write_outputs(outs, str(d))
+    files = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert files == sorted(f.name for f in (tmp_path / "b").iterdir()) == sorted(
+        ["flat_bounds.npy", "flat_bounds_nonfinite.npy", "hit_indices.npy", "closest_isect.npy", "closest_isect_nonfinite.npy",
+         "closest_isect_rows.npy"])
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in got.values())
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / (k + ".npy"))) for k, v in got.items())
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 1_000_000
+    assert np.array_equal(dec(got["flat_bounds"], got["flat_bounds_nonfinite"]), bounds, equal_nan=True)
+    assert np.array_equal(got["hit_indices"], np.arange(100.0))
+    rows = got["closest_isect_rows"].astype(np.int64)
+    assert 0 < len(rows) < len(big) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(dec(got["closest_isect"], got["closest_isect_nonfinite"]), big[rows])

@@ -22,7 +22,7 @@ def _run(extra_args, env_extra=None):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(env_extra or {})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cubes", "2500", "--rays", "200000", "--steps", "5", "--warmup", "2",
-           "--settle-steps", "10", "--extra-steps", "3", "--cpu-sample-rays", "100000"] + extra_args
+           "--settle-steps", "10", "--extra-steps", "3", "--cpu-sample-rays", "100000", "--full"] + extra_args
     detail_file = os.path.join(tempfile.mkdtemp(prefix="bvh_bench_"), "detail.json")
     p = subprocess.run(cmd + ["--detail-out", detail_file], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
@@ -75,3 +75,69 @@ def test_harness_as_the_headline(mode):
     assert out["parity"]["equal"] is True and out["cpu_harness"]["value"] > 0
     assert "intersect_bh" in out["config"]["workload"] and out["phases_ms"]["ray_gen_ms"] > 0
     assert "step_excludes" not in out        # (those compare against the index step of `value`: not measured beside a harness headline)
+
+
+def test_plain_run_times_the_headline_and_dumps_what_it_computed(tmp_path):
+    """Without --full a run is the headline alone: exactly K timed steps (the regions add up to them), the line's contract keys, no section
+    beside it, no detail file.  --dump-outputs writes the last step's FlatNode array and CSR, and those are the oracle's for the same inputs."""
+    import bvh_amd
+    import numpy as np
+    from bvh_amd import testbase as tb
+    from oracle import orc
+    if bvh_amd.device_count() <= 0:
+        pytest.fail("GPU test selected but no HIP device is visible (no CPU fallback exists)")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    dump = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cubes", "2500", "--rays", "200000", "--steps", "7", "--warmup", "2",
+           "--settle-steps", "10", "--dump-outputs", str(dump)]
+    p = subprocess.run(cmd, env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "Mrays/s (build+traverse)" and out["unit"] == "Mrays/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["steps"] == 7 and out["value"] > 0 and out["ms_per_step"] > 0 and len(out["regions_ms_per_step"]) == 5
+    assert abs(out["value"] - 200000 / (out["ms_per_step"] * 1e-3) / 1e6) <= 2e-3 * out["value"]     # (both rounded on the line)
+    for k in ("parity", "roofline", "phases_ms", "pipelined", "step_excludes", "extra_configs", "cpu_baseline", "detail"):
+        assert k not in out, k
+    names = sorted(f.name for f in dump.iterdir())
+    assert names == ["flat_bounds.npy", "flat_bounds_nonfinite.npy", "flat_links.npy", "hit_indices.npy", "hit_offsets.npy"], names
+    assert sum(f.stat().st_size for f in dump.iterdir()) <= 64_000_000
+    _, aabbs = tb.create_n_cubes(2500)
+    oflat = orc.flatten(orc.build(aabbs).nodes)
+    ooff, oidx, _, _ = orc.traverse_flat(oflat, aabbs, orc.create_rays(0, 200000), threads=orc.max_threads())
+    got = {n[:-4]: np.load(dump / n) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+    assert np.array_equal(got["hit_offsets"], ooff.astype(np.float64)) and np.array_equal(got["hit_indices"], oidx.astype(np.float64))
+    # the shape entries' Aabb::empty() (+inf, -inf): 0 in flat_bounds, +1 / -1 in flat_bounds_nonfinite
+    v, c = got["flat_bounds"], got["flat_bounds_nonfinite"]
+    assert set(np.unique(c)) == {-1.0, 0.0, 1.0} and not v[c != 0].any()
+    assert np.array_equal(np.where(c == 1, np.inf, np.where(c == -1, -np.inf, v)), np.concatenate([oflat["min"], oflat["max"]], axis=1))
+    assert np.array_equal(got["flat_links"], np.stack([oflat["entry"], oflat["exit"], oflat["shape"]], axis=1).astype(np.float64))
+
+
+@pytest.mark.parametrize("mode", ["closest", "triangles"])
+def test_plain_harness_run_dumps_its_results(mode, tmp_path):
+    """--dump-outputs under --harness: the nearest hit per ray (closest) or the CSR with every candidate's Intersection (triangles)"""
+    import bvh_amd
+    import numpy as np
+    if bvh_amd.device_count() <= 0:
+        pytest.fail("GPU test selected but no HIP device is visible (no CPU fallback exists)")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cubes", "2500", "--rays", "200000", "--steps", "5", "--warmup", "2",
+           "--settle-steps", "10", "--harness", mode, "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["workload_name"] == "cubes120k+" + mode and out["steps"] == 5 and "parity" not in out
+    got = {f.name[:-4]: np.load(f) for f in tmp_path.iterdir()}
+    assert all(np.isfinite(a).all() for a in got.values())     # (misses' infinite distances are coded in <name>_nonfinite)
+    base = {k for k in got if not k.endswith("_nonfinite")}
+    assert all(k[:-len("_nonfinite")] in base and got[k].shape == got[k[:-len("_nonfinite")]].shape for k in set(got) - base)
+    assert got["flat_links"].shape[1] == 3 and got["flat_bounds"].dtype == np.float32 and "flat_bounds_nonfinite" in got
+    if mode == "closest":
+        assert base == {"flat_bounds", "flat_links", "closest_isect", "closest_shape"}
+        assert got["closest_isect"].shape == (200000, 3) and got["closest_shape"].shape == (200000,)
+    else:
+        assert base == {"flat_bounds", "flat_links", "hit_offsets", "hit_indices", "triangle_isect"}
+        assert got["hit_offsets"][-1] == len(got["hit_indices"]) == len(got["triangle_isect"]) > 0

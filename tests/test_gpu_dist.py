@@ -64,7 +64,7 @@ def test_bench_two_ranks_one_gpu(scene_dist):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "3", "--warmup", "1", "--cubes", str(cubes), "--rays", str(R),
-           "--backend", "gloo", "--one-device", "--scene-dist", scene_dist, "--no-extra"] + (["--scaling", "strong"] if strong else [])
+           "--backend", "gloo", "--one-device", "--scene-dist", scene_dist, "--no-extra", "--full"] + (["--scaling", "strong"] if strong else [])
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -99,7 +99,7 @@ def test_bench_launches_its_own_ranks():
     cubes, R = 2000, 60_000
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--cubes", str(cubes),
-           "--rays", str(R), "--backend", "gloo", "--one-device", "--no-extra"]
+           "--rays", str(R), "--backend", "gloo", "--one-device", "--no-extra", "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -115,6 +115,25 @@ def test_bench_launches_its_own_ranks():
         assert bad.returncode != 0 and not [ln for ln in bad.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_plain_two_rank_run_prints_the_headline():
+    """without --full an N > 1 run is the headline alone (both plans probed under --scene-dist auto, the faster one reported), nothing beside it"""
+    import bvh_amd
+    if bvh_amd.device_count() <= 0:
+        pytest.fail("GPU test selected but no HIP device is visible (no CPU fallback exists)")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--cubes", "2000",
+           "--rays", "60000", "--backend", "gloo", "--one-device"]
+    p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["n_gpus"] == 2 and out["steps"] == 6 and out["value"] > 0 and len(out["regions_ms_per_step"]) == 5
+    assert set(out["scene_dist_plans"]) == {"replicate", "bcast-torch"}
+    for k in ("parity", "roofline", "phases_ms", "extra_configs", "hits_all_ranks"):
+        assert k not in out, k
+
+
 def test_bench_exchange_plan_cannot_take_the_line_down():
     """N > 1, --scene-dist auto: the replicate plan (no data-path collective) is measured FIRST; the exchange plan — whose RCCL form has
     never run on more than one GPU — runs under a watchdog.  A collective that never returns (simulated) ends the run after
@@ -125,7 +144,7 @@ def test_bench_exchange_plan_cannot_take_the_line_down():
     cubes, R = 2000, 60_000
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--cubes", str(cubes),
-           "--rays", str(R), "--backend", "gloo", "--one-device", "--no-extra", "--no-parity", "--collective-timeout", "8"]
+           "--rays", str(R), "--backend", "gloo", "--one-device", "--no-extra", "--no-parity", "--collective-timeout", "8", "--full"]
     p = subprocess.run(cmd, env=dict(env, BVH_BENCH_TEST_HANG_EXCHANGE="1"), cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -157,7 +176,7 @@ def test_bench_four_ranks_share_the_gpu():
     cubes, R = 3000, 50_000
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "4", "--warmup", "2", "--cubes", str(cubes),
-           "--rays", str(R), "--backend", "gloo", "--one-device", "--no-extra"]
+           "--rays", str(R), "--backend", "gloo", "--one-device", "--no-extra", "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
@@ -180,7 +199,7 @@ def test_bench_n2_extras_carry_both_plans():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["BVH_BENCH_STRONG_RAYS"] = "4000000"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--cubes", "2000", "--rays", "60000",
-           "--backend", "gloo", "--one-device", "--extra-steps", "2", "--standin-detail", "4", "--settle-steps", "5"]
+           "--backend", "gloo", "--one-device", "--extra-steps", "2", "--standin-detail", "4", "--settle-steps", "5", "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])

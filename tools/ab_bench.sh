@@ -8,7 +8,7 @@ mkdir -p $(dirname $out); : > $out
 for rep in $(seq $reps); do
   for so in "$A" "$B"; do
     if [ "$so" = "-" ]; then unset BVH_AMD_SO; else export BVH_AMD_SO=$R/$so; fi
-    python bench.py --no-cpu-baseline --pipeline-streams 0 --no-extra $args 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --pipeline-streams 0 --no-extra $args 2>/dev/null | python -c "
 import json, sys
 j = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$so', j['value'], j['ms_per_step'], j['phases_ms'], 'parity', j.get('parity', {}).get('equal'))" >> $out

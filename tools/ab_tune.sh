@@ -6,7 +6,7 @@ cd $R
 for i in $(seq 1 ${ROUNDS:-3}); do
   for mode in base alt; do
     if [ $mode = alt ]; then export "$@"; fi
-    python bench.py --steps 300 --warmup 20 --no-cpu-baseline --pipeline-streams 0 --no-extra --no-parity 2>/dev/null | python -c "
+    python bench.py --full --steps 300 --warmup 20 --no-cpu-baseline --pipeline-streams 0 --no-extra --no-parity 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$mode', d['value'], d['ms_per_step'], d['phases_ms'])"
     if [ $mode = alt ]; then for kv in "$@"; do unset "${kv%%=*}"; done; fi
   done

@@ -11,5 +11,5 @@ for n in 100000 1000000; do
 echo "== big_scene_check $n cubes"; timeout 900 python tools/big_scene_check.py $n 2>&1 | grep -v "^RCCL\|^HIP\|^ROCm\|^Hostname\|^Librccl\|amdgpu.ids"
 done
 echo "== bench cubes12m"
-python bench.py --workload cubes12m --steps 20 --warmup 3 --settle-steps 5 --no-cpu-baseline --pipeline-streams 0 --no-extra --parity-max-rays 1000000 2>/dev/null | python -c "
+python bench.py --full --workload cubes12m --steps 20 --warmup 3 --settle-steps 5 --no-cpu-baseline --pipeline-streams 0 --no-extra --parity-max-rays 1000000 2>/dev/null | python -c "
 import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(j['value'], j['ms_per_step'], j['phases_ms'], j['parity'])"

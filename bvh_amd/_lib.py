@@ -142,6 +142,8 @@ SYMBOLS = [
     ("bvhgpu_hits_fetch", _i, [_vp, _vp, _vp, _vp, _i]),
     ("bvhgpu_hits_device", _i, [_vp, _pp, _pp, _pp]),
     ("bvhgpu_hits_destroy", None, [_vp]),
+    ("bvhgpu_query_f32", _i, [_vp, _i, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_query_f64", _i, [_vp, _i, _vp, _sz, _i, _u, _pp]),
     ("bvhgpu_enable_timing", _i, [_vp, _i]),
     ("bvhgpu_last_timings", _i, [_vp, C.POINTER(Timings)]),
     ("bvhgpu_obj_parse", _i, [C.c_char_p, _sz, C.POINTER(C.POINTER(C.c_float)), C.POINTER(_sz), _vp]),
@@ -166,6 +168,9 @@ TUNE_BUILD_LEVEL_TILE = 20      # builder, two launches per level: positions per
 TUNE_FLATTEN_INLINE = 21        # f32: the builder's wave tier writes the flatten's FLAT / WIDE parts for its subtrees itself (1 default, 0 = the flatten kernel writes everything)
 TUNE_HOST_CHUNKS = 17            # bvhgpu_traverse_host_*: chunks the batch is walked in (0, default = by batch size)
 TUNE_BUILD_LEVEL_PERSIST = 16    # builder, level tier: tree levels 3.. of the tier as ONE persistent launch, one level-3 subtree per XCD (1) or a launch per level (0)
+TUNE_QUERY_VARIANT = 22         # bvhgpu_query_*: 0 binary walk, 1 wide walk where it applies, -1 (default) wide from a measured batch size on
+QUERY_AABB, QUERY_POINT, QUERY_BALL = 1, 2, 3   # bvhgpu_query_* kinds
+QUERY_WIDTH = {QUERY_AABB: 6, QUERY_POINT: 3, QUERY_BALL: 4}   # scalars per query
 TRAVERSE_RAYS_OD6 = 512
 WALK_WIDE, WALK_STAGED, WALK_REC8, WALK_F64_GUIDE = 1, 2, 4, 8   # bvhgpu_hits_walk_info
 ABI_VERSION = 7

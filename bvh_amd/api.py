@@ -237,6 +237,39 @@ class Aabb:
         return f"Aabb(min={self.min.tolist()}, max={self.max.tolist()})"
 
 
+class Ball:
+    """struct Ball<T,3> (ball.rs:13-19): centre + radius; Sphere = Ball (ball.rs:23).  A point query is a length-3 sequence or array."""
+
+    def __init__(self, center, radius, dtype=np.float32):
+        self.center = np.asarray(center, dtype=dtype).reshape(3).copy()
+        self.radius = np.dtype(dtype).type(radius)
+
+    @staticmethod
+    def new(center, radius, dtype=np.float32) -> "Ball":  # ball.rs:30-32
+        return Ball(center, radius, dtype)
+
+    def as4(self) -> np.ndarray:
+        return np.concatenate([self.center, np.asarray([self.radius], dtype=self.center.dtype)])
+
+    def __repr__(self):
+        return f"Ball(center={self.center.tolist()}, radius={float(self.radius)})"
+
+
+Sphere = Ball
+
+
+def _query_row(query, ft):
+    """(kind, one row of scalars) of an Aabb / Ball / point query in the tree's dtype"""
+    if isinstance(query, Aabb):
+        return _lib.QUERY_AABB, np.asarray(query.as6(), dtype=ft)
+    if isinstance(query, Ball):
+        return _lib.QUERY_BALL, np.asarray(query.as4(), dtype=ft)
+    p = np.asarray(query, dtype=ft).reshape(-1)
+    if p.shape != (3,):
+        raise TypeError("traverse takes a Ray, an Aabb, a Ball / Sphere or a point (3 coordinates)")
+    return _lib.QUERY_POINT, p
+
+
 class Bounded:
     """trait Bounded (aabb_impl.rs:28-56)."""
 
@@ -622,13 +655,56 @@ class _TreeBase:
         return int(o.value or 0), int(i.value or 0)
 
     def traverse(self, query, shapes: Sequence) -> List:
-        """BoundingHierarchy::traverse (bounding_hierarchy.rs:246-250): the shapes whose AABB `query`
-        (a Ray) intersects, in the reference's order."""
-        if not isinstance(query, Ray):
-            raise NotImplementedError("the MI355X engine implements traverse for Ray queries "
-                                      "(IntersectsAabb for Aabb/Point/Ball are out of scope, SURVEY §2)")
-        _, idx, _, _ = self.traverse_batch(query._batch)
+        """BoundingHierarchy::traverse (bounding_hierarchy.rs:246-250): the shapes whose AABB `query` intersects, in the
+        reference's order.  `query`: a Ray, an Aabb, a Ball / Sphere or a point (the crate's four IntersectsAabb types)."""
+        if isinstance(query, Ray):
+            _, idx, _, _ = self.traverse_batch(query._batch)
+        else:
+            kind, row = _query_row(query, np.float32 if self.sfx == "f32" else np.float64)
+            _, idx = self.query_batch(kind, row.reshape(1, -1))
         return [shapes[i] for i in idx.tolist()]
+
+    # ---- AABB / point / ball queries --------------------------------------------------------
+    def query_batch(self, kind, queries, fetch: bool = True):
+        """bvhgpu_query_*: FlatBvh::traverse (flat_bvh.rs:396-431) for a batch of AABB / point / ball queries.
+        kind: "aabb" / "point" / "ball" (or _lib.QUERY_*); queries: (n, 6) / (n, 3) / (n, 4) in the tree's dtype — a numpy array
+        (HOST) or a torch GPU tensor (DEVICE), or None with kind "aabb" for the tree's own shape AABBs (self_overlaps).
+        returns (offsets[n+1], indices[total]) in the reference's per-query order; fetch=False returns (None, None) and leaves
+        the result in HBM (hits_device)."""
+        kind = {"aabb": _lib.QUERY_AABB, "point": _lib.QUERY_POINT, "ball": _lib.QUERY_BALL, "sphere": _lib.QUERY_BALL}.get(kind, kind)
+        lib = _lib.load()
+        fn = getattr(lib, f"bvhgpu_query_{self.sfx}")
+        ft = np.float32 if self.sfx == "f32" else np.float64
+        width = _lib.QUERY_WIDTH.get(kind, 1)
+        keep = None
+        if queries is None:
+            n = self.info()[0]
+            qp, mem = None, HOST
+        elif _is_device_tensor(queries):
+            if str(queries.dtype) != ("torch.float32" if self.sfx == "f32" else "torch.float64"):
+                raise BvhGpuError(_lib.DTYPE_MISMATCH, "query dtype differs from tree dtype")
+            keep = queries.contiguous()
+            n = keep.numel() // width
+            qp, mem = ptr(keep.data_ptr()), DEVICE
+        else:
+            if isinstance(queries, np.ndarray) and queries.dtype != ft:
+                raise BvhGpuError(_lib.DTYPE_MISMATCH, "query dtype differs from tree dtype")
+            keep = np.ascontiguousarray(queries, dtype=ft).reshape(-1)
+            n = keep.size // width
+            qp, mem = ptr(keep), HOST
+        check(fn(self._t, kind, qp, n, mem, 0, C.byref(self._hits.h)), self.ctx._h)
+        if not fetch:
+            return None, None
+        return self._hits.fetch(n)
+
+    def self_overlaps(self, fetch: bool = True):
+        """every shape's AABB against the tree (broad phase): row i = the shapes whose AABB touches shape i's, in the
+        reference's order (row i contains i).  No upload: the tree's own boxes are the queries."""
+        return self.query_batch(_lib.QUERY_AABB, None, fetch=fetch)
+
+    def query_kernel(self) -> str:
+        """the walk kernel of the last batch on this tree's result object (bvhgpu_hits_walk_kernel)"""
+        return self._hits.walk_kernel()
 
     # ---- multi-GPU scene transport ---------------------------------------------------------
     def scene_nbytes(self) -> int:
@@ -867,6 +943,10 @@ class Bvh(_TreeBase):
         (bvh_node.rs:288-319 visits the same boxes in the same order)."""
         self.flatten_in_place()
         return super().traverse(query, shapes)
+
+    def query_batch(self, kind, queries, fetch: bool = True):
+        self.flatten_in_place()
+        return super().query_batch(kind, queries, fetch)
 
     def nearest_batch(self, points, triangles: bool = False):
         """Bvh::nearest_to answered by the flat loop (flat_bvh.rs:513-562): the distance is the same as the

@@ -246,6 +246,7 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
         *hits = h;
         const auto* dev = static_cast<const typename Traits<T>::Ray*>(
             to_device(ctx, rays, n_rays * sizeof(typename Traits<T>::Ray), mem, ctx->upload));
+        h->pend_kind = 0; h->pend_queries = nullptr; h->pend_qwide = false;   // (the object may have held a query batch)
         if (async) {
             h->force_binary = false; h->pend_attempts = 0; h->deferred_rc = 0; h->replays = 0;
             h->pend_gen = tree->gen; h->pend_on_pending = tree->pending_build || tree->pending_recv;
@@ -255,6 +256,42 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
         } else {
             traverse_batch<T>(tree, dev, n_rays, flags, h);
         }
+        return (int)BVHGPU_OK;
+    });
+}
+
+// bvhgpu_query_*: an AABB / point / ball batch (query.hip).  queries == NULL: the tree's own shape AABBs (self-overlap).
+template <typename T>
+int do_query(bvhgpu_tree* tree, int kind, const T* queries, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
+    if (!tree) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = tree->ctx;
+    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
+    if (kind != BVHGPU_QUERY_AABB && kind != BVHGPU_QUERY_POINT && kind != BVHGPU_QUERY_BALL) return fail(ctx, BVHGPU_INVALID_ARG, "unknown query kind");
+    if (flags != 0) return fail(ctx, BVHGPU_INVALID_ARG, "query flags are reserved (0)");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    { const int rc = settle(tree); if (rc != BVHGPU_OK) return rc; }
+    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
+    if (tree->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from query dtype");
+    if (!tree->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    const bool self = queries == nullptr;
+    if (self && !(kind == BVHGPU_QUERY_AABB && n == tree->n))
+        return fail(ctx, BVHGPU_INVALID_ARG, "queries is NULL: only BVHGPU_QUERY_AABB with n = the tree's shape count (self-overlap)");
+    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 queries in one batch");
+    if (tree->exact_only && !tree->built && !tree->unfolded)
+        return fail(ctx, BVHGPU_INVALID_ARG, "an imported tree whose build had a split without SAH winner: its leaves' navigator boxes were folded away");
+    const size_t per = kind == BVHGPU_QUERY_AABB ? 6 : (kind == BVHGPU_QUERY_POINT ? 3 : 4);
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        bvhgpu_hits* h = *hits;
+        if (!h) h = new bvhgpu_hits();
+        *hits = h;
+        const T* dev = self ? tree->aabbs.as<T>() : queries;
+        if (!self && mem == BVHGPU_HOST && n) {   // staged into the result object: a replay reads them again
+            h->qbuf.reserve(n * per * sizeof(T));
+            BVH_HIP(hipMemcpyAsync(h->qbuf.p, queries, n * per * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+            dev = h->qbuf.as<T>();
+        }
+        query_batch<T>(tree, kind, dev, n, h);
         return (int)BVHGPU_OK;
     });
 }
@@ -1157,6 +1194,13 @@ int bvhgpu_traverse_f64(bvhgpu_tree* tree, const bvhgpu_ray_f64* rays, size_t n_
     return do_traverse<double>(tree, rays, n_rays, mem, flags, hits);
 }
 
+int bvhgpu_query_f32(bvhgpu_tree* tree, int kind, const float* queries, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_query<float>(tree, kind, queries, n, mem, flags, hits);
+}
+int bvhgpu_query_f64(bvhgpu_tree* tree, int kind, const double* queries, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_query<double>(tree, kind, queries, n, mem, flags, hits);
+}
+
 int bvhgpu_traverse_host_f32(bvhgpu_tree* tree, const float* origins, const float* directions, size_t n_rays, unsigned flags, uint32_t* offsets,
                              uint32_t* indices, size_t indices_cap, uint64_t* total) {
     return do_traverse_host<float>(tree, nullptr, 0, false, origins, directions, n_rays, flags, offsets, indices, indices_cap, total);
@@ -1251,7 +1295,7 @@ int bvhgpu_hits_info(const bvhgpu_hits* h, size_t* n_rays, uint64_t* total, bvhg
 int bvhgpu_hits_walk_info(const bvhgpu_hits* h, unsigned* flags) {
     if (!h || !flags) return BVHGPU_INVALID_ARG;
     if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    *flags = (h->pend_wide ? BVHGPU_WALK_WIDE : 0u) | (h->pend_wide && h->pend_staged ? BVHGPU_WALK_STAGED : 0u) |
+    *flags = (h->pend_wide || h->pend_qwide ? BVHGPU_WALK_WIDE : 0u) | (h->pend_wide && h->pend_staged ? BVHGPU_WALK_STAGED : 0u) |
              (h->pend_wide && h->pend_rec8 ? BVHGPU_WALK_REC8 : 0u) | (h->pend_wide && h->pend_guide ? BVHGPU_WALK_F64_GUIDE : 0u);
     return BVHGPU_OK;
 }
@@ -1295,7 +1339,7 @@ void bvhgpu_hits_destroy(bvhgpu_hits* h) {
     h->indices.release(); h->tslice.release(); h->blocksums.release(); h->scan_sums.release(); h->ctr.release();
     h->isect.release(); h->closest.release(); h->closest_prim.release(); h->closest_key.release();
     h->heap_dist.release(); h->heap_node.release();
-    h->wg_items.release(); h->raybuf.release();
+    h->wg_items.release(); h->raybuf.release(); h->qbuf.release();
     if (h->ev_items) (void)hipEventDestroy(h->ev_items);
     h->wcounts.release(); h->ray_mask.release(); h->item_cnt.release(); h->wstack.release(); h->ray_items.release(); h->witems.release();
     if (h->pin) (void)hipHostFree(h->pin);

@@ -77,7 +77,7 @@ struct bvhgpu_ctx {
     bool own_stream = false;
     std::string err;
     int n_cu = 256;
-    int tune[BVHGPU_TUNE_COUNT] = {3, -1, -1, 16384, 0, 0, 1, 0, 0, 0, 0, 0, -1, 1, 1, 1, 0, 0, 256, 2, 0, BVH_FLATTEN_INLINE_DEFAULT};  // bvhgpu_set_tuning defaults
+    int tune[BVHGPU_TUNE_COUNT] = {3, -1, -1, 16384, 0, 0, 1, 0, 0, 0, 0, 0, -1, 1, 1, 1, 0, 0, 256, 2, 0, BVH_FLATTEN_INLINE_DEFAULT, -1};  // bvhgpu_set_tuning defaults
     // timing
     bool timing = false;
     hipEvent_t ev[8] = {};
@@ -229,6 +229,11 @@ struct bvhgpu_hits {
     hipEvent_t ev_items = nullptr;      // the early item filter of this batch has finished (side stream → main stream)
     bvhgpu::DevBuf wg_items;            // per workgroup of the wide walk: {items at the front, items at the back} of its list region, written by
                                         // the early filter (front == NONE: the workgroup filters its rays itself)
+    // AABB / point / ball queries (query.hip): the batch in flight is a query batch of this kind (BVHGPU_QUERY_*; 0 = rays)
+    int pend_kind = 0;
+    const void* pend_queries = nullptr;  // its queries in HBM (the caller's, the tree's own AABBs, or `qbuf`)
+    bool pend_qwide = false;             // ... walked by k_query_wide (a lane's stack overflow replays it with the binary walk)
+    bvhgpu::DevBuf qbuf;                 // HOST queries staged here, so that a replay reads them again
     uint32_t replays = 0;               // times bvhgpu_hits_wait had to enqueue the asynchronous batch again
     int deferred_rc = 0;                // status of a completion that ran on behalf of another call (rebuild / destroy of the tree)
     std::string deferred_err;
@@ -264,6 +269,11 @@ template <typename T> void wide_from_trav(bvhgpu_tree* t);   // wide nodes + the
 void recv_finalize(bvhgpu_tree* t);
 // capi.hip: completes the asynchronous batches still in flight on a tree whose arrays are about to be overwritten or freed
 void settle_waiters(bvhgpu_tree* t);
+// query.hip: AABB / point / ball query batches (bvhgpu_query_*).  query_batch runs the batch to completion like traverse_batch;
+// launch_query is the walk launch of traverse_enqueue for a query batch (h->pend_kind != 0), which provides the CSR plumbing
+template <typename T> void query_batch(bvhgpu_tree* t, int kind, const T* queries_dev, size_t n, bvhgpu_hits* h);
+template <typename T> struct WalkOut;
+template <typename T> void launch_query(bvhgpu_tree* t, size_t n, const WalkOut<T>& w, bvhgpu_hits* h, uint32_t* ovf_flag);
 // refit.hip
 template <typename T> void refit_tree(bvhgpu_tree* t, const T* aabbs_dev);
 // traverse.hip

@@ -20,266 +20,9 @@
 #include <cstdio>
 #include <type_traits>
 
-#include "engine.hpp"
+#include "walk.hpp"
 
 namespace bvhgpu {
-
-constexpr int SCAN_ITEMS = 4;
-constexpr int SCAN_BLOCK = 256 * SCAN_ITEMS;   // rays per workgroup of the count scan
-
-// what a walk produces besides the CSR of shape indices
-enum : int {
-    MODE_INDICES = 0,   // Vec<&Shape> only
-    MODE_T_SLICE = 1,   // + Ray::intersection_slice_for_aabb per hit (2 scalars)
-    MODE_TRIANGLES = 2, // + Ray::intersects_triangle per hit: Intersection{distance,u,v} (3 scalars)
-    MODE_CLOSEST = 3    // no CSR: per ray the candidate triangle with the smallest distance
-};
-template <int MODE> struct ModeVals { static constexpr int N = MODE == MODE_T_SLICE ? 2 : (MODE == MODE_TRIANGLES ? 3 : 0); };
-
-// ---- node fetch: two (f32) / four (f64) 16-byte loads per lane -------------------------------
-template <typename T> struct NodeRegs { T mn[3], mx[3]; uint32_t exit, shape; };
-
-__device__ __forceinline__ NodeRegs<float> load_node(const TravNode<float>* p) {
-    const float4* q = reinterpret_cast<const float4*>(p);
-    float4 a = q[0], b = q[1];
-    NodeRegs<float> r;
-    r.mn[0] = a.x; r.mn[1] = a.y; r.mn[2] = a.z; r.exit = __float_as_uint(a.w);
-    r.mx[0] = b.x; r.mx[1] = b.y; r.mx[2] = b.z; r.shape = __float_as_uint(b.w);
-    return r;
-}
-__device__ __forceinline__ NodeRegs<double> load_node(const TravNode<double>* p) {
-    const double2* q = reinterpret_cast<const double2*>(p);
-    double2 a = q[0], b = q[1], c = q[2], d = q[3];
-    NodeRegs<double> r;
-    r.mn[0] = a.x; r.mn[1] = a.y; r.mn[2] = b.x;
-    r.mx[0] = b.y; r.mx[1] = c.x; r.mx[2] = c.y;
-    unsigned long long es = (unsigned long long)__double_as_longlong(d.x);
-    r.exit = (uint32_t)(es & 0xFFFFFFFFull);
-    r.shape = (uint32_t)(es >> 32);
-    return r;
-}
-
-struct HitRec { uint32_t ray, k, shape; };
-
-// everything a walk kernel writes
-template <typename T> struct WalkOut {
-    uint32_t* counts;            // per ray: number of shapes returned
-    HitRec* pool;                // hit records in arrival order
-    T* pool_v;                   // ModeVals::N scalars per record
-    unsigned long long pool_cap;
-    unsigned long long* ctr;     // [0] pool slots taken [1] device steps [2] leaf-entry steps [4] wave steps [5] candidates (closest mode)
-    const T* tris;               // n x 9 vertices (triangle modes)
-    T* closest;                  // per ray {distance,u,v} (closest mode)
-    uint32_t* closest_prim;      // per ray shape index or NONE
-    unsigned long long* closest_key;   // closest mode with rays cut into items (f32): per ray min over its items of {key(distance) << 32 | item << 28 | shape}
-                                 // (kept all-ones between batches; k_closest_resolve turns the winner into closest / closest_prim).  NULL: one lane owns the ray
-    uint32_t* item_cnt;          // wide walk with several items per ray: hits of item (ray, j), written only when non-zero
-    uint32_t* ray_items;         // ... and per ray the set of j that wrote one (kept all-zero between batches like counts)
-    uint32_t* scan_sums;         // wide walk: hits per SCAN_BLOCK rays, added up by the workgroups as they finish (a zeroed set; NULL: k_scan_reduce does the sums)
-    uint4* pool_pair;            // wide walk, whole rays, indices only: pair records {ray, k, shape, shape | NONE} (report_pair) in the pool's memory instead of the 12-byte
-                                 // HitRec: 8 bytes per hit, one offset gather per two hits in the scatter.  NULL: HitRec
-    uint32_t* raybuf;            // wide walk, whole rays, indices only: the first 2^stage_shift shapes of ray r go straight to raybuf[r << stage_shift | k]
-    uint32_t stage_shift;        // (4 bytes per hit, no record, no atomic); only later hits of a ray become pool records.  NULL: everything through the pool
-};
-
-// ---- Ray::intersects_triangle (ray_impl.rs:154-213), Möller–Trumbore with back-face culling.  Same
-//      sequence of IEEE operations as the reference: nalgebra cross = (ay*bz - az*by, az*bx - ax*bz,
-//      ax*by - ay*bx), dot = (a0*b0 + a1*b1) + a2*b2, no contraction.  Returns the Intersection fields.
-template <typename T> __device__ __forceinline__ void cross3(const T a[3], const T b[3], T out[3]) {
-    T p0 = a[1] * b[2], q0 = a[2] * b[1];
-    T p1 = a[2] * b[0], q1 = a[0] * b[2];
-    T p2 = a[0] * b[1], q2 = a[1] * b[0];
-    out[0] = p0 - q0; out[1] = p1 - q1; out[2] = p2 - q2;
-}
-template <typename T> __device__ __forceinline__ T dot3(const T a[3], const T b[3]) {
-    T x = a[0] * b[0], y = a[1] * b[1], z = a[2] * b[2];
-    T s = x + y;
-    return s + z;
-}
-template <typename T>
-__device__ __forceinline__ void ray_triangle(const T o[3], const T d[3], const T* __restrict__ tri, T out[3]) {
-    const T a[3] = {tri[0], tri[1], tri[2]};
-    T ab[3], ac[3], uvec[3], ao[3], vvec[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) { ab[k] = tri[3 + k] - a[k]; ac[k] = tri[6 + k] - a[k]; }   // :170-171
-    cross3<T>(d, ac, uvec);                                                                  // :176
-    const T det = dot3<T>(ab, uvec);                                                         // :181
-    out[0] = Traits<T>::inf(); out[1] = 0; out[2] = 0;
-    if (det < Traits<T>::eps()) return;                                                      // :186-188
-    const T inv_det = (T)1 / det;                                                            // :190
-#pragma unroll
-    for (int k = 0; k < 3; k++) ao[k] = o[k] - a[k];                                         // :193
-    const T u = dot3<T>(ao, uvec) * inv_det;                                                 // :196
-    out[1] = u;
-    if (!(u >= (T)0 && u <= (T)1)) return;                                                   // :199-201
-    cross3<T>(ao, ab, vvec);                                                                 // :204
-    const T v = dot3<T>(d, vvec) * inv_det;                                                  // :207
-    out[2] = v;
-    if (v < (T)0 || u + v > (T)1) return;                                                    // :209-211
-    const T dist = dot3<T>(ac, vvec) * inv_det;                                              // :213
-    if (dist > Traits<T>::eps()) out[0] = dist;                                              // :215-219
-}
-
-// ---- per-lane ray state
-template <typename T, int MODE> struct LaneRay {
-    T o[3], inv[3];
-    T d[MODE >= MODE_TRIANGLES ? 3 : 1];   // direction: only the triangle stage needs it
-    T best[MODE == MODE_CLOSEST ? 3 : 1];  // closest Intersection so far
-    uint32_t best_prim;
-    uint32_t r, cnt;
-    bool fin;                              // all components finite → NaN-free slab test is exact
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int k = 0; k < 3; k++) { o[k] = 0; inv[k] = 0; }
-        d[0] = 0; best[0] = 0; best_prim = NONE; r = NONE; cnt = 0; fin = true;
-    }
-    __device__ __forceinline__ void load(const typename Traits<T>::Ray* __restrict__ rays, uint32_t ray) {
-        const typename Traits<T>::Ray* rp = rays + ray;
-#pragma unroll
-        for (int k = 0; k < 3; k++) { o[k] = rp->o[k]; inv[k] = rp->inv[k]; }
-        if (MODE >= MODE_TRIANGLES) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) d[k] = rp->d[k];
-        }
-        if (MODE == MODE_CLOSEST) { best[0] = Traits<T>::inf(); best[1] = 0; best[2] = 0; }
-        best_prim = NONE; r = ray; cnt = 0;
-        fin = ray_is_finite<T>(o, inv);
-    }
-    // o / inv were filled by the caller (the guide walk's f32 view of an f64 ray): the rest of load()
-    __device__ __forceinline__ void loaded(uint32_t ray) {
-        best_prim = NONE; r = ray; cnt = 0;
-        fin = ray_is_finite<T>(o, inv);
-    }
-    // the ray has left the tree: its Vec / closest hit is complete
-    __device__ __forceinline__ void retire(const WalkOut<T>& w) {
-        if (MODE == MODE_CLOSEST) {
-            w.closest[3 * (size_t)r] = best[0]; w.closest[3 * (size_t)r + 1] = best[1]; w.closest[3 * (size_t)r + 2] = best[2];
-            w.closest_prim[r] = best_prim;
-        } else {
-            w.counts[r] = cnt;
-        }
-        r = NONE;
-    }
-};
-
-// Hit records go to the pool in per-wave chunks: one global atomic per chunk instead of one per wave-step with
-// a hit.  One address sustains only ≈88 atomics/µs on this chip, and a hit-heavy scene (58 M hits from 10 M
-// primary rays on the stand-in atrium) made the walk 8x slower with fixed 64-record chunks; a wave's chunk size
-// therefore doubles with every chunk it fills (64 → 8192), which bounds the slack by the records written.
-constexpr uint32_t POOL_CHUNK_MIN = 64;     // >= 64: one wave-step reports at most 64 hits
-constexpr uint32_t POOL_CHUNK_MAX = 8192;
-// wave-uniform cursor into this wave's current chunk of the hit pool
-struct PoolCursor { unsigned long long pos = 0; uint32_t left = 0; uint32_t next = POOL_CHUNK_MIN; };
-
-// mark the unused tail of a wave's chunk so that k_hits_scatter skips it
-__device__ __forceinline__ void pool_invalidate_tail(HitRec* pool, unsigned long long pool_cap, const PoolCursor& pc, int lane) {
-    for (uint32_t j = (uint32_t)lane; j < pc.left; j += WAVE)
-        if (pc.pos + j < pool_cap) pool[pc.pos + j].ray = NONE;
-}
-
-// A leaf box was hit (rec) in some lanes of the wave: do what the MODE asks for with the shape.
-template <typename T, int MODE>
-__device__ __forceinline__ void report(bool rec, uint32_t shape, T t0, T t1, LaneRay<T, MODE>& ray, const WalkOut<T>& w,
-                                       PoolCursor& pc, int lane, unsigned long long lt) {
-    const unsigned long long m = __ballot(rec);
-    if (!m) return;
-    T vals[3] = {t0, t1, 0};
-    if (MODE >= MODE_TRIANGLES && rec) ray_triangle<T>(ray.o, ray.d, w.tris + 9 * (size_t)shape, vals);
-    if (MODE == MODE_CLOSEST) {
-        if (rec) {
-            if (vals[0] < ray.best[0]) { ray.best[0] = vals[0]; ray.best[1] = vals[1]; ray.best[2] = vals[2]; ray.best_prim = shape; }
-            ray.cnt++;
-        }
-        return;
-    }
-    constexpr int NV = ModeVals<MODE>::N;
-    const uint32_t h = (uint32_t)__popcll(m);
-    if (h > pc.left) {   // wave-uniform: start a new chunk, invalidate what is left of the old one
-        pool_invalidate_tail(w.pool, w.pool_cap, pc, lane);
-        unsigned int blo = 0, bhi = 0;
-        if (lane == 0) {
-            unsigned long long b = atomicAdd(&w.ctr[0], (unsigned long long)pc.next);
-            blo = (unsigned int)b; bhi = (unsigned int)(b >> 32);
-        }
-        blo = __builtin_amdgcn_readfirstlane(blo); bhi = __builtin_amdgcn_readfirstlane(bhi);
-        pc.pos = ((unsigned long long)bhi << 32) | blo;
-        pc.left = pc.next;
-        pc.next = pc.next < POOL_CHUNK_MAX ? pc.next * 2 : POOL_CHUNK_MAX;
-    }
-    if (rec) {
-        const unsigned long long slot = pc.pos + __popcll(m & lt);
-        if (slot < w.pool_cap) {
-            HitRec hr; hr.ray = ray.r; hr.k = ray.cnt; hr.shape = shape;
-            w.pool[slot] = hr;
-#pragma unroll
-            for (int k = 0; k < NV; k++) w.pool_v[NV * slot + k] = vals[k];
-        }
-        ray.cnt++;
-    }
-    pc.pos += h; pc.left -= h;
-}
-
-struct __attribute__((packed, aligned(4))) DwordPair { uint32_t a, b; };   // two consecutive CSR entries, stored at once
-#ifndef SCATTER8_UNROLL
-#define SCATTER8_UNROLL 16
-#endif
-// Whole-ray index batches (WalkOut::pool_pair) write PAIR records, 16 bytes for two hits: {ray, k of the first, shape, shape | NONE}.  A lane
-// keeps one hit pending and writes a record when its ray's next hit arrives — or, alone, when the ray retires (flush) — so the pool holds
-// 8 bytes per hit instead of HitRec's 12, and the scatter reads one ray offset per TWO hits: the CSR assembly of a hit-heavy batch (457 M
-// hits for configs[3]'s 100 M rays) is bound by exactly those dependent gathers.  Measured against the 8-byte single-hit record
-// {ray, k << 25 | shape} it replaced (profiles/r4_pair_records_*_ab.log): 12.5 M incoherent rays 2.88 -> 2.75 ms per step, 10 M primary
-// rays 1.914 -> 1.868; and no limit on hits per ray or shapes per scene, so no fallback format.
-__device__ __forceinline__ void pool_invalidate_tail16(uint4* pool, unsigned long long pool_cap, const PoolCursor& pc, int lane) {
-    for (uint32_t j = (uint32_t)lane; j < pc.left; j += WAVE)
-        if (pc.pos + j < pool_cap) pool[pc.pos + j].x = NONE;
-}
-template <typename RAY>
-__device__ __forceinline__ void report_pair(bool rec, bool flush, uint32_t shape, RAY& ray, uint32_t& pend, uint4* pool, unsigned long long pool_cap,
-                                            unsigned long long* ctr, PoolCursor& pc, int lane, unsigned long long lt) {
-    const bool emit = (rec || flush) && pend != NONE;
-    const unsigned long long m = __ballot(emit);
-    if (m) {
-        const uint32_t h = (uint32_t)__popcll(m);
-        if (h > pc.left) {   // wave-uniform: start a new chunk, invalidate what is left of the old one
-            pool_invalidate_tail16(pool, pool_cap, pc, lane);
-            unsigned int blo = 0, bhi = 0;
-            if (lane == 0) {
-                unsigned long long b = atomicAdd(&ctr[0], (unsigned long long)pc.next);
-                blo = (unsigned int)b; bhi = (unsigned int)(b >> 32);
-            }
-            blo = __builtin_amdgcn_readfirstlane(blo); bhi = __builtin_amdgcn_readfirstlane(bhi);
-            pc.pos = ((unsigned long long)bhi << 32) | blo;
-            pc.left = pc.next;
-            pc.next = pc.next < POOL_CHUNK_MAX ? pc.next * 2 : POOL_CHUNK_MAX;
-        }
-        if (emit) {
-            const unsigned long long slot = pc.pos + __popcll(m & lt);
-            if (slot < pool_cap) pool[slot] = make_uint4(ray.r, ray.cnt - 1u, pend, rec ? shape : NONE);   // (the pending hit is number cnt - 1)
-        }
-        pc.pos += h; pc.left -= h;
-    }
-    if (rec) { pend = emit ? NONE : shape; ray.cnt++; }
-    else if (emit) pend = NONE;
-}
-
-template <typename T, int MODE>
-__device__ __forceinline__ void walk_epilogue(const WalkOut<T>& w, PoolCursor& pc, int lane, bool stats,
-                                              unsigned long long steps, unsigned long long leaf_steps,
-                                              unsigned long long wsteps, unsigned long long cands) {
-    if (MODE != MODE_CLOSEST) pool_invalidate_tail(w.pool, w.pool_cap, pc, lane);
-    if (stats) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            steps += __shfl_down(steps, d);
-            leaf_steps += __shfl_down(leaf_steps, d);
-            cands += __shfl_down(cands, d);
-        }
-        if (lane == 0) {
-            atomicAdd(&w.ctr[1], steps); atomicAdd(&w.ctr[2], leaf_steps); atomicAdd(&w.ctr[4], wsteps);
-            if (MODE == MODE_CLOSEST) atomicAdd(&w.ctr[5], cands);
-        }
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // one ray per lane per launch
@@ -768,30 +511,6 @@ constexpr uint32_t WIDE_ITEM_WHOLE = 16;               // j of an uncut ray (its
 constexpr uint32_t WIDE_BSUM_MAX = 128;                // 64-ray blocks per workgroup up to which the walk keeps the scan's block sums
 constexpr size_t WIDE_ITEM_MAX_RAYS = (size_t)1 << 27;
 
-template <typename T> struct WideRegs { T mn[3][4], mx[3][4]; uint32_t ref[4]; };
-template <typename T> struct WideIo {
-    static constexpr int CHUNKS = (int)(sizeof(WideRegs<T>) / 16);   // 7 (f32) / 13 (f64) 16-byte chunks per node
-    static_assert(sizeof(WideRegs<T>) % 16 == 0, "wide regs");
-    static __device__ __forceinline__ WideRegs<T> from_global(const WideNode<T>* __restrict__ p) {
-        const uint4* q = reinterpret_cast<const uint4*>(p);
-        uint4 c[CHUNKS];
-#pragma unroll
-        for (int j = 0; j < CHUNKS; j++) c[j] = q[j];
-        WideRegs<T> r;
-        __builtin_memcpy(&r, c, sizeof r);
-        return r;
-    }
-    // LDS copy: node-major, CHUNKS x 16 bytes per slot, so the chunk offsets are immediates of the ds_read_b128s
-    static __device__ __forceinline__ WideRegs<T> from_lds(const uint4* nodes, uint32_t slot) {
-        const uint4* q = nodes + __umul24(slot, (uint32_t)CHUNKS);   // (24-bit multiply: full rate, v_mul_lo_u32 is quarter rate)
-        uint4 c[CHUNKS];
-#pragma unroll
-        for (int j = 0; j < CHUNKS; j++) c[j] = q[j];
-        WideRegs<T> r;
-        __builtin_memcpy(&r, c, sizeof r);
-        return r;
-    }
-};
 
 // reference of the subtree in slot `c` of a node that sits in LDS slot `q`: grandchildren that are resident too are named by
 // their LDS slot (4-ary heap number), so that the walk never has to translate
@@ -1903,9 +1622,11 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
     const bool big_batch = !ordered && n_rays >= (size_t)ctx->tune[BVHGPU_TUNE_TRAVERSE_LDS_MIN_RAYS];
     // walk kernel: wide walk (see k_traverse_wide for what it needs), else persistent workgroups over the binary array with
     // its top in LDS, else one ray per lane per launch
+    // (a query batch — h->pend_kind, query.hip — goes through the plain CSR path of the binary walks whichever walk launch_query picks)
+    const bool query = h->pend_kind != 0;
     const bool use_wide = variant >= 3 && big_batch && t->has_wide && !t->exact_only && !t->unfolded && !stats &&
-                          mode != MODE_T_SLICE && !h->force_binary && t->n >= 2;
-    const bool use_lds = !use_wide && variant != 0 && t->slot_entry.p != nullptr && big_batch;
+                          mode != MODE_T_SLICE && !h->force_binary && t->n >= 2 && !query;
+    const bool use_lds = !use_wide && variant != 0 && t->slot_entry.p != nullptr && big_batch && !query;
     // several items per ray while a resident lane gets fewer than ~4 rays: the tail of the launch dominates there
     const bool few_rays = n_rays < (size_t)ctx->n_cu * 2048 * 4;
     uint32_t split_at = 0;
@@ -2159,7 +1880,8 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
     w.counts = counts; w.pool = h->pool.as<HitRec>(); w.pool_v = h->pool_t.as<T>(); w.pool_cap = cap;
     w.pool_pair = rec8 ? h->pool.as<uint4>() : nullptr;
     if (ctx->timing) { BVH_HIP(hipEventRecord(ctx->ev[4], st)); }
-    DISPATCH_WALK();
+    if (query) launch_query<T>(t, n_rays, w, h, ovf_flag);
+    else DISPATCH_WALK();
     if (ctx->timing) { BVH_HIP(hipEventRecord(ctx->ev[5], st)); }
     unsigned long long* bs = h->blocksums.as<unsigned long long>();
     uint32_t* offs = h->offsets.as<uint32_t>();
@@ -2241,6 +1963,9 @@ bool traverse_check(bvhgpu_hits* h) {
     if (ordered && (pin[7] & 1ull)) throw HipFail{hipErrorInvalidValue, "ORDERED_DEPTH", __LINE__};
     if (h->pend_guide && (pin[7] & WALK_FLAG_GUIDE_RANGE)) {   // a ray outside the guide walk's range: this result object goes back to the f64 walk
         h->no_guide = true; h->wcounts_clean = false; return false;   // (the replay of this batch walks in f64; traverse_enqueue sets the back-off)
+    }
+    if (h->pend_qwide && (pin[7] & 4ull)) {   // a lane of the wide query walk outgrew its LDS stack: replay with the binary walk
+        h->force_binary = true; return false;
     }
     if (h->pend_wide && (pin[7] & 4ull)) {   // a lane's stack outgrew LDS + workspace: the binary walks need no stack
         h->force_binary = true; h->wcounts_clean = false; h->bs_clean = false; h->ckey_clean = false; h->ray_items.release(); return false;

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define BVHGPU_ABI_VERSION 7 /* 7: bvhgpu_host_alloc/free/register/unregister, bvhgpu_traverse_host_*, bvhgpu_build_traverse_host_*, bvhgpu_traverse_host_indices, BVHGPU_TUNE_COUNT 20 (slots 17 = HOST_CHUNKS, 18 = WIDE_MIN_RAYS_PER_WG, 19 = HOST_ZERO_COPY).  6: BVHGPU_TUNE_COUNT 17 (slots 15 = FLATTEN_LAZY, 16 = BUILD_LEVEL_PERSIST), bvhgpu_hits_walk_kernel.  5: bvhgpu_rccl_info.  4: BVHGPU_TUNE_COUNT 15 (slot 14 = WIDE_F64_GUIDE), bvhgpu_hits_walk_info.  3: BVHGPU_REBROADCAST, broadcast status header, scene blob BVH6 (exact_only), BVHGPU_TUNE_COUNT 14 (slots 11 = WIDE_EARLY_ITEMS, 12 = WIDE_STAGE_SHIFT, 13 = WIDE_REC8), BVHGPU_TRAVERSE_RAYS_READY, bvhgpu_device_alloc/free/copy */
+#define BVHGPU_ABI_VERSION 7 /* 7: bvhgpu_host_alloc/free/register/unregister, bvhgpu_traverse_host_*, bvhgpu_build_traverse_host_*, bvhgpu_traverse_host_indices, bvhgpu_query_f32/_f64 + BVHGPU_QUERY_AABB/_POINT/_BALL, BVHGPU_TUNE_COUNT 23 (slots 17 = HOST_CHUNKS, 18 = WIDE_MIN_RAYS_PER_WG, 19 = HOST_ZERO_COPY, 20 = BUILD_LEVEL_TILE, 21 = FLATTEN_INLINE, 22 = QUERY_VARIANT).  6: BVHGPU_TUNE_COUNT 17 (slots 15 = FLATTEN_LAZY, 16 = BUILD_LEVEL_PERSIST), bvhgpu_hits_walk_kernel.  5: bvhgpu_rccl_info.  4: BVHGPU_TUNE_COUNT 15 (slot 14 = WIDE_F64_GUIDE), bvhgpu_hits_walk_info.  3: BVHGPU_REBROADCAST, broadcast status header, scene blob BVH6 (exact_only), BVHGPU_TUNE_COUNT 14 (slots 11 = WIDE_EARLY_ITEMS, 12 = WIDE_STAGE_SHIFT, 13 = WIDE_REC8), BVHGPU_TRAVERSE_RAYS_READY, bvhgpu_device_alloc/free/copy */
 #define BVHGPU_NONE 0xFFFFFFFFu /* u32::MAX marker (flat_bvh.rs:51-53, :124, :137) */
 
 typedef enum {
@@ -369,6 +369,28 @@ int bvhgpu_hits_fetch_closest(bvhgpu_hits *hits, void *isect, uint32_t *shape, i
 int bvhgpu_hits_device(const bvhgpu_hits *hits, const uint32_t **offsets, const uint32_t **indices, const void **tslice);
 void bvhgpu_hits_destroy(bvhgpu_hits *hits);
 
+/* ---- AABB / point / ball queries: <FlatBvh as BoundingHierarchy>::traverse (flat_bvh.rs:396-431) with the crate's other three
+ * IntersectsAabb queries (aabb/intersection.rs:35-45, ball.rs:102-106), for a BATCH.  Query i's list is the list
+ * FlatBvh::traverse(&q_i, shapes) returns, in its order (flat-array / DFS left-first order): inner entries test the node box, leaf
+ * entries the shape's own AABB, with the predicate of the kind (restated operation by operation, no contraction):
+ *   BVHGPU_QUERY_AABB   6 T per query (min xyz, max xyz)  Aabb::intersects_aabb (aabb_impl.rs:240-248): a hit unless, on some axis,
+ *                                                          q.max < lo or hi < q.min (touching counts; a NaN component hits every box)
+ *   BVHGPU_QUERY_POINT  3 T per query                      Aabb::contains (aabb_impl.rs:175-177): lo <= p <= hi on all axes (NaN: no hit)
+ *   BVHGPU_QUERY_BALL   4 T per query (centre xyz, radius) Ball::intersects_aabb (ball.rs:85-99): ((0 + d0*d0) + d1*d1) + d2*d2 <= r*r
+ *                                                          with d = clamp(c, lo, hi) - c, clamp as num_traits (c < lo ? lo : c > hi ? hi : c)
+ * `queries` lives in `mem` (HOST queries are staged into the result object).  queries == NULL with BVHGPU_QUERY_AABB and n equal to
+ * the tree's shape count: query i is shape i's own AABB (broad phase, no upload; row i contains i).  `flags` is reserved (0).
+ * The result is an ordinary result object: bvhgpu_hits_info / _fetch (tslice NULL) / _device / _walk_info / _walk_kernel / _wait
+ * apply; _fetch_triangles / _fetch_closest return BVHGPU_INVALID_ARG.  Synchronises like bvhgpu_traverse_*.  Errors: queries of
+ * another dtype than the tree's → BVHGPU_DTYPE_MISMATCH; an unknown kind → BVHGPU_INVALID_ARG; a tree that is not flattened →
+ * BVHGPU_NOT_FLATTENED; more than 2^32-1 hits → BVHGPU_OVERFLOW.  A tree imported (scene blob, broadcast) from a build that had a
+ * split without SAH winner is refused (BVHGPU_INVALID_ARG): its leaves' navigator boxes were folded away. */
+#define BVHGPU_QUERY_AABB 1
+#define BVHGPU_QUERY_POINT 2
+#define BVHGPU_QUERY_BALL 3
+int bvhgpu_query_f32(bvhgpu_tree *tree, int kind, const float *queries, size_t n, int mem, unsigned flags, bvhgpu_hits **hits);
+int bvhgpu_query_f64(bvhgpu_tree *tree, int kind, const double *queries, size_t n, int mem, unsigned flags, bvhgpu_hits **hits);
+
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */
 typedef struct { float build_ms, flatten_ms, traverse_kernel_ms, traverse_total_ms; } bvhgpu_timings;
@@ -448,7 +470,12 @@ typedef enum {
     BVHGPU_TUNE_FLATTEN_INLINE = 21,       /* f32 trees, the flatten enqueued with a build: the builder's wave tier writes the FlatNode / wide-node entries of the
                                               subtrees it builds (<= 64 shapes: 97 % of the nodes) itself and the flatten kernel behind it only the nodes above:
                                               1 (default), or 0: the flatten kernel writes everything.  Same arrays either way */
-    BVHGPU_TUNE_COUNT = 22
+    BVHGPU_TUNE_QUERY_VARIANT = 22,        /* bvhgpu_query_*: 0 = the binary walk (one query per lane over the folded array); 1 = the wide walk (four grandchild
+                                              boxes per step, per-lane stack in LDS) wherever its preconditions hold; -1 (default) = by kind, dtype and batch size where the
+                                              wide walk measured ahead on configs[1]'s scene: points (f32 below 262 144 queries, f64 always), f64
+                                              boxes, f64 balls from 262 144 queries; the binary walk otherwise (profiles/r7_query_bench.json).
+                                              Results never change */
+    BVHGPU_TUNE_COUNT = 23
 } bvhgpu_tune;
 int bvhgpu_set_tuning(bvhgpu_ctx *ctx, int knob, int value);
 int bvhgpu_get_tuning(const bvhgpu_ctx *ctx, int knob, int *value);

@@ -40,6 +40,9 @@ pub const BVHGPU_WALK_REC8: c_uint = 4;
 pub const BVHGPU_WALK_F64_GUIDE: c_uint = 8;
 pub const BVHGPU_COMM_ID_BYTES: usize = 128;
 pub const BVHGPU_BCAST_TRIANGLES: c_uint = 1;
+pub const BVHGPU_QUERY_AABB: c_int = 1;
+pub const BVHGPU_QUERY_POINT: c_int = 2;
+pub const BVHGPU_QUERY_BALL: c_int = 3;
 
 #[repr(C)] pub struct bvhgpu_ctx { _p: [u8; 0] }
 #[repr(C)] pub struct bvhgpu_tree { _p: [u8; 0] }
@@ -165,6 +168,9 @@ extern "C" {
     pub fn bvhgpu_hits_fetch_closest(h: *mut bvhgpu_hits, isect: *mut c_void, shape: *mut u32, mem: c_int) -> c_int;
     pub fn bvhgpu_hits_device(h: *const bvhgpu_hits, offsets: *mut *const u32, indices: *mut *const u32, tslice: *mut *const c_void) -> c_int;
     pub fn bvhgpu_hits_destroy(h: *mut bvhgpu_hits);
+    // AABB / point / ball queries: FlatBvh::traverse (flat_bvh.rs:396-431) with Aabb / Point / Ball (aabb/intersection.rs:35-45, ball.rs:102-106)
+    pub fn bvhgpu_query_f32(t: *mut bvhgpu_tree, kind: c_int, queries: *const f32, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_query_f64(t: *mut bvhgpu_tree, kind: c_int, queries: *const f64, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     // timing, scene ingest, tuning
     pub fn bvhgpu_enable_timing(ctx: *mut bvhgpu_ctx, on: c_int) -> c_int;
     pub fn bvhgpu_last_timings(ctx: *mut bvhgpu_ctx, out: *mut bvhgpu_timings) -> c_int;

@@ -1,8 +1,9 @@
 //! `GpuBvh<T>`: the `bvh` crate's `BoundingHierarchy<T, 3>` (src/bounding_hierarchy.rs:89-336) on an MI355X, for `T = f32`
 //! and `T = f64`, over the C ABI of libbvh_mi355x.so (include/bvh_mi355x.h).  Build / flatten / batched traversal run on the
 //! GPU and give the arrays the crate's own `Bvh::build` + `Bvh::flatten` + `FlatBvh::traverse` give, bit for bit (see
-//! DESIGN.md §2); queries that need user callbacks (`IntersectsAabb` for anything but rays, arbitrary `PointDistance`) run the
-//! crate's own loops over the downloaded flat array.
+//! DESIGN.md §2), and so do batches of the crate's other query types (`traverse_aabbs` / `traverse_points` / `traverse_balls` /
+//! `self_overlaps`); the trait's generic `traverse` (one query of any `IntersectsAabb` type — stable Rust cannot specialise it) and
+//! arbitrary `PointDistance` callbacks run the crate's own loops over the downloaded flat array.
 //!
 //! The scalar type is a sealed trait (`GpuScalar`, implemented for `f32` and `f64` only — the two instantiations the
 //! engine has): it names the `#[repr(C)]` images of `BvhNode` / `FlatNode` / `Ray` for that type and the `_f32` / `_f64` entry
@@ -19,6 +20,7 @@
 pub mod ffi;
 
 use bvh::aabb::{Aabb, IntersectsAabb};
+use bvh::ball::Ball;
 use bvh::bounding_hierarchy::{BHShape, BHValue, BoundingHierarchy};
 use bvh::bvh::{Bvh, BvhNode, BvhNodeBuildArgs};
 use bvh::flat_bvh::{FlatBvh, FlatNode};
@@ -85,6 +87,7 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
     unsafe fn traverse(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
     unsafe fn set_triangles(t: *mut ffi::bvhgpu_tree, verts: *const Self, n: usize, mem: c_int) -> c_int;
     unsafe fn tree_from_flat(ctx: *mut ffi::bvhgpu_ctx, flat: *const Self::Flat, n_flat: usize, shape_aabbs: *const Self, n: usize, out: *mut *mut ffi::bvhgpu_tree) -> c_int;
+    unsafe fn query(t: *mut ffi::bvhgpu_tree, kind: c_int, queries: *const Self, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
 
     fn node_to_crate(raw: &Self::Node) -> BvhNode<Self, 3>;
     fn flat_to_crate(raw: &Self::Flat) -> FlatNode<Self, 3>;
@@ -94,7 +97,7 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
 
 macro_rules! impl_gpu_scalar {
     ($t:ty, $dtype:expr, $node:ident, $flat:ident, $ray:ident, $build_flat:ident, $rebuild_flat:ident, $refit:ident, $traverse:ident,
-     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $flat_ctor:expr) => {
+     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $flat_ctor:expr) => {
         impl GpuScalar for $t {
             type Node = ffi::$node;
             type Flat = ffi::$flat;
@@ -126,6 +129,9 @@ macro_rules! impl_gpu_scalar {
             }
             unsafe fn tree_from_flat(ctx: *mut ffi::bvhgpu_ctx, flat: *const ffi::$flat, n_flat: usize, shape_aabbs: *const $t, n: usize, out: *mut *mut ffi::bvhgpu_tree) -> c_int {
                 ffi::$from_flat(ctx, flat, n_flat, shape_aabbs, n, out)
+            }
+            unsafe fn query(t: *mut ffi::bvhgpu_tree, kind: c_int, queries: *const $t, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int {
+                ffi::$query(t, kind, queries, n, mem, flags, hits)
             }
             fn node_to_crate(r: &ffi::$node) -> BvhNode<$t, 3> {
                 if r.shape != ffi::BVHGPU_NONE {
@@ -165,11 +171,11 @@ macro_rules! impl_gpu_scalar {
 }
 impl_gpu_scalar!(f32, ffi::BVHGPU_F32, bvhgpu_node_f32, bvhgpu_flat_f32, bvhgpu_ray_f32, bvhgpu_build_flat_f32, bvhgpu_rebuild_flat_f32,
                  bvhgpu_refit_f32, bvhgpu_traverse_f32, bvhgpu_tree_set_triangles_f32, bvhgpu_tree_from_flat_f32,
-                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32,
+                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f32 { min, max, entry, exit, shape });
 impl_gpu_scalar!(f64, ffi::BVHGPU_F64, bvhgpu_node_f64, bvhgpu_flat_f64, bvhgpu_ray_f64, bvhgpu_build_flat_f64, bvhgpu_rebuild_flat_f64,
                  bvhgpu_refit_f64, bvhgpu_traverse_f64, bvhgpu_tree_set_triangles_f64, bvhgpu_tree_from_flat_f64,
-                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64,
+                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f64 { min, max, entry, exit, shape, _pad: 0 });
 
 fn aabb_to_6<T: GpuScalar>(b: &Aabb<T, 3>) -> [T; 6] {
@@ -275,6 +281,53 @@ impl<T: GpuScalar> GpuBvh<T> {
         let mut raw = vec![T::Flat::default(); nf];
         unsafe { check(self.ctx, ffi::bvhgpu_flat_nodes(self.tree, raw.as_mut_ptr().cast(), ffi::BVHGPU_HOST)); }
         raw.iter().map(T::flat_to_crate).collect()
+    }
+
+    /// `FlatBvh::traverse` (src/flat_bvh.rs:396-431) for many boxes at once: query i's list is `flat.traverse(&aabbs[i], shapes)`'s
+    /// shape indices, in its order (`Aabb::intersects_aabb`, src/aabb/aabb_impl.rs:240-248; touching boxes count)
+    pub fn traverse_aabbs(&self, aabbs: &[Aabb<T, 3>]) -> BatchHits {
+        let q: Vec<[T; 6]> = aabbs.iter().map(aabb_to_6).collect();
+        self.query_batch(ffi::BVHGPU_QUERY_AABB, q.as_ptr().cast(), q.len())
+    }
+
+    /// The same for points (`Aabb::contains`, src/aabb/aabb_impl.rs:175-177)
+    pub fn traverse_points(&self, points: &[Point3<T>]) -> BatchHits {
+        let q: Vec<[T; 3]> = points.iter().map(|p| [p.x, p.y, p.z]).collect();
+        self.query_batch(ffi::BVHGPU_QUERY_POINT, q.as_ptr().cast(), q.len())
+    }
+
+    /// The same for balls / spheres (`Ball::intersects_aabb`, src/ball.rs:85-99)
+    pub fn traverse_balls(&self, balls: &[Ball<T, 3>]) -> BatchHits {
+        let q: Vec<[T; 4]> = balls.iter().map(|b| [b.center.x, b.center.y, b.center.z, b.radius]).collect();
+        self.query_batch(ffi::BVHGPU_QUERY_BALL, q.as_ptr().cast(), q.len())
+    }
+
+    /// Broad phase: every shape's AABB against the hierarchy (row i = the shapes whose AABB touches shape i's, in
+    /// `FlatBvh::traverse` order; row i contains i).  The tree's own copy of the boxes is the query batch: nothing is uploaded.
+    pub fn self_overlaps(&self) -> BatchHits {
+        self.query_batch(ffi::BVHGPU_QUERY_AABB, core::ptr::null(), self.n_shapes)
+    }
+
+    fn query_batch(&self, kind: c_int, queries: *const T, n: usize) -> BatchHits {
+        assert!(!self.flat_stale, "rebuild_async: call sync_flat() before a query batch");
+        let mut hits = core::ptr::null_mut();
+        let mut offsets = vec![0u32; n + 1];
+        let mut total = 0u64;
+        unsafe {
+            let rc = T::query(self.tree, kind, queries, n, ffi::BVHGPU_HOST, 0, &mut hits);
+            if rc == ffi::BVHGPU_OK {
+                check(self.ctx, ffi::bvhgpu_hits_info(hits, core::ptr::null_mut(), &mut total, core::ptr::null_mut()));
+            }
+            let mut indices = vec![0u32; if rc == ffi::BVHGPU_OK { total as usize } else { 0 }];
+            let rc2 = if rc == ffi::BVHGPU_OK {
+                ffi::bvhgpu_hits_fetch(hits, offsets.as_mut_ptr(), indices.as_mut_ptr(), core::ptr::null_mut(), ffi::BVHGPU_HOST)
+            } else {
+                rc
+            };
+            ffi::bvhgpu_hits_destroy(hits);
+            check(self.ctx, rc2);
+            BatchHits { offsets, indices }
+        }
     }
 
     /// `FlatBvh::traverse` (src/flat_bvh.rs:396-431) for many rays at once — what the GPU is for
@@ -436,8 +489,10 @@ impl<T: GpuScalar> BoundingHierarchy<T, 3> for GpuBvh<T> {
         query: &Query,
         shapes: &'a [Shape],
     ) -> Vec<&'a Shape> {
-        // one generic query: the crate's own loop over the downloaded flat array (src/flat_bvh.rs:396-431);
-        // ray BATCHES go through `traverse_batch`
+        // one generic query: the crate's own loop over the downloaded flat array (src/flat_bvh.rs:396-431).  Stable Rust cannot
+        // specialise this method on the query type, so it stays on the CPU for every `IntersectsAabb`; BATCHES of the crate's own
+        // query types run on the GPU through `traverse_batch` (rays), `traverse_aabbs`, `traverse_points`, `traverse_balls`
+        // and `self_overlaps`
         assert!(!self.flat_stale, "rebuild_async: call sync_flat() before a generic query");
         self.flat.traverse(query, shapes)
     }

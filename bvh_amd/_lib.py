@@ -144,6 +144,9 @@ SYMBOLS = [
     ("bvhgpu_hits_destroy", None, [_vp]),
     ("bvhgpu_query_f32", _i, [_vp, _i, _vp, _sz, _i, _u, _pp]),
     ("bvhgpu_query_f64", _i, [_vp, _i, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_traverse_any_f32", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_traverse_any_f64", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_hits_fetch_any", _i, [_vp, _vp, _vp, _i]),
     ("bvhgpu_enable_timing", _i, [_vp, _i]),
     ("bvhgpu_last_timings", _i, [_vp, C.POINTER(Timings)]),
     ("bvhgpu_obj_parse", _i, [C.c_char_p, _sz, C.POINTER(C.POINTER(C.c_float)), C.POINTER(_sz), _vp]),

@@ -451,6 +451,13 @@ class _Hits:
         check(_lib.load().bvhgpu_hits_fetch_closest(self.h, ptr(isect), ptr(shape), HOST), self.ctx._h)
         return isect, shape
 
+    def fetch_any(self, n_rays: int, dtype=np.float32):
+        """any-hit batches: (Intersection{distance,u,v}[n,3], shape[n]) of the completed batch, copied to the host"""
+        isect = np.zeros((n_rays, 3), dtype=dtype)
+        shape = np.zeros(n_rays, dtype=np.uint32)
+        check(_lib.load().bvhgpu_hits_fetch_any(self.h, ptr(isect), ptr(shape), HOST), self.ctx._h)
+        return isect, shape
+
     def fetch_triangles(self, dtype=np.float32):
         """TRIANGLES batches: Intersection{distance,u,v} of every candidate, CSR order"""
         total = C.c_uint64()
@@ -609,6 +616,45 @@ class _TreeBase:
         shape = np.zeros(rays.n, dtype=np.uint32)
         check(lib.bvhgpu_hits_fetch_closest(self._hits.h, ptr(isect), ptr(shape), HOST), self.ctx._h)
         return isect, shape, sd
+
+    def any_hits(self, rays: RayBatch, tmax=None, fetch: bool = True, coherent: bool = False):
+        """bvhgpu_traverse_any_*: occlusion of the segments o .. o + tmax[i]·d.  Per ray the FIRST shape of FlatBvh::traverse's list
+        (flat_bvh.rs:396-431, in its order) whose Ray::intersects_triangle distance is < tmax[i], with that Intersection; shape NONE and
+        (+inf, 0, 0) when there is none.  tmax: None (+inf for every ray), or n values in the tree's dtype in the rays' memory — a numpy
+        array for HOST rays, a torch GPU tensor for rays in HBM.  Needs set_triangles.  returns (isect[n,3], shape[n]); fetch=False
+        returns (None, None) and leaves the result on the tree's result object."""
+        if rays.sfx != self.sfx:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
+        ft = np.float32 if self.sfx == "f32" else np.float64
+        keep, tp = None, None
+        if tmax is not None:
+            if _is_device_tensor(tmax):
+                if rays.mem != DEVICE:
+                    raise BvhGpuError(_lib.INVALID_ARG, "tmax is a GPU tensor but the rays are in host memory")
+                if str(tmax.dtype) != ("torch.float32" if self.sfx == "f32" else "torch.float64"):
+                    raise BvhGpuError(_lib.DTYPE_MISMATCH, "tmax dtype differs from tree dtype")
+                keep = tmax.contiguous()
+                n, tp = keep.numel(), ptr(keep.data_ptr())
+            else:
+                if rays.mem != HOST:
+                    raise BvhGpuError(_lib.INVALID_ARG, "tmax is in host memory but the rays are in HBM")
+                if isinstance(tmax, np.ndarray) and tmax.dtype != ft:
+                    raise BvhGpuError(_lib.DTYPE_MISMATCH, "tmax dtype differs from tree dtype")
+                keep = np.ascontiguousarray(tmax, dtype=ft).reshape(-1)
+                n, tp = keep.size, ptr(keep)
+            if n != rays.n:
+                raise BvhGpuError(_lib.INVALID_ARG, f"tmax has {n} values for {rays.n} rays")
+        lib = _lib.load()
+        fn = getattr(lib, f"bvhgpu_traverse_any_{self.sfx}")
+        check(fn(self._t, rays._ptr(), tp, rays.n, rays.mem, TRAVERSE_COHERENT if coherent else 0, C.byref(self._hits.h)), self.ctx._h)
+        if not fetch:
+            return None, None
+        return self._hits.fetch_any(rays.n, ft)
+
+    def occluded(self, rays: RayBatch, tmax=None) -> np.ndarray:
+        """bool[n]: does segment i hit any triangle (any_hits(...) shape != NONE)"""
+        _, shape = self.any_hits(rays, tmax)
+        return shape != NONE
 
     # ---- point query ---------------------------------------------------------------------
     def nearest_batch(self, points, triangles: bool = False):

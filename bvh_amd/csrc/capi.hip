@@ -239,6 +239,7 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
     }
     if ((flags & BVHGPU_TRAVERSE_TRIANGLES) && (flags & BVHGPU_TRAVERSE_CLOSEST))
         return fail(ctx, BVHGPU_INVALID_ARG, "TRIANGLES and CLOSEST are alternatives");
+    flags &= ~TRAVERSE_ANY_HIT;   // (internal: only bvhgpu_traverse_any_* sets it)
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = *hits;
@@ -256,6 +257,42 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
         } else {
             traverse_batch<T>(tree, dev, n_rays, flags, h);
         }
+        return (int)BVHGPU_OK;
+    });
+}
+
+// bvhgpu_traverse_any_*: per ray the first candidate of FlatBvh::traverse's list whose triangle distance is < tmax[i] (traverse.hip MODE_ANY).
+// tmax == NULL: +inf for every ray.  HOST tmax is staged into the result object, so that a replay (wide-walk stack overflow) reads it again.
+template <typename T>
+int do_traverse_any(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, const T* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits) {
+    if (!tree) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = tree->ctx;
+    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
+    if (flags & ~BVHGPU_TRAVERSE_COHERENT) return fail(ctx, BVHGPU_INVALID_ARG, "any-hit flags: 0 or BVHGPU_TRAVERSE_COHERENT");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    { const int rc = settle(tree); if (rc != BVHGPU_OK) return rc; }
+    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
+    if (tree->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from ray dtype");
+    if (!tree->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    if (n_rays && !rays) return fail(ctx, BVHGPU_INVALID_ARG, "rays is NULL");
+    if (n_rays >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 rays in one batch");
+    if (!tree->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "any-hit queries need bvhgpu_tree_set_triangles first");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        bvhgpu_hits* h = *hits;
+        if (!h) h = new bvhgpu_hits();
+        *hits = h;
+        const auto* dev = static_cast<const typename Traits<T>::Ray*>(
+            to_device(ctx, rays, n_rays * sizeof(typename Traits<T>::Ray), mem, ctx->upload));
+        h->pend_kind = 0; h->pend_queries = nullptr; h->pend_qwide = false;   // (the object may have held a query batch)
+        const T* tmax_dev = tmax;
+        if (tmax && n_rays && mem == BVHGPU_HOST) {
+            h->tmaxbuf.reserve(n_rays * sizeof(T));
+            BVH_HIP(hipMemcpyAsync(h->tmaxbuf.p, tmax, n_rays * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+            tmax_dev = h->tmaxbuf.as<T>();
+        }
+        h->pend_tmax = tmax_dev;
+        traverse_batch<T>(tree, dev, n_rays, flags | TRAVERSE_ANY_HIT, h);
         return (int)BVHGPU_OK;
     });
 }
@@ -1194,6 +1231,13 @@ int bvhgpu_traverse_f64(bvhgpu_tree* tree, const bvhgpu_ray_f64* rays, size_t n_
     return do_traverse<double>(tree, rays, n_rays, mem, flags, hits);
 }
 
+int bvhgpu_traverse_any_f32(bvhgpu_tree* tree, const bvhgpu_ray_f32* rays, const float* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_traverse_any<float>(tree, rays, tmax, n_rays, mem, flags, hits);
+}
+int bvhgpu_traverse_any_f64(bvhgpu_tree* tree, const bvhgpu_ray_f64* rays, const double* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_traverse_any<double>(tree, rays, tmax, n_rays, mem, flags, hits);
+}
+
 int bvhgpu_query_f32(bvhgpu_tree* tree, int kind, const float* queries, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
     return do_query<float>(tree, kind, queries, n, mem, flags, hits);
 }
@@ -1283,6 +1327,19 @@ int bvhgpu_hits_fetch_closest(bvhgpu_hits* h, void* isect, uint32_t* shape, int 
     });
 }
 
+int bvhgpu_hits_fetch_any(bvhgpu_hits* h, void* isect, uint32_t* shape, int mem) {
+    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = h->ctx;
+    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (!(h->flags & TRAVERSE_ANY_HIT)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_traverse_any_* batch");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        if (isect && h->n_rays) copy_out(ctx, isect, h->closest.p, h->n_rays * 3 * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
+        if (shape && h->n_rays) copy_out(ctx, shape, h->closest_prim.p, h->n_rays * 4, mem);
+        return (int)BVHGPU_OK;
+    });
+}
+
 int bvhgpu_hits_info(const bvhgpu_hits* h, size_t* n_rays, uint64_t* total, bvhgpu_traverse_stats* stats) {
     if (!h) return BVHGPU_INVALID_ARG;
     if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
@@ -1312,6 +1369,7 @@ int bvhgpu_hits_fetch(bvhgpu_hits* h, uint32_t* offsets, uint32_t* indices, void
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (tslice && !(h->flags & BVHGPU_TRAVERSE_T_SLICE)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_T_SLICE");
     if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR: use bvhgpu_hits_fetch_closest");
+    if (h->flags & TRAVERSE_ANY_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR: use bvhgpu_hits_fetch_any");
     return guarded(ctx, [&] {
         use_device(ctx);
         if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
@@ -1325,6 +1383,7 @@ int bvhgpu_hits_device(const bvhgpu_hits* h, const uint32_t** offsets, const uin
     if (!h) return BVHGPU_INVALID_ARG;
     if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(h->ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR");
+    if (h->flags & TRAVERSE_ANY_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR");
     if (offsets) *offsets = h->offsets.as<uint32_t>();
     if (indices) *indices = h->indices.as<uint32_t>();
     if (tslice) *tslice = (h->flags & BVHGPU_TRAVERSE_T_SLICE) ? h->tslice.p : nullptr;
@@ -1339,7 +1398,7 @@ void bvhgpu_hits_destroy(bvhgpu_hits* h) {
     h->indices.release(); h->tslice.release(); h->blocksums.release(); h->scan_sums.release(); h->ctr.release();
     h->isect.release(); h->closest.release(); h->closest_prim.release(); h->closest_key.release();
     h->heap_dist.release(); h->heap_node.release();
-    h->wg_items.release(); h->raybuf.release(); h->qbuf.release();
+    h->wg_items.release(); h->raybuf.release(); h->qbuf.release(); h->tmaxbuf.release(); h->any_key.release(); h->any_part.release();
     if (h->ev_items) (void)hipEventDestroy(h->ev_items);
     h->wcounts.release(); h->ray_mask.release(); h->item_cnt.release(); h->wstack.release(); h->ray_items.release(); h->witems.release();
     if (h->pin) (void)hipHostFree(h->pin);

@@ -35,6 +35,10 @@ struct DevBuf {
     template <typename U> U* as() const { return reinterpret_cast<U*>(p); }
 };
 
+// result objects of bvhgpu_traverse_any_*: an internal bit of bvhgpu_hits::flags next to the caller's BVHGPU_TRAVERSE_* flags (which
+// bvhgpu_traverse_any_* restricts to COHERENT), so that the walk dispatch, traverse_check and the fetch functions tell the kinds apart
+constexpr unsigned TRAVERSE_ANY_HIT = 1u << 31;
+
 }  // namespace bvhgpu
 
 struct bvhgpu_comm;
@@ -234,6 +238,12 @@ struct bvhgpu_hits {
     const void* pend_queries = nullptr;  // its queries in HBM (the caller's, the tree's own AABBs, or `qbuf`)
     bool pend_qwide = false;             // ... walked by k_query_wide (a lane's stack overflow replays it with the binary walk)
     bvhgpu::DevBuf qbuf;                 // HOST queries staged here, so that a replay reads them again
+    // any-hit batches (bvhgpu_traverse_any_*): per-ray segment ends in HBM (the caller's, or `tmaxbuf`; NULL = +inf), read by every replay
+    const void* pend_tmax = nullptr;
+    bvhgpu::DevBuf tmaxbuf;              // HOST tmax staged here
+    bvhgpu::DevBuf any_key;              // n_rays u32: any-hit batches walked as items (traverse.hip WalkOut::any_key), all-ones between batches
+    bool akey_clean = false;
+    bvhgpu::DevBuf any_part;             // per workgroup of k_any_resolve: its occluded rays (k_any_publish adds them up)
     uint32_t replays = 0;               // times bvhgpu_hits_wait had to enqueue the asynchronous batch again
     int deferred_rc = 0;                // status of a completion that ran on behalf of another call (rebuild / destroy of the tree)
     std::string deferred_err;

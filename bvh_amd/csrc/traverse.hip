@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void k_traverse(const TravNode<T>* __restrict_
     const bool active = r < n_rays;
     LaneRay<T, MODE> ray;
     ray.clear();
-    if (active) ray.load(rays, r);
+    if (active) ray.load(rays, r, w.tmax);
     uint32_t i = active ? 0u : n_trav;
     PoolCursor pc;
     unsigned long long steps = 0, leaf_steps = 0, wsteps = 0;
@@ -61,6 +61,7 @@ __global__ __launch_bounds__(256) void k_traverse(const TravNode<T>* __restrict_
             if (STATS) { steps++; leaf_steps += leaf ? 1 : 0; }
         }
         report<T, MODE>(rec, shape, t0, t1, ray, w, pc, lane, lt);
+        if (MODE == MODE_ANY && ray.best_prim != NONE) i = n_trav;   // occluded: the ray is done
     }
     const unsigned long long cands = active ? ray.cnt : 0;
     if (active) ray.retire(w);
@@ -406,12 +407,12 @@ __global__ __launch_bounds__(LDS_THREADS) void k_traverse_lds(const TravNode<T>*
                 if (!run && base < wg_end && mine < wg_end) {
                     if (split_at) {
                         const bool right = (mine & 1u) != 0u;
-                        ray.load(rays, mine >> 1);
+                        ray.load(rays, mine >> 1, w.tmax);
                         ray.r = mine;                       // counts / pool records are per item
                         i = right ? split_at : 0u; limit = right ? n_trav : split_at;
                         slot = right ? 3u : 2u;             // heap numbers of the root's children
                     } else {
-                        ray.load(rays, mine);
+                        ray.load(rays, mine, w.tmax);
                         i = 0; limit = n_trav; slot = first_slot;
                     }
                     run = true;
@@ -443,6 +444,7 @@ __global__ __launch_bounds__(LDS_THREADS) void k_traverse_lds(const TravNode<T>*
                 if (STATS) { steps++; leaf_steps += leaf ? 1 : 0; }
             }
             report<T, MODE>(rec, shape, t0, t1, ray, w, pc, lane, lt);
+            if (MODE == MODE_ANY && ray.best_prim != NONE) i = limit;   // occluded: retired at the next refill
         }
     }
     walk_epilogue<T, MODE>(w, pc, lane, STATS, steps, leaf_steps, wsteps, cands);
@@ -905,7 +907,20 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES) void k_traverse_wide(
             if (MODE == MODE_INDICES && ITEMS_LOG4 == 0 && w.pool_pair)   // (wave-uniform) a retiring ray's unpaired last hit
                 report_pair(false, !run && item != NONE, 0u, ray, pair_pend, w.pool_pair, w.pool_cap, w.ctr, pc, lane, lt);
             if (!run && item != NONE) {   // the item has left the tree: its part of the ray's list is complete
-                if (MODE == MODE_CLOSEST) {
+                if (MODE == MODE_ANY) {
+                    if constexpr (ITEMS_LOG4 == 0) {
+                        const size_t r = item;
+                        w.closest[3 * r] = ray.best[0]; w.closest[3 * r + 1] = ray.best[1]; w.closest[3 * r + 2] = ray.best[2];
+                        w.closest_prim[r] = ray.best_prim;
+                    } else if (ray.best_prim != NONE) {
+                        // The ray's list is the concatenation of its items' lists in item order, and this lane stopped at its item's first
+                        // candidate inside the segment: the ray's answer is the candidate of the LOWEST item that found one.  Item (< 16) and
+                        // shape (< 2^28: WIDE_MAX_SHAPES) fit one 32-bit key: one atomicMin; k_any_resolve recomputes the Intersection.
+                        const uint32_t j = item & ((1u << WIDE_ITEM_BITS) - 1u);
+                        const uint32_t jj = j == WIDE_ITEM_WHOLE ? 0u : j;
+                        atomicMin(&w.any_key[item >> WIDE_ITEM_BITS], (jj << 28) | ray.best_prim);
+                    }
+                } else if (MODE == MODE_CLOSEST) {
                     if constexpr (ITEMS_LOG4 == 0) {
                         const size_t r = item;
                         if constexpr (!GUIDE_CLOSEST) { w.closest[3 * r] = ray.best[0]; w.closest[3 * r + 1] = ray.best[1]; w.closest[3 * r + 2] = ray.best[2]; }
@@ -957,7 +972,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES) void k_traverse_wide(
                         item = ray_of(mine);
                         if (item < n_rays) {
                             if constexpr (GUIDE != 0) { bool bad; guide_ray_load(ga.rays64, item, guide_S, ray.o, ray.inv, bad); guide_bad = guide_bad || bad; ray.loaded(item); gbest = __builtin_inf(); }
-                            else ray.load(rays, item);
+                            else ray.load(rays, item, w.tmax);
                             cur = WIDE_INNER | WIDE_RESIDENT | 0u;   // the root is heap slot 0 (K >= 1)
                         } else {
                             item = NONE;                         // padding of the batch's last 64-ray block
@@ -966,7 +981,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES) void k_traverse_wide(
                         item = list[mine < n_front ? mine : per_wg * ITEMS - 1u - (mine - n_front)];
                         const uint32_t j = item & ((1u << WIDE_ITEM_BITS) - 1u);
                         if constexpr (GUIDE != 0) { bool bad; guide_ray_load(ga.rays64, item >> WIDE_ITEM_BITS, guide_S, ray.o, ray.inv, bad); ray.loaded(item >> WIDE_ITEM_BITS); gbest = __builtin_inf(); }   // (the filter has looked at its range)
-                        else ray.load(rays, item >> WIDE_ITEM_BITS);
+                        else ray.load(rays, item >> WIDE_ITEM_BITS, w.tmax);
                         cur = j == WIDE_ITEM_WHOLE ? (WIDE_INNER | WIDE_RESIDENT | 0u) : s_item_ref[j];
                         if (j == WIDE_ITEM_WHOLE) item = item & ~((1u << WIDE_ITEM_BITS) - 1u);   // filed under j = 0
                     }
@@ -1048,6 +1063,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES) void k_traverse_wide(
                 }
             } else if (MODE == MODE_INDICES && ITEMS_LOG4 == 0 && w.pool_pair) report_pair(rec, false, shape, ray, pair_pend, w.pool_pair, w.pool_cap, w.ctr, pc, lane, lt);   // (wave-uniform)
             else report<T, MODE>(rec, shape, (T)0, (T)0, ray, w, pc, lane, lt);
+            if (MODE == MODE_ANY && ray.best_prim != NONE) { cur = CUR_NONE; sp = 0; }   // occluded: the item retires at the next refill
         }
         if (ovf) { cur = CUR_NONE; sp = 0; }
     }
@@ -1058,7 +1074,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES) void k_traverse_wide(
         pc.left = 0;                                                // (nothing left for the epilogue's HitRec form to invalidate)
     }
     walk_epilogue<T, MODE>(w, pc, lane, false, 0, 0, 0, 0);
-    if (MODE != MODE_CLOSEST && w.scan_sums) {   // every wave of the workgroup gets here: all items of its rays have retired
+    if (MODE < MODE_CLOSEST && w.scan_sums) {   // every wave of the workgroup gets here: all items of its rays have retired
         __syncthreads();
         // one atomic per 64-ray block that has hits, on the sum of its scan block (workgroups finish at different times and a
         // scan block's 16 sums come from 16 workgroups: nothing like the per-item atomics that were tried first)
@@ -1508,6 +1524,67 @@ __global__ __launch_bounds__(256) void k_closest_from_prim(const uint32_t* __res
     closest[3 * (size_t)r] = out[0]; closest[3 * (size_t)r + 1] = out[1]; closest[3 * (size_t)r + 2] = out[2];
 }
 
+// Any-hit batch, after its walk: KEYED (rays walked as items, WalkOut::any_key) — the winner's shape comes out of the key and its Intersection
+// is computed again, the same function on the same operands as in the walk (the same bits); the key goes back to all-ones for the next batch.
+// Every form: the occluded rays of each workgroup are counted into part[workgroup], and k_any_publish adds them up into the counter that
+// becomes bvhgpu_hits_info's total.  (No atomics on one address: it takes only ~88 per µs on this chip — one per wave of a 1 M-ray batch made
+// this kernel take 0.19 ms, one per workgroup of a 512-workgroup grid still 15 µs against k_closest_resolve's 9.)
+template <typename T, bool KEYED>
+__global__ __launch_bounds__(256) void k_any_resolve(uint32_t* __restrict__ key, const typename Traits<T>::Ray* __restrict__ rays,
+                                                     const T* __restrict__ tris, uint32_t n_rays, T* __restrict__ isect, uint32_t* __restrict__ prim,
+                                                     uint32_t* __restrict__ part) {
+    __shared__ uint32_t s_cnt[256 / WAVE];
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t p = NONE;
+    if (r < n_rays) {
+        if (KEYED) {
+            const uint32_t k = key[r];
+            T out[3] = {Traits<T>::inf(), 0, 0};
+            if (k != NONE) {
+                p = k & 0x0FFFFFFFu;
+                const typename Traits<T>::Ray* rp = rays + r;
+                const T o[3] = {rp->o[0], rp->o[1], rp->o[2]}, d[3] = {rp->d[0], rp->d[1], rp->d[2]};
+                ray_triangle<T>(o, d, tris + 9 * (size_t)p, out);
+                key[r] = NONE;
+            }
+            isect[3 * (size_t)r] = out[0]; isect[3 * (size_t)r + 1] = out[1]; isect[3 * (size_t)r + 2] = out[2];
+            prim[r] = p;
+        } else {
+            p = prim[r];
+        }
+    }
+    const uint32_t m = (uint32_t)__popcll(__ballot(p != NONE));
+    if (lane_id() == 0) s_cnt[threadIdx.x / WAVE] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (uint32_t w = 0; w < blockDim.x / WAVE; w++) sum += s_cnt[w];
+        part[blockIdx.x] = sum;
+    }
+}
+// k_publish_counters for an any-hit batch: ctr[3] = the sum of k_any_resolve's per-workgroup counts, then the 8 counters go to the pinned
+// host page and are zeroed for the next call
+__global__ __launch_bounds__(256) void k_any_publish(unsigned long long* __restrict__ ctr, unsigned long long* __restrict__ host_page,
+                                                     const uint32_t* __restrict__ part, uint32_t n_part) {
+    __shared__ unsigned long long s_sum[256 / WAVE];
+    unsigned long long sum = 0;
+    for (uint32_t i = threadIdx.x; i < n_part; i += blockDim.x) sum += part[i];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d);
+    if (lane_id() == 0) s_sum[threadIdx.x / WAVE] = sum;
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        unsigned long long v = ctr[threadIdx.x];
+        if (threadIdx.x == 3) {
+            v = 0;
+            for (uint32_t w = 0; w < blockDim.x / WAVE; w++) v += s_sum[w];
+        }
+        host_page[threadIdx.x] = v;
+        ctr[threadIdx.x] = 0;
+    }
+    __threadfence_system();
+}
+
 // ---- wide walk launch ------------------------------------------------------------------------
 // Workgroup geometry: `wg_per_cu` workgroups of `threads` share a CU's 160 KB of LDS; each keeps the per-lane stack
 // (stack_lds entries x threads x 4 B) and as many top-of-tree wide nodes as fit in the rest.
@@ -1612,7 +1689,8 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
     const bool stats = (flags & BVHGPU_TRAVERSE_STATS) != 0;
     const bool coherent = (flags & BVHGPU_TRAVERSE_COHERENT) != 0;
     const int ordered = (flags & BVHGPU_TRAVERSE_NEAREST_FIRST) ? 1 : ((flags & BVHGPU_TRAVERSE_FARTHEST_FIRST) ? 2 : 0);
-    const int mode = (flags & BVHGPU_TRAVERSE_CLOSEST) ? MODE_CLOSEST
+    const int mode = (flags & TRAVERSE_ANY_HIT) ? MODE_ANY
+                   : (flags & BVHGPU_TRAVERSE_CLOSEST) ? MODE_CLOSEST
                    : (flags & BVHGPU_TRAVERSE_TRIANGLES) ? MODE_TRIANGLES
                    : (flags & BVHGPU_TRAVERSE_T_SLICE) ? MODE_T_SLICE : MODE_INDICES;
     const int nv = mode == MODE_T_SLICE ? 2 : (mode == MODE_TRIANGLES ? 3 : 0);
@@ -1630,16 +1708,17 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
     // several items per ray while a resident lane gets fewer than ~4 rays: the tail of the launch dominates there
     const bool few_rays = n_rays < (size_t)ctx->n_cu * 2048 * 4;
     uint32_t split_at = 0;
-    if (use_lds && mode != MODE_CLOSEST && ctx->tune[BVHGPU_TUNE_TRAVERSE_SPLIT] != 0 && t->n >= 2 && !t->unfolded && few_rays)
+    if (use_lds && mode < MODE_CLOSEST && ctx->tune[BVHGPU_TUNE_TRAVERSE_SPLIT] != 0 && t->n >= 2 && !t->unfolded && few_rays)
         split_at = 1;   // the kernel reads the boundary itself: exit index of entry 0 (the root's left child)
     int items_log4 = 0;
-    if (use_wide && mode != MODE_CLOSEST && n_rays < WIDE_ITEM_MAX_RAYS) {
+    if (use_wide && mode < MODE_CLOSEST && n_rays < WIDE_ITEM_MAX_RAYS) {
         const int want = ctx->tune[BVHGPU_TUNE_WIDE_ITEMS_LOG4];
         items_log4 = want >= 0 ? std::min(want, 2) : (few_rays ? 2 : 0);
     }
     // closest hit: the same cut into 16 items below ~2 M rays — the per-ray minimum over the items goes through WalkOut::closest_key (f32: one
-    // 64-bit atomicMin per item with a candidate) or through the (ray, item) slots (f64: k_closest_resolve_slots)
-    if (use_wide && mode == MODE_CLOSEST && n_rays < WIDE_ITEM_MAX_RAYS) {
+    // 64-bit atomicMin per item with a candidate) or through the (ray, item) slots (f64: k_closest_resolve_slots).  Any hit: the same choice, the
+    // lowest item with a candidate through WalkOut::any_key (one 32-bit atomicMin per item with a candidate, f32 and f64)
+    if (use_wide && mode >= MODE_CLOSEST && n_rays < WIDE_ITEM_MAX_RAYS) {
         const int want = ctx->tune[BVHGPU_TUNE_WIDE_ITEMS_LOG4];
         items_log4 = (want >= 0 ? want >= 2 : few_rays) ? 2 : 0;
     }
@@ -1678,7 +1757,7 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
     WalkOut<T> w;
     w.counts = nullptr; w.pool = nullptr; w.pool_v = nullptr; w.pool_cap = 0; w.ctr = ctr;
     w.tris = t->tris.as<T>(); w.closest = nullptr; w.closest_prim = nullptr; w.closest_key = nullptr; w.item_cnt = nullptr; w.ray_items = nullptr; w.scan_sums = nullptr;
-    w.raybuf = nullptr; w.stage_shift = 0; w.pool_pair = nullptr;
+    w.raybuf = nullptr; w.stage_shift = 0; w.pool_pair = nullptr; w.tmax = nullptr; w.any_key = nullptr;
 
     uint32_t* ovf_flag = reinterpret_cast<uint32_t*>(ctr + 7);   // bit 0 ordered-iterator stack, bit 1 heap workspace, bit 2 wide-walk stack
     const bool best_first = ordered && (flags & BVHGPU_TRAVERSE_BEST_FIRST) != 0;
@@ -1714,7 +1793,7 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
                 WalkOut<float> wg;   // the same outputs: an index batch touches none of the T-typed ones
                 wg.counts = w.counts; wg.pool = w.pool; wg.pool_v = nullptr; wg.pool_cap = w.pool_cap; wg.ctr = w.ctr; wg.tris = nullptr;
                 wg.closest = nullptr; wg.closest_prim = nullptr; wg.closest_key = nullptr; wg.item_cnt = w.item_cnt; wg.ray_items = w.ray_items; wg.scan_sums = w.scan_sums;
-                wg.pool_pair = w.pool_pair; wg.raybuf = w.raybuf; wg.stage_shift = w.stage_shift;
+                wg.pool_pair = w.pool_pair; wg.raybuf = w.raybuf; wg.stage_shift = w.stage_shift; wg.tmax = nullptr; wg.any_key = nullptr;
                 const GuideArgs ga{reinterpret_cast<const bvhgpu_ray_f64*>(rays_dev), t->aabbs.as<double>(), t->guide_info.as<float>(), nullptr};
                 if (items_log4 == 2) launch_wide<float, MODE_INDICES, 2, 1>(t, r32, n_rays, wg, h, ovf_flag, false, ga);
                 else if (items_log4 == 1) launch_wide<float, MODE_INDICES, 1, 1>(t, r32, n_rays, wg, h, ovf_flag, false, ga);
@@ -1727,17 +1806,22 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
                 WalkOut<float> wg;
                 wg.counts = nullptr; wg.pool = nullptr; wg.pool_v = nullptr; wg.pool_cap = 0; wg.ctr = w.ctr; wg.tris = nullptr;
                 wg.closest = nullptr; wg.closest_prim = w.closest_prim; wg.closest_key = nullptr; wg.item_cnt = w.item_cnt; wg.ray_items = w.ray_items; wg.scan_sums = nullptr;
-                wg.pool_pair = nullptr; wg.raybuf = nullptr; wg.stage_shift = 0;
+                wg.pool_pair = nullptr; wg.raybuf = nullptr; wg.stage_shift = 0; wg.tmax = nullptr; wg.any_key = nullptr;
                 const GuideArgs ga{reinterpret_cast<const bvhgpu_ray_f64*>(rays_dev), t->aabbs.as<double>(), t->guide_info.as<float>(), t->tris.as<double>()};
                 if (items_log4 == 2) launch_wide<float, MODE_CLOSEST, 2, 1>(t, nullptr, n_rays, wg, h, ovf_flag, false, ga);
                 else launch_wide<float, MODE_CLOSEST, 0, 1>(t, nullptr, n_rays, wg, h, ovf_flag, false, ga);
                 return;
             }
         }
-        if (M != MODE_CLOSEST && items_log4 == 2) launch_wide<T, M, (M == MODE_CLOSEST ? 0 : 2)>(t, rays_dev, n_rays, w, h, ovf_flag, early_items);
-        else if (M != MODE_CLOSEST && items_log4 == 1) launch_wide<T, M, (M == MODE_CLOSEST ? 0 : 1)>(t, rays_dev, n_rays, w, h, ovf_flag, false);
-        else if (M == MODE_CLOSEST && items_log4 == 2) launch_wide<T, M, (M == MODE_CLOSEST ? 2 : 0)>(t, rays_dev, n_rays, w, h, ovf_flag, false);
-        else launch_wide<T, M, 0>(t, rays_dev, n_rays, w, h, ovf_flag, false);
+        if constexpr (M == MODE_ANY) {   // whole rays or 16 items, like CLOSEST
+            if (items_log4 == 2) launch_wide<T, MODE_ANY, 2>(t, rays_dev, n_rays, w, h, ovf_flag, false);
+            else launch_wide<T, MODE_ANY, 0>(t, rays_dev, n_rays, w, h, ovf_flag, false);
+        } else {
+            if (M != MODE_CLOSEST && items_log4 == 2) launch_wide<T, M, (M == MODE_CLOSEST ? 0 : 2)>(t, rays_dev, n_rays, w, h, ovf_flag, early_items);
+            else if (M != MODE_CLOSEST && items_log4 == 1) launch_wide<T, M, (M == MODE_CLOSEST ? 0 : 1)>(t, rays_dev, n_rays, w, h, ovf_flag, false);
+            else if (M == MODE_CLOSEST && items_log4 == 2) launch_wide<T, M, (M == MODE_CLOSEST ? 2 : 0)>(t, rays_dev, n_rays, w, h, ovf_flag, false);
+            else launch_wide<T, M, 0>(t, rays_dev, n_rays, w, h, ovf_flag, false);
+        }
     };
 #define DISPATCH_WALK_INNER()                                                                        \
     do {                                                                                             \
@@ -1753,6 +1837,7 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
             switch (mode) {                                                                          \
                 case MODE_INDICES: dispatch_wide(std::integral_constant<int, MODE_INDICES>{}); break;        \
                 case MODE_TRIANGLES: dispatch_wide(std::integral_constant<int, MODE_TRIANGLES>{}); break;    \
+                case MODE_ANY: dispatch_wide(std::integral_constant<int, MODE_ANY>{}); break;                \
                 default: dispatch_wide(std::integral_constant<int, MODE_CLOSEST>{}); break;          \
             }                                                                                        \
             break;                                                                                   \
@@ -1764,6 +1849,7 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
                                else launch_walk<T, MODE_T_SLICE, false>(t, rays_dev, n_rays, w, use_lds, split_at); break; \
             case MODE_TRIANGLES: if (stats) launch_walk<T, MODE_TRIANGLES, true>(t, rays_dev, n_rays, w, use_lds, split_at); \
                                  else launch_walk<T, MODE_TRIANGLES, false>(t, rays_dev, n_rays, w, use_lds, split_at); break; \
+            case MODE_ANY: launch_walk<T, MODE_ANY, false>(t, rays_dev, n_rays, w, use_lds, split_at); break;                   \
             default: if (stats) launch_walk<T, MODE_CLOSEST, true>(t, rays_dev, n_rays, w, use_lds, split_at);           \
                      else launch_walk<T, MODE_CLOSEST, false>(t, rays_dev, n_rays, w, use_lds, split_at); break;         \
         }                                                                                            \
@@ -1772,6 +1858,34 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
 
     if (!h->ctr_clean) BVH_HIP(hipMemsetAsync(ctr, 0, 8 * sizeof(unsigned long long), st));   // (only this batch's set has to be clean)
     h->ctr_clean = false;
+    if (mode == MODE_ANY) {   // no CSR: one Intersection + shape per ray (closest / closest_prim), the occluded rays counted in ctr[3]
+        h->closest.reserve(std::max<size_t>(n_rays, 1) * 3 * sizeof(T));
+        h->closest_prim.reserve(std::max<size_t>(n_rays, 1) * 4);
+        if (n_rays == 0) { h->pend_tree = nullptr; return; }
+        w.closest = h->closest.as<T>(); w.closest_prim = h->closest_prim.as<uint32_t>();
+        w.tmax = static_cast<const T*>(h->pend_tmax);
+        const bool by_items = use_wide && items_log4 == 2;
+        if (by_items) {   // the per-ray keys: all-ones between batches (k_any_resolve puts them back)
+            if (h->any_key.reserve(n_rays * 4)) h->akey_clean = false;
+            if (!h->akey_clean) BVH_HIP(hipMemsetAsync(h->any_key.p, 0xFF, h->any_key.cap, st));
+            h->akey_clean = true;
+            w.any_key = h->any_key.as<uint32_t>();
+        }
+        if (ctx->timing) { BVH_HIP(hipEventRecord(ctx->ev[4], st)); }
+        DISPATCH_WALK();
+        if (ctx->timing) BVH_HIP(hipEventRecord(ctx->ev[5], st));
+        const uint32_t nb = (uint32_t)((n_rays + 255) / 256);
+        h->any_part.reserve((size_t)nb * 4);
+        if (by_items) hipLaunchKernelGGL((k_any_resolve<T, true>), dim3(nb), dim3(256), 0, st, w.any_key, rays_dev, t->tris.as<T>(), (uint32_t)n_rays, w.closest, w.closest_prim,
+                                         h->any_part.as<uint32_t>());
+        else hipLaunchKernelGGL((k_any_resolve<T, false>), dim3(nb), dim3(256), 0, st, nullptr, rays_dev, t->tris.as<T>(), (uint32_t)n_rays, w.closest, w.closest_prim,
+                                h->any_part.as<uint32_t>());
+        if (ctx->timing) BVH_HIP(hipEventRecord(ctx->ev[6], st));
+        hipLaunchKernelGGL(k_any_publish, dim3(1), dim3(256), 0, st, ctr, pin, (const uint32_t*)h->any_part.as<uint32_t>(), nb);   // readback + reset for the next call
+        h->ctr_clean = true;
+        join_flat(t);
+        return;
+    }
     if (mode == MODE_CLOSEST) {   // no CSR: one Intersection + shape per ray
         h->closest.reserve(std::max<size_t>(n_rays, 1) * 3 * sizeof(T));
         h->closest_prim.reserve(std::max<size_t>(n_rays, 1) * 4);
@@ -1968,7 +2082,13 @@ bool traverse_check(bvhgpu_hits* h) {
         h->force_binary = true; return false;
     }
     if (h->pend_wide && (pin[7] & 4ull)) {   // a lane's stack outgrew LDS + workspace: the binary walks need no stack
-        h->force_binary = true; h->wcounts_clean = false; h->bs_clean = false; h->ckey_clean = false; h->ray_items.release(); return false;
+        h->force_binary = true; h->wcounts_clean = false; h->bs_clean = false; h->ckey_clean = false; h->akey_clean = false; h->ray_items.release(); return false;
+    }
+    if (flags & TRAVERSE_ANY_HIT) {   // the occluded rays, counted by k_any_resolve / k_any_publish
+        h->total = pin[3];
+        if (ctx->timing) ctx->ev_set |= 4u;
+        h->pend_tree = nullptr;
+        return true;
     }
     if (flags & BVHGPU_TRAVERSE_CLOSEST) {
         if (stats) {

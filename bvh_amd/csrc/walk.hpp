@@ -15,7 +15,8 @@ enum : int {
     MODE_INDICES = 0,   // Vec<&Shape> only
     MODE_T_SLICE = 1,   // + Ray::intersection_slice_for_aabb per hit (2 scalars)
     MODE_TRIANGLES = 2, // + Ray::intersects_triangle per hit: Intersection{distance,u,v} (3 scalars)
-    MODE_CLOSEST = 3    // no CSR: per ray the candidate triangle with the smallest distance
+    MODE_CLOSEST = 3,   // no CSR: per ray the candidate triangle with the smallest distance
+    MODE_ANY = 4        // no CSR: per ray the FIRST candidate (reference order) whose triangle distance is < the ray's tmax; the walk stops there
 };
 template <int MODE> struct ModeVals { static constexpr int N = MODE == MODE_T_SLICE ? 2 : (MODE == MODE_TRIANGLES ? 3 : 0); };
 
@@ -63,6 +64,9 @@ template <typename T> struct WalkOut {
                                  // HitRec: 8 bytes per hit, one offset gather per two hits in the scatter.  NULL: HitRec
     uint32_t* raybuf;            // wide walk, whole rays, indices only: the first 2^stage_shift shapes of ray r go straight to raybuf[r << stage_shift | k]
     uint32_t stage_shift;        // (4 bytes per hit, no record, no atomic); only later hits of a ray become pool records.  NULL: everything through the pool
+    const T* tmax;               // any-hit mode: per ray the end of its segment (NULL: +inf for every ray)
+    uint32_t* any_key;           // any-hit mode with rays cut into items: per ray min over its items that found a candidate of {item << 28 | shape}
+                                 // (kept all-ones between batches; k_any_resolve turns the winner into closest / closest_prim).  NULL: one lane owns the ray
 };
 
 // ---- Ray::intersects_triangle (ray_impl.rs:154-213), Möller–Trumbore with back-face culling.  Same
@@ -107,16 +111,18 @@ __device__ __forceinline__ void ray_triangle(const T o[3], const T d[3], const T
 template <typename T, int MODE> struct LaneRay {
     T o[3], inv[3];
     T d[MODE >= MODE_TRIANGLES ? 3 : 1];   // direction: only the triangle stage needs it
-    T best[MODE == MODE_CLOSEST ? 3 : 1];  // closest Intersection so far
+    T best[MODE >= MODE_CLOSEST ? 3 : 1];  // closest Intersection so far / the any-hit candidate
+    T tmax;                                // any-hit mode: end of the segment
     uint32_t best_prim;
     uint32_t r, cnt;
     bool fin;                              // all components finite → NaN-free slab test is exact
     __device__ __forceinline__ void clear() {
 #pragma unroll
         for (int k = 0; k < 3; k++) { o[k] = 0; inv[k] = 0; }
-        d[0] = 0; best[0] = 0; best_prim = NONE; r = NONE; cnt = 0; fin = true;
+        d[0] = 0; best[0] = 0; tmax = 0; best_prim = NONE; r = NONE; cnt = 0; fin = true;
     }
-    __device__ __forceinline__ void load(const typename Traits<T>::Ray* __restrict__ rays, uint32_t ray) {
+    // tmaxs: WalkOut::tmax (any-hit mode only)
+    __device__ __forceinline__ void load(const typename Traits<T>::Ray* __restrict__ rays, uint32_t ray, const T* __restrict__ tmaxs = nullptr) {
         const typename Traits<T>::Ray* rp = rays + ray;
 #pragma unroll
         for (int k = 0; k < 3; k++) { o[k] = rp->o[k]; inv[k] = rp->inv[k]; }
@@ -124,7 +130,8 @@ template <typename T, int MODE> struct LaneRay {
 #pragma unroll
             for (int k = 0; k < 3; k++) d[k] = rp->d[k];
         }
-        if (MODE == MODE_CLOSEST) { best[0] = Traits<T>::inf(); best[1] = 0; best[2] = 0; }
+        if (MODE >= MODE_CLOSEST) { best[0] = Traits<T>::inf(); best[1] = 0; best[2] = 0; }
+        if (MODE == MODE_ANY) tmax = tmaxs ? tmaxs[ray] : Traits<T>::inf();
         best_prim = NONE; r = ray; cnt = 0;
         fin = ray_is_finite<T>(o, inv);
     }
@@ -135,7 +142,7 @@ template <typename T, int MODE> struct LaneRay {
     }
     // the ray has left the tree: its Vec / closest hit is complete
     __device__ __forceinline__ void retire(const WalkOut<T>& w) {
-        if (MODE == MODE_CLOSEST) {
+        if (MODE >= MODE_CLOSEST) {
             w.closest[3 * (size_t)r] = best[0]; w.closest[3 * (size_t)r + 1] = best[1]; w.closest[3 * (size_t)r + 2] = best[2];
             w.closest_prim[r] = best_prim;
         } else {
@@ -173,6 +180,10 @@ __device__ __forceinline__ void report(bool rec, uint32_t shape, T t0, T t1, Lan
             if (vals[0] < ray.best[0]) { ray.best[0] = vals[0]; ray.best[1] = vals[1]; ray.best[2] = vals[2]; ray.best_prim = shape; }
             ray.cnt++;
         }
+        return;
+    }
+    if (MODE == MODE_ANY) {   // the first candidate inside the segment ends the ray (the walk sees best_prim != NONE and empties the lane)
+        if (rec && vals[0] < ray.tmax) { ray.best[0] = vals[0]; ray.best[1] = vals[1]; ray.best[2] = vals[2]; ray.best_prim = shape; }
         return;
     }
     constexpr int NV = ModeVals<MODE>::N;
@@ -249,7 +260,7 @@ template <typename T, int MODE>
 __device__ __forceinline__ void walk_epilogue(const WalkOut<T>& w, PoolCursor& pc, int lane, bool stats,
                                               unsigned long long steps, unsigned long long leaf_steps,
                                               unsigned long long wsteps, unsigned long long cands) {
-    if (MODE != MODE_CLOSEST) pool_invalidate_tail(w.pool, w.pool_cap, pc, lane);
+    if (MODE < MODE_CLOSEST) pool_invalidate_tail(w.pool, w.pool_cap, pc, lane);
     if (stats) {
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) {

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define BVHGPU_ABI_VERSION 7 /* 7: bvhgpu_host_alloc/free/register/unregister, bvhgpu_traverse_host_*, bvhgpu_build_traverse_host_*, bvhgpu_traverse_host_indices, bvhgpu_query_f32/_f64 + BVHGPU_QUERY_AABB/_POINT/_BALL, BVHGPU_TUNE_COUNT 23 (slots 17 = HOST_CHUNKS, 18 = WIDE_MIN_RAYS_PER_WG, 19 = HOST_ZERO_COPY, 20 = BUILD_LEVEL_TILE, 21 = FLATTEN_INLINE, 22 = QUERY_VARIANT).  6: BVHGPU_TUNE_COUNT 17 (slots 15 = FLATTEN_LAZY, 16 = BUILD_LEVEL_PERSIST), bvhgpu_hits_walk_kernel.  5: bvhgpu_rccl_info.  4: BVHGPU_TUNE_COUNT 15 (slot 14 = WIDE_F64_GUIDE), bvhgpu_hits_walk_info.  3: BVHGPU_REBROADCAST, broadcast status header, scene blob BVH6 (exact_only), BVHGPU_TUNE_COUNT 14 (slots 11 = WIDE_EARLY_ITEMS, 12 = WIDE_STAGE_SHIFT, 13 = WIDE_REC8), BVHGPU_TRAVERSE_RAYS_READY, bvhgpu_device_alloc/free/copy */
+#define BVHGPU_ABI_VERSION 7 /* 7: bvhgpu_host_alloc/free/register/unregister, bvhgpu_traverse_host_*, bvhgpu_build_traverse_host_*, bvhgpu_traverse_host_indices, bvhgpu_query_f32/_f64 + BVHGPU_QUERY_AABB/_POINT/_BALL, bvhgpu_traverse_any_f32/_f64 + bvhgpu_hits_fetch_any, BVHGPU_TUNE_COUNT 23 (slots 17 = HOST_CHUNKS, 18 = WIDE_MIN_RAYS_PER_WG, 19 = HOST_ZERO_COPY, 20 = BUILD_LEVEL_TILE, 21 = FLATTEN_INLINE, 22 = QUERY_VARIANT).  6: BVHGPU_TUNE_COUNT 17 (slots 15 = FLATTEN_LAZY, 16 = BUILD_LEVEL_PERSIST), bvhgpu_hits_walk_kernel.  5: bvhgpu_rccl_info.  4: BVHGPU_TUNE_COUNT 15 (slot 14 = WIDE_F64_GUIDE), bvhgpu_hits_walk_info.  3: BVHGPU_REBROADCAST, broadcast status header, scene blob BVH6 (exact_only), BVHGPU_TUNE_COUNT 14 (slots 11 = WIDE_EARLY_ITEMS, 12 = WIDE_STAGE_SHIFT, 13 = WIDE_REC8), BVHGPU_TRAVERSE_RAYS_READY, bvhgpu_device_alloc/free/copy */
 #define BVHGPU_NONE 0xFFFFFFFFu /* u32::MAX marker (flat_bvh.rs:51-53, :124, :137) */
 
 typedef enum {
@@ -390,6 +390,24 @@ void bvhgpu_hits_destroy(bvhgpu_hits *hits);
 #define BVHGPU_QUERY_BALL 3
 int bvhgpu_query_f32(bvhgpu_tree *tree, int kind, const float *queries, size_t n, int mem, unsigned flags, bvhgpu_hits **hits);
 int bvhgpu_query_f64(bvhgpu_tree *tree, int kind, const double *queries, size_t n, int mem, unsigned flags, bvhgpu_hits **hits);
+
+/* ---- any-hit (occlusion) queries for ray segments: "does the segment from o to o + tmax·d hit any triangle?" (shadow / visibility rays).
+ * Ray i comes with tmax[i] in the tree's dtype (tmax == NULL: +inf for every ray).  Let L_i be the list FlatBvh::traverse(&ray_i, shapes)
+ * returns (flat_bvh.rs:396-431), in its order, and isect_s = Ray::intersects_triangle (ray_impl.rs:154-213) on shape s's triangle, the same
+ * IEEE sequence as the TRIANGLES output.  The result for ray i is the FIRST s in L_i with isect_s.distance < tmax[i] (strict, in T) and its
+ * Intersection {distance, u, v}; if there is none, BVHGPU_NONE and {+inf, 0, 0}.  So a miss (distance +inf) never occludes, not even with
+ * tmax = +inf, and a NaN tmax or tmax <= epsilon never occludes.  The answer is the first candidate in reference order, not the nearest one:
+ * it is deterministic, and every walk stops at it.  Needs bvhgpu_tree_set_triangles.
+ * `rays` and `tmax` live in `mem` (HOST tmax is staged into the result object).  `flags`: 0 or BVHGPU_TRAVERSE_COHERENT (a hint); every other
+ * bit → BVHGPU_INVALID_ARG.  No triangles → BVHGPU_INVALID_ARG; tree not flattened → BVHGPU_NOT_FLATTENED; another dtype than the tree's →
+ * BVHGPU_DTYPE_MISMATCH; n_rays = 0 is fine.  Synchronises like bvhgpu_traverse_*.  bvhgpu_hits_info's `total` is the number of occluded
+ * rays; _fetch / _fetch_triangles / _fetch_closest / _device return BVHGPU_INVALID_ARG on such a result, and bvhgpu_hits_fetch_any on any
+ * other.  bvhgpu_hits_fetch_any: per ray {distance, u, v} (n x 3 T) and the shape (n u32); either may be NULL. */
+int bvhgpu_traverse_any_f32(bvhgpu_tree *tree, const bvhgpu_ray_f32 *rays, const float *tmax, size_t n_rays, int mem, unsigned flags,
+                            bvhgpu_hits **hits);
+int bvhgpu_traverse_any_f64(bvhgpu_tree *tree, const bvhgpu_ray_f64 *rays, const double *tmax, size_t n_rays, int mem, unsigned flags,
+                            bvhgpu_hits **hits);
+int bvhgpu_hits_fetch_any(bvhgpu_hits *hits, void *isect, uint32_t *shape, int mem);
 
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */

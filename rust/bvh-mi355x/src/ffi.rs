@@ -171,6 +171,10 @@ extern "C" {
     // AABB / point / ball queries: FlatBvh::traverse (flat_bvh.rs:396-431) with Aabb / Point / Ball (aabb/intersection.rs:35-45, ball.rs:102-106)
     pub fn bvhgpu_query_f32(t: *mut bvhgpu_tree, kind: c_int, queries: *const f32, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_query_f64(t: *mut bvhgpu_tree, kind: c_int, queries: *const f64, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    // any-hit (occlusion) queries for ray segments: per ray the first candidate of FlatBvh::traverse's list whose triangle distance is < tmax
+    pub fn bvhgpu_traverse_any_f32(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_traverse_any_f64(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_hits_fetch_any(h: *mut bvhgpu_hits, isect: *mut c_void, shape: *mut u32, mem: c_int) -> c_int;
     // timing, scene ingest, tuning
     pub fn bvhgpu_enable_timing(ctx: *mut bvhgpu_ctx, on: c_int) -> c_int;
     pub fn bvhgpu_last_timings(ctx: *mut bvhgpu_ctx, out: *mut bvhgpu_timings) -> c_int;

@@ -88,6 +88,8 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
     unsafe fn set_triangles(t: *mut ffi::bvhgpu_tree, verts: *const Self, n: usize, mem: c_int) -> c_int;
     unsafe fn tree_from_flat(ctx: *mut ffi::bvhgpu_ctx, flat: *const Self::Flat, n_flat: usize, shape_aabbs: *const Self, n: usize, out: *mut *mut ffi::bvhgpu_tree) -> c_int;
     unsafe fn query(t: *mut ffi::bvhgpu_tree, kind: c_int, queries: *const Self, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn traverse_any(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
 
     fn node_to_crate(raw: &Self::Node) -> BvhNode<Self, 3>;
     fn flat_to_crate(raw: &Self::Flat) -> FlatNode<Self, 3>;
@@ -97,7 +99,8 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
 
 macro_rules! impl_gpu_scalar {
     ($t:ty, $dtype:expr, $node:ident, $flat:ident, $ray:ident, $build_flat:ident, $rebuild_flat:ident, $refit:ident, $traverse:ident,
-     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $flat_ctor:expr) => {
+     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident,
+     $flat_ctor:expr) => {
         impl GpuScalar for $t {
             type Node = ffi::$node;
             type Flat = ffi::$flat;
@@ -132,6 +135,9 @@ macro_rules! impl_gpu_scalar {
             }
             unsafe fn query(t: *mut ffi::bvhgpu_tree, kind: c_int, queries: *const $t, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int {
                 ffi::$query(t, kind, queries, n, mem, flags, hits)
+            }
+            unsafe fn traverse_any(t: *mut ffi::bvhgpu_tree, rays: *const ffi::$ray, tmax: *const $t, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int {
+                ffi::$traverse_any(t, rays, tmax, n, mem, flags, hits)
             }
             fn node_to_crate(r: &ffi::$node) -> BvhNode<$t, 3> {
                 if r.shape != ffi::BVHGPU_NONE {
@@ -171,11 +177,11 @@ macro_rules! impl_gpu_scalar {
 }
 impl_gpu_scalar!(f32, ffi::BVHGPU_F32, bvhgpu_node_f32, bvhgpu_flat_f32, bvhgpu_ray_f32, bvhgpu_build_flat_f32, bvhgpu_rebuild_flat_f32,
                  bvhgpu_refit_f32, bvhgpu_traverse_f32, bvhgpu_tree_set_triangles_f32, bvhgpu_tree_from_flat_f32,
-                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32,
+                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f32 { min, max, entry, exit, shape });
 impl_gpu_scalar!(f64, ffi::BVHGPU_F64, bvhgpu_node_f64, bvhgpu_flat_f64, bvhgpu_ray_f64, bvhgpu_build_flat_f64, bvhgpu_rebuild_flat_f64,
                  bvhgpu_refit_f64, bvhgpu_traverse_f64, bvhgpu_tree_set_triangles_f64, bvhgpu_tree_from_flat_f64,
-                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64,
+                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f64 { min, max, entry, exit, shape, _pad: 0 });
 
 fn aabb_to_6<T: GpuScalar>(b: &Aabb<T, 3>) -> [T; 6] {
@@ -432,6 +438,32 @@ impl<T: GpuScalar> GpuBvh<T> {
             ffi::bvhgpu_hits_destroy(hits);
         }
         isect.iter().zip(shape).map(|(i, s)| ClosestHit { intersection: Intersection::new(i[0], i[1], i[2]), shape: s }).collect()
+    }
+
+    /// Occlusion of ray segments (shadow / visibility rays, `bvhgpu_traverse_any_*`): per ray the FIRST shape of `FlatBvh::traverse`'s
+    /// list, in its order, whose `Ray::intersects_triangle` distance is `< tmax[i]` (`tmax: None` = +inf for every ray), with that
+    /// Intersection; `shape == u32::MAX` and `distance == +inf` when the segment hits nothing.  Every walk stops at the first such
+    /// candidate.  Needs `set_triangles`.
+    pub fn traverse_any(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>) -> Vec<ClosestHit<T>> {
+        if let Some(tm) = tmax {
+            assert_eq!(tm.len(), rays.len(), "one tmax per ray");
+        }
+        let r: Vec<T::RayC> = rays.iter().map(T::ray_to_ffi).collect();
+        let mut hits = core::ptr::null_mut();
+        let mut isect = vec![[T::default(); 3]; rays.len()];
+        let mut shape = vec![0u32; rays.len()];
+        let tp = tmax.map_or(core::ptr::null(), |t| t.as_ptr());
+        unsafe {
+            check(self.ctx, T::traverse_any(self.tree, r.as_ptr(), tp, r.len(), ffi::BVHGPU_HOST, 0, &mut hits));
+            check(self.ctx, ffi::bvhgpu_hits_fetch_any(hits, isect.as_mut_ptr() as *mut c_void, shape.as_mut_ptr(), ffi::BVHGPU_HOST));
+            ffi::bvhgpu_hits_destroy(hits);
+        }
+        isect.iter().zip(shape).map(|(i, s)| ClosestHit { intersection: Intersection::new(i[0], i[1], i[2]), shape: s }).collect()
+    }
+
+    /// `traverse_any` reduced to one flag per ray: does segment i hit any triangle
+    pub fn occluded(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>) -> Vec<bool> {
+        self.traverse_any(rays, tmax).iter().map(|h| h.shape != ffi::BVHGPU_NONE).collect()
     }
 
     /// Build again from new AABBs into the same device buffers (a frame loop: no allocation in the steady state)

@@ -228,6 +228,14 @@ template <typename T> __host__ __device__ inline int bucket_of(T c, T cmin, T ex
     return (int)scaled;
 }
 
+// Aabb join on NaN-free floats in ONE instruction: V_MIN_F32 / V_MAX_F32 (and the F64 forms) order
+// -0 < +0 (ISA: "if S0 == +0 and S1 == -0 return S1"), i.e. exactly tmin / tmax above and the integer-key
+// order.  Written as asm so that no canonicalising v_max x,x is added for values that come out of shuffles.
+__device__ __forceinline__ float join_min(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float join_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ double join_min(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ double join_max(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+
 // ------------------------------------------------------------------------------------------------
 // ray / AABB slab test (src/ray/intersect_default.rs:16-37) — bit-exact boolean
 // ------------------------------------------------------------------------------------------------
@@ -239,26 +247,28 @@ __device__ __forceinline__ bool slab_hit(const T o[3], const T inv[3], const T m
     T l2 = (mn[2] - o[2]) * inv[2], h2 = (mx[2] - o[2]) * inv[2];
     // has_nan(lbr) | has_nan(rtr) -> miss (:22-28).  x != x is the NaN test.
     bool nan = (l0 != l0) | (h0 != h0) | (l1 != l1) | (h1 != h1) | (l2 != l2) | (h2 != h2);
-    // NaN-free from here: min/max are exact and order-free
-    T a0 = l0 < h0 ? l0 : h0, b0 = l0 < h0 ? h0 : l0;
-    T a1 = l1 < h1 ? l1 : h1, b1 = l1 < h1 ? h1 : l1;
-    T a2 = l2 < h2 ? l2 : h2, b2 = l2 < h2 ? h2 : l2;
-    T tmn = a0 > a1 ? a0 : a1;
-    tmn = tmn > a2 ? tmn : a2;
-    T tmx = b0 < b1 ? b0 : b1;
-    tmx = tmx < b2 ? tmx : b2;
+    // NaN-free from here: inf_sup and the folds order -0 < +0 like tmin / tmax (the t-slice's tmax can be a
+    // zero of either sign: a flat box at the origin's plane gives l = -0, h = +0)
+    T a0 = join_min(l0, h0), b0 = join_max(l0, h0);
+    T a1 = join_min(l1, h1), b1 = join_max(l1, h1);
+    T a2 = join_min(l2, h2), b2 = join_max(l2, h2);
+    T tmn = join_max(join_max(a0, a1), a2);
+    T tmx = join_min(join_min(b0, b1), b2);
     T z = tmn > (T)0 ? tmn : (T)0;  // fast_max(tmin, 0) (utils.rs:52-54)
     tmin_out = z;                   // intersection_slice_for_aabb's tmin (ray_impl.rs:135)
     tmax_out = tmx;
     return !nan && (tmx >= z);
 }
 
-// The same boolean for a ray whose origin and inv_direction are all finite and a NaN-free box: then no
-// l/h can be NaN (inf - finite = inf, inf * finite-nonzero = inf; |inv| >= 1 for a normalised direction),
-// the NaN branch (:22-28) is dead, and on NaN-free values IEEE minNum/maxNum return the same VALUE as
-// the reference's compare-selects (only the sign of a zero result can differ, which no comparison sees).
+// The same boolean for a ray whose origin is finite and whose inv_direction is finite and NONZERO
+// (ray_is_finite below), against a finite box: then no l/h can be NaN (b - o may round to ±inf, but
+// inf * finite-nonzero = ±inf; only inf * 0 is NaN), the NaN branch (:22-28) is dead, and on NaN-free
+// values IEEE minNum/maxNum return the same VALUE as the reference's folds (only the sign of a zero result
+// can differ, which no comparison sees).  A zero inv component (a caller-built ray: Ray's fields are
+// public) with an origin far enough from a box overflows b - o and makes the product NaN, which the
+// reference turns into a miss but minNum/maxNum would drop.
 // v_min_f32 / v_max_f32 / v_max3_f32 / v_min3_f32: 22 VALU instead of 43.  Not used when the t-slice is
-// returned (sign of zero), nor for rays with a non-finite component (wave-uniform fallback to slab_hit).
+// returned (sign of zero), nor for rays that fail ray_is_finite (wave-uniform fallback to slab_hit).
 template <typename T>
 __device__ __forceinline__ bool slab_hit_finite(const T o[3], const T inv[3], const T mn[3], const T mx[3]) {
     T l0 = (mn[0] - o[0]) * inv[0], h0 = (mx[0] - o[0]) * inv[0];
@@ -318,23 +328,19 @@ __device__ __forceinline__ bool slab_hit_finite_len<float>(const float o[3], con
     len = tmx - t0;
     return tmx >= t0;
 }
+// the precondition of slab_hit_finite and of the wide walk's skipped ancestor tests: o finite, inv finite and
+// nonzero (one check per ray)
 template <typename T> __device__ __forceinline__ bool ray_is_finite(const T o[3], const T inv[3]) {
     bool f = true;
 #pragma unroll
-    for (int k = 0; k < 3; k++) f = f && (fabs(o[k]) < Traits<T>::inf()) && (fabs(inv[k]) < Traits<T>::inf());
-    return f;   // false for inf and for NaN
+    for (int k = 0; k < 3; k++)
+        f = f && (fabs(o[k]) < Traits<T>::inf()) && (fabs(inv[k]) < Traits<T>::inf()) && (inv[k] != (T)0);
+    return f;   // false for inf, for NaN and for ±0 in inv
 }
 
 // ------------------------------------------------------------------------------------------------
 // wave64 helpers
 // ------------------------------------------------------------------------------------------------
-// Aabb join on NaN-free floats in ONE instruction: V_MIN_F32 / V_MAX_F32 (and the F64 forms) order
-// -0 < +0 (ISA: "if S0 == +0 and S1 == -0 return S1"), i.e. exactly tmin / tmax above and the integer-key
-// order.  Written as asm so that no canonicalising v_max x,x is added for values that come out of shuffles.
-__device__ __forceinline__ float join_min(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float join_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ double join_min(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ double join_max(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // value of lane (byte address `addr4` = 4 * lane) — one ds_bpermute_b32 per dword
 __device__ __forceinline__ float lane_fetch(float v, int addr4) {
     return __int_as_float(__builtin_amdgcn_ds_bpermute(addr4, __float_as_int(v)));

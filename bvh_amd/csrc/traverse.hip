@@ -456,14 +456,16 @@ __global__ __launch_bounds__(LDS_THREADS) void k_traverse_lds(const TravNode<T>*
 // Why it returns the reference's list.  FlatBvh::traverse reports shape s iff the slab test passes for every
 // ancestor box of s and for s's own AABB (flat_bvh.rs:408-427), in pre-order.  Every ancestor box is the exact join
 // (component-wise min / max, no rounding) of the AABBs below it, so it contains s's AABB component by component.
-// For a ray whose origin and inverse direction are finite, against finite boxes, no product (b - o) * inv is NaN and
-// each is monotone in b (IEEE subtraction and multiplication by a constant are monotone under round-to-nearest):
+// For a ray whose origin is finite and whose inverse direction is finite and nonzero (common.hpp ray_is_finite), against
+// finite boxes, no product (b - o) * inv is NaN (b - o may round to ±inf; only inf * 0 would be NaN) and each is
+// monotone in b (IEEE subtraction and multiplication by a constant are monotone under round-to-nearest):
 // growing a box can only lower its entry parameter and raise its exit parameter, so
 //        slab(ray, AABB(s)) passes  ⇒  slab(ray, every ancestor box of s) passes.
 // The ancestor tests are therefore redundant for the RESULT, and a walk may skip tree levels as long as it keeps the
 // pre-order: this kernel visits, for an inner node b, the four grandchildren directly (common.hpp WideNode).  On the
 // 120k-triangle scene a ray needs 20 dependent steps instead of 79, for the same 79 box tests.  Rays with a non-finite
-// component (axis-parallel: inv = ±inf) can produce NaN products, which the reference turns into a miss
+// component (axis-parallel: inv = ±inf) or a zero inv component (caller-built rays) can produce NaN products, which the
+// reference turns into a miss
 // (intersect_default.rs:22-28) and which break the implication above; waves holding such a ray take the exact
 // sequence instead: the skipped child box is rebuilt as the join of its two grandchild boxes (bit-identical to
 // the builder's box up to the sign of a zero, which no product distinguishes) and tested with the reference's

@@ -367,8 +367,9 @@ def ray_slice(ray, box):  # ray_impl.rs:118-145 → (tmin, tmax) or None
         return None
     inf = [_min(a, b) for a, b in zip(lbr, rtr)]
     sup = [_max(a, b) for a, b in zip(lbr, rtr)]
-    tmin = max(max(inf), type(inf[0])(0))
-    tmax = min(sup)
+    m = _max(_max(inf[0], inf[1]), inf[2])      # inf.max(), -0 < +0 like every fold of aabb_impl.rs
+    tmin = m if m > 0 else type(m)(0)           # fast_max(x, 0) (utils.rs:52-54): +0 unless x > 0
+    tmax = _min(_min(sup[0], sup[1]), sup[2])   # sup.min(): a zero tmax keeps its sign
     return None if tmin > tmax else (tmin, tmax)
 
 

@@ -1,0 +1,459 @@
+"""Every query at floating-point extremes on the MI355X, byte for byte against the oracle at the same precision (two NaNs count
+as equal): a scale sweep from all-subnormal scenes to overflowing surface areas and an overflowing root, mixed magnitudes in one
+tree at every builder tier, caller-built rays (inv = ±0, subnormal, huge, not 1/d), signed-zero t-slices, Ray::new edges and
+nearest_to on degenerate triangles.  The CPU side of the same inputs is pinned by tests/test_fp_extremes_cpu.py."""
+import numpy as np
+import pytest
+
+import query_ref as qr
+from test_fp_extremes_cpu import (BANDS, degenerate_triangles, ray_new_dirs, root_centroid_extent_overflows, same,
+                                  voronoi_points)
+
+pytestmark = pytest.mark.gpu
+
+NONE = 0xFFFFFFFF
+KNOB_QUERY = 22   # BVHGPU_TUNE_QUERY_VARIANT
+
+
+@pytest.fixture(scope="module")
+def eng():
+    import bvh_amd
+    if bvh_amd.device_count() <= 0:
+        pytest.fail("GPU test selected but no HIP device is visible (no CPU fallback exists)")
+    return bvh_amd
+
+
+@pytest.fixture(scope="module")
+def orc():
+    from oracle import orc as o
+    return o
+
+
+def _tname(dtype):
+    return "float" if dtype == np.float32 else "double"
+
+
+def _rb(eng, rays):
+    dt = np.float32 if rays.dtype.itemsize == 36 else np.float64
+    return eng.RayBatch(len(rays), dt, host=np.ascontiguousarray(rays))
+
+
+# binary, LDS and wide walks (whole rays and 16 items per ray), forced by tuning as in test_gpu_any_hit.py's WALKS table;
+# {m} is the walk mode (0 CSR, 2 triangles, 3 closest hit, 4 any hit)
+WALKS = [
+    ({0: 0, 3: 0}, "bvhgpu::k_traverse<{t}, {m}, false>"),
+    ({0: 2, 3: 0}, "bvhgpu::k_traverse_lds<{t}, {m}, false>"),
+    ({0: 3, 3: 0, 1: 0}, "bvhgpu::k_traverse_wide<"),
+    ({0: 3, 3: 0, 1: 2}, "bvhgpu::k_traverse_wide<"),
+]
+
+
+def _ctx(tune):
+    from bvh_amd import Context
+    ctx = Context(0)
+    for k, v in tune.items():
+        ctx.set_tuning(k, v)
+    return ctx
+
+
+def first_match(off, idx, oisect, tmax):
+    """any-hit's definition on the oracle's CSR: per row the first candidate with distance < tmax (strict)"""
+    n = len(off) - 1
+    isect = np.zeros((n, 3), dtype=oisect.dtype)
+    isect[:, 0] = np.inf
+    shape = np.full(n, NONE, dtype=np.uint32)
+    for r in range(n):
+        for j in range(int(off[r]), int(off[r + 1])):
+            if oisect[j, 0] < tmax[r]:
+                isect[r] = oisect[j]
+                shape[r] = idx[j]
+                break
+    return isect, shape
+
+
+def _oracle_rays(orc, tris, aabbs, oflat, rays):
+    ooff, oidx, ots, _ = orc.traverse_flat(oflat, aabbs, rays, want_t=True, threads=orc.max_threads())
+    oisect, oclosest, oprim = orc.triangle_stage(tris, rays, ooff, oidx)
+    return ooff, oidx, ots, oisect, oclosest, oprim
+
+
+def _check_modes(eng, flat, rays, want, tmax, dtype, label, wide_eligible):
+    """CSR, triangles, closest hit and any hit through every walk; returns the kernel names per walk.  wide_eligible: the tree
+    has an SAH winner at every split (otherwise the wide walk hands the batch to the binary walk)"""
+    ooff, oidx, ots, oisect, oclosest, oprim = want
+    wany = first_match(ooff, oidx, oisect, tmax)
+    t = _tname(dtype)
+    names = []
+    for tune, kernel in WALKS:
+        ctx = flat.ctx
+        saved = {k: ctx.get_tuning(k) for k in tune}
+        for k, v in tune.items():
+            ctx.set_tuning(k, v)
+        rb = _rb(eng, rays)
+        off, idx, _, _ = flat.traverse_batch(rb)
+        assert off.tobytes() == ooff.tobytes() and idx.tobytes() == oidx.tobytes(), (label, tune, "CSR")
+        k_csr = flat.query_kernel()
+        goff, gidx, gisect, _ = flat.intersect_triangles(rb)
+        assert goff.tobytes() == ooff.tobytes() and gidx.tobytes() == oidx.tobytes(), (label, tune, "triangles")
+        assert same(gisect, oisect), (label, tune, "triangles")
+        cl, prim, _ = flat.closest_hits(rb)
+        assert same(cl, oclosest) and np.array_equal(prim, oprim), (label, tune, "closest")
+        k_cl = flat.query_kernel()
+        isect, shape = flat.any_hits(rb, tmax)
+        assert same(isect, wany[0]) and np.array_equal(shape, wany[1]), (label, tune, "any")
+        k_any = flat.query_kernel()
+        for kname, m in ((k_csr, 0), (k_cl, 3), (k_any, 4)):
+            if "wide" in kernel:
+                assert kname.startswith(kernel) or not wide_eligible, (label, tune, kname)
+            else:
+                assert kname.startswith(kernel.format(t=t, m=m)), (label, tune, kname)
+        names.append((k_csr, k_cl, k_any))
+        for k, v in saved.items():
+            ctx.set_tuning(k, v)
+    print(f"walks {label}: " + "; ".join(" / ".join(n) for n in names))
+    return names
+
+
+# ---- 1. scale sweep ---------------------------------------------------------------------------------------------------------
+def _sweep_scene(k, dtype, n_cubes=200):
+    """cubes of the benchmark generator (coordinates up to 1e5) with their triangles, plus degenerate triangles, scaled by 2^k
+    in f64 and then rounded to dtype"""
+    from bvh_amd import testbase as tb
+    tris, _ = tb.create_n_cubes(n_cubes)
+    t = tris.astype(np.float64).reshape(-1, 3, 3)
+    deg = degenerate_triangles(dtype)[1:] * 250.0 + np.array([7.0, -3.0, 11.0])
+    t = np.concatenate([t, deg])
+    t = (t * 2.0 ** k).astype(dtype)
+    aabbs = np.concatenate([t.min(axis=1), t.max(axis=1)], axis=1)
+    return t, aabbs
+
+
+def _sweep_rays(orc, tris64, n, k, dtype, seed):
+    """rays aimed at random triangles' centres from around the scene, a tenth in random directions, a few axis-parallel"""
+    rng = np.random.default_rng(seed)
+    centres = tris64.mean(axis=1)
+    target = centres[rng.integers(0, len(centres), size=n)] + rng.uniform(-0.3, 0.3, size=(n, 3))
+    o = rng.uniform(-1.2e5, 1.2e5, size=(n, 3))
+    d = target - o
+    d[: n // 10] = rng.normal(size=(n // 10, 3))
+    d[n // 10: n // 10 + 30] = np.eye(3)[rng.integers(0, 3, 30)] * rng.choice([-1.0, 1.0], size=(30, 1))
+    return orc.make_rays((o * 2.0 ** k).astype(dtype), d.astype(dtype), dtype), rng
+
+
+# a large scale where Möller–Trumbore's products (about 2^(3k + 17) here) stay finite: triangle hits are required there.  In the
+# surface-area overflow band they overflow and the reference reports no triangle hit; at tiny scales det < epsilon.
+FINITE = {np.float32: 30, np.float64: 300}
+
+
+def _sweep_params():
+    out = []
+    for dtype in (np.float32, np.float64):
+        b = BANDS[dtype]
+        for k in [b["subnormal"], b["straddle"], FINITE[dtype]] + b["sa_overflow"] + [b["overflow"]]:
+            out.append(pytest.param(dtype, k, id=f"{_tname(dtype)}-2^{k}"))
+    return out
+
+
+@pytest.mark.parametrize("dtype,k", _sweep_params())
+def test_scale_sweep_every_query(eng, orc, dtype, k):
+    from bvh_amd import Context, FlatBvh
+    from bvh_amd._lib import INVALID_ARG, BvhGpuError
+    tris, aabbs = _sweep_scene(k, dtype)
+    ctx = Context(0)
+    if root_centroid_extent_overflows(aabbs):
+        # the reference panics on the NaN bucket index (bvh_node.rs:214-217): the oracle is not called
+        with pytest.raises(BvhGpuError) as e:
+            eng.Bvh.from_aabbs(aabbs, ctx)
+        assert e.value.status == INVALID_ARG
+        assert k == BANDS[dtype]["overflow"]
+        print(f"scale {_tname(dtype)} 2^{k}: refused (INVALID_ARG)")
+        return
+    assert k != BANDS[dtype]["overflow"]
+    sc = 2.0 ** k
+    # build + flatten
+    bvh = eng.Bvh.from_aabbs(aabbs, ctx)
+    ot = orc.build(aabbs)
+    assert bvh.nodes.tobytes() == ot.nodes.tobytes() and np.array_equal(bvh.shape_nodes, ot.shape_node)
+    flat = bvh.flatten()
+    oflat = orc.flatten(ot.nodes)
+    assert flat.nodes.tobytes() == oflat.tobytes()
+    flat.set_triangles(tris)
+    # rays: CSR with t-slices, then every mode through every walk
+    tris64 = tris.astype(np.float64) / sc
+    rays, rng = _sweep_rays(orc, tris64, 3000, k, dtype, seed=abs(k))
+    want = _oracle_rays(orc, tris, aabbs, oflat, rays)
+    ooff, oidx, ots, oisect, oclosest, oprim = want
+    counts = np.diff(ooff.astype(np.int64))
+    assert (counts > 0).sum() > 100 and (counts == 0).sum() > 100, "the CSR must have hits and misses"
+    off, idx, ts, _ = flat.traverse_batch(_rb(eng, rays), want_t=True)
+    assert off.tobytes() == ooff.tobytes() and idx.tobytes() == oidx.tobytes() and same(ts, ots)
+    c = oclosest[:, 0].astype(np.float64)
+    tmax = (np.where(np.isfinite(c), c, 2e5 * sc) * rng.uniform(0.3, 1.7, size=len(c))).astype(dtype)
+    if k == FINITE[dtype]:
+        assert np.isfinite(c).sum() > 100 and (first_match(ooff, oidx, oisect, tmax)[1] != NONE).sum() > 50
+    _check_modes(eng, flat, rays, want, tmax, dtype, f"{_tname(dtype)} 2^{k}", wide_eligible=False)
+    # ordered and heap walks
+    if orc.tree_stats(ot.nodes, aabbs)["max_depth"] < 31:
+        for order, asc in (("nearest", True), ("farthest", False)):
+            noff, nidx, _, _ = flat.traverse_batch(_rb(eng, rays), order=order)
+            qoff, qidx = orc.traverse_child_ordered(ot.nodes, aabbs, rays, asc)
+            assert np.array_equal(noff, qoff) and np.array_equal(nidx, qidx), order
+    for order, asc in (("nearest_heap", True), ("farthest_heap", False)):
+        noff, nidx, _, _ = flat.traverse_batch(_rb(eng, rays), order=order)
+        qoff, qidx = orc.traverse_distance(ot.nodes, aabbs, rays, asc)
+        assert np.array_equal(noff, qoff) and np.array_equal(nidx, qidx), order
+    # AABB / point / ball queries, both walks of knob 22
+    a64 = aabbs.astype(np.float64) / sc
+    near = rng.integers(0, len(a64), size=600)
+    cq = (a64[near, :3] + a64[near, 3:]) * 0.5 + rng.normal(size=(600, 3)) * 2.0
+    e = rng.uniform(0.0, 3.0, size=(600, 3))
+    pq = cq + rng.normal(size=(600, 3)) * 0.3
+    pq[:300] = (a64[near[:300], :3] + a64[near[:300], 3:]) * 0.5          # box centres (the triangles' boxes are flat)
+    queries = {qr.AABB: np.concatenate([cq - e, cq + e], axis=1), qr.POINT: pq, qr.BALL: np.concatenate([cq, e[:, :1]], axis=1)}
+    for kind, q64 in queries.items():
+        q = (q64 * sc).astype(dtype)
+        qoff, qidx = qr.walk(oflat, aabbs, kind, q)
+        # where surface areas overflow, splits without an SAH winner leave empty child boxes that no query enters (the
+        # reference's answer: nothing); elsewhere the queries must find shapes
+        assert len(qidx) > 0 or k in BANDS[dtype]["sa_overflow"], kind
+        for knob in (0, 1):
+            ctx.set_tuning(KNOB_QUERY, knob)
+            off, idx = flat.query_batch(kind, q)
+            assert off.tobytes() == qoff.tobytes() and idx.tobytes() == qidx.tobytes(), (kind, knob)
+        ctx.set_tuning(KNOB_QUERY, -1)
+    # nearest_to on boxes and on triangles
+    pts = (rng.uniform(-1.1e5, 1.1e5, size=(500, 3)) * sc).astype(dtype)
+    pts[:200] = (cq[:200] * sc).astype(dtype)
+    for use_tris in (False, True):
+        s_, d_ = flat.nearest_batch(pts, triangles=use_tris)
+        os_, od_ = orc.nearest(oflat, aabbs, pts, tris if use_tris else None)
+        assert np.array_equal(s_, os_) and same(d_, od_), use_tris
+    # scene blob round trip
+    blob = np.zeros(flat.scene_nbytes(), dtype=np.uint8)
+    flat.scene_export(blob)
+    peer = FlatBvh.scene_import(blob, len(blob), ctx)
+    poff, pidx, _, _ = peer.traverse_batch(_rb(eng, rays))
+    assert poff.tobytes() == ooff.tobytes() and pidx.tobytes() == oidx.tobytes()
+    cl, prim, _ = peer.closest_hits(_rb(eng, rays))
+    assert same(cl, oclosest) and np.array_equal(prim, oprim)
+    # refit by a rigid shift of every shape, scaled like the scene
+    shift = (np.repeat(rng.uniform(-3, 3, size=(len(a64), 3)), 2, axis=0).reshape(-1, 6) * sc)
+    a1 = (a64 * sc + shift).astype(dtype)
+    bvh.refit(a1)
+    on = orc.refit(ot.nodes, a1)
+    assert bvh.nodes.tobytes() == on.tobytes()
+    assert flat.nodes.tobytes() == orc.flatten(on).tobytes()
+    print(f"scale {_tname(dtype)} 2^{k}: accepted, {len(oidx)} CSR hits, {int(np.isfinite(c).sum())} closest hits")
+
+
+# ---- 2. mixed magnitudes in one tree ----------------------------------------------------------------------------------------
+def _mixed(n, dtype, seed):
+    """half of the shapes near 2^-120 (2^-1000 in f64), half far out (2^70 / 2^520): surface areas of 0 and of +inf in the top
+    levels, finite below"""
+    rng = np.random.default_rng(seed)
+    lo_s, hi_s = (2.0 ** -120, 2.0 ** 70) if dtype == np.float32 else (2.0 ** -1000, 2.0 ** 520)
+    h = n // 2
+    c = np.empty((n, 3))
+    e = np.empty((n, 3))
+    c[:h] = lo_s * (1.0 + rng.uniform(0, 1, size=(h, 3)))
+    e[:h] = lo_s * rng.uniform(0, 0.3, size=(h, 3))
+    c[h:] = hi_s * rng.normal(size=(n - h, 3))
+    e[h:] = hi_s * rng.uniform(0, 0.01, size=(n - h, 3))
+    perm = rng.permutation(n)
+    a = np.concatenate([c - e, c + e], axis=1)[perm].astype(dtype)
+    return a, hi_s, rng
+
+
+@pytest.mark.parametrize("dtype,n", [(np.float32, 64), (np.float32, 65), (np.float32, 4096), (np.float32, 4097),
+                                     (np.float32, 20000), (np.float64, 65), (np.float64, 4097), (np.float32, 260_000)])
+def test_mixed_magnitudes_every_tier(eng, orc, dtype, n):
+    from bvh_amd._lib import TUNE_BUILD_LEVEL_LAUNCHES
+    aabbs, hi_s, rng = _mixed(n, dtype, seed=n)
+    assert not root_centroid_extent_overflows(aabbs)
+    ot = orc.build(aabbs, parallel=n > 50000, threads=orc.max_threads() if n > 50000 else 0)
+    oflat = orc.flatten(ot.nodes)
+    m = 500 if n > 50000 else 2000
+    o = rng.uniform(-3, 3, size=(m, 3)) * hi_s
+    a64 = aabbs.astype(np.float64)
+    big = a64[np.abs(a64).max(axis=1) > 1.0]
+    tgt = big[rng.integers(0, len(big), size=m)]
+    d = (tgt[:, :3] + tgt[:, 3:]) * 0.5 - o                 # toward a far shape
+    d[: m // 4] = rng.normal(size=(m // 4, 3))              # anywhere
+    n_origin = 10 if n > 50000 else 50                      # through the tiny cluster: from far out, every tiny box is one point
+    d[m // 4: m // 4 + n_origin] = -o[m // 4: m // 4 + n_origin]
+    rays = orc.make_rays(o.astype(dtype), d.astype(dtype), dtype)
+    ooff, oidx, _, _ = orc.traverse_flat(oflat, aabbs, rays, threads=orc.max_threads())
+    counts = np.diff(ooff.astype(np.int64))
+    assert (counts > 0).sum() > 100 and (counts == 0).sum() > 100, ((counts > 0).sum(), (counts == 0).sum())
+    sel = a64[rng.integers(0, n, size=300)]
+    q = np.concatenate([2 * sel[:, :3] - sel[:, 3:], 2 * sel[:, 3:] - sel[:, :3]], axis=1).astype(dtype)   # each box grown by itself
+    qoff, qidx = qr.walk(oflat, aabbs, qr.AABB, q)   # (splits without an SAH winner above both halves leave empty child boxes,
+                                                     # which no box query enters and every ray enters: flat_bvh.rs:411-418)
+    for launches in (1, 2):
+        ctx = _ctx({TUNE_BUILD_LEVEL_LAUNCHES: launches})
+        bvh = eng.Bvh.from_aabbs(aabbs, ctx)
+        assert bvh.nodes.tobytes() == ot.nodes.tobytes() and np.array_equal(bvh.shape_nodes, ot.shape_node), launches
+        flat = bvh.flatten()
+        assert flat.nodes.tobytes() == oflat.tobytes(), launches
+        for tune in ({0: 0, 3: 0}, {0: 3, 3: 0, 1: 2}):
+            for kk, v in tune.items():
+                ctx.set_tuning(kk, v)
+            off, idx, _, _ = flat.traverse_batch(_rb(eng, rays))
+            assert off.tobytes() == ooff.tobytes() and idx.tobytes() == oidx.tobytes(), (launches, tune)
+        off, idx = flat.query_batch(qr.AABB, q)
+        assert off.tobytes() == qoff.tobytes() and idx.tobytes() == qidx.tobytes(), launches
+
+
+# ---- 3. caller-built rays ---------------------------------------------------------------------------------------------------
+def _flat_plane_scene(dtype, n=3000, seed=17):
+    """every triangle in the plane x = X (2^104 in f32, 2^971 in f64: half an ulp of the largest finite value), spread normally
+    in y and z: finite areas, a tree with SAH winners everywhere (the wide walk takes it)"""
+    rng = np.random.default_rng(seed)
+    X = 2.0 ** (104 if dtype == np.float32 else 971)
+    y, z = rng.normal(scale=20.0, size=n), rng.normal(scale=20.0, size=n)
+    a = np.stack([np.full(n, X), y, z], axis=1)
+    tris = np.stack([a, a + [0.0, 0.0, 1.0], a + [0.0, 1.0, 0.0]], axis=1).astype(dtype)   # front face toward -x
+    aabbs = np.concatenate([tris.min(axis=1), tris.max(axis=1)], axis=1)
+    return tris, aabbs, X
+
+
+def _caller_rays(dtype, X, n, seed):
+    """Ray structs written directly: inv = ±0 (with origins whose b - o overflows, and with near ones), subnormal and huge inv,
+    |inv| < 1, inv not 1/d"""
+    from test_fp_extremes_cpu import special
+    rt = np.dtype([("o", dtype, 3), ("d", dtype, 3), ("inv", dtype, 3)])
+    v = special(dtype)
+    rng = np.random.default_rng(seed)
+    r = np.zeros(n, dtype=rt)
+    yz = rng.normal(scale=20.0, size=(n, 2))
+    ox = rng.choice([-float(v["mx"]), 0.0, -X, X * 0.5, -1.0], size=n)
+    r["o"] = np.column_stack([ox, yz]).astype(dtype)
+    inv = np.empty((n, 3))
+    inv[:, 0] = rng.choice([0.0, -0.0, 1.0, float(v["sub"]), float(v["mx"]), 0.25, 2.0 ** -60, -3.0], size=n)
+    inv[:, 1:] = rng.choice([1.0, -1.0, 0.0, -0.0, 0.5, 4.0, np.inf, float(v["sub"]), 2.0 ** 40], size=(n, 2))
+    # the overflow construction: o.x = -MAX, inv = (0, 1, 1) (each box lies in the +y, +z quadrant of the origin's reach)
+    m = n // 5
+    r["o"][:m, 0] = -v["mx"]
+    inv[:m] = [0.0, 1.0, 1.0]
+    inv[m: m + 20] = [-0.0, 1.0, 1.0]
+    r["inv"] = inv.astype(dtype)
+    d = np.tile([1.0, 0.0, 0.0], (n, 1))                                 # along +x: Möller–Trumbore's products stay finite
+    d[::4] = rng.normal(size=(len(d[::4]), 3))
+    r["d"] = d.astype(dtype)
+    return r, m
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_caller_built_rays_every_walk(eng, orc, dtype):
+    from bvh_amd import Context
+    tris, aabbs, X = _flat_plane_scene(dtype)
+    rays, m = _caller_rays(dtype, X, 6000, seed=3)
+    ot = orc.build(aabbs)
+    oflat = orc.flatten(ot.nodes)
+    want = _oracle_rays(orc, tris, aabbs, oflat, rays)
+    ooff, oidx, ots, oisect, oclosest, oprim = want
+    counts = np.diff(ooff.astype(np.int64))
+    with np.errstate(all="ignore"):
+        assert np.isnan((aabbs[0, 0] - rays["o"][0, 0]) * rays["inv"][0, 0])
+    assert np.all(counts[:m] == 0)                                       # the reference: a NaN slab is a miss
+    assert (counts[m:] > 0).sum() > 200 and (counts[m:] == 0).sum() > 200
+    rng = np.random.default_rng(8)
+    c = oclosest[:, 0].astype(np.float64)
+    tmax = np.where(np.isfinite(c), c * rng.uniform(0.3, 1.7, size=len(c)), np.inf).astype(dtype)
+    assert np.isfinite(c).sum() > 50 and (first_match(ooff, oidx, oisect, tmax)[1] != NONE).sum() > 20
+    ctx = Context(0)
+    bvh = eng.Bvh.from_aabbs(aabbs, ctx)
+    assert bvh.nodes.tobytes() == ot.nodes.tobytes()
+    flat = bvh.flatten()
+    flat.set_triangles(tris)
+    off, idx, ts, _ = flat.traverse_batch(_rb(eng, rays), want_t=True)
+    assert off.tobytes() == ooff.tobytes() and idx.tobytes() == oidx.tobytes() and same(ts, ots)
+    _check_modes(eng, flat, rays, want, tmax, dtype, f"caller-built {_tname(dtype)}", wide_eligible=True)
+    # the same rays through the default tuning (a batch of 20 000: the wide walk's own choice of items)
+    big = np.concatenate([rays] * 4)[:20000]
+    goff, gidx, _, st = flat.traverse_batch(_rb(eng, big), stats=False)
+    boff, bidx, _, _ = orc.traverse_flat(oflat, aabbs, big, threads=orc.max_threads())
+    assert goff.tobytes() == boff.tobytes() and gidx.tobytes() == bidx.tobytes()
+    print(f"walks caller-built {_tname(dtype)} default: {st['kernel']}")
+
+
+# ---- 4. signed-zero slices --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_signed_zero_slices(eng, orc, dtype):
+    """flat [-0, +0] (and [-0, -0], [+0, +0]) boxes on each axis and origins with +0 / -0 in that plane: the device t-slice carries
+    the oracle's zero signs (inf_sup and the folds order -0 < +0)"""
+    from bvh_amd import Aabb, Ray
+    boxes, rays_o, rays_d = [], [], []
+    for ax in range(3):
+        for lo, hi in ((-0.0, 0.0), (-0.0, -0.0), (0.0, 0.0)):
+            b = np.array([-1.0, -1.0, -1.0, 1.0, 1.0, 1.0]); b[ax] = lo; b[3 + ax] = hi
+            boxes.append(b)
+        for oz in (0.0, -0.0):
+            for sgn in (1.0, -1.0):
+                o = np.array([0.25, -0.5, 0.125]); o[ax] = oz
+                d = np.zeros(3); d[ax] = sgn
+                rays_o.append(o); rays_d.append(d)
+                d2 = d.copy(); d2[(ax + 1) % 3] = 0.5                  # oblique: the other slabs are finite
+                rays_o.append(o); rays_d.append(d2)
+    boxes = np.array(boxes, dtype=dtype)
+    rays = orc.make_rays(np.array(rays_o), np.array(rays_d), dtype)
+    neg = 0
+    for bi, box in enumerate(boxes):
+        for ri in range(len(rays)):
+            want = orc.ray_slice(rays[ri], box)
+            ray = Ray(rays_o[ri], rays_d[ri], dtype)
+            got = ray.intersection_slice_for_aabb(Aabb(box[:3], box[3:], dtype))
+            assert (want is None) == (got is None), (box, rays_o[ri], rays_d[ri], want, got)
+            if want is not None:
+                assert np.array(got, dtype=dtype).tobytes() == np.array(want, dtype=dtype).tobytes(), (box, rays_o[ri], rays_d[ri], want, got)
+                neg += int(np.signbit(want[1]))
+    assert neg >= 6
+    # the same boxes as one scene, every ray batched with want_t (the binary walk of the t-slice mode)
+    flat = eng.Bvh.from_aabbs(boxes).flatten()
+    oflat = orc.flatten(orc.build(boxes).nodes)
+    ooff, oidx, ots, _ = orc.traverse_flat(oflat, boxes, rays, want_t=True)
+    off, idx, ts, _ = flat.traverse_batch(_rb(eng, rays), want_t=True)
+    assert off.tobytes() == ooff.tobytes() and idx.tobytes() == oidx.tobytes()
+    assert ts.tobytes() == ots.tobytes()
+    assert np.signbit(ots[:, 1][ots[:, 1] == 0]).any() and (~np.signbit(ots[:, 1][ots[:, 1] == 0])).any()
+
+
+# ---- 5. Ray::new edges ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_ray_new_edges(eng, orc, dtype):
+    d = np.array(ray_new_dirs(dtype), dtype=dtype)
+    o = np.zeros_like(d)
+    o[::2] = np.array([-0.0, 0.0, 1.0], dtype=dtype)
+    got = eng.RayBatch.new(o, d, dtype).host
+    want = orc.make_rays(o, d, dtype)
+    for f in ("o", "d", "inv"):
+        assert same(got[f], want[f]), (f, got[f], want[f])
+    assert np.isnan(want["inv"]).any() and np.isinf(want["inv"]).any()
+
+
+# ---- 6. nearest_to on degenerate triangles ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_nearest_on_degenerate_triangles(eng, orc, dtype):
+    """coincident and collinear vertices (closest_point_triangle's vertex / edge branches and closest_point_segment), each
+    triangle far from the others, with points in every Voronoi region around it"""
+    base = degenerate_triangles(dtype)
+    tris, pts = [], []
+    for i, t in enumerate(base):
+        off = np.array([100.0 * i, -50.0 * (i % 3), 30.0 * (i % 2)])
+        tris.append(t + off)
+        pts.append(voronoi_points(t) + off)
+    scales = (0, 60, -100) if dtype == np.float32 else (0, 500, -900)
+    for k in scales:
+        sc = 2.0 ** k
+        t = (np.array(tris) * sc).astype(dtype)
+        p = (np.concatenate(pts) * sc).astype(dtype)
+        aabbs = np.concatenate([t.min(axis=1), t.max(axis=1)], axis=1)
+        flat = eng.Bvh.from_aabbs(aabbs).flatten()
+        flat.set_triangles(t)
+        oflat = orc.flatten(orc.build(aabbs).nodes)
+        for use_tris in (False, True):
+            s_, d_ = flat.nearest_batch(p, triangles=use_tris)
+            os_, od_ = orc.nearest(oflat, aabbs, p, t if use_tris else None)
+            assert np.array_equal(s_, os_) and same(d_, od_), (k, use_tris)
+        if k == 0:   # (at the tiny scale every squared distance underflows to 0: the first shape wins everywhere)
+            assert len(np.unique(os_)) == len(t) and (od_ == 0).any() and (od_ > 0).any()

@@ -1,13 +1,15 @@
 """Parity tests proper: the HIP engine (through the C ABI, via bvh_amd's ctypes mirror) against the
 CPU oracle on the same seeded inputs, and against the reference's own known-answer vectors.
 Bar: bit-exact for BvhNode / FlatNode arrays, shape->node map, CSR offsets and indices (order
-included); f32 t-values within 1e-5 relative (they are in fact bit-identical), f64 within 1e-12.
+included) and t-slices (two NaNs count as equal).
 """
 import json
 import os
 
 import numpy as np
 import pytest
+
+from test_fp_extremes_cpu import same as same_bytes  # byte equality, two NaNs equal
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +35,7 @@ def _rb(eng, rays):
     return eng.RayBatch(len(rays), dt, host=np.ascontiguousarray(rays))
 
 
-def _full_parity(eng, orc, aabbs, rays, t_rtol):
+def _full_parity(eng, orc, aabbs, rays):
     bvh = eng.Bvh.from_aabbs(aabbs)
     ot = orc.build(aabbs)
     assert bvh.nodes.tobytes() == ot.nodes.tobytes()
@@ -46,7 +48,7 @@ def _full_parity(eng, orc, aabbs, rays, t_rtol):
     assert np.array_equal(off, ooff)
     assert np.array_equal(idx, oidx)
     if len(idx):
-        assert np.allclose(ts, ots, rtol=t_rtol, atol=0)
+        assert same_bytes(ts, ots)
     assert st["hits"] == ost["hits"] and st["visited"] == ost["visited"] and st["leaf_visits"] == ost["leaf_visits"]
     # the same batch without STATS / T_SLICE: the default walk for large batches (the wide walk) must give the same CSR
     off2, idx2, _, _ = flat.traverse_batch(_rb(eng, rays))
@@ -115,7 +117,7 @@ def test_reference_slab_edge_cases(eng, dtype):
 def test_parity_config0_1200_triangles(eng, orc):
     from bvh_amd import testbase as tb
     _, aabbs = tb.create_n_cubes(100)
-    _full_parity(eng, orc, aabbs, orc.create_rays(0, 1000), 1e-5)
+    _full_parity(eng, orc, aabbs, orc.create_rays(0, 1000))
 
 
 def test_parity_config1_120k_triangles(eng, orc):
@@ -123,7 +125,7 @@ def test_parity_config1_120k_triangles(eng, orc):
     CSR (order included), t-slices and visit counters against the oracle (which needs < 1 s for it, multi-threaded)."""
     from bvh_amd import testbase as tb
     _, aabbs = tb.create_n_cubes(10_000)
-    bvh, flat, ot, oflat = _full_parity(eng, orc, aabbs, orc.create_rays(0, 1_000_000), 1e-5)
+    bvh, flat, ot, oflat = _full_parity(eng, orc, aabbs, orc.create_rays(0, 1_000_000))
     assert orc.check_tree(bvh.nodes, aabbs) == 0  # assert_consistent + assert_tight + coverage on the GPU tree
 
 
@@ -133,7 +135,7 @@ def test_parity_config4_f64(eng, orc):
     _, aabbs = tb.create_n_cubes(10_000)
     r32 = orc.create_rays(0, 1_000_000)
     rays = orc.make_rays(r32["o"].astype(np.float64), r32["d"].astype(np.float64), np.float64)
-    _full_parity(eng, orc, aabbs.astype(np.float64), rays, 1e-12)
+    _full_parity(eng, orc, aabbs.astype(np.float64), rays)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -146,7 +148,7 @@ def test_parity_ragged_sizes(eng, orc, n, dtype):
     aabbs = np.concatenate([lo, lo + ext], axis=1)
     o = rng.uniform(-120, 120, size=(300, 3)).astype(dtype)
     d = rng.normal(size=(300, 3)).astype(dtype)
-    _full_parity(eng, orc, aabbs, orc.make_rays(o, d, dtype), 1e-5 if dtype == np.float32 else 1e-12)
+    _full_parity(eng, orc, aabbs, orc.make_rays(o, d, dtype))
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -164,10 +166,10 @@ def test_parity_degenerate_and_collisions(eng, orc, dtype):
     d = rng.integers(-1, 2, size=(2000, 3)).astype(dtype)          # axis-parallel / diagonal directions
     d[np.all(d == 0, axis=1)] = [1, 0, 0]
     rays = orc.make_rays(o, d, dtype)
-    _full_parity(eng, orc, aabbs, rays, 1e-5 if dtype == np.float32 else 1e-12)
+    _full_parity(eng, orc, aabbs, rays)
     # all shapes identical: every split is the halving path
     same = np.tile(aabbs[500], (777, 1))
-    _full_parity(eng, orc, same, rays[:200], 1e-5 if dtype == np.float32 else 1e-12)
+    _full_parity(eng, orc, same, rays[:200])
 
 
 def test_parity_unbalanced_deep_tree(eng, orc):
@@ -180,7 +182,7 @@ def test_parity_unbalanced_deep_tree(eng, orc):
     aabbs = np.concatenate([lo, lo + np.float32(0.5)], axis=1).astype(np.float32)
     o = np.zeros((64, 3), np.float32); o[:, 1] = 0.25; o[:, 2] = 0.25; o[:, 0] = -1
     d = np.tile(np.array([1, 0, 0], np.float32), (64, 1))
-    bvh, *_ = _full_parity(eng, orc, aabbs, orc.make_rays(o, d), 1e-5)
+    bvh, *_ = _full_parity(eng, orc, aabbs, orc.make_rays(o, d))
     assert bvh.build_levels >= 5  # optimistic batch for n = 12 000 is 4 passes: the continuation ran
 
 
@@ -319,7 +321,7 @@ def test_parity_mid_tier_boundaries(eng, orc, n, dtype):
     aabbs = np.concatenate([lo, lo + ext], axis=1)
     o = rng.uniform(-1100, 1100, size=(500, 3)).astype(dtype)
     d = rng.normal(size=(500, 3)).astype(dtype)
-    _full_parity(eng, orc, aabbs, orc.make_rays(o, d, dtype), 1e-5 if dtype == np.float32 else 1e-12)
+    _full_parity(eng, orc, aabbs, orc.make_rays(o, d, dtype))
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -410,7 +412,7 @@ def test_hit_pool_growth_and_order(eng, orc):
     o = np.tile(np.array([-5, 0.5, 0.5], np.float32), (300, 1)); o[:, 1] += np.linspace(0, 0.4, 300, dtype=np.float32)
     d = np.tile(np.array([1, 0, 0], np.float32), (300, 1))
     rays = orc.make_rays(o, d)
-    bvh, flat, ot, oflat = _full_parity(eng, orc, aabbs, rays, 1e-5)
+    bvh, flat, ot, oflat = _full_parity(eng, orc, aabbs, rays)
     off, idx, _, _ = flat.traverse_batch(_rb(eng, rays))
     assert off[-1] == 300 * n  # every ray reports every box: 1.2 M hits from 300 rays
 
@@ -548,7 +550,6 @@ def test_wide_walk_same_result(eng, orc, items, stack_lds, wg_per_cu, threads, s
 
 
 def _variant_suite(eng, orc, ctx, dtype, deep=False):
-    rtol = 1e-5 if dtype == np.float32 else 1e-12
     rng = np.random.default_rng(77)
 
     def check(aabbs, rays, flat_upload=None, counters=True):
@@ -565,7 +566,7 @@ def _variant_suite(eng, orc, ctx, dtype, deep=False):
         ooff, oidx, ots, ost = orc.traverse_flat(oflat, cur, rays, want_t=True, threads=orc.max_threads())
         assert np.array_equal(off, ooff) and np.array_equal(idx, oidx)
         if len(idx):
-            assert np.allclose(ts, ots, rtol=rtol, atol=0)
+            assert same_bytes(ts, ots)
         if counters:
             assert (st["hits"], st["visited"], st["leaf_visits"]) == (ost["hits"], ost["visited"], ost["leaf_visits"])
         off2, idx2, _, _ = tree.traverse_batch(rb)          # the NaN-free fast slab test (no t-slice requested)
@@ -795,7 +796,7 @@ def test_parity_signed_zero_bounds(eng, orc, n, dtype):
     assert np.signbit(aabbs[aabbs == 0]).any() and (~np.signbit(aabbs[aabbs == 0])).any()
     o = rng.uniform(-3, 3, size=(400, 3)).astype(dtype)
     d = rng.normal(size=(400, 3)).astype(dtype)
-    _full_parity(eng, orc, aabbs, orc.make_rays(o, d, dtype), 1e-5 if dtype == np.float32 else 1e-12)
+    _full_parity(eng, orc, aabbs, orc.make_rays(o, d, dtype))
 
 
 # ------------------------------------------------------------------ point query (BoundingHierarchy::nearest_to)
@@ -1202,9 +1203,15 @@ def test_c_abi_from_plain_c(eng, orc, tmp_path):
 def test_fuzz_all_queries(eng, orc, seed):
     """in the spirit of the reference's fuzz.rs ("all traversals agree", fuzz.rs:321-324): random scenes of random
     size and character (spread, clustered, grid-aligned with exact ties, duplicated shapes), random rays and points;
-    every query the engine offers against the oracle, both dtypes alternating."""
+    every query the engine offers against the oracle, both dtypes alternating.  Each seed scales its scene by 2^k — 1, an
+    all-subnormal band, a band where surface areas overflow, 2^-20 — and a tenth of its rays are caller-built (inv = ±0,
+    subnormal, huge, or not 1/d)."""
+    import query_ref as qr
+    from test_gpu_any_hit import first_match
     rng = np.random.default_rng(1000 + seed)
     dtype = np.float32 if seed % 2 == 0 else np.float64
+    k_scale = (0, -140 if dtype == np.float32 else -1040, 70 if dtype == np.float32 else 520, -20)[(seed // 2) % 4]
+    sc = 2.0 ** k_scale
     n = int(rng.integers(1, 6000 if seed % 7 else 60000))
     kind = seed % 4
     if kind == 0:
@@ -1216,15 +1223,24 @@ def test_fuzz_all_queries(eng, orc, seed):
         a = rng.integers(-8, 8, size=(n, 3)).astype(float)
     else:
         a = rng.uniform(-50, 50, size=(n, 3)); a[n // 3:] = a[: n - n // 3][rng.integers(0, max(n - n // 3, 1), n - n // 3)]
-    a = a.astype(dtype)
-    tri = np.stack([a, a + rng.uniform(0, 2, size=(n, 3)).astype(dtype), a + rng.uniform(0, 2, size=(n, 3)).astype(dtype)], axis=1)
+    a = a.astype(dtype).astype(np.float64)
+    tri64 = np.stack([a, a + rng.uniform(0, 2, size=(n, 3)).astype(dtype), a + rng.uniform(0, 2, size=(n, 3)).astype(dtype)], axis=1)
+    tri = (tri64 * sc).astype(dtype)
     aabbs = np.concatenate([tri.min(axis=1), tri.max(axis=1)], axis=1).astype(dtype)
-    m = 1500
-    o = rng.uniform(-60, 60, size=(m, 3)).astype(dtype)
-    d = (tri[rng.integers(0, n, m)].mean(axis=1) - o).astype(dtype)
+    m = 120 if k_scale < -100 else 1500                # (x86 arithmetic on subnormals is slow: the oracle's share of the time)
+    o64 = rng.uniform(-60, 60, size=(m, 3))
+    o = (o64 * sc).astype(dtype)
+    d = (tri64[rng.integers(0, n, m)].mean(axis=1) - o64).astype(dtype)
     d[: m // 5] = rng.normal(size=(m // 5, 3))
     d[m // 5: m // 4] = rng.integers(-1, 2, size=(m // 4 - m // 5, 3)); d[np.all(d == 0, axis=1)] = [1, 0, 0]
     rays = orc.make_rays(o, d, dtype)
+    cb = rng.random(m) < 0.1                            # caller-built rays: Ray's fields are public
+    fi = np.finfo(dtype)
+    pick = np.array([0.0, -0.0, fi.smallest_subnormal, fi.max, 0.5, 3.0])[rng.integers(0, 6, size=(m, 3))]
+    keep = rng.random((m, 3)) < 0.5
+    with np.errstate(over="ignore", invalid="ignore"):
+        inv_cb = np.where(keep, rays["inv"].astype(np.float64), np.where(pick < 1.0, pick, pick * rays["inv"]))
+        rays["inv"][cb] = inv_cb[cb].astype(dtype)
     bvh = eng.Bvh.from_aabbs(aabbs)
     ot = orc.build(aabbs)
     assert bvh.nodes.tobytes() == ot.nodes.tobytes() and np.array_equal(bvh.shape_nodes, ot.shape_node)
@@ -1235,11 +1251,16 @@ def test_fuzz_all_queries(eng, orc, seed):
     rb = _rb(eng, rays)
     ooff, oidx, ots, ost = orc.traverse_flat(oflat, aabbs, rays, want_t=True)
     off, idx, ts, st = flat.traverse_batch(rb, want_t=True, stats=True)
-    assert np.array_equal(off, ooff) and np.array_equal(idx, oidx) and st["visited"] == ost["visited"]
+    assert np.array_equal(off, ooff) and np.array_equal(idx, oidx)
     if len(idx):
-        assert np.allclose(ts, ots, rtol=1e-5 if dtype == np.float32 else 1e-12, atol=0)
-    toff, tidx = orc.traverse_tree(ot.nodes, aabbs, rays)               # Bvh::traverse == FlatBvh::traverse
-    assert np.array_equal(toff, ooff) and np.array_equal(tidx, oidx)
+        assert same_bytes(ts, ots)
+    # a split without SAH winner (the band where surface areas overflow) leaves empty child boxes, which every ray enters:
+    # Bvh::traverse then reports the shapes below them unfiltered while FlatBvh::traverse tests each shape's own AABB, and
+    # the visit counters stop being comparable (see _variant_suite's overflow scene)
+    if not np.any((oflat["entry"] != 0xFFFFFFFF) & (oflat["min"][:, 0] > oflat["max"][:, 0])):
+        assert st["visited"] == ost["visited"]
+        toff, tidx = orc.traverse_tree(ot.nodes, aabbs, rays)           # Bvh::traverse == FlatBvh::traverse
+        assert np.array_equal(toff, ooff) and np.array_equal(tidx, oidx)
     # the large-batch walk (four grandchildren per step, rays cut into items) on the same small batch, and the two level-tier
     # schedules of the builder alternating with the seed
     from bvh_amd import Context
@@ -1261,7 +1282,7 @@ def test_fuzz_all_queries(eng, orc, seed):
     oisect, oclosest, oprim = orc.triangle_stage(tri, rays, ooff, oidx)
     _, _, isect, _ = flat.intersect_triangles(rb)
     cl, prim, _ = flat.closest_hits(rb)
-    assert isect.tobytes() == oisect.tobytes() and cl.tobytes() == oclosest.tobytes() and np.array_equal(prim, oprim)
+    assert same_bytes(isect, oisect) and same_bytes(cl, oclosest) and np.array_equal(prim, oprim)
     if orc.tree_stats(ot.nodes, aabbs)["max_depth"] < 31:
         for order, asc in (("nearest", True), ("farthest", False)):
             noff, nidx, _, _ = flat.traverse_batch(rb, order=order)
@@ -1271,11 +1292,26 @@ def test_fuzz_all_queries(eng, orc, seed):
         noff, nidx, _, _ = flat.traverse_batch(rb, order=order)
         qoff, qidx = orc.traverse_distance(ot.nodes, aabbs, rays, asc)
         assert np.array_equal(noff, qoff) and np.array_equal(nidx, qidx)
-    pts = rng.uniform(-60, 60, size=(800, 3)).astype(dtype)
+    pts = (rng.uniform(-60, 60, size=(800 if m == 1500 else 60, 3)) * sc).astype(dtype)
     for use_tris in (False, True):
         s_, d_ = flat.nearest_batch(pts, triangles=use_tris)
         os_, od_ = orc.nearest(oflat, aabbs, pts, tri if use_tris else None)
-        assert np.array_equal(s_, os_) and d_.tobytes() == od_.tobytes()
+        assert np.array_equal(s_, os_) and same_bytes(d_, od_)
+    # any hit with segment ends drawn around the nearest hit
+    c = oclosest[:, 0].astype(np.float64)
+    tmax = (np.where(np.isfinite(c), c, 200.0 * sc) * rng.uniform(0.3, 1.7, size=m)).astype(dtype)
+    want = first_match(ooff, oidx, oisect, tmax)
+    isect_a, shape_a = flat.any_hits(rb, tmax)
+    assert same_bytes(isect_a, want[0]) and np.array_equal(shape_a, want[1])
+    # AABB / point / ball queries around random shapes, the walks of knob 22 alternating with the seed
+    cq = (a[rng.integers(0, n, 150)] + rng.normal(size=(150, 3)))
+    e = rng.uniform(0, 3, size=(150, 3))
+    for qkind, q64 in ((qr.AABB, np.concatenate([cq - e, cq + e], axis=1)), (qr.POINT, cq), (qr.BALL, np.concatenate([cq, e[:, :1]], axis=1))):
+        q = (q64 * sc).astype(dtype)
+        qoff, qidx = qr.walk(oflat, aabbs, qkind, q)
+        wctx.set_tuning(22, (seed // 8) % 2)
+        goff, gidx = wflat.query_batch(qkind, q)
+        assert goff.tobytes() == qoff.tobytes() and gidx.tobytes() == qidx.tobytes(), qkind
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])

@@ -19,6 +19,7 @@ BCAST_TRIANGLES = 1
 F32, F64 = 0, 1
 HOST, DEVICE = 0, 1
 NONE = 0xFFFFFFFF
+KNN_MAX_K = 64   # BVHGPU_KNN_MAX_K: largest k of bvhgpu_knearest_*
 TRAVERSE_T_SLICE = 1
 TRAVERSE_STATS = 2
 TRAVERSE_TRIANGLES = 4
@@ -123,6 +124,8 @@ SYMBOLS = [
     ("bvhgpu_gen_primary_rays_f64", _i, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint64, _sz, _vp]),
     ("bvhgpu_nearest_f32", _i, [_vp, _vp, _sz, _i, _i, _vp, _vp]),
     ("bvhgpu_nearest_f64", _i, [_vp, _vp, _sz, _i, _i, _vp, _vp]),
+    ("bvhgpu_knearest_f32", _i, [_vp, _vp, _sz, _i, _i, C.c_uint32, _vp, _vp]),
+    ("bvhgpu_knearest_f64", _i, [_vp, _vp, _sz, _i, _i, C.c_uint32, _vp, _vp]),
     ("bvhgpu_ray_triangle_pairs_f32", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("bvhgpu_ray_triangle_pairs_f64", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("bvhgpu_traverse_f32", _i, [_vp, _vp, _sz, _i, _u, _pp]),

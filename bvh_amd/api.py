@@ -669,6 +669,38 @@ class _TreeBase:
         check(fn(self._t, ptr(p), len(p), HOST, 1 if triangles else 0, ptr(shape), ptr(dist)), self.ctx._h)
         return shape, dist
 
+    def knearest_batch(self, points, k: int, triangles: bool = False):
+        """bvhgpu_knearest_*: the k nearest shapes of every point — the loop of nearest_to (flat_bvh.rs:524-558) with a list of at most k
+        (distance, shape) pairs in place of best_element, every comparison the strict <.  1 <= k <= _lib.KNN_MAX_K.  Shape distance as
+        for nearest_batch (triangles=True needs set_triangles; a point cloud is zero-size boxes with triangles=False).
+        points: (n, 3) in the tree's dtype — a numpy array (HOST) or a torch GPU tensor (DEVICE).
+        returns (shape[n, k], dist[n, k]): rows ascending in dist (a row that holds a NaN need not be sorted), equal distances in leaf
+        pre-order; slots beyond the number of shapes hold NONE and +inf.  numpy in: numpy out, shape as uint32.  torch in: torch tensors on
+        the same device, written by the kernel with no host round trip, shape as torch.int32 — so NONE reads as -1 there."""
+        fn = getattr(_lib.load(), f"bvhgpu_knearest_{self.sfx}")
+        ft = np.float32 if self.sfx == "f32" else np.float64
+        k = int(k)
+        rows = k if 1 <= k <= _lib.KNN_MAX_K else 0       # (out of range: the engine answers INVALID_ARG before it touches a buffer)
+        kind = 1 if triangles else 0
+        if _is_device_tensor(points):
+            import torch
+            if str(points.dtype) != ("torch.float32" if self.sfx == "f32" else "torch.float64"):
+                raise BvhGpuError(_lib.DTYPE_MISMATCH, "point dtype differs from tree dtype")
+            p = points.contiguous()
+            n = p.numel() // 3
+            shape = torch.empty((n, rows), dtype=torch.int32, device=p.device)
+            dist = torch.empty((n, rows), dtype=p.dtype, device=p.device)
+            torch.cuda.current_stream(p.device).synchronize()   # the engine works on its own stream: the points must be there
+            check(fn(self._t, ptr(p.data_ptr()), n, DEVICE, kind, k & 0xFFFFFFFF, ptr(shape.data_ptr()), ptr(dist.data_ptr())), self.ctx._h)
+            return shape, dist
+        if isinstance(points, np.ndarray) and points.dtype != ft:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "point dtype differs from tree dtype")
+        p = np.ascontiguousarray(points, dtype=ft).reshape(-1, 3)
+        shape = np.zeros((len(p), rows), dtype=np.uint32)
+        dist = np.zeros((len(p), rows), dtype=ft)
+        check(fn(self._t, ptr(p), len(p), HOST, kind, k & 0xFFFFFFFF, ptr(shape), ptr(dist)), self.ctx._h)
+        return shape, dist
+
     def nearest_to(self, query, shapes: Sequence, triangles: bool = False):
         """BoundingHierarchy::nearest_to (bounding_hierarchy.rs:262-336): Option<(&Shape, distance)>."""
         s, d = self.nearest_batch([query], triangles)
@@ -999,6 +1031,10 @@ class Bvh(_TreeBase):
         recursive form's (bvh_node.rs:327-374); on exact ties the two reference forms may name different shapes."""
         self.flatten_in_place()
         return super().nearest_batch(points, triangles)
+
+    def knearest_batch(self, points, k: int, triangles: bool = False):
+        self.flatten_in_place()
+        return super().knearest_batch(points, k, triangles)
 
 
 class _FlatView(FlatBvh):

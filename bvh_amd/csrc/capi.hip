@@ -501,6 +501,35 @@ int do_nearest(bvhgpu_tree* t, const T* points, size_t n, int mem, int kind, uin
     });
 }
 
+// bvhgpu_knearest_*: do_nearest's rules with n x k outputs
+template <typename T>
+int do_knearest(bvhgpu_tree* t, const T* points, size_t n, int mem, int kind, uint32_t k, uint32_t* out_shape, T* out_dist) {
+    if (!t) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = t->ctx;
+    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
+    if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from point dtype");
+    if (!t->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    if (k == 0 || k > BVHGPU_KNN_MAX_K) return fail(ctx, BVHGPU_INVALID_ARG, "k must be between 1 and BVHGPU_KNN_MAX_K");
+    if (n && (!points || !out_shape || !out_dist)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
+    if (kind != 0 && kind != 1) return fail(ctx, BVHGPU_INVALID_ARG, "shape kind must be 0 (AABB) or 1 (triangle)");
+    if (kind == 1 && !t->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "triangle distance needs bvhgpu_tree_set_triangles first");
+    if (n >= 0xFFFFFFFFull || n * (size_t)k >= 0x100000000ull) return fail(ctx, BVHGPU_OVERFLOW, "too many results (points x k) in one call");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        const T* pd = points; uint32_t* sd = out_shape; T* dd = out_dist;
+        const size_t pb = n * 3 * sizeof(T), sb = n * k * 4, db = n * k * sizeof(T);
+        if (mem == BVHGPU_HOST) {
+            ctx->upload.reserve(pb + sb + db + 64);
+            char* base = ctx->upload.as<char>();
+            if (pb) BVH_HIP(hipMemcpyAsync(base, points, pb, hipMemcpyHostToDevice, ctx->stream));
+            pd = reinterpret_cast<const T*>(base); dd = reinterpret_cast<T*>(base + pb); sd = reinterpret_cast<uint32_t*>(base + pb + db);
+        }
+        knearest_batch<T>(t, pd, n, kind, k, sd, dd);
+        if (mem == BVHGPU_HOST) { copy_out(ctx, out_dist, dd, db, BVHGPU_HOST); copy_out(ctx, out_shape, sd, sb, BVHGPU_HOST); }
+        else BVH_HIP(hipStreamSynchronize(ctx->stream));   // the rows are complete when the call returns, whichever stream reads them next
+        return (int)BVHGPU_OK;
+    });
+}
 
 // ---- host-resident batches (ABI 7): bvhgpu_traverse_host_* / bvhgpu_build_traverse_host_* -------------------------------------------
 // What GpuBvh::traverse_batch of the Rust shim costs a caller whose rays live in host memory and who wants the hit lists back there is a
@@ -1215,6 +1244,12 @@ int bvhgpu_nearest_f32(bvhgpu_tree* t, const float* points, size_t n, int mem, i
 }
 int bvhgpu_nearest_f64(bvhgpu_tree* t, const double* points, size_t n, int mem, int kind, uint32_t* out_shape, double* out_dist) {
     return do_nearest<double>(t, points, n, mem, kind, out_shape, out_dist);
+}
+int bvhgpu_knearest_f32(bvhgpu_tree* t, const float* points, size_t n, int mem, int kind, uint32_t k, uint32_t* out_shape, float* out_dist) {
+    return do_knearest<float>(t, points, n, mem, kind, k, out_shape, out_dist);
+}
+int bvhgpu_knearest_f64(bvhgpu_tree* t, const double* points, size_t n, int mem, int kind, uint32_t k, uint32_t* out_shape, double* out_dist) {
+    return do_knearest<double>(t, points, n, mem, kind, k, out_shape, out_dist);
 }
 int bvhgpu_ray_triangle_pairs_f32(bvhgpu_ctx* ctx, const bvhgpu_ray_f32* rays, const float* tris, size_t n, int mem, float* out) {
     return do_pairs<float>(ctx, rays, tris, n, mem, out);

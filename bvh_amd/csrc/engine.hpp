@@ -296,6 +296,9 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
 bool traverse_check(bvhgpu_hits* h);   // after a stream synchronise: false = enqueue again
 template <typename T>
 void nearest_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint32_t* out_shape_dev, T* out_dist_dev);
+// knn.hip: the k nearest shapes per point (bvhgpu_knearest_*); out_*: n x k, an empty hierarchy fills them with padding
+template <typename T>
+void knearest_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint32_t k, uint32_t* out_shape_dev, T* out_dist_dev);
 template <typename T>
 void ray_triangle_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays_dev, const T* tris_dev, size_t n, T* out_dev);
 template <typename T>

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define BVHGPU_ABI_VERSION 7 /* 7: bvhgpu_host_alloc/free/register/unregister, bvhgpu_traverse_host_*, bvhgpu_build_traverse_host_*, bvhgpu_traverse_host_indices, bvhgpu_query_f32/_f64 + BVHGPU_QUERY_AABB/_POINT/_BALL, bvhgpu_traverse_any_f32/_f64 + bvhgpu_hits_fetch_any, BVHGPU_TUNE_COUNT 23 (slots 17 = HOST_CHUNKS, 18 = WIDE_MIN_RAYS_PER_WG, 19 = HOST_ZERO_COPY, 20 = BUILD_LEVEL_TILE, 21 = FLATTEN_INLINE, 22 = QUERY_VARIANT).  6: BVHGPU_TUNE_COUNT 17 (slots 15 = FLATTEN_LAZY, 16 = BUILD_LEVEL_PERSIST), bvhgpu_hits_walk_kernel.  5: bvhgpu_rccl_info.  4: BVHGPU_TUNE_COUNT 15 (slot 14 = WIDE_F64_GUIDE), bvhgpu_hits_walk_info.  3: BVHGPU_REBROADCAST, broadcast status header, scene blob BVH6 (exact_only), BVHGPU_TUNE_COUNT 14 (slots 11 = WIDE_EARLY_ITEMS, 12 = WIDE_STAGE_SHIFT, 13 = WIDE_REC8), BVHGPU_TRAVERSE_RAYS_READY, bvhgpu_device_alloc/free/copy */
+#define BVHGPU_ABI_VERSION 7 /* 7: bvhgpu_host_alloc/free/register/unregister, bvhgpu_traverse_host_*, bvhgpu_build_traverse_host_*, bvhgpu_traverse_host_indices, bvhgpu_query_f32/_f64 + BVHGPU_QUERY_AABB/_POINT/_BALL, bvhgpu_traverse_any_f32/_f64 + bvhgpu_hits_fetch_any, bvhgpu_knearest_f32/_f64 + BVHGPU_KNN_MAX_K, BVHGPU_TUNE_COUNT 23 (slots 17 = HOST_CHUNKS, 18 = WIDE_MIN_RAYS_PER_WG, 19 = HOST_ZERO_COPY, 20 = BUILD_LEVEL_TILE, 21 = FLATTEN_INLINE, 22 = QUERY_VARIANT).  6: BVHGPU_TUNE_COUNT 17 (slots 15 = FLATTEN_LAZY, 16 = BUILD_LEVEL_PERSIST), bvhgpu_hits_walk_kernel.  5: bvhgpu_rccl_info.  4: BVHGPU_TUNE_COUNT 15 (slot 14 = WIDE_F64_GUIDE), bvhgpu_hits_walk_info.  3: BVHGPU_REBROADCAST, broadcast status header, scene blob BVH6 (exact_only), BVHGPU_TUNE_COUNT 14 (slots 11 = WIDE_EARLY_ITEMS, 12 = WIDE_STAGE_SHIFT, 13 = WIDE_REC8), BVHGPU_TRAVERSE_RAYS_READY, bvhgpu_device_alloc/free/copy */
 #define BVHGPU_NONE 0xFFFFFFFFu /* u32::MAX marker (flat_bvh.rs:51-53, :124, :137) */
 
 typedef enum {
@@ -287,6 +287,30 @@ int bvhgpu_gen_rays_f64(bvhgpu_ctx *ctx, uint64_t first, size_t n, const float b
  * empty hierarchy), out_dist[i] = the distance (not squared, :561).  `mem` applies to all three buffers. ---- */
 int bvhgpu_nearest_f32(bvhgpu_tree *tree, const float *points, size_t n, int mem, int kind, uint32_t *out_shape, float *out_dist);
 int bvhgpu_nearest_f64(bvhgpu_tree *tree, const double *points, size_t n, int mem, int kind, uint32_t *out_shape, double *out_dist);
+
+/* ---- k nearest shapes per point (ABI 7).  The reference has no such query; the engine defines it as the smallest change to the loop of
+ * nearest_to over the FlatNode array (flat_bvh.rs:524-558): `best_element` becomes a list L of at most k pairs (dist2, shape).
+ *   full = len(L) == k;  bound = L[last].dist2
+ *   non-leaf entry (:546-556): md = node.aabb.min_distance_squared(query); go to entry_index iff !full || md < bound, else to exit_index
+ *   leaf entry (:533-544): d = shape.distance_squared(query); accept iff !full || d < bound.  On accept: if full, drop L[last]; insert
+ *     (d, shape) in front of the first element e with d < e.dist2, or at the end if there is none.  Then exit_index.
+ * All comparisons are the strict < of the scalar type.  So a NaN distance is accepted only while the list is not full, goes behind
+ * everything the list holds at that moment, and once it is L[last] of a full list nothing replaces it (what nearest_to does with a NaN
+ * best_dist).  Entries accepted later that are not smaller than anything in front of the NaN land behind it: a row that holds a NaN
+ * need not be sorted.  Rows without a NaN are ascending, and among equal distances the shape met first (leaf pre-order) comes first.
+ * Output row i: out_shape[i*k + j] = L[j].shape, out_dist[i*k + j] = sqrt(L[j].dist2) (:561) for j < len(L); the remaining k - len(L)
+ * slots (fewer than k shapes, an empty hierarchy) are PADDING: shape BVHGPU_NONE, distance +inf.  (bvhgpu_nearest_* writes distance 0
+ * for an empty hierarchy; a padded slot here is +inf so that a NaN-free row stays ascending.)  With k = 1 a row is bit for bit what
+ * bvhgpu_nearest_* returns, except that distance of the empty hierarchy.
+ * kind as for bvhgpu_nearest_*: 0 = the shape's own Aabb::min_distance_squared (a point cloud is kind 0 on zero-size boxes), 1 = closest
+ * point on the triangle (needs bvhgpu_tree_set_triangles).  1 <= k <= BVHGPU_KNN_MAX_K, else BVHGPU_INVALID_ARG; n * k must stay below
+ * 2^32 (BVHGPU_OVERFLOW).  `mem` applies to all three buffers; n = 0 is fine.  The tree must be flattened.  The call
+ * returns when the rows are complete (BVHGPU_DEVICE too). ---- */
+#define BVHGPU_KNN_MAX_K 64u /* the lists of a 64-lane workgroup live in LDS: 64 x 64 x (8 + 4) bytes = 48 KB in f64 */
+int bvhgpu_knearest_f32(bvhgpu_tree *tree, const float *points, size_t n, int mem, int kind, uint32_t k,
+                        uint32_t *out_shape /* n x k */, float *out_dist /* n x k */);
+int bvhgpu_knearest_f64(bvhgpu_tree *tree, const double *points, size_t n, int mem, int kind, uint32_t k,
+                        uint32_t *out_shape /* n x k */, double *out_dist /* n x k */);
 
 /* Ray::intersects_triangle (ray_impl.rs:154-213) for n independent pairs: ray i against triangle i
  * (tris: n x [a xyz, b xyz, c xyz]); out: n x {distance,u,v}.  `mem` applies to all three buffers. */

@@ -5,6 +5,7 @@ use core::ffi::{c_char, c_int, c_uint, c_void};
 
 pub const BVHGPU_ABI_VERSION: c_int = 7;
 pub const BVHGPU_NONE: u32 = u32::MAX; // flat_bvh.rs:51-53
+pub const BVHGPU_KNN_MAX_K: u32 = 64; // largest k of bvhgpu_knearest_*
 
 // bvhgpu_status
 pub const BVHGPU_OK: c_int = 0;
@@ -145,6 +146,9 @@ extern "C" {
     // nearest_to (flat_bvh.rs:513-562) and Ray::intersects_triangle pairs (ray_impl.rs:154-213)
     pub fn bvhgpu_nearest_f32(t: *mut bvhgpu_tree, points: *const f32, n: usize, mem: c_int, kind: c_int, out_shape: *mut u32, out_dist: *mut f32) -> c_int;
     pub fn bvhgpu_nearest_f64(t: *mut bvhgpu_tree, points: *const f64, n: usize, mem: c_int, kind: c_int, out_shape: *mut u32, out_dist: *mut f64) -> c_int;
+    // the k nearest shapes per point (out_*: n x k; padding = BVHGPU_NONE / +inf; 1 <= k <= BVHGPU_KNN_MAX_K)
+    pub fn bvhgpu_knearest_f32(t: *mut bvhgpu_tree, points: *const f32, n: usize, mem: c_int, kind: c_int, k: u32, out_shape: *mut u32, out_dist: *mut f32) -> c_int;
+    pub fn bvhgpu_knearest_f64(t: *mut bvhgpu_tree, points: *const f64, n: usize, mem: c_int, kind: c_int, k: u32, out_shape: *mut u32, out_dist: *mut f64) -> c_int;
     pub fn bvhgpu_ray_triangle_pairs_f32(ctx: *mut bvhgpu_ctx, rays: *const bvhgpu_ray_f32, tris: *const f32, n: usize, mem: c_int, out: *mut f32) -> c_int;
     pub fn bvhgpu_ray_triangle_pairs_f64(ctx: *mut bvhgpu_ctx, rays: *const bvhgpu_ray_f64, tris: *const f64, n: usize, mem: c_int, out: *mut f64) -> c_int;
     // traverse: FlatBvh::traverse (flat_bvh.rs:396-431) for a batch → CSR

@@ -90,6 +90,8 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
     unsafe fn query(t: *mut ffi::bvhgpu_tree, kind: c_int, queries: *const Self, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
     #[allow(clippy::too_many_arguments)]
     unsafe fn traverse_any(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn knearest(t: *mut ffi::bvhgpu_tree, points: *const Self, n: usize, mem: c_int, kind: c_int, k: u32, out_shape: *mut u32, out_dist: *mut Self) -> c_int;
 
     fn node_to_crate(raw: &Self::Node) -> BvhNode<Self, 3>;
     fn flat_to_crate(raw: &Self::Flat) -> FlatNode<Self, 3>;
@@ -99,7 +101,7 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
 
 macro_rules! impl_gpu_scalar {
     ($t:ty, $dtype:expr, $node:ident, $flat:ident, $ray:ident, $build_flat:ident, $rebuild_flat:ident, $refit:ident, $traverse:ident,
-     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident,
+     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $knearest:ident,
      $flat_ctor:expr) => {
         impl GpuScalar for $t {
             type Node = ffi::$node;
@@ -139,6 +141,9 @@ macro_rules! impl_gpu_scalar {
             unsafe fn traverse_any(t: *mut ffi::bvhgpu_tree, rays: *const ffi::$ray, tmax: *const $t, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int {
                 ffi::$traverse_any(t, rays, tmax, n, mem, flags, hits)
             }
+            unsafe fn knearest(t: *mut ffi::bvhgpu_tree, points: *const $t, n: usize, mem: c_int, kind: c_int, k: u32, out_shape: *mut u32, out_dist: *mut $t) -> c_int {
+                ffi::$knearest(t, points, n, mem, kind, k, out_shape, out_dist)
+            }
             fn node_to_crate(r: &ffi::$node) -> BvhNode<$t, 3> {
                 if r.shape != ffi::BVHGPU_NONE {
                     BvhNode::Leaf { parent_index: r.parent as usize, shape_index: r.shape as usize }
@@ -177,11 +182,11 @@ macro_rules! impl_gpu_scalar {
 }
 impl_gpu_scalar!(f32, ffi::BVHGPU_F32, bvhgpu_node_f32, bvhgpu_flat_f32, bvhgpu_ray_f32, bvhgpu_build_flat_f32, bvhgpu_rebuild_flat_f32,
                  bvhgpu_refit_f32, bvhgpu_traverse_f32, bvhgpu_tree_set_triangles_f32, bvhgpu_tree_from_flat_f32,
-                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32,
+                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_knearest_f32,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f32 { min, max, entry, exit, shape });
 impl_gpu_scalar!(f64, ffi::BVHGPU_F64, bvhgpu_node_f64, bvhgpu_flat_f64, bvhgpu_ray_f64, bvhgpu_build_flat_f64, bvhgpu_rebuild_flat_f64,
                  bvhgpu_refit_f64, bvhgpu_traverse_f64, bvhgpu_tree_set_triangles_f64, bvhgpu_tree_from_flat_f64,
-                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64,
+                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_knearest_f64,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f64 { min, max, entry, exit, shape, _pad: 0 });
 
 fn aabb_to_6<T: GpuScalar>(b: &Aabb<T, 3>) -> [T; 6] {
@@ -464,6 +469,23 @@ impl<T: GpuScalar> GpuBvh<T> {
     /// `traverse_any` reduced to one flag per ray: does segment i hit any triangle
     pub fn occluded(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>) -> Vec<bool> {
         self.traverse_any(rays, tmax).iter().map(|h| h.shape != ffi::BVHGPU_NONE).collect()
+    }
+
+    /// The `k` nearest shapes of every point (`bvhgpu_knearest_*`): the loop of `FlatBvh::nearest_to` (src/flat_bvh.rs:524-558) with a list of
+    /// at most `k` (distance, shape) pairs in place of `best_element`, every comparison the strict `<`.  Returns row-major `points.len() x k`
+    /// arrays: shape indices and distances (not squared), ascending per row (a row that holds a NaN distance need not be sorted), equal
+    /// distances in leaf pre-order; slots beyond the number of shapes hold `u32::MAX` and `+inf`.  `triangles`: closest point on the
+    /// triangle (needs `set_triangles`) instead of the shape's own AABB.  `1 <= k <= ffi::BVHGPU_KNN_MAX_K`; `k = 1` is `nearest_to` per point.
+    pub fn nearest_k(&self, points: &[[T; 3]], k: usize, triangles: bool) -> (Vec<u32>, Vec<T>) {
+        let k32 = u32::try_from(k).unwrap_or(u32::MAX);   // (out of range: the engine answers BVHGPU_INVALID_ARG and `check` panics with its message)
+        let slots = if (1..=ffi::BVHGPU_KNN_MAX_K).contains(&k32) { points.len() * k } else { 0 };
+        let mut shape = vec![0u32; slots];
+        let mut dist = vec![T::default(); slots];
+        unsafe {
+            check(self.ctx, T::knearest(self.tree, points.as_ptr().cast(), points.len(), ffi::BVHGPU_HOST, triangles as c_int, k32,
+                                        shape.as_mut_ptr(), dist.as_mut_ptr()));
+        }
+        (shape, dist)
     }
 
     /// Build again from new AABBs into the same device buffers (a frame loop: no allocation in the steady state)

@@ -126,6 +126,8 @@ SYMBOLS = [
     ("bvhgpu_nearest_f64", _i, [_vp, _vp, _sz, _i, _i, _vp, _vp]),
     ("bvhgpu_knearest_f32", _i, [_vp, _vp, _sz, _i, _i, C.c_uint32, _vp, _vp]),
     ("bvhgpu_knearest_f64", _i, [_vp, _vp, _sz, _i, _i, C.c_uint32, _vp, _vp]),
+    ("bvhgpu_knearest_tree_f32", _i, [_vp, _vp, _sz, _i, _i, C.c_uint32, _vp, _vp, _vp]),
+    ("bvhgpu_knearest_tree_f64", _i, [_vp, _vp, _sz, _i, _i, C.c_uint32, _vp, _vp, _vp]),
     ("bvhgpu_ray_triangle_pairs_f32", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("bvhgpu_ray_triangle_pairs_f64", _i, [_vp, _vp, _vp, _sz, _i, _vp]),
     ("bvhgpu_traverse_f32", _i, [_vp, _vp, _sz, _i, _u, _pp]),

@@ -701,6 +701,64 @@ class _TreeBase:
         check(fn(self._t, ptr(p), len(p), HOST, kind, k & 0xFFFFFFFF, ptr(shape), ptr(dist)), self.ctx._h)
         return shape, dist
 
+    def knearest_tree_batch(self, points, k: int, triangles: bool = False, max_dist=None):
+        """bvhgpu_knearest_tree_*: the rows of knearest_batch found nearest child first — BvhNode::nearest_to_recursive (bvh_node.rs:327-374,
+        what Bvh::nearest_to calls) over the BvhNode array with the list of at most k (distance, shape) pairs in place of best_candidate.
+        With k = 1 and no max_dist a row is what Bvh::nearest_to returns.  Equal distances stay in the order this walk meets them, which is
+        not leaf pre-order: knearest_batch may order ties differently and pick differently among ties at the k-th distance.
+        max_dist: None, a scalar (the same limit for every point) or n values in the points' memory — a numpy array for numpy points, a torch
+        GPU tensor for tensor points.  Nothing farther than max_dist[i] enters row i (dist2 <= max_dist[i]^2); a negative or NaN limit gives
+        a row of padding.  The tree must have been built here (a Bvh or its flatten(); no flatten is needed): an uploaded FlatBvh or an
+        imported scene has no BvhNode array and raises INVALID_ARG.  points / returns: as knearest_batch."""
+        fn = getattr(_lib.load(), f"bvhgpu_knearest_tree_{self.sfx}")
+        ft = np.float32 if self.sfx == "f32" else np.float64
+        k = int(k)
+        rows = k if 1 <= k <= _lib.KNN_MAX_K else 0       # (out of range: the engine answers INVALID_ARG before it touches a buffer)
+        kind = 1 if triangles else 0
+        scalar = max_dist is not None and not _is_device_tensor(max_dist) and np.ndim(max_dist) == 0
+        if _is_device_tensor(points):
+            import torch
+            if str(points.dtype) != ("torch.float32" if self.sfx == "f32" else "torch.float64"):
+                raise BvhGpuError(_lib.DTYPE_MISMATCH, "point dtype differs from tree dtype")
+            p = points.contiguous()
+            n = p.numel() // 3
+            m, mp = None, None
+            if scalar:
+                m = torch.full((n,), float(max_dist), dtype=p.dtype, device=p.device)
+            elif max_dist is not None:
+                if not _is_device_tensor(max_dist):
+                    raise BvhGpuError(_lib.INVALID_ARG, "max_dist is in host memory but the points are in HBM")
+                if max_dist.dtype != p.dtype:
+                    raise BvhGpuError(_lib.DTYPE_MISMATCH, "max_dist dtype differs from tree dtype")
+                m = max_dist.contiguous()
+            if m is not None:
+                if m.numel() != n:
+                    raise BvhGpuError(_lib.INVALID_ARG, f"max_dist has {m.numel()} values for {n} points")
+                mp = ptr(m.data_ptr())
+            shape = torch.empty((n, rows), dtype=torch.int32, device=p.device)
+            dist = torch.empty((n, rows), dtype=p.dtype, device=p.device)
+            torch.cuda.current_stream(p.device).synchronize()   # the engine works on its own stream: the points must be there
+            check(fn(self._t, ptr(p.data_ptr()), n, DEVICE, kind, k & 0xFFFFFFFF, mp, ptr(shape.data_ptr()), ptr(dist.data_ptr())), self.ctx._h)
+            return shape, dist
+        if isinstance(points, np.ndarray) and points.dtype != ft:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "point dtype differs from tree dtype")
+        p = np.ascontiguousarray(points, dtype=ft).reshape(-1, 3)
+        m = None
+        if scalar:
+            m = np.full(len(p), max_dist, dtype=ft)
+        elif max_dist is not None:
+            if _is_device_tensor(max_dist):
+                raise BvhGpuError(_lib.INVALID_ARG, "max_dist is a GPU tensor but the points are in host memory")
+            if isinstance(max_dist, np.ndarray) and max_dist.dtype != ft:
+                raise BvhGpuError(_lib.DTYPE_MISMATCH, "max_dist dtype differs from tree dtype")
+            m = np.ascontiguousarray(max_dist, dtype=ft).reshape(-1)
+        if m is not None and m.size != len(p):
+            raise BvhGpuError(_lib.INVALID_ARG, f"max_dist has {m.size} values for {len(p)} points")
+        shape = np.zeros((len(p), rows), dtype=np.uint32)
+        dist = np.zeros((len(p), rows), dtype=ft)
+        check(fn(self._t, ptr(p), len(p), HOST, kind, k & 0xFFFFFFFF, ptr(m), ptr(shape), ptr(dist)), self.ctx._h)
+        return shape, dist
+
     def nearest_to(self, query, shapes: Sequence, triangles: bool = False):
         """BoundingHierarchy::nearest_to (bounding_hierarchy.rs:262-336): Option<(&Shape, distance)>."""
         s, d = self.nearest_batch([query], triangles)

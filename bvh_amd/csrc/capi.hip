@@ -531,6 +531,39 @@ int do_knearest(bvhgpu_tree* t, const T* points, size_t n, int mem, int kind, ui
     });
 }
 
+// bvhgpu_knearest_tree_*: do_knearest's rules, except that the walk reads the BvhNode array (a tree built here, flattened or not) and takes
+// an optional limit per point
+template <typename T>
+int do_knearest_tree(bvhgpu_tree* t, const T* points, size_t n, int mem, int kind, uint32_t k, const T* max_dist, uint32_t* out_shape, T* out_dist) {
+    if (!t) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = t->ctx;
+    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
+    if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from point dtype");
+    if (!t->built) return fail(ctx, BVHGPU_INVALID_ARG, "the nearest-first descent needs a tree that was built here (uploaded and imported trees carry no BvhNode array)");
+    if (k == 0 || k > BVHGPU_KNN_MAX_K) return fail(ctx, BVHGPU_INVALID_ARG, "k must be between 1 and BVHGPU_KNN_MAX_K");
+    if (n && (!points || !out_shape || !out_dist)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
+    if (kind != 0 && kind != 1) return fail(ctx, BVHGPU_INVALID_ARG, "shape kind must be 0 (AABB) or 1 (triangle)");
+    if (kind == 1 && !t->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "triangle distance needs bvhgpu_tree_set_triangles first");
+    if (n >= 0xFFFFFFFFull || n * (size_t)k >= 0x100000000ull) return fail(ctx, BVHGPU_OVERFLOW, "too many results (points x k) in one call");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        const T* pd = points; const T* md = max_dist; uint32_t* sd = out_shape; T* dd = out_dist;
+        const size_t pb = n * 3 * sizeof(T), mb = max_dist ? n * sizeof(T) : 0, sb = n * k * 4, db = n * k * sizeof(T);
+        if (mem == BVHGPU_HOST) {
+            ctx->upload.reserve(pb + mb + sb + db + 64);
+            char* base = ctx->upload.as<char>();
+            if (pb) BVH_HIP(hipMemcpyAsync(base, points, pb, hipMemcpyHostToDevice, ctx->stream));
+            if (mb) BVH_HIP(hipMemcpyAsync(base + pb, max_dist, mb, hipMemcpyHostToDevice, ctx->stream));
+            pd = reinterpret_cast<const T*>(base); md = max_dist ? reinterpret_cast<const T*>(base + pb) : nullptr;
+            dd = reinterpret_cast<T*>(base + pb + mb); sd = reinterpret_cast<uint32_t*>(base + pb + mb + db);
+        }
+        knearest_tree_batch<T>(t, pd, n, kind, k, md, sd, dd);
+        if (mem == BVHGPU_HOST) { copy_out(ctx, out_dist, dd, db, BVHGPU_HOST); copy_out(ctx, out_shape, sd, sb, BVHGPU_HOST); }
+        else BVH_HIP(hipStreamSynchronize(ctx->stream));   // the rows are complete when the call returns, whichever stream reads them next
+        return (int)BVHGPU_OK;
+    });
+}
+
 // ---- host-resident batches (ABI 7): bvhgpu_traverse_host_* / bvhgpu_build_traverse_host_* -------------------------------------------
 // What GpuBvh::traverse_batch of the Rust shim costs a caller whose rays live in host memory and who wants the hit lists back there is a
 // PCIe problem, not a kernel problem: 1 M rays are 36 MB as Ray structs and 24 MB as origins + directions, the CSR offsets 4 MB.  The
@@ -1250,6 +1283,14 @@ int bvhgpu_knearest_f32(bvhgpu_tree* t, const float* points, size_t n, int mem, 
 }
 int bvhgpu_knearest_f64(bvhgpu_tree* t, const double* points, size_t n, int mem, int kind, uint32_t k, uint32_t* out_shape, double* out_dist) {
     return do_knearest<double>(t, points, n, mem, kind, k, out_shape, out_dist);
+}
+int bvhgpu_knearest_tree_f32(bvhgpu_tree* t, const float* points, size_t n, int mem, int kind, uint32_t k, const float* max_dist,
+                             uint32_t* out_shape, float* out_dist) {
+    return do_knearest_tree<float>(t, points, n, mem, kind, k, max_dist, out_shape, out_dist);
+}
+int bvhgpu_knearest_tree_f64(bvhgpu_tree* t, const double* points, size_t n, int mem, int kind, uint32_t k, const double* max_dist,
+                             uint32_t* out_shape, double* out_dist) {
+    return do_knearest_tree<double>(t, points, n, mem, kind, k, max_dist, out_shape, out_dist);
 }
 int bvhgpu_ray_triangle_pairs_f32(bvhgpu_ctx* ctx, const bvhgpu_ray_f32* rays, const float* tris, size_t n, int mem, float* out) {
     return do_pairs<float>(ctx, rays, tris, n, mem, out);

@@ -299,6 +299,10 @@ void nearest_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint
 // knn.hip: the k nearest shapes per point (bvhgpu_knearest_*); out_*: n x k, an empty hierarchy fills them with padding
 template <typename T>
 void knearest_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint32_t k, uint32_t* out_shape_dev, T* out_dist_dev);
+// knn_tree.hip: the same rows found nearest child first over the BvhNode array (bvhgpu_knearest_tree_*); max_dist_dev: NULL or n limits
+template <typename T>
+void knearest_tree_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint32_t k, const T* max_dist_dev, uint32_t* out_shape_dev,
+                         T* out_dist_dev);
 template <typename T>
 void ray_triangle_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays_dev, const T* tris_dev, size_t n, T* out_dev);
 template <typename T>

@@ -312,6 +312,39 @@ int bvhgpu_knearest_f32(bvhgpu_tree *tree, const float *points, size_t n, int me
 int bvhgpu_knearest_f64(bvhgpu_tree *tree, const double *points, size_t n, int mem, int kind, uint32_t k,
                         uint32_t *out_shape /* n x k */, double *out_dist /* n x k */);
 
+/* ---- the same rows found nearest child first (the "tree form"; bvhgpu_knearest_* above is the "flat form").  Definition:
+ * BvhNode::nearest_to_recursive (bvh_node.rs:327-374, what Bvh::nearest_to calls, bvh_impl.rs:221-238) over the BvhNode array, with the
+ * list L above in place of `best_candidate` and an optional limit per point, m = max_dist[i]:
+ *   full = len(L) == k;  bound = L[last].dist2;  r2 = m * m (one multiplication in T)
+ *   admit(x) = (max_dist == NULL || (m >= 0 && x <= r2)) && (!full || x < bound)
+ *   visit(node), starting at node 0:
+ *     Leaf{shape}: d = shape.distance_squared(p) (kind as above); if admit(d): drop L[last] of a full list and insert (d, shape) in front
+ *       of the first element e with d < e.dist2, or at the end if there is none.
+ *     Node{l, l_aabb, r, r_aabb}: c = [(l, l_aabb.min_distance_squared(p)), (r, r_aabb.min_distance_squared(p))]; if c[0].1 > c[1].1
+ *       swap them (strict >: ties and NaN keep the left child first); then for (idx, cd) in c: if admit(cd): visit(idx) — the second
+ *       test sees the list as the first subtree left it.
+ * Every comparison is the <, > or <= of the scalar type exactly as written; a NaN distance behaves as in the flat form (a row that holds
+ * a NaN need not be sorted).  Rows without a NaN are ascending.  TIES: equal distances stay in the order THIS walk meets them, which is
+ * not leaf pre-order — the flat and the tree form may order equal distances differently, and may pick different shapes among ties at the
+ * k-th distance.
+ * Output row i as for bvhgpu_knearest_*: out_shape[i*k + j] = L[j].shape, out_dist[i*k + j] = sqrt(L[j].dist2) for j < len(L); the other
+ * slots are PADDING: shape BVHGPU_NONE, distance +inf.  An empty hierarchy gives rows of padding.  With k = 1 and max_dist == NULL a row
+ * is bit for bit what Bvh::nearest_to returns (except the empty hierarchy's distance, +inf here).
+ * max_dist: NULL, or n values of the tree's dtype in the points' memory space.  A shape or subtree farther than max_dist[i] is never
+ * admitted (dist2 <= max_dist[i]^2 is the test, so the limit itself is inside); 0 keeps only shapes at distance 0; a negative or NaN
+ * max_dist[i] gives a row of padding; +inf differs from NULL only for NaN distances (NaN <= +inf is false).
+ * Arguments as for bvhgpu_knearest_*: 1 <= k <= BVHGPU_KNN_MAX_K, else BVHGPU_INVALID_ARG; kind 1 needs bvhgpu_tree_set_triangles;
+ * n * k below 2^32 (BVHGPU_OVERFLOW); n = 0 is fine; `mem` applies to all four buffers.  The tree must have been built here
+ * (bvhgpu_build_* / rebuild_*, still building or not): an uploaded FlatBvh, a scene import or a broadcast carries no BvhNode array
+ * and gets BVHGPU_INVALID_ARG.  It need NOT be flattened, as Bvh::nearest_to needs no FlatBvh.  The walk has no depth limit.  The call
+ * returns when the rows are complete (BVHGPU_DEVICE too). ---- */
+int bvhgpu_knearest_tree_f32(bvhgpu_tree *tree, const float *points, size_t n, int mem, int kind, uint32_t k,
+                             const float *max_dist /* NULL, or n values in the points' memory space */,
+                             uint32_t *out_shape /* n x k */, float *out_dist /* n x k */);
+int bvhgpu_knearest_tree_f64(bvhgpu_tree *tree, const double *points, size_t n, int mem, int kind, uint32_t k,
+                             const double *max_dist /* NULL, or n values in the points' memory space */,
+                             uint32_t *out_shape /* n x k */, double *out_dist /* n x k */);
+
 /* Ray::intersects_triangle (ray_impl.rs:154-213) for n independent pairs: ray i against triangle i
  * (tris: n x [a xyz, b xyz, c xyz]); out: n x {distance,u,v}.  `mem` applies to all three buffers. */
 int bvhgpu_ray_triangle_pairs_f32(bvhgpu_ctx *ctx, const bvhgpu_ray_f32 *rays, const float *tris, size_t n, int mem, float *out);

@@ -149,6 +149,8 @@ extern "C" {
     // the k nearest shapes per point (out_*: n x k; padding = BVHGPU_NONE / +inf; 1 <= k <= BVHGPU_KNN_MAX_K)
     pub fn bvhgpu_knearest_f32(t: *mut bvhgpu_tree, points: *const f32, n: usize, mem: c_int, kind: c_int, k: u32, out_shape: *mut u32, out_dist: *mut f32) -> c_int;
     pub fn bvhgpu_knearest_f64(t: *mut bvhgpu_tree, points: *const f64, n: usize, mem: c_int, kind: c_int, k: u32, out_shape: *mut u32, out_dist: *mut f64) -> c_int;
+    pub fn bvhgpu_knearest_tree_f32(t: *mut bvhgpu_tree, points: *const f32, n: usize, mem: c_int, kind: c_int, k: u32, max_dist: *const f32, out_shape: *mut u32, out_dist: *mut f32) -> c_int;
+    pub fn bvhgpu_knearest_tree_f64(t: *mut bvhgpu_tree, points: *const f64, n: usize, mem: c_int, kind: c_int, k: u32, max_dist: *const f64, out_shape: *mut u32, out_dist: *mut f64) -> c_int;
     pub fn bvhgpu_ray_triangle_pairs_f32(ctx: *mut bvhgpu_ctx, rays: *const bvhgpu_ray_f32, tris: *const f32, n: usize, mem: c_int, out: *mut f32) -> c_int;
     pub fn bvhgpu_ray_triangle_pairs_f64(ctx: *mut bvhgpu_ctx, rays: *const bvhgpu_ray_f64, tris: *const f64, n: usize, mem: c_int, out: *mut f64) -> c_int;
     // traverse: FlatBvh::traverse (flat_bvh.rs:396-431) for a batch → CSR

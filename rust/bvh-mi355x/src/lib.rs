@@ -92,6 +92,8 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
     unsafe fn traverse_any(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
     #[allow(clippy::too_many_arguments)]
     unsafe fn knearest(t: *mut ffi::bvhgpu_tree, points: *const Self, n: usize, mem: c_int, kind: c_int, k: u32, out_shape: *mut u32, out_dist: *mut Self) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn knearest_tree(t: *mut ffi::bvhgpu_tree, points: *const Self, n: usize, mem: c_int, kind: c_int, k: u32, max_dist: *const Self, out_shape: *mut u32, out_dist: *mut Self) -> c_int;
 
     fn node_to_crate(raw: &Self::Node) -> BvhNode<Self, 3>;
     fn flat_to_crate(raw: &Self::Flat) -> FlatNode<Self, 3>;
@@ -101,7 +103,7 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
 
 macro_rules! impl_gpu_scalar {
     ($t:ty, $dtype:expr, $node:ident, $flat:ident, $ray:ident, $build_flat:ident, $rebuild_flat:ident, $refit:ident, $traverse:ident,
-     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $knearest:ident,
+     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $knearest:ident, $knearest_tree:ident,
      $flat_ctor:expr) => {
         impl GpuScalar for $t {
             type Node = ffi::$node;
@@ -144,6 +146,9 @@ macro_rules! impl_gpu_scalar {
             unsafe fn knearest(t: *mut ffi::bvhgpu_tree, points: *const $t, n: usize, mem: c_int, kind: c_int, k: u32, out_shape: *mut u32, out_dist: *mut $t) -> c_int {
                 ffi::$knearest(t, points, n, mem, kind, k, out_shape, out_dist)
             }
+            unsafe fn knearest_tree(t: *mut ffi::bvhgpu_tree, points: *const $t, n: usize, mem: c_int, kind: c_int, k: u32, max_dist: *const $t, out_shape: *mut u32, out_dist: *mut $t) -> c_int {
+                ffi::$knearest_tree(t, points, n, mem, kind, k, max_dist, out_shape, out_dist)
+            }
             fn node_to_crate(r: &ffi::$node) -> BvhNode<$t, 3> {
                 if r.shape != ffi::BVHGPU_NONE {
                     BvhNode::Leaf { parent_index: r.parent as usize, shape_index: r.shape as usize }
@@ -182,11 +187,11 @@ macro_rules! impl_gpu_scalar {
 }
 impl_gpu_scalar!(f32, ffi::BVHGPU_F32, bvhgpu_node_f32, bvhgpu_flat_f32, bvhgpu_ray_f32, bvhgpu_build_flat_f32, bvhgpu_rebuild_flat_f32,
                  bvhgpu_refit_f32, bvhgpu_traverse_f32, bvhgpu_tree_set_triangles_f32, bvhgpu_tree_from_flat_f32,
-                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_knearest_f32,
+                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_knearest_f32, bvhgpu_knearest_tree_f32,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f32 { min, max, entry, exit, shape });
 impl_gpu_scalar!(f64, ffi::BVHGPU_F64, bvhgpu_node_f64, bvhgpu_flat_f64, bvhgpu_ray_f64, bvhgpu_build_flat_f64, bvhgpu_rebuild_flat_f64,
                  bvhgpu_refit_f64, bvhgpu_traverse_f64, bvhgpu_tree_set_triangles_f64, bvhgpu_tree_from_flat_f64,
-                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_knearest_f64,
+                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_knearest_f64, bvhgpu_knearest_tree_f64,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f64 { min, max, entry, exit, shape, _pad: 0 });
 
 fn aabb_to_6<T: GpuScalar>(b: &Aabb<T, 3>) -> [T; 6] {
@@ -484,6 +489,26 @@ impl<T: GpuScalar> GpuBvh<T> {
         unsafe {
             check(self.ctx, T::knearest(self.tree, points.as_ptr().cast(), points.len(), ffi::BVHGPU_HOST, triangles as c_int, k32,
                                         shape.as_mut_ptr(), dist.as_mut_ptr()));
+        }
+        (shape, dist)
+    }
+
+    /// The rows of `nearest_k` found nearest child first (`bvhgpu_knearest_tree_*`): `BvhNode::nearest_to_recursive` (src/bvh/bvh_node.rs:327-374,
+    /// what `Bvh::nearest_to` calls) over the BvhNode array with the list of at most `k` pairs in place of `best_candidate`.  With `k = 1` and
+    /// no `max_dist` a row is what `Bvh::nearest_to` returns.  Equal distances stay in the order this walk meets them, which is not leaf
+    /// pre-order: `nearest_k` may order ties differently and pick differently among ties at the k-th distance.  `max_dist`: one limit per
+    /// point — nothing farther enters its row (`dist2 <= max_dist[i]^2`); a negative or NaN limit gives a row of padding.
+    pub fn nearest_k_tree(&self, points: &[[T; 3]], k: usize, triangles: bool, max_dist: Option<&[T]>) -> (Vec<u32>, Vec<T>) {
+        if let Some(m) = max_dist {
+            assert_eq!(m.len(), points.len(), "max_dist needs one value per point");
+        }
+        let k32 = u32::try_from(k).unwrap_or(u32::MAX);   // (out of range: the engine answers BVHGPU_INVALID_ARG and `check` panics with its message)
+        let slots = if (1..=ffi::BVHGPU_KNN_MAX_K).contains(&k32) { points.len() * k } else { 0 };
+        let mut shape = vec![0u32; slots];
+        let mut dist = vec![T::default(); slots];
+        unsafe {
+            check(self.ctx, T::knearest_tree(self.tree, points.as_ptr().cast(), points.len(), ffi::BVHGPU_HOST, triangles as c_int, k32,
+                                             max_dist.map_or(core::ptr::null(), |m| m.as_ptr()), shape.as_mut_ptr(), dist.as_mut_ptr()));
         }
         (shape, dist)
     }

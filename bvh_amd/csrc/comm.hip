@@ -18,7 +18,7 @@
 //    leaves in HBM.  The peers copy the received header to pinned memory behind the receive and look at it when their
 //    tree is first waited for (bvhgpu_tree_wait / bvhgpu_hits_wait / any entry point that inspects the tree).
 //  * What the header carries besides the sizes: `exact_only` (a split without SAH winner: the receiver must not walk the
-//    tree wide, traverse.hip) and "the optimistic build was not complete" (unbalanced tree on a first build) — then the
+//    tree wide, walk_wide.hip) and "the optimistic build was not complete" (unbalanced tree on a first build) — then the
 //    root's wait and the peers' waits all return BVHGPU_REBROADCAST and every rank repeats the call.
 //  * RCCL is loaded on first use (dlopen): a single-GPU consumer of libbvh_mi355x.so does not need librccl at all, and a
 //    process that already holds a copy (PyTorch bundles one) shares it.  No librccl → BVHGPU_RCCL_ERROR.

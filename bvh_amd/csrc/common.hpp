@@ -126,7 +126,7 @@ static_assert(sizeof(TravNode<double>) == 64, "trav f64");
 // second one absent.  SoA over the four slots, one 16-byte chunk per coordinate, so a lane fetches a node with 7 (f32) /
 // 13 (f64) 16-byte loads from one 128- / 256-byte line.  ref: a leaf holds its shape index (< 2^31); an inner grandchild
 // holds WIDE_INNER | its tree node index (it has a wide node of its own); an absent slot holds NONE and a NaN box (which
-// fails every slab test).  Why skipping b's children is exact: see traverse.hip.
+// fails every slab test).  Why skipping b's children is exact: see walk_wide.hip.
 // ------------------------------------------------------------------------------------------------
 template <typename T> struct WideNode;
 template <> struct __attribute__((aligned(128))) WideNode<float> {

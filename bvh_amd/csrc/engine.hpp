@@ -1,5 +1,5 @@
 // engine.hpp — host-side objects behind the opaque C handles, and the per-phase entry points
-// implemented in build.hip / flatten.hip / traverse.hip.
+// implemented in build.hip / flatten.hip / traverse.hip and the files traverse.hip hands a batch to (walk.hpp).
 #pragma once
 
 #include <string>
@@ -93,7 +93,7 @@ struct bvhgpu_ctx {
     void* pinned = nullptr;   // 4 KiB pinned host page for tiny D2H reads
     bvhgpu::HostBatch* host = nullptr;   // state of bvhgpu_traverse_host_* (capi.hip), made on first use
     hipStream_t side = nullptr;   // second stream of the ctx (created on first use): work that may run BESIDE the main chain — the
-                                  // item filter of a batch whose tree is still building (traverse.hip k_wide_items)
+                                  // item filter of a batch whose tree is still building (walk_wide.hip k_wide_items)
 };
 
 struct bvhgpu_tree {
@@ -148,11 +148,11 @@ struct bvhgpu_tree {
     bvhgpu::DevBuf shape_node;  // n * u32
     bvhgpu::DevBuf flat;        // n_flat * Flat     (reference layout, for export/parity)
     bvhgpu::DevBuf trav;        // n_trav * TravNode (engine layout, what traversal reads)
-    bvhgpu::DevBuf wide;        // n_nodes * WideNode: the four grandchildren of every inner node (wide walk, traverse.hip)
+    bvhgpu::DevBuf wide;        // n_nodes * WideNode: the four grandchildren of every inner node (wide walk, walk_wide.hip)
     bvhgpu::DevBuf wslot_node;  // WideCfg::SLOTS * u32: tree node held in 4-ary heap slot s of the LDS-resident top (NONE = none)
     bool has_wide = false;
     // f64 trees: the same wide nodes as f32 boxes that CONTAIN the f64 ones (rounded outward and grown by GUIDE_GROW x the scene's largest
-    // |coordinate|): index batches are walked over these with f32 rays and only leaf candidates are tested in f64 (traverse.hip "guide walk")
+    // |coordinate|): index batches are walked over these with f32 rays and only leaf candidates are tested in f64 (walk_wide.hip "guide walk")
     bvhgpu::DevBuf wide_guide;  // n_nodes * WideNode<float>
     bvhgpu::DevBuf guide_info;  // float[4]: [0] = S, the largest |coordinate| of the root's child boxes
     bool has_guide = false;
@@ -192,7 +192,7 @@ struct bvhgpu_hits {
     bvhgpu::DevBuf isect;    // total * 3 T: Intersection{distance,u,v} per candidate (TRIANGLES)
     bvhgpu::DevBuf closest;  // n_rays * 3 T (CLOSEST)
     bvhgpu::DevBuf closest_prim;  // n_rays u32
-    bvhgpu::DevBuf closest_key;   // n_rays u64: CLOSEST batches walked as items (traverse.hip WalkOut::closest_key), all-ones between batches
+    bvhgpu::DevBuf closest_key;   // n_rays u64: CLOSEST batches walked as items (walk.hpp WalkOut::closest_key), all-ones between batches
     bool ckey_clean = false;
     bvhgpu::DevBuf blocksums;
     bvhgpu::DevBuf scan_sums;    // wide walk: two sets of hits per scan block (k_scan_final's input instead of a reduce pass), kept zero
@@ -201,10 +201,10 @@ struct bvhgpu_hits {
     uint32_t heap_cap = 48;  // ... entries per lane (doubles when a batch overflows it)
     size_t pool_cap = 0;
     size_t idx_cap = 0;      // capacity of indices[] in entries (>= pool_cap; staged output sizes it by the hit total)
-    bvhgpu::DevBuf raybuf;   // staged output of the wide walk: 2^shift shape indices per ray (traverse.hip WalkOut::raybuf)
+    bvhgpu::DevBuf raybuf;   // staged output of the wide walk: 2^shift shape indices per ray (walk.hpp WalkOut::raybuf)
     bool pend_staged = false;
     std::string walk_kernel;  // the kernel the last batch was handed to, as rocprofv3 spells it (bvhgpu_hits_walk_kernel)
-    bool pend_rec8 = false;   // the batch in flight writes pair records (8 bytes per hit: traverse.hip report_pair)
+    bool pend_rec8 = false;   // the batch in flight writes pair records (8 bytes per hit: walk.hpp report_pair)
     bool pend_guide = false, no_guide = false; // guide walk in the batch in flight / the batch is being replayed in f64 (a ray was out of the guide's range)
     uint32_t guide_backoff = 0, guide_skip = 0; // f64 index batches that skip the guide after such a replay: 1, 2, 4 … 64 on consecutive failures / still to skip
     bool ctr_clean = false;  // the counters were zeroed behind the previous call's readback
@@ -241,7 +241,7 @@ struct bvhgpu_hits {
     // any-hit batches (bvhgpu_traverse_any_*): per-ray segment ends in HBM (the caller's, or `tmaxbuf`; NULL = +inf), read by every replay
     const void* pend_tmax = nullptr;
     bvhgpu::DevBuf tmaxbuf;              // HOST tmax staged here
-    bvhgpu::DevBuf any_key;              // n_rays u32: any-hit batches walked as items (traverse.hip WalkOut::any_key), all-ones between batches
+    bvhgpu::DevBuf any_key;              // n_rays u32: any-hit batches walked as items (walk.hpp WalkOut::any_key), all-ones between batches
     bool akey_clean = false;
     bvhgpu::DevBuf any_part;             // per workgroup of k_any_resolve: its occluded rays (k_any_publish adds them up)
     uint32_t replays = 0;               // times bvhgpu_hits_wait had to enqueue the asynchronous batch again
@@ -281,6 +281,7 @@ void recv_finalize(bvhgpu_tree* t);
 void settle_waiters(bvhgpu_tree* t);
 // query.hip: AABB / point / ball query batches (bvhgpu_query_*).  query_batch runs the batch to completion like traverse_batch;
 // launch_query is the walk launch of traverse_enqueue for a query batch (h->pend_kind != 0), which provides the CSR plumbing
+// (the launches for ray batches — launch_binary, launch_ordered, launch_wide_walk — and csr_enqueue are declared in walk.hpp)
 template <typename T> void query_batch(bvhgpu_tree* t, int kind, const T* queries_dev, size_t n, bvhgpu_hits* h);
 template <typename T> struct WalkOut;
 template <typename T> void launch_query(bvhgpu_tree* t, size_t n, const WalkOut<T>& w, bvhgpu_hits* h, uint32_t* ovf_flag);
@@ -294,6 +295,7 @@ template <typename T>
 void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, size_t n_rays, unsigned flags,
                       bvhgpu_hits* h);
 bool traverse_check(bvhgpu_hits* h);   // after a stream synchronise: false = enqueue again
+// nearest.hip
 template <typename T>
 void nearest_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint32_t* out_shape_dev, T* out_dist_dev);
 // knn.hip: the k nearest shapes per point (bvhgpu_knearest_*); out_*: n x k, an empty hierarchy fills them with padding
@@ -303,6 +305,7 @@ void knearest_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uin
 template <typename T>
 void knearest_tree_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint32_t k, const T* max_dist_dev, uint32_t* out_shape_dev,
                          T* out_dist_dev);
+// rays.hip
 template <typename T>
 void ray_triangle_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays_dev, const T* tris_dev, size_t n, T* out_dev);
 template <typename T>

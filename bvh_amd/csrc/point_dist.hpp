@@ -1,5 +1,5 @@
-// point_dist.hpp — the two shape distances of the point queries (k_nearest in traverse.hip, k_knearest in knn.hip), moved unchanged
-// out of traverse.hip so that both walks compute the same bits:
+// point_dist.hpp — the two shape distances of the point queries (k_nearest in nearest.hip, k_knearest in knn.hip), moved unchanged
+// out of the file k_nearest used to share with the ray walks so that both walks compute the same bits:
 // Shape distance = <Triangle as PointDistance>::distance_squared (testbase.rs:367-443: Embree's closest point on a
 // triangle with degenerate-triangle guards) or the shape's own Aabb::min_distance_squared (UnitBox,
 // testbase.rs:101-105; aabb_impl.rs:618-629).  Same operation order as the reference, no contraction.

@@ -1,6 +1,7 @@
-// walk.hpp — what every walk kernel over the engine's traversal arrays shares (moved unchanged out of traverse.hip so that
+// walk.hpp — what every walk kernel over the engine's traversal arrays shares (walk_binary.hip, walk_ordered.hip, walk_wide.hip and
 // query.hip's walks use the same pool records, chunking and per-lane bookkeeping): output modes, node fetch, hit records, WalkOut,
-// Ray::intersects_triangle, the per-lane ray state, the hit pool's per-wave chunks and the walk epilogue.
+// Ray::intersects_triangle, the per-lane ray state, the hit pool's per-wave chunks and the walk epilogue; and what traverse_enqueue
+// (traverse.hip) calls in those files and in csr.hip: one launcher per file, which picks its kernel instantiation itself.
 #pragma once
 
 #include "engine.hpp"
@@ -9,6 +10,13 @@ namespace bvhgpu {
 
 constexpr int SCAN_ITEMS = 4;
 constexpr int SCAN_BLOCK = 256 * SCAN_ITEMS;   // rays per workgroup of the count scan
+constexpr uint32_t SCAN_FUSED_MAX_BLOCKS = 2048;   // up to this many blocks every block sums its predecessors itself
+constexpr int COUNT_PLAIN = 0, COUNT_PAIR = 1, COUNT_MASKED = 2;   // how a ray's count is stored (csr.hip ray_count)
+constexpr uint32_t WIDE_ITEM_BITS = 5;                 // wide walk: item = ray << 5 | j (the pool records of a batch cut into items carry it)
+constexpr uint32_t WIDE_BSUM_MAX = 128;                // wide walk: 64-ray blocks per workgroup up to which the walk keeps the scan's block sums
+constexpr size_t WIDE_ITEM_MAX_RAYS = (size_t)1 << 27; // wide walk: item = ray << 5 | j is a 32-bit word
+constexpr unsigned long long WALK_FLAG_GUIDE_RANGE = 16ull;   // ctr[7] bit: a ray was outside the guide walk's range — the host replays in f64
+constexpr uint32_t HEAP_OVERFLOW_BIT = 2u;             // ctr[7] bit: a lane's best-first heap outgrew its workspace (k_traverse_heap)
 
 // what a walk produces besides the CSR of shape indices
 enum : int {
@@ -300,5 +308,37 @@ template <typename T> struct WideIo {
         return r;
     }
 };
+
+// ---- the walk launches of traverse_enqueue, one per file; each writes h->walk_kernel: the kernel's name as rocprofv3 spells it
+//      (bvhgpu_hits_walk_kernel: bench.py looks its counters up under this name instead of rebuilding template strings by hand)
+template <typename T> inline const char* walk_type_name() { return sizeof(T) == 4 ? "float" : "double"; }
+// walk_binary.hip: k_traverse, or k_traverse_lds (use_lds; split_at != 0: every ray as two items)
+template <typename T>
+void launch_binary(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, size_t n_rays, const WalkOut<T>& w, bvhgpu_hits* h, int mode, bool stats,
+                   bool use_lds, uint32_t split_at);
+// walk_ordered.hip: k_traverse_ordered, or k_traverse_heap (best_first)
+template <typename T>
+void launch_ordered(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, size_t n_rays, const WalkOut<T>& w, bvhgpu_hits* h, int mode, bool ascending,
+                    bool best_first, uint32_t* ovf_flag);
+// walk_wide.hip: k_traverse_wide, and the number of workgroups that launch will have
+template <typename T>
+void launch_wide_walk(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, size_t n_rays, const WalkOut<T>& w, bvhgpu_hits* h, int mode, int items_log4,
+                      bool use_guide, bool early_items, uint32_t* ovf_flag);
+template <typename T> size_t wide_walk_grid(const bvhgpu_ctx* ctx, size_t n_rays, int items_log4, bool coherent, bool use_guide);
+// csr.hip: counts → offsets → indices (+ values) behind the walk, from what traverse_enqueue has decided about the batch (the counter set
+// of the batch is w.ctr); publish_counters: the 8 walk / scan counters to the host page, zeroed for the next call
+struct CsrArgs {
+    int count_kind;                        // COUNT_*: one count per ray, two (k_traverse_lds split), or the wide walk's masked counts
+    int nv;                                // scalars per hit besides the shape index (ModeVals)
+    int items_log4;                        // wide walk: 4^items_log4 items per ray
+    int stage_shift;                       // staged output (WalkOut::raybuf): 2^stage_shift shapes per ray; 0: none
+    bool rec8;                             // the pool holds pair records (WalkOut::pool_pair)
+    uint32_t nb;                           // scan blocks of SCAN_BLOCK rays
+    unsigned long long cap;                // pool capacity in records
+    unsigned long long *ctr_other, *pin;   // the next batch's counter set (zeroed here), the pinned host page
+    uint32_t* bsum_other;                  // the next batch's set of scan sums (zeroed here); NULL: the walk left no sums
+};
+template <typename T> void csr_enqueue(bvhgpu_hits* h, size_t n_rays, const WalkOut<T>& w, const CsrArgs& a);
+void publish_counters(hipStream_t st, unsigned long long* ctr, unsigned long long* host_page);
 
 }  // namespace bvhgpu

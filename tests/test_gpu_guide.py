@@ -1,4 +1,4 @@
-"""f64 index batches walked over the tree's f32 guide boxes (traverse.hip "guide walk", BVHGPU_TUNE_WIDE_F64_GUIDE): the lists are the
+"""f64 index batches walked over the tree's f32 guide boxes (walk_wide.hip "guide walk", BVHGPU_TUNE_WIDE_F64_GUIDE): the lists are the
 oracle's — on random rays, on rays that graze faces / edges / corners of the shapes' boxes (where a conservative inner test and the
 f64 leaf test must agree exactly), with whole rays and with rays cut into items, after a refit, on an imported scene — and a batch with
 a ray outside the guide walk's range is replayed with the f64 walk without the caller noticing."""

@@ -1317,7 +1317,7 @@ def test_fuzz_all_queries(eng, orc, seed):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("coherent", [False, True])
 def test_pair_records_every_hit_count(eng, orc, dtype, coherent):
-    """Whole-ray index batches hand their hits over as PAIR records (traverse.hip report_pair: two consecutive hits of a ray per 16-byte
+    """Whole-ray index batches hand their hits over as PAIR records (walk.hpp report_pair: two consecutive hits of a ray per 16-byte
     record, the last one alone when the count is odd; behind the first 8 per-ray slot entries when the batch is COHERENT).  Rays with
     exactly 0, 1, 2, ... 90 hits, interleaved so that one wave holds odd and even counts, retiring rays and fresh ones at once; a small
     batch first, so that the large one finds the pool too small (grow + replay), then the large one again on the grown pool."""

@@ -1,4 +1,4 @@
-"""The containment argument of the f64 guide walk (bvh_amd/csrc/common.hpp "guide boxes", traverse.hip "guide walk"), replayed in numpy:
+"""The containment argument of the f64 guide walk (bvh_amd/csrc/common.hpp "guide boxes", walk_wide.hip "guide walk"), replayed in numpy:
 an f64 box grown by 2^-18 x S and rounded outward to f32, tested with the round-to-nearest f32 copy of an f64 ray whose origin lies
 within 3 x S and whose |1/d| x 4 S lies inside 2^+-100, must pass the f32 slab test whenever the f64 box passes the f64 test — on rays
 aimed AT the faces, edges and corners of the boxes (grazing cases, where a rounding could flip the outcome), flat boxes and rays that

@@ -97,7 +97,7 @@ def _newest_default_line():
 def test_committed_bench_line_follows_from_the_committed_profiles():
     """VERDICT r4 #8 — the evidence chain, checked on every CPU run.  The newest committed line of a default bench run
     (profiles/r<N>_v<M>_bench_default.json) must be reproducible from the profile files it cites:
-      (a) roofline.kernel names a kernel that is a row of the cited round's kernel_stats.md (a template-argument change in traverse.hip
+      (a) roofline.kernel names a kernel that is a row of the cited round's kernel_stats.md (a template-argument change in a walk file
           can no longer silently drop the roofline),
       (b) roofline.frac recomputes from the cited bound.json's counters and the line's own kernel time, within 3 %,
       (c) the kernels of one step, at their profiled average durations, fit into the line's ms_per_step."""

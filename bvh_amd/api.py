@@ -1000,8 +1000,10 @@ class Bvh(_TreeBase):
     def refit(self, aabbs) -> "Bvh":
         """The shapes moved: same topology, every child AABB recomputed from the new shape AABBs
         (Bvh::fix_aabbs_ascending, optimization.rs:355-391, applied to the whole tree); a flattened tree is
-        re-flattened.  ~10x cheaper than rebuild(); update_shapes' re-insertion (optimization.rs:337-352) is not
-        reproduced — rebuild() when the topology should follow the motion."""
+        re-flattened.  ~2.5x cheaper than rebuild(flatten=True) (0.08 against 0.20 ms at 120 k shapes); update_shapes' re-insertion (optimization.rs:337-352) is not
+        reproduced — rebuild() when the topology should follow the motion.  Input contract as for a build: with two or more
+        shapes a NaN or ±inf component raises INVALID_ARG and leaves the tree exactly as it was; the call returns when that check
+        has read the input (one host round trip)."""
         lib = _lib.load()
         fn = getattr(lib, f"bvhgpu_refit_{self.sfx}")
         if _is_device_tensor(aabbs):

@@ -190,11 +190,17 @@ template <typename T> int do_refit(bvhgpu_tree* t, const T* aabbs, size_t n, int
     if (n && !aabbs) return fail(ctx, BVHGPU_INVALID_ARG, "aabbs is NULL");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "bad mem kind");
     use_device(ctx);
+    // HOST input is staged in the ctx (one shape: straight into the tree's own copy, nothing is validated), so that the tree's arrays are
+    // first written after the input has passed the builders' contract; k_refit_leaves then copies it into the tree's own copy
     const T* dev = aabbs;
-    if (n && mem == BVHGPU_HOST) {  // upload straight into the tree's own copy
-        BVH_HIP(hipMemcpyAsync(t->aabbs.p, aabbs, n * 6 * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    if (n == 1 && mem == BVHGPU_HOST) {
+        BVH_HIP(hipMemcpyAsync(t->aabbs.p, aabbs, 6 * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
         dev = t->aabbs.as<T>();
+    } else if (n) {
+        dev = static_cast<const T*>(to_device(ctx, aabbs, n * 6 * sizeof(T), mem, ctx->upload));
     }
+    if (!refit_input_ok<T>(t, dev))
+        return fail(ctx, BVHGPU_INVALID_ARG, "refit: shape AABBs contain NaN or infinity (the builders' input contract); the tree is unchanged");
     refit_tree<T>(t, dev);
     return BVHGPU_OK;
 }

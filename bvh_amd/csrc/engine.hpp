@@ -287,6 +287,7 @@ template <typename T> struct WalkOut;
 template <typename T> void launch_query(bvhgpu_tree* t, size_t n, const WalkOut<T>& w, bvhgpu_hits* h, uint32_t* ovf_flag);
 // refit.hip
 template <typename T> void refit_tree(bvhgpu_tree* t, const T* aabbs_dev);
+template <typename T> bool refit_input_ok(bvhgpu_tree* t, const T* aabbs_dev);   // n >= 2: no NaN / ±inf component (reads the input only; one host round trip)
 // traverse.hip
 template <typename T>
 void traverse_batch(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, size_t n_rays, unsigned flags,

@@ -6,7 +6,7 @@
 // child_l_aabb.join(child_r_aabb)), walking up from a changed node.  Applied to every node, bottom-up, that is a
 // refit of the whole tree.  (update_shapes, optimization.rs:337-352, removes and re-inserts the changed shapes one
 // at a time — a serial pointer chase that also changes the topology; here moved shapes are answered by this refit,
-// ~10x cheaper than a build, or by a full rebuild when the topology should follow the motion.)
+// ~2.5x cheaper than build + flatten (0.08 against 0.20 ms at 120 k shapes), or by a full rebuild when the topology should follow the motion.)
 //
 // No bottom-up pointer chase on the GPU: a tree built here keeps, for every node, the range of SORTED POSITIONS of
 // its shapes (node_start, node_count: the leaves of a subtree are contiguous in pre-order), so a child box is a
@@ -16,6 +16,10 @@
 //   k_refit_segs    a complete binary tree of joins over the positions (heap layout, 1024-leaf groups per
 //                   workgroup reduced in LDS; one more launch per 10 levels)
 //   k_refit_nodes   per inner node two range queries (<= 2 log2 N boxes each, L2-resident) → child boxes
+//
+// Input contract: the builders' (build.hip k_prep).  join_min / join_max are defined on NaN-free floats only — a NaN
+// component would vanish from every ancestor box without a trace — so for n >= 2 k_refit_check looks at every component
+// first and the call answers NaN / ±inf with BVHGPU_INVALID_ARG before anything of the tree is written (refit_input_ok).
 #include "engine.hpp"
 
 namespace bvhgpu {
@@ -120,6 +124,36 @@ __global__ __launch_bounds__(256) void k_refit_nodes(typename Traits<T>::Node* _
         nd->r_min[k] = rb[k]; nd->r_max[k] = rb[3 + k];
     }
 }
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_refit_check(const T* __restrict__ aabbs, size_t count, uint32_t* __restrict__ flag) {
+    bool bad = false;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x)
+        bad = bad || !(fabs(aabbs[i]) < Traits<T>::inf());   // NaN or ±inf (the comparison is false for NaN)
+    if (__any(bad) && lane_id() == 0) atomicOr(flag, 1u);
+}
+
+// Every component of the n x 6 array in HBM is finite (n >= 2; a single shape is accepted as it is, as the builders accept it).
+// One host round trip; reads the input only.  The flag word lives in the ctx and is zeroed in front of every check.
+template <typename T> bool refit_input_ok(bvhgpu_tree* t, const T* aabbs_dev) {
+    if (t->n < 2) return true;
+    bvhgpu_ctx* ctx = t->ctx;
+    hipStream_t st = ctx->stream;
+    ctx->counters.reserve(64);
+    uint32_t* flag = ctx->counters.as<uint32_t>();
+    BVH_HIP(hipMemsetAsync(flag, 0, sizeof(uint32_t), st));
+    const size_t count = 6 * t->n;
+    const uint32_t grid = (uint32_t)std::min<size_t>((count + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_refit_check<T>, dim3(grid), dim3(256), 0, st, aabbs_dev, count, flag);
+    BVH_HIP(hipGetLastError());
+    uint32_t* host = static_cast<uint32_t*>(ctx->pinned);
+    BVH_HIP(hipMemcpyAsync(host, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    BVH_HIP(hipStreamSynchronize(st));
+    return *host == 0u;
+}
+
+template bool refit_input_ok<float>(bvhgpu_tree*, const float*);
+template bool refit_input_ok<double>(bvhgpu_tree*, const double*);
 
 template <typename T> void refit_tree(bvhgpu_tree* t, const T* aabbs_dev) {
     using Tr = Traits<T>;

@@ -694,6 +694,7 @@ inline size_t wide_grid(const bvhgpu_ctx* ctx, uint32_t threads, uint32_t wg_per
     return std::min<size_t>(std::max<size_t>(full, 1), slots);
 }
 constexpr uint32_t WIDE_GSTACK = 24;   // stack entries per lane beyond the LDS part, in HBM (a walk pushes at most 3 per wide level)
+// (tests/test_gpu_refit.py WIDE_STACK restates this and WideGeom's smallest default LDS part, 6, to know on which trees no lane can overflow)
 
 // GUIDE: T = float on an f64 tree — the nodes are the tree's guide boxes, rays_dev unused (NULL), ga the f64 batch: every ray is converted where the walk loads it (guide_ray_load)
 template <typename T, int MODE, int ITEMS_LOG4, int GUIDE = 0>

@@ -171,7 +171,13 @@ int bvhgpu_rebuild_flat_f64(bvhgpu_tree *tree, const double *aabbs, size_t n, in
  * applied to the whole tree.  n must equal the tree's shape count; the tree must have been built here.  If the tree
  * is flattened its flat / traversal arrays are regenerated.  The result is consistent and tight (the properties
  * the reference asserts after update_shapes, optimization.rs tests); refit with the AABBs of the build reproduces
- * the built tree bit for bit.  Bvh::update_shapes itself (optimization.rs:337-352: remove + re-insert, one shape at a
+ * the built tree bit for bit, unless a split had no SAH winner (then the empty child boxes become exact joins and the
+ * wide walk becomes available).
+ * Input contract: the builders'.  For n >= 2 a NaN or +-inf component anywhere in `aabbs` makes the call itself return
+ * BVHGPU_INVALID_ARG and the tree — BvhNode array, its copy of the shape AABBs, flat / traversal arrays — is left exactly
+ * as it was (the input is checked on the device before anything is written: the call waits for that check, one host round
+ * trip; HOST input is staged in the ctx meanwhile).  A single shape (n == 1) is accepted as it is, as the builders accept
+ * it.  Bvh::update_shapes itself (optimization.rs:337-352: remove + re-insert, one shape at a
  * time, topology changes) has no device counterpart: moved shapes are answered by this refit or by a rebuild.
  * Triangle vertices (bvhgpu_tree_set_triangles) are the caller's to refresh. */
 int bvhgpu_refit_f32(bvhgpu_tree *tree, const float *aabbs, size_t n, int mem);

@@ -25,6 +25,7 @@ TRAVERSE_STATS = 2
 TRAVERSE_TRIANGLES = 4
 TRAVERSE_CLOSEST = 8
 TRAVERSE_COHERENT = 16
+TRAVERSE_FIRST = 1024
 TRAVERSE_NEAREST_FIRST = 32
 TRAVERSE_FARTHEST_FIRST = 64
 TRAVERSE_BEST_FIRST = 128
@@ -152,6 +153,9 @@ SYMBOLS = [
     ("bvhgpu_traverse_any_f32", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
     ("bvhgpu_traverse_any_f64", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
     ("bvhgpu_hits_fetch_any", _i, [_vp, _vp, _vp, _i]),
+    ("bvhgpu_traverse_box_f32", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_traverse_box_f64", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_hits_fetch_box", _i, [_vp, _vp, _vp, _i]),
     ("bvhgpu_enable_timing", _i, [_vp, _i]),
     ("bvhgpu_last_timings", _i, [_vp, C.POINTER(Timings)]),
     ("bvhgpu_obj_parse", _i, [C.c_char_p, _sz, C.POINTER(C.POINTER(C.c_float)), C.POINTER(_sz), _vp]),

@@ -458,6 +458,13 @@ class _Hits:
         check(_lib.load().bvhgpu_hits_fetch_any(self.h, ptr(isect), ptr(shape), HOST), self.ctx._h)
         return isect, shape
 
+    def fetch_box(self, n_rays: int, dtype=np.float32):
+        """box batches: (slice{enter,exit}[n,2], shape[n]) of the completed batch, copied to the host"""
+        ts = np.zeros((n_rays, 2), dtype=dtype)
+        shape = np.zeros(n_rays, dtype=np.uint32)
+        check(_lib.load().bvhgpu_hits_fetch_box(self.h, ptr(ts), ptr(shape), HOST), self.ctx._h)
+        return ts, shape
+
     def fetch_triangles(self, dtype=np.float32):
         """TRIANGLES batches: Intersection{distance,u,v} of every candidate, CSR order"""
         total = C.c_uint64()
@@ -617,14 +624,9 @@ class _TreeBase:
         check(lib.bvhgpu_hits_fetch_closest(self._hits.h, ptr(isect), ptr(shape), HOST), self.ctx._h)
         return isect, shape, sd
 
-    def any_hits(self, rays: RayBatch, tmax=None, fetch: bool = True, coherent: bool = False):
-        """bvhgpu_traverse_any_*: occlusion of the segments o .. o + tmax[i]·d.  Per ray the FIRST shape of FlatBvh::traverse's list
-        (flat_bvh.rs:396-431, in its order) whose Ray::intersects_triangle distance is < tmax[i], with that Intersection; shape NONE and
-        (+inf, 0, 0) when there is none.  tmax: None (+inf for every ray), or n values in the tree's dtype in the rays' memory — a numpy
-        array for HOST rays, a torch GPU tensor for rays in HBM.  Needs set_triangles.  returns (isect[n,3], shape[n]); fetch=False
-        returns (None, None) and leaves the result on the tree's result object."""
-        if rays.sfx != self.sfx:
-            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
+    def _tmax_arg(self, rays: RayBatch, tmax):
+        """per-ray segment ends of any_hits / the box queries → (array kept alive, pointer or None): n values in the tree's dtype in the
+        rays' memory — a numpy array for HOST rays, a torch GPU tensor for rays in HBM"""
         ft = np.float32 if self.sfx == "f32" else np.float64
         keep, tp = None, None
         if tmax is not None:
@@ -644,6 +646,18 @@ class _TreeBase:
                 n, tp = keep.size, ptr(keep)
             if n != rays.n:
                 raise BvhGpuError(_lib.INVALID_ARG, f"tmax has {n} values for {rays.n} rays")
+        return keep, tp
+
+    def any_hits(self, rays: RayBatch, tmax=None, fetch: bool = True, coherent: bool = False):
+        """bvhgpu_traverse_any_*: occlusion of the segments o .. o + tmax[i]·d.  Per ray the FIRST shape of FlatBvh::traverse's list
+        (flat_bvh.rs:396-431, in its order) whose Ray::intersects_triangle distance is < tmax[i], with that Intersection; shape NONE and
+        (+inf, 0, 0) when there is none.  tmax: None (+inf for every ray), or n values in the tree's dtype in the rays' memory — a numpy
+        array for HOST rays, a torch GPU tensor for rays in HBM.  Needs set_triangles.  returns (isect[n,3], shape[n]); fetch=False
+        returns (None, None) and leaves the result on the tree's result object."""
+        if rays.sfx != self.sfx:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
+        ft = np.float32 if self.sfx == "f32" else np.float64
+        keep, tp = self._tmax_arg(rays, tmax)   # (keep: the array tp points into stays alive over the call)
         lib = _lib.load()
         fn = getattr(lib, f"bvhgpu_traverse_any_{self.sfx}")
         check(fn(self._t, rays._ptr(), tp, rays.n, rays.mem, TRAVERSE_COHERENT if coherent else 0, C.byref(self._hits.h)), self.ctx._h)
@@ -654,6 +668,35 @@ class _TreeBase:
     def occluded(self, rays: RayBatch, tmax=None) -> np.ndarray:
         """bool[n]: does segment i hit any triangle (any_hits(...) shape != NONE)"""
         _, shape = self.any_hits(rays, tmax)
+        return shape != NONE
+
+    # ---- ray queries against the shapes' own boxes (no triangles) ---------------------------
+    def _box_hits(self, rays: RayBatch, tmax, fetch: bool, coherent: bool, first: bool):
+        if rays.sfx != self.sfx:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
+        keep, tp = self._tmax_arg(rays, tmax)   # (keep: the array tp points into stays alive over the call)
+        flags = (TRAVERSE_COHERENT if coherent else 0) | (_lib.TRAVERSE_FIRST if first else 0)
+        fn = getattr(_lib.load(), f"bvhgpu_traverse_box_{self.sfx}")
+        check(fn(self._t, rays._ptr(), tp, rays.n, rays.mem, flags, C.byref(self._hits.h)), self.ctx._h)
+        if not fetch:
+            return None, None
+        return self._hits.fetch_box(rays.n, np.float32 if self.sfx == "f32" else np.float64)
+
+    def closest_box_hits(self, rays: RayBatch, tmax=None, fetch: bool = True, coherent: bool = False):
+        """bvhgpu_traverse_box_*: per ray the shape of FlatBvh::traverse's list (flat_bvh.rs:396-431) whose own AABB the ray enters first,
+        among those with enter < tmax[i] (strict; the first of the list on equal entries), with Ray::intersection_slice_for_aabb's
+        (enter, exit) on that box; shape NONE and (+inf, 0) when there is none.  No triangles needed.  tmax as for any_hits.
+        returns (slice[n,2], shape[n]); fetch=False returns (None, None) and leaves the result on the tree's result object."""
+        return self._box_hits(rays, tmax, fetch, coherent, False)
+
+    def first_box_hits(self, rays: RayBatch, tmax=None, fetch: bool = True, coherent: bool = False):
+        """bvhgpu_traverse_box_* with BVHGPU_TRAVERSE_FIRST: the FIRST shape of the ray's list with enter < tmax[i] instead of the
+        nearest one (any-hit: every walk stops at it).  returns (slice[n,2], shape[n]) like closest_box_hits."""
+        return self._box_hits(rays, tmax, fetch, coherent, True)
+
+    def box_occluded(self, rays: RayBatch, tmax=None) -> np.ndarray:
+        """bool[n]: does ray i enter any shape's box before tmax[i] (first_box_hits(...) shape != NONE)"""
+        _, shape = self.first_box_hits(rays, tmax)
         return shape != NONE
 
     # ---- point query ---------------------------------------------------------------------

@@ -245,7 +245,7 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
     }
     if ((flags & BVHGPU_TRAVERSE_TRIANGLES) && (flags & BVHGPU_TRAVERSE_CLOSEST))
         return fail(ctx, BVHGPU_INVALID_ARG, "TRIANGLES and CLOSEST are alternatives");
-    flags &= ~TRAVERSE_ANY_HIT;   // (internal: only bvhgpu_traverse_any_* sets it)
+    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT);   // (internal: only bvhgpu_traverse_any_* / bvhgpu_traverse_box_* set them)
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = *hits;
@@ -299,6 +299,42 @@ int do_traverse_any(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, cons
         }
         h->pend_tmax = tmax_dev;
         traverse_batch<T>(tree, dev, n_rays, flags | TRAVERSE_ANY_HIT, h);
+        return (int)BVHGPU_OK;
+    });
+}
+
+// bvhgpu_traverse_box_*: per ray the shape of FlatBvh::traverse's list whose own AABB the ray enters first — or, with BVHGPU_TRAVERSE_FIRST, the first
+// one of the list — among those with enter < tmax[i] (traverse.hip MODE_BOX_CLOSEST / MODE_BOX_FIRST).  No triangles are needed or read.
+// tmax is handled as in do_traverse_any.
+template <typename T>
+int do_traverse_box(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, const T* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits) {
+    if (!tree) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = tree->ctx;
+    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
+    if (flags & ~(BVHGPU_TRAVERSE_COHERENT | BVHGPU_TRAVERSE_FIRST)) return fail(ctx, BVHGPU_INVALID_ARG, "box-hit flags: BVHGPU_TRAVERSE_COHERENT and BVHGPU_TRAVERSE_FIRST only");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    { const int rc = settle(tree); if (rc != BVHGPU_OK) return rc; }
+    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
+    if (tree->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from ray dtype");
+    if (!tree->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    if (n_rays && !rays) return fail(ctx, BVHGPU_INVALID_ARG, "rays is NULL");
+    if (n_rays >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 rays in one batch");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        bvhgpu_hits* h = *hits;
+        if (!h) h = new bvhgpu_hits();
+        *hits = h;
+        const auto* dev = static_cast<const typename Traits<T>::Ray*>(
+            to_device(ctx, rays, n_rays * sizeof(typename Traits<T>::Ray), mem, ctx->upload));
+        h->pend_kind = 0; h->pend_queries = nullptr; h->pend_qwide = false;   // (the object may have held a query batch)
+        const T* tmax_dev = tmax;
+        if (tmax && n_rays && mem == BVHGPU_HOST) {
+            h->tmaxbuf.reserve(n_rays * sizeof(T));
+            BVH_HIP(hipMemcpyAsync(h->tmaxbuf.p, tmax, n_rays * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+            tmax_dev = h->tmaxbuf.as<T>();
+        }
+        h->pend_tmax = tmax_dev;
+        traverse_batch<T>(tree, dev, n_rays, flags | TRAVERSE_BOX_HIT, h);
         return (int)BVHGPU_OK;
     });
 }
@@ -1320,6 +1356,13 @@ int bvhgpu_traverse_any_f64(bvhgpu_tree* tree, const bvhgpu_ray_f64* rays, const
     return do_traverse_any<double>(tree, rays, tmax, n_rays, mem, flags, hits);
 }
 
+int bvhgpu_traverse_box_f32(bvhgpu_tree* tree, const bvhgpu_ray_f32* rays, const float* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_traverse_box<float>(tree, rays, tmax, n_rays, mem, flags, hits);
+}
+int bvhgpu_traverse_box_f64(bvhgpu_tree* tree, const bvhgpu_ray_f64* rays, const double* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_traverse_box<double>(tree, rays, tmax, n_rays, mem, flags, hits);
+}
+
 int bvhgpu_query_f32(bvhgpu_tree* tree, int kind, const float* queries, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
     return do_query<float>(tree, kind, queries, n, mem, flags, hits);
 }
@@ -1422,6 +1465,19 @@ int bvhgpu_hits_fetch_any(bvhgpu_hits* h, void* isect, uint32_t* shape, int mem)
     });
 }
 
+int bvhgpu_hits_fetch_box(bvhgpu_hits* h, void* slice, uint32_t* shape, int mem) {
+    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = h->ctx;
+    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (!(h->flags & TRAVERSE_BOX_HIT)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_traverse_box_* batch");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        if (slice && h->n_rays) copy_out(ctx, slice, h->closest.p, h->n_rays * 2 * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
+        if (shape && h->n_rays) copy_out(ctx, shape, h->closest_prim.p, h->n_rays * 4, mem);
+        return (int)BVHGPU_OK;
+    });
+}
+
 int bvhgpu_hits_info(const bvhgpu_hits* h, size_t* n_rays, uint64_t* total, bvhgpu_traverse_stats* stats) {
     if (!h) return BVHGPU_INVALID_ARG;
     if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
@@ -1452,6 +1508,7 @@ int bvhgpu_hits_fetch(bvhgpu_hits* h, uint32_t* offsets, uint32_t* indices, void
     if (tslice && !(h->flags & BVHGPU_TRAVERSE_T_SLICE)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_T_SLICE");
     if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR: use bvhgpu_hits_fetch_closest");
     if (h->flags & TRAVERSE_ANY_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR: use bvhgpu_hits_fetch_any");
+    if (h->flags & TRAVERSE_BOX_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "a box-hit batch produces no CSR: use bvhgpu_hits_fetch_box");
     return guarded(ctx, [&] {
         use_device(ctx);
         if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
@@ -1466,6 +1523,7 @@ int bvhgpu_hits_device(const bvhgpu_hits* h, const uint32_t** offsets, const uin
     if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(h->ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR");
     if (h->flags & TRAVERSE_ANY_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR");
+    if (h->flags & TRAVERSE_BOX_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "a box-hit batch produces no CSR");
     if (offsets) *offsets = h->offsets.as<uint32_t>();
     if (indices) *indices = h->indices.as<uint32_t>();
     if (tslice) *tslice = (h->flags & BVHGPU_TRAVERSE_T_SLICE) ? h->tslice.p : nullptr;

@@ -38,6 +38,8 @@ struct DevBuf {
 // result objects of bvhgpu_traverse_any_*: an internal bit of bvhgpu_hits::flags next to the caller's BVHGPU_TRAVERSE_* flags (which
 // bvhgpu_traverse_any_* restricts to COHERENT), so that the walk dispatch, traverse_check and the fetch functions tell the kinds apart
 constexpr unsigned TRAVERSE_ANY_HIT = 1u << 31;
+// result objects of bvhgpu_traverse_box_* (MODE_BOX_CLOSEST, or MODE_BOX_FIRST with BVHGPU_TRAVERSE_FIRST): marked the same way
+constexpr unsigned TRAVERSE_BOX_HIT = 1u << 30;
 
 }  // namespace bvhgpu
 
@@ -238,7 +240,7 @@ struct bvhgpu_hits {
     const void* pend_queries = nullptr;  // its queries in HBM (the caller's, the tree's own AABBs, or `qbuf`)
     bool pend_qwide = false;             // ... walked by k_query_wide (a lane's stack overflow replays it with the binary walk)
     bvhgpu::DevBuf qbuf;                 // HOST queries staged here, so that a replay reads them again
-    // any-hit batches (bvhgpu_traverse_any_*): per-ray segment ends in HBM (the caller's, or `tmaxbuf`; NULL = +inf), read by every replay
+    // any-hit and box batches (bvhgpu_traverse_any_* / bvhgpu_traverse_box_*): per-ray segment ends in HBM (the caller's, or `tmaxbuf`; NULL = +inf), read by every replay
     const void* pend_tmax = nullptr;
     bvhgpu::DevBuf tmaxbuf;              // HOST tmax staged here
     bvhgpu::DevBuf any_key;              // n_rays u32: any-hit batches walked as items (walk.hpp WalkOut::any_key), all-ones between batches

@@ -120,7 +120,66 @@ __global__ __launch_bounds__(256) void k_any_resolve(uint32_t* __restrict__ key,
         part[blockIdx.x] = sum;
     }
 }
-// k_publish_counters for an any-hit batch: ctr[3] = the sum of k_any_resolve's per-workgroup counts, then the 8 counters go to the pinned
+// Box batch (MODE_BOX_CLOSEST / MODE_BOX_FIRST), after its walk: per ray {enter, exit} of the winning shape's own AABB and the shape, and the
+// rays that have one counted like k_any_resolve's occluded rays (part[workgroup] → k_any_publish → bvhgpu_hits_info's total).  SRC = where
+// the walk left the winner: BOX_SRC_RAY — whole rays, slice and shape are in place already; BOX_SRC_KEY32 — rays walked as items, first mode:
+// the lowest item's candidate, {item << 28 | shape} (WalkOut::any_key); BOX_SRC_KEY64 — items, closest, f32: {key(enter) << 32 | item << 28 |
+// shape} (WalkOut::closest_key; enter >= +0, so the key orders like the value); BOX_SRC_SLOTS — items, closest, f64: the candidates by
+// (ray, item), reduced in item order with the reference's strict < (k_closest_resolve_slots).  The winner's slice is computed again from the
+// ray and the box — slab_hit on the operands the walk used, hence the same bits — and keys / item sets go back to their idle values.
+enum : int { BOX_SRC_RAY = 0, BOX_SRC_KEY32 = 1, BOX_SRC_KEY64 = 2, BOX_SRC_SLOTS = 3 };
+template <typename T, int SRC>
+__global__ __launch_bounds__(256) void k_box_resolve(uint32_t* __restrict__ key32, unsigned long long* __restrict__ key64, uint32_t* __restrict__ ray_items,
+                                                     const uint32_t* __restrict__ item_prim, const typename Traits<T>::Ray* __restrict__ rays,
+                                                     const T* __restrict__ aabbs, uint32_t n_rays, T* __restrict__ slice, uint32_t* __restrict__ prim,
+                                                     uint32_t* __restrict__ part) {
+    __shared__ uint32_t s_cnt[256 / WAVE];
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t p = NONE;
+    if (r < n_rays) {
+        if (SRC == BOX_SRC_RAY) {
+            p = prim[r];
+        } else {
+            T best[2] = {Traits<T>::inf(), 0};
+            const typename Traits<T>::Ray* rp = rays + r;
+            const T o[3] = {rp->o[0], rp->o[1], rp->o[2]}, inv[3] = {rp->inv[0], rp->inv[1], rp->inv[2]};
+            auto slice_of = [&](uint32_t shape, T& t0, T& t1) {
+                const T* b = aabbs + 6 * (size_t)shape;
+                const T mn[3] = {b[0], b[1], b[2]}, mx[3] = {b[3], b[4], b[5]};
+                slab_hit<T>(o, inv, mn, mx, t0, t1);
+            };
+            if (SRC == BOX_SRC_KEY32) {
+                const uint32_t k = key32[r];
+                if (k != NONE) { p = k & 0x0FFFFFFFu; slice_of(p, best[0], best[1]); key32[r] = NONE; }
+            } else if (SRC == BOX_SRC_KEY64) {
+                const unsigned long long k = key64[r];
+                if (k != ~0ull) { p = (uint32_t)(k & 0x0FFFFFFFull); slice_of(p, best[0], best[1]); key64[r] = ~0ull; }
+            } else {
+                uint32_t m = ray_items[r];
+                if (m) ray_items[r] = 0u;
+                while (m) {
+                    const int j = __ffs((int)m) - 1;
+                    m &= m - 1u;
+                    const uint32_t q = item_prim[((size_t)r << 4) + (uint32_t)j];
+                    T t0, t1;
+                    slice_of(q, t0, t1);
+                    if (t0 < best[0]) { best[0] = t0; best[1] = t1; p = q; }
+                }
+            }
+            slice[2 * (size_t)r] = best[0]; slice[2 * (size_t)r + 1] = best[1];
+            prim[r] = p;
+        }
+    }
+    const uint32_t m = (uint32_t)__popcll(__ballot(p != NONE));
+    if (lane_id() == 0) s_cnt[threadIdx.x / WAVE] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (uint32_t w = 0; w < blockDim.x / WAVE; w++) sum += s_cnt[w];
+        part[blockIdx.x] = sum;
+    }
+}
+// k_publish_counters for an any-hit or box batch: ctr[3] = the sum of k_any_resolve's per-workgroup counts, then the 8 counters go to the pinned
 // host page and are zeroed for the next call
 __global__ __launch_bounds__(256) void k_any_publish(unsigned long long* __restrict__ ctr, unsigned long long* __restrict__ host_page,
                                                      const uint32_t* __restrict__ part, uint32_t n_part) {
@@ -153,7 +212,8 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
     const bool stats = (flags & BVHGPU_TRAVERSE_STATS) != 0;
     const bool coherent = (flags & BVHGPU_TRAVERSE_COHERENT) != 0;
     const int ordered = (flags & BVHGPU_TRAVERSE_NEAREST_FIRST) ? 1 : ((flags & BVHGPU_TRAVERSE_FARTHEST_FIRST) ? 2 : 0);
-    const int mode = (flags & TRAVERSE_ANY_HIT) ? MODE_ANY
+    const int mode = (flags & TRAVERSE_BOX_HIT) ? ((flags & BVHGPU_TRAVERSE_FIRST) ? MODE_BOX_FIRST : MODE_BOX_CLOSEST)
+                   : (flags & TRAVERSE_ANY_HIT) ? MODE_ANY
                    : (flags & BVHGPU_TRAVERSE_CLOSEST) ? MODE_CLOSEST
                    : (flags & BVHGPU_TRAVERSE_TRIANGLES) ? MODE_TRIANGLES
                    : (flags & BVHGPU_TRAVERSE_T_SLICE) ? MODE_T_SLICE : MODE_INDICES;
@@ -177,7 +237,7 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
     // CSR batches: 1, 4 or 16 items per ray.  Closest hit: whole rays, or the same cut into 16 items below ~2 M rays — the per-ray minimum over
     // the items goes through WalkOut::closest_key (f32: one 64-bit atomicMin per item with a candidate) or through the (ray, item) slots (f64:
     // k_closest_resolve_slots).  Any hit: the same choice, the lowest item with a candidate through WalkOut::any_key (one 32-bit atomicMin per
-    // item with a candidate, f32 and f64)
+    // item with a candidate, f32 and f64).  Box batches: closest like closest hit, first like any hit (k_box_resolve)
     int items_log4 = 0;
     if (use_wide && n_rays < WIDE_ITEM_MAX_RAYS) {
         const int want = ctx->tune[BVHGPU_TUNE_WIDE_ITEMS_LOG4];
@@ -217,7 +277,9 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
     unsigned long long* ctr_other = h->ctr.as<unsigned long long>() + 8 * ((h->ctr_set & 1) ^ 1);
 
     WalkOut<T> w{};
-    w.ctr = ctr; w.tris = t->tris.as<T>();
+    const bool box = mode_box(mode);
+    w.ctr = ctr;
+    if (box) w.set_boxes(t->aabbs.as<T>()); else w.tris = t->tris.as<T>();   // (box batches read no triangles: their leaf primitive is the shape's own AABB)
 
     uint32_t* ovf_flag = reinterpret_cast<uint32_t*>(ctr + 7);   // bit 0 ordered-iterator stack, bit 1 heap workspace, bit 2 wide-walk stack
     const bool best_first = ordered && (flags & BVHGPU_TRAVERSE_BEST_FIRST) != 0;
@@ -233,13 +295,13 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
 
     if (!h->ctr_clean) BVH_HIP(hipMemsetAsync(ctr, 0, 8 * sizeof(unsigned long long), st));   // (only this batch's set has to be clean)
     h->ctr_clean = false;
-    if (mode >= MODE_CLOSEST) {   // no CSR: one Intersection + shape per ray (closest / closest_prim); any hit: the occluded rays counted in ctr[3]
-        const bool any = mode == MODE_ANY;
+    if (mode >= MODE_CLOSEST) {   // no CSR: one Intersection (box: one t-slice) + shape per ray (closest / closest_prim); any hit and box: the rays with an answer counted in ctr[3]
+        const bool any = mode_first(mode);   // (the first candidate ends the ray: the keys of any hit)
         h->closest.reserve(std::max<size_t>(n_rays, 1) * 3 * sizeof(T));
         h->closest_prim.reserve(std::max<size_t>(n_rays, 1) * 4);
         if (n_rays == 0) { h->pend_tree = nullptr; return; }
         w.closest = h->closest.as<T>(); w.closest_prim = h->closest_prim.as<uint32_t>();
-        if (any) w.tmax = static_cast<const T*>(h->pend_tmax);
+        if (mode_tmax(mode)) w.tmax = static_cast<const T*>(h->pend_tmax);
         const bool by_items = use_wide && items_log4 == 2;
         const bool keyed = by_items && (any || sizeof(T) == 4);
         if (keyed) {   // the per-ray keys (u32 any hit, u64 closest hit): all-ones between batches (the resolve kernel puts them back)
@@ -259,7 +321,18 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
         const dim3 rgrid((unsigned)((n_rays + 255) / 256)), rblock(256);
         const T* tris = t->tris.as<T>();
         const uint32_t nr = (uint32_t)n_rays;
-        if (any) {
+        if (box) {
+            h->any_part.reserve((size_t)rgrid.x * 4);
+            uint32_t* part = h->any_part.as<uint32_t>();
+            const T* boxes = t->aabbs.as<T>();
+#define BOX_RESOLVE(SRC) hipLaunchKernelGGL((k_box_resolve<T, SRC>), rgrid, rblock, 0, st, w.any_key, w.closest_key, w.ray_items, (const uint32_t*)w.item_cnt, \
+                                            rays_dev, boxes, nr, w.closest, w.closest_prim, part)
+            if (!by_items) BOX_RESOLVE(BOX_SRC_RAY);
+            else if (any) BOX_RESOLVE(BOX_SRC_KEY32);
+            else if (keyed) BOX_RESOLVE(BOX_SRC_KEY64);
+            else BOX_RESOLVE(BOX_SRC_SLOTS);
+#undef BOX_RESOLVE
+        } else if (any) {
             h->any_part.reserve((size_t)rgrid.x * 4);
             if (by_items) hipLaunchKernelGGL((k_any_resolve<T, true>), rgrid, rblock, 0, st, w.any_key, rays_dev, tris, nr, w.closest, w.closest_prim, h->any_part.as<uint32_t>());
             else hipLaunchKernelGGL((k_any_resolve<T, false>), rgrid, rblock, 0, st, nullptr, rays_dev, tris, nr, w.closest, w.closest_prim, h->any_part.as<uint32_t>());
@@ -272,7 +345,7 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
         }
         if (ctx->timing) BVH_HIP(hipEventRecord(ctx->ev[6], st));
         // readback + reset for the next call
-        if (any) hipLaunchKernelGGL(k_any_publish, dim3(1), dim3(256), 0, st, ctr, pin, (const uint32_t*)h->any_part.as<uint32_t>(), rgrid.x);
+        if (any || box) hipLaunchKernelGGL(k_any_publish, dim3(1), dim3(256), 0, st, ctr, pin, (const uint32_t*)h->any_part.as<uint32_t>(), rgrid.x);
         else publish_counters(st, ctr, pin);
         h->ctr_clean = true;
         join_flat(t);
@@ -387,7 +460,7 @@ bool traverse_check(bvhgpu_hits* h) {
     if (h->pend_wide && (pin[7] & 4ull)) {   // a lane's stack outgrew LDS + workspace: the binary walks need no stack
         h->force_binary = true; h->wcounts_clean = false; h->bs_clean = false; h->ckey_clean = false; h->akey_clean = false; h->ray_items.release(); return false;
     }
-    if (flags & TRAVERSE_ANY_HIT) {   // the occluded rays, counted by k_any_resolve / k_any_publish
+    if (flags & (TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT)) {   // the occluded rays (box: the rays with a candidate), counted by k_any_resolve / k_box_resolve and k_any_publish
         h->total = pin[3];
         if (ctx->timing) ctx->ev_set |= 4u;
         h->pend_tree = nullptr;

@@ -24,8 +24,15 @@ enum : int {
     MODE_T_SLICE = 1,   // + Ray::intersection_slice_for_aabb per hit (2 scalars)
     MODE_TRIANGLES = 2, // + Ray::intersects_triangle per hit: Intersection{distance,u,v} (3 scalars)
     MODE_CLOSEST = 3,   // no CSR: per ray the candidate triangle with the smallest distance
-    MODE_ANY = 4        // no CSR: per ray the FIRST candidate (reference order) whose triangle distance is < the ray's tmax; the walk stops there
+    MODE_ANY = 4,       // no CSR: per ray the FIRST candidate (reference order) whose triangle distance is < the ray's tmax; the walk stops there
+    MODE_BOX_CLOSEST = 5,   // no CSR, no triangles: per ray the shape of its list whose own AABB the ray enters first (t-slice {enter, exit}) with enter < tmax
+    MODE_BOX_FIRST = 6      // ... the FIRST shape of its list (reference order) with enter < tmax; the walk stops there
 };
+// what the output modes share (the per-ray modes are MODE >= MODE_CLOSEST, the CSR modes MODE < MODE_CLOSEST)
+constexpr bool mode_tris(int m) { return m >= MODE_TRIANGLES && m <= MODE_ANY; }          // the leaf stage is Ray::intersects_triangle: needs the direction and w.tris
+constexpr bool mode_box(int m) { return m == MODE_BOX_CLOSEST || m == MODE_BOX_FIRST; }   // the leaf stage is the t-slice of the shape's own AABB
+constexpr bool mode_first(int m) { return m == MODE_ANY || m == MODE_BOX_FIRST; }         // the ray ends at its first candidate
+constexpr bool mode_tmax(int m) { return m == MODE_ANY || mode_box(m); }                  // candidates are limited by the ray's tmax
 template <int MODE> struct ModeVals { static constexpr int N = MODE == MODE_T_SLICE ? 2 : (MODE == MODE_TRIANGLES ? 3 : 0); };
 
 // ---- node fetch: two (f32) / four (f64) 16-byte loads per lane -------------------------------
@@ -60,8 +67,9 @@ template <typename T> struct WalkOut {
     T* pool_v;                   // ModeVals::N scalars per record
     unsigned long long pool_cap;
     unsigned long long* ctr;     // [0] pool slots taken [1] device steps [2] leaf-entry steps [4] wave steps [5] candidates (closest mode)
-    const T* tris;               // n x 9 vertices (triangle modes)
-    T* closest;                  // per ray {distance,u,v} (closest mode)
+    const T* tris;               // the leaf primitives.  Triangle modes: n x 9 vertices.  Box modes: the n x 6 shape AABBs, read through boxes() — one
+                                 // pointer for both, so that the kernel arguments of the existing instantiations stay as they are
+    T* closest;                  // per ray {distance,u,v} (closest mode); box modes: per ray {enter, exit}, 2 scalars
     uint32_t* closest_prim;      // per ray shape index or NONE
     unsigned long long* closest_key;   // closest mode with rays cut into items (f32): per ray min over its items of {key(distance) << 32 | item << 28 | shape}
                                  // (kept all-ones between batches; k_closest_resolve turns the winner into closest / closest_prim).  NULL: one lane owns the ray
@@ -72,9 +80,12 @@ template <typename T> struct WalkOut {
                                  // HitRec: 8 bytes per hit, one offset gather per two hits in the scatter.  NULL: HitRec
     uint32_t* raybuf;            // wide walk, whole rays, indices only: the first 2^stage_shift shapes of ray r go straight to raybuf[r << stage_shift | k]
     uint32_t stage_shift;        // (4 bytes per hit, no record, no atomic); only later hits of a ray become pool records.  NULL: everything through the pool
-    const T* tmax;               // any-hit mode: per ray the end of its segment (NULL: +inf for every ray)
+    const T* tmax;               // any-hit and box modes: per ray the end of its segment (NULL: +inf for every ray)
     uint32_t* any_key;           // any-hit mode with rays cut into items: per ray min over its items that found a candidate of {item << 28 | shape}
                                  // (kept all-ones between batches; k_any_resolve turns the winner into closest / closest_prim).  NULL: one lane owns the ray
+    // box modes: shape s's own AABB {min xyz, max xyz} (the wide walk's leaf stage)
+    __host__ __device__ __forceinline__ const T* box(uint32_t s) const { return tris + 6 * (size_t)s; }
+    __host__ __device__ __forceinline__ void set_boxes(const T* aabbs) { tris = aabbs; }
 };
 
 // ---- Ray::intersects_triangle (ray_impl.rs:154-213), Möller–Trumbore with back-face culling.  Same
@@ -118,9 +129,9 @@ __device__ __forceinline__ void ray_triangle(const T o[3], const T d[3], const T
 // ---- per-lane ray state
 template <typename T, int MODE> struct LaneRay {
     T o[3], inv[3];
-    T d[MODE >= MODE_TRIANGLES ? 3 : 1];   // direction: only the triangle stage needs it
-    T best[MODE >= MODE_CLOSEST ? 3 : 1];  // closest Intersection so far / the any-hit candidate
-    T tmax;                                // any-hit mode: end of the segment
+    T d[mode_tris(MODE) ? 3 : 1];          // direction: only the triangle stage needs it
+    T best[MODE >= MODE_CLOSEST ? 3 : 1];  // closest Intersection so far / the any-hit candidate / box modes: {enter, exit} of the candidate
+    T tmax;                                // any-hit and box modes: end of the segment
     uint32_t best_prim;
     uint32_t r, cnt;
     bool fin;                              // all components finite → NaN-free slab test is exact
@@ -129,17 +140,17 @@ template <typename T, int MODE> struct LaneRay {
         for (int k = 0; k < 3; k++) { o[k] = 0; inv[k] = 0; }
         d[0] = 0; best[0] = 0; tmax = 0; best_prim = NONE; r = NONE; cnt = 0; fin = true;
     }
-    // tmaxs: WalkOut::tmax (any-hit mode only)
+    // tmaxs: WalkOut::tmax (any-hit and box modes only)
     __device__ __forceinline__ void load(const typename Traits<T>::Ray* __restrict__ rays, uint32_t ray, const T* __restrict__ tmaxs = nullptr) {
         const typename Traits<T>::Ray* rp = rays + ray;
 #pragma unroll
         for (int k = 0; k < 3; k++) { o[k] = rp->o[k]; inv[k] = rp->inv[k]; }
-        if (MODE >= MODE_TRIANGLES) {
+        if (mode_tris(MODE)) {
 #pragma unroll
             for (int k = 0; k < 3; k++) d[k] = rp->d[k];
         }
         if (MODE >= MODE_CLOSEST) { best[0] = Traits<T>::inf(); best[1] = 0; best[2] = 0; }
-        if (MODE == MODE_ANY) tmax = tmaxs ? tmaxs[ray] : Traits<T>::inf();
+        if (mode_tmax(MODE)) tmax = tmaxs ? tmaxs[ray] : Traits<T>::inf();
         best_prim = NONE; r = ray; cnt = 0;
         fin = ray_is_finite<T>(o, inv);
     }
@@ -150,7 +161,10 @@ template <typename T, int MODE> struct LaneRay {
     }
     // the ray has left the tree: its Vec / closest hit is complete
     __device__ __forceinline__ void retire(const WalkOut<T>& w) {
-        if (MODE >= MODE_CLOSEST) {
+        if (mode_box(MODE)) {
+            w.closest[2 * (size_t)r] = best[0]; w.closest[2 * (size_t)r + 1] = best[1];
+            w.closest_prim[r] = best_prim;
+        } else if (MODE >= MODE_CLOSEST) {
             w.closest[3 * (size_t)r] = best[0]; w.closest[3 * (size_t)r + 1] = best[1]; w.closest[3 * (size_t)r + 2] = best[2];
             w.closest_prim[r] = best_prim;
         } else {
@@ -176,13 +190,14 @@ __device__ __forceinline__ void pool_invalidate_tail(HitRec* pool, unsigned long
 }
 
 // A leaf box was hit (rec) in some lanes of the wave: do what the MODE asks for with the shape.
+// t0 / t1: the box's t-slice (slab_hit's outputs) where the MODE returns or compares it (T_SLICE and the box modes).
 template <typename T, int MODE>
 __device__ __forceinline__ void report(bool rec, uint32_t shape, T t0, T t1, LaneRay<T, MODE>& ray, const WalkOut<T>& w,
                                        PoolCursor& pc, int lane, unsigned long long lt) {
     const unsigned long long m = __ballot(rec);
     if (!m) return;
     T vals[3] = {t0, t1, 0};
-    if (MODE >= MODE_TRIANGLES && rec) ray_triangle<T>(ray.o, ray.d, w.tris + 9 * (size_t)shape, vals);
+    if (mode_tris(MODE) && rec) ray_triangle<T>(ray.o, ray.d, w.tris + 9 * (size_t)shape, vals);
     if (MODE == MODE_CLOSEST) {
         if (rec) {
             if (vals[0] < ray.best[0]) { ray.best[0] = vals[0]; ray.best[1] = vals[1]; ray.best[2] = vals[2]; ray.best_prim = shape; }
@@ -192,6 +207,12 @@ __device__ __forceinline__ void report(bool rec, uint32_t shape, T t0, T t1, Lan
     }
     if (MODE == MODE_ANY) {   // the first candidate inside the segment ends the ray (the walk sees best_prim != NONE and empties the lane)
         if (rec && vals[0] < ray.tmax) { ray.best[0] = vals[0]; ray.best[1] = vals[1]; ray.best[2] = vals[2]; ray.best_prim = shape; }
+        return;
+    }
+    if (mode_box(MODE)) {
+        // a candidate enters its box before the segment ends (strict, in T: a NaN, zero or negative tmax admits nothing).  Closest: strictly
+        // nearer than the lane's best so far, so that on equal entries the first of the list stays; first: it ends the ray like MODE_ANY
+        if (rec && t0 < ray.tmax && (MODE == MODE_BOX_FIRST || t0 < ray.best[0])) { ray.best[0] = t0; ray.best[1] = t1; ray.best_prim = shape; }
         return;
     }
     constexpr int NV = ModeVals<MODE>::N;

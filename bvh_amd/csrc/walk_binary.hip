@@ -25,8 +25,9 @@ __global__ __launch_bounds__(256) void k_traverse(const TravNode<T>* __restrict_
     uint32_t i = active ? 0u : n_trav;
     PoolCursor pc;
     unsigned long long steps = 0, leaf_steps = 0, wsteps = 0;
-    // wave-uniform: every ray of this wave is finite → the NaN-free slab test (common.hpp) is exact
-    const bool fast = MODE != MODE_T_SLICE && !__any(active && !ray.fin);
+    // wave-uniform: every ray of this wave is finite → the NaN-free slab test (common.hpp) is exact (it does not return the t-slice, which
+    // T_SLICE and the box modes need of every leaf)
+    const bool fast = MODE != MODE_T_SLICE && !mode_box(MODE) && !__any(active && !ray.fin);
     while (true) {
         const bool run = i < n_trav;
         if (!__any(run)) break;
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(256) void k_traverse(const TravNode<T>* __restrict_
             if (STATS) { steps++; leaf_steps += leaf ? 1 : 0; }
         }
         report<T, MODE>(rec, shape, t0, t1, ray, w, pc, lane, lt);
-        if (MODE == MODE_ANY && ray.best_prim != NONE) i = n_trav;   // occluded: the ray is done
+        if (mode_first(MODE) && ray.best_prim != NONE) i = n_trav;   // occluded: the ray is done
     }
     const unsigned long long cands = active ? ray.cnt : 0;
     if (active) ray.retire(w);
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(LDS_THREADS) void k_traverse_lds(const TravNode<T>*
             }
             if (!__any(run)) break;
         }
-        const bool fast = MODE != MODE_T_SLICE && !__any(run && !ray.fin);   // wave-uniform
+        const bool fast = MODE != MODE_T_SLICE && !mode_box(MODE) && !__any(run && !ray.fin);   // wave-uniform
         // ---- LDS_INNER walk steps
         for (int s = 0; s < LDS_INNER; s++) {
             bool rec = false;
@@ -201,7 +202,7 @@ __global__ __launch_bounds__(LDS_THREADS) void k_traverse_lds(const TravNode<T>*
                 if (STATS) { steps++; leaf_steps += leaf ? 1 : 0; }
             }
             report<T, MODE>(rec, shape, t0, t1, ray, w, pc, lane, lt);
-            if (MODE == MODE_ANY && ray.best_prim != NONE) i = limit;   // occluded: retired at the next refill
+            if (mode_first(MODE) && ray.best_prim != NONE) i = limit;   // occluded: retired at the next refill
         }
     }
     walk_epilogue<T, MODE>(w, pc, lane, STATS, steps, leaf_steps, wsteps, cands);
@@ -264,6 +265,8 @@ void launch_binary(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, size
         case MODE_T_SLICE: if (stats) WALK(MODE_T_SLICE, true); else WALK(MODE_T_SLICE, false); break;
         case MODE_TRIANGLES: if (stats) WALK(MODE_TRIANGLES, true); else WALK(MODE_TRIANGLES, false); break;
         case MODE_ANY: WALK(MODE_ANY, false); break;
+        case MODE_BOX_CLOSEST: WALK(MODE_BOX_CLOSEST, false); break;
+        case MODE_BOX_FIRST: WALK(MODE_BOX_FIRST, false); break;
         default: if (stats) WALK(MODE_CLOSEST, true); else WALK(MODE_CLOSEST, false); break;
     }
 #undef WALK

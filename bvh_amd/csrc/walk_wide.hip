@@ -462,23 +462,25 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES) void k_traverse_wide(
             if (MODE == MODE_INDICES && ITEMS_LOG4 == 0 && w.pool_pair)   // (wave-uniform) a retiring ray's unpaired last hit
                 report_pair(false, !run && item != NONE, 0u, ray, pair_pend, w.pool_pair, w.pool_cap, w.ctr, pc, lane, lt);
             if (!run && item != NONE) {   // the item has left the tree: its part of the ray's list is complete
-                if (MODE == MODE_ANY) {
+                if (mode_first(MODE)) {
                     if constexpr (ITEMS_LOG4 == 0) {
                         const size_t r = item;
-                        w.closest[3 * r] = ray.best[0]; w.closest[3 * r + 1] = ray.best[1]; w.closest[3 * r + 2] = ray.best[2];
+                        if constexpr (mode_box(MODE)) { w.closest[2 * r] = ray.best[0]; w.closest[2 * r + 1] = ray.best[1]; }
+                        else { w.closest[3 * r] = ray.best[0]; w.closest[3 * r + 1] = ray.best[1]; w.closest[3 * r + 2] = ray.best[2]; }
                         w.closest_prim[r] = ray.best_prim;
                     } else if (ray.best_prim != NONE) {
                         // The ray's list is the concatenation of its items' lists in item order, and this lane stopped at its item's first
                         // candidate inside the segment: the ray's answer is the candidate of the LOWEST item that found one.  Item (< 16) and
-                        // shape (< 2^28: WIDE_MAX_SHAPES) fit one 32-bit key: one atomicMin; k_any_resolve recomputes the Intersection.
+                        // shape (< 2^28: WIDE_MAX_SHAPES) fit one 32-bit key: one atomicMin; k_any_resolve recomputes the Intersection (k_box_resolve the t-slice).
                         const uint32_t j = item & ((1u << WIDE_ITEM_BITS) - 1u);
                         const uint32_t jj = j == WIDE_ITEM_WHOLE ? 0u : j;
                         atomicMin(&w.any_key[item >> WIDE_ITEM_BITS], (jj << 28) | ray.best_prim);
                     }
-                } else if (MODE == MODE_CLOSEST) {
+                } else if (MODE == MODE_CLOSEST || MODE == MODE_BOX_CLOSEST) {   // (box: the distance is the entry parameter, non-negative — the same keys and slots)
                     if constexpr (ITEMS_LOG4 == 0) {
                         const size_t r = item;
-                        if constexpr (!GUIDE_CLOSEST) { w.closest[3 * r] = ray.best[0]; w.closest[3 * r + 1] = ray.best[1]; w.closest[3 * r + 2] = ray.best[2]; }
+                        if constexpr (mode_box(MODE)) { w.closest[2 * r] = ray.best[0]; w.closest[2 * r + 1] = ray.best[1]; }
+                        else if constexpr (!GUIDE_CLOSEST) { w.closest[3 * r] = ray.best[0]; w.closest[3 * r + 1] = ray.best[1]; w.closest[3 * r + 2] = ray.best[2]; }
                         w.closest_prim[r] = ray.best_prim;   // (guide: the shape only — k_closest_from_prim recomputes its Intersection in f64)
                     } else if (ray.best_prim != NONE) {
                         // The ray's other items sit in other lanes: the nearest candidate of the RAY is the minimum over its items of (distance, item
@@ -608,6 +610,14 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES) void k_traverse_wide(
                     rec = false;
                 }
             }
+            T t0 = 0, t1 = 0;
+            if constexpr (mode_box(MODE)) {   // the leaf stage of the box modes: the literal t-slice of the shape's own AABB (the wide node that held it is gone,
+                if (rec) {                    // and the NaN-free test that found it does not return the slice) — the same boolean, so rec stands
+                    const T* b = w.box(shape);
+                    const T mn[3] = {b[0], b[1], b[2]}, mx[3] = {b[3], b[4], b[5]};
+                    slab_hit<T>(ray.o, ray.inv, mn, mx, t0, t1);
+                }
+            }
             if constexpr (GUIDE_CLOSEST) {   // (wave-uniform skip, like the f64 box test above: candidates are rare)
                 if (__any(rec)) {
                     if (rec) {
@@ -617,8 +627,8 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES) void k_traverse_wide(
                     }
                 }
             } else if (MODE == MODE_INDICES && ITEMS_LOG4 == 0 && w.pool_pair) report_pair(rec, false, shape, ray, pair_pend, w.pool_pair, w.pool_cap, w.ctr, pc, lane, lt);   // (wave-uniform)
-            else report<T, MODE>(rec, shape, (T)0, (T)0, ray, w, pc, lane, lt);
-            if (MODE == MODE_ANY && ray.best_prim != NONE) { cur = CUR_NONE; sp = 0; }   // occluded: the item retires at the next refill
+            else report<T, MODE>(rec, shape, t0, t1, ray, w, pc, lane, lt);
+            if (mode_first(MODE) && ray.best_prim != NONE) { cur = CUR_NONE; sp = 0; }   // occluded: the item retires at the next refill
         }
         if (ovf) { cur = CUR_NONE; sp = 0; }
     }
@@ -784,6 +794,8 @@ void launch_wide_walk(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
         case MODE_INDICES: launch_wide_items<T, MODE_INDICES>(t, rays_dev, n_rays, w, h, items_log4, ovf_flag, early_items); break;
         case MODE_TRIANGLES: launch_wide_items<T, MODE_TRIANGLES>(t, rays_dev, n_rays, w, h, items_log4, ovf_flag, early_items); break;
         case MODE_ANY: launch_wide_items<T, MODE_ANY>(t, rays_dev, n_rays, w, h, items_log4, ovf_flag, false); break;
+        case MODE_BOX_CLOSEST: launch_wide_items<T, MODE_BOX_CLOSEST>(t, rays_dev, n_rays, w, h, items_log4, ovf_flag, false); break;
+        case MODE_BOX_FIRST: launch_wide_items<T, MODE_BOX_FIRST>(t, rays_dev, n_rays, w, h, items_log4, ovf_flag, false); break;
         default: launch_wide_items<T, MODE_CLOSEST>(t, rays_dev, n_rays, w, h, items_log4, ovf_flag, false); break;
     }
 }

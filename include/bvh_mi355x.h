@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define BVHGPU_ABI_VERSION 7 /* 7: bvhgpu_host_alloc/free/register/unregister, bvhgpu_traverse_host_*, bvhgpu_build_traverse_host_*, bvhgpu_traverse_host_indices, bvhgpu_query_f32/_f64 + BVHGPU_QUERY_AABB/_POINT/_BALL, bvhgpu_traverse_any_f32/_f64 + bvhgpu_hits_fetch_any, bvhgpu_knearest_f32/_f64 + BVHGPU_KNN_MAX_K, BVHGPU_TUNE_COUNT 23 (slots 17 = HOST_CHUNKS, 18 = WIDE_MIN_RAYS_PER_WG, 19 = HOST_ZERO_COPY, 20 = BUILD_LEVEL_TILE, 21 = FLATTEN_INLINE, 22 = QUERY_VARIANT).  6: BVHGPU_TUNE_COUNT 17 (slots 15 = FLATTEN_LAZY, 16 = BUILD_LEVEL_PERSIST), bvhgpu_hits_walk_kernel.  5: bvhgpu_rccl_info.  4: BVHGPU_TUNE_COUNT 15 (slot 14 = WIDE_F64_GUIDE), bvhgpu_hits_walk_info.  3: BVHGPU_REBROADCAST, broadcast status header, scene blob BVH6 (exact_only), BVHGPU_TUNE_COUNT 14 (slots 11 = WIDE_EARLY_ITEMS, 12 = WIDE_STAGE_SHIFT, 13 = WIDE_REC8), BVHGPU_TRAVERSE_RAYS_READY, bvhgpu_device_alloc/free/copy */
+#define BVHGPU_ABI_VERSION 7 /* 7: bvhgpu_host_alloc/free/register/unregister, bvhgpu_traverse_host_*, bvhgpu_build_traverse_host_*, bvhgpu_traverse_host_indices, bvhgpu_query_f32/_f64 + BVHGPU_QUERY_AABB/_POINT/_BALL, bvhgpu_traverse_any_f32/_f64 + bvhgpu_hits_fetch_any, bvhgpu_traverse_box_f32/_f64 + bvhgpu_hits_fetch_box + BVHGPU_TRAVERSE_FIRST, bvhgpu_knearest_f32/_f64 + BVHGPU_KNN_MAX_K, BVHGPU_TUNE_COUNT 23 (slots 17 = HOST_CHUNKS, 18 = WIDE_MIN_RAYS_PER_WG, 19 = HOST_ZERO_COPY, 20 = BUILD_LEVEL_TILE, 21 = FLATTEN_INLINE, 22 = QUERY_VARIANT).  6: BVHGPU_TUNE_COUNT 17 (slots 15 = FLATTEN_LAZY, 16 = BUILD_LEVEL_PERSIST), bvhgpu_hits_walk_kernel.  5: bvhgpu_rccl_info.  4: BVHGPU_TUNE_COUNT 15 (slot 14 = WIDE_F64_GUIDE), bvhgpu_hits_walk_info.  3: BVHGPU_REBROADCAST, broadcast status header, scene blob BVH6 (exact_only), BVHGPU_TUNE_COUNT 14 (slots 11 = WIDE_EARLY_ITEMS, 12 = WIDE_STAGE_SHIFT, 13 = WIDE_REC8), BVHGPU_TRAVERSE_RAYS_READY, bvhgpu_device_alloc/free/copy */
 #define BVHGPU_NONE 0xFFFFFFFFu /* u32::MAX marker (flat_bvh.rs:51-53, :124, :137) */
 
 typedef enum {
@@ -88,6 +88,7 @@ typedef enum { BVHGPU_HOST = 0, BVHGPU_DEVICE = 1 } bvhgpu_mem;
                                         instead of two: the copy engines idle 10 - 20 µs between two transfers */
 #define BVHGPU_TRAVERSE_COHERENT 16u /* hint: neighbouring rays are similar (primary rays).  Large whole-ray batches then hand their hits over
                                         through per-ray slots instead of pool records (BVHGPU_TUNE_WIDE_STAGE_SHIFT); results never depend on it */
+#define BVHGPU_TRAVERSE_FIRST 1024u /* bvhgpu_traverse_box_* only: the first candidate of the ray's list instead of the one entered first */
 
 /* ---- POD layouts (little-endian, natural alignment, no packing pragmas) ---- */
 
@@ -471,6 +472,33 @@ int bvhgpu_traverse_any_f32(bvhgpu_tree *tree, const bvhgpu_ray_f32 *rays, const
 int bvhgpu_traverse_any_f64(bvhgpu_tree *tree, const bvhgpu_ray_f64 *rays, const double *tmax, size_t n_rays, int mem, unsigned flags,
                             bvhgpu_hits **hits);
 int bvhgpu_hits_fetch_any(bvhgpu_hits *hits, void *isect, uint32_t *shape, int mem);
+
+/* ---- closest-hit and any-hit ray queries against the shapes' own boxes: "which shape's box does the ray enter first?" / "is anything in the
+ * way before tmax?" for trees without triangles (voxel worlds, box scenes, picking / visibility over sphere bounds).
+ * Ray i comes with tmax[i] in the tree's dtype.  A NULL tmax means +inf for every ray.
+ *  - L_i is the list FlatBvh::traverse(&ray_i, shapes) returns (flat_bvh.rs:396-431), in its order.  This is the engine's CSR row.
+ *  - For s in L_i, (enter_s, exit_s) is Ray::intersection_slice_for_aabb (ray_impl.rs:118-145) on shape s's AABB as the tree holds it.  These
+ *    are the same values BVHGPU_TRAVERSE_T_SLICE returns for that hit.
+ *  - The slab test and the slice share one condition (!nan && tmx >= max(tmn, 0)).  So the slice is Some for every member of L_i.
+ *  - enter_s is never NaN, never negative and never -0.  max(tmn, 0) returns +0.
+ * A shape s is a candidate iff enter_s < tmax[i].  The comparison is strict and done in T.  So a NaN, zero or negative tmax admits nothing,
+ * and tmax == enter_s does not admit s.
+ *  - closest (default): the candidate with the smallest enter_s.  On equal enter_s the first one in L_i order wins.
+ *  - first (BVHGPU_TRAVERSE_FIRST, any-hit): the first candidate in L_i order.  Every walk may stop at it.
+ * Per ray the result is {enter, exit} (2 T) and the shape index.  With no candidate it is {+inf, 0} and BVHGPU_NONE.  bvhgpu_hits_info's
+ * `total` is the number of rays with a candidate.  No triangles are needed or read.  The definition holds for every tree the CSR walks
+ * accept: built here, refitted, imported / broadcast, an uploaded FlatBvh whose shapes moved (leaf tests use the shape AABBs), trees with
+ * empty child bounds (a split without SAH winner).
+ * `rays` and `tmax` live in `mem` (HOST tmax is staged into the result object).  `flags`: BVHGPU_TRAVERSE_COHERENT (a hint) and
+ * BVHGPU_TRAVERSE_FIRST; every other bit → BVHGPU_INVALID_ARG.  Tree not flattened → BVHGPU_NOT_FLATTENED; another dtype than the tree's →
+ * BVHGPU_DTYPE_MISMATCH; n_rays = 0 and an empty tree are fine.  Synchronises like bvhgpu_traverse_any_*.  _fetch / _fetch_triangles /
+ * _fetch_closest / _fetch_any / _device return BVHGPU_INVALID_ARG on such a result, and bvhgpu_hits_fetch_box on any other.
+ * bvhgpu_hits_fetch_box: per ray {enter, exit} (n x 2 T) and the shape (n u32); either may be NULL. */
+int bvhgpu_traverse_box_f32(bvhgpu_tree *tree, const bvhgpu_ray_f32 *rays, const float *tmax, size_t n_rays, int mem, unsigned flags,
+                            bvhgpu_hits **hits);
+int bvhgpu_traverse_box_f64(bvhgpu_tree *tree, const bvhgpu_ray_f64 *rays, const double *tmax, size_t n_rays, int mem, unsigned flags,
+                            bvhgpu_hits **hits);
+int bvhgpu_hits_fetch_box(bvhgpu_hits *hits, void *slice, uint32_t *shape, int mem);
 
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */

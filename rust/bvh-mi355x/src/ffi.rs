@@ -29,6 +29,7 @@ pub const BVHGPU_TRAVERSE_STATS: c_uint = 2;
 pub const BVHGPU_TRAVERSE_TRIANGLES: c_uint = 4;
 pub const BVHGPU_TRAVERSE_CLOSEST: c_uint = 8;
 pub const BVHGPU_TRAVERSE_COHERENT: c_uint = 16;
+pub const BVHGPU_TRAVERSE_FIRST: c_uint = 1024;
 pub const BVHGPU_TRAVERSE_NEAREST_FIRST: c_uint = 32;
 pub const BVHGPU_TRAVERSE_FARTHEST_FIRST: c_uint = 64;
 pub const BVHGPU_TRAVERSE_BEST_FIRST: c_uint = 128;
@@ -181,6 +182,9 @@ extern "C" {
     pub fn bvhgpu_traverse_any_f32(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_traverse_any_f64(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_hits_fetch_any(h: *mut bvhgpu_hits, isect: *mut c_void, shape: *mut u32, mem: c_int) -> c_int;
+    pub fn bvhgpu_traverse_box_f32(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_traverse_box_f64(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_hits_fetch_box(h: *mut bvhgpu_hits, slice: *mut c_void, shape: *mut u32, mem: c_int) -> c_int;
     // timing, scene ingest, tuning
     pub fn bvhgpu_enable_timing(ctx: *mut bvhgpu_ctx, on: c_int) -> c_int;
     pub fn bvhgpu_last_timings(ctx: *mut bvhgpu_ctx, out: *mut bvhgpu_timings) -> c_int;

@@ -91,6 +91,8 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
     #[allow(clippy::too_many_arguments)]
     unsafe fn traverse_any(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
     #[allow(clippy::too_many_arguments)]
+    unsafe fn traverse_box(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
+    #[allow(clippy::too_many_arguments)]
     unsafe fn knearest(t: *mut ffi::bvhgpu_tree, points: *const Self, n: usize, mem: c_int, kind: c_int, k: u32, out_shape: *mut u32, out_dist: *mut Self) -> c_int;
     #[allow(clippy::too_many_arguments)]
     unsafe fn knearest_tree(t: *mut ffi::bvhgpu_tree, points: *const Self, n: usize, mem: c_int, kind: c_int, k: u32, max_dist: *const Self, out_shape: *mut u32, out_dist: *mut Self) -> c_int;
@@ -103,7 +105,7 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
 
 macro_rules! impl_gpu_scalar {
     ($t:ty, $dtype:expr, $node:ident, $flat:ident, $ray:ident, $build_flat:ident, $rebuild_flat:ident, $refit:ident, $traverse:ident,
-     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $knearest:ident, $knearest_tree:ident,
+     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $traverse_box:ident, $knearest:ident, $knearest_tree:ident,
      $flat_ctor:expr) => {
         impl GpuScalar for $t {
             type Node = ffi::$node;
@@ -142,6 +144,9 @@ macro_rules! impl_gpu_scalar {
             }
             unsafe fn traverse_any(t: *mut ffi::bvhgpu_tree, rays: *const ffi::$ray, tmax: *const $t, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int {
                 ffi::$traverse_any(t, rays, tmax, n, mem, flags, hits)
+            }
+            unsafe fn traverse_box(t: *mut ffi::bvhgpu_tree, rays: *const ffi::$ray, tmax: *const $t, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int {
+                ffi::$traverse_box(t, rays, tmax, n, mem, flags, hits)
             }
             unsafe fn knearest(t: *mut ffi::bvhgpu_tree, points: *const $t, n: usize, mem: c_int, kind: c_int, k: u32, out_shape: *mut u32, out_dist: *mut $t) -> c_int {
                 ffi::$knearest(t, points, n, mem, kind, k, out_shape, out_dist)
@@ -187,11 +192,11 @@ macro_rules! impl_gpu_scalar {
 }
 impl_gpu_scalar!(f32, ffi::BVHGPU_F32, bvhgpu_node_f32, bvhgpu_flat_f32, bvhgpu_ray_f32, bvhgpu_build_flat_f32, bvhgpu_rebuild_flat_f32,
                  bvhgpu_refit_f32, bvhgpu_traverse_f32, bvhgpu_tree_set_triangles_f32, bvhgpu_tree_from_flat_f32,
-                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_knearest_f32, bvhgpu_knearest_tree_f32,
+                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_traverse_box_f32, bvhgpu_knearest_f32, bvhgpu_knearest_tree_f32,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f32 { min, max, entry, exit, shape });
 impl_gpu_scalar!(f64, ffi::BVHGPU_F64, bvhgpu_node_f64, bvhgpu_flat_f64, bvhgpu_ray_f64, bvhgpu_build_flat_f64, bvhgpu_rebuild_flat_f64,
                  bvhgpu_refit_f64, bvhgpu_traverse_f64, bvhgpu_tree_set_triangles_f64, bvhgpu_tree_from_flat_f64,
-                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_knearest_f64, bvhgpu_knearest_tree_f64,
+                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_traverse_box_f64, bvhgpu_knearest_f64, bvhgpu_knearest_tree_f64,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f64 { min, max, entry, exit, shape, _pad: 0 });
 
 fn aabb_to_6<T: GpuScalar>(b: &Aabb<T, 3>) -> [T; 6] {
@@ -231,6 +236,14 @@ pub struct BatchHits {
 /// `distance == +inf` when the ray hits nothing
 pub struct ClosestHit<T> {
     pub intersection: Intersection<T>,
+    pub shape: u32,
+}
+
+/// Result of a ray query against the shapes' own boxes (`GpuBvh::traverse_box`): `Ray::intersection_slice_for_aabb`'s `(enter, exit)` on the
+/// winning shape's AABB and that shape; `shape == u32::MAX`, `enter == +inf` and `exit == 0` when the ray has no candidate
+pub struct BoxHit<T> {
+    pub enter: T,
+    pub exit: T,
     pub shape: u32,
 }
 
@@ -474,6 +487,28 @@ impl<T: GpuScalar> GpuBvh<T> {
     /// `traverse_any` reduced to one flag per ray: does segment i hit any triangle
     pub fn occluded(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>) -> Vec<bool> {
         self.traverse_any(rays, tmax).iter().map(|h| h.shape != ffi::BVHGPU_NONE).collect()
+    }
+
+    /// Ray queries against the shapes' own boxes, no triangles needed (`bvhgpu_traverse_box_*`): per ray, among the shapes of
+    /// `FlatBvh::traverse`'s list whose `Ray::intersection_slice_for_aabb` entry is `< tmax[i]` (strict; `tmax: None` = +inf for every ray),
+    /// the one entered first — the first of the list on equal entries — or, with `first`, the first of the list (any-hit: every walk stops
+    /// at it).
+    pub fn traverse_box(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>, first: bool) -> Vec<BoxHit<T>> {
+        if let Some(tm) = tmax {
+            assert_eq!(tm.len(), rays.len(), "one tmax per ray");
+        }
+        let r: Vec<T::RayC> = rays.iter().map(T::ray_to_ffi).collect();
+        let mut hits = core::ptr::null_mut();
+        let mut slice = vec![[T::default(); 2]; rays.len()];
+        let mut shape = vec![0u32; rays.len()];
+        let tp = tmax.map_or(core::ptr::null(), |t| t.as_ptr());
+        let flags = if first { ffi::BVHGPU_TRAVERSE_FIRST } else { 0 };
+        unsafe {
+            check(self.ctx, T::traverse_box(self.tree, r.as_ptr(), tp, r.len(), ffi::BVHGPU_HOST, flags, &mut hits));
+            check(self.ctx, ffi::bvhgpu_hits_fetch_box(hits, slice.as_mut_ptr() as *mut c_void, shape.as_mut_ptr(), ffi::BVHGPU_HOST));
+            ffi::bvhgpu_hits_destroy(hits);
+        }
+        slice.iter().zip(shape).map(|(t, s)| BoxHit { enter: t[0], exit: t[1], shape: s }).collect()
     }
 
     /// The `k` nearest shapes of every point (`bvhgpu_knearest_*`): the loop of `FlatBvh::nearest_to` (src/flat_bvh.rs:524-558) with a list of

@@ -712,53 +712,15 @@ class _TreeBase:
         check(fn(self._t, ptr(p), len(p), HOST, 1 if triangles else 0, ptr(shape), ptr(dist)), self.ctx._h)
         return shape, dist
 
-    def knearest_batch(self, points, k: int, triangles: bool = False):
-        """bvhgpu_knearest_*: the k nearest shapes of every point — the loop of nearest_to (flat_bvh.rs:524-558) with a list of at most k
-        (distance, shape) pairs in place of best_element, every comparison the strict <.  1 <= k <= _lib.KNN_MAX_K.  Shape distance as
-        for nearest_batch (triangles=True needs set_triangles; a point cloud is zero-size boxes with triangles=False).
-        points: (n, 3) in the tree's dtype — a numpy array (HOST) or a torch GPU tensor (DEVICE).
-        returns (shape[n, k], dist[n, k]): rows ascending in dist (a row that holds a NaN need not be sorted), equal distances in leaf
-        pre-order; slots beyond the number of shapes hold NONE and +inf.  numpy in: numpy out, shape as uint32.  torch in: torch tensors on
-        the same device, written by the kernel with no host round trip, shape as torch.int32 — so NONE reads as -1 there."""
-        fn = getattr(_lib.load(), f"bvhgpu_knearest_{self.sfx}")
-        ft = np.float32 if self.sfx == "f32" else np.float64
-        k = int(k)
-        rows = k if 1 <= k <= _lib.KNN_MAX_K else 0       # (out of range: the engine answers INVALID_ARG before it touches a buffer)
-        kind = 1 if triangles else 0
-        if _is_device_tensor(points):
-            import torch
-            if str(points.dtype) != ("torch.float32" if self.sfx == "f32" else "torch.float64"):
-                raise BvhGpuError(_lib.DTYPE_MISMATCH, "point dtype differs from tree dtype")
-            p = points.contiguous()
-            n = p.numel() // 3
-            shape = torch.empty((n, rows), dtype=torch.int32, device=p.device)
-            dist = torch.empty((n, rows), dtype=p.dtype, device=p.device)
-            torch.cuda.current_stream(p.device).synchronize()   # the engine works on its own stream: the points must be there
-            check(fn(self._t, ptr(p.data_ptr()), n, DEVICE, kind, k & 0xFFFFFFFF, ptr(shape.data_ptr()), ptr(dist.data_ptr())), self.ctx._h)
-            return shape, dist
-        if isinstance(points, np.ndarray) and points.dtype != ft:
-            raise BvhGpuError(_lib.DTYPE_MISMATCH, "point dtype differs from tree dtype")
-        p = np.ascontiguousarray(points, dtype=ft).reshape(-1, 3)
-        shape = np.zeros((len(p), rows), dtype=np.uint32)
-        dist = np.zeros((len(p), rows), dtype=ft)
-        check(fn(self._t, ptr(p), len(p), HOST, kind, k & 0xFFFFFFFF, ptr(shape), ptr(dist)), self.ctx._h)
-        return shape, dist
-
-    def knearest_tree_batch(self, points, k: int, triangles: bool = False, max_dist=None):
-        """bvhgpu_knearest_tree_*: the rows of knearest_batch found nearest child first — BvhNode::nearest_to_recursive (bvh_node.rs:327-374,
-        what Bvh::nearest_to calls) over the BvhNode array with the list of at most k (distance, shape) pairs in place of best_candidate.
-        With k = 1 and no max_dist a row is what Bvh::nearest_to returns.  Equal distances stay in the order this walk meets them, which is
-        not leaf pre-order: knearest_batch may order ties differently and pick differently among ties at the k-th distance.
-        max_dist: None, a scalar (the same limit for every point) or n values in the points' memory — a numpy array for numpy points, a torch
-        GPU tensor for tensor points.  Nothing farther than max_dist[i] enters row i (dist2 <= max_dist[i]^2); a negative or NaN limit gives
-        a row of padding.  The tree must have been built here (a Bvh or its flatten(); no flatten is needed): an uploaded FlatBvh or an
-        imported scene has no BvhNode array and raises INVALID_ARG.  points / returns: as knearest_batch."""
-        fn = getattr(_lib.load(), f"bvhgpu_knearest_tree_{self.sfx}")
+    def _knearest(self, entry: str, points, k: int, triangles: bool, max_dist, with_limit: bool):
+        """marshalling of knearest_batch (entry "knearest": no limit argument) and knearest_tree_batch ("knearest_tree": max_dist or NULL)"""
+        fn = getattr(_lib.load(), f"bvhgpu_{entry}_{self.sfx}")
         ft = np.float32 if self.sfx == "f32" else np.float64
         k = int(k)
         rows = k if 1 <= k <= _lib.KNN_MAX_K else 0       # (out of range: the engine answers INVALID_ARG before it touches a buffer)
         kind = 1 if triangles else 0
         scalar = max_dist is not None and not _is_device_tensor(max_dist) and np.ndim(max_dist) == 0
+        limit = (lambda mp: (mp,)) if with_limit else (lambda mp: ())   # (bvhgpu_knearest_* has no max_dist argument)
         if _is_device_tensor(points):
             import torch
             if str(points.dtype) != ("torch.float32" if self.sfx == "f32" else "torch.float64"):
@@ -781,7 +743,7 @@ class _TreeBase:
             shape = torch.empty((n, rows), dtype=torch.int32, device=p.device)
             dist = torch.empty((n, rows), dtype=p.dtype, device=p.device)
             torch.cuda.current_stream(p.device).synchronize()   # the engine works on its own stream: the points must be there
-            check(fn(self._t, ptr(p.data_ptr()), n, DEVICE, kind, k & 0xFFFFFFFF, mp, ptr(shape.data_ptr()), ptr(dist.data_ptr())), self.ctx._h)
+            check(fn(self._t, ptr(p.data_ptr()), n, DEVICE, kind, k & 0xFFFFFFFF, *limit(mp), ptr(shape.data_ptr()), ptr(dist.data_ptr())), self.ctx._h)
             return shape, dist
         if isinstance(points, np.ndarray) and points.dtype != ft:
             raise BvhGpuError(_lib.DTYPE_MISMATCH, "point dtype differs from tree dtype")
@@ -799,8 +761,29 @@ class _TreeBase:
             raise BvhGpuError(_lib.INVALID_ARG, f"max_dist has {m.size} values for {len(p)} points")
         shape = np.zeros((len(p), rows), dtype=np.uint32)
         dist = np.zeros((len(p), rows), dtype=ft)
-        check(fn(self._t, ptr(p), len(p), HOST, kind, k & 0xFFFFFFFF, ptr(m), ptr(shape), ptr(dist)), self.ctx._h)
+        check(fn(self._t, ptr(p), len(p), HOST, kind, k & 0xFFFFFFFF, *limit(ptr(m)), ptr(shape), ptr(dist)), self.ctx._h)
         return shape, dist
+
+    def knearest_batch(self, points, k: int, triangles: bool = False):
+        """bvhgpu_knearest_*: the k nearest shapes of every point — the loop of nearest_to (flat_bvh.rs:524-558) with a list of at most k
+        (distance, shape) pairs in place of best_element, every comparison the strict <.  1 <= k <= _lib.KNN_MAX_K.  Shape distance as
+        for nearest_batch (triangles=True needs set_triangles; a point cloud is zero-size boxes with triangles=False).
+        points: (n, 3) in the tree's dtype — a numpy array (HOST) or a torch GPU tensor (DEVICE).
+        returns (shape[n, k], dist[n, k]): rows ascending in dist (a row that holds a NaN need not be sorted), equal distances in leaf
+        pre-order; slots beyond the number of shapes hold NONE and +inf.  numpy in: numpy out, shape as uint32.  torch in: torch tensors on
+        the same device, written by the kernel with no host round trip, shape as torch.int32 — so NONE reads as -1 there."""
+        return self._knearest("knearest", points, k, triangles, None, False)
+
+    def knearest_tree_batch(self, points, k: int, triangles: bool = False, max_dist=None):
+        """bvhgpu_knearest_tree_*: the rows of knearest_batch found nearest child first — BvhNode::nearest_to_recursive (bvh_node.rs:327-374,
+        what Bvh::nearest_to calls) over the BvhNode array with the list of at most k (distance, shape) pairs in place of best_candidate.
+        With k = 1 and no max_dist a row is what Bvh::nearest_to returns.  Equal distances stay in the order this walk meets them, which is
+        not leaf pre-order: knearest_batch may order ties differently and pick differently among ties at the k-th distance.
+        max_dist: None, a scalar (the same limit for every point) or n values in the points' memory — a numpy array for numpy points, a torch
+        GPU tensor for tensor points.  Nothing farther than max_dist[i] enters row i (dist2 <= max_dist[i]^2); a negative or NaN limit gives
+        a row of padding.  The tree must have been built here (a Bvh or its flatten(); no flatten is needed): an uploaded FlatBvh or an
+        imported scene has no BvhNode array and raises INVALID_ARG.  points / returns: as knearest_batch."""
+        return self._knearest("knearest_tree", points, k, triangles, max_dist, True)
 
     def nearest_to(self, query, shapes: Sequence, triangles: bool = False):
         """BoundingHierarchy::nearest_to (bounding_hierarchy.rs:262-336): Option<(&Shape, distance)>."""

@@ -2457,8 +2457,8 @@ template <typename T> void build_finalize(bvhgpu_tree* t) {
     uint32_t* pin = reinterpret_cast<uint32_t*>(t->pin);
     if (pin[CTR_FLAGS] & BUILD_FLAG_NONFINITE) {
         t->flattened = false;
-        t->failed_gen = t->gen; t->failed_what = "NONFINITE";   // (batches already enqueued on this generation walked nothing: their waits say so)
-        throw HipFail{hipErrorInvalidValue, "NONFINITE", __LINE__};
+        t->failed_gen = t->gen; t->failed_what = Fail::NonFinite;   // (batches already enqueued on this generation walked nothing: their waits say so)
+        throw HipFail{hipErrorInvalidValue, nullptr, __LINE__, Fail::NonFinite};
     }
     if (t->pend_persist && (pin[CTR_FLAGS] & BUILD_FLAG_PERSIST_GAVE_UP)) {
         // the persistent level tier left the tree unfinished: the same generation again with a launch per level (this tree stays with that)

@@ -21,28 +21,27 @@ template <typename F> int guarded(bvhgpu_ctx* ctx, F&& f) {
     try {
         return f();
     } catch (const HipFail& e) {
+        switch (e.kind) {
+            case Fail::None: break;
+            case Fail::Overflow: return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-1 hits in one batch");
+            case Fail::NonFinite:
+                return fail(ctx, BVHGPU_INVALID_ARG, "shape AABBs contain NaN or infinity (or their centroid extent overflows): the reference panics on "
+                                                     "such input (bvh_node.rs:214-217, to_usize().unwrap()); nothing was built");
+            case Fail::Rebroadcast:
+                return fail(ctx, BVHGPU_REBROADCAST, "the tree was broadcast before its build was finalized and the build then needed the slow path (unbalanced tree): "
+                                                     "this rank's tree and results are complete, the peers' are not — every rank calls bvhgpu_bcast_known again");
+            case Fail::RecvRebroadcast:
+                return fail(ctx, BVHGPU_REBROADCAST, "the root broadcast its tree before the build was finalized and the build was not complete: nothing usable was "
+                                                     "received — every rank calls bvhgpu_bcast_known again");
+            case Fail::RecvInvalid:
+                return fail(ctx, BVHGPU_INVALID_ARG, "the broadcast's root reported that it had no valid tree to send (its own call returned the reason); nothing was received");
+            case Fail::RecvGarbled: return fail(ctx, BVHGPU_RCCL_ERROR, "the broadcast header did not arrive intact");
+            case Fail::StaleTree: return fail(ctx, BVHGPU_INVALID_ARG, "the tree changed before the asynchronous batch was completed");
+            case Fail::OrderedDepth: return fail(ctx, BVHGPU_OVERFLOW, "tree deeper than the ordered iterator's 32-entry stack (child_distance_traverse.rs:36)");
+        }
         char buf[512];
         snprintf(buf, sizeof buf, "%s failed: %s (line %d)", e.what, hipGetErrorString(e.err), e.line);
-        if (e.what && std::strcmp(e.what, "OVERFLOW") == 0) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-1 hits in one batch");
-        if (e.what && std::strcmp(e.what, "NONFINITE") == 0)
-            return fail(ctx, BVHGPU_INVALID_ARG, "shape AABBs contain NaN or infinity (or their centroid extent overflows): the reference panics on "
-                                                 "such input (bvh_node.rs:214-217, to_usize().unwrap()); nothing was built");
-        if (e.what && std::strcmp(e.what, "REBROADCAST") == 0)
-            return fail(ctx, BVHGPU_REBROADCAST, "the tree was broadcast before its build was finalized and the build then needed the slow path (unbalanced tree): "
-                                                 "this rank's tree and results are complete, the peers' are not — every rank calls bvhgpu_bcast_known again");
-        if (e.what && std::strcmp(e.what, "RECV_REBROADCAST") == 0)
-            return fail(ctx, BVHGPU_REBROADCAST, "the root broadcast its tree before the build was finalized and the build was not complete: nothing usable was "
-                                                 "received — every rank calls bvhgpu_bcast_known again");
-        if (e.what && std::strcmp(e.what, "RECV_INVALID") == 0)
-            return fail(ctx, BVHGPU_INVALID_ARG, "the broadcast's root reported that it had no valid tree to send (its own call returned the reason); nothing was received");
-        if (e.what && std::strcmp(e.what, "RECV_GARBLED") == 0)
-            return fail(ctx, BVHGPU_RCCL_ERROR, "the broadcast header did not arrive intact");
-        if (e.what && std::strcmp(e.what, "STALE_TREE") == 0)
-            return fail(ctx, BVHGPU_INVALID_ARG, "the tree changed before the asynchronous batch was completed");
-        if (e.what && std::strcmp(e.what, "ORDERED_DEPTH") == 0)
-            return fail(ctx, BVHGPU_OVERFLOW, "tree deeper than the ordered iterator's 32-entry stack (child_distance_traverse.rs:36)");
-        if (e.err == hipErrorOutOfMemory) return fail(ctx, BVHGPU_OOM, buf);
-        return fail(ctx, BVHGPU_HIP_ERROR, buf);
+        return fail(ctx, e.err == hipErrorOutOfMemory ? BVHGPU_OOM : BVHGPU_HIP_ERROR, buf);
     } catch (const std::bad_alloc&) {
         return fail(ctx, BVHGPU_OOM, "host allocation failed");
     } catch (...) {
@@ -67,23 +66,6 @@ void copy_out(bvhgpu_ctx* ctx, void* dst, const void* src_dev, size_t bytes, int
     BVH_HIP(hipStreamSynchronize(ctx->stream));
 }
 
-void free_tree_buffers(bvhgpu_tree* t) {
-    if (t->flat_beside && t->ctx && t->ctx->side) { (void)hipStreamSynchronize(t->ctx->side); t->flat_beside = false; }
-    t->aabbs.release(); t->nodes.release(); t->node_start.release(); t->node_count.release();
-    t->xbar.release(); t->shape_node.release(); t->flat.release(); t->trav.release(); t->slot_entry.release(); t->node_slot.release(); t->tris.release();
-    t->idx[0].release(); t->idx[1].release(); t->bk.release(); t->lvbuf.release();
-    t->big[0].release(); t->big[1].release(); t->mid2.release(); t->small.release();
-    t->stats[0].release(); t->stats[1].release();
-    t->tile_item[0].release(); t->tile_item[1].release(); t->tile_cnt.release(); t->chunk_cnt.release(); t->ctr.release(); t->refit_seg.release();
-    t->wide.release(); t->wslot_node.release(); t->wide_guide.release(); t->guide_info.release();
-    t->bstat.release();
-    if (t->ev_flat0) { (void)hipEventDestroy(t->ev_flat0); t->ev_flat0 = nullptr; }
-    if (t->ev_flat) { (void)hipEventDestroy(t->ev_flat); t->ev_flat = nullptr; }
-    if (t->ev_top) { (void)hipEventDestroy(t->ev_top); t->ev_top = nullptr; }
-    if (t->pin) { (void)hipHostFree(t->pin); t->pin = nullptr; }
-    if (t->pin_recv) { (void)hipHostFree(t->pin_recv); t->pin_recv = nullptr; }
-}
-
 // an asynchronous build may still be in flight: wait for it and finish / validate it (build.hip build_finalize); likewise a
 // broadcast that was received on the stream (comm.hip recv_finalize: its status header tells whether the root's tree was good)
 void ensure_built(bvhgpu_tree* t) {
@@ -91,7 +73,17 @@ void ensure_built(bvhgpu_tree* t) {
     if (!t->pending_build) return;
     const bool sent_early = t->bcast_gen == t->gen;   // bvhgpu_bcast_known went out before this finalize (optimistic)
     if (t->dtype == BVHGPU_F32) build_finalize<float>(t); else build_finalize<double>(t);
-    if (sent_early && t->redone_gen == t->gen) throw HipFail{hipErrorNotReady, "REBROADCAST", __LINE__};
+    if (sent_early && t->redone_gen == t->gen) throw HipFail{hipErrorNotReady, nullptr, __LINE__, Fail::Rebroadcast};
+}
+// ... for a caller that replaces the tree's contents: what the previous build or receive came to no longer matters (a failed HIP call does)
+void ensure_built_ignoring_outcome(bvhgpu_tree* t) {
+    try { ensure_built(t); }
+    catch (const HipFail& e) {
+        switch (e.kind) {
+            case Fail::Rebroadcast: case Fail::NonFinite: case Fail::RecvRebroadcast: case Fail::RecvInvalid: case Fail::RecvGarbled: break;
+            default: throw;
+        }
+    }
 }
 int settle(bvhgpu_tree* t) {   // entry points that look at a tree's state first complete its asynchronous build
     if (!t->pending_build && !t->pending_recv) return BVHGPU_OK;
@@ -121,13 +113,13 @@ void finish_hits(bvhgpu_hits* h) {
     if (!t) return;   // empty batch
     bool rebroadcast = false;
     try { ensure_built(t); }
-    catch (const HipFail& e) { if (e.what && std::strcmp(e.what, "REBROADCAST") == 0) rebroadcast = true; else throw; }
+    catch (const HipFail& e) { if (e.kind == Fail::Rebroadcast) rebroadcast = true; else throw; }
     // the generation this batch walked turned out to hold nothing (NaN / inf input, a broadcast whose root had no valid tree) and the
     // error may have been consumed elsewhere — bvhgpu_tree_wait, a rebuild that replaces the tree, another result object's wait: the
     // wait of THIS batch still returns what the synchronous call would have returned, never lists from an unbuilt tree
-    if (t->failed_gen != 0 && t->failed_gen == h->pend_gen) throw HipFail{hipErrorInvalidValue, t->failed_what ? t->failed_what : "NONFINITE", __LINE__};
+    if (t->failed_gen != 0 && t->failed_gen == h->pend_gen) throw HipFail{hipErrorInvalidValue, nullptr, __LINE__, t->failed_what != Fail::None ? t->failed_what : Fail::NonFinite};
     bool replay = h->pend_on_pending && h->pend_gen == t->gen && (t->redone_gen == h->pend_gen || (h->pend_wide && t->exact_only));
-    if (h->pend_gen != t->gen) throw HipFail{hipErrorInvalidValue, "STALE_TREE", __LINE__};   // (rebuild / import settle the waiters first: unreachable)
+    if (h->pend_gen != t->gen) throw HipFail{hipErrorInvalidValue, nullptr, __LINE__, Fail::StaleTree};   // (rebuild / import settle the waiters first: unreachable)
     const void* rays = h->pend_rays;
     for (;;) {
         if (!replay && traverse_check(h)) break;
@@ -137,7 +129,7 @@ void finish_hits(bvhgpu_hits* h) {
         else traverse_enqueue<double>(t, static_cast<const bvhgpu_ray_f64*>(rays), h->n_rays, h->flags, h);
         BVH_HIP(hipStreamSynchronize(ctx->stream));
     }
-    if (rebroadcast) throw HipFail{hipErrorNotReady, "REBROADCAST", __LINE__};   // this rank's result is complete; the peers' trees are not
+    if (rebroadcast) throw HipFail{hipErrorNotReady, nullptr, __LINE__, Fail::Rebroadcast};   // this rank's result is complete; the peers' trees are not
 }
 // Before a tree's arrays are overwritten or freed (rebuild, refit, import, broadcast receive, destroy): the asynchronous batches
 // that were enqueued on it are completed first, so that a replay never runs on the wrong tree and no result object keeps a
@@ -161,8 +153,7 @@ template <typename T> int do_build(bvhgpu_tree* t, const T* aabbs, size_t n, int
     if (n > MAX_SHAPES) return fail(ctx, BVHGPU_OVERFLOW, "too many shapes for u32 flat indices");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "bad mem kind");
     use_device(ctx);
-    try { ensure_built(t); }   // a previous asynchronous build of this tree (its outcome no longer matters: everything is rebuilt)
-    catch (const HipFail& e) { if (!e.what || (std::strcmp(e.what, "REBROADCAST") != 0 && std::strcmp(e.what, "NONFINITE") != 0 && std::strncmp(e.what, "RECV_", 5) != 0)) throw; }
+    ensure_built_ignoring_outcome(t);   // a previous asynchronous build of this tree (its outcome no longer matters: everything is rebuilt)
     settle_waiters_impl(t);
     if (ctx->timing) BVH_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
     const T* dev = aabbs;
@@ -205,6 +196,21 @@ template <typename T> int do_refit(bvhgpu_tree* t, const T* aabbs, size_t n, int
     return BVHGPU_OK;
 }
 
+// bvhgpu_rebuild*_f32 / _f64 and bvhgpu_refit_f32 / _f64: the tree must be of the entry point's dtype
+template <typename T> int tree_is(bvhgpu_tree* t) {
+    if (!t) return BVHGPU_INVALID_ARG;
+    if (t->dtype != Traits<T>::dtype) return fail(t->ctx, BVHGPU_DTYPE_MISMATCH, t->dtype == BVHGPU_F64 ? "tree is f64" : "tree is f32");
+    return BVHGPU_OK;
+}
+template <typename T> int rebuild(bvhgpu_tree* t, const T* aabbs, size_t n, int mem, bool flat, bool async) {
+    const int rc = tree_is<T>(t);
+    return rc != BVHGPU_OK ? rc : guarded(t->ctx, [&] { return do_build<T>(t, aabbs, n, mem, flat, async); });
+}
+template <typename T> int refit(bvhgpu_tree* t, const T* aabbs, size_t n, int mem) {
+    const int rc = tree_is<T>(t);
+    return rc != BVHGPU_OK ? rc : guarded(t->ctx, [&] { return do_refit<T>(t, aabbs, n, mem); });
+}
+
 template <typename T> int new_build(bvhgpu_ctx* ctx, const T* aabbs, size_t n, int mem, bvhgpu_tree** out, bool flat = false) {
     if (!ctx || !out) return fail(ctx, BVHGPU_INVALID_ARG, "ctx/out is NULL");
     *out = nullptr;
@@ -212,24 +218,59 @@ template <typename T> int new_build(bvhgpu_ctx* ctx, const T* aabbs, size_t n, i
     t->ctx = ctx;
     t->dtype = Traits<T>::dtype;
     int rc = guarded(ctx, [&] { return do_build<T>(t, aabbs, n, mem, flat); });
-    if (rc != BVHGPU_OK) { free_tree_buffers(t); delete t; return rc; }
+    if (rc != BVHGPU_OK) { delete t; return rc; }
     *out = t;
     return BVHGPU_OK;
+}
+
+// ---- result-object batches: bvhgpu_traverse_* / _traverse_async_* / _traverse_any_* / _traverse_box_* / _query_* ----------------------
+// What a family tests between batch_open and batch_refusal — its flags, `mem`, the wait for the tree's build — stays in the family:
+// the families differ there on purpose (an any-hit batch refuses bad flags before it settles the tree, a ray batch does not), and
+// which refusal a caller gets when two apply is part of the interface.
+int batch_open(bvhgpu_tree* tree, bvhgpu_hits** hits) {
+    if (!tree) return BVHGPU_INVALID_ARG;
+    if (!hits) return fail(tree->ctx, BVHGPU_INVALID_ARG, "hits is NULL");
+    return BVHGPU_OK;
+}
+// the refusals every family shares, in the order every family reports them (input_missing: the family's own test of its input pointer)
+template <typename T>
+int batch_refusal(bvhgpu_tree* tree, bvhgpu_hits* const* hits, const char* noun, const char* plural, bool input_missing, const char* missing_msg, size_t n) {
+    bvhgpu_ctx* ctx = tree->ctx;
+    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
+    if (tree->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, std::string("tree dtype differs from ") + noun + " dtype");
+    if (!tree->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    if (input_missing) return fail(ctx, BVHGPU_INVALID_ARG, missing_msg);
+    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, std::string("more than 2^32-2 ") + plural + " in one batch");
+    return BVHGPU_OK;
+}
+// the caller's result object, made if there is none yet
+bvhgpu_hits* batch_hits(bvhgpu_hits** hits) {
+    bvhgpu_hits* h = *hits;
+    if (!h) h = new bvhgpu_hits();
+    *hits = h;
+    h->pend_kind = 0; h->pend_queries = nullptr; h->pend_qwide = false;   // (the object may have held a query batch)
+    return h;
+}
+// per-ray segment ends of an any-hit / box batch.  tmax == NULL: +inf for every ray.  HOST tmax is staged into the result object, so that
+// a replay (wide-walk stack overflow) reads it again.
+template <typename T> void stage_tmax(bvhgpu_ctx* ctx, bvhgpu_hits* h, const T* tmax, size_t n_rays, int mem) {
+    const T* tmax_dev = tmax;
+    if (tmax && n_rays && mem == BVHGPU_HOST) {
+        h->tmaxbuf.reserve(n_rays * sizeof(T));
+        BVH_HIP(hipMemcpyAsync(h->tmaxbuf.p, tmax, n_rays * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        tmax_dev = h->tmaxbuf.as<T>();
+    }
+    h->pend_tmax = tmax_dev;
 }
 
 template <typename T>
 int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n_rays, int mem, unsigned flags,
                 bvhgpu_hits** hits, bool async = false) {
-    if (!tree) return BVHGPU_INVALID_ARG;
+    { const int rc = batch_open(tree, hits); if (rc != BVHGPU_OK) return rc; }
     bvhgpu_ctx* ctx = tree->ctx;
-    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
     if (!async) { const int rc = settle(tree); if (rc != BVHGPU_OK) return rc; }
     else if (mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "asynchronous traversal takes rays that are resident in HBM");
-    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
-    if (tree->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from ray dtype");
-    if (!tree->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
-    if (n_rays && !rays) return fail(ctx, BVHGPU_INVALID_ARG, "rays is NULL");
-    if (n_rays >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 rays in one batch");
+    { const int rc = batch_refusal<T>(tree, hits, "ray", "rays", n_rays && !rays, "rays is NULL", n_rays); if (rc != BVHGPU_OK) return rc; }
     if ((flags & (BVHGPU_TRAVERSE_TRIANGLES | BVHGPU_TRAVERSE_CLOSEST)) && !tree->has_tris)
         return fail(ctx, BVHGPU_INVALID_ARG, "TRIANGLES / CLOSEST need bvhgpu_tree_set_triangles first");
     if ((flags & BVHGPU_TRAVERSE_T_SLICE) && (flags & (BVHGPU_TRAVERSE_TRIANGLES | BVHGPU_TRAVERSE_CLOSEST)))
@@ -248,12 +289,9 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
     flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT);   // (internal: only bvhgpu_traverse_any_* / bvhgpu_traverse_box_* set them)
     return guarded(ctx, [&] {
         use_device(ctx);
-        bvhgpu_hits* h = *hits;
-        if (!h) h = new bvhgpu_hits();
-        *hits = h;
+        bvhgpu_hits* h = batch_hits(hits);
         const auto* dev = static_cast<const typename Traits<T>::Ray*>(
             to_device(ctx, rays, n_rays * sizeof(typename Traits<T>::Ray), mem, ctx->upload));
-        h->pend_kind = 0; h->pend_queries = nullptr; h->pend_qwide = false;   // (the object may have held a query batch)
         if (async) {
             h->force_binary = false; h->pend_attempts = 0; h->deferred_rc = 0; h->replays = 0;
             h->pend_gen = tree->gen; h->pend_on_pending = tree->pending_build || tree->pending_recv;
@@ -267,103 +305,59 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
     });
 }
 
-// bvhgpu_traverse_any_*: per ray the first candidate of FlatBvh::traverse's list whose triangle distance is < tmax[i] (traverse.hip MODE_ANY).
-// tmax == NULL: +inf for every ray.  HOST tmax is staged into the result object, so that a replay (wide-walk stack overflow) reads it again.
+// bvhgpu_traverse_any_* and bvhgpu_traverse_box_*: one result per ray among the candidates of FlatBvh::traverse's list below tmax[i].
+//   any-hit (kind_bit TRAVERSE_ANY_HIT, traverse.hip MODE_ANY): the first candidate whose triangle distance is < tmax[i]; needs triangles.
+//   box hit (kind_bit TRAVERSE_BOX_HIT, MODE_BOX_CLOSEST / MODE_BOX_FIRST): the shape whose own AABB the ray enters first — or, with
+//   BVHGPU_TRAVERSE_FIRST, the first one of the list — among those with enter < tmax[i].  No triangles are needed or read.
 template <typename T>
-int do_traverse_any(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, const T* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits) {
-    if (!tree) return BVHGPU_INVALID_ARG;
+int do_traverse_tmax(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, const T* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits,
+                     unsigned allowed_flags, const char* flags_msg, unsigned kind_bit, const char* tris_msg) {   // tris_msg == NULL: no triangles needed
+    { const int rc = batch_open(tree, hits); if (rc != BVHGPU_OK) return rc; }
     bvhgpu_ctx* ctx = tree->ctx;
-    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
-    if (flags & ~BVHGPU_TRAVERSE_COHERENT) return fail(ctx, BVHGPU_INVALID_ARG, "any-hit flags: 0 or BVHGPU_TRAVERSE_COHERENT");
+    if (flags & ~allowed_flags) return fail(ctx, BVHGPU_INVALID_ARG, flags_msg);
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
     { const int rc = settle(tree); if (rc != BVHGPU_OK) return rc; }
-    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
-    if (tree->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from ray dtype");
-    if (!tree->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
-    if (n_rays && !rays) return fail(ctx, BVHGPU_INVALID_ARG, "rays is NULL");
-    if (n_rays >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 rays in one batch");
-    if (!tree->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "any-hit queries need bvhgpu_tree_set_triangles first");
+    { const int rc = batch_refusal<T>(tree, hits, "ray", "rays", n_rays && !rays, "rays is NULL", n_rays); if (rc != BVHGPU_OK) return rc; }
+    if (tris_msg && !tree->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, tris_msg);
     return guarded(ctx, [&] {
         use_device(ctx);
-        bvhgpu_hits* h = *hits;
-        if (!h) h = new bvhgpu_hits();
-        *hits = h;
+        bvhgpu_hits* h = batch_hits(hits);
         const auto* dev = static_cast<const typename Traits<T>::Ray*>(
             to_device(ctx, rays, n_rays * sizeof(typename Traits<T>::Ray), mem, ctx->upload));
-        h->pend_kind = 0; h->pend_queries = nullptr; h->pend_qwide = false;   // (the object may have held a query batch)
-        const T* tmax_dev = tmax;
-        if (tmax && n_rays && mem == BVHGPU_HOST) {
-            h->tmaxbuf.reserve(n_rays * sizeof(T));
-            BVH_HIP(hipMemcpyAsync(h->tmaxbuf.p, tmax, n_rays * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-            tmax_dev = h->tmaxbuf.as<T>();
-        }
-        h->pend_tmax = tmax_dev;
-        traverse_batch<T>(tree, dev, n_rays, flags | TRAVERSE_ANY_HIT, h);
+        stage_tmax<T>(ctx, h, tmax, n_rays, mem);
+        traverse_batch<T>(tree, dev, n_rays, flags | kind_bit, h);
         return (int)BVHGPU_OK;
     });
 }
-
-// bvhgpu_traverse_box_*: per ray the shape of FlatBvh::traverse's list whose own AABB the ray enters first — or, with BVHGPU_TRAVERSE_FIRST, the first
-// one of the list — among those with enter < tmax[i] (traverse.hip MODE_BOX_CLOSEST / MODE_BOX_FIRST).  No triangles are needed or read.
-// tmax is handled as in do_traverse_any.
+template <typename T>
+int do_traverse_any(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, const T* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_traverse_tmax<T>(tree, rays, tmax, n_rays, mem, flags, hits, BVHGPU_TRAVERSE_COHERENT, "any-hit flags: 0 or BVHGPU_TRAVERSE_COHERENT",
+                               TRAVERSE_ANY_HIT, "any-hit queries need bvhgpu_tree_set_triangles first");
+}
 template <typename T>
 int do_traverse_box(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, const T* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits) {
-    if (!tree) return BVHGPU_INVALID_ARG;
-    bvhgpu_ctx* ctx = tree->ctx;
-    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
-    if (flags & ~(BVHGPU_TRAVERSE_COHERENT | BVHGPU_TRAVERSE_FIRST)) return fail(ctx, BVHGPU_INVALID_ARG, "box-hit flags: BVHGPU_TRAVERSE_COHERENT and BVHGPU_TRAVERSE_FIRST only");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    { const int rc = settle(tree); if (rc != BVHGPU_OK) return rc; }
-    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
-    if (tree->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from ray dtype");
-    if (!tree->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
-    if (n_rays && !rays) return fail(ctx, BVHGPU_INVALID_ARG, "rays is NULL");
-    if (n_rays >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 rays in one batch");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        bvhgpu_hits* h = *hits;
-        if (!h) h = new bvhgpu_hits();
-        *hits = h;
-        const auto* dev = static_cast<const typename Traits<T>::Ray*>(
-            to_device(ctx, rays, n_rays * sizeof(typename Traits<T>::Ray), mem, ctx->upload));
-        h->pend_kind = 0; h->pend_queries = nullptr; h->pend_qwide = false;   // (the object may have held a query batch)
-        const T* tmax_dev = tmax;
-        if (tmax && n_rays && mem == BVHGPU_HOST) {
-            h->tmaxbuf.reserve(n_rays * sizeof(T));
-            BVH_HIP(hipMemcpyAsync(h->tmaxbuf.p, tmax, n_rays * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-            tmax_dev = h->tmaxbuf.as<T>();
-        }
-        h->pend_tmax = tmax_dev;
-        traverse_batch<T>(tree, dev, n_rays, flags | TRAVERSE_BOX_HIT, h);
-        return (int)BVHGPU_OK;
-    });
+    return do_traverse_tmax<T>(tree, rays, tmax, n_rays, mem, flags, hits, BVHGPU_TRAVERSE_COHERENT | BVHGPU_TRAVERSE_FIRST,
+                               "box-hit flags: BVHGPU_TRAVERSE_COHERENT and BVHGPU_TRAVERSE_FIRST only", TRAVERSE_BOX_HIT, nullptr);
 }
 
 // bvhgpu_query_*: an AABB / point / ball batch (query.hip).  queries == NULL: the tree's own shape AABBs (self-overlap).
 template <typename T>
 int do_query(bvhgpu_tree* tree, int kind, const T* queries, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
-    if (!tree) return BVHGPU_INVALID_ARG;
+    { const int rc = batch_open(tree, hits); if (rc != BVHGPU_OK) return rc; }
     bvhgpu_ctx* ctx = tree->ctx;
-    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
     if (kind != BVHGPU_QUERY_AABB && kind != BVHGPU_QUERY_POINT && kind != BVHGPU_QUERY_BALL) return fail(ctx, BVHGPU_INVALID_ARG, "unknown query kind");
     if (flags != 0) return fail(ctx, BVHGPU_INVALID_ARG, "query flags are reserved (0)");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
     { const int rc = settle(tree); if (rc != BVHGPU_OK) return rc; }
-    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
-    if (tree->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from query dtype");
-    if (!tree->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
     const bool self = queries == nullptr;
-    if (self && !(kind == BVHGPU_QUERY_AABB && n == tree->n))
-        return fail(ctx, BVHGPU_INVALID_ARG, "queries is NULL: only BVHGPU_QUERY_AABB with n = the tree's shape count (self-overlap)");
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 queries in one batch");
+    { const int rc = batch_refusal<T>(tree, hits, "query", "queries", self && !(kind == BVHGPU_QUERY_AABB && n == tree->n),
+                                      "queries is NULL: only BVHGPU_QUERY_AABB with n = the tree's shape count (self-overlap)", n); if (rc != BVHGPU_OK) return rc; }
     if (tree->exact_only && !tree->built && !tree->unfolded)
         return fail(ctx, BVHGPU_INVALID_ARG, "an imported tree whose build had a split without SAH winner: its leaves' navigator boxes were folded away");
     const size_t per = kind == BVHGPU_QUERY_AABB ? 6 : (kind == BVHGPU_QUERY_POINT ? 3 : 4);
     return guarded(ctx, [&] {
         use_device(ctx);
-        bvhgpu_hits* h = *hits;
-        if (!h) h = new bvhgpu_hits();
-        *hits = h;
+        bvhgpu_hits* h = batch_hits(hits);
         const T* dev = self ? tree->aabbs.as<T>() : queries;
         if (!self && mem == BVHGPU_HOST && n) {   // staged into the result object: a replay reads them again
             h->qbuf.reserve(n * per * sizeof(T));
@@ -400,6 +394,21 @@ int do_rays_new(bvhgpu_ctx* ctx, const T* origins, const T* dirs, size_t n, int 
         if (mem_out == BVHGPU_HOST) copy_out(ctx, out, outd, n * sizeof(Ray), BVHGPU_HOST);
         return (int)BVHGPU_OK;
     });
+}
+
+// bvhgpu_gen_rays_* / bvhgpu_gen_primary_rays_*: rays written straight into HBM
+void gen_rays(bvhgpu_ctx* ctx, uint64_t first, size_t n, const float bounds[6], bvhgpu_ray_f32* out_dev) { gen_rays_f32(ctx, first, n, bounds, out_dev); }
+void gen_rays(bvhgpu_ctx* ctx, uint64_t first, size_t n, const float bounds[6], bvhgpu_ray_f64* out_dev) { gen_rays_f64(ctx, first, n, bounds, out_dev); }
+template <typename Ray> int do_gen_rays(bvhgpu_ctx* ctx, uint64_t first, size_t n, const float bounds[6], Ray* out_dev) {
+    if (!ctx || !bounds || (n && !out_dev)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
+    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "too many rays in one call");
+    return guarded(ctx, [&] { use_device(ctx); gen_rays(ctx, first, n, bounds, out_dev); return (int)BVHGPU_OK; });
+}
+template <typename T>
+int do_gen_primary(bvhgpu_ctx* ctx, const float cam[14], uint32_t width, uint32_t height, uint64_t first, size_t n, typename Traits<T>::Ray* out_dev) {
+    if (!ctx || !cam || (n && !out_dev) || !width || !height) return fail(ctx, BVHGPU_INVALID_ARG, "bad argument");
+    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "too many rays in one call");
+    return guarded(ctx, [&] { use_device(ctx); gen_primary<T>(ctx, cam, width, height, first, n, out_dev); return (int)BVHGPU_OK; });
 }
 
 // ---- FlatBvh upload: convert the reference layout to the engine layout on the host (a marshalling
@@ -483,7 +492,7 @@ int tree_from_flat(bvhgpu_ctx* ctx, const typename Traits<T>::Flat* flat, size_t
         BVH_HIP(hipStreamSynchronize(ctx->stream));
         return (int)BVHGPU_OK;
     });
-    if (rc != BVHGPU_OK) { free_tree_buffers(t); delete t; return rc; }
+    if (rc != BVHGPU_OK) { delete t; return rc; }
     t->built = false; t->flattened = true; t->unfolded = true; t->lazy_flat = false;
     *out = t;
     return BVHGPU_OK;
@@ -512,81 +521,28 @@ int do_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays, const T* tris
     });
 }
 
+// ---- point batches: bvhgpu_nearest_* / bvhgpu_knearest_* / bvhgpu_knearest_tree_* --------------------------------------------------
+// One set of rules and one staging layout (points | max_dist | dist | shape); bvhgpu_nearest_* is k = 1 without limits, and only the
+// nearest-first descent takes max_dist.  That descent reads the BvhNode array (a tree built here, flattened or not); the other two walks
+// read the flattened arrays.
+enum class PointWalk { Nearest, KNearest, KNearestTree };
 template <typename T>
-int do_nearest(bvhgpu_tree* t, const T* points, size_t n, int mem, int kind, uint32_t* out_shape, T* out_dist) {
+int do_points(bvhgpu_tree* t, PointWalk walk, const T* points, size_t n, int mem, int kind, uint32_t k, const T* max_dist, uint32_t* out_shape, T* out_dist) {
     if (!t) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = t->ctx;
     { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
     if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from point dtype");
-    if (!t->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
-    if (n && (!points || !out_shape || !out_dist)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
-    if (kind != 0 && kind != 1) return fail(ctx, BVHGPU_INVALID_ARG, "shape kind must be 0 (AABB) or 1 (triangle)");
-    if (kind == 1 && !t->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "triangle distance needs bvhgpu_tree_set_triangles first");
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "too many points in one call");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        const T* pd = points; uint32_t* sd = out_shape; T* dd = out_dist;
-        if (mem == BVHGPU_HOST) {
-            const size_t pb = n * 3 * sizeof(T), sb = n * 4, db = n * sizeof(T);
-            ctx->upload.reserve(pb + sb + db + 64);
-            char* base = ctx->upload.as<char>();
-            if (pb) BVH_HIP(hipMemcpyAsync(base, points, pb, hipMemcpyHostToDevice, ctx->stream));
-            pd = reinterpret_cast<const T*>(base); dd = reinterpret_cast<T*>(base + pb); sd = reinterpret_cast<uint32_t*>(base + pb + db);
-        }
-        if (t->n == 0) {   // empty hierarchy → None for every query (flat_bvh.rs:518-520)
-            if (n) { BVH_HIP(hipMemsetAsync(sd, 0xFF, n * 4, ctx->stream)); BVH_HIP(hipMemsetAsync(dd, 0, n * sizeof(T), ctx->stream)); }
-        } else {
-            nearest_batch<T>(t, pd, n, kind, sd, dd);
-        }
-        if (mem == BVHGPU_HOST) { copy_out(ctx, out_dist, dd, n * sizeof(T), BVHGPU_HOST); copy_out(ctx, out_shape, sd, n * 4, BVHGPU_HOST); }
-        return (int)BVHGPU_OK;
-    });
-}
-
-// bvhgpu_knearest_*: do_nearest's rules with n x k outputs
-template <typename T>
-int do_knearest(bvhgpu_tree* t, const T* points, size_t n, int mem, int kind, uint32_t k, uint32_t* out_shape, T* out_dist) {
-    if (!t) return BVHGPU_INVALID_ARG;
-    bvhgpu_ctx* ctx = t->ctx;
-    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
-    if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from point dtype");
-    if (!t->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    if (walk == PointWalk::KNearestTree) {
+        if (!t->built) return fail(ctx, BVHGPU_INVALID_ARG, "the nearest-first descent needs a tree that was built here (uploaded and imported trees carry no BvhNode array)");
+    } else if (!t->flattened) {
+        return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    }
     if (k == 0 || k > BVHGPU_KNN_MAX_K) return fail(ctx, BVHGPU_INVALID_ARG, "k must be between 1 and BVHGPU_KNN_MAX_K");
     if (n && (!points || !out_shape || !out_dist)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
     if (kind != 0 && kind != 1) return fail(ctx, BVHGPU_INVALID_ARG, "shape kind must be 0 (AABB) or 1 (triangle)");
     if (kind == 1 && !t->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "triangle distance needs bvhgpu_tree_set_triangles first");
-    if (n >= 0xFFFFFFFFull || n * (size_t)k >= 0x100000000ull) return fail(ctx, BVHGPU_OVERFLOW, "too many results (points x k) in one call");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        const T* pd = points; uint32_t* sd = out_shape; T* dd = out_dist;
-        const size_t pb = n * 3 * sizeof(T), sb = n * k * 4, db = n * k * sizeof(T);
-        if (mem == BVHGPU_HOST) {
-            ctx->upload.reserve(pb + sb + db + 64);
-            char* base = ctx->upload.as<char>();
-            if (pb) BVH_HIP(hipMemcpyAsync(base, points, pb, hipMemcpyHostToDevice, ctx->stream));
-            pd = reinterpret_cast<const T*>(base); dd = reinterpret_cast<T*>(base + pb); sd = reinterpret_cast<uint32_t*>(base + pb + db);
-        }
-        knearest_batch<T>(t, pd, n, kind, k, sd, dd);
-        if (mem == BVHGPU_HOST) { copy_out(ctx, out_dist, dd, db, BVHGPU_HOST); copy_out(ctx, out_shape, sd, sb, BVHGPU_HOST); }
-        else BVH_HIP(hipStreamSynchronize(ctx->stream));   // the rows are complete when the call returns, whichever stream reads them next
-        return (int)BVHGPU_OK;
-    });
-}
-
-// bvhgpu_knearest_tree_*: do_knearest's rules, except that the walk reads the BvhNode array (a tree built here, flattened or not) and takes
-// an optional limit per point
-template <typename T>
-int do_knearest_tree(bvhgpu_tree* t, const T* points, size_t n, int mem, int kind, uint32_t k, const T* max_dist, uint32_t* out_shape, T* out_dist) {
-    if (!t) return BVHGPU_INVALID_ARG;
-    bvhgpu_ctx* ctx = t->ctx;
-    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
-    if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from point dtype");
-    if (!t->built) return fail(ctx, BVHGPU_INVALID_ARG, "the nearest-first descent needs a tree that was built here (uploaded and imported trees carry no BvhNode array)");
-    if (k == 0 || k > BVHGPU_KNN_MAX_K) return fail(ctx, BVHGPU_INVALID_ARG, "k must be between 1 and BVHGPU_KNN_MAX_K");
-    if (n && (!points || !out_shape || !out_dist)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
-    if (kind != 0 && kind != 1) return fail(ctx, BVHGPU_INVALID_ARG, "shape kind must be 0 (AABB) or 1 (triangle)");
-    if (kind == 1 && !t->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "triangle distance needs bvhgpu_tree_set_triangles first");
-    if (n >= 0xFFFFFFFFull || n * (size_t)k >= 0x100000000ull) return fail(ctx, BVHGPU_OVERFLOW, "too many results (points x k) in one call");
+    if (n >= 0xFFFFFFFFull || n * (size_t)k >= 0x100000000ull)
+        return fail(ctx, BVHGPU_OVERFLOW, walk == PointWalk::Nearest ? "too many points in one call" : "too many results (points x k) in one call");
     return guarded(ctx, [&] {
         use_device(ctx);
         const T* pd = points; const T* md = max_dist; uint32_t* sd = out_shape; T* dd = out_dist;
@@ -599,9 +555,15 @@ int do_knearest_tree(bvhgpu_tree* t, const T* points, size_t n, int mem, int kin
             pd = reinterpret_cast<const T*>(base); md = max_dist ? reinterpret_cast<const T*>(base + pb) : nullptr;
             dd = reinterpret_cast<T*>(base + pb + mb); sd = reinterpret_cast<uint32_t*>(base + pb + mb + db);
         }
-        knearest_tree_batch<T>(t, pd, n, kind, k, md, sd, dd);
+        if (walk == PointWalk::KNearestTree) knearest_tree_batch<T>(t, pd, n, kind, k, md, sd, dd);
+        else if (walk == PointWalk::KNearest) knearest_batch<T>(t, pd, n, kind, k, sd, dd);
+        else if (t->n == 0) {   // empty hierarchy → None for every query (flat_bvh.rs:518-520)
+            if (n) { BVH_HIP(hipMemsetAsync(sd, 0xFF, n * 4, ctx->stream)); BVH_HIP(hipMemsetAsync(dd, 0, n * sizeof(T), ctx->stream)); }
+        } else {
+            nearest_batch<T>(t, pd, n, kind, sd, dd);
+        }
         if (mem == BVHGPU_HOST) { copy_out(ctx, out_dist, dd, db, BVHGPU_HOST); copy_out(ctx, out_shape, sd, sb, BVHGPU_HOST); }
-        else BVH_HIP(hipStreamSynchronize(ctx->stream));   // the rows are complete when the call returns, whichever stream reads them next
+        else if (walk != PointWalk::Nearest) BVH_HIP(hipStreamSynchronize(ctx->stream));   // k-nearest: the rows are complete when the call returns, whichever stream reads them next
         return (int)BVHGPU_OK;
     });
 }
@@ -619,24 +581,6 @@ int do_knearest_tree(bvhgpu_tree* t, const T* points, size_t n, int mem, int kin
 //                  the previous batch had hits
 // and ONE host wait at the end.  A chunk that had to be replayed (hit pool too small on a first batch, a build that finished on the
 // slow path) sends its results again, in one piece.
-void free_host_batch(bvhgpu_ctx* ctx) {
-    HostBatch* hb = ctx->host;
-    if (!hb) return;
-    ctx->host = nullptr;
-    for (auto& h : hb->hits) if (h) { bvhgpu_hits_destroy(h); h = nullptr; }
-    for (auto& e : hb->ev_up) if (e) (void)hipEventDestroy(e);
-    for (auto& e : hb->ev_done) if (e) (void)hipEventDestroy(e);
-    if (hb->up) { (void)hipStreamSynchronize(hb->up); (void)hipStreamDestroy(hb->up); }
-    if (hb->up2) { (void)hipStreamSynchronize(hb->up2); (void)hipStreamDestroy(hb->up2); }
-    for (auto& e : hb->ev_up2) if (e) (void)hipEventDestroy(e);
-    if (hb->ev_main) (void)hipEventDestroy(hb->ev_main);
-    if (hb->ev_aabbs) (void)hipEventDestroy(hb->ev_aabbs);
-    hb->indices.release();
-    if (hb->down) { (void)hipStreamSynchronize(hb->down); (void)hipStreamDestroy(hb->down); }
-    hb->od.release(); hb->rays.release(); hb->offsets.release();
-    delete hb;
-}
-
 // the address under which the device sees a host range (pinned: bvhgpu_host_alloc / _register), or NULL for pageable memory
 template <typename U> U* dev_visible(U* p) {
     void* d = nullptr;
@@ -789,7 +733,7 @@ int host_batch_walk(bvhgpu_tree* tree, unsigned flags, uint32_t* offsets, uint32
         BVH_HIP(hipStreamSynchronize(hb.down));
         uint64_t tot = 0;
         for (int k = 0; k < K; k++) tot += hb.hits[k]->total;
-        if (tot > 0xFFFFFFFFull) throw HipFail{hipErrorInvalidValue, "OVERFLOW", __LINE__};
+        if (tot > 0xFFFFFFFFull) throw HipFail{hipErrorInvalidValue, nullptr, __LINE__, Fail::Overflow};
         if (replayed) {   // what went down came from an incomplete walk: rebase again, one copy
             for (int k = 0; k < K; k++) rebase_chunk(k);
             if (!hb.offsets_host) BVH_HIP(hipMemcpyAsync(offsets, offs_all, (n_rays + 1) * 4, hipMemcpyDeviceToHost, st));
@@ -845,8 +789,7 @@ int do_traverse_host(bvhgpu_tree* tree, const T* aabbs, size_t n_shapes, bool re
     return guarded(ctx, [&] {
         use_device(ctx);
         if (rebuild) {   // whatever is in flight on the tree is completed before its shape array is overwritten (as bvhgpu_rebuild_* does)
-            try { ensure_built(tree); }
-            catch (const HipFail& e) { if (!e.what || (std::strcmp(e.what, "REBROADCAST") != 0 && std::strcmp(e.what, "NONFINITE") != 0 && std::strncmp(e.what, "RECV_", 5) != 0)) throw; }
+            ensure_built_ignoring_outcome(tree);
             settle_waiters_impl(tree);
         }
         host_batch_init(ctx);
@@ -944,13 +887,6 @@ void bvhgpu_destroy(bvhgpu_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    free_host_batch(ctx);
-    ctx->upload.release();
-    ctx->counters.release();
-    for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
-    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
-    if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
-    if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
 
@@ -1013,27 +949,11 @@ int bvhgpu_build_f32(bvhgpu_ctx* ctx, const float* aabbs, size_t n, int mem, bvh
 int bvhgpu_build_f64(bvhgpu_ctx* ctx, const double* aabbs, size_t n, int mem, bvhgpu_tree** out) {
     return new_build<double>(ctx, aabbs, n, mem, out);
 }
-int bvhgpu_rebuild_f32(bvhgpu_tree* t, const float* aabbs, size_t n, int mem) {
-    if (!t) return BVHGPU_INVALID_ARG;
-    if (t->dtype != BVHGPU_F32) return fail(t->ctx, BVHGPU_DTYPE_MISMATCH, "tree is f64");
-    return guarded(t->ctx, [&] { return do_build<float>(t, aabbs, n, mem); });
-}
-int bvhgpu_rebuild_f64(bvhgpu_tree* t, const double* aabbs, size_t n, int mem) {
-    if (!t) return BVHGPU_INVALID_ARG;
-    if (t->dtype != BVHGPU_F64) return fail(t->ctx, BVHGPU_DTYPE_MISMATCH, "tree is f32");
-    return guarded(t->ctx, [&] { return do_build<double>(t, aabbs, n, mem); });
-}
+int bvhgpu_rebuild_f32(bvhgpu_tree* t, const float* aabbs, size_t n, int mem) { return rebuild<float>(t, aabbs, n, mem, false, false); }
+int bvhgpu_rebuild_f64(bvhgpu_tree* t, const double* aabbs, size_t n, int mem) { return rebuild<double>(t, aabbs, n, mem, false, false); }
 
-int bvhgpu_refit_f32(bvhgpu_tree* t, const float* aabbs, size_t n, int mem) {
-    if (!t) return BVHGPU_INVALID_ARG;
-    if (t->dtype != BVHGPU_F32) return fail(t->ctx, BVHGPU_DTYPE_MISMATCH, "tree is f64");
-    return guarded(t->ctx, [&] { return do_refit<float>(t, aabbs, n, mem); });
-}
-int bvhgpu_refit_f64(bvhgpu_tree* t, const double* aabbs, size_t n, int mem) {
-    if (!t) return BVHGPU_INVALID_ARG;
-    if (t->dtype != BVHGPU_F64) return fail(t->ctx, BVHGPU_DTYPE_MISMATCH, "tree is f32");
-    return guarded(t->ctx, [&] { return do_refit<double>(t, aabbs, n, mem); });
-}
+int bvhgpu_refit_f32(bvhgpu_tree* t, const float* aabbs, size_t n, int mem) { return refit<float>(t, aabbs, n, mem); }
+int bvhgpu_refit_f64(bvhgpu_tree* t, const double* aabbs, size_t n, int mem) { return refit<double>(t, aabbs, n, mem); }
 
 // FlatBvh::build (flat_bvh.rs:328-331) = Bvh::build + flatten in one call: one host round trip instead of two
 int bvhgpu_build_flat_f32(bvhgpu_ctx* ctx, const float* aabbs, size_t n, int mem, bvhgpu_tree** out) {
@@ -1042,28 +962,12 @@ int bvhgpu_build_flat_f32(bvhgpu_ctx* ctx, const float* aabbs, size_t n, int mem
 int bvhgpu_build_flat_f64(bvhgpu_ctx* ctx, const double* aabbs, size_t n, int mem, bvhgpu_tree** out) {
     return new_build<double>(ctx, aabbs, n, mem, out, true);
 }
-int bvhgpu_rebuild_flat_f32(bvhgpu_tree* t, const float* aabbs, size_t n, int mem) {
-    if (!t) return BVHGPU_INVALID_ARG;
-    if (t->dtype != BVHGPU_F32) return fail(t->ctx, BVHGPU_DTYPE_MISMATCH, "tree is f64");
-    return guarded(t->ctx, [&] { return do_build<float>(t, aabbs, n, mem, true); });
-}
-int bvhgpu_rebuild_flat_f64(bvhgpu_tree* t, const double* aabbs, size_t n, int mem) {
-    if (!t) return BVHGPU_INVALID_ARG;
-    if (t->dtype != BVHGPU_F64) return fail(t->ctx, BVHGPU_DTYPE_MISMATCH, "tree is f32");
-    return guarded(t->ctx, [&] { return do_build<double>(t, aabbs, n, mem, true); });
-}
+int bvhgpu_rebuild_flat_f32(bvhgpu_tree* t, const float* aabbs, size_t n, int mem) { return rebuild<float>(t, aabbs, n, mem, true, false); }
+int bvhgpu_rebuild_flat_f64(bvhgpu_tree* t, const double* aabbs, size_t n, int mem) { return rebuild<double>(t, aabbs, n, mem, true, false); }
 
 // ---- asynchronous step ----
-int bvhgpu_rebuild_flat_async_f32(bvhgpu_tree* t, const float* aabbs, size_t n, int mem) {
-    if (!t) return BVHGPU_INVALID_ARG;
-    if (t->dtype != BVHGPU_F32) return fail(t->ctx, BVHGPU_DTYPE_MISMATCH, "tree is f64");
-    return guarded(t->ctx, [&] { return do_build<float>(t, aabbs, n, mem, true, true); });
-}
-int bvhgpu_rebuild_flat_async_f64(bvhgpu_tree* t, const double* aabbs, size_t n, int mem) {
-    if (!t) return BVHGPU_INVALID_ARG;
-    if (t->dtype != BVHGPU_F64) return fail(t->ctx, BVHGPU_DTYPE_MISMATCH, "tree is f32");
-    return guarded(t->ctx, [&] { return do_build<double>(t, aabbs, n, mem, true, true); });
-}
+int bvhgpu_rebuild_flat_async_f32(bvhgpu_tree* t, const float* aabbs, size_t n, int mem) { return rebuild<float>(t, aabbs, n, mem, true, true); }
+int bvhgpu_rebuild_flat_async_f64(bvhgpu_tree* t, const double* aabbs, size_t n, int mem) { return rebuild<double>(t, aabbs, n, mem, true, true); }
 int bvhgpu_tree_wait(bvhgpu_tree* t) {
     if (!t) return BVHGPU_INVALID_ARG;
     return settle(t);
@@ -1095,7 +999,6 @@ void bvhgpu_tree_destroy(bvhgpu_tree* t) {
         (void)settle(t);
         settle_waiters_impl(t);
     }
-    free_tree_buffers(t);
     delete t;
 }
 
@@ -1279,7 +1182,7 @@ int bvhgpu_scene_import(bvhgpu_ctx* ctx, const void* src, size_t nbytes, int mem
         if (mem != BVHGPU_DEVICE) BVH_HIP(hipStreamSynchronize(ctx->stream));
         return (int)BVHGPU_OK;
     });
-    if (rc != BVHGPU_OK) { if (!given) { free_tree_buffers(t); delete t; } return rc; }
+    if (rc != BVHGPU_OK) { if (!given) delete t; return rc; }
     *out = t;
     return BVHGPU_OK;
 }
@@ -1291,48 +1194,36 @@ int bvhgpu_rays_new_f32(bvhgpu_ctx* ctx, const float* o, const float* d, size_t 
 int bvhgpu_rays_new_f64(bvhgpu_ctx* ctx, const double* o, const double* d, size_t n, int mem_in, bvhgpu_ray_f64* out, int mem_out) {
     return do_rays_new<double>(ctx, o, d, n, mem_in, out, mem_out);
 }
-int bvhgpu_gen_rays_f32(bvhgpu_ctx* ctx, uint64_t first, size_t n, const float bounds[6], bvhgpu_ray_f32* out_dev) {
-    if (!ctx || !bounds || (n && !out_dev)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "too many rays in one call");
-    return guarded(ctx, [&] { use_device(ctx); gen_rays_f32(ctx, first, n, bounds, out_dev); return (int)BVHGPU_OK; });
-}
-int bvhgpu_gen_rays_f64(bvhgpu_ctx* ctx, uint64_t first, size_t n, const float bounds[6], bvhgpu_ray_f64* out_dev) {
-    if (!ctx || !bounds || (n && !out_dev)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "too many rays in one call");
-    return guarded(ctx, [&] { use_device(ctx); gen_rays_f64(ctx, first, n, bounds, out_dev); return (int)BVHGPU_OK; });
-}
+int bvhgpu_gen_rays_f32(bvhgpu_ctx* ctx, uint64_t first, size_t n, const float bounds[6], bvhgpu_ray_f32* out_dev) { return do_gen_rays(ctx, first, n, bounds, out_dev); }
+int bvhgpu_gen_rays_f64(bvhgpu_ctx* ctx, uint64_t first, size_t n, const float bounds[6], bvhgpu_ray_f64* out_dev) { return do_gen_rays(ctx, first, n, bounds, out_dev); }
 
 int bvhgpu_gen_primary_rays_f32(bvhgpu_ctx* ctx, const float cam[14], uint32_t width, uint32_t height, uint64_t first, size_t n,
                                 bvhgpu_ray_f32* out_dev) {
-    if (!ctx || !cam || (n && !out_dev) || !width || !height) return fail(ctx, BVHGPU_INVALID_ARG, "bad argument");
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "too many rays in one call");
-    return guarded(ctx, [&] { use_device(ctx); gen_primary<float>(ctx, cam, width, height, first, n, out_dev); return (int)BVHGPU_OK; });
+    return do_gen_primary<float>(ctx, cam, width, height, first, n, out_dev);
 }
 int bvhgpu_gen_primary_rays_f64(bvhgpu_ctx* ctx, const float cam[14], uint32_t width, uint32_t height, uint64_t first, size_t n,
                                 bvhgpu_ray_f64* out_dev) {
-    if (!ctx || !cam || (n && !out_dev) || !width || !height) return fail(ctx, BVHGPU_INVALID_ARG, "bad argument");
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "too many rays in one call");
-    return guarded(ctx, [&] { use_device(ctx); gen_primary<double>(ctx, cam, width, height, first, n, out_dev); return (int)BVHGPU_OK; });
+    return do_gen_primary<double>(ctx, cam, width, height, first, n, out_dev);
 }
 int bvhgpu_nearest_f32(bvhgpu_tree* t, const float* points, size_t n, int mem, int kind, uint32_t* out_shape, float* out_dist) {
-    return do_nearest<float>(t, points, n, mem, kind, out_shape, out_dist);
+    return do_points<float>(t, PointWalk::Nearest, points, n, mem, kind, 1, nullptr, out_shape, out_dist);
 }
 int bvhgpu_nearest_f64(bvhgpu_tree* t, const double* points, size_t n, int mem, int kind, uint32_t* out_shape, double* out_dist) {
-    return do_nearest<double>(t, points, n, mem, kind, out_shape, out_dist);
+    return do_points<double>(t, PointWalk::Nearest, points, n, mem, kind, 1, nullptr, out_shape, out_dist);
 }
 int bvhgpu_knearest_f32(bvhgpu_tree* t, const float* points, size_t n, int mem, int kind, uint32_t k, uint32_t* out_shape, float* out_dist) {
-    return do_knearest<float>(t, points, n, mem, kind, k, out_shape, out_dist);
+    return do_points<float>(t, PointWalk::KNearest, points, n, mem, kind, k, nullptr, out_shape, out_dist);
 }
 int bvhgpu_knearest_f64(bvhgpu_tree* t, const double* points, size_t n, int mem, int kind, uint32_t k, uint32_t* out_shape, double* out_dist) {
-    return do_knearest<double>(t, points, n, mem, kind, k, out_shape, out_dist);
+    return do_points<double>(t, PointWalk::KNearest, points, n, mem, kind, k, nullptr, out_shape, out_dist);
 }
 int bvhgpu_knearest_tree_f32(bvhgpu_tree* t, const float* points, size_t n, int mem, int kind, uint32_t k, const float* max_dist,
                              uint32_t* out_shape, float* out_dist) {
-    return do_knearest_tree<float>(t, points, n, mem, kind, k, max_dist, out_shape, out_dist);
+    return do_points<float>(t, PointWalk::KNearestTree, points, n, mem, kind, k, max_dist, out_shape, out_dist);
 }
 int bvhgpu_knearest_tree_f64(bvhgpu_tree* t, const double* points, size_t n, int mem, int kind, uint32_t k, const double* max_dist,
                              uint32_t* out_shape, double* out_dist) {
-    return do_knearest_tree<double>(t, points, n, mem, kind, k, max_dist, out_shape, out_dist);
+    return do_points<double>(t, PointWalk::KNearestTree, points, n, mem, kind, k, max_dist, out_shape, out_dist);
 }
 int bvhgpu_ray_triangle_pairs_f32(bvhgpu_ctx* ctx, const bvhgpu_ray_f32* rays, const float* tris, size_t n, int mem, float* out) {
     return do_pairs<float>(ctx, rays, tris, n, mem, out);
@@ -1439,43 +1330,27 @@ int bvhgpu_hits_fetch_triangles(bvhgpu_hits* h, void* isect, int mem) {
         return (int)BVHGPU_OK;
     });
 }
+// one record per ray (`per_ray` scalars in h->closest, the shape in h->closest_prim) of a batch whose flags hold `kind_bit`
+static int fetch_per_ray(bvhgpu_hits* h, void* values, uint32_t* shape, int mem, unsigned kind_bit, const char* other_kind_msg, size_t per_ray) {
+    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = h->ctx;
+    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (!(h->flags & kind_bit)) return fail(ctx, BVHGPU_INVALID_ARG, other_kind_msg);
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        if (values && h->n_rays) copy_out(ctx, values, h->closest.p, h->n_rays * per_ray * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
+        if (shape && h->n_rays) copy_out(ctx, shape, h->closest_prim.p, h->n_rays * 4, mem);
+        return (int)BVHGPU_OK;
+    });
+}
 int bvhgpu_hits_fetch_closest(bvhgpu_hits* h, void* isect, uint32_t* shape, int mem) {
-    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
-    bvhgpu_ctx* ctx = h->ctx;
-    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (!(h->flags & BVHGPU_TRAVERSE_CLOSEST)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_CLOSEST");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        if (isect && h->n_rays) copy_out(ctx, isect, h->closest.p, h->n_rays * 3 * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
-        if (shape && h->n_rays) copy_out(ctx, shape, h->closest_prim.p, h->n_rays * 4, mem);
-        return (int)BVHGPU_OK;
-    });
+    return fetch_per_ray(h, isect, shape, mem, BVHGPU_TRAVERSE_CLOSEST, "traverse was run without BVHGPU_TRAVERSE_CLOSEST", 3);
 }
-
 int bvhgpu_hits_fetch_any(bvhgpu_hits* h, void* isect, uint32_t* shape, int mem) {
-    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
-    bvhgpu_ctx* ctx = h->ctx;
-    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (!(h->flags & TRAVERSE_ANY_HIT)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_traverse_any_* batch");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        if (isect && h->n_rays) copy_out(ctx, isect, h->closest.p, h->n_rays * 3 * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
-        if (shape && h->n_rays) copy_out(ctx, shape, h->closest_prim.p, h->n_rays * 4, mem);
-        return (int)BVHGPU_OK;
-    });
+    return fetch_per_ray(h, isect, shape, mem, TRAVERSE_ANY_HIT, "the result object holds no bvhgpu_traverse_any_* batch", 3);
 }
-
 int bvhgpu_hits_fetch_box(bvhgpu_hits* h, void* slice, uint32_t* shape, int mem) {
-    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
-    bvhgpu_ctx* ctx = h->ctx;
-    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (!(h->flags & TRAVERSE_BOX_HIT)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_traverse_box_* batch");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        if (slice && h->n_rays) copy_out(ctx, slice, h->closest.p, h->n_rays * 2 * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
-        if (shape && h->n_rays) copy_out(ctx, shape, h->closest_prim.p, h->n_rays * 4, mem);
-        return (int)BVHGPU_OK;
-    });
+    return fetch_per_ray(h, slice, shape, mem, TRAVERSE_BOX_HIT, "the result object holds no bvhgpu_traverse_box_* batch", 2);
 }
 
 int bvhgpu_hits_info(const bvhgpu_hits* h, size_t* n_rays, uint64_t* total, bvhgpu_traverse_stats* stats) {
@@ -1534,14 +1409,6 @@ void bvhgpu_hits_destroy(bvhgpu_hits* h) {
     if (!h) return;
     if (h->ctx) { (void)hipSetDevice(h->ctx->device); (void)hipStreamSynchronize(h->ctx->stream); }
     detach_waiter(h);   // an asynchronous batch that is never waited for: its tree forgets it
-    h->counts.release(); h->offsets.release(); h->pool.release(); h->pool_t.release();
-    h->indices.release(); h->tslice.release(); h->blocksums.release(); h->scan_sums.release(); h->ctr.release();
-    h->isect.release(); h->closest.release(); h->closest_prim.release(); h->closest_key.release();
-    h->heap_dist.release(); h->heap_node.release();
-    h->wg_items.release(); h->raybuf.release(); h->qbuf.release(); h->tmaxbuf.release(); h->any_key.release(); h->any_part.release();
-    if (h->ev_items) (void)hipEventDestroy(h->ev_items);
-    h->wcounts.release(); h->ray_mask.release(); h->item_cnt.release(); h->wstack.release(); h->ray_items.release(); h->witems.release();
-    if (h->pin) (void)hipHostFree(h->pin);
     delete h;
 }
 

@@ -135,13 +135,17 @@ template <typename F> int comm_guarded(bvhgpu_ctx* ctx, F&& f) {
         return comm_fail(ctx, BVHGPU_RCCL_ERROR, buf);
     } catch (const HipFail& e) {
         char buf[512];
-        if (e.what && std::strcmp(e.what, "NONFINITE") == 0)
-            return comm_fail(ctx, BVHGPU_INVALID_ARG, "shape AABBs contain NaN or infinity (bvh_node.rs:214-217): nothing was built, nothing usable was sent");
-        if (e.what && std::strcmp(e.what, "RECV_REBROADCAST") == 0)
-            return comm_fail(ctx, BVHGPU_REBROADCAST, "the tree was received from a root whose optimistic build was not complete: every rank calls bvhgpu_bcast_known again");
-        if (e.what && std::strncmp(e.what, "RECV_", 5) == 0)
-            return comm_fail(ctx, BVHGPU_INVALID_ARG, "the tree was received from a root that had no valid tree to send");
-        snprintf(buf, sizeof buf, "%s failed: %s (comm.hip line %d)", e.what, hipGetErrorString(e.err), e.line);
+        switch (e.kind) {
+            case Fail::NonFinite:
+                return comm_fail(ctx, BVHGPU_INVALID_ARG, "shape AABBs contain NaN or infinity (bvh_node.rs:214-217): nothing was built, nothing usable was sent");
+            case Fail::RecvRebroadcast:
+                return comm_fail(ctx, BVHGPU_REBROADCAST, "the tree was received from a root whose optimistic build was not complete: every rank calls bvhgpu_bcast_known again");
+            case Fail::RecvInvalid:
+            case Fail::RecvGarbled:
+                return comm_fail(ctx, BVHGPU_INVALID_ARG, "the tree was received from a root that had no valid tree to send");
+            default: break;   // (the other kinds are not thrown under this guard: reported like a failed HIP call, as before)
+        }
+        snprintf(buf, sizeof buf, "%s failed: %s (comm.hip line %d)", e.what ? e.what : "?", hipGetErrorString(e.err), e.line);
         return comm_fail(ctx, e.err == hipErrorOutOfMemory ? BVHGPU_OOM : BVHGPU_HIP_ERROR, buf);
     } catch (const std::bad_alloc&) {
         return comm_fail(ctx, BVHGPU_OOM, "host allocation failed");
@@ -347,10 +351,10 @@ void recv_finalize(bvhgpu_tree* t) {
     t->pending_recv = false;
     const BcastHeader h = *reinterpret_cast<const BcastHeader*>(t->pin_recv);
     // (nothing usable arrived: batches that were enqueued on this generation meanwhile return the same status from their own wait)
-    auto nothing = [&](hipError_t e, const char* what, int line) { t->flattened = false; t->failed_gen = t->gen; t->failed_what = what; throw HipFail{e, what, line}; };
-    if (h.magic != BCAST_MAGIC || h.status > BH_UNFINISHED) nothing(hipErrorUnknown, "RECV_GARBLED", __LINE__);
-    if (h.status == BH_INVALID) nothing(hipErrorInvalidValue, "RECV_INVALID", __LINE__);
-    if (h.status == BH_UNFINISHED) nothing(hipErrorNotReady, "RECV_REBROADCAST", __LINE__);
+    auto nothing = [&](hipError_t e, Fail what, int line) { t->flattened = false; t->failed_gen = t->gen; t->failed_what = what; throw HipFail{e, nullptr, line, what}; };
+    if (h.magic != BCAST_MAGIC || h.status > BH_UNFINISHED) nothing(hipErrorUnknown, Fail::RecvGarbled, __LINE__);
+    if (h.status == BH_INVALID) nothing(hipErrorInvalidValue, Fail::RecvInvalid, __LINE__);
+    if (h.status == BH_UNFINISHED) nothing(hipErrorNotReady, Fail::RecvRebroadcast, __LINE__);
     t->exact_only = (h.flags & 1u) != 0;   // batches that were enqueued meanwhile and walked wide are replayed by their wait
     if (t->exact_only) t->has_wide = false;
 }

@@ -411,7 +411,10 @@ __device__ __forceinline__ unsigned long long mask_range(int lo, int hi) {  // b
 }
 
 // error plumbing -------------------------------------------------------------------------------
-struct HipFail { hipError_t err; const char* what; int line; };
+// kind == None: a HIP call failed and `what` is its text.  Every other kind is a failure of the engine's own (capi.hip guarded() and
+// comm.hip comm_guarded() turn it into a status and a message); `what` is then NULL.
+enum class Fail { None, NonFinite, Overflow, Rebroadcast, RecvRebroadcast, RecvInvalid, RecvGarbled, StaleTree, OrderedDepth };
+struct HipFail { hipError_t err; const char* what; int line; Fail kind = Fail::None; };
 #define BVH_HIP(x)                                                     \
     do {                                                               \
         hipError_t _e = (x);                                           \

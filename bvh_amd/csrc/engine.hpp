@@ -9,10 +9,14 @@
 
 namespace bvhgpu {
 
-// RAII-less device buffer that only ever grows (no allocation on the steady-state hot loop)
+// device buffer that only ever grows (no allocation on the steady-state hot loop) and is freed with the object it is a member of
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     bool reserve(size_t bytes) {   // true: a new (uninitialised) allocation was made
         if (bytes <= cap) return false;
         if (p) (void)hipFree(p);
@@ -27,7 +31,7 @@ struct DevBuf {
         cap = want;
         return true;
     }
-    void release() {
+    void release() {   // (also for a buffer that is dropped on purpose while its owner lives on)
         if (p) (void)hipFree(p);
         p = nullptr;
         cap = 0;
@@ -71,6 +75,17 @@ struct HostBatch {
     uint32_t* indices_host = nullptr;
     bool od6 = false;       // ... side by side in ONE array of n_rays x 6 (BVHGPU_TRAVERSE_RAYS_OD6)
     bool with_od = false;   // the batch came as origins + directions (Ray::new on the device) rather than as Ray structs
+    ~HostBatch() {   // (the buffers free themselves behind this)
+        for (auto& h : hits) if (h) { bvhgpu_hits_destroy(h); h = nullptr; }
+        for (auto& e : ev_up) if (e) (void)hipEventDestroy(e);
+        for (auto& e : ev_done) if (e) (void)hipEventDestroy(e);
+        if (up) { (void)hipStreamSynchronize(up); (void)hipStreamDestroy(up); }
+        if (up2) { (void)hipStreamSynchronize(up2); (void)hipStreamDestroy(up2); }
+        for (auto& e : ev_up2) if (e) (void)hipEventDestroy(e);
+        if (ev_main) (void)hipEventDestroy(ev_main);
+        if (ev_aabbs) (void)hipEventDestroy(ev_aabbs);
+        if (down) { (void)hipStreamSynchronize(down); (void)hipStreamDestroy(down); }
+    }
 };
 }
 
@@ -96,6 +111,13 @@ struct bvhgpu_ctx {
     bvhgpu::HostBatch* host = nullptr;   // state of bvhgpu_traverse_host_* (capi.hip), made on first use
     hipStream_t side = nullptr;   // second stream of the ctx (created on first use): work that may run BESIDE the main chain — the
                                   // item filter of a batch whose tree is still building (walk_wide.hip k_wide_items)
+    ~bvhgpu_ctx() {   // the host batch (its result objects wait on `stream`) first, the streams last; the buffers free themselves behind this
+        delete host;
+        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+        if (pinned) (void)hipHostFree(pinned);
+        if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 struct bvhgpu_tree {
@@ -122,7 +144,7 @@ struct bvhgpu_tree {
                                  // bvhgpu_hits_wait — by EVERY result object that recorded it, whoever finalized the build first
     uint64_t bcast_gen = 0;      // the generation that bvhgpu_bcast_known sent before its build was finalized (comm.hip)
     uint64_t failed_gen = 0;     // the generation whose build_finalize / recv_finalize found nothing usable (NaN / inf input, a root without a
-    const char* failed_what = nullptr;   // valid tree): WHOEVER consumed that error first (bvhgpu_tree_wait, a rebuild, another result object's
+    bvhgpu::Fail failed_what = bvhgpu::Fail::None;   // valid tree): WHOEVER consumed that error first (bvhgpu_tree_wait, a rebuild, another result object's
                                  // wait), every asynchronous batch that was enqueued on that generation returns it from its own wait
     bool pending_recv = false;   // a broadcast was received on the stream; its status header (t->pin_recv) has not been looked at yet
     void* pin_recv = nullptr;    // 64 B of pinned host memory: the received broadcast header
@@ -176,6 +198,14 @@ struct bvhgpu_tree {
     bvhgpu::DevBuf chunk_cnt;   // two-launch level schedule: the same counts per block of 256 tile ids (build.hip BuildArgs::chunk_cnt)
     bvhgpu::DevBuf ctr;         // counters
     bvhgpu::DevBuf refit_seg;   // refit: complete binary tree of joins over the sorted positions (2 * n_pad boxes)
+    ~bvhgpu_tree() {   // (the buffers free themselves behind this: the side stream must have finished with flat / trav / slot_entry before)
+        if (flat_beside && ctx && ctx->side) { (void)hipStreamSynchronize(ctx->side); flat_beside = false; }
+        if (ev_flat0) (void)hipEventDestroy(ev_flat0);
+        if (ev_flat) (void)hipEventDestroy(ev_flat);
+        if (ev_top) (void)hipEventDestroy(ev_top);
+        if (pin) (void)hipHostFree(pin);
+        if (pin_recv) (void)hipHostFree(pin_recv);
+    }
 };
 
 struct bvhgpu_hits {
@@ -249,6 +279,10 @@ struct bvhgpu_hits {
     uint32_t replays = 0;               // times bvhgpu_hits_wait had to enqueue the asynchronous batch again
     int deferred_rc = 0;                // status of a completion that ran on behalf of another call (rebuild / destroy of the tree)
     std::string deferred_err;
+    ~bvhgpu_hits() {
+        if (ev_items) (void)hipEventDestroy(ev_items);
+        if (pin) (void)hipHostFree(pin);
+    }
 };
 
 namespace bvhgpu {
@@ -277,7 +311,7 @@ constexpr uint32_t BSTAT_NONFINITE = 1u, BSTAT_EMPTY_SPLIT = 2u;   // = build.hi
 constexpr uint32_t BSTAT_UNFINISHED = 0x100u;
 constexpr int BUILD_CTR_TOPMASK = 5;   // u32 slot of the build counters: bit h = the level tier wrote the BvhNode of heap number h (h < 16)                      // the optimistic schedule left nodes in the level queue
 template <typename T> void wide_from_trav(bvhgpu_tree* t);   // wide nodes + their LDS slot table from trav + slot_entry
-// comm.hip: completes a broadcast that was received on the stream (reads the status header; throws RECV_* on a bad one)
+// comm.hip: completes a broadcast that was received on the stream (reads the status header; throws Fail::Recv* on a bad one)
 void recv_finalize(bvhgpu_tree* t);
 // capi.hip: completes the asynchronous batches still in flight on a tree whose arrays are about to be overwritten or freed
 void settle_waiters(bvhgpu_tree* t);

@@ -450,7 +450,7 @@ bool traverse_check(bvhgpu_hits* h) {
         if (++h->pend_attempts > 24) throw HipFail{hipErrorUnknown, "best-first heap did not converge", __LINE__};
         h->heap_cap *= 2; return false;
     }
-    if (ordered && (pin[7] & 1ull)) throw HipFail{hipErrorInvalidValue, "ORDERED_DEPTH", __LINE__};
+    if (ordered && (pin[7] & 1ull)) throw HipFail{hipErrorInvalidValue, nullptr, __LINE__, Fail::OrderedDepth};
     if (h->pend_guide && (pin[7] & WALK_FLAG_GUIDE_RANGE)) {   // a ray outside the guide walk's range: this result object goes back to the f64 walk
         h->no_guide = true; h->wcounts_clean = false; return false;   // (the replay of this batch walks in f64; traverse_enqueue sets the back-off)
     }
@@ -482,7 +482,7 @@ bool traverse_check(bvhgpu_hits* h) {
     const unsigned long long total = pin[3];  // sum of the per-ray counts = number of hits
     const bool pair_recs = h->pend_rec8;   // `used` counts 16-byte records of two hits, pool_cap 12-byte slots
     if ((pair_recs ? 2 * used : used) < total && !h->pend_staged) throw HipFail{hipErrorUnknown, "hit pool / count scan mismatch", __LINE__};
-    if (total > 0xFFFFFFFFull) throw HipFail{hipErrorInvalidValue, "OVERFLOW", __LINE__};
+    if (total > 0xFFFFFFFFull) throw HipFail{hipErrorInvalidValue, nullptr, __LINE__, Fail::Overflow};
     // Pool or index array too small: grow to the need and replay — both in ONE replay (the count scan is complete even when records were
     // dropped, and pair records need fewer pool slots than there are hits, so the pool no longer sizes the index array).
     const bool pool_small = used > (pair_recs ? (unsigned long long)h->pool_cap * sizeof(HitRec) / 16u : (unsigned long long)h->pool_cap);

@@ -245,7 +245,7 @@ static void launch_ordered_as(bvhgpu_tree* t, const typename Traits<T>::Ray* ray
         const unsigned heap_grid = (unsigned)std::min<size_t>((n_rays + 255) / 256, (size_t)ctx->n_cu * 4);
         const size_t lanes = (size_t)heap_grid * 256;
         if (lanes * h->heap_cap * (sizeof(T) + 4) > ((size_t)16 << 30))
-            throw HipFail{hipErrorInvalidValue, "ORDERED_DEPTH", __LINE__};
+            throw HipFail{hipErrorInvalidValue, nullptr, __LINE__, Fail::OrderedDepth};
         h->heap_dist.reserve(lanes * h->heap_cap * sizeof(T));
         h->heap_node.reserve(lanes * h->heap_cap * 4);
         hipLaunchKernelGGL((k_traverse_heap<T, MODE, ASCENDING>), dim3(heap_grid), dim3(256), 0, st,

@@ -156,6 +156,11 @@ SYMBOLS = [
     ("bvhgpu_traverse_box_f32", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
     ("bvhgpu_traverse_box_f64", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
     ("bvhgpu_hits_fetch_box", _i, [_vp, _vp, _vp, _i]),
+    ("bvhgpu_tree_set_spheres_f32", _i, [_vp, _vp, _sz, _i]),
+    ("bvhgpu_tree_set_spheres_f64", _i, [_vp, _vp, _sz, _i]),
+    ("bvhgpu_traverse_sphere_f32", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_traverse_sphere_f64", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_hits_fetch_sphere", _i, [_vp, _vp, _vp, _i]),
     ("bvhgpu_enable_timing", _i, [_vp, _i]),
     ("bvhgpu_last_timings", _i, [_vp, C.POINTER(Timings)]),
     ("bvhgpu_obj_parse", _i, [C.c_char_p, _sz, C.POINTER(C.POINTER(C.c_float)), C.POINTER(_sz), _vp]),

@@ -258,6 +258,16 @@ class Ball:
 Sphere = Ball
 
 
+def spheres_aabbs(spheres) -> np.ndarray:
+    """the AABBs a sphere scene is built from, [c - r, c + r] as (n,6) in the input's dtype (the reference's examples/simple.rs, Sphere::aabb)"""
+    s = np.asarray(spheres)
+    if s.dtype not in (np.float32, np.float64):
+        s = s.astype(np.float64)
+    s = s.reshape(-1, 4)
+    r = s[:, 3:4]
+    return np.ascontiguousarray(np.concatenate([s[:, :3] - r, s[:, :3] + r], axis=1))
+
+
 def _query_row(query, ft):
     """(kind, one row of scalars) of an Aabb / Ball / point query in the tree's dtype"""
     if isinstance(query, Aabb):
@@ -463,6 +473,13 @@ class _Hits:
         ts = np.zeros((n_rays, 2), dtype=dtype)
         shape = np.zeros(n_rays, dtype=np.uint32)
         check(_lib.load().bvhgpu_hits_fetch_box(self.h, ptr(ts), ptr(shape), HOST), self.ctx._h)
+        return ts, shape
+
+    def fetch_sphere(self, n_rays: int, dtype=np.float32):
+        """sphere batches: (hit{distance,exit}[n,2], shape[n]) of the completed batch, copied to the host"""
+        ts = np.zeros((n_rays, 2), dtype=dtype)
+        shape = np.zeros(n_rays, dtype=np.uint32)
+        check(_lib.load().bvhgpu_hits_fetch_sphere(self.h, ptr(ts), ptr(shape), HOST), self.ctx._h)
         return ts, shape
 
     def fetch_triangles(self, dtype=np.float32):
@@ -697,6 +714,51 @@ class _TreeBase:
     def box_occluded(self, rays: RayBatch, tmax=None) -> np.ndarray:
         """bool[n]: does ray i enter any shape's box before tmax[i] (first_box_hits(...) shape != NONE)"""
         _, shape = self.first_box_hits(rays, tmax)
+        return shape != NONE
+
+    # ---- ray queries against sphere shapes (no triangles) -----------------------------------
+    def set_spheres(self, spheres) -> None:
+        """bvhgpu_tree_set_spheres_*: one sphere per shape, (n,4) [cx, cy, cz, r] in the tree's dtype; numpy or torch GPU tensor.  Independent
+        of the AABBs the tree was built from (normally spheres_aabbs(spheres)); never validated."""
+        fn = getattr(_lib.load(), f"bvhgpu_tree_set_spheres_{self.sfx}")
+        if _is_device_tensor(spheres):
+            if str(spheres.dtype) != ("torch.float32" if self.sfx == "f32" else "torch.float64"):
+                raise BvhGpuError(_lib.DTYPE_MISMATCH, "sphere dtype differs from tree dtype")
+            keep = spheres.contiguous()
+            check(fn(self._t, ptr(keep.data_ptr()), keep.numel() // 4, DEVICE), self.ctx._h)
+        else:
+            ft = np.float32 if self.sfx == "f32" else np.float64
+            if isinstance(spheres, np.ndarray) and spheres.dtype != ft:
+                raise BvhGpuError(_lib.DTYPE_MISMATCH, "sphere dtype differs from tree dtype")
+            a = np.ascontiguousarray(spheres, dtype=ft).reshape(-1, 4)
+            check(fn(self._t, ptr(a), len(a), HOST), self.ctx._h)
+
+    def _sphere_hits(self, rays: RayBatch, tmax, fetch: bool, coherent: bool, first: bool):
+        if rays.sfx != self.sfx:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
+        keep, tp = self._tmax_arg(rays, tmax)   # (keep: the array tp points into stays alive over the call)
+        flags = (TRAVERSE_COHERENT if coherent else 0) | (_lib.TRAVERSE_FIRST if first else 0)
+        fn = getattr(_lib.load(), f"bvhgpu_traverse_sphere_{self.sfx}")
+        check(fn(self._t, rays._ptr(), tp, rays.n, rays.mem, flags, C.byref(self._hits.h)), self.ctx._h)
+        if not fetch:
+            return None, None
+        return self._hits.fetch_sphere(rays.n, np.float32 if self.sfx == "f32" else np.float64)
+
+    def closest_sphere_hits(self, rays: RayBatch, tmax=None, fetch: bool = True, coherent: bool = False):
+        """bvhgpu_traverse_sphere_*: per ray the shape of FlatBvh::traverse's list (flat_bvh.rs:396-431) whose sphere (set_spheres) the ray
+        hits nearest, among those with distance < tmax[i] (strict; the first of the list on equal distances), with (distance, exit) on
+        that sphere; shape NONE and (+inf, 0) when there is none.  Needs set_spheres, no triangles.  tmax as for any_hits.
+        returns (hit[n,2], shape[n]); fetch=False returns (None, None) and leaves the result on the tree's result object."""
+        return self._sphere_hits(rays, tmax, fetch, coherent, False)
+
+    def first_sphere_hits(self, rays: RayBatch, tmax=None, fetch: bool = True, coherent: bool = False):
+        """bvhgpu_traverse_sphere_* with BVHGPU_TRAVERSE_FIRST: the FIRST shape of the ray's list whose sphere is hit with distance <
+        tmax[i] instead of the nearest one (any-hit: every walk stops at it).  returns (hit[n,2], shape[n]) like closest_sphere_hits."""
+        return self._sphere_hits(rays, tmax, fetch, coherent, True)
+
+    def sphere_occluded(self, rays: RayBatch, tmax=None) -> np.ndarray:
+        """bool[n]: does ray i hit any shape's sphere before tmax[i] (first_sphere_hits(...) shape != NONE)"""
+        _, shape = self.first_sphere_hits(rays, tmax)
         return shape != NONE
 
     # ---- point query ---------------------------------------------------------------------

@@ -2330,7 +2330,7 @@ template <typename T> void build_enqueue(bvhgpu_tree* t, const T* aabbs_dev, siz
     t->built = false; t->flattened = false; t->lazy_flat = false; t->pending_build = false; t->exact_only = false; t->pending_recv = false;
     t->pend_persist = false;
     if (!redo) t->gen++;   // results enqueued from here on belong to this build (bvhgpu_hits_wait compares generations)
-    if (n != t->n) t->has_tris = false;   // one triangle per shape: a different shape count invalidates the vertex array
+    if (n != t->n) { t->has_tris = false; t->has_spheres = false; }   // one triangle / sphere per shape: a different shape count invalidates those arrays
     t->n = n; t->n_nodes = n ? 2 * n - 1 : 0;
     t->n_flat = n >= 2 ? 3 * n - 2 : n;
     t->n_trav = n >= 2 ? 2 * n - 2 : n;

@@ -286,7 +286,7 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
     }
     if ((flags & BVHGPU_TRAVERSE_TRIANGLES) && (flags & BVHGPU_TRAVERSE_CLOSEST))
         return fail(ctx, BVHGPU_INVALID_ARG, "TRIANGLES and CLOSEST are alternatives");
-    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT);   // (internal: only bvhgpu_traverse_any_* / bvhgpu_traverse_box_* set them)
+    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT | TRAVERSE_SPHERE_HIT);   // (internal: only bvhgpu_traverse_any_* / _box_* / _sphere_* set them)
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
@@ -305,20 +305,22 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
     });
 }
 
-// bvhgpu_traverse_any_* and bvhgpu_traverse_box_*: one result per ray among the candidates of FlatBvh::traverse's list below tmax[i].
+// bvhgpu_traverse_any_*, bvhgpu_traverse_box_* and bvhgpu_traverse_sphere_*: one result per ray among the candidates of FlatBvh::traverse's list below tmax[i].
 //   any-hit (kind_bit TRAVERSE_ANY_HIT, traverse.hip MODE_ANY): the first candidate whose triangle distance is < tmax[i]; needs triangles.
 //   box hit (kind_bit TRAVERSE_BOX_HIT, MODE_BOX_CLOSEST / MODE_BOX_FIRST): the shape whose own AABB the ray enters first — or, with
 //   BVHGPU_TRAVERSE_FIRST, the first one of the list — among those with enter < tmax[i].  No triangles are needed or read.
+//   sphere hit (kind_bit TRAVERSE_SPHERE_HIT, MODE_SPHERE_CLOSEST / MODE_SPHERE_FIRST): the same two choices among the shapes whose sphere
+//   (bvhgpu_tree_set_spheres_*) the ray hits with distance < tmax[i] (walk.hpp ray_sphere); needs the spheres, no triangles.
 template <typename T>
 int do_traverse_tmax(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, const T* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits,
-                     unsigned allowed_flags, const char* flags_msg, unsigned kind_bit, const char* tris_msg) {   // tris_msg == NULL: no triangles needed
+                     unsigned allowed_flags, const char* flags_msg, unsigned kind_bit, const char* needs_msg) {   // needs_msg: the refusal when the kind's per-shape array (sphere hit: the spheres, else the triangles) is not set; NULL: none needed
     { const int rc = batch_open(tree, hits); if (rc != BVHGPU_OK) return rc; }
     bvhgpu_ctx* ctx = tree->ctx;
     if (flags & ~allowed_flags) return fail(ctx, BVHGPU_INVALID_ARG, flags_msg);
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
     { const int rc = settle(tree); if (rc != BVHGPU_OK) return rc; }
     { const int rc = batch_refusal<T>(tree, hits, "ray", "rays", n_rays && !rays, "rays is NULL", n_rays); if (rc != BVHGPU_OK) return rc; }
-    if (tris_msg && !tree->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, tris_msg);
+    if (needs_msg && !(kind_bit == TRAVERSE_SPHERE_HIT ? tree->has_spheres : tree->has_tris)) return fail(ctx, BVHGPU_INVALID_ARG, needs_msg);
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
@@ -338,6 +340,12 @@ template <typename T>
 int do_traverse_box(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, const T* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits) {
     return do_traverse_tmax<T>(tree, rays, tmax, n_rays, mem, flags, hits, BVHGPU_TRAVERSE_COHERENT | BVHGPU_TRAVERSE_FIRST,
                                "box-hit flags: BVHGPU_TRAVERSE_COHERENT and BVHGPU_TRAVERSE_FIRST only", TRAVERSE_BOX_HIT, nullptr);
+}
+template <typename T>
+int do_traverse_sphere(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, const T* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_traverse_tmax<T>(tree, rays, tmax, n_rays, mem, flags, hits, BVHGPU_TRAVERSE_COHERENT | BVHGPU_TRAVERSE_FIRST,
+                               "sphere-hit flags: BVHGPU_TRAVERSE_COHERENT and BVHGPU_TRAVERSE_FIRST only", TRAVERSE_SPHERE_HIT,
+                               "sphere queries need bvhgpu_tree_set_spheres first");
 }
 
 // bvhgpu_query_*: an AABB / point / ball batch (query.hip).  queries == NULL: the tree's own shape AABBs (self-overlap).
@@ -1175,6 +1183,7 @@ int bvhgpu_scene_import(bvhgpu_ctx* ctx, const void* src, size_t nbytes, int mem
         t->dtype = (int)hd.dtype; t->n = hd.n; t->n_trav = hd.n_trav; t->n_nodes = 0; t->n_flat = 0;
         t->unfolded = hd.unfolded != 0;
         t->has_tris = gb != 0;
+        t->has_spheres = false;   // (spheres do not travel in a scene blob: none until bvhgpu_tree_set_spheres_*)
         t->built = false; t->flattened = true; t->exact_only = hd.exact_only != 0;
         t->pending_build = false; t->pending_recv = false; t->gen++;
         if (t->exact_only) t->has_wide = false;   // (never walked wide: no wide nodes needed)
@@ -1254,6 +1263,13 @@ int bvhgpu_traverse_box_f64(bvhgpu_tree* tree, const bvhgpu_ray_f64* rays, const
     return do_traverse_box<double>(tree, rays, tmax, n_rays, mem, flags, hits);
 }
 
+int bvhgpu_traverse_sphere_f32(bvhgpu_tree* tree, const bvhgpu_ray_f32* rays, const float* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_traverse_sphere<float>(tree, rays, tmax, n_rays, mem, flags, hits);
+}
+int bvhgpu_traverse_sphere_f64(bvhgpu_tree* tree, const bvhgpu_ray_f64* rays, const double* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_traverse_sphere<double>(tree, rays, tmax, n_rays, mem, flags, hits);
+}
+
 int bvhgpu_query_f32(bvhgpu_tree* tree, int kind, const float* queries, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
     return do_query<float>(tree, kind, queries, n, mem, flags, hits);
 }
@@ -1319,10 +1335,35 @@ static int set_triangles(bvhgpu_tree* t, const void* verts, size_t n, int mem, i
 int bvhgpu_tree_set_triangles_f32(bvhgpu_tree* t, const float* verts, size_t n, int mem) { return set_triangles(t, verts, n, mem, BVHGPU_F32); }
 int bvhgpu_tree_set_triangles_f64(bvhgpu_tree* t, const double* verts, size_t n, int mem) { return set_triangles(t, verts, n, mem, BVHGPU_F64); }
 
+// one sphere {cx, cy, cz, r} per shape, in a buffer of its own (a tree may hold triangles and spheres at once); nothing is validated
+static int set_spheres(bvhgpu_tree* t, const void* spheres, size_t n, int mem, int dtype) {
+    if (!t) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = t->ctx;
+    if (t->dtype != dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "sphere dtype differs from tree dtype");
+    if (n != t->n) return fail(ctx, BVHGPU_INVALID_ARG, "one sphere per shape is required");
+    if (n && !spheres) return fail(ctx, BVHGPU_INVALID_ARG, "spheres is NULL");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        const size_t bytes = n * 4 * (dtype == BVHGPU_F32 ? 4 : 8);
+        settle_waiters_impl(t);   // (a replay of a batch in flight must see the spheres it was enqueued with)
+        t->spheres.reserve(bytes + 16);
+        if (bytes) {
+            BVH_HIP(hipMemcpyAsync(t->spheres.p, spheres, bytes, mem == BVHGPU_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+            if (mem != BVHGPU_DEVICE) BVH_HIP(hipStreamSynchronize(ctx->stream));
+        }
+        t->has_spheres = true;
+        return (int)BVHGPU_OK;
+    });
+}
+int bvhgpu_tree_set_spheres_f32(bvhgpu_tree* t, const float* spheres, size_t n, int mem) { return set_spheres(t, spheres, n, mem, BVHGPU_F32); }
+int bvhgpu_tree_set_spheres_f64(bvhgpu_tree* t, const double* spheres, size_t n, int mem) { return set_spheres(t, spheres, n, mem, BVHGPU_F64); }
+
 int bvhgpu_hits_fetch_triangles(bvhgpu_hits* h, void* isect, int mem) {
     if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "a sphere-hit batch has no triangle values: use bvhgpu_hits_fetch_sphere");
     if (!(h->flags & BVHGPU_TRAVERSE_TRIANGLES)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_TRIANGLES");
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -1335,6 +1376,8 @@ static int fetch_per_ray(bvhgpu_hits* h, void* values, uint32_t* shape, int mem,
     if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if ((h->flags & TRAVERSE_SPHERE_HIT) && kind_bit != TRAVERSE_SPHERE_HIT)
+        return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
     if (!(h->flags & kind_bit)) return fail(ctx, BVHGPU_INVALID_ARG, other_kind_msg);
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -1351,6 +1394,9 @@ int bvhgpu_hits_fetch_any(bvhgpu_hits* h, void* isect, uint32_t* shape, int mem)
 }
 int bvhgpu_hits_fetch_box(bvhgpu_hits* h, void* slice, uint32_t* shape, int mem) {
     return fetch_per_ray(h, slice, shape, mem, TRAVERSE_BOX_HIT, "the result object holds no bvhgpu_traverse_box_* batch", 2);
+}
+int bvhgpu_hits_fetch_sphere(bvhgpu_hits* h, void* slice, uint32_t* shape, int mem) {
+    return fetch_per_ray(h, slice, shape, mem, TRAVERSE_SPHERE_HIT, "the result object holds no bvhgpu_traverse_sphere_* batch", 2);
 }
 
 int bvhgpu_hits_info(const bvhgpu_hits* h, size_t* n_rays, uint64_t* total, bvhgpu_traverse_stats* stats) {
@@ -1384,6 +1430,7 @@ int bvhgpu_hits_fetch(bvhgpu_hits* h, uint32_t* offsets, uint32_t* indices, void
     if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR: use bvhgpu_hits_fetch_closest");
     if (h->flags & TRAVERSE_ANY_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR: use bvhgpu_hits_fetch_any");
     if (h->flags & TRAVERSE_BOX_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "a box-hit batch produces no CSR: use bvhgpu_hits_fetch_box");
+    if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "a sphere-hit batch produces no CSR: use bvhgpu_hits_fetch_sphere");
     return guarded(ctx, [&] {
         use_device(ctx);
         if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
@@ -1399,6 +1446,7 @@ int bvhgpu_hits_device(const bvhgpu_hits* h, const uint32_t** offsets, const uin
     if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(h->ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR");
     if (h->flags & TRAVERSE_ANY_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR");
     if (h->flags & TRAVERSE_BOX_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "a box-hit batch produces no CSR");
+    if (h->flags & TRAVERSE_SPHERE_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "a sphere-hit batch produces no CSR: use bvhgpu_hits_fetch_sphere");
     if (offsets) *offsets = h->offsets.as<uint32_t>();
     if (indices) *indices = h->indices.as<uint32_t>();
     if (tslice) *tslice = (h->flags & BVHGPU_TRAVERSE_T_SLICE) ? h->tslice.p : nullptr;

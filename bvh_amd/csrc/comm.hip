@@ -218,6 +218,7 @@ void bcast_arrays(bvhgpu_comm* c, bvhgpu_tree** trees, int root, int dtype, size
         if (sb) t->slot_entry.reserve(sb); else t->slot_entry.release();
         if (gb) t->tris.reserve(gb + 16);
         t->has_tris = gb != 0;
+        t->has_spheres = false;   // (spheres do not travel: the receiving tree has none until bvhgpu_tree_set_spheres_*)
         if (with_header && !t->pin_recv) BVH_HIP(hipHostMalloc(&t->pin_recv, 64, hipHostMallocDefault));
     }
     // send buffers of the root: its tree's arrays, or scratch when it has none to offer

@@ -44,6 +44,8 @@ struct DevBuf {
 constexpr unsigned TRAVERSE_ANY_HIT = 1u << 31;
 // result objects of bvhgpu_traverse_box_* (MODE_BOX_CLOSEST, or MODE_BOX_FIRST with BVHGPU_TRAVERSE_FIRST): marked the same way
 constexpr unsigned TRAVERSE_BOX_HIT = 1u << 30;
+// result objects of bvhgpu_traverse_sphere_* (MODE_SPHERE_CLOSEST, or MODE_SPHERE_FIRST with BVHGPU_TRAVERSE_FIRST): marked the same way
+constexpr unsigned TRAVERSE_SPHERE_HIT = 1u << 29;
 
 }  // namespace bvhgpu
 
@@ -182,6 +184,8 @@ struct bvhgpu_tree {
     bool has_guide = false;
     bvhgpu::DevBuf tris;        // n * 9 T triangle vertices (optional: triangle stage)
     bool has_tris = false;
+    bvhgpu::DevBuf spheres;     // n * 4 T {cx, cy, cz, r} per shape (optional: bvhgpu_tree_set_spheres_*, the leaf stage of bvhgpu_traverse_sphere_*)
+    bool has_spheres = false;
     bvhgpu::DevBuf slot_entry;  // TopCfg::SLOTS * u32: traversal entry held in LDS slot s (NONE = unused slot)
     bvhgpu::DevBuf node_slot;   // n_nodes * u16: LDS slot of the node's traversal entry (SLOT_NONE = not resident)
     // build scratch (kept for rebuild)
@@ -270,7 +274,7 @@ struct bvhgpu_hits {
     const void* pend_queries = nullptr;  // its queries in HBM (the caller's, the tree's own AABBs, or `qbuf`)
     bool pend_qwide = false;             // ... walked by k_query_wide (a lane's stack overflow replays it with the binary walk)
     bvhgpu::DevBuf qbuf;                 // HOST queries staged here, so that a replay reads them again
-    // any-hit and box batches (bvhgpu_traverse_any_* / bvhgpu_traverse_box_*): per-ray segment ends in HBM (the caller's, or `tmaxbuf`; NULL = +inf), read by every replay
+    // any-hit, box and sphere batches (bvhgpu_traverse_any_* / _box_* / _sphere_*): per-ray segment ends in HBM (the caller's, or `tmaxbuf`; NULL = +inf), read by every replay
     const void* pend_tmax = nullptr;
     bvhgpu::DevBuf tmaxbuf;              // HOST tmax staged here
     bvhgpu::DevBuf any_key;              // n_rays u32: any-hit batches walked as items (walk.hpp WalkOut::any_key), all-ones between batches

@@ -179,7 +179,58 @@ __global__ __launch_bounds__(256) void k_box_resolve(uint32_t* __restrict__ key3
         part[blockIdx.x] = sum;
     }
 }
-// k_publish_counters for an any-hit or box batch: ctr[3] = the sum of k_any_resolve's per-workgroup counts, then the 8 counters go to the pinned
+// Sphere batch (MODE_SPHERE_CLOSEST / MODE_SPHERE_FIRST), after its walk: k_box_resolve's sibling with ray_sphere as the leaf stage (a sibling,
+// not a template parameter of k_box_resolve, whose instantiations keep their names and text).  Per ray {distance, exit} of the winning
+// shape's sphere and the shape; the rays that have one are counted into part[workgroup].  SRC as above (BOX_SRC_*): distance > eps > 0, so
+// its bits order as unsigned integers and the walk's keys and slots are the box batches'.  Every candidate the walk filed had distance <
+// tmax already; the winner's hit is computed again — ray_sphere on the operands the walk used, hence the same bits.
+template <typename T, int SRC>
+__global__ __launch_bounds__(256) void k_sphere_resolve(uint32_t* __restrict__ key32, unsigned long long* __restrict__ key64, uint32_t* __restrict__ ray_items,
+                                                        const uint32_t* __restrict__ item_prim, const typename Traits<T>::Ray* __restrict__ rays,
+                                                        const T* __restrict__ spheres, uint32_t n_rays, T* __restrict__ hit, uint32_t* __restrict__ prim,
+                                                        uint32_t* __restrict__ part) {
+    __shared__ uint32_t s_cnt[256 / WAVE];
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t p = NONE;
+    if (r < n_rays) {
+        if (SRC == BOX_SRC_RAY) {
+            p = prim[r];
+        } else {
+            T best[2] = {Traits<T>::inf(), 0};
+            const typename Traits<T>::Ray* rp = rays + r;
+            const T o[3] = {rp->o[0], rp->o[1], rp->o[2]}, d[3] = {rp->d[0], rp->d[1], rp->d[2]};
+            if (SRC == BOX_SRC_KEY32) {
+                const uint32_t k = key32[r];
+                if (k != NONE) { p = k & 0x0FFFFFFFu; ray_sphere<T>(o, d, spheres + 4 * (size_t)p, best); key32[r] = NONE; }
+            } else if (SRC == BOX_SRC_KEY64) {
+                const unsigned long long k = key64[r];
+                if (k != ~0ull) { p = (uint32_t)(k & 0x0FFFFFFFull); ray_sphere<T>(o, d, spheres + 4 * (size_t)p, best); key64[r] = ~0ull; }
+            } else {
+                uint32_t m = ray_items[r];
+                if (m) ray_items[r] = 0u;
+                while (m) {
+                    const int j = __ffs((int)m) - 1;
+                    m &= m - 1u;
+                    const uint32_t q = item_prim[((size_t)r << 4) + (uint32_t)j];
+                    T t[2];
+                    ray_sphere<T>(o, d, spheres + 4 * (size_t)q, t);
+                    if (t[0] < best[0]) { best[0] = t[0]; best[1] = t[1]; p = q; }
+                }
+            }
+            hit[2 * (size_t)r] = best[0]; hit[2 * (size_t)r + 1] = best[1];
+            prim[r] = p;
+        }
+    }
+    const uint32_t m = (uint32_t)__popcll(__ballot(p != NONE));
+    if (lane_id() == 0) s_cnt[threadIdx.x / WAVE] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (uint32_t w = 0; w < blockDim.x / WAVE; w++) sum += s_cnt[w];
+        part[blockIdx.x] = sum;
+    }
+}
+// k_publish_counters for an any-hit, box or sphere batch: ctr[3] = the sum of k_any_resolve's per-workgroup counts, then the 8 counters go to the pinned
 // host page and are zeroed for the next call
 __global__ __launch_bounds__(256) void k_any_publish(unsigned long long* __restrict__ ctr, unsigned long long* __restrict__ host_page,
                                                      const uint32_t* __restrict__ part, uint32_t n_part) {
@@ -212,7 +263,8 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
     const bool stats = (flags & BVHGPU_TRAVERSE_STATS) != 0;
     const bool coherent = (flags & BVHGPU_TRAVERSE_COHERENT) != 0;
     const int ordered = (flags & BVHGPU_TRAVERSE_NEAREST_FIRST) ? 1 : ((flags & BVHGPU_TRAVERSE_FARTHEST_FIRST) ? 2 : 0);
-    const int mode = (flags & TRAVERSE_BOX_HIT) ? ((flags & BVHGPU_TRAVERSE_FIRST) ? MODE_BOX_FIRST : MODE_BOX_CLOSEST)
+    const int mode = (flags & TRAVERSE_SPHERE_HIT) ? ((flags & BVHGPU_TRAVERSE_FIRST) ? MODE_SPHERE_FIRST : MODE_SPHERE_CLOSEST)
+                   : (flags & TRAVERSE_BOX_HIT) ? ((flags & BVHGPU_TRAVERSE_FIRST) ? MODE_BOX_FIRST : MODE_BOX_CLOSEST)
                    : (flags & TRAVERSE_ANY_HIT) ? MODE_ANY
                    : (flags & BVHGPU_TRAVERSE_CLOSEST) ? MODE_CLOSEST
                    : (flags & BVHGPU_TRAVERSE_TRIANGLES) ? MODE_TRIANGLES
@@ -237,7 +289,7 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
     // CSR batches: 1, 4 or 16 items per ray.  Closest hit: whole rays, or the same cut into 16 items below ~2 M rays — the per-ray minimum over
     // the items goes through WalkOut::closest_key (f32: one 64-bit atomicMin per item with a candidate) or through the (ray, item) slots (f64:
     // k_closest_resolve_slots).  Any hit: the same choice, the lowest item with a candidate through WalkOut::any_key (one 32-bit atomicMin per
-    // item with a candidate, f32 and f64).  Box batches: closest like closest hit, first like any hit (k_box_resolve)
+    // item with a candidate, f32 and f64).  Box and sphere batches: closest like closest hit, first like any hit (k_box_resolve / k_sphere_resolve)
     int items_log4 = 0;
     if (use_wide && n_rays < WIDE_ITEM_MAX_RAYS) {
         const int want = ctx->tune[BVHGPU_TUNE_WIDE_ITEMS_LOG4];
@@ -277,9 +329,11 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
     unsigned long long* ctr_other = h->ctr.as<unsigned long long>() + 8 * ((h->ctr_set & 1) ^ 1);
 
     WalkOut<T> w{};
-    const bool box = mode_box(mode);
+    const bool box = mode_box(mode), sphere = mode_sphere(mode);
     w.ctr = ctr;
-    if (box) w.set_boxes(t->aabbs.as<T>()); else w.tris = t->tris.as<T>();   // (box batches read no triangles: their leaf primitive is the shape's own AABB)
+    if (box) w.set_boxes(t->aabbs.as<T>());   // (box batches read no triangles: their leaf primitive is the shape's own AABB)
+    else if (sphere) w.set_spheres(t->spheres.as<T>());   // (nor do sphere batches: bvhgpu_tree_set_spheres_*'s array)
+    else w.tris = t->tris.as<T>();
 
     uint32_t* ovf_flag = reinterpret_cast<uint32_t*>(ctr + 7);   // bit 0 ordered-iterator stack, bit 1 heap workspace, bit 2 wide-walk stack
     const bool best_first = ordered && (flags & BVHGPU_TRAVERSE_BEST_FIRST) != 0;
@@ -332,6 +386,17 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
             else if (keyed) BOX_RESOLVE(BOX_SRC_KEY64);
             else BOX_RESOLVE(BOX_SRC_SLOTS);
 #undef BOX_RESOLVE
+        } else if (sphere) {
+            h->any_part.reserve((size_t)rgrid.x * 4);
+            uint32_t* part = h->any_part.as<uint32_t>();
+            const T* spheres = t->spheres.as<T>();
+#define SPHERE_RESOLVE(SRC) hipLaunchKernelGGL((k_sphere_resolve<T, SRC>), rgrid, rblock, 0, st, w.any_key, w.closest_key, w.ray_items, (const uint32_t*)w.item_cnt, \
+                                               rays_dev, spheres, nr, w.closest, w.closest_prim, part)
+            if (!by_items) SPHERE_RESOLVE(BOX_SRC_RAY);
+            else if (any) SPHERE_RESOLVE(BOX_SRC_KEY32);
+            else if (keyed) SPHERE_RESOLVE(BOX_SRC_KEY64);
+            else SPHERE_RESOLVE(BOX_SRC_SLOTS);
+#undef SPHERE_RESOLVE
         } else if (any) {
             h->any_part.reserve((size_t)rgrid.x * 4);
             if (by_items) hipLaunchKernelGGL((k_any_resolve<T, true>), rgrid, rblock, 0, st, w.any_key, rays_dev, tris, nr, w.closest, w.closest_prim, h->any_part.as<uint32_t>());
@@ -345,7 +410,7 @@ void traverse_enqueue(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
         }
         if (ctx->timing) BVH_HIP(hipEventRecord(ctx->ev[6], st));
         // readback + reset for the next call
-        if (any || box) hipLaunchKernelGGL(k_any_publish, dim3(1), dim3(256), 0, st, ctr, pin, (const uint32_t*)h->any_part.as<uint32_t>(), rgrid.x);
+        if (any || box || sphere) hipLaunchKernelGGL(k_any_publish, dim3(1), dim3(256), 0, st, ctr, pin, (const uint32_t*)h->any_part.as<uint32_t>(), rgrid.x);
         else publish_counters(st, ctr, pin);
         h->ctr_clean = true;
         join_flat(t);
@@ -460,7 +525,7 @@ bool traverse_check(bvhgpu_hits* h) {
     if (h->pend_wide && (pin[7] & 4ull)) {   // a lane's stack outgrew LDS + workspace: the binary walks need no stack
         h->force_binary = true; h->wcounts_clean = false; h->bs_clean = false; h->ckey_clean = false; h->akey_clean = false; h->ray_items.release(); return false;
     }
-    if (flags & (TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT)) {   // the occluded rays (box: the rays with a candidate), counted by k_any_resolve / k_box_resolve and k_any_publish
+    if (flags & (TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT | TRAVERSE_SPHERE_HIT)) {   // the occluded rays (box, sphere: the rays with a candidate), counted by k_any_resolve / k_box_resolve / k_sphere_resolve and k_any_publish
         h->total = pin[3];
         if (ctx->timing) ctx->ev_set |= 4u;
         h->pend_tree = nullptr;

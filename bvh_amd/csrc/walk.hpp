@@ -26,13 +26,17 @@ enum : int {
     MODE_CLOSEST = 3,   // no CSR: per ray the candidate triangle with the smallest distance
     MODE_ANY = 4,       // no CSR: per ray the FIRST candidate (reference order) whose triangle distance is < the ray's tmax; the walk stops there
     MODE_BOX_CLOSEST = 5,   // no CSR, no triangles: per ray the shape of its list whose own AABB the ray enters first (t-slice {enter, exit}) with enter < tmax
-    MODE_BOX_FIRST = 6      // ... the FIRST shape of its list (reference order) with enter < tmax; the walk stops there
+    MODE_BOX_FIRST = 6,     // ... the FIRST shape of its list (reference order) with enter < tmax; the walk stops there
+    MODE_SPHERE_CLOSEST = 7,   // no CSR, no triangles: per ray the shape of its list whose sphere (WalkOut::sphere) the ray hits nearest ({distance, exit}) with distance < tmax
+    MODE_SPHERE_FIRST = 8      // ... the FIRST shape of its list (reference order) whose sphere the ray hits with distance < tmax; the walk stops there
 };
 // what the output modes share (the per-ray modes are MODE >= MODE_CLOSEST, the CSR modes MODE < MODE_CLOSEST)
 constexpr bool mode_tris(int m) { return m >= MODE_TRIANGLES && m <= MODE_ANY; }          // the leaf stage is Ray::intersects_triangle: needs the direction and w.tris
 constexpr bool mode_box(int m) { return m == MODE_BOX_CLOSEST || m == MODE_BOX_FIRST; }   // the leaf stage is the t-slice of the shape's own AABB
-constexpr bool mode_first(int m) { return m == MODE_ANY || m == MODE_BOX_FIRST; }         // the ray ends at its first candidate
-constexpr bool mode_tmax(int m) { return m == MODE_ANY || mode_box(m); }                  // candidates are limited by the ray's tmax
+constexpr bool mode_sphere(int m) { return m == MODE_SPHERE_CLOSEST || m == MODE_SPHERE_FIRST; }   // the leaf stage is ray_sphere on the shape's sphere: needs the direction
+constexpr bool mode_first(int m) { return m == MODE_ANY || m == MODE_BOX_FIRST || m == MODE_SPHERE_FIRST; }   // the ray ends at its first candidate
+constexpr bool mode_tmax(int m) { return m == MODE_ANY || mode_box(m) || mode_sphere(m); }   // candidates are limited by the ray's tmax
+constexpr bool mode_pair(int m) { return mode_box(m) || mode_sphere(m); }                 // the per-ray record is 2 scalars ({enter, exit} / {distance, exit}), not an Intersection
 template <int MODE> struct ModeVals { static constexpr int N = MODE == MODE_T_SLICE ? 2 : (MODE == MODE_TRIANGLES ? 3 : 0); };
 
 // ---- node fetch: two (f32) / four (f64) 16-byte loads per lane -------------------------------
@@ -67,9 +71,10 @@ template <typename T> struct WalkOut {
     T* pool_v;                   // ModeVals::N scalars per record
     unsigned long long pool_cap;
     unsigned long long* ctr;     // [0] pool slots taken [1] device steps [2] leaf-entry steps [4] wave steps [5] candidates (closest mode)
-    const T* tris;               // the leaf primitives.  Triangle modes: n x 9 vertices.  Box modes: the n x 6 shape AABBs, read through boxes() — one
-                                 // pointer for both, so that the kernel arguments of the existing instantiations stay as they are
-    T* closest;                  // per ray {distance,u,v} (closest mode); box modes: per ray {enter, exit}, 2 scalars
+    const T* tris;               // the leaf primitives.  Triangle modes: n x 9 vertices.  Box modes: the n x 6 shape AABBs, read through box().  Sphere modes:
+                                 // the n x 4 spheres {cx, cy, cz, r}, read through sphere() — one pointer for all, so that the kernel arguments of the
+                                 // existing instantiations stay as they are
+    T* closest;                  // per ray {distance,u,v} (closest mode); box modes: per ray {enter, exit}, sphere modes: {distance, exit} — 2 scalars
     uint32_t* closest_prim;      // per ray shape index or NONE
     unsigned long long* closest_key;   // closest mode with rays cut into items (f32): per ray min over its items of {key(distance) << 32 | item << 28 | shape}
                                  // (kept all-ones between batches; k_closest_resolve turns the winner into closest / closest_prim).  NULL: one lane owns the ray
@@ -80,12 +85,15 @@ template <typename T> struct WalkOut {
                                  // HitRec: 8 bytes per hit, one offset gather per two hits in the scatter.  NULL: HitRec
     uint32_t* raybuf;            // wide walk, whole rays, indices only: the first 2^stage_shift shapes of ray r go straight to raybuf[r << stage_shift | k]
     uint32_t stage_shift;        // (4 bytes per hit, no record, no atomic); only later hits of a ray become pool records.  NULL: everything through the pool
-    const T* tmax;               // any-hit and box modes: per ray the end of its segment (NULL: +inf for every ray)
+    const T* tmax;               // any-hit, box and sphere modes: per ray the end of its segment (NULL: +inf for every ray)
     uint32_t* any_key;           // any-hit mode with rays cut into items: per ray min over its items that found a candidate of {item << 28 | shape}
                                  // (kept all-ones between batches; k_any_resolve turns the winner into closest / closest_prim).  NULL: one lane owns the ray
     // box modes: shape s's own AABB {min xyz, max xyz} (the wide walk's leaf stage)
     __host__ __device__ __forceinline__ const T* box(uint32_t s) const { return tris + 6 * (size_t)s; }
     __host__ __device__ __forceinline__ void set_boxes(const T* aabbs) { tris = aabbs; }
+    // sphere modes: shape s's sphere {cx, cy, cz, r} (16-byte aligned: bvhgpu_tree::spheres is an allocation of its own)
+    __host__ __device__ __forceinline__ const T* sphere(uint32_t s) const { return tris + 4 * (size_t)s; }
+    __host__ __device__ __forceinline__ void set_spheres(const T* spheres) { tris = spheres; }
 };
 
 // ---- Ray::intersects_triangle (ray_impl.rs:154-213), Möller–Trumbore with back-face culling.  Same
@@ -126,12 +134,45 @@ __device__ __forceinline__ void ray_triangle(const T o[3], const T d[3], const T
     if (dist > Traits<T>::eps()) out[0] = dist;                                              // :215-219
 }
 
+// ---- the leaf stage of the sphere modes (include/bvh_mi355x.h, bvhgpu_traverse_sphere_*): the geometric form — the ray's point nearest the
+//      centre, then the half chord — because b*b - a*c loses r*r against |o - c|^2 in f32 for distant origins.  Every operation is rounded once
+//      in T, dot3 as above, no contraction.  out = {distance, exit}; a miss is {+inf, 0}.  Nothing is special-cased: a NaN centre, radius or
+//      direction and a zero direction (a = 0: tc is NaN or inf, l is NaN) fail disc >= 0; r < 0 enters squared; an origin inside the sphere has
+//      t0 <= eps and hits at t1.  `sphere` is 16-byte aligned: one 16-byte load (f32), two (f64).
+__device__ __forceinline__ void load_sphere(const float* __restrict__ p, float s[4]) {
+    const float4 v = *reinterpret_cast<const float4*>(p);
+    s[0] = v.x; s[1] = v.y; s[2] = v.z; s[3] = v.w;
+}
+__device__ __forceinline__ void load_sphere(const double* __restrict__ p, double s[4]) {
+    const double2 a = reinterpret_cast<const double2*>(p)[0], b = reinterpret_cast<const double2*>(p)[1];
+    s[0] = a.x; s[1] = a.y; s[2] = b.x; s[3] = b.y;
+}
+template <typename T>
+__device__ __forceinline__ void ray_sphere(const T o[3], const T d[3], const T* __restrict__ sphere, T out[2]) {
+    T s[4], f[3], l[3];
+    load_sphere(sphere, s);
+#pragma unroll
+    for (int k = 0; k < 3; k++) f[k] = o[k] - s[k];
+    const T a = dot3<T>(d, d);
+    const T tc = (-dot3<T>(f, d)) / a;                 // parameter of the ray's point nearest the centre
+#pragma unroll
+    for (int k = 0; k < 3; k++) { const T td = tc * d[k]; l[k] = f[k] + td; }   // centre → that point
+    const T rr = s[3] * s[3];
+    const T disc = rr - dot3<T>(l, l);
+    out[0] = Traits<T>::inf(); out[1] = 0;
+    if (!(disc >= (T)0)) return;
+    const T h = sqrt(disc / a);
+    const T t0 = tc - h, t1 = tc + h;
+    const T t = t0 > Traits<T>::eps() ? t0 : t1;
+    if (t > Traits<T>::eps()) { out[0] = t; out[1] = t1; }
+}
+
 // ---- per-lane ray state
 template <typename T, int MODE> struct LaneRay {
     T o[3], inv[3];
-    T d[mode_tris(MODE) ? 3 : 1];          // direction: only the triangle stage needs it
-    T best[MODE >= MODE_CLOSEST ? 3 : 1];  // closest Intersection so far / the any-hit candidate / box modes: {enter, exit} of the candidate
-    T tmax;                                // any-hit and box modes: end of the segment
+    T d[mode_tris(MODE) || mode_sphere(MODE) ? 3 : 1];   // direction: only the triangle and sphere stages need it
+    T best[MODE >= MODE_CLOSEST ? 3 : 1];  // closest Intersection so far / the any-hit candidate / box modes: {enter, exit}, sphere modes: {distance, exit} of the candidate
+    T tmax;                                // any-hit, box and sphere modes: end of the segment
     uint32_t best_prim;
     uint32_t r, cnt;
     bool fin;                              // all components finite → NaN-free slab test is exact
@@ -140,12 +181,12 @@ template <typename T, int MODE> struct LaneRay {
         for (int k = 0; k < 3; k++) { o[k] = 0; inv[k] = 0; }
         d[0] = 0; best[0] = 0; tmax = 0; best_prim = NONE; r = NONE; cnt = 0; fin = true;
     }
-    // tmaxs: WalkOut::tmax (any-hit and box modes only)
+    // tmaxs: WalkOut::tmax (any-hit, box and sphere modes only)
     __device__ __forceinline__ void load(const typename Traits<T>::Ray* __restrict__ rays, uint32_t ray, const T* __restrict__ tmaxs = nullptr) {
         const typename Traits<T>::Ray* rp = rays + ray;
 #pragma unroll
         for (int k = 0; k < 3; k++) { o[k] = rp->o[k]; inv[k] = rp->inv[k]; }
-        if (mode_tris(MODE)) {
+        if (mode_tris(MODE) || mode_sphere(MODE)) {
 #pragma unroll
             for (int k = 0; k < 3; k++) d[k] = rp->d[k];
         }
@@ -161,7 +202,7 @@ template <typename T, int MODE> struct LaneRay {
     }
     // the ray has left the tree: its Vec / closest hit is complete
     __device__ __forceinline__ void retire(const WalkOut<T>& w) {
-        if (mode_box(MODE)) {
+        if (mode_pair(MODE)) {
             w.closest[2 * (size_t)r] = best[0]; w.closest[2 * (size_t)r + 1] = best[1];
             w.closest_prim[r] = best_prim;
         } else if (MODE >= MODE_CLOSEST) {
@@ -213,6 +254,15 @@ __device__ __forceinline__ void report(bool rec, uint32_t shape, T t0, T t1, Lan
         // a candidate enters its box before the segment ends (strict, in T: a NaN, zero or negative tmax admits nothing).  Closest: strictly
         // nearer than the lane's best so far, so that on equal entries the first of the list stays; first: it ends the ray like MODE_ANY
         if (rec && t0 < ray.tmax && (MODE == MODE_BOX_FIRST || t0 < ray.best[0])) { ray.best[0] = t0; ray.best[1] = t1; ray.best_prim = shape; }
+        return;
+    }
+    if (mode_sphere(MODE)) {
+        // the same rule on ray_sphere's distance: a miss is +inf, which is below no tmax (NULL tmax: +inf) — strict, so ties keep the first
+        if (rec) {
+            T hit[2];
+            ray_sphere<T>(ray.o, ray.d, w.sphere(shape), hit);
+            if (hit[0] < ray.tmax && (MODE == MODE_SPHERE_FIRST || hit[0] < ray.best[0])) { ray.best[0] = hit[0]; ray.best[1] = hit[1]; ray.best_prim = shape; }
+        }
         return;
     }
     constexpr int NV = ModeVals<MODE>::N;

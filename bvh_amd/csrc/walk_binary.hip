@@ -267,6 +267,8 @@ void launch_binary(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, size
         case MODE_ANY: WALK(MODE_ANY, false); break;
         case MODE_BOX_CLOSEST: WALK(MODE_BOX_CLOSEST, false); break;
         case MODE_BOX_FIRST: WALK(MODE_BOX_FIRST, false); break;
+        case MODE_SPHERE_CLOSEST: WALK(MODE_SPHERE_CLOSEST, false); break;
+        case MODE_SPHERE_FIRST: WALK(MODE_SPHERE_FIRST, false); break;
         default: if (stats) WALK(MODE_CLOSEST, true); else WALK(MODE_CLOSEST, false); break;
     }
 #undef WALK

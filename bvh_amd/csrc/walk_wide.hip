@@ -465,21 +465,22 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES) void k_traverse_wide(
                 if (mode_first(MODE)) {
                     if constexpr (ITEMS_LOG4 == 0) {
                         const size_t r = item;
-                        if constexpr (mode_box(MODE)) { w.closest[2 * r] = ray.best[0]; w.closest[2 * r + 1] = ray.best[1]; }
+                        if constexpr (mode_pair(MODE)) { w.closest[2 * r] = ray.best[0]; w.closest[2 * r + 1] = ray.best[1]; }
                         else { w.closest[3 * r] = ray.best[0]; w.closest[3 * r + 1] = ray.best[1]; w.closest[3 * r + 2] = ray.best[2]; }
                         w.closest_prim[r] = ray.best_prim;
                     } else if (ray.best_prim != NONE) {
                         // The ray's list is the concatenation of its items' lists in item order, and this lane stopped at its item's first
                         // candidate inside the segment: the ray's answer is the candidate of the LOWEST item that found one.  Item (< 16) and
-                        // shape (< 2^28: WIDE_MAX_SHAPES) fit one 32-bit key: one atomicMin; k_any_resolve recomputes the Intersection (k_box_resolve the t-slice).
+                        // shape (< 2^28: WIDE_MAX_SHAPES) fit one 32-bit key: one atomicMin; k_any_resolve recomputes the Intersection (k_box_resolve the t-slice,
+                        // k_sphere_resolve the sphere hit).
                         const uint32_t j = item & ((1u << WIDE_ITEM_BITS) - 1u);
                         const uint32_t jj = j == WIDE_ITEM_WHOLE ? 0u : j;
                         atomicMin(&w.any_key[item >> WIDE_ITEM_BITS], (jj << 28) | ray.best_prim);
                     }
-                } else if (MODE == MODE_CLOSEST || MODE == MODE_BOX_CLOSEST) {   // (box: the distance is the entry parameter, non-negative — the same keys and slots)
+                } else if (MODE == MODE_CLOSEST || MODE == MODE_BOX_CLOSEST || MODE == MODE_SPHERE_CLOSEST) {   // (box: the distance is the entry parameter, non-negative; sphere: > eps — the same keys and slots)
                     if constexpr (ITEMS_LOG4 == 0) {
                         const size_t r = item;
-                        if constexpr (mode_box(MODE)) { w.closest[2 * r] = ray.best[0]; w.closest[2 * r + 1] = ray.best[1]; }
+                        if constexpr (mode_pair(MODE)) { w.closest[2 * r] = ray.best[0]; w.closest[2 * r + 1] = ray.best[1]; }
                         else if constexpr (!GUIDE_CLOSEST) { w.closest[3 * r] = ray.best[0]; w.closest[3 * r + 1] = ray.best[1]; w.closest[3 * r + 2] = ray.best[2]; }
                         w.closest_prim[r] = ray.best_prim;   // (guide: the shape only — k_closest_from_prim recomputes its Intersection in f64)
                     } else if (ray.best_prim != NONE) {
@@ -796,6 +797,8 @@ void launch_wide_walk(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, s
         case MODE_ANY: launch_wide_items<T, MODE_ANY>(t, rays_dev, n_rays, w, h, items_log4, ovf_flag, false); break;
         case MODE_BOX_CLOSEST: launch_wide_items<T, MODE_BOX_CLOSEST>(t, rays_dev, n_rays, w, h, items_log4, ovf_flag, false); break;
         case MODE_BOX_FIRST: launch_wide_items<T, MODE_BOX_FIRST>(t, rays_dev, n_rays, w, h, items_log4, ovf_flag, false); break;
+        case MODE_SPHERE_CLOSEST: launch_wide_items<T, MODE_SPHERE_CLOSEST>(t, rays_dev, n_rays, w, h, items_log4, ovf_flag, false); break;
+        case MODE_SPHERE_FIRST: launch_wide_items<T, MODE_SPHERE_FIRST>(t, rays_dev, n_rays, w, h, items_log4, ovf_flag, false); break;
         default: launch_wide_items<T, MODE_CLOSEST>(t, rays_dev, n_rays, w, h, items_log4, ovf_flag, false); break;
     }
 }

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define BVHGPU_ABI_VERSION 7 /* 7: bvhgpu_host_alloc/free/register/unregister, bvhgpu_traverse_host_*, bvhgpu_build_traverse_host_*, bvhgpu_traverse_host_indices, bvhgpu_query_f32/_f64 + BVHGPU_QUERY_AABB/_POINT/_BALL, bvhgpu_traverse_any_f32/_f64 + bvhgpu_hits_fetch_any, bvhgpu_traverse_box_f32/_f64 + bvhgpu_hits_fetch_box + BVHGPU_TRAVERSE_FIRST, bvhgpu_knearest_f32/_f64 + BVHGPU_KNN_MAX_K, BVHGPU_TUNE_COUNT 23 (slots 17 = HOST_CHUNKS, 18 = WIDE_MIN_RAYS_PER_WG, 19 = HOST_ZERO_COPY, 20 = BUILD_LEVEL_TILE, 21 = FLATTEN_INLINE, 22 = QUERY_VARIANT).  6: BVHGPU_TUNE_COUNT 17 (slots 15 = FLATTEN_LAZY, 16 = BUILD_LEVEL_PERSIST), bvhgpu_hits_walk_kernel.  5: bvhgpu_rccl_info.  4: BVHGPU_TUNE_COUNT 15 (slot 14 = WIDE_F64_GUIDE), bvhgpu_hits_walk_info.  3: BVHGPU_REBROADCAST, broadcast status header, scene blob BVH6 (exact_only), BVHGPU_TUNE_COUNT 14 (slots 11 = WIDE_EARLY_ITEMS, 12 = WIDE_STAGE_SHIFT, 13 = WIDE_REC8), BVHGPU_TRAVERSE_RAYS_READY, bvhgpu_device_alloc/free/copy */
+#define BVHGPU_ABI_VERSION 7 /* 7: bvhgpu_host_alloc/free/register/unregister, bvhgpu_traverse_host_*, bvhgpu_build_traverse_host_*, bvhgpu_traverse_host_indices, bvhgpu_query_f32/_f64 + BVHGPU_QUERY_AABB/_POINT/_BALL, bvhgpu_traverse_any_f32/_f64 + bvhgpu_hits_fetch_any, bvhgpu_traverse_box_f32/_f64 + bvhgpu_hits_fetch_box + BVHGPU_TRAVERSE_FIRST, bvhgpu_tree_set_spheres_f32/_f64 + bvhgpu_traverse_sphere_f32/_f64 + bvhgpu_hits_fetch_sphere, bvhgpu_knearest_f32/_f64 + BVHGPU_KNN_MAX_K, BVHGPU_TUNE_COUNT 23 (slots 17 = HOST_CHUNKS, 18 = WIDE_MIN_RAYS_PER_WG, 19 = HOST_ZERO_COPY, 20 = BUILD_LEVEL_TILE, 21 = FLATTEN_INLINE, 22 = QUERY_VARIANT).  6: BVHGPU_TUNE_COUNT 17 (slots 15 = FLATTEN_LAZY, 16 = BUILD_LEVEL_PERSIST), bvhgpu_hits_walk_kernel.  5: bvhgpu_rccl_info.  4: BVHGPU_TUNE_COUNT 15 (slot 14 = WIDE_F64_GUIDE), bvhgpu_hits_walk_info.  3: BVHGPU_REBROADCAST, broadcast status header, scene blob BVH6 (exact_only), BVHGPU_TUNE_COUNT 14 (slots 11 = WIDE_EARLY_ITEMS, 12 = WIDE_STAGE_SHIFT, 13 = WIDE_REC8), BVHGPU_TRAVERSE_RAYS_READY, bvhgpu_device_alloc/free/copy */
 #define BVHGPU_NONE 0xFFFFFFFFu /* u32::MAX marker (flat_bvh.rs:51-53, :124, :137) */
 
 typedef enum {
@@ -88,7 +88,7 @@ typedef enum { BVHGPU_HOST = 0, BVHGPU_DEVICE = 1 } bvhgpu_mem;
                                         instead of two: the copy engines idle 10 - 20 µs between two transfers */
 #define BVHGPU_TRAVERSE_COHERENT 16u /* hint: neighbouring rays are similar (primary rays).  Large whole-ray batches then hand their hits over
                                         through per-ray slots instead of pool records (BVHGPU_TUNE_WIDE_STAGE_SHIFT); results never depend on it */
-#define BVHGPU_TRAVERSE_FIRST 1024u /* bvhgpu_traverse_box_* only: the first candidate of the ray's list instead of the one entered first */
+#define BVHGPU_TRAVERSE_FIRST 1024u /* bvhgpu_traverse_box_* / bvhgpu_traverse_sphere_* only: the first candidate of the ray's list instead of the nearest one */
 
 /* ---- POD layouts (little-endian, natural alignment, no packing pragmas) ---- */
 
@@ -499,6 +499,51 @@ int bvhgpu_traverse_box_f32(bvhgpu_tree *tree, const bvhgpu_ray_f32 *rays, const
 int bvhgpu_traverse_box_f64(bvhgpu_tree *tree, const bvhgpu_ray_f64 *rays, const double *tmax, size_t n_rays, int mem, unsigned flags,
                             bvhgpu_hits **hits);
 int bvhgpu_hits_fetch_box(bvhgpu_hits *hits, void *slice, uint32_t *shape, int mem);
+
+/* ---- closest-hit and any-hit ray queries against sphere shapes: "which sphere does this ray hit first?" / "is anything in the way before
+ * tmax?" for particles, atoms, splats, bounding spheres — the fused form of the reference's first example (examples/simple.rs: build from the
+ * spheres' AABBs, traverse, then a ray-sphere test over the returned list on the host).
+ * Shape s has a sphere {c[3], r} in the tree's dtype T, set with bvhgpu_tree_set_spheres_*.  The sphere is independent of the AABB the tree
+ * was built from.  The caller normally builds from c -/+ r, as simple.rs does.
+ * Ray i has tmax[i] in T.  A NULL tmax means +inf for every ray.  L_i is the list FlatBvh::traverse(&ray_i, shapes) returns, in its order.
+ * That is the engine's CSR row.
+ * For s in L_i, with the ray's o and d as the Ray record holds them, the leaf stage is the following.  Every operation is rounded once in T,
+ * with no contraction.  dot3 is (a0*b0 + a1*b1) + a2*b2.
+ *     f[k] = o[k] - c[k]
+ *     a    = dot3(d, d)
+ *     tc   = (-dot3(f, d)) / a              parameter of the ray's point nearest the centre
+ *     l[k] = f[k] + tc * d[k]               centre -> that point
+ *     disc = r*r - dot3(l, l)
+ *     if !(disc >= 0): miss
+ *     h  = sqrt(disc / a)
+ *     t0 = tc - h ;  t1 = tc + h
+ *     t  = (t0 > eps) ? t0 : t1             eps = T::epsilon(), the triangle stage's bound
+ *     hit iff t > eps  ->  {distance = t, exit = t1};   miss -> {+inf, 0}
+ *  - Why the geometric form.  It is chosen over b*b - a*c because that form loses r*r against |f|^2 in f32 for distant origins.
+ *  - What follows from the arithmetic.  Nothing else is special-cased.  A NaN centre, radius or direction misses.  r < 0 acts like |r|.  A
+ *    zero direction misses.  An origin inside the sphere hits at t1.  A distance of +inf is never below any tmax.
+ *  - Candidate.  s is a candidate iff it hits and distance < tmax[i], strict and in T.  A NaN, zero or negative tmax admits nothing.
+ *  - closest (default): the candidate with the smallest distance, and the first of L_i on equal distances.
+ *  - first (BVHGPU_TRAVERSE_FIRST): the first candidate of L_i.  Every walk may stop there.
+ *  - Result per ray.  {distance, exit} and the shape.  Without a candidate, {+inf, 0} and BVHGPU_NONE.  bvhgpu_hits_info's `total` is the
+ *    number of rays with a candidate.
+ *  - Sphere data is never validated.  NaN, infinite and negative radii follow the arithmetic.
+ *  - Trees.  It holds for every tree the CSR walks accept: built here, refitted, an uploaded FlatBvh, imported, or with empty child bounds.
+ *    Scene export and broadcast do not carry spheres.  A receiving tree has none until they are set.
+ * bvhgpu_tree_set_spheres_*: `spheres` is n x 4 T {cx, cy, cz, r} in `mem`; the tree keeps its own HBM copy, beside any triangles.  n must
+ * equal the tree's shape count (BVHGPU_INVALID_ARG); another dtype than the tree's is BVHGPU_DTYPE_MISMATCH.  A rebuild with a different
+ * shape count drops the spheres, as it drops the triangles; refit does not touch them.
+ * bvhgpu_traverse_sphere_*: `rays`, `tmax`, `flags` (BVHGPU_TRAVERSE_COHERENT, BVHGPU_TRAVERSE_FIRST) and the statuses are those of
+ * bvhgpu_traverse_box_*; without spheres set, BVHGPU_INVALID_ARG ("... need bvhgpu_tree_set_spheres first").  _fetch / _fetch_triangles /
+ * _fetch_closest / _fetch_any / _fetch_box / _device return BVHGPU_INVALID_ARG on such a result, and bvhgpu_hits_fetch_sphere on any other.
+ * bvhgpu_hits_fetch_sphere: per ray {distance, exit} (n x 2 T) and the shape (n u32); either may be NULL. */
+int bvhgpu_tree_set_spheres_f32(bvhgpu_tree *tree, const float *spheres /* n x 4: cx, cy, cz, r */, size_t n, int mem);
+int bvhgpu_tree_set_spheres_f64(bvhgpu_tree *tree, const double *spheres /* n x 4: cx, cy, cz, r */, size_t n, int mem);
+int bvhgpu_traverse_sphere_f32(bvhgpu_tree *tree, const bvhgpu_ray_f32 *rays, const float *tmax, size_t n_rays, int mem, unsigned flags,
+                               bvhgpu_hits **hits);
+int bvhgpu_traverse_sphere_f64(bvhgpu_tree *tree, const bvhgpu_ray_f64 *rays, const double *tmax, size_t n_rays, int mem, unsigned flags,
+                               bvhgpu_hits **hits);
+int bvhgpu_hits_fetch_sphere(bvhgpu_hits *hits, void *slice, uint32_t *shape, int mem);
 
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */

@@ -185,6 +185,11 @@ extern "C" {
     pub fn bvhgpu_traverse_box_f32(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_traverse_box_f64(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_hits_fetch_box(h: *mut bvhgpu_hits, slice: *mut c_void, shape: *mut u32, mem: c_int) -> c_int;
+    pub fn bvhgpu_tree_set_spheres_f32(t: *mut bvhgpu_tree, spheres: *const f32, n: usize, mem: c_int) -> c_int;
+    pub fn bvhgpu_tree_set_spheres_f64(t: *mut bvhgpu_tree, spheres: *const f64, n: usize, mem: c_int) -> c_int;
+    pub fn bvhgpu_traverse_sphere_f32(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_traverse_sphere_f64(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_hits_fetch_sphere(h: *mut bvhgpu_hits, slice: *mut c_void, shape: *mut u32, mem: c_int) -> c_int;
     // timing, scene ingest, tuning
     pub fn bvhgpu_enable_timing(ctx: *mut bvhgpu_ctx, on: c_int) -> c_int;
     pub fn bvhgpu_last_timings(ctx: *mut bvhgpu_ctx, out: *mut bvhgpu_timings) -> c_int;

@@ -92,6 +92,9 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
     unsafe fn traverse_any(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
     #[allow(clippy::too_many_arguments)]
     unsafe fn traverse_box(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
+    unsafe fn set_spheres(t: *mut ffi::bvhgpu_tree, spheres: *const Self, n: usize, mem: c_int) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn traverse_sphere(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
     #[allow(clippy::too_many_arguments)]
     unsafe fn knearest(t: *mut ffi::bvhgpu_tree, points: *const Self, n: usize, mem: c_int, kind: c_int, k: u32, out_shape: *mut u32, out_dist: *mut Self) -> c_int;
     #[allow(clippy::too_many_arguments)]
@@ -105,7 +108,7 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
 
 macro_rules! impl_gpu_scalar {
     ($t:ty, $dtype:expr, $node:ident, $flat:ident, $ray:ident, $build_flat:ident, $rebuild_flat:ident, $refit:ident, $traverse:ident,
-     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $traverse_box:ident, $knearest:ident, $knearest_tree:ident,
+     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $traverse_box:ident, $set_spheres:ident, $traverse_sphere:ident, $knearest:ident, $knearest_tree:ident,
      $flat_ctor:expr) => {
         impl GpuScalar for $t {
             type Node = ffi::$node;
@@ -147,6 +150,12 @@ macro_rules! impl_gpu_scalar {
             }
             unsafe fn traverse_box(t: *mut ffi::bvhgpu_tree, rays: *const ffi::$ray, tmax: *const $t, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int {
                 ffi::$traverse_box(t, rays, tmax, n, mem, flags, hits)
+            }
+            unsafe fn set_spheres(t: *mut ffi::bvhgpu_tree, spheres: *const $t, n: usize, mem: c_int) -> c_int {
+                ffi::$set_spheres(t, spheres, n, mem)
+            }
+            unsafe fn traverse_sphere(t: *mut ffi::bvhgpu_tree, rays: *const ffi::$ray, tmax: *const $t, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int {
+                ffi::$traverse_sphere(t, rays, tmax, n, mem, flags, hits)
             }
             unsafe fn knearest(t: *mut ffi::bvhgpu_tree, points: *const $t, n: usize, mem: c_int, kind: c_int, k: u32, out_shape: *mut u32, out_dist: *mut $t) -> c_int {
                 ffi::$knearest(t, points, n, mem, kind, k, out_shape, out_dist)
@@ -192,11 +201,11 @@ macro_rules! impl_gpu_scalar {
 }
 impl_gpu_scalar!(f32, ffi::BVHGPU_F32, bvhgpu_node_f32, bvhgpu_flat_f32, bvhgpu_ray_f32, bvhgpu_build_flat_f32, bvhgpu_rebuild_flat_f32,
                  bvhgpu_refit_f32, bvhgpu_traverse_f32, bvhgpu_tree_set_triangles_f32, bvhgpu_tree_from_flat_f32,
-                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_traverse_box_f32, bvhgpu_knearest_f32, bvhgpu_knearest_tree_f32,
+                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_traverse_box_f32, bvhgpu_tree_set_spheres_f32, bvhgpu_traverse_sphere_f32, bvhgpu_knearest_f32, bvhgpu_knearest_tree_f32,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f32 { min, max, entry, exit, shape });
 impl_gpu_scalar!(f64, ffi::BVHGPU_F64, bvhgpu_node_f64, bvhgpu_flat_f64, bvhgpu_ray_f64, bvhgpu_build_flat_f64, bvhgpu_rebuild_flat_f64,
                  bvhgpu_refit_f64, bvhgpu_traverse_f64, bvhgpu_tree_set_triangles_f64, bvhgpu_tree_from_flat_f64,
-                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_traverse_box_f64, bvhgpu_knearest_f64, bvhgpu_knearest_tree_f64,
+                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_traverse_box_f64, bvhgpu_tree_set_spheres_f64, bvhgpu_traverse_sphere_f64, bvhgpu_knearest_f64, bvhgpu_knearest_tree_f64,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f64 { min, max, entry, exit, shape, _pad: 0 });
 
 fn aabb_to_6<T: GpuScalar>(b: &Aabb<T, 3>) -> [T; 6] {
@@ -243,6 +252,15 @@ pub struct ClosestHit<T> {
 /// winning shape's AABB and that shape; `shape == u32::MAX`, `enter == +inf` and `exit == 0` when the ray has no candidate
 pub struct BoxHit<T> {
     pub enter: T,
+    pub exit: T,
+    pub shape: u32,
+}
+
+/// Result of a ray query against sphere shapes (`GpuBvh::closest_sphere_hits` / `first_sphere_hits`): the ray parameters at which it enters
+/// (`distance`; the exit for an origin inside) and leaves (`exit`) the winning shape's sphere, and that shape; `shape == u32::MAX`,
+/// `distance == +inf` and `exit == 0` when the ray has no candidate
+pub struct SphereHit<T> {
+    pub distance: T,
     pub exit: T,
     pub shape: u32,
 }
@@ -509,6 +527,48 @@ impl<T: GpuScalar> GpuBvh<T> {
             ffi::bvhgpu_hits_destroy(hits);
         }
         slice.iter().zip(shape).map(|(t, s)| BoxHit { enter: t[0], exit: t[1], shape: s }).collect()
+    }
+
+    /// One sphere per shape, `[cx, cy, cz, r]` (`bvhgpu_tree_set_spheres_*`): the leaf primitive of the sphere queries.  Independent of the
+    /// AABBs the tree was built from — normally `c ∓ r`, as the reference's `examples/simple.rs` builds them; never validated.
+    pub fn set_spheres(&mut self, spheres: &[[T; 4]]) {
+        assert_eq!(spheres.len(), self.n_shapes, "one sphere per shape");
+        unsafe { check(self.ctx, T::set_spheres(self.tree, spheres.as_ptr().cast(), spheres.len(), ffi::BVHGPU_HOST)); }
+    }
+
+    fn sphere_hits(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>, first: bool) -> Vec<SphereHit<T>> {
+        if let Some(tm) = tmax {
+            assert_eq!(tm.len(), rays.len(), "one tmax per ray");
+        }
+        let r: Vec<T::RayC> = rays.iter().map(T::ray_to_ffi).collect();
+        let mut hits = core::ptr::null_mut();
+        let mut hit = vec![[T::default(); 2]; rays.len()];
+        let mut shape = vec![0u32; rays.len()];
+        let tp = tmax.map_or(core::ptr::null(), |t| t.as_ptr());
+        let flags = if first { ffi::BVHGPU_TRAVERSE_FIRST } else { 0 };
+        unsafe {
+            check(self.ctx, T::traverse_sphere(self.tree, r.as_ptr(), tp, r.len(), ffi::BVHGPU_HOST, flags, &mut hits));
+            check(self.ctx, ffi::bvhgpu_hits_fetch_sphere(hits, hit.as_mut_ptr() as *mut c_void, shape.as_mut_ptr(), ffi::BVHGPU_HOST));
+            ffi::bvhgpu_hits_destroy(hits);
+        }
+        hit.iter().zip(shape).map(|(t, s)| SphereHit { distance: t[0], exit: t[1], shape: s }).collect()
+    }
+
+    /// What `examples/simple.rs` computes on the host after `traverse`, fused into the walk (`bvhgpu_traverse_sphere_*`): per ray, among
+    /// the shapes of `FlatBvh::traverse`'s list whose sphere the ray hits with `distance < tmax[i]` (strict; `tmax: None` = +inf for every
+    /// ray), the nearest one — the first of the list on equal distances.  Needs `set_spheres`.
+    pub fn closest_sphere_hits(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>) -> Vec<SphereHit<T>> {
+        self.sphere_hits(rays, tmax, false)
+    }
+
+    /// ... the FIRST such shape of the list instead of the nearest one (`BVHGPU_TRAVERSE_FIRST`, any-hit: every walk stops at it)
+    pub fn first_sphere_hits(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>) -> Vec<SphereHit<T>> {
+        self.sphere_hits(rays, tmax, true)
+    }
+
+    /// `first_sphere_hits` reduced to one flag per ray: does ray i hit any sphere before `tmax[i]`
+    pub fn sphere_occluded(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>) -> Vec<bool> {
+        self.first_sphere_hits(rays, tmax).iter().map(|h| h.shape != ffi::BVHGPU_NONE).collect()
     }
 
     /// The `k` nearest shapes of every point (`bvhgpu_knearest_*`): the loop of `FlatBvh::nearest_to` (src/flat_bvh.rs:524-558) with a list of

@@ -761,6 +761,39 @@ class _TreeBase:
         _, shape = self.first_sphere_hits(rays, tmax)
         return shape != NONE
 
+    # ---- multi-hit ray queries ---------------------------------------------------------------
+    def khits_batch(self, rays: RayBatch, k: int, leaf: str = "box", tmax=None):
+        """bvhgpu_traverse_khits_*: the k nearest hits of every ray.  Row i is the candidates of FlatBvh::traverse's list (flat_bvh.rs:396-431)
+        — the members whose leaf-stage distance is < tmax[i], strict — in a stable ascending sort by distance (equal distances in list
+        order), cut to the first k.  leaf: "box" ({enter, exit} on the shape's own AABB), "triangle" (Intersection{distance, u, v}; needs
+        set_triangles) or "sphere" ({distance, exit}; needs set_spheres).  1 <= k <= _lib.KHITS_MAX_K.  tmax as for any_hits.
+        returns (vals[n, k, W], shape[n, k]), W = 3 for triangles, else 2; slots beyond the number of candidates hold NONE and (+inf, 0[, 0]).
+        HOST rays: numpy out, shape as uint32.  Rays in HBM: torch tensors on the same device, written by the kernel with no host round
+        trip, shape as torch.int32 — so NONE reads as -1 there."""
+        if rays.sfx != self.sfx:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
+        if leaf not in _lib.LEAF_KINDS:
+            raise BvhGpuError(_lib.INVALID_ARG, f"leaf must be one of {sorted(_lib.LEAF_KINDS)}")
+        kind = _lib.LEAF_KINDS[leaf]
+        w = _lib.LEAF_WIDTH[kind]
+        k = int(k)
+        rows = k if 1 <= k <= _lib.KHITS_MAX_K else 0     # (out of range: the engine answers INVALID_ARG before it touches a buffer)
+        keep, tp = self._tmax_arg(rays, tmax)   # (keep: the array tp points into stays alive over the call)
+        fn = getattr(_lib.load(), f"bvhgpu_traverse_khits_{self.sfx}")
+        if rays.mem == DEVICE:
+            import torch
+            dev = rays.device.device
+            shape = torch.empty((rays.n, rows), dtype=torch.int32, device=dev)
+            vals = torch.empty((rays.n, rows, w), dtype=torch.float32 if self.sfx == "f32" else torch.float64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()   # the engine works on its own stream: the rays must be there
+            check(fn(self._t, rays._ptr(), tp, rays.n, DEVICE, kind, k & 0xFFFFFFFF, ptr(shape.data_ptr()), ptr(vals.data_ptr())), self.ctx._h)
+            return vals, shape
+        ft = np.float32 if self.sfx == "f32" else np.float64
+        shape = np.zeros((rays.n, rows), dtype=np.uint32)
+        vals = np.zeros((rays.n, rows, w), dtype=ft)
+        check(fn(self._t, rays._ptr(), tp, rays.n, HOST, kind, k & 0xFFFFFFFF, ptr(shape), ptr(vals)), self.ctx._h)
+        return vals, shape
+
     # ---- point query ---------------------------------------------------------------------
     def nearest_batch(self, points, triangles: bool = False):
         """<FlatBvh as BoundingHierarchy>::nearest_to (flat_bvh.rs:513-562) for many points.  Shape distance: the
@@ -1183,6 +1216,10 @@ class Bvh(_TreeBase):
     def knearest_batch(self, points, k: int, triangles: bool = False):
         self.flatten_in_place()
         return super().knearest_batch(points, k, triangles)
+
+    def khits_batch(self, rays: RayBatch, k: int, leaf: str = "box", tmax=None):
+        self.flatten_in_place()
+        return super().khits_batch(rays, k, leaf, tmax)
 
 
 class _FlatView(FlatBvh):

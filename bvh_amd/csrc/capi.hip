@@ -576,6 +576,44 @@ int do_points(bvhgpu_tree* t, PointWalk walk, const T* points, size_t n, int mem
     });
 }
 
+// ---- multi-hit ray batches: bvhgpu_traverse_khits_* ----------------------------------------------------------------------------------
+// do_points' rules, order and staging for rays: one layout (rays | tmax | vals | shape), synchronous, and a refused call touches no buffer.
+template <typename T>
+int do_khits(bvhgpu_tree* t, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, int leaf, uint32_t k, uint32_t* out_shape, T* out_vals) {
+    using Ray = typename Traits<T>::Ray;
+    if (!t) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL tree");
+    bvhgpu_ctx* ctx = t->ctx;
+    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
+    if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from ray dtype");
+    if (!t->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    if (k == 0 || k > BVHGPU_KHITS_MAX_K) return fail(ctx, BVHGPU_INVALID_ARG, "k must be between 1 and BVHGPU_KHITS_MAX_K");
+    if (n && (!rays || !out_shape || !out_vals)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (leaf != BVHGPU_LEAF_BOX && leaf != BVHGPU_LEAF_TRIANGLE && leaf != BVHGPU_LEAF_SPHERE)
+        return fail(ctx, BVHGPU_INVALID_ARG, "leaf must be BVHGPU_LEAF_BOX, BVHGPU_LEAF_TRIANGLE or BVHGPU_LEAF_SPHERE");
+    if (leaf == BVHGPU_LEAF_TRIANGLE && !t->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "triangle hits need bvhgpu_tree_set_triangles first");
+    if (leaf == BVHGPU_LEAF_SPHERE && !t->has_spheres) return fail(ctx, BVHGPU_INVALID_ARG, "sphere hits need bvhgpu_tree_set_spheres first");
+    if (n >= 0xFFFFFFFFull || n * (size_t)k >= 0x100000000ull) return fail(ctx, BVHGPU_OVERFLOW, "too many results (rays x k) in one call");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        const Ray* rd = rays; const T* td = tmax; uint32_t* sd = out_shape; T* vd = out_vals;
+        const size_t w = leaf == BVHGPU_LEAF_TRIANGLE ? 3 : 2;
+        const size_t rb = n * sizeof(Ray), tb = tmax ? n * sizeof(T) : 0, vb = n * k * w * sizeof(T), sb = n * k * 4;
+        if (mem == BVHGPU_HOST) {
+            ctx->upload.reserve(rb + tb + vb + sb + 64);
+            char* base = ctx->upload.as<char>();
+            if (rb) BVH_HIP(hipMemcpyAsync(base, rays, rb, hipMemcpyHostToDevice, ctx->stream));
+            if (tb) BVH_HIP(hipMemcpyAsync(base + rb, tmax, tb, hipMemcpyHostToDevice, ctx->stream));
+            rd = reinterpret_cast<const Ray*>(base); td = tb ? reinterpret_cast<const T*>(base + rb) : nullptr;
+            vd = reinterpret_cast<T*>(base + rb + tb); sd = reinterpret_cast<uint32_t*>(base + rb + tb + vb);
+        }
+        khits_batch<T>(t, rd, n ? td : nullptr, n, leaf, k, sd, vd);
+        if (mem == BVHGPU_HOST) { copy_out(ctx, out_vals, vd, vb, BVHGPU_HOST); copy_out(ctx, out_shape, sd, sb, BVHGPU_HOST); }
+        else BVH_HIP(hipStreamSynchronize(ctx->stream));   // the rows are complete when the call returns, whichever stream reads them next
+        return (int)BVHGPU_OK;
+    });
+}
+
 // ---- host-resident batches (ABI 7): bvhgpu_traverse_host_* / bvhgpu_build_traverse_host_* -------------------------------------------
 // What GpuBvh::traverse_batch of the Rust shim costs a caller whose rays live in host memory and who wants the hit lists back there is a
 // PCIe problem, not a kernel problem: 1 M rays are 36 MB as Ray structs and 24 MB as origins + directions, the CSR offsets 4 MB.  The
@@ -1233,6 +1271,14 @@ int bvhgpu_knearest_tree_f32(bvhgpu_tree* t, const float* points, size_t n, int 
 int bvhgpu_knearest_tree_f64(bvhgpu_tree* t, const double* points, size_t n, int mem, int kind, uint32_t k, const double* max_dist,
                              uint32_t* out_shape, double* out_dist) {
     return do_points<double>(t, PointWalk::KNearestTree, points, n, mem, kind, k, max_dist, out_shape, out_dist);
+}
+int bvhgpu_traverse_khits_f32(bvhgpu_tree* t, const bvhgpu_ray_f32* rays, const float* tmax, size_t n_rays, int mem, int leaf, uint32_t k,
+                              uint32_t* out_shape, float* out_vals) {
+    return do_khits<float>(t, rays, tmax, n_rays, mem, leaf, k, out_shape, out_vals);
+}
+int bvhgpu_traverse_khits_f64(bvhgpu_tree* t, const bvhgpu_ray_f64* rays, const double* tmax, size_t n_rays, int mem, int leaf, uint32_t k,
+                              uint32_t* out_shape, double* out_vals) {
+    return do_khits<double>(t, rays, tmax, n_rays, mem, leaf, k, out_shape, out_vals);
 }
 int bvhgpu_ray_triangle_pairs_f32(bvhgpu_ctx* ctx, const bvhgpu_ray_f32* rays, const float* tris, size_t n, int mem, float* out) {
     return do_pairs<float>(ctx, rays, tris, n, mem, out);

@@ -346,6 +346,11 @@ void knearest_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uin
 template <typename T>
 void knearest_tree_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint32_t k, const T* max_dist_dev, uint32_t* out_shape_dev,
                          T* out_dist_dev);
+// khits.hip: the k nearest hits per ray (bvhgpu_traverse_khits_*); leaf: BVHGPU_LEAF_*; tmax_dev: NULL or n segment ends; out_shape: n x k,
+// out_vals: n x k x W (W = 3 for triangles, else 2); an empty hierarchy fills them with padding
+template <typename T>
+void khits_batch(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, int leaf, uint32_t k,
+                 uint32_t* out_shape_dev, T* out_vals_dev);
 // rays.hip
 template <typename T>
 void ray_triangle_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays_dev, const T* tris_dev, size_t n, T* out_dev);

@@ -545,6 +545,44 @@ int bvhgpu_traverse_sphere_f64(bvhgpu_tree *tree, const bvhgpu_ray_f64 *rays, co
                                bvhgpu_hits **hits);
 int bvhgpu_hits_fetch_sphere(bvhgpu_hits *hits, void *slice, uint32_t *shape, int mem);
 
+/* ---- multi-hit ray queries: the k nearest hits of every ray, in order — transparency and depth peeling, absorption through particles or
+ * splats, LiDAR multi-return, picking through a front surface, inside/outside parity — without fetching the whole CSR and reducing it on
+ * the host.  The ray counterpart of bvhgpu_knearest_*.
+ * Ray i has tmax[i] in the tree's dtype T.  A NULL tmax means +inf for every ray.  L_i is the list FlatBvh::traverse(&ray_i, shapes)
+ * returns, in its order.  That is the engine's CSR row.
+ * For s in L_i the leaf stage `leaf` gives a record of W scalars.  Its first scalar is the DISTANCE.
+ *     BVHGPU_LEAF_BOX       {enter, exit}       W = 2   Ray::intersection_slice_for_aabb on s's AABB as the tree holds it: the bits
+ *                                                       BVHGPU_TRAVERSE_T_SLICE returns.  Needs nothing.
+ *     BVHGPU_LEAF_TRIANGLE  {distance, u, v}    W = 3   Ray::intersects_triangle's Intersection: the bits BVHGPU_TRAVERSE_TRIANGLES returns.
+ *                                                       Needs bvhgpu_tree_set_triangles_*.
+ *     BVHGPU_LEAF_SPHERE    {distance, exit}    W = 2   the sphere leaf stage of bvhgpu_traverse_sphere_* above.  Needs bvhgpu_tree_set_spheres_*.
+ *  - Candidate.  s is a candidate iff distance < tmax[i], strict and in T.  A miss (+inf) is never a candidate.  A NaN, zero or negative
+ *    tmax admits nothing.
+ *  - Row i.  The candidates of L_i in a stable ascending sort by distance, cut to the first k.  Equal distances stay in the order of L_i.
+ *    That order is not shape-index order.
+ *  - Padding.  Slots beyond the number of candidates hold BVHGPU_NONE and {+inf, 0} / {+inf, 0, 0}, the existing no-candidate records.
+ *  - Incremental form, which the kernel runs: bvhgpu_knearest_*'s list with the strict < of T.  While the list is not full every candidate
+ *    enters.  A full list accepts d iff d < L[k-1] and drops L[k-1].  An accepted d goes in front of the first element e with d < e, else
+ *    to the end.  A candidate's distance is never NaN (enter is max(tmin, 0); the triangle and sphere stages return +inf or a value > eps),
+ *    so rows are always sorted.
+ *  - Limits.  1 <= k <= BVHGPU_KHITS_MAX_K, else BVHGPU_INVALID_ARG.
+ *  - Trees.  It holds for every tree the binary CSR walks accept: built here, refitted, an uploaded FlatBvh, scene-imported, trees with
+ *    empty child bounds, one shape, and no shapes (every slot is padding).
+ *  - No pruning.  The walk visits all of L_i, as BVHGPU_TRAVERSE_CLOSEST does.
+ * out_shape[i*k + j] and out_vals[(i*k + j)*W ..] are slot j of row i.  `rays`, `tmax` and both outputs live in `mem`.  The call is
+ * synchronous: the rows are complete when it returns.  Refused, touching no buffer: a NULL tree; a tree of another dtype
+ * (BVHGPU_DTYPE_MISMATCH); a tree that is not flattened (BVHGPU_NOT_FLATTENED); k out of range, a NULL pointer with n_rays > 0, a `mem`
+ * that is neither BVHGPU_HOST nor BVHGPU_DEVICE, an unknown `leaf`, triangles or spheres that were not set (BVHGPU_INVALID_ARG);
+ * n_rays >= 2^32-1 or n_rays * k >= 2^32 (BVHGPU_OVERFLOW). */
+#define BVHGPU_KHITS_MAX_K 64u /* the lists of a 64-lane workgroup live in LDS: 64 x 64 x (8 + 4) bytes = 48 KB in f64 */
+#define BVHGPU_LEAF_BOX 0
+#define BVHGPU_LEAF_TRIANGLE 1
+#define BVHGPU_LEAF_SPHERE 2
+int bvhgpu_traverse_khits_f32(bvhgpu_tree *tree, const bvhgpu_ray_f32 *rays, const float *tmax, size_t n_rays, int mem, int leaf, uint32_t k,
+                              uint32_t *out_shape /* n x k */, float *out_vals /* n x k x W */);
+int bvhgpu_traverse_khits_f64(bvhgpu_tree *tree, const bvhgpu_ray_f64 *rays, const double *tmax, size_t n_rays, int mem, int leaf, uint32_t k,
+                              uint32_t *out_shape /* n x k */, double *out_vals /* n x k x W */);
+
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */
 typedef struct { float build_ms, flatten_ms, traverse_kernel_ms, traverse_total_ms; } bvhgpu_timings;

@@ -99,6 +99,8 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
     unsafe fn knearest(t: *mut ffi::bvhgpu_tree, points: *const Self, n: usize, mem: c_int, kind: c_int, k: u32, out_shape: *mut u32, out_dist: *mut Self) -> c_int;
     #[allow(clippy::too_many_arguments)]
     unsafe fn knearest_tree(t: *mut ffi::bvhgpu_tree, points: *const Self, n: usize, mem: c_int, kind: c_int, k: u32, max_dist: *const Self, out_shape: *mut u32, out_dist: *mut Self) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn traverse_khits(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, leaf: c_int, k: u32, out_shape: *mut u32, out_vals: *mut Self) -> c_int;
 
     fn node_to_crate(raw: &Self::Node) -> BvhNode<Self, 3>;
     fn flat_to_crate(raw: &Self::Flat) -> FlatNode<Self, 3>;
@@ -108,7 +110,7 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
 
 macro_rules! impl_gpu_scalar {
     ($t:ty, $dtype:expr, $node:ident, $flat:ident, $ray:ident, $build_flat:ident, $rebuild_flat:ident, $refit:ident, $traverse:ident,
-     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $traverse_box:ident, $set_spheres:ident, $traverse_sphere:ident, $knearest:ident, $knearest_tree:ident,
+     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $traverse_box:ident, $set_spheres:ident, $traverse_sphere:ident, $knearest:ident, $knearest_tree:ident, $traverse_khits:ident,
      $flat_ctor:expr) => {
         impl GpuScalar for $t {
             type Node = ffi::$node;
@@ -163,6 +165,9 @@ macro_rules! impl_gpu_scalar {
             unsafe fn knearest_tree(t: *mut ffi::bvhgpu_tree, points: *const $t, n: usize, mem: c_int, kind: c_int, k: u32, max_dist: *const $t, out_shape: *mut u32, out_dist: *mut $t) -> c_int {
                 ffi::$knearest_tree(t, points, n, mem, kind, k, max_dist, out_shape, out_dist)
             }
+            unsafe fn traverse_khits(t: *mut ffi::bvhgpu_tree, rays: *const ffi::$ray, tmax: *const $t, n: usize, mem: c_int, leaf: c_int, k: u32, out_shape: *mut u32, out_vals: *mut $t) -> c_int {
+                ffi::$traverse_khits(t, rays, tmax, n, mem, leaf, k, out_shape, out_vals)
+            }
             fn node_to_crate(r: &ffi::$node) -> BvhNode<$t, 3> {
                 if r.shape != ffi::BVHGPU_NONE {
                     BvhNode::Leaf { parent_index: r.parent as usize, shape_index: r.shape as usize }
@@ -201,11 +206,11 @@ macro_rules! impl_gpu_scalar {
 }
 impl_gpu_scalar!(f32, ffi::BVHGPU_F32, bvhgpu_node_f32, bvhgpu_flat_f32, bvhgpu_ray_f32, bvhgpu_build_flat_f32, bvhgpu_rebuild_flat_f32,
                  bvhgpu_refit_f32, bvhgpu_traverse_f32, bvhgpu_tree_set_triangles_f32, bvhgpu_tree_from_flat_f32,
-                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_traverse_box_f32, bvhgpu_tree_set_spheres_f32, bvhgpu_traverse_sphere_f32, bvhgpu_knearest_f32, bvhgpu_knearest_tree_f32,
+                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_traverse_box_f32, bvhgpu_tree_set_spheres_f32, bvhgpu_traverse_sphere_f32, bvhgpu_knearest_f32, bvhgpu_knearest_tree_f32, bvhgpu_traverse_khits_f32,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f32 { min, max, entry, exit, shape });
 impl_gpu_scalar!(f64, ffi::BVHGPU_F64, bvhgpu_node_f64, bvhgpu_flat_f64, bvhgpu_ray_f64, bvhgpu_build_flat_f64, bvhgpu_rebuild_flat_f64,
                  bvhgpu_refit_f64, bvhgpu_traverse_f64, bvhgpu_tree_set_triangles_f64, bvhgpu_tree_from_flat_f64,
-                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_traverse_box_f64, bvhgpu_tree_set_spheres_f64, bvhgpu_traverse_sphere_f64, bvhgpu_knearest_f64, bvhgpu_knearest_tree_f64,
+                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_traverse_box_f64, bvhgpu_tree_set_spheres_f64, bvhgpu_traverse_sphere_f64, bvhgpu_knearest_f64, bvhgpu_knearest_tree_f64, bvhgpu_traverse_khits_f64,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f64 { min, max, entry, exit, shape, _pad: 0 });
 
 fn aabb_to_6<T: GpuScalar>(b: &Aabb<T, 3>) -> [T; 6] {
@@ -569,6 +574,29 @@ impl<T: GpuScalar> GpuBvh<T> {
     /// `first_sphere_hits` reduced to one flag per ray: does ray i hit any sphere before `tmax[i]`
     pub fn sphere_occluded(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>) -> Vec<bool> {
         self.first_sphere_hits(rays, tmax).iter().map(|h| h.shape != ffi::BVHGPU_NONE).collect()
+    }
+
+    /// The `k` nearest hits of every ray (`bvhgpu_traverse_khits_*`): the members of `FlatBvh::traverse`'s list whose leaf-stage distance is
+    /// `< tmax[i]` (strict; `tmax: None` = +inf for every ray), in a stable ascending sort by distance — equal distances in list order — cut
+    /// to the first `k`.  `leaf`: `ffi::BVHGPU_LEAF_BOX` (`{enter, exit}` on the shape's own AABB), `ffi::BVHGPU_LEAF_TRIANGLE`
+    /// (`Intersection{distance, u, v}`; needs `set_triangles`) or `ffi::BVHGPU_LEAF_SPHERE` (`{distance, exit}`; needs `set_spheres`).
+    /// Returns row-major `rays.len() x k` shape indices and `rays.len() x k x W` record scalars (W = 3 for triangles, else 2); slots beyond
+    /// the number of candidates hold `u32::MAX` and `{+inf, 0[, 0]}`.  `1 <= k <= ffi::BVHGPU_KHITS_MAX_K`.
+    pub fn traverse_khits(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>, leaf: c_int, k: usize) -> (Vec<u32>, Vec<T>) {
+        if let Some(tm) = tmax {
+            assert_eq!(tm.len(), rays.len(), "one tmax per ray");
+        }
+        let k32 = u32::try_from(k).unwrap_or(u32::MAX);   // (out of range: the engine answers BVHGPU_INVALID_ARG and `check` panics with its message)
+        let slots = if (1..=ffi::BVHGPU_KHITS_MAX_K).contains(&k32) { rays.len() * k } else { 0 };
+        let w = if leaf == ffi::BVHGPU_LEAF_TRIANGLE { 3 } else { 2 };
+        let r: Vec<T::RayC> = rays.iter().map(T::ray_to_ffi).collect();
+        let mut shape = vec![0u32; slots];
+        let mut vals = vec![T::default(); slots * w];
+        unsafe {
+            check(self.ctx, T::traverse_khits(self.tree, r.as_ptr(), tmax.map_or(core::ptr::null(), |t| t.as_ptr()), r.len(), ffi::BVHGPU_HOST,
+                                              leaf, k32, shape.as_mut_ptr(), vals.as_mut_ptr()));
+        }
+        (shape, vals)
     }
 
     /// The `k` nearest shapes of every point (`bvhgpu_knearest_*`): the loop of `FlatBvh::nearest_to` (src/flat_bvh.rs:524-558) with a list of

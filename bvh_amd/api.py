@@ -500,6 +500,29 @@ class _Hits:
         check(lib.bvhgpu_hits_fetch(self.h, ptr(offsets), ptr(indices), None, HOST), self.ctx._h)
         return offsets, indices
 
+    def fetch_allhits(self, n_rays: int, leaf: str = "box", dtype=np.float32, device=None):
+        """all-hits batches (bvhgpu_hits_fetch_allhits): (offsets[n+1], shape[total], vals[total, W]) of the completed batch.  device None:
+        copied to the host, offsets and shape as uint32.  device: torch tensors there, filled by device-to-device copies — shape as
+        torch.int32, offsets widened to torch.int64 on the device."""
+        lib = _lib.load()
+        total = C.c_uint64()
+        check(lib.bvhgpu_hits_info(self.h, None, C.byref(total), None), self.ctx._h)
+        total, w = int(total.value), _lib.LEAF_WIDTH[_lib.LEAF_KINDS[leaf]]
+        if device is not None:
+            import torch
+            off32 = torch.empty(n_rays + 1, dtype=torch.int32, device=device)
+            shape = torch.empty(total, dtype=torch.int32, device=device)
+            vals = torch.empty((total, w), dtype=torch.float32 if np.dtype(dtype) == np.float32 else torch.float64, device=device)
+            torch.cuda.current_stream(device).synchronize()
+            check(lib.bvhgpu_hits_fetch_allhits(self.h, ptr(off32.data_ptr()), ptr(shape.data_ptr()) if total else None,
+                                                ptr(vals.data_ptr()) if total else None, DEVICE), self.ctx._h)
+            return off32.to(torch.int64) & 0xFFFFFFFF, shape, vals
+        offsets = np.zeros(n_rays + 1, dtype=np.uint32)
+        shape = np.zeros(total, dtype=np.uint32)
+        vals = np.zeros((total, w), dtype=dtype)
+        check(lib.bvhgpu_hits_fetch_allhits(self.h, ptr(offsets), ptr(shape), ptr(vals), HOST), self.ctx._h)
+        return offsets, shape, vals
+
     def close(self):
         if getattr(self, "h", None) and not _closing:
             _lib.load().bvhgpu_hits_destroy(self.h)
@@ -793,6 +816,28 @@ class _TreeBase:
         vals = np.zeros((rays.n, rows, w), dtype=ft)
         check(fn(self._t, rays._ptr(), tp, rays.n, HOST, kind, k & 0xFFFFFFFF, ptr(shape), ptr(vals)), self.ctx._h)
         return vals, shape
+
+    def allhits_batch(self, rays: RayBatch, leaf: str = "box", tmax=None, sort: bool = True):
+        """bvhgpu_traverse_allhits_*: every hit of every ray, as a CSR.  Row i is ALL candidates of FlatBvh::traverse's list (flat_bvh.rs:396-431)
+        — the members whose leaf-stage distance is < tmax[i], strict — in a stable ascending sort by distance (equal distances in list
+        order); sort=False (BVHGPU_ALLHITS_LIST_ORDER) leaves them in list order.  leaf and tmax as for khits_batch.
+        returns (offsets[n+1], shape[total], vals[total, W]), W = 3 for triangles, else 2; no padding.  The first min(k, len) entries of a
+        sorted row are khits_batch's row.  HOST rays: numpy out, offsets and shape as uint32.  Rays in HBM: torch tensors on the same
+        device, shape as torch.int32, offsets as torch.int64."""
+        if rays.sfx != self.sfx:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
+        if leaf not in _lib.LEAF_KINDS:
+            raise BvhGpuError(_lib.INVALID_ARG, f"leaf must be one of {sorted(_lib.LEAF_KINDS)}")
+        keep, tp = self._tmax_arg(rays, tmax)   # (keep: the array tp points into stays alive over the call)
+        fn = getattr(_lib.load(), f"bvhgpu_traverse_allhits_{self.sfx}")
+        dev = None
+        if rays.mem == DEVICE:
+            import torch
+            dev = rays.device.device
+            torch.cuda.current_stream(dev).synchronize()   # the engine works on its own stream: the rays must be there
+        check(fn(self._t, rays._ptr(), tp, rays.n, rays.mem, _lib.LEAF_KINDS[leaf], 0 if sort else _lib.ALLHITS_LIST_ORDER, C.byref(self._hits.h)),
+              self.ctx._h)
+        return self._hits.fetch_allhits(rays.n, leaf, np.float32 if self.sfx == "f32" else np.float64, dev)
 
     # ---- point query ---------------------------------------------------------------------
     def nearest_batch(self, points, triangles: bool = False):
@@ -1220,6 +1265,10 @@ class Bvh(_TreeBase):
     def khits_batch(self, rays: RayBatch, k: int, leaf: str = "box", tmax=None):
         self.flatten_in_place()
         return super().khits_batch(rays, k, leaf, tmax)
+
+    def allhits_batch(self, rays: RayBatch, leaf: str = "box", tmax=None, sort: bool = True):
+        self.flatten_in_place()
+        return super().allhits_batch(rays, leaf, tmax, sort)
 
 
 class _FlatView(FlatBvh):

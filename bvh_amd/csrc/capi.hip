@@ -286,7 +286,7 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
     }
     if ((flags & BVHGPU_TRAVERSE_TRIANGLES) && (flags & BVHGPU_TRAVERSE_CLOSEST))
         return fail(ctx, BVHGPU_INVALID_ARG, "TRIANGLES and CLOSEST are alternatives");
-    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT | TRAVERSE_SPHERE_HIT);   // (internal: only bvhgpu_traverse_any_* / _box_* / _sphere_* set them)
+    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT | TRAVERSE_SPHERE_HIT | TRAVERSE_ALLHITS);   // (internal: only bvhgpu_traverse_any_* / _box_* / _sphere_* / _allhits_* set them)
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
@@ -610,6 +610,39 @@ int do_khits(bvhgpu_tree* t, const typename Traits<T>::Ray* rays, const T* tmax,
         khits_batch<T>(t, rd, n ? td : nullptr, n, leaf, k, sd, vd);
         if (mem == BVHGPU_HOST) { copy_out(ctx, out_vals, vd, vb, BVHGPU_HOST); copy_out(ctx, out_shape, sd, sb, BVHGPU_HOST); }
         else BVH_HIP(hipStreamSynchronize(ctx->stream));   // the rows are complete when the call returns, whichever stream reads them next
+        return (int)BVHGPU_OK;
+    });
+}
+
+// ---- all-hits ray batches: bvhgpu_traverse_allhits_* ----------------------------------------------------------------------------------
+// do_khits' rules and order; the result goes to a result object (allhits.hip), whose buffers a later batch of any kind reuses.  A refused
+// call touches no buffer and leaves *hits as it was.
+template <typename T>
+int do_allhits(bvhgpu_tree* t, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, int leaf, unsigned flags, bvhgpu_hits** hits) {
+    using Ray = typename Traits<T>::Ray;
+    if (!t) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL tree");
+    bvhgpu_ctx* ctx = t->ctx;
+    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
+    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
+    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
+    if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from ray dtype");
+    if (!t->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    if (n && !rays) return fail(ctx, BVHGPU_INVALID_ARG, "rays is NULL");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (leaf != BVHGPU_LEAF_BOX && leaf != BVHGPU_LEAF_TRIANGLE && leaf != BVHGPU_LEAF_SPHERE)
+        return fail(ctx, BVHGPU_INVALID_ARG, "leaf must be BVHGPU_LEAF_BOX, BVHGPU_LEAF_TRIANGLE or BVHGPU_LEAF_SPHERE");
+    if (flags & ~BVHGPU_ALLHITS_LIST_ORDER) return fail(ctx, BVHGPU_INVALID_ARG, "all-hits flags: 0 or BVHGPU_ALLHITS_LIST_ORDER");
+    if (leaf == BVHGPU_LEAF_TRIANGLE && !t->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "triangle hits need bvhgpu_tree_set_triangles first");
+    if (leaf == BVHGPU_LEAF_SPHERE && !t->has_spheres) return fail(ctx, BVHGPU_INVALID_ARG, "sphere hits need bvhgpu_tree_set_spheres first");
+    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 rays in one batch");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        bvhgpu_hits* h = batch_hits(hits);
+        const auto* dev = static_cast<const Ray*>(to_device(ctx, rays, n * sizeof(Ray), mem, ctx->upload));
+        stage_tmax<T>(ctx, h, tmax, n, mem);   // (a HOST tmax is staged as the box and sphere batches stage it)
+        const T* td = n ? static_cast<const T*>(h->pend_tmax) : nullptr;
+        h->pend_tmax = nullptr;                // (nothing replays this batch)
+        allhits_batch<T>(t, dev, td, n, leaf, flags, h);
         return (int)BVHGPU_OK;
     });
 }
@@ -1280,6 +1313,14 @@ int bvhgpu_traverse_khits_f64(bvhgpu_tree* t, const bvhgpu_ray_f64* rays, const 
                               uint32_t* out_shape, double* out_vals) {
     return do_khits<double>(t, rays, tmax, n_rays, mem, leaf, k, out_shape, out_vals);
 }
+int bvhgpu_traverse_allhits_f32(bvhgpu_tree* t, const bvhgpu_ray_f32* rays, const float* tmax, size_t n_rays, int mem, int leaf, unsigned flags,
+                                bvhgpu_hits** hits) {
+    return do_allhits<float>(t, rays, tmax, n_rays, mem, leaf, flags, hits);
+}
+int bvhgpu_traverse_allhits_f64(bvhgpu_tree* t, const bvhgpu_ray_f64* rays, const double* tmax, size_t n_rays, int mem, int leaf, unsigned flags,
+                                bvhgpu_hits** hits) {
+    return do_allhits<double>(t, rays, tmax, n_rays, mem, leaf, flags, hits);
+}
 int bvhgpu_ray_triangle_pairs_f32(bvhgpu_ctx* ctx, const bvhgpu_ray_f32* rays, const float* tris, size_t n, int mem, float* out) {
     return do_pairs<float>(ctx, rays, tris, n, mem, out);
 }
@@ -1410,6 +1451,7 @@ int bvhgpu_hits_fetch_triangles(bvhgpu_hits* h, void* isect, int mem) {
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "a sphere-hit batch has no triangle values: use bvhgpu_hits_fetch_sphere");
+    if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
     if (!(h->flags & BVHGPU_TRAVERSE_TRIANGLES)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_TRIANGLES");
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -1424,6 +1466,7 @@ static int fetch_per_ray(bvhgpu_hits* h, void* values, uint32_t* shape, int mem,
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if ((h->flags & TRAVERSE_SPHERE_HIT) && kind_bit != TRAVERSE_SPHERE_HIT)
         return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
+    if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
     if (!(h->flags & kind_bit)) return fail(ctx, BVHGPU_INVALID_ARG, other_kind_msg);
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -1472,6 +1515,7 @@ int bvhgpu_hits_fetch(bvhgpu_hits* h, uint32_t* offsets, uint32_t* indices, void
     if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "an all-hits batch has a CSR of its own: use bvhgpu_hits_fetch_allhits");
     if (tslice && !(h->flags & BVHGPU_TRAVERSE_T_SLICE)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_T_SLICE");
     if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR: use bvhgpu_hits_fetch_closest");
     if (h->flags & TRAVERSE_ANY_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR: use bvhgpu_hits_fetch_any");
@@ -1486,9 +1530,27 @@ int bvhgpu_hits_fetch(bvhgpu_hits* h, uint32_t* offsets, uint32_t* indices, void
     });
 }
 
+// the CSR of an all-hits batch: offsets (n_rays + 1 u32), the shapes (total u32), the records (total x W T); each may be NULL
+int bvhgpu_hits_fetch_allhits(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape, void* vals, int mem) {
+    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = h->ctx;
+    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (!(h->flags & TRAVERSE_ALLHITS)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_traverse_allhits_* batch");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        const size_t w = h->ah_leaf == BVHGPU_LEAF_TRIANGLE ? 3 : 2;
+        if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
+        if (shape && h->total) copy_out(ctx, shape, h->indices.p, h->total * 4, mem);
+        if (vals && h->total) copy_out(ctx, vals, h->ah_vals.p, h->total * w * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
+        return (int)BVHGPU_OK;
+    });
+}
+
 int bvhgpu_hits_device(const bvhgpu_hits* h, const uint32_t** offsets, const uint32_t** indices, const void** tslice) {
     if (!h) return BVHGPU_INVALID_ARG;
     if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_ALLHITS) return fail(h->ctx, BVHGPU_INVALID_ARG, "an all-hits batch has a CSR of its own: use bvhgpu_hits_fetch_allhits");
     if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(h->ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR");
     if (h->flags & TRAVERSE_ANY_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR");
     if (h->flags & TRAVERSE_BOX_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "a box-hit batch produces no CSR");

@@ -46,6 +46,8 @@ constexpr unsigned TRAVERSE_ANY_HIT = 1u << 31;
 constexpr unsigned TRAVERSE_BOX_HIT = 1u << 30;
 // result objects of bvhgpu_traverse_sphere_* (MODE_SPHERE_CLOSEST, or MODE_SPHERE_FIRST with BVHGPU_TRAVERSE_FIRST): marked the same way
 constexpr unsigned TRAVERSE_SPHERE_HIT = 1u << 29;
+// result objects of bvhgpu_traverse_allhits_* (allhits.hip): marked the same way; the only bit such a result carries
+constexpr unsigned TRAVERSE_ALLHITS = 1u << 28;
 
 }  // namespace bvhgpu
 
@@ -280,6 +282,11 @@ struct bvhgpu_hits {
     bvhgpu::DevBuf any_key;              // n_rays u32: any-hit batches walked as items (walk.hpp WalkOut::any_key), all-ones between batches
     bool akey_clean = false;
     bvhgpu::DevBuf any_part;             // per workgroup of k_any_resolve: its occluded rays (k_any_publish adds them up)
+    // all-hits batches (bvhgpu_traverse_allhits_*, allhits.hip): the CSR is `offsets` / `indices` (the shapes) / `ah_vals` (total x W T)
+    int ah_leaf = 0;                     // BVHGPU_LEAF_* of the batch (W = 3 for triangles, else 2)
+    bvhgpu::DevBuf ah_vals;
+    bvhgpu::DevBuf ah_counts, ah_sums;   // n_rays u32 candidate counts; {total, long rows, rows beyond LDS} + a 64-bit sum per scan block
+    bvhgpu::DevBuf ah_work, ah_pos;      // the long rows of a sorted batch (ray ids); list positions of the rows sorted in global memory
     uint32_t replays = 0;               // times bvhgpu_hits_wait had to enqueue the asynchronous batch again
     int deferred_rc = 0;                // status of a completion that ran on behalf of another call (rebuild / destroy of the tree)
     std::string deferred_err;
@@ -351,6 +358,11 @@ void knearest_tree_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind
 template <typename T>
 void khits_batch(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, int leaf, uint32_t k,
                  uint32_t* out_shape_dev, T* out_vals_dev);
+// allhits.hip: every hit per ray as a CSR (bvhgpu_traverse_allhits_*); leaf: BVHGPU_LEAF_*; flags: BVHGPU_ALLHITS_*; tmax_dev: NULL or n segment
+// ends.  Synchronous: h->offsets / h->indices / h->ah_vals and h->total are complete on return.  Throws Fail::Overflow when the batch has
+// more than 2^32-1 candidates (the result object then holds an empty all-hits result).
+template <typename T>
+void allhits_batch(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, int leaf, unsigned flags, bvhgpu_hits* h);
 // rays.hip
 template <typename T>
 void ray_triangle_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays_dev, const T* tris_dev, size_t n, T* out_dev);

@@ -586,6 +586,47 @@ int bvhgpu_traverse_khits_f32(bvhgpu_tree *tree, const bvhgpu_ray_f32 *rays, con
 int bvhgpu_traverse_khits_f64(bvhgpu_tree *tree, const bvhgpu_ray_f64 *rays, const double *tmax, size_t n_rays, int mem, int leaf, uint32_t k,
                               uint32_t *out_shape /* n x k */, double *out_vals /* n x k x W */);
 
+/* ---- all-hits ray queries: EVERY hit of every ray, in order, as a CSR — absorption or transmittance through all particles along a ray,
+ * order-independent transparency with an unknown layer count, inside/outside parity, LiDAR full-waveform returns, "exactly the triangles
+ * this segment crosses" — without fetching the candidate CSR of bvhgpu_traverse_* and filtering and sorting it on the host.  The unbounded
+ * form of bvhgpu_traverse_khits_* above.
+ * Ray i has tmax[i] in the tree's dtype T.  A NULL tmax means +inf for every ray.  L_i is the list FlatBvh::traverse(&ray_i, shapes)
+ * returns, in its order.  That is the engine's CSR row.
+ * For s in L_i the leaf stage `leaf` gives a record of W scalars whose first scalar is the DISTANCE.  The leaf stage is exactly that of
+ * bvhgpu_traverse_khits_*: BVHGPU_LEAF_BOX, BVHGPU_LEAF_TRIANGLE or BVHGPU_LEAF_SPHERE, the same device functions on the same operands,
+ * so the bits are the same.
+ *  - Candidate.  s is a candidate iff distance < tmax[i], strict and in T.  A miss (+inf) is never a candidate.  A NaN, zero or negative
+ *    tmax admits nothing.
+ *  - Row i, default.  All candidates of L_i in a stable ascending sort by distance.  Equal distances stay in the order of L_i.  A
+ *    candidate's distance is never NaN, so the order is the total order on (distance, position in L_i): it is unique whatever algorithm
+ *    produces it.
+ *  - Row i with BVHGPU_ALLHITS_LIST_ORDER.  The candidates in the order of L_i, with no sort pass.
+ *  - Output.  offsets[n_rays + 1] holds the exclusive prefix sums of the row lengths, as u32; offsets[n_rays] == total.  shape[total] holds
+ *    the shape indices, as u32.  vals[total x W] holds the records.  There is no padding anywhere.
+ *  - Consequence.  For every k, the first min(k, len) entries of a default row are row i of bvhgpu_traverse_khits_* in front of its padding.
+ *  - Trees.  Every tree bvhgpu_traverse_khits_* accepts: built here, refitted, an uploaded FlatBvh, scene-imported, trees with empty
+ *    child bounds, with one shape, and with no shapes (all offsets 0).
+ *  - No pruning.  The walk visits all of L_i.
+ *  - Limits.  n_rays < 2^32-1, else BVHGPU_OVERFLOW.  total <= 2^32-1, else BVHGPU_OVERFLOW: the total is summed in 64 bits and the
+ *    status is returned after the count pass, before anything is sized by it; the result object then holds an empty all-hits result.
+ * `rays` and `tmax` live in `mem`.  The call is synchronous: the result object is complete on return.  *hits may be NULL or an earlier
+ * result object of any kind, whose buffers are then reused.  bvhgpu_hits_info gives n_rays and total, the number of candidates;
+ * stats.hits == total and the other stats are 0.  bvhgpu_hits_wait returns BVHGPU_OK, bvhgpu_hits_walk_info gives 0,
+ * bvhgpu_hits_walk_kernel names the fill kernel.  _fetch / _fetch_triangles / _fetch_closest / _fetch_any / _fetch_box / _fetch_sphere /
+ * _device return BVHGPU_INVALID_ARG on such a result, and bvhgpu_hits_fetch_allhits on any other.
+ * Refused, touching no buffer and leaving *hits as it was, in this order: a NULL tree or a NULL `hits`; what the settle of the tree's
+ * asynchronous build returns; a result object that still holds an asynchronous batch; a tree of another dtype (BVHGPU_DTYPE_MISMATCH);
+ * a tree that is not flattened (BVHGPU_NOT_FLATTENED); a NULL `rays` with n_rays > 0, a `mem` that is neither BVHGPU_HOST nor
+ * BVHGPU_DEVICE, an unknown `leaf`, a flag bit other than BVHGPU_ALLHITS_LIST_ORDER, triangles or spheres that were not set
+ * (BVHGPU_INVALID_ARG); n_rays >= 2^32-1 (BVHGPU_OVERFLOW).
+ * bvhgpu_hits_fetch_allhits: offsets (n_rays + 1 u32), shape (total u32) and vals (total x W T) copied to `mem`; each may be NULL. */
+#define BVHGPU_ALLHITS_LIST_ORDER 1u /* rows in the order of FlatBvh::traverse's list instead of ascending distance */
+int bvhgpu_traverse_allhits_f32(bvhgpu_tree *tree, const bvhgpu_ray_f32 *rays, const float *tmax, size_t n_rays, int mem, int leaf, unsigned flags,
+                                bvhgpu_hits **hits);
+int bvhgpu_traverse_allhits_f64(bvhgpu_tree *tree, const bvhgpu_ray_f64 *rays, const double *tmax, size_t n_rays, int mem, int leaf, unsigned flags,
+                                bvhgpu_hits **hits);
+int bvhgpu_hits_fetch_allhits(bvhgpu_hits *hits, uint32_t *offsets, uint32_t *shape, void *vals, int mem);
+
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */
 typedef struct { float build_ms, flatten_ms, traverse_kernel_ms, traverse_total_ms; } bvhgpu_timings;

@@ -7,6 +7,7 @@ pub const BVHGPU_ABI_VERSION: c_int = 7;
 pub const BVHGPU_NONE: u32 = u32::MAX; // flat_bvh.rs:51-53
 pub const BVHGPU_KNN_MAX_K: u32 = 64; // largest k of bvhgpu_knearest_*
 pub const BVHGPU_KHITS_MAX_K: u32 = 64; // largest k of bvhgpu_traverse_khits_*
+pub const BVHGPU_ALLHITS_LIST_ORDER: c_uint = 1; // bvhgpu_traverse_allhits_*: rows in list order, no sort pass
 pub const BVHGPU_LEAF_BOX: c_int = 0; // leaf stage of bvhgpu_traverse_khits_*: {enter, exit} on the shape's own AABB
 pub const BVHGPU_LEAF_TRIANGLE: c_int = 1; // ... Intersection{distance, u, v} (needs the triangles)
 pub const BVHGPU_LEAF_SPHERE: c_int = 2; // ... {distance, exit} (needs the spheres)
@@ -192,6 +193,10 @@ extern "C" {
     // the k nearest hits per ray (out_shape: n x k, out_vals: n x k x W; padding = BVHGPU_NONE / {+inf, 0[, 0]}; 1 <= k <= BVHGPU_KHITS_MAX_K)
     pub fn bvhgpu_traverse_khits_f32(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, leaf: c_int, k: u32, out_shape: *mut u32, out_vals: *mut f32) -> c_int;
     pub fn bvhgpu_traverse_khits_f64(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, leaf: c_int, k: u32, out_shape: *mut u32, out_vals: *mut f64) -> c_int;
+    // every hit per ray as a CSR (offsets: n + 1, shape: total, vals: total x W; no padding; rows in ascending distance, or in list order with BVHGPU_ALLHITS_LIST_ORDER)
+    pub fn bvhgpu_traverse_allhits_f32(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, leaf: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_traverse_allhits_f64(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, leaf: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_hits_fetch_allhits(h: *mut bvhgpu_hits, offsets: *mut u32, shape: *mut u32, vals: *mut c_void, mem: c_int) -> c_int;
     pub fn bvhgpu_tree_set_spheres_f32(t: *mut bvhgpu_tree, spheres: *const f32, n: usize, mem: c_int) -> c_int;
     pub fn bvhgpu_tree_set_spheres_f64(t: *mut bvhgpu_tree, spheres: *const f64, n: usize, mem: c_int) -> c_int;
     pub fn bvhgpu_traverse_sphere_f32(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;

@@ -101,6 +101,8 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
     unsafe fn knearest_tree(t: *mut ffi::bvhgpu_tree, points: *const Self, n: usize, mem: c_int, kind: c_int, k: u32, max_dist: *const Self, out_shape: *mut u32, out_dist: *mut Self) -> c_int;
     #[allow(clippy::too_many_arguments)]
     unsafe fn traverse_khits(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, leaf: c_int, k: u32, out_shape: *mut u32, out_vals: *mut Self) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn traverse_allhits(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, leaf: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
 
     fn node_to_crate(raw: &Self::Node) -> BvhNode<Self, 3>;
     fn flat_to_crate(raw: &Self::Flat) -> FlatNode<Self, 3>;
@@ -110,7 +112,7 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
 
 macro_rules! impl_gpu_scalar {
     ($t:ty, $dtype:expr, $node:ident, $flat:ident, $ray:ident, $build_flat:ident, $rebuild_flat:ident, $refit:ident, $traverse:ident,
-     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $traverse_box:ident, $set_spheres:ident, $traverse_sphere:ident, $knearest:ident, $knearest_tree:ident, $traverse_khits:ident,
+     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $traverse_box:ident, $set_spheres:ident, $traverse_sphere:ident, $knearest:ident, $knearest_tree:ident, $traverse_khits:ident, $traverse_allhits:ident,
      $flat_ctor:expr) => {
         impl GpuScalar for $t {
             type Node = ffi::$node;
@@ -168,6 +170,9 @@ macro_rules! impl_gpu_scalar {
             unsafe fn traverse_khits(t: *mut ffi::bvhgpu_tree, rays: *const ffi::$ray, tmax: *const $t, n: usize, mem: c_int, leaf: c_int, k: u32, out_shape: *mut u32, out_vals: *mut $t) -> c_int {
                 ffi::$traverse_khits(t, rays, tmax, n, mem, leaf, k, out_shape, out_vals)
             }
+            unsafe fn traverse_allhits(t: *mut ffi::bvhgpu_tree, rays: *const ffi::$ray, tmax: *const $t, n: usize, mem: c_int, leaf: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int {
+                ffi::$traverse_allhits(t, rays, tmax, n, mem, leaf, flags, hits)
+            }
             fn node_to_crate(r: &ffi::$node) -> BvhNode<$t, 3> {
                 if r.shape != ffi::BVHGPU_NONE {
                     BvhNode::Leaf { parent_index: r.parent as usize, shape_index: r.shape as usize }
@@ -206,11 +211,11 @@ macro_rules! impl_gpu_scalar {
 }
 impl_gpu_scalar!(f32, ffi::BVHGPU_F32, bvhgpu_node_f32, bvhgpu_flat_f32, bvhgpu_ray_f32, bvhgpu_build_flat_f32, bvhgpu_rebuild_flat_f32,
                  bvhgpu_refit_f32, bvhgpu_traverse_f32, bvhgpu_tree_set_triangles_f32, bvhgpu_tree_from_flat_f32,
-                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_traverse_box_f32, bvhgpu_tree_set_spheres_f32, bvhgpu_traverse_sphere_f32, bvhgpu_knearest_f32, bvhgpu_knearest_tree_f32, bvhgpu_traverse_khits_f32,
+                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_traverse_box_f32, bvhgpu_tree_set_spheres_f32, bvhgpu_traverse_sphere_f32, bvhgpu_knearest_f32, bvhgpu_knearest_tree_f32, bvhgpu_traverse_khits_f32, bvhgpu_traverse_allhits_f32,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f32 { min, max, entry, exit, shape });
 impl_gpu_scalar!(f64, ffi::BVHGPU_F64, bvhgpu_node_f64, bvhgpu_flat_f64, bvhgpu_ray_f64, bvhgpu_build_flat_f64, bvhgpu_rebuild_flat_f64,
                  bvhgpu_refit_f64, bvhgpu_traverse_f64, bvhgpu_tree_set_triangles_f64, bvhgpu_tree_from_flat_f64,
-                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_traverse_box_f64, bvhgpu_tree_set_spheres_f64, bvhgpu_traverse_sphere_f64, bvhgpu_knearest_f64, bvhgpu_knearest_tree_f64, bvhgpu_traverse_khits_f64,
+                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_traverse_box_f64, bvhgpu_tree_set_spheres_f64, bvhgpu_traverse_sphere_f64, bvhgpu_knearest_f64, bvhgpu_knearest_tree_f64, bvhgpu_traverse_khits_f64, bvhgpu_traverse_allhits_f64,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f64 { min, max, entry, exit, shape, _pad: 0 });
 
 fn aabb_to_6<T: GpuScalar>(b: &Aabb<T, 3>) -> [T; 6] {
@@ -597,6 +602,34 @@ impl<T: GpuScalar> GpuBvh<T> {
                                               leaf, k32, shape.as_mut_ptr(), vals.as_mut_ptr()));
         }
         (shape, vals)
+    }
+
+    /// EVERY hit of every ray, as a CSR (`bvhgpu_traverse_allhits_*`): row i is all members of `FlatBvh::traverse`'s list whose leaf-stage
+    /// distance is `< tmax[i]` (strict; `tmax: None` = +inf for every ray), in a stable ascending sort by distance — equal distances in list
+    /// order — or, with `sort: false` (`ffi::BVHGPU_ALLHITS_LIST_ORDER`), in list order.  `leaf` as for `traverse_khits`.  Returns
+    /// `(offsets, shape, vals)`: `rays.len() + 1` exclusive prefix sums of the row lengths, `total` shape indices and `total x W` record
+    /// scalars (W = 3 for triangles, else 2), with no padding.  The first `min(k, len)` entries of a sorted row are `traverse_khits`' row.
+    pub fn traverse_allhits(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>, leaf: c_int, sort: bool) -> (Vec<u32>, Vec<u32>, Vec<T>) {
+        if let Some(tm) = tmax {
+            assert_eq!(tm.len(), rays.len(), "one tmax per ray");
+        }
+        let w = if leaf == ffi::BVHGPU_LEAF_TRIANGLE { 3 } else { 2 };
+        let r: Vec<T::RayC> = rays.iter().map(T::ray_to_ffi).collect();
+        let mut hits = core::ptr::null_mut();
+        let flags = if sort { 0 } else { ffi::BVHGPU_ALLHITS_LIST_ORDER };
+        let mut offsets = vec![0u32; rays.len() + 1];
+        let (mut shape, mut vals) = (Vec::new(), Vec::new());
+        unsafe {
+            check(self.ctx, T::traverse_allhits(self.tree, r.as_ptr(), tmax.map_or(core::ptr::null(), |t| t.as_ptr()), r.len(), ffi::BVHGPU_HOST,
+                                                leaf, flags, &mut hits));
+            let mut total = 0u64;
+            check(self.ctx, ffi::bvhgpu_hits_info(hits, core::ptr::null_mut(), &mut total, core::ptr::null_mut()));
+            shape.resize(total as usize, 0u32);
+            vals.resize(total as usize * w, T::default());
+            check(self.ctx, ffi::bvhgpu_hits_fetch_allhits(hits, offsets.as_mut_ptr(), shape.as_mut_ptr(), vals.as_mut_ptr() as *mut c_void, ffi::BVHGPU_HOST));
+            ffi::bvhgpu_hits_destroy(hits);
+        }
+        (offsets, shape, vals)
     }
 
     /// The `k` nearest shapes of every point (`bvhgpu_knearest_*`): the loop of `FlatBvh::nearest_to` (src/flat_bvh.rs:524-558) with a list of

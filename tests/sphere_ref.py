@@ -46,13 +46,14 @@ def list_hits(off, idx, rays, spheres):
                       np.ascontiguousarray(spheres[idx.astype(np.int64)]))
 
 
-def sphere_match(off, idx, rays, spheres, tmax, first):
+def sphere_match(off, idx, rays, spheres, tmax, first, hits=None):
     """the definition on a CSR (offsets, indices of FlatBvh::traverse's lists), the rays' records and the n x 4 spheres →
     (hit{distance,exit}[n,2], shape[n]).  A member is a candidate iff it hits and distance < tmax (strict, in T; tmax None = +inf); closest:
-    the smallest distance, the first of the row on equal distances; first: the first candidate of the row; none: {+inf, 0} and NONE."""
+    the smallest distance, the first of the row on equal distances; first: the first candidate of the row; none: {+inf, 0} and NONE.
+    hits: list_hits(off, idx, rays, spheres) where the caller has it already."""
     n = len(off) - 1
     T = spheres.dtype
-    hits = list_hits(off, idx, rays, spheres)
+    hits = list_hits(off, idx, rays, spheres) if hits is None else hits
     counts = np.diff(off.astype(np.int64))
     t = np.full(n, np.inf, dtype=T) if tmax is None else np.asarray(tmax, dtype=T)
     total = len(hits)

@@ -1199,48 +1199,44 @@ def test_c_abi_from_plain_c(eng, orc, tmp_path):
     check_shards(out4, 4)
 
 
+def _unreached_combos():
+    """fuzz_scenes.OTHER_COMBOS on seeds 100..107; from BVH_FUZZ_SEEDS = 32 on all 24 combinations outside the historic map, on seeds 100..123"""
+    import fuzz_scenes as fs
+    combos = fs.OTHER_COMBOS
+    if int(os.environ.get("BVH_FUZZ_SEEDS", "12")) >= 32:
+        reached = {(d, k, fs.k_scales(d).index(s)) for d, k, s in map(fs.historic, range(8))}
+        rest = [(d, k, si) for d in (np.float32, np.float64) for k in range(4) for si in range(4) if (d, k, si) not in reached and (d, k, si) not in fs.OTHER_COMBOS]
+        combos = fs.OTHER_COMBOS + rest
+    return [pytest.param(100 + j, d, k, si, id=f"{100 + j}-{'f32' if d == np.float32 else 'f64'}-{fs.KINDS[k]}-{fs.SCALES[si]}") for j, (d, k, si) in enumerate(combos)]
+
+
 @pytest.mark.parametrize("seed", range(int(os.environ.get("BVH_FUZZ_SEEDS", "12"))))   # BVH_FUZZ_SEEDS=400 for a long soak
 def test_fuzz_all_queries(eng, orc, seed):
     """in the spirit of the reference's fuzz.rs ("all traversals agree", fuzz.rs:321-324): random scenes of random
     size and character (spread, clustered, grid-aligned with exact ties, duplicated shapes), random rays and points;
-    every query the engine offers against the oracle, both dtypes alternating.  Each seed scales its scene by 2^k — 1, an
-    all-subnormal band, a band where surface areas overflow, 2^-20 — and a tenth of its rays are caller-built (inv = ±0,
-    subnormal, huge, or not 1/d)."""
+    every query the engine offered when this test was written against the oracle (tests/test_gpu_fuzz_queries.py has the later
+    families).  Each seed scales its scene by 2^k — 1, an all-subnormal band, a band where surface areas overflow, 2^-20 — and a tenth of
+    its rays are caller-built (inv = ±0, subnormal, huge, or not 1/d).  dtype, kind and scale follow from seed % 8 (fuzz_scenes.historic):
+    8 of the 32 combinations, however many seeds run; test_fuzz_all_queries_other_combos runs the same body on the others."""
+    import fuzz_scenes as fs
+    _fuzz_all_queries(eng, orc, seed, *fs.historic(seed))
+
+
+@pytest.mark.parametrize("seed,dtype,kind,scale_index", _unreached_combos())
+def test_fuzz_all_queries_other_combos(eng, orc, seed, dtype, kind, scale_index):
+    """test_fuzz_all_queries' body on combinations its map never reaches: grid-aligned scenes (the only ones with exact distance ties) in
+    f64 and at scale 1, duplicated shapes in f32, spread and clustered scenes in the subnormal band of the other dtype"""
+    import fuzz_scenes as fs
+    _fuzz_all_queries(eng, orc, seed, dtype, kind, fs.k_scales(dtype)[scale_index])
+
+
+def _fuzz_all_queries(eng, orc, seed, dtype, kind, k_scale):
+    """the scene of fuzz_scenes.draw(seed, dtype, kind, k_scale); the seed also rotates the tuning knobs"""
+    import fuzz_scenes as fs
     import query_ref as qr
     from test_gpu_any_hit import first_match
-    rng = np.random.default_rng(1000 + seed)
-    dtype = np.float32 if seed % 2 == 0 else np.float64
-    k_scale = (0, -140 if dtype == np.float32 else -1040, 70 if dtype == np.float32 else 520, -20)[(seed // 2) % 4]
-    sc = 2.0 ** k_scale
-    n = int(rng.integers(1, 6000 if seed % 7 else 60000))
-    kind = seed % 4
-    if kind == 0:
-        a = rng.uniform(-50, 50, size=(n, 3))
-    elif kind == 1:
-        c = rng.uniform(-50, 50, size=(max(n // 40, 1), 3))
-        a = c[rng.integers(0, len(c), n)] + rng.normal(scale=0.5, size=(n, 3))
-    elif kind == 2:
-        a = rng.integers(-8, 8, size=(n, 3)).astype(float)
-    else:
-        a = rng.uniform(-50, 50, size=(n, 3)); a[n // 3:] = a[: n - n // 3][rng.integers(0, max(n - n // 3, 1), n - n // 3)]
-    a = a.astype(dtype).astype(np.float64)
-    tri64 = np.stack([a, a + rng.uniform(0, 2, size=(n, 3)).astype(dtype), a + rng.uniform(0, 2, size=(n, 3)).astype(dtype)], axis=1)
-    tri = (tri64 * sc).astype(dtype)
-    aabbs = np.concatenate([tri.min(axis=1), tri.max(axis=1)], axis=1).astype(dtype)
-    m = 120 if k_scale < -100 else 1500                # (x86 arithmetic on subnormals is slow: the oracle's share of the time)
-    o64 = rng.uniform(-60, 60, size=(m, 3))
-    o = (o64 * sc).astype(dtype)
-    d = (tri64[rng.integers(0, n, m)].mean(axis=1) - o64).astype(dtype)
-    d[: m // 5] = rng.normal(size=(m // 5, 3))
-    d[m // 5: m // 4] = rng.integers(-1, 2, size=(m // 4 - m // 5, 3)); d[np.all(d == 0, axis=1)] = [1, 0, 0]
-    rays = orc.make_rays(o, d, dtype)
-    cb = rng.random(m) < 0.1                            # caller-built rays: Ray's fields are public
-    fi = np.finfo(dtype)
-    pick = np.array([0.0, -0.0, fi.smallest_subnormal, fi.max, 0.5, 3.0])[rng.integers(0, 6, size=(m, 3))]
-    keep = rng.random((m, 3)) < 0.5
-    with np.errstate(over="ignore", invalid="ignore"):
-        inv_cb = np.where(keep, rays["inv"].astype(np.float64), np.where(pick < 1.0, pick, pick * rays["inv"]))
-        rays["inv"][cb] = inv_cb[cb].astype(dtype)
+    scene = fs.draw(seed, dtype, kind, k_scale)
+    sc, tri, aabbs, rays = (scene[name] for name in ("sc", "tri", "aabbs", "rays"))
     bvh = eng.Bvh.from_aabbs(aabbs)
     ot = orc.build(aabbs)
     assert bvh.nodes.tobytes() == ot.nodes.tobytes() and np.array_equal(bvh.shape_nodes, ot.shape_node)
@@ -1292,20 +1288,19 @@ def test_fuzz_all_queries(eng, orc, seed):
         noff, nidx, _, _ = flat.traverse_batch(rb, order=order)
         qoff, qidx = orc.traverse_distance(ot.nodes, aabbs, rays, asc)
         assert np.array_equal(noff, qoff) and np.array_equal(nidx, qidx)
-    pts = (rng.uniform(-60, 60, size=(800 if m == 1500 else 60, 3)) * sc).astype(dtype)
+    pts = scene["pts"]
     for use_tris in (False, True):
         s_, d_ = flat.nearest_batch(pts, triangles=use_tris)
         os_, od_ = orc.nearest(oflat, aabbs, pts, tri if use_tris else None)
         assert np.array_equal(s_, os_) and same_bytes(d_, od_)
     # any hit with segment ends drawn around the nearest hit
     c = oclosest[:, 0].astype(np.float64)
-    tmax = (np.where(np.isfinite(c), c, 200.0 * sc) * rng.uniform(0.3, 1.7, size=m)).astype(dtype)
+    tmax = (np.where(np.isfinite(c), c, 200.0 * sc) * scene["tmax_u"]).astype(dtype)
     want = first_match(ooff, oidx, oisect, tmax)
     isect_a, shape_a = flat.any_hits(rb, tmax)
     assert same_bytes(isect_a, want[0]) and np.array_equal(shape_a, want[1])
     # AABB / point / ball queries around random shapes, the walks of knob 22 alternating with the seed
-    cq = (a[rng.integers(0, n, 150)] + rng.normal(size=(150, 3)))
-    e = rng.uniform(0, 3, size=(150, 3))
+    cq, e = scene["cq"], scene["e"]
     for qkind, q64 in ((qr.AABB, np.concatenate([cq - e, cq + e], axis=1)), (qr.POINT, cq), (qr.BALL, np.concatenate([cq, e[:, :1]], axis=1))):
         q = (q64 * sc).astype(dtype)
         qoff, qidx = qr.walk(oflat, aabbs, qkind, q)

@@ -25,6 +25,8 @@ LEAF_BOX, LEAF_TRIANGLE, LEAF_SPHERE = 0, 1, 2   # BVHGPU_LEAF_*: the leaf stage
 LEAF_KINDS = {"box": LEAF_BOX, "triangle": LEAF_TRIANGLE, "sphere": LEAF_SPHERE}
 LEAF_WIDTH = {LEAF_BOX: 2, LEAF_TRIANGLE: 3, LEAF_SPHERE: 2}   # scalars per record
 ALLHITS_LIST_ORDER = 1   # BVHGPU_ALLHITS_LIST_ORDER: rows of bvhgpu_traverse_allhits_* in list order, no sort pass
+WITHIN_LIST_ORDER = 1    # BVHGPU_WITHIN_LIST_ORDER: rows of bvhgpu_within_* in the order the loop met them, no sort pass
+WITHIN_COUNT_ONLY = 2    # BVHGPU_WITHIN_COUNT_ONLY: offsets and total only
 TRAVERSE_T_SLICE = 1
 TRAVERSE_STATS = 2
 TRAVERSE_TRIANGLES = 4
@@ -171,6 +173,9 @@ SYMBOLS = [
     ("bvhgpu_traverse_allhits_f32", _i, [_vp, _vp, _vp, _sz, _i, _i, _u, _pp]),
     ("bvhgpu_traverse_allhits_f64", _i, [_vp, _vp, _vp, _sz, _i, _i, _u, _pp]),
     ("bvhgpu_hits_fetch_allhits", _i, [_vp, _vp, _vp, _vp, _i]),
+    ("bvhgpu_within_f32", _i, [_vp, _vp, _vp, _sz, _i, _i, _u, _pp]),
+    ("bvhgpu_within_f64", _i, [_vp, _vp, _vp, _sz, _i, _i, _u, _pp]),
+    ("bvhgpu_hits_fetch_within", _i, [_vp, _vp, _vp, _vp, _i]),
     ("bvhgpu_enable_timing", _i, [_vp, _i]),
     ("bvhgpu_last_timings", _i, [_vp, C.POINTER(Timings)]),
     ("bvhgpu_obj_parse", _i, [C.c_char_p, _sz, C.POINTER(C.POINTER(C.c_float)), C.POINTER(_sz), _vp]),

@@ -523,6 +523,29 @@ class _Hits:
         check(lib.bvhgpu_hits_fetch_allhits(self.h, ptr(offsets), ptr(shape), ptr(vals), HOST), self.ctx._h)
         return offsets, shape, vals
 
+    def fetch_within(self, n: int, dtype=np.float32, device=None, count_only: bool = False):
+        """within batches (bvhgpu_hits_fetch_within): (offsets[n+1], shape[total], dist[total]) of the completed batch; a count-only batch
+        has empty shape and dist.  device None: copied to the host, offsets and shape as uint32.  device: torch tensors there, filled by
+        device-to-device copies — shape as torch.int32, offsets widened to torch.int64 on the device."""
+        lib = _lib.load()
+        total = C.c_uint64()
+        check(lib.bvhgpu_hits_info(self.h, None, C.byref(total), None), self.ctx._h)
+        rows = 0 if count_only else int(total.value)
+        if device is not None:
+            import torch
+            off32 = torch.empty(n + 1, dtype=torch.int32, device=device)
+            shape = torch.empty(rows, dtype=torch.int32, device=device)
+            dist = torch.empty(rows, dtype=torch.float32 if np.dtype(dtype) == np.float32 else torch.float64, device=device)
+            torch.cuda.current_stream(device).synchronize()
+            check(lib.bvhgpu_hits_fetch_within(self.h, ptr(off32.data_ptr()), ptr(shape.data_ptr()) if rows else None,
+                                               ptr(dist.data_ptr()) if rows else None, DEVICE), self.ctx._h)
+            return off32.to(torch.int64) & 0xFFFFFFFF, shape, dist
+        offsets = np.zeros(n + 1, dtype=np.uint32)
+        shape = np.zeros(rows, dtype=np.uint32)
+        dist = np.zeros(rows, dtype=dtype)
+        check(lib.bvhgpu_hits_fetch_within(self.h, ptr(offsets), ptr(shape) if rows else None, ptr(dist) if rows else None, HOST), self.ctx._h)
+        return offsets, shape, dist
+
     def close(self):
         if getattr(self, "h", None) and not _closing:
             _lib.load().bvhgpu_hits_destroy(self.h)
@@ -925,6 +948,59 @@ class _TreeBase:
         imported scene has no BvhNode array and raises INVALID_ARG.  points / returns: as knearest_batch."""
         return self._knearest("knearest_tree", points, k, triangles, max_dist, True)
 
+    def within_batch(self, points, max_dist, triangles: bool = False, sort: bool = True, count_only: bool = False):
+        """bvhgpu_within_*: every shape within max_dist[i] of point i, as a CSR — the loop of nearest_to (flat_bvh.rs:524-558) with the
+        moving best_dist replaced by the fixed limit r2 = max_dist[i]^2 (one multiplication in the tree's dtype) and every comparison <=,
+        so the limit itself is inside; a negative or NaN limit gives an empty row, +inf keeps every shape whose distance is not NaN.  Shape
+        distance as for knearest_batch (triangles=True needs set_triangles).  Rows are in a stable ascending sort by distance, equal
+        distances in leaf pre-order; sort=False (BVHGPU_WITHIN_LIST_ORDER) leaves them in the order the loop met them; count_only=True
+        (BVHGPU_WITHIN_COUNT_ONLY) produces the offsets alone (shape and dist are empty).
+        points: (n, 3) in the tree's dtype — a numpy array (HOST) or a torch GPU tensor (DEVICE).  max_dist: a scalar (the same limit for
+        every point) or n values in the points' memory.
+        returns (offsets[n+1], shape[total], dist[total]); no padding.  numpy in: numpy out, offsets and shape as uint32.  torch in: torch
+        tensors on the same device, shape as torch.int32, offsets as torch.int64."""
+        fn = getattr(_lib.load(), f"bvhgpu_within_{self.sfx}")
+        ft = np.float32 if self.sfx == "f32" else np.float64
+        kind = 1 if triangles else 0
+        flags = (0 if sort else _lib.WITHIN_LIST_ORDER) | (_lib.WITHIN_COUNT_ONLY if count_only else 0)
+        if max_dist is None:
+            raise BvhGpuError(_lib.INVALID_ARG, "within_batch needs max_dist (a scalar or one value per point)")
+        scalar = not _is_device_tensor(max_dist) and np.ndim(max_dist) == 0
+        if _is_device_tensor(points):
+            import torch
+            if str(points.dtype) != ("torch.float32" if self.sfx == "f32" else "torch.float64"):
+                raise BvhGpuError(_lib.DTYPE_MISMATCH, "point dtype differs from tree dtype")
+            p = points.contiguous()
+            n = p.numel() // 3
+            if scalar:
+                m = torch.full((n,), float(max_dist), dtype=p.dtype, device=p.device)
+            else:
+                if not _is_device_tensor(max_dist):
+                    raise BvhGpuError(_lib.INVALID_ARG, "max_dist is in host memory but the points are in HBM")
+                if max_dist.dtype != p.dtype:
+                    raise BvhGpuError(_lib.DTYPE_MISMATCH, "max_dist dtype differs from tree dtype")
+                m = max_dist.contiguous()
+            if m.numel() != n:
+                raise BvhGpuError(_lib.INVALID_ARG, f"max_dist has {m.numel()} values for {n} points")
+            torch.cuda.current_stream(p.device).synchronize()   # the engine works on its own stream: the points must be there
+            check(fn(self._t, ptr(p.data_ptr()), ptr(m.data_ptr()), n, DEVICE, kind, flags, C.byref(self._hits.h)), self.ctx._h)
+            return self._hits.fetch_within(n, ft, p.device, count_only)
+        if isinstance(points, np.ndarray) and points.dtype != ft:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "point dtype differs from tree dtype")
+        p = np.ascontiguousarray(points, dtype=ft).reshape(-1, 3)
+        if scalar:
+            m = np.full(len(p), max_dist, dtype=ft)
+        else:
+            if _is_device_tensor(max_dist):
+                raise BvhGpuError(_lib.INVALID_ARG, "max_dist is a GPU tensor but the points are in host memory")
+            if isinstance(max_dist, np.ndarray) and max_dist.dtype != ft:
+                raise BvhGpuError(_lib.DTYPE_MISMATCH, "max_dist dtype differs from tree dtype")
+            m = np.ascontiguousarray(max_dist, dtype=ft).reshape(-1)
+        if m.size != len(p):
+            raise BvhGpuError(_lib.INVALID_ARG, f"max_dist has {m.size} values for {len(p)} points")
+        check(fn(self._t, ptr(p), ptr(m), len(p), HOST, kind, flags, C.byref(self._hits.h)), self.ctx._h)
+        return self._hits.fetch_within(len(p), ft, None, count_only)
+
     def nearest_to(self, query, shapes: Sequence, triangles: bool = False):
         """BoundingHierarchy::nearest_to (bounding_hierarchy.rs:262-336): Option<(&Shape, distance)>."""
         s, d = self.nearest_batch([query], triangles)
@@ -1269,6 +1345,10 @@ class Bvh(_TreeBase):
     def allhits_batch(self, rays: RayBatch, leaf: str = "box", tmax=None, sort: bool = True):
         self.flatten_in_place()
         return super().allhits_batch(rays, leaf, tmax, sort)
+
+    def within_batch(self, points, max_dist, triangles: bool = False, sort: bool = True, count_only: bool = False):
+        self.flatten_in_place()
+        return super().within_batch(points, max_dist, triangles, sort, count_only)
 
 
 class _FlatView(FlatBvh):

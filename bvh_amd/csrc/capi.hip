@@ -286,7 +286,7 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
     }
     if ((flags & BVHGPU_TRAVERSE_TRIANGLES) && (flags & BVHGPU_TRAVERSE_CLOSEST))
         return fail(ctx, BVHGPU_INVALID_ARG, "TRIANGLES and CLOSEST are alternatives");
-    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT | TRAVERSE_SPHERE_HIT | TRAVERSE_ALLHITS);   // (internal: only bvhgpu_traverse_any_* / _box_* / _sphere_* / _allhits_* set them)
+    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT | TRAVERSE_SPHERE_HIT | TRAVERSE_ALLHITS | TRAVERSE_WITHIN);   // (internal: only bvhgpu_traverse_any_* / _box_* / _sphere_* / _allhits_* and bvhgpu_within_* set them)
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
@@ -643,6 +643,38 @@ int do_allhits(bvhgpu_tree* t, const typename Traits<T>::Ray* rays, const T* tma
         const T* td = n ? static_cast<const T*>(h->pend_tmax) : nullptr;
         h->pend_tmax = nullptr;                // (nothing replays this batch)
         allhits_batch<T>(t, dev, td, n, leaf, flags, h);
+        return (int)BVHGPU_OK;
+    });
+}
+
+// ---- radius-search point batches: bvhgpu_within_* ---------------------------------------------------------------------------------------
+// do_allhits' shape with points and limits in place of rays and tmax; the result goes to a result object (within.hip), whose buffers a
+// later batch of any kind reuses.  A refused call touches no buffer and leaves *hits as it was.
+template <typename T>
+int do_within(bvhgpu_tree* t, const T* points, const T* max_dist, size_t n, int mem, int kind, unsigned flags, bvhgpu_hits** hits) {
+    if (!t) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL tree");
+    bvhgpu_ctx* ctx = t->ctx;
+    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
+    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
+    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
+    if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from point dtype");
+    if (!t->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    if (n && !points) return fail(ctx, BVHGPU_INVALID_ARG, "points is NULL");
+    if (n && !max_dist) return fail(ctx, BVHGPU_INVALID_ARG, "max_dist is NULL");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (kind != 0 && kind != 1) return fail(ctx, BVHGPU_INVALID_ARG, "shape kind must be 0 (AABB) or 1 (triangle)");
+    if (flags & ~(BVHGPU_WITHIN_LIST_ORDER | BVHGPU_WITHIN_COUNT_ONLY))
+        return fail(ctx, BVHGPU_INVALID_ARG, "within flags: BVHGPU_WITHIN_LIST_ORDER and BVHGPU_WITHIN_COUNT_ONLY only");
+    if (kind == 1 && !t->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "triangle distance needs bvhgpu_tree_set_triangles first");
+    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 points in one batch");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        bvhgpu_hits* h = batch_hits(hits);
+        const auto* dev = static_cast<const T*>(to_device(ctx, points, n * 3 * sizeof(T), mem, ctx->upload));
+        stage_tmax<T>(ctx, h, max_dist, n, mem);   // (HOST limits are staged as do_allhits stages tmax)
+        const T* md = n ? static_cast<const T*>(h->pend_tmax) : nullptr;
+        h->pend_tmax = nullptr;                    // (nothing replays this batch)
+        within_batch<T>(t, dev, md, n, kind, flags, h);
         return (int)BVHGPU_OK;
     });
 }
@@ -1321,6 +1353,12 @@ int bvhgpu_traverse_allhits_f64(bvhgpu_tree* t, const bvhgpu_ray_f64* rays, cons
                                 bvhgpu_hits** hits) {
     return do_allhits<double>(t, rays, tmax, n_rays, mem, leaf, flags, hits);
 }
+int bvhgpu_within_f32(bvhgpu_tree* t, const float* points, const float* max_dist, size_t n, int mem, int kind, unsigned flags, bvhgpu_hits** hits) {
+    return do_within<float>(t, points, max_dist, n, mem, kind, flags, hits);
+}
+int bvhgpu_within_f64(bvhgpu_tree* t, const double* points, const double* max_dist, size_t n, int mem, int kind, unsigned flags, bvhgpu_hits** hits) {
+    return do_within<double>(t, points, max_dist, n, mem, kind, flags, hits);
+}
 int bvhgpu_ray_triangle_pairs_f32(bvhgpu_ctx* ctx, const bvhgpu_ray_f32* rays, const float* tris, size_t n, int mem, float* out) {
     return do_pairs<float>(ctx, rays, tris, n, mem, out);
 }
@@ -1452,6 +1490,7 @@ int bvhgpu_hits_fetch_triangles(bvhgpu_hits* h, void* isect, int mem) {
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "a sphere-hit batch has no triangle values: use bvhgpu_hits_fetch_sphere");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
+    if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (!(h->flags & BVHGPU_TRAVERSE_TRIANGLES)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_TRIANGLES");
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -1467,6 +1506,7 @@ static int fetch_per_ray(bvhgpu_hits* h, void* values, uint32_t* shape, int mem,
     if ((h->flags & TRAVERSE_SPHERE_HIT) && kind_bit != TRAVERSE_SPHERE_HIT)
         return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
+    if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (!(h->flags & kind_bit)) return fail(ctx, BVHGPU_INVALID_ARG, other_kind_msg);
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -1516,6 +1556,7 @@ int bvhgpu_hits_fetch(bvhgpu_hits* h, uint32_t* offsets, uint32_t* indices, void
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "an all-hits batch has a CSR of its own: use bvhgpu_hits_fetch_allhits");
+    if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (tslice && !(h->flags & BVHGPU_TRAVERSE_T_SLICE)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_T_SLICE");
     if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR: use bvhgpu_hits_fetch_closest");
     if (h->flags & TRAVERSE_ANY_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR: use bvhgpu_hits_fetch_any");
@@ -1535,6 +1576,7 @@ int bvhgpu_hits_fetch_allhits(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape
     if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (!(h->flags & TRAVERSE_ALLHITS)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_traverse_allhits_* batch");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
     return guarded(ctx, [&] {
@@ -1547,10 +1589,29 @@ int bvhgpu_hits_fetch_allhits(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape
     });
 }
 
+// the CSR of a within batch: offsets (n + 1 u32), the shapes (total u32), the distances (total T); each may be NULL.  A COUNT_ONLY batch
+// has offsets only: its shapes and distances are empty, whatever `total` says.
+int bvhgpu_hits_fetch_within(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape, void* dist, int mem) {
+    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = h->ctx;
+    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (!(h->flags & TRAVERSE_WITHIN)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_within_* batch");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        const size_t rows = h->wi_count_only ? 0 : (size_t)h->total;
+        if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
+        if (shape && rows) copy_out(ctx, shape, h->indices.p, rows * 4, mem);
+        if (dist && rows) copy_out(ctx, dist, h->ah_vals.p, rows * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
+        return (int)BVHGPU_OK;
+    });
+}
+
 int bvhgpu_hits_device(const bvhgpu_hits* h, const uint32_t** offsets, const uint32_t** indices, const void** tslice) {
     if (!h) return BVHGPU_INVALID_ARG;
     if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_ALLHITS) return fail(h->ctx, BVHGPU_INVALID_ARG, "an all-hits batch has a CSR of its own: use bvhgpu_hits_fetch_allhits");
+    if (h->flags & TRAVERSE_WITHIN) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(h->ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR");
     if (h->flags & TRAVERSE_ANY_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR");
     if (h->flags & TRAVERSE_BOX_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "a box-hit batch produces no CSR");

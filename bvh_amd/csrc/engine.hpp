@@ -48,6 +48,9 @@ constexpr unsigned TRAVERSE_BOX_HIT = 1u << 30;
 constexpr unsigned TRAVERSE_SPHERE_HIT = 1u << 29;
 // result objects of bvhgpu_traverse_allhits_* (allhits.hip): marked the same way; the only bit such a result carries
 constexpr unsigned TRAVERSE_ALLHITS = 1u << 28;
+// result objects of bvhgpu_within_* (within.hip): marked the same way; the only bit such a result carries.  (The caller flags end at
+// BVHGPU_TRAVERSE_FIRST = 1u << 10, and BVHGPU_WITHIN_* are never stored in bvhgpu_hits::flags.)
+constexpr unsigned TRAVERSE_WITHIN = 1u << 27;
 
 }  // namespace bvhgpu
 
@@ -287,6 +290,9 @@ struct bvhgpu_hits {
     bvhgpu::DevBuf ah_vals;
     bvhgpu::DevBuf ah_counts, ah_sums;   // n_rays u32 candidate counts; {total, long rows, rows beyond LDS} + a 64-bit sum per scan block
     bvhgpu::DevBuf ah_work, ah_pos;      // the long rows of a sorted batch (ray ids); list positions of the rows sorted in global memory
+    // within batches (bvhgpu_within_*, within.hip) reuse them: the CSR is `offsets` / `indices` (the shapes) / `ah_vals` (total T distances)
+    bool wi_count_only = false;          // BVHGPU_WITHIN_COUNT_ONLY: `offsets` and `total` only, no shapes and no distances
+    bvhgpu::DevBuf wi_unfold;            // the FlatNode array of a built tree with empty child bounds as an unfolded TravNode array (within.hip)
     uint32_t replays = 0;               // times bvhgpu_hits_wait had to enqueue the asynchronous batch again
     int deferred_rc = 0;                // status of a completion that ran on behalf of another call (rebuild / destroy of the tree)
     std::string deferred_err;
@@ -363,6 +369,11 @@ void khits_batch(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, const 
 // more than 2^32-1 candidates (the result object then holds an empty all-hits result).
 template <typename T>
 void allhits_batch(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, int leaf, unsigned flags, bvhgpu_hits* h);
+// within.hip: every shape within max_dist_dev[i] of point i as a CSR (bvhgpu_within_*); kind: 0 the shapes' AABBs, 1 their triangles; flags:
+// BVHGPU_WITHIN_*.  Synchronous: h->offsets / h->indices / h->ah_vals and h->total are complete on return.  Throws Fail::Overflow when the
+// batch has more than 2^32-1 candidates (the result object then holds an empty within result).
+template <typename T>
+void within_batch(bvhgpu_tree* t, const T* points_dev, const T* max_dist_dev, size_t n, int kind, unsigned flags, bvhgpu_hits* h);
 // rays.hip
 template <typename T>
 void ray_triangle_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays_dev, const T* tris_dev, size_t n, T* out_dev);

@@ -1,0 +1,431 @@
+// within.hip — every shape within max_dist of every query point of a batch, in order, as a CSR (bvhgpu_within_*; include/bvh_mi355x.h,
+// DESIGN.md §4i).
+//
+// The definition is <FlatBvh as BoundingHierarchy>::nearest_to's loop (flat_bvh.rs:524-558) with the moving `best_dist` replaced by a
+// fixed limit.  Point p_i comes with m = max_dist[i] in the tree's dtype T; r2 = m * m is ONE multiplication in T.  A negative or NaN m
+// (!(m >= 0)) gives an empty row without a walk.
+//   i = 0
+//   while i < len(flat):
+//     non-leaf entry: md = aabb.min_distance_squared(p);  i = (md <= r2) ? entry_index : exit_index
+//     leaf entry:     d  = shape.distance_squared(p);     if d <= r2: candidate (d, shape);  i = exit_index
+// shape.distance_squared is kind 0, the shape's own Aabb::min_distance_squared, or kind 1, the triangle (point_dist.hpp, unchanged: the
+// bits of k_knearest).  Every comparison is T's <= as written, so the limit itself is inside: m = 0 keeps the shapes at distance 0,
+// m = +inf (r2 = +inf) keeps every shape whose distance is not NaN, and a NaN d is never a candidate — a candidate's key is never NaN and
+// the sorted order below is a total order.  aabb_min_dist2 ends every axis with max(0), which turns NaN into 0: a NaN coordinate of the
+// point contributes 0 on its axis to every box distance (a point that is all NaN is at distance 0 of every box), an infinite coordinate
+// gives +inf against a finite box (entered only with m = +inf) and, against a box that is infinite on that axis, NaN -> 0.  The triangle
+// distance has no such guard: a NaN or infinite point gives it NaN (never a candidate) or +inf.
+//   Row i, default: ALL candidates in a stable ascending sort by d; equal d stay in the order the loop met them (leaf pre-order).  The
+//   output distance is sqrt(d), as in the k-nearest rows.
+//   Row i with BVHGPU_WITHIN_LIST_ORDER: the candidates in the order the loop met them, no sort pass.
+//   BVHGPU_WITHIN_COUNT_ONLY: only `offsets` (and the total); the fill and sort passes do not run.
+// The threshold never moves, so the candidate set does not depend on the order a walk visits nodes in: it is "every box on the shape's
+// path passes md <= r2 and the shape passes d <= r2".  Nearest-first descent buys nothing here; the 32 / 64-byte `trav` entries are the
+// array to walk.
+//
+// The schedule is allhits.hip's with a point in place of the ray; every walk is k_knearest's loop, one point per lane (within_walk):
+//   k_within_count       counts[q] = the candidates of point q (lanes with a negative or NaN limit do not walk)
+//   k_within_block_sums  64-bit sum per block of WITHIN_SCAN_BLOCK counts; the points of a sorted batch whose rows are longer than
+//                        WITHIN_LANE_ROW_MAX are appended to the long-row worklist (any order), those above WITHIN_LDS_ROW_MAX counted
+//   k_within_scan_sums   exclusive scan of the block sums (one workgroup); the batch's 64-bit total
+//   ... ONE host read {total, long rows, rows beyond LDS}: BVHGPU_OVERFLOW before anything is sized by the total ...
+//   k_within_scan_final  offsets[q] = block base + exclusive scan inside the block, offsets[n] = total
+//   k_within_fill        walks again; lane q owns [offsets[q], offsets[q + 1]).  A row of a sorted batch up to WITHIN_LANE_ROW_MAX is built
+//                        by k_knearest's insertion (search from the back with the strict <: stable) on its own region — the key of
+//                        element e lives in dist[e] — and a final per-lane pass turns the keys into sqrt.  A LIST_ORDER row gets
+//                        (shape, sqrt(d)) appended as the walk meets them.  A longer row of a sorted batch gets (d, shape) appended in
+//                        list order (and its positions, beyond WITHIN_LDS_ROW_MAX) and is left to
+//   k_within_sort_row    one workgroup per long row: allhits.hip's all-ascending bitonic network on the keys (d, position) with the shape
+//                        as payload, in LDS up to WITHIN_LDS_ROW_MAX elements, in place in global memory beyond; then sqrt.
+// The three scan kernels restate allhits.hip's (the library is built without relocatable device code, and allhits.hip keeps its
+// instruction text), as knn_tree.hip restates knn.hip's insertion.  The row length is uniform per workgroup of k_within_sort_row: every
+// loop bound and every barrier there depends on it alone.  No walk has a cross-lane operation.
+//
+// Which array is walked.  `trav` folds a leaf's navigator entry and its leaf entry into one entry that carries the shape's own box: for
+// a tree built here that box is bit-identical to the navigator box — except below a split without SAH winner (t->exact_only), whose two
+// child boxes are Aabb::empty().  min_distance_squared of the empty box is 0 for every point (NaN -> 0 on every axis), so the reference
+// enters such a leaf whatever the point, while the folded entry would test the shape's box.  With kind 0 that is the same decision (d IS
+// that box distance); with kind 1 it is not where rounding puts the box distance above the triangle distance (a point on a vertex,
+// m = 0).  A built tree with such a split is therefore walked over an unfolded mirror of its FlatNode array (k_within_unfold, written into
+// the result object per batch; query.hip walks the FlatNode array itself for the same reason), with the UNFOLDED rule.
+#include <cstdio>
+
+#include "point_dist.hpp"
+
+namespace bvhgpu {
+
+// Thresholds: allhits.hip's values.  DESIGN.md §4i: on radius rows of about 20 and 200 a lane tier ending at 8 or at 128 is slower than
+// 32; the LDS limit has not been varied (no measured row comes near it).  WITHIN_LANE_ROW_MAX: a lane's insertion into global memory costs up to len^2 / 2
+// element moves that no other lane of the wave shares.  WITHIN_LDS_ROW_MAX: 2048 x (8 + 4 + 4) bytes = 32 KB in f64, 24 KB in f32 — five
+// (six) workgroups share a CU's 160 KB of LDS.
+#ifndef BVH_WITHIN_LANE_ROW_MAX   // (developer builds, build_ext.py --variant: tools/within_bench.py against other thresholds)
+#define BVH_WITHIN_LANE_ROW_MAX 32
+#endif
+#ifndef BVH_WITHIN_LDS_ROW_MAX
+#define BVH_WITHIN_LDS_ROW_MAX 2048
+#endif
+constexpr uint32_t WITHIN_LANE_ROW_MAX = BVH_WITHIN_LANE_ROW_MAX;
+constexpr uint32_t WITHIN_LDS_ROW_MAX = BVH_WITHIN_LDS_ROW_MAX;
+constexpr uint32_t WITHIN_SORT_THREADS = 256;
+constexpr uint32_t WITHIN_SCAN_ITEMS = 4;
+constexpr uint32_t WITHIN_SCAN_BLOCK = 256 * WITHIN_SCAN_ITEMS;   // counts per workgroup of the scan
+static_assert(WITHIN_LDS_ROW_MAX * (sizeof(double) + 8u) <= 64u * 1024u, "a row sorted in LDS must fit a workgroup's LDS");
+static_assert((WITHIN_LDS_ROW_MAX & (WITHIN_LDS_ROW_MAX - 1)) == 0, "the LDS tier pads a row to a power of two inside its arrays");
+
+// what the host reads between the scan and the fill (the first 16 bytes of the sums buffer)
+struct WithinMeta { unsigned long long total; uint32_t n_long, n_beyond_lds; };
+
+template <typename T> struct WithinPoint {
+    T p[3], r2;
+    bool walk;   // the limit is neither negative nor NaN
+    __device__ __forceinline__ void load(const T* __restrict__ points, const T* __restrict__ max_dist, uint32_t q) {
+        for (int c = 0; c < 3; c++) p[c] = points[3 * (size_t)q + c];
+        const T m = max_dist[q];
+        r2 = m * m;
+        walk = m >= (T)0;
+    }
+};
+
+// the FlatNode array as an unfolded TravNode array, entry for entry (a non-leaf entry's entry_index is i + 1: flat_bvh.rs:104-127)
+template <typename T>
+__global__ __launch_bounds__(256) void k_within_unfold(const typename Traits<T>::Flat* __restrict__ flat, uint32_t n_flat, TravNode<T>* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_flat) return;
+    const typename Traits<T>::Flat f = flat[i];
+    TravNode<T> e = {};
+    for (int c = 0; c < 3; c++) { e.mn[c] = f.min[c]; e.mx[c] = f.max[c]; }
+    e.exit = f.exit;
+    e.shape = f.entry == NONE ? f.shape : (TRAV_INNER | SLOT_NONE);
+    out[i] = e;
+}
+
+// k_knearest's loop with the fixed threshold: on_candidate(shape, d) for every shape the definition keeps, in the order it meets them
+template <typename T, bool TRIANGLE, bool UNFOLDED, typename F>
+__device__ __forceinline__ void within_walk(const TravNode<T>* __restrict__ nodes, uint32_t n_trav, const T* __restrict__ shape_aabbs,
+                                            const T* __restrict__ tris, const WithinPoint<T>& pt, F&& on_candidate) {
+    uint32_t i = 0;
+    while (i < n_trav) {
+        const NodeRegs<T> nd = load_node(nodes + i);
+        const bool leaf = trav_is_leaf(nd.shape);
+        bool enter = true;
+        if (!(UNFOLDED && leaf)) {   // (a leaf entry of an unfolded array has no navigator test)
+            const T md = aabb_min_dist2<T>(nd.mn, nd.mx, pt.p);
+            enter = md <= pt.r2;
+        }
+        if (leaf) {
+            if (enter) {
+                T d;
+                if (TRIANGLE) d = triangle_dist2<T>(tris + 9 * (size_t)nd.shape, pt.p);
+                else {
+                    const T* sb = shape_aabbs + 6 * (size_t)nd.shape;
+                    const T mn[3] = {sb[0], sb[1], sb[2]}, mx[3] = {sb[3], sb[4], sb[5]};
+                    d = aabb_min_dist2<T>(mn, mx, pt.p);
+                }
+                if (d <= pt.r2) on_candidate(nd.shape, d);
+            }
+            i = nd.exit;
+        } else {
+            i = enter ? i + 1 : nd.exit;
+        }
+    }
+}
+
+template <typename T, bool TRIANGLE, bool UNFOLDED>
+__global__ __launch_bounds__(256) void k_within_count(const TravNode<T>* __restrict__ nodes, uint32_t n_trav, const T* __restrict__ shape_aabbs,
+                                                      const T* __restrict__ tris, const T* __restrict__ points,
+                                                      const T* __restrict__ max_dist, uint32_t n, uint32_t* __restrict__ counts) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    WithinPoint<T> pt;
+    pt.load(points, max_dist, q);
+    uint32_t cnt = 0;
+    if (pt.walk) within_walk<T, TRIANGLE, UNFOLDED>(nodes, n_trav, shape_aabbs, tris, pt, [&](uint32_t, T) { cnt++; });
+    counts[q] = cnt;
+}
+
+// ---- the scan of the counts (allhits.hip's three kernels, restated) -----------------------------------------------------------------
+// sums[b] = the counts of block b, in 64 bits; the long rows of a sorted batch (lane_max != 0) go to the worklist
+__global__ __launch_bounds__(256) void k_within_block_sums(const uint32_t* __restrict__ counts, uint32_t n, unsigned long long* __restrict__ sums,
+                                                           WithinMeta* __restrict__ meta, uint32_t* __restrict__ work, uint32_t lane_max, uint32_t lds_max) {
+    __shared__ unsigned long long part[256];
+    const uint32_t base = blockIdx.x * WITHIN_SCAN_BLOCK + threadIdx.x * WITHIN_SCAN_ITEMS;
+    unsigned long long s = 0;
+    for (uint32_t j = 0; j < WITHIN_SCAN_ITEMS; j++) {
+        const uint32_t q = base + j;
+        if (q < n) {   // (base + j cannot wrap: n < 2^32 - 1 and the grid covers n)
+            const uint32_t c = counts[q];
+            s += c;
+            if (lane_max != 0 && c > lane_max) {
+                work[atomicAdd(&meta->n_long, 1u)] = q;   // (at most n entries: one per point)
+                if (c > lds_max) atomicAdd(&meta->n_beyond_lds, 1u);
+            }
+        }
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (uint32_t w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) sums[blockIdx.x] = part[0];
+}
+
+// one workgroup: sums[b] becomes the sum of the blocks in front of b; meta->total
+__global__ __launch_bounds__(256) void k_within_scan_sums(unsigned long long* __restrict__ sums, uint32_t nb, WithinMeta* __restrict__ meta) {
+    __shared__ unsigned long long part[256];
+    __shared__ unsigned long long carry_s;
+    if (threadIdx.x == 0) carry_s = 0;
+    __syncthreads();
+    for (uint32_t b0 = 0; b0 < nb; b0 += 256) {   // (nb is uniform: every thread runs every barrier)
+        const uint32_t b = b0 + threadIdx.x;
+        const unsigned long long own = b < nb ? sums[b] : 0ull;
+        part[threadIdx.x] = own;
+        __syncthreads();
+        for (uint32_t w = 1; w < 256; w <<= 1) {
+            const unsigned long long add = threadIdx.x >= w ? part[threadIdx.x - w] : 0ull;
+            __syncthreads();
+            part[threadIdx.x] += add;
+            __syncthreads();
+        }
+        const unsigned long long carry = carry_s;
+        if (b < nb) sums[b] = carry + part[threadIdx.x] - own;
+        __syncthreads();
+        if (threadIdx.x == 255) carry_s = carry + part[255];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) meta->total = carry_s;
+}
+
+// offsets[q] for the block's counts (the host has checked that the total fits 32 bits)
+__global__ __launch_bounds__(256) void k_within_scan_final(const uint32_t* __restrict__ counts, uint32_t n, const unsigned long long* __restrict__ sums,
+                                                           const WithinMeta* __restrict__ meta, uint32_t* __restrict__ offsets) {
+    __shared__ uint32_t part[256];
+    const uint32_t base = blockIdx.x * WITHIN_SCAN_BLOCK + threadIdx.x * WITHIN_SCAN_ITEMS;
+    uint32_t c[WITHIN_SCAN_ITEMS], own = 0;
+    for (uint32_t j = 0; j < WITHIN_SCAN_ITEMS; j++) {
+        c[j] = base + j < n ? counts[base + j] : 0u;
+        own += c[j];
+    }
+    part[threadIdx.x] = own;
+    __syncthreads();
+    for (uint32_t w = 1; w < 256; w <<= 1) {
+        const uint32_t add = threadIdx.x >= w ? part[threadIdx.x - w] : 0u;
+        __syncthreads();
+        part[threadIdx.x] += add;
+        __syncthreads();
+    }
+    uint32_t run = (uint32_t)sums[blockIdx.x] + part[threadIdx.x] - own;
+    for (uint32_t j = 0; j < WITHIN_SCAN_ITEMS; j++) {
+        if (base + j < n) offsets[base + j] = run;
+        run += c[j];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) offsets[n] = (uint32_t)meta->total;
+}
+
+// ---- the second walk ----------------------------------------------------------------------------------------------------------------
+// pos: NULL, or total u32 — the list positions of the rows beyond WITHIN_LDS_ROW_MAX (a sorted batch that has such rows)
+template <typename T, bool TRIANGLE, bool UNFOLDED, bool SORTED>
+__global__ __launch_bounds__(256) void k_within_fill(const TravNode<T>* __restrict__ nodes, uint32_t n_trav, const T* __restrict__ shape_aabbs,
+                                                     const T* __restrict__ tris, const T* __restrict__ points, const T* __restrict__ max_dist,
+                                                     uint32_t n, const uint32_t* __restrict__ offsets, uint32_t* __restrict__ shape,
+                                                     T* __restrict__ dist, uint32_t* __restrict__ pos) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const uint32_t beg = offsets[q], len = offsets[q + 1] - beg;
+    if (len == 0) return;   // (the count pass walked this point, or refused its limit: nothing to write)
+    WithinPoint<T> pt;
+    pt.load(points, max_dist, q);
+    uint32_t* __restrict__ rs = shape + beg;
+    T* __restrict__ rd = dist + beg;
+    const bool insert = SORTED && len <= WITHIN_LANE_ROW_MAX;
+    const bool with_pos = SORTED && pos != nullptr && len > WITHIN_LDS_ROW_MAX;
+    uint32_t cnt = 0;
+    within_walk<T, TRIANGLE, UNFOLDED>(nodes, n_trav, shape_aabbs, tris, pt, [&](uint32_t s, T d) {
+        if (cnt >= len) return;   // (never: this walk is the count pass's; a lane stays inside its own region whatever happens)
+        if (insert) {
+            // ascending list: the first element e with d < e is where a scan from the back stops, so search and shift are one loop
+            uint32_t hole = cnt;
+#pragma unroll 1
+            while (hole > 0) {
+                const T e = rd[hole - 1];
+                if (!(d < e)) break;
+                rd[hole] = e;
+                rs[hole] = rs[hole - 1];
+                hole--;
+            }
+            rd[hole] = d;
+            rs[hole] = s;
+        } else if (SORTED) {   // a long row: (d, shape) in list order for k_within_sort_row
+            rd[cnt] = d;
+            rs[cnt] = s;
+            if (with_pos) pos[beg + cnt] = cnt;
+        } else {               // list order: the distance as the walk meets it
+            rd[cnt] = sqrt(d);
+            rs[cnt] = s;
+        }
+        cnt++;
+    });
+    if (insert) {
+#pragma unroll 1
+        for (uint32_t j = 0; j < cnt; j++) rd[j] = sqrt(rd[j]);
+    }
+}
+
+// the all-ascending bitonic network on len elements padded (virtually) to P = 2^k >= len; element e: key (kd[e], kp[e]), payload ks[e].
+// First step of every merge mirrors, the others shift: every comparator leaves the smaller key at the lower index, so the slots between
+// the row's length and P — (+inf, UINT32_MAX) by definition — never move and need no storage.  Every thread of the workgroup calls it
+// with the same len and P.  GLOBAL: the arrays are in global memory (a fence in front of the barrier).
+template <typename T, bool GLOBAL>
+__device__ __forceinline__ void within_bitonic(T* kd, uint32_t* kp, uint32_t* ks, uint32_t len, uint32_t P) {
+    const uint32_t half = P >> 1;
+    for (uint32_t k = 2; k <= P; k <<= 1) {
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            const bool mirror = j == (k >> 1);
+            for (uint32_t t = threadIdx.x; t < half; t += WITHIN_SORT_THREADS) {
+                const uint32_t lo = 2 * j * (t / j) + (t % j);
+                const uint32_t hi = mirror ? 2 * j * (t / j) + (2 * j - 1 - (t % j)) : lo + j;
+                if (hi < len) {   // (lo < hi; a slot beyond the row is the largest key: nothing to exchange)
+                    const T dl = kd[lo], dh = kd[hi];
+                    const uint32_t pl = kp[lo], ph = kp[hi];
+                    if (dh < dl || (dh == dl && ph < pl)) {
+                        kd[lo] = dh; kd[hi] = dl;
+                        kp[lo] = ph; kp[hi] = pl;
+                        const uint32_t sl = ks[lo], sh = ks[hi];
+                        ks[lo] = sh; ks[hi] = sl;
+                    }
+                }
+            }
+            if (GLOBAL) __threadfence_block();
+            __syncthreads();
+        }
+    }
+}
+
+// one workgroup per long row of a sorted batch
+template <typename T>
+__global__ __launch_bounds__(WITHIN_SORT_THREADS) void k_within_sort_row(const uint32_t* __restrict__ work, const uint32_t* __restrict__ offsets,
+                                                                         uint32_t* shape, T* dist, uint32_t* pos) {
+    __shared__ T ld[WITHIN_LDS_ROW_MAX];
+    __shared__ uint32_t lp[WITHIN_LDS_ROW_MAX];
+    __shared__ uint32_t ls[WITHIN_LDS_ROW_MAX];
+    const uint32_t q = work[blockIdx.x];
+    const uint32_t beg = offsets[q], len = offsets[q + 1] - beg;   // uniform over the workgroup
+    uint32_t P = 1;
+    while (P < len) P <<= 1;
+    uint32_t* rs = shape + beg;
+    T* rd = dist + beg;
+    if (len <= WITHIN_LDS_ROW_MAX) {
+        for (uint32_t e = threadIdx.x; e < len; e += WITHIN_SORT_THREADS) { ld[e] = rd[e]; lp[e] = e; ls[e] = rs[e]; }
+        __syncthreads();
+        within_bitonic<T, false>(ld, lp, ls, len, P);
+        for (uint32_t e = threadIdx.x; e < len; e += WITHIN_SORT_THREADS) { rd[e] = sqrt(ld[e]); rs[e] = ls[e]; }
+    } else if (pos != nullptr) {   // (the host passes the positions whenever a row is this long)
+        __threadfence_block();
+        __syncthreads();
+        within_bitonic<T, true>(rd, pos + beg, rs, len, P);
+        for (uint32_t e = threadIdx.x; e < len; e += WITHIN_SORT_THREADS) rd[e] = sqrt(rd[e]);   // (the network ended with a barrier)
+    }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+template <typename T, bool TRIANGLE, bool UNFOLDED>
+static void within_launch(bvhgpu_tree* t, const TravNode<T>* nodes, uint32_t n_trav, const T* points_dev, const T* max_dist_dev, size_t n, bool sorted,
+                          bool count_only, bvhgpu_hits* h) {
+    bvhgpu_ctx* ctx = t->ctx;
+    hipStream_t st = ctx->stream;
+    const T* aabbs = t->aabbs.as<T>();
+    const T* tris = t->tris.as<T>();
+    const uint32_t n32 = (uint32_t)n;
+    const dim3 pgrid((unsigned)((n + 255) / 256)), block(256);
+    const uint32_t nb = (uint32_t)((n + WITHIN_SCAN_BLOCK - 1) / WITHIN_SCAN_BLOCK);
+    const bool rows_sorted = sorted && !count_only;
+    h->ah_counts.reserve(n * 4);
+    h->ah_sums.reserve(sizeof(WithinMeta) + (size_t)nb * sizeof(unsigned long long));
+    if (rows_sorted) h->ah_work.reserve(n * 4);
+    WithinMeta* meta = h->ah_sums.as<WithinMeta>();
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(meta + 1);
+    uint32_t* counts = h->ah_counts.as<uint32_t>();
+    uint32_t* offsets = h->offsets.as<uint32_t>();
+    BVH_HIP(hipMemsetAsync(meta, 0, sizeof(WithinMeta), st));
+    hipLaunchKernelGGL((k_within_count<T, TRIANGLE, UNFOLDED>), pgrid, block, 0, st, nodes, n_trav, aabbs, tris, points_dev, max_dist_dev, n32, counts);
+    hipLaunchKernelGGL(k_within_block_sums, dim3(nb), block, 0, st, counts, n32, sums, meta, h->ah_work.as<uint32_t>(),
+                       rows_sorted ? WITHIN_LANE_ROW_MAX : 0u, WITHIN_LDS_ROW_MAX);
+    hipLaunchKernelGGL(k_within_scan_sums, dim3(1), block, 0, st, sums, nb, meta);
+    BVH_HIP(hipGetLastError());
+    WithinMeta* got = static_cast<WithinMeta*>(ctx->pinned);
+    BVH_HIP(hipMemcpyAsync(got, meta, sizeof(WithinMeta), hipMemcpyDeviceToHost, st));
+    BVH_HIP(hipStreamSynchronize(st));
+    const unsigned long long total = got->total;
+    const uint32_t n_long = got->n_long, n_beyond = got->n_beyond_lds;
+    if (total > 0xFFFFFFFFull) throw HipFail{hipErrorInvalidValue, nullptr, __LINE__, Fail::Overflow};
+    if (total == 0) {   // every row is empty
+        BVH_HIP(hipMemsetAsync(offsets, 0, (n + 1) * 4, st));
+        return;
+    }
+    hipLaunchKernelGGL(k_within_scan_final, dim3(nb), block, 0, st, counts, n32, sums, meta, offsets);
+    if (!count_only) {
+        h->indices.reserve((size_t)total * 4);
+        h->ah_vals.reserve((size_t)total * sizeof(T));
+        uint32_t* pos = nullptr;
+        if (n_beyond) { h->ah_pos.reserve((size_t)total * 4); pos = h->ah_pos.as<uint32_t>(); }
+        uint32_t* shape = h->indices.as<uint32_t>();
+        T* dist = h->ah_vals.as<T>();
+        if (sorted) hipLaunchKernelGGL((k_within_fill<T, TRIANGLE, UNFOLDED, true>), pgrid, block, 0, st, nodes, n_trav, aabbs, tris, points_dev, max_dist_dev, n32,
+                                       offsets, shape, dist, pos);
+        else hipLaunchKernelGGL((k_within_fill<T, TRIANGLE, UNFOLDED, false>), pgrid, block, 0, st, nodes, n_trav, aabbs, tris, points_dev, max_dist_dev, n32,
+                                offsets, shape, dist, pos);
+        if (sorted && n_long)
+            hipLaunchKernelGGL((k_within_sort_row<T>), dim3(n_long), dim3(WITHIN_SORT_THREADS), 0, st, h->ah_work.as<uint32_t>(), offsets, shape, dist, pos);
+    }
+    BVH_HIP(hipGetLastError());
+    h->total = total;
+}
+
+template <typename T>
+void within_batch(bvhgpu_tree* t, const T* points_dev, const T* max_dist_dev, size_t n, int kind, unsigned flags, bvhgpu_hits* h) {
+    bvhgpu_ctx* ctx = t->ctx;
+    hipStream_t st = ctx->stream;
+    const bool count_only = (flags & BVHGPU_WITHIN_COUNT_ONLY) != 0;
+    const bool sorted = (flags & BVHGPU_WITHIN_LIST_ORDER) == 0;
+    const bool mirror = t->exact_only && t->built && !t->unfolded && t->n >= 2;   // (see "Which array is walked" at the top)
+    const bool unfolded = t->unfolded || t->n == 1 || mirror;   // a single-shape tree has one (leaf) entry and no navigator
+    // the result object becomes an (empty) within result first: whatever fails below leaves it consistent
+    h->ctx = ctx; h->dtype = Traits<T>::dtype; h->flags = TRAVERSE_WITHIN; h->ah_leaf = 0; h->wi_count_only = count_only; h->n_rays = 0; h->total = 0;
+    h->stats = bvhgpu_traverse_stats{0, 0, 0, 0, 0};
+    h->pend_tree = nullptr; h->pend_rays = nullptr; h->pend_async = false;
+    h->pend_wide = false; h->pend_staged = false; h->pend_rec8 = false; h->pend_guide = false; h->pend_qwide = false;
+    char name[112];
+    const char* tri = kind == 1 ? "true" : "false";
+    const char* unf = unfolded ? "true" : "false";
+    if (count_only) std::snprintf(name, sizeof name, "bvhgpu::k_within_count<%s, %s, %s>", walk_type_name<T>(), tri, unf);
+    else std::snprintf(name, sizeof name, "bvhgpu::k_within_fill<%s, %s, %s, %s>", walk_type_name<T>(), tri, unf, sorted ? "true" : "false");
+    h->walk_kernel = name;
+    h->offsets.reserve((n + 1) * 4);   // (behind the flags: a reserve that throws leaves an empty within result, never the old kind's flags over a new buffer)
+    BVH_HIP(hipMemsetAsync(h->offsets.p, 0, 4, st));
+    if (n == 0 || t->n == 0) {   // no points, or an empty hierarchy: every row is empty
+        BVH_HIP(hipMemsetAsync(h->offsets.p, 0, (n + 1) * 4, st));
+    } else {
+        ensure_flat_arrays(t);
+        const TravNode<T>* nodes = t->trav.as<TravNode<T>>();
+        uint32_t n_trav = (uint32_t)t->n_trav;
+        if (mirror) {
+            n_trav = (uint32_t)t->n_flat;
+            h->wi_unfold.reserve((size_t)n_trav * sizeof(TravNode<T>));
+            hipLaunchKernelGGL((k_within_unfold<T>), dim3((n_trav + 255) / 256), dim3(256), 0, st, t->flat.as<typename Traits<T>::Flat>(), n_trav,
+                               h->wi_unfold.as<TravNode<T>>());
+            BVH_HIP(hipGetLastError());
+            nodes = h->wi_unfold.as<TravNode<T>>();
+        }
+        if (kind == 1) { if (unfolded) within_launch<T, true, true>(t, nodes, n_trav, points_dev, max_dist_dev, n, sorted, count_only, h);
+                         else within_launch<T, true, false>(t, nodes, n_trav, points_dev, max_dist_dev, n, sorted, count_only, h); }
+        else { if (unfolded) within_launch<T, false, true>(t, nodes, n_trav, points_dev, max_dist_dev, n, sorted, count_only, h);
+               else within_launch<T, false, false>(t, nodes, n_trav, points_dev, max_dist_dev, n, sorted, count_only, h); }
+    }
+    BVH_HIP(hipStreamSynchronize(st));   // the result is complete when the call returns
+    h->n_rays = n;
+    h->stats.hits = h->total;
+}
+template void within_batch<float>(bvhgpu_tree*, const float*, const float*, size_t, int, unsigned, bvhgpu_hits*);
+template void within_batch<double>(bvhgpu_tree*, const double*, const double*, size_t, int, unsigned, bvhgpu_hits*);
+
+}  // namespace bvhgpu

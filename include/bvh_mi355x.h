@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define BVHGPU_ABI_VERSION 7 /* 7: bvhgpu_host_alloc/free/register/unregister, bvhgpu_traverse_host_*, bvhgpu_build_traverse_host_*, bvhgpu_traverse_host_indices, bvhgpu_query_f32/_f64 + BVHGPU_QUERY_AABB/_POINT/_BALL, bvhgpu_traverse_any_f32/_f64 + bvhgpu_hits_fetch_any, bvhgpu_traverse_box_f32/_f64 + bvhgpu_hits_fetch_box + BVHGPU_TRAVERSE_FIRST, bvhgpu_tree_set_spheres_f32/_f64 + bvhgpu_traverse_sphere_f32/_f64 + bvhgpu_hits_fetch_sphere, bvhgpu_knearest_f32/_f64 + BVHGPU_KNN_MAX_K, BVHGPU_TUNE_COUNT 23 (slots 17 = HOST_CHUNKS, 18 = WIDE_MIN_RAYS_PER_WG, 19 = HOST_ZERO_COPY, 20 = BUILD_LEVEL_TILE, 21 = FLATTEN_INLINE, 22 = QUERY_VARIANT).  6: BVHGPU_TUNE_COUNT 17 (slots 15 = FLATTEN_LAZY, 16 = BUILD_LEVEL_PERSIST), bvhgpu_hits_walk_kernel.  5: bvhgpu_rccl_info.  4: BVHGPU_TUNE_COUNT 15 (slot 14 = WIDE_F64_GUIDE), bvhgpu_hits_walk_info.  3: BVHGPU_REBROADCAST, broadcast status header, scene blob BVH6 (exact_only), BVHGPU_TUNE_COUNT 14 (slots 11 = WIDE_EARLY_ITEMS, 12 = WIDE_STAGE_SHIFT, 13 = WIDE_REC8), BVHGPU_TRAVERSE_RAYS_READY, bvhgpu_device_alloc/free/copy */
+#define BVHGPU_ABI_VERSION 7 /* 7: bvhgpu_host_alloc/free/register/unregister, bvhgpu_traverse_host_*, bvhgpu_build_traverse_host_*, bvhgpu_traverse_host_indices, bvhgpu_query_f32/_f64 + BVHGPU_QUERY_AABB/_POINT/_BALL, bvhgpu_traverse_any_f32/_f64 + bvhgpu_hits_fetch_any, bvhgpu_traverse_box_f32/_f64 + bvhgpu_hits_fetch_box + BVHGPU_TRAVERSE_FIRST, bvhgpu_tree_set_spheres_f32/_f64 + bvhgpu_traverse_sphere_f32/_f64 + bvhgpu_hits_fetch_sphere, bvhgpu_knearest_f32/_f64 + BVHGPU_KNN_MAX_K, bvhgpu_within_f32/_f64 + bvhgpu_hits_fetch_within + BVHGPU_WITHIN_LIST_ORDER / _COUNT_ONLY (symbols only: the ABI stays 7), BVHGPU_TUNE_COUNT 23 (slots 17 = HOST_CHUNKS, 18 = WIDE_MIN_RAYS_PER_WG, 19 = HOST_ZERO_COPY, 20 = BUILD_LEVEL_TILE, 21 = FLATTEN_INLINE, 22 = QUERY_VARIANT).  6: BVHGPU_TUNE_COUNT 17 (slots 15 = FLATTEN_LAZY, 16 = BUILD_LEVEL_PERSIST), bvhgpu_hits_walk_kernel.  5: bvhgpu_rccl_info.  4: BVHGPU_TUNE_COUNT 15 (slot 14 = WIDE_F64_GUIDE), bvhgpu_hits_walk_info.  3: BVHGPU_REBROADCAST, broadcast status header, scene blob BVH6 (exact_only), BVHGPU_TUNE_COUNT 14 (slots 11 = WIDE_EARLY_ITEMS, 12 = WIDE_STAGE_SHIFT, 13 = WIDE_REC8), BVHGPU_TRAVERSE_RAYS_READY, bvhgpu_device_alloc/free/copy */
 #define BVHGPU_NONE 0xFFFFFFFFu /* u32::MAX marker (flat_bvh.rs:51-53, :124, :137) */
 
 typedef enum {
@@ -613,7 +613,7 @@ int bvhgpu_traverse_khits_f64(bvhgpu_tree *tree, const bvhgpu_ray_f64 *rays, con
  * result object of any kind, whose buffers are then reused.  bvhgpu_hits_info gives n_rays and total, the number of candidates;
  * stats.hits == total and the other stats are 0.  bvhgpu_hits_wait returns BVHGPU_OK, bvhgpu_hits_walk_info gives 0,
  * bvhgpu_hits_walk_kernel names the fill kernel.  _fetch / _fetch_triangles / _fetch_closest / _fetch_any / _fetch_box / _fetch_sphere /
- * _device return BVHGPU_INVALID_ARG on such a result, and bvhgpu_hits_fetch_allhits on any other.
+ * _fetch_within / _device return BVHGPU_INVALID_ARG on such a result, and bvhgpu_hits_fetch_allhits on any other.
  * Refused, touching no buffer and leaving *hits as it was, in this order: a NULL tree or a NULL `hits`; what the settle of the tree's
  * asynchronous build returns; a result object that still holds an asynchronous batch; a tree of another dtype (BVHGPU_DTYPE_MISMATCH);
  * a tree that is not flattened (BVHGPU_NOT_FLATTENED); a NULL `rays` with n_rays > 0, a `mem` that is neither BVHGPU_HOST nor
@@ -626,6 +626,64 @@ int bvhgpu_traverse_allhits_f32(bvhgpu_tree *tree, const bvhgpu_ray_f32 *rays, c
 int bvhgpu_traverse_allhits_f64(bvhgpu_tree *tree, const bvhgpu_ray_f64 *rays, const double *tmax, size_t n_rays, int mem, int leaf, unsigned flags,
                                 bvhgpu_hits **hits);
 int bvhgpu_hits_fetch_allhits(bvhgpu_hits *hits, uint32_t *offsets, uint32_t *shape, void *vals, int mem);
+
+/* ---- radius search: EVERY shape within max_dist of every query point, in order, as a CSR — normals and density estimation on point
+ * clouds, DBSCAN, contact candidates with real triangle distances, "everything within r of this probe" — without cutting rows at
+ * BVHGPU_KNN_MAX_K and without fetching the ball query's CSR and computing, filtering and sorting distances on the host.  The unbounded
+ * form of bvhgpu_knearest_tree_*'s max_dist.
+ * Definition: the loop of nearest_to over the FlatNode array (flat_bvh.rs:524-558) with the moving `best_dist` replaced by a fixed limit.
+ * Point p_i has m = max_dist[i] in the tree's dtype T; r2 = m * m is one multiplication in T.  A negative or NaN m gives an empty row
+ * without a walk.
+ *   i = 0
+ *   while i < len(flat):
+ *     non-leaf entry: md = aabb.min_distance_squared(p);  i = (md <= r2) ? entry_index : exit_index
+ *     leaf entry:     d  = shape.distance_squared(p);     if d <= r2: candidate (d, shape);  i = exit_index
+ *  - shape.distance_squared is `kind` 0, the shape's own Aabb::min_distance_squared, or `kind` 1, the triangle (needs
+ *    bvhgpu_tree_set_triangles): the device functions of bvhgpu_knearest_*, so the bits are the same.  Every comparison is T's <= as
+ *    written, so the limit itself is inside.  m = 0 keeps the shapes at distance 0.  m = +inf keeps every shape whose distance is not NaN.
+ *    A NaN d is never a candidate, so a candidate's key is never NaN and the sorted order below is a total order.
+ *  - NaN and infinite point coordinates.  Aabb::min_distance_squared ends every axis with max(0), which turns NaN into 0: a NaN
+ *    coordinate adds 0 on its axis to every box distance (an all-NaN point is at distance 0 of every box).  An infinite coordinate gives
+ *    +inf against a finite box, which only m = +inf admits.  The triangle distance has no such guard: such points give it NaN or +inf.
+ *  - Row i, default.  All candidates in a stable ascending sort by d.  Equal d stay in the order the loop met them (leaf pre-order).  The
+ *    output distance is sqrt(d), as in the k-nearest rows.
+ *  - Row i with BVHGPU_WITHIN_LIST_ORDER.  The candidates in the order the loop met them, with no sort pass.  Where every operation is
+ *    exact, kind 0 gives exactly the shapes and order of bvhgpu_query_*'s BVHGPU_QUERY_BALL row.
+ *  - BVHGPU_WITHIN_COUNT_ONLY.  Only `offsets` is produced (neighbour counts); `total` is still reported; shape and dist are empty.
+ *  - Walk-independence.  The threshold never moves, so the candidate set is "every box on the shape's path passes md <= r2 and the shape
+ *    passes d <= r2", whatever order a walk visits nodes in.  The boxes of the non-leaf entries are the child boxes of the BvhNode array,
+ *    so for a row no longer than k, bvhgpu_knearest_tree_*(k, max_dist) holds the same candidates with bit-equal distances; only the order
+ *    inside a group of equal distances may differ.
+ *  - Output.  offsets[n + 1] holds the exclusive prefix sums of the row lengths, as u32; offsets[n] == total.  shape[total] holds the
+ *    shape indices, as u32.  dist[total] holds the distances, as T.  There is no padding anywhere.
+ *  - Trees.  Every tree bvhgpu_knearest_* accepts: built here, refitted, an uploaded FlatBvh, scene-imported, trees with empty child
+ *    bounds, one shape, and no shapes (all offsets 0).  One caveat: a tree whose build had a split without SAH winner (empty child
+ *    bounds) and that arrived by scene import or broadcast carries the folded traversal array only, in which a leaf's navigator box —
+ *    empty below such a split, at distance 0 of every point — is replaced by the shape's own box.  With kind 0 the rows are the
+ *    definition's all the same.  With kind 1 a row can lack a triangle whose distance is within the limit while its box's distance,
+ *    by rounding, is not (a query on a triangle vertex with max_dist 0).  Trees built, rebuilt or refitted here and uploaded FlatBvhs
+ *    have no such case.
+ *  - Limits.  n < 2^32 - 1 and total <= 2^32 - 1, else BVHGPU_OVERFLOW.  The total is summed in 64 bits and checked before anything is
+ *    sized by it.
+ * The call is synchronous: the result object is complete on return, for BVHGPU_HOST and BVHGPU_DEVICE points alike (`mem` applies to
+ * `points` and `max_dist`).  *hits may be NULL or a result object of any kind, whose buffers are then reused.  bvhgpu_hits_info gives n
+ * and total; stats.hits == total and the other stats are 0.  bvhgpu_hits_wait returns BVHGPU_OK, bvhgpu_hits_walk_info gives 0,
+ * bvhgpu_hits_walk_kernel names the fill kernel (the count kernel of a COUNT_ONLY batch).  _fetch / _fetch_triangles / _fetch_closest /
+ * _fetch_any / _fetch_box / _fetch_sphere / _fetch_allhits / _device return BVHGPU_INVALID_ARG on such a result, and
+ * bvhgpu_hits_fetch_within on any other.
+ * Refused, touching no buffer and leaving *hits as it was, in this order: a NULL tree or a NULL `hits`; what the settle of the tree's
+ * asynchronous build returns; a result object that still holds an asynchronous batch; a tree of another dtype (BVHGPU_DTYPE_MISMATCH);
+ * a tree that is not flattened (BVHGPU_NOT_FLATTENED); a NULL `points` or a NULL `max_dist` with n > 0, a `mem` that is neither
+ * BVHGPU_HOST nor BVHGPU_DEVICE, a `kind` other than 0 / 1, a flag bit other than the two below, triangles that were not set for kind 1
+ * (BVHGPU_INVALID_ARG); n >= 2^32-1 (BVHGPU_OVERFLOW).
+ * bvhgpu_hits_fetch_within: offsets (n + 1 u32), shape (total u32) and dist (total T) copied to `mem`; each may be NULL. */
+#define BVHGPU_WITHIN_LIST_ORDER 1u /* rows in the order the loop met the candidates instead of ascending distance */
+#define BVHGPU_WITHIN_COUNT_ONLY 2u /* offsets (neighbour counts) and the total only */
+int bvhgpu_within_f32(bvhgpu_tree *tree, const float *points, const float *max_dist, size_t n, int mem, int kind, unsigned flags,
+                      bvhgpu_hits **hits);
+int bvhgpu_within_f64(bvhgpu_tree *tree, const double *points, const double *max_dist, size_t n, int mem, int kind, unsigned flags,
+                      bvhgpu_hits **hits);
+int bvhgpu_hits_fetch_within(bvhgpu_hits *hits, uint32_t *offsets, uint32_t *shape, void *dist, int mem);
 
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */

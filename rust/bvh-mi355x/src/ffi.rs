@@ -8,6 +8,8 @@ pub const BVHGPU_NONE: u32 = u32::MAX; // flat_bvh.rs:51-53
 pub const BVHGPU_KNN_MAX_K: u32 = 64; // largest k of bvhgpu_knearest_*
 pub const BVHGPU_KHITS_MAX_K: u32 = 64; // largest k of bvhgpu_traverse_khits_*
 pub const BVHGPU_ALLHITS_LIST_ORDER: c_uint = 1; // bvhgpu_traverse_allhits_*: rows in list order, no sort pass
+pub const BVHGPU_WITHIN_LIST_ORDER: c_uint = 1; // bvhgpu_within_*: rows in the order the loop met the candidates, no sort pass
+pub const BVHGPU_WITHIN_COUNT_ONLY: c_uint = 2; // bvhgpu_within_*: offsets (neighbour counts) and the total only
 pub const BVHGPU_LEAF_BOX: c_int = 0; // leaf stage of bvhgpu_traverse_khits_*: {enter, exit} on the shape's own AABB
 pub const BVHGPU_LEAF_TRIANGLE: c_int = 1; // ... Intersection{distance, u, v} (needs the triangles)
 pub const BVHGPU_LEAF_SPHERE: c_int = 2; // ... {distance, exit} (needs the spheres)
@@ -197,6 +199,10 @@ extern "C" {
     pub fn bvhgpu_traverse_allhits_f32(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, leaf: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_traverse_allhits_f64(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, leaf: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_hits_fetch_allhits(h: *mut bvhgpu_hits, offsets: *mut u32, shape: *mut u32, vals: *mut c_void, mem: c_int) -> c_int;
+    // every shape within max_dist[i] of point i as a CSR (offsets: n + 1, shape: total, dist: total; no padding; rows in ascending distance, or in the loop's order with BVHGPU_WITHIN_LIST_ORDER; offsets only with BVHGPU_WITHIN_COUNT_ONLY)
+    pub fn bvhgpu_within_f32(t: *mut bvhgpu_tree, points: *const f32, max_dist: *const f32, n: usize, mem: c_int, kind: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_within_f64(t: *mut bvhgpu_tree, points: *const f64, max_dist: *const f64, n: usize, mem: c_int, kind: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_hits_fetch_within(h: *mut bvhgpu_hits, offsets: *mut u32, shape: *mut u32, dist: *mut c_void, mem: c_int) -> c_int;
     pub fn bvhgpu_tree_set_spheres_f32(t: *mut bvhgpu_tree, spheres: *const f32, n: usize, mem: c_int) -> c_int;
     pub fn bvhgpu_tree_set_spheres_f64(t: *mut bvhgpu_tree, spheres: *const f64, n: usize, mem: c_int) -> c_int;
     pub fn bvhgpu_traverse_sphere_f32(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;

@@ -103,6 +103,8 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
     unsafe fn traverse_khits(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, leaf: c_int, k: u32, out_shape: *mut u32, out_vals: *mut Self) -> c_int;
     #[allow(clippy::too_many_arguments)]
     unsafe fn traverse_allhits(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, leaf: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
+    #[allow(clippy::too_many_arguments)]
+    unsafe fn within(t: *mut ffi::bvhgpu_tree, points: *const Self, max_dist: *const Self, n: usize, mem: c_int, kind: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
 
     fn node_to_crate(raw: &Self::Node) -> BvhNode<Self, 3>;
     fn flat_to_crate(raw: &Self::Flat) -> FlatNode<Self, 3>;
@@ -112,7 +114,7 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
 
 macro_rules! impl_gpu_scalar {
     ($t:ty, $dtype:expr, $node:ident, $flat:ident, $ray:ident, $build_flat:ident, $rebuild_flat:ident, $refit:ident, $traverse:ident,
-     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $traverse_box:ident, $set_spheres:ident, $traverse_sphere:ident, $knearest:ident, $knearest_tree:ident, $traverse_khits:ident, $traverse_allhits:ident,
+     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $traverse_box:ident, $set_spheres:ident, $traverse_sphere:ident, $knearest:ident, $knearest_tree:ident, $traverse_khits:ident, $traverse_allhits:ident, $within:ident,
      $flat_ctor:expr) => {
         impl GpuScalar for $t {
             type Node = ffi::$node;
@@ -173,6 +175,9 @@ macro_rules! impl_gpu_scalar {
             unsafe fn traverse_allhits(t: *mut ffi::bvhgpu_tree, rays: *const ffi::$ray, tmax: *const $t, n: usize, mem: c_int, leaf: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int {
                 ffi::$traverse_allhits(t, rays, tmax, n, mem, leaf, flags, hits)
             }
+            unsafe fn within(t: *mut ffi::bvhgpu_tree, points: *const $t, max_dist: *const $t, n: usize, mem: c_int, kind: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int {
+                ffi::$within(t, points, max_dist, n, mem, kind, flags, hits)
+            }
             fn node_to_crate(r: &ffi::$node) -> BvhNode<$t, 3> {
                 if r.shape != ffi::BVHGPU_NONE {
                     BvhNode::Leaf { parent_index: r.parent as usize, shape_index: r.shape as usize }
@@ -211,11 +216,11 @@ macro_rules! impl_gpu_scalar {
 }
 impl_gpu_scalar!(f32, ffi::BVHGPU_F32, bvhgpu_node_f32, bvhgpu_flat_f32, bvhgpu_ray_f32, bvhgpu_build_flat_f32, bvhgpu_rebuild_flat_f32,
                  bvhgpu_refit_f32, bvhgpu_traverse_f32, bvhgpu_tree_set_triangles_f32, bvhgpu_tree_from_flat_f32,
-                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_traverse_box_f32, bvhgpu_tree_set_spheres_f32, bvhgpu_traverse_sphere_f32, bvhgpu_knearest_f32, bvhgpu_knearest_tree_f32, bvhgpu_traverse_khits_f32, bvhgpu_traverse_allhits_f32,
+                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_traverse_box_f32, bvhgpu_tree_set_spheres_f32, bvhgpu_traverse_sphere_f32, bvhgpu_knearest_f32, bvhgpu_knearest_tree_f32, bvhgpu_traverse_khits_f32, bvhgpu_traverse_allhits_f32, bvhgpu_within_f32,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f32 { min, max, entry, exit, shape });
 impl_gpu_scalar!(f64, ffi::BVHGPU_F64, bvhgpu_node_f64, bvhgpu_flat_f64, bvhgpu_ray_f64, bvhgpu_build_flat_f64, bvhgpu_rebuild_flat_f64,
                  bvhgpu_refit_f64, bvhgpu_traverse_f64, bvhgpu_tree_set_triangles_f64, bvhgpu_tree_from_flat_f64,
-                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_traverse_box_f64, bvhgpu_tree_set_spheres_f64, bvhgpu_traverse_sphere_f64, bvhgpu_knearest_f64, bvhgpu_knearest_tree_f64, bvhgpu_traverse_khits_f64, bvhgpu_traverse_allhits_f64,
+                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_traverse_box_f64, bvhgpu_tree_set_spheres_f64, bvhgpu_traverse_sphere_f64, bvhgpu_knearest_f64, bvhgpu_knearest_tree_f64, bvhgpu_traverse_khits_f64, bvhgpu_traverse_allhits_f64, bvhgpu_within_f64,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f64 { min, max, entry, exit, shape, _pad: 0 });
 
 fn aabb_to_6<T: GpuScalar>(b: &Aabb<T, 3>) -> [T; 6] {
@@ -630,6 +635,34 @@ impl<T: GpuScalar> GpuBvh<T> {
             ffi::bvhgpu_hits_destroy(hits);
         }
         (offsets, shape, vals)
+    }
+
+    /// EVERY shape within `max_dist[i]` of point i, as a CSR (`bvhgpu_within_*`): the loop of `FlatBvh::nearest_to` (src/flat_bvh.rs:524-558)
+    /// with the moving `best_dist` replaced by the fixed limit `max_dist[i]^2` and every comparison `<=`, so the limit itself is inside; a
+    /// negative or NaN limit gives an empty row.  Rows are in a stable ascending sort by distance — equal distances in leaf pre-order — or,
+    /// with `sort: false` (`ffi::BVHGPU_WITHIN_LIST_ORDER`), in the order the loop met the shapes.  `triangles`: closest point on the
+    /// triangle (needs `set_triangles`) instead of the shape's own AABB.  Returns `(offsets, shape, dist)`: `points.len() + 1` exclusive
+    /// prefix sums of the row lengths, `total` shape indices and `total` distances (not squared), with no padding.  `count_only`
+    /// (`ffi::BVHGPU_WITHIN_COUNT_ONLY`): the offsets alone, `shape` and `dist` stay empty.
+    pub fn within_distance(&self, points: &[[T; 3]], max_dist: &[T], triangles: bool, sort: bool, count_only: bool) -> (Vec<u32>, Vec<u32>, Vec<T>) {
+        assert_eq!(max_dist.len(), points.len(), "one max_dist per point");
+        let mut hits = core::ptr::null_mut();
+        let flags = (if sort { 0 } else { ffi::BVHGPU_WITHIN_LIST_ORDER }) | (if count_only { ffi::BVHGPU_WITHIN_COUNT_ONLY } else { 0 });
+        let mut offsets = vec![0u32; points.len() + 1];
+        let (mut shape, mut dist) = (Vec::new(), Vec::new());
+        unsafe {
+            check(self.ctx, T::within(self.tree, points.as_ptr().cast(), max_dist.as_ptr(), points.len(), ffi::BVHGPU_HOST, triangles as c_int,
+                                      flags, &mut hits));
+            let mut total = 0u64;
+            check(self.ctx, ffi::bvhgpu_hits_info(hits, core::ptr::null_mut(), &mut total, core::ptr::null_mut()));
+            if !count_only {
+                shape.resize(total as usize, 0u32);
+                dist.resize(total as usize, T::default());
+            }
+            check(self.ctx, ffi::bvhgpu_hits_fetch_within(hits, offsets.as_mut_ptr(), shape.as_mut_ptr(), dist.as_mut_ptr() as *mut c_void, ffi::BVHGPU_HOST));
+            ffi::bvhgpu_hits_destroy(hits);
+        }
+        (offsets, shape, dist)
     }
 
     /// The `k` nearest shapes of every point (`bvhgpu_knearest_*`): the loop of `FlatBvh::nearest_to` (src/flat_bvh.rs:524-558) with a list of

@@ -16,20 +16,12 @@
 // list lives in LDS, dynamic size block x k x (sizeof(T) + 4) bytes from the ACTUAL k, slot-major: slot j of lane l is element j x block + l
 // of two arrays (distances, then shapes).  A wave's access to one slot is 64 consecutive 4-byte (8-byte) words: conflict-free under both LDS
 // banking rules.  A lane only ever touches its own column, so the kernel has no barrier.
-// Block size (knn_block): the largest of 256 / 128 / 64 lanes whose lists fit 32 KB, so that several workgroups share a CU's LDS;
-// 64 lanes above that (k = 64 in f64: 48 KB, inside the 64 KB a workgroup gets without attributes).
+// Block size: walk.hpp's topk_block.
 #include "point_dist.hpp"
 
 namespace bvhgpu {
 
-static_assert(BVHGPU_KNN_MAX_K * 64u * (sizeof(double) + 4u) <= 64u * 1024u, "the k-nearest lists of 64 lanes must fit a workgroup's LDS");
-
-template <typename T> static unsigned knn_block(uint32_t k) {
-    const size_t per_lane = (size_t)k * (sizeof(T) + 4);
-    if (256 * per_lane <= 32 * 1024) return 256;
-    if (128 * per_lane <= 32 * 1024) return 128;
-    return 64;
-}
+static_assert(topk_fits(BVHGPU_KNN_MAX_K), "the k-nearest lists of 64 lanes must fit a workgroup's LDS");
 
 template <typename T, bool TRIANGLE, bool UNFOLDED>
 __global__ __launch_bounds__(256) void k_knearest(const TravNode<T>* __restrict__ nodes, uint32_t n_trav,
@@ -130,7 +122,7 @@ void knearest_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uin
         BVH_HIP(hipGetLastError());
         return;
     }
-    const unsigned bs = knn_block<T>(k);
+    const unsigned bs = topk_block<T>(k);
     const dim3 grid((unsigned)((n + bs - 1) / bs)), block(bs);
     const size_t lds = (size_t)bs * k * (sizeof(T) + 4);
     ensure_flat_arrays(t);

@@ -23,20 +23,15 @@
 // coming back from child c it computes the same two distances again — same inputs, same bits, same order — and tests the second child if
 // c was the first, otherwise goes further up; it ends when it comes back to node 0 with nothing left.  A step is one record load and two
 // aabb_min_dist2 (point_dist.hpp, unchanged: the oracle's bits).  len / bound / full / has_nan live in registers, r2 and m >= 0 are
-// evaluated once per lane.  The list is knn.hip's: dynamic LDS, block x k x (sizeof(T) + 4) bytes, slot-major, knn_block's block sizes,
-// no barrier.  The insertion below is a copy of k_knearest's: moving it into a shared header changed k_knearest's instruction text.
+// evaluated once per lane.  The list is knn.hip's: dynamic LDS, block x k x (sizeof(T) + 4) bytes, slot-major, topk_block's block sizes,
+// no barrier.  The insertion below is a copy of k_knearest's (k_ray_khits holds a third, without the NaN branch).  Sharing it has been tried
+// twice; the second time as a __forceinline__ template taking ld, ls, block, k and references to len / full / has_nan / bound: it changed
+// the instruction text of 17 of the 22 kernels that hold the insertion and the register counts of several, so it stays restated.
 #include "point_dist.hpp"
 
 namespace bvhgpu {
 
-static_assert(BVHGPU_KNN_MAX_K * 64u * (sizeof(double) + 4u) <= 64u * 1024u, "the k-nearest lists of 64 lanes must fit a workgroup's LDS");
-
-template <typename T> static unsigned knn_tree_block(uint32_t k) {   // = knn.hip's knn_block
-    const size_t per_lane = (size_t)k * (sizeof(T) + 4);
-    if (256 * per_lane <= 32 * 1024) return 256;
-    if (128 * per_lane <= 32 * 1024) return 128;
-    return 64;
-}
+static_assert(topk_fits(BVHGPU_KNN_MAX_K), "the k-nearest lists of 64 lanes must fit a workgroup's LDS");
 
 // ---- record fetch: four (f32) / seven (f64) 16-byte loads per lane; the records are 16-byte aligned (64 B / 112 B in a hipMalloc'ed array)
 template <typename T> struct TreeRegs { T lmn[3], lmx[3], rmn[3], rmx[3]; uint32_t parent, l, r, shape; };
@@ -166,7 +161,7 @@ void knearest_tree_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind
     if (!n) return;
     using Node = typename Traits<T>::Node;
     hipStream_t st = t->ctx->stream;
-    const unsigned bs = knn_tree_block<T>(k);
+    const unsigned bs = topk_block<T>(k);
     const dim3 grid((unsigned)((n + bs - 1) / bs)), block(bs);
     const size_t lds = (size_t)bs * k * (sizeof(T) + 4);
     const uint32_t n_nodes = t->n ? (uint32_t)t->n_nodes : 0u;

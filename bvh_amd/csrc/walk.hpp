@@ -167,6 +167,39 @@ __device__ __forceinline__ void ray_sphere(const T o[3], const T d[3], const T* 
     if (t > Traits<T>::eps()) { out[0] = t; out[1] = t1; }
 }
 
+// ---- the leaf stage of the row queries: the record of shape s for the ray, whose first scalar is its DISTANCE.  prims is t->aabbs
+//      (n x 6), t->tris (n x 9) or t->spheres (n x 4) by LEAF; W scalars of out[] make the record.  allhits.hip uses it; khits.hip still
+//      carries its own copy (khits_record, KH_*), the same text, which is to be replaced by this one.
+enum : int { LEAF_BOX = BVHGPU_LEAF_BOX, LEAF_TRIANGLE = BVHGPU_LEAF_TRIANGLE, LEAF_SPHERE = BVHGPU_LEAF_SPHERE };
+template <int LEAF> struct LeafVals { static constexpr uint32_t W = LEAF == LEAF_TRIANGLE ? 3u : 2u; };
+template <typename T, int LEAF>
+__device__ __forceinline__ void leaf_record(const T o[3], const T d[3], const T inv[3], const T* __restrict__ prims, uint32_t s, T out[3]) {
+    out[2] = 0;
+    if (LEAF == LEAF_TRIANGLE) {
+        ray_triangle<T>(o, d, prims + 9 * (size_t)s, out);
+    } else if (LEAF == LEAF_SPHERE) {
+        ray_sphere<T>(o, d, prims + 4 * (size_t)s, out);
+    } else {
+        const T* b = prims + 6 * (size_t)s;
+        const T mn[3] = {b[0], b[1], b[2]}, mx[3] = {b[3], b[4], b[5]};
+        T t0, t1;
+        const bool hit = slab_hit<T>(o, inv, mn, mx, t0, t1);
+        out[0] = hit ? t0 : Traits<T>::inf(); out[1] = hit ? t1 : (T)0;
+    }
+}
+
+// ---- the per-lane top-k lists in LDS (knn.hip, knn_tree.hip; khits.hip still restates the rule as khits_block): k slots of (T key, u32
+//      shape) per lane.  Block size: the largest of 256 / 128 / 64 lanes whose lists fit 32 KB, so that several workgroups share a CU's
+//      LDS; 64 lanes above that (k = 64 in f64: 48 KB, inside the 64 KB a workgroup gets without attributes — topk_fits checks a family's
+//      largest k)
+template <typename T> inline unsigned topk_block(uint32_t k) {
+    const size_t per_lane = (size_t)k * (sizeof(T) + 4);
+    if (256 * per_lane <= 32 * 1024) return 256;
+    if (128 * per_lane <= 32 * 1024) return 128;
+    return 64;
+}
+constexpr bool topk_fits(uint32_t max_k) { return max_k * 64u * (sizeof(double) + 4u) <= 64u * 1024u; }   // the lists of 64 lanes fit a workgroup's LDS
+
 // ---- per-lane ray state
 template <typename T, int MODE> struct LaneRay {
     T o[3], inv[3];

@@ -23,23 +23,17 @@
 // path passes md <= r2 and the shape passes d <= r2".  Nearest-first descent buys nothing here; the 32 / 64-byte `trav` entries are the
 // array to walk.
 //
-// The schedule is allhits.hip's with a point in place of the ray; every walk is k_knearest's loop, one point per lane (within_walk):
+// The batch is rows.hip's schedule (count walk, scan, ONE host read, offsets, fill walk, a workgroup per long row) with a point per
+// lane; every walk is k_knearest's loop (within_walk), and no walk has a cross-lane operation.  What this family puts into it:
 //   k_within_count       counts[q] = the candidates of point q (lanes with a negative or NaN limit do not walk)
-//   k_within_block_sums  64-bit sum per block of WITHIN_SCAN_BLOCK counts; the points of a sorted batch whose rows are longer than
-//                        WITHIN_LANE_ROW_MAX are appended to the long-row worklist (any order), those above WITHIN_LDS_ROW_MAX counted
-//   k_within_scan_sums   exclusive scan of the block sums (one workgroup); the batch's 64-bit total
-//   ... ONE host read {total, long rows, rows beyond LDS}: BVHGPU_OVERFLOW before anything is sized by the total ...
-//   k_within_scan_final  offsets[q] = block base + exclusive scan inside the block, offsets[n] = total
-//   k_within_fill        walks again; lane q owns [offsets[q], offsets[q + 1]).  A row of a sorted batch up to WITHIN_LANE_ROW_MAX is built
-//                        by k_knearest's insertion (search from the back with the strict <: stable) on its own region — the key of
-//                        element e lives in dist[e] — and a final per-lane pass turns the keys into sqrt.  A LIST_ORDER row gets
-//                        (shape, sqrt(d)) appended as the walk meets them.  A longer row of a sorted batch gets (d, shape) appended in
-//                        list order (and its positions, beyond WITHIN_LDS_ROW_MAX) and is left to
-//   k_within_sort_row    one workgroup per long row: allhits.hip's all-ascending bitonic network on the keys (d, position) with the shape
-//                        as payload, in LDS up to WITHIN_LDS_ROW_MAX elements, in place in global memory beyond; then sqrt.
-// The three scan kernels restate allhits.hip's (the library is built without relocatable device code, and allhits.hip keeps its
-// instruction text), as knn_tree.hip restates knn.hip's insertion.  The row length is uniform per workgroup of k_within_sort_row: every
-// loop bound and every barrier there depends on it alone.  No walk has a cross-lane operation.
+//   k_within_fill        A row of a sorted batch up to WITHIN_LANE_ROW_MAX is built by k_knearest's insertion (search from the back with
+//                        the strict <: stable) on its own region — the key of element e lives in dist[e] — and a final per-lane pass
+//                        turns the keys into sqrt.  A LIST_ORDER row gets (shape, sqrt(d)) appended as the walk meets them.  A longer row
+//                        of a sorted batch gets (d, shape) appended in list order (and its positions, beyond WITHIN_LDS_ROW_MAX) and is
+//                        left to
+//   k_within_sort_row    rows_bitonic on the keys (d, position) with the shape as payload, in LDS up to WITHIN_LDS_ROW_MAX elements, in
+//                        place in global memory beyond; then sqrt.
+// The row length is uniform per workgroup of k_within_sort_row: every loop bound and every barrier there depends on it alone.
 //
 // Which array is walked.  `trav` folds a leaf's navigator entry and its leaf entry into one entry that carries the shape's own box: for
 // a tree built here that box is bit-identical to the navigator box — except below a split without SAH winner (t->exact_only), whose two
@@ -51,10 +45,11 @@
 #include <cstdio>
 
 #include "point_dist.hpp"
+#include "rows.hpp"
 
 namespace bvhgpu {
 
-// Thresholds: allhits.hip's values.  DESIGN.md §4i: on radius rows of about 20 and 200 a lane tier ending at 8 or at 128 is slower than
+// Thresholds (rows.hpp): allhits.hip's values.  DESIGN.md §4i: on radius rows of about 20 and 200 a lane tier ending at 8 or at 128 is slower than
 // 32; the LDS limit has not been varied (no measured row comes near it).  WITHIN_LANE_ROW_MAX: a lane's insertion into global memory costs up to len^2 / 2
 // element moves that no other lane of the wave shares.  WITHIN_LDS_ROW_MAX: 2048 x (8 + 4 + 4) bytes = 32 KB in f64, 24 KB in f32 — five
 // (six) workgroups share a CU's 160 KB of LDS.
@@ -66,14 +61,7 @@ namespace bvhgpu {
 #endif
 constexpr uint32_t WITHIN_LANE_ROW_MAX = BVH_WITHIN_LANE_ROW_MAX;
 constexpr uint32_t WITHIN_LDS_ROW_MAX = BVH_WITHIN_LDS_ROW_MAX;
-constexpr uint32_t WITHIN_SORT_THREADS = 256;
-constexpr uint32_t WITHIN_SCAN_ITEMS = 4;
-constexpr uint32_t WITHIN_SCAN_BLOCK = 256 * WITHIN_SCAN_ITEMS;   // counts per workgroup of the scan
-static_assert(WITHIN_LDS_ROW_MAX * (sizeof(double) + 8u) <= 64u * 1024u, "a row sorted in LDS must fit a workgroup's LDS");
-static_assert((WITHIN_LDS_ROW_MAX & (WITHIN_LDS_ROW_MAX - 1)) == 0, "the LDS tier pads a row to a power of two inside its arrays");
-
-// what the host reads between the scan and the fill (the first 16 bytes of the sums buffer)
-struct WithinMeta { unsigned long long total; uint32_t n_long, n_beyond_lds; };
+static_assert(rows_lds_row_max_ok(WITHIN_LDS_ROW_MAX), "a row sorted in LDS must fit a workgroup's LDS, padded to a power of two");
 
 template <typename T> struct WithinPoint {
     T p[3], r2;
@@ -143,85 +131,6 @@ __global__ __launch_bounds__(256) void k_within_count(const TravNode<T>* __restr
     counts[q] = cnt;
 }
 
-// ---- the scan of the counts (allhits.hip's three kernels, restated) -----------------------------------------------------------------
-// sums[b] = the counts of block b, in 64 bits; the long rows of a sorted batch (lane_max != 0) go to the worklist
-__global__ __launch_bounds__(256) void k_within_block_sums(const uint32_t* __restrict__ counts, uint32_t n, unsigned long long* __restrict__ sums,
-                                                           WithinMeta* __restrict__ meta, uint32_t* __restrict__ work, uint32_t lane_max, uint32_t lds_max) {
-    __shared__ unsigned long long part[256];
-    const uint32_t base = blockIdx.x * WITHIN_SCAN_BLOCK + threadIdx.x * WITHIN_SCAN_ITEMS;
-    unsigned long long s = 0;
-    for (uint32_t j = 0; j < WITHIN_SCAN_ITEMS; j++) {
-        const uint32_t q = base + j;
-        if (q < n) {   // (base + j cannot wrap: n < 2^32 - 1 and the grid covers n)
-            const uint32_t c = counts[q];
-            s += c;
-            if (lane_max != 0 && c > lane_max) {
-                work[atomicAdd(&meta->n_long, 1u)] = q;   // (at most n entries: one per point)
-                if (c > lds_max) atomicAdd(&meta->n_beyond_lds, 1u);
-            }
-        }
-    }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (uint32_t w = 128; w > 0; w >>= 1) {
-        if (threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sums[blockIdx.x] = part[0];
-}
-
-// one workgroup: sums[b] becomes the sum of the blocks in front of b; meta->total
-__global__ __launch_bounds__(256) void k_within_scan_sums(unsigned long long* __restrict__ sums, uint32_t nb, WithinMeta* __restrict__ meta) {
-    __shared__ unsigned long long part[256];
-    __shared__ unsigned long long carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (uint32_t b0 = 0; b0 < nb; b0 += 256) {   // (nb is uniform: every thread runs every barrier)
-        const uint32_t b = b0 + threadIdx.x;
-        const unsigned long long own = b < nb ? sums[b] : 0ull;
-        part[threadIdx.x] = own;
-        __syncthreads();
-        for (uint32_t w = 1; w < 256; w <<= 1) {
-            const unsigned long long add = threadIdx.x >= w ? part[threadIdx.x - w] : 0ull;
-            __syncthreads();
-            part[threadIdx.x] += add;
-            __syncthreads();
-        }
-        const unsigned long long carry = carry_s;
-        if (b < nb) sums[b] = carry + part[threadIdx.x] - own;
-        __syncthreads();
-        if (threadIdx.x == 255) carry_s = carry + part[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) meta->total = carry_s;
-}
-
-// offsets[q] for the block's counts (the host has checked that the total fits 32 bits)
-__global__ __launch_bounds__(256) void k_within_scan_final(const uint32_t* __restrict__ counts, uint32_t n, const unsigned long long* __restrict__ sums,
-                                                           const WithinMeta* __restrict__ meta, uint32_t* __restrict__ offsets) {
-    __shared__ uint32_t part[256];
-    const uint32_t base = blockIdx.x * WITHIN_SCAN_BLOCK + threadIdx.x * WITHIN_SCAN_ITEMS;
-    uint32_t c[WITHIN_SCAN_ITEMS], own = 0;
-    for (uint32_t j = 0; j < WITHIN_SCAN_ITEMS; j++) {
-        c[j] = base + j < n ? counts[base + j] : 0u;
-        own += c[j];
-    }
-    part[threadIdx.x] = own;
-    __syncthreads();
-    for (uint32_t w = 1; w < 256; w <<= 1) {
-        const uint32_t add = threadIdx.x >= w ? part[threadIdx.x - w] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = (uint32_t)sums[blockIdx.x] + part[threadIdx.x] - own;
-    for (uint32_t j = 0; j < WITHIN_SCAN_ITEMS; j++) {
-        if (base + j < n) offsets[base + j] = run;
-        run += c[j];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) offsets[n] = (uint32_t)meta->total;
-}
-
 // ---- the second walk ----------------------------------------------------------------------------------------------------------------
 // pos: NULL, or total u32 — the list positions of the rows beyond WITHIN_LDS_ROW_MAX (a sorted batch that has such rows)
 template <typename T, bool TRIANGLE, bool UNFOLDED, bool SORTED>
@@ -271,39 +180,9 @@ __global__ __launch_bounds__(256) void k_within_fill(const TravNode<T>* __restri
     }
 }
 
-// the all-ascending bitonic network on len elements padded (virtually) to P = 2^k >= len; element e: key (kd[e], kp[e]), payload ks[e].
-// First step of every merge mirrors, the others shift: every comparator leaves the smaller key at the lower index, so the slots between
-// the row's length and P — (+inf, UINT32_MAX) by definition — never move and need no storage.  Every thread of the workgroup calls it
-// with the same len and P.  GLOBAL: the arrays are in global memory (a fence in front of the barrier).
-template <typename T, bool GLOBAL>
-__device__ __forceinline__ void within_bitonic(T* kd, uint32_t* kp, uint32_t* ks, uint32_t len, uint32_t P) {
-    const uint32_t half = P >> 1;
-    for (uint32_t k = 2; k <= P; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            const bool mirror = j == (k >> 1);
-            for (uint32_t t = threadIdx.x; t < half; t += WITHIN_SORT_THREADS) {
-                const uint32_t lo = 2 * j * (t / j) + (t % j);
-                const uint32_t hi = mirror ? 2 * j * (t / j) + (2 * j - 1 - (t % j)) : lo + j;
-                if (hi < len) {   // (lo < hi; a slot beyond the row is the largest key: nothing to exchange)
-                    const T dl = kd[lo], dh = kd[hi];
-                    const uint32_t pl = kp[lo], ph = kp[hi];
-                    if (dh < dl || (dh == dl && ph < pl)) {
-                        kd[lo] = dh; kd[hi] = dl;
-                        kp[lo] = ph; kp[hi] = pl;
-                        const uint32_t sl = ks[lo], sh = ks[hi];
-                        ks[lo] = sh; ks[hi] = sl;
-                    }
-                }
-            }
-            if (GLOBAL) __threadfence_block();
-            __syncthreads();
-        }
-    }
-}
-
 // one workgroup per long row of a sorted batch
 template <typename T>
-__global__ __launch_bounds__(WITHIN_SORT_THREADS) void k_within_sort_row(const uint32_t* __restrict__ work, const uint32_t* __restrict__ offsets,
+__global__ __launch_bounds__(ROWS_SORT_THREADS) void k_within_sort_row(const uint32_t* __restrict__ work, const uint32_t* __restrict__ offsets,
                                                                          uint32_t* shape, T* dist, uint32_t* pos) {
     __shared__ T ld[WITHIN_LDS_ROW_MAX];
     __shared__ uint32_t lp[WITHIN_LDS_ROW_MAX];
@@ -315,15 +194,15 @@ __global__ __launch_bounds__(WITHIN_SORT_THREADS) void k_within_sort_row(const u
     uint32_t* rs = shape + beg;
     T* rd = dist + beg;
     if (len <= WITHIN_LDS_ROW_MAX) {
-        for (uint32_t e = threadIdx.x; e < len; e += WITHIN_SORT_THREADS) { ld[e] = rd[e]; lp[e] = e; ls[e] = rs[e]; }
+        for (uint32_t e = threadIdx.x; e < len; e += ROWS_SORT_THREADS) { ld[e] = rd[e]; lp[e] = e; ls[e] = rs[e]; }
         __syncthreads();
-        within_bitonic<T, false>(ld, lp, ls, len, P);
-        for (uint32_t e = threadIdx.x; e < len; e += WITHIN_SORT_THREADS) { rd[e] = sqrt(ld[e]); rs[e] = ls[e]; }
+        rows_bitonic<T, false>(ld, 1u, lp, ls, len, P);
+        for (uint32_t e = threadIdx.x; e < len; e += ROWS_SORT_THREADS) { rd[e] = sqrt(ld[e]); rs[e] = ls[e]; }
     } else if (pos != nullptr) {   // (the host passes the positions whenever a row is this long)
         __threadfence_block();
         __syncthreads();
-        within_bitonic<T, true>(rd, pos + beg, rs, len, P);
-        for (uint32_t e = threadIdx.x; e < len; e += WITHIN_SORT_THREADS) rd[e] = sqrt(rd[e]);   // (the network ended with a barrier)
+        rows_bitonic<T, true>(rd, 1u, pos + beg, rs, len, P);
+        for (uint32_t e = threadIdx.x; e < len; e += ROWS_SORT_THREADS) rd[e] = sqrt(rd[e]);   // (the network ended with a barrier)
     }
 }
 
@@ -331,54 +210,34 @@ __global__ __launch_bounds__(WITHIN_SORT_THREADS) void k_within_sort_row(const u
 template <typename T, bool TRIANGLE, bool UNFOLDED>
 static void within_launch(bvhgpu_tree* t, const TravNode<T>* nodes, uint32_t n_trav, const T* points_dev, const T* max_dist_dev, size_t n, bool sorted,
                           bool count_only, bvhgpu_hits* h) {
-    bvhgpu_ctx* ctx = t->ctx;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = t->ctx->stream;
     const T* aabbs = t->aabbs.as<T>();
     const T* tris = t->tris.as<T>();
     const uint32_t n32 = (uint32_t)n;
     const dim3 pgrid((unsigned)((n + 255) / 256)), block(256);
-    const uint32_t nb = (uint32_t)((n + WITHIN_SCAN_BLOCK - 1) / WITHIN_SCAN_BLOCK);
     const bool rows_sorted = sorted && !count_only;
-    h->ah_counts.reserve(n * 4);
-    h->ah_sums.reserve(sizeof(WithinMeta) + (size_t)nb * sizeof(unsigned long long));
-    if (rows_sorted) h->ah_work.reserve(n * 4);
-    WithinMeta* meta = h->ah_sums.as<WithinMeta>();
-    unsigned long long* sums = reinterpret_cast<unsigned long long*>(meta + 1);
-    uint32_t* counts = h->ah_counts.as<uint32_t>();
+    uint32_t* counts = rows_begin(h, n, rows_sorted);
     uint32_t* offsets = h->offsets.as<uint32_t>();
-    BVH_HIP(hipMemsetAsync(meta, 0, sizeof(WithinMeta), st));
     hipLaunchKernelGGL((k_within_count<T, TRIANGLE, UNFOLDED>), pgrid, block, 0, st, nodes, n_trav, aabbs, tris, points_dev, max_dist_dev, n32, counts);
-    hipLaunchKernelGGL(k_within_block_sums, dim3(nb), block, 0, st, counts, n32, sums, meta, h->ah_work.as<uint32_t>(),
-                       rows_sorted ? WITHIN_LANE_ROW_MAX : 0u, WITHIN_LDS_ROW_MAX);
-    hipLaunchKernelGGL(k_within_scan_sums, dim3(1), block, 0, st, sums, nb, meta);
-    BVH_HIP(hipGetLastError());
-    WithinMeta* got = static_cast<WithinMeta*>(ctx->pinned);
-    BVH_HIP(hipMemcpyAsync(got, meta, sizeof(WithinMeta), hipMemcpyDeviceToHost, st));
-    BVH_HIP(hipStreamSynchronize(st));
-    const unsigned long long total = got->total;
-    const uint32_t n_long = got->n_long, n_beyond = got->n_beyond_lds;
-    if (total > 0xFFFFFFFFull) throw HipFail{hipErrorInvalidValue, nullptr, __LINE__, Fail::Overflow};
-    if (total == 0) {   // every row is empty
-        BVH_HIP(hipMemsetAsync(offsets, 0, (n + 1) * 4, st));
-        return;
-    }
-    hipLaunchKernelGGL(k_within_scan_final, dim3(nb), block, 0, st, counts, n32, sums, meta, offsets);
+    const RowsTotals rows = rows_scan(h, n, rows_sorted ? WITHIN_LANE_ROW_MAX : 0u, WITHIN_LDS_ROW_MAX);
+    if (rows.total == 0) return;   // every row is empty
+    rows_offsets(h, n);
     if (!count_only) {
-        h->indices.reserve((size_t)total * 4);
-        h->ah_vals.reserve((size_t)total * sizeof(T));
+        h->indices.reserve((size_t)rows.total * 4);
+        h->ah_vals.reserve((size_t)rows.total * sizeof(T));
         uint32_t* pos = nullptr;
-        if (n_beyond) { h->ah_pos.reserve((size_t)total * 4); pos = h->ah_pos.as<uint32_t>(); }
+        if (rows.n_beyond_lds) { h->ah_pos.reserve((size_t)rows.total * 4); pos = h->ah_pos.as<uint32_t>(); }
         uint32_t* shape = h->indices.as<uint32_t>();
         T* dist = h->ah_vals.as<T>();
         if (sorted) hipLaunchKernelGGL((k_within_fill<T, TRIANGLE, UNFOLDED, true>), pgrid, block, 0, st, nodes, n_trav, aabbs, tris, points_dev, max_dist_dev, n32,
                                        offsets, shape, dist, pos);
         else hipLaunchKernelGGL((k_within_fill<T, TRIANGLE, UNFOLDED, false>), pgrid, block, 0, st, nodes, n_trav, aabbs, tris, points_dev, max_dist_dev, n32,
                                 offsets, shape, dist, pos);
-        if (sorted && n_long)
-            hipLaunchKernelGGL((k_within_sort_row<T>), dim3(n_long), dim3(WITHIN_SORT_THREADS), 0, st, h->ah_work.as<uint32_t>(), offsets, shape, dist, pos);
+        if (sorted && rows.n_long)
+            hipLaunchKernelGGL((k_within_sort_row<T>), dim3(rows.n_long), dim3(ROWS_SORT_THREADS), 0, st, h->ah_work.as<uint32_t>(), offsets, shape, dist, pos);
     }
     BVH_HIP(hipGetLastError());
-    h->total = total;
+    h->total = rows.total;
 }
 
 template <typename T>
@@ -390,10 +249,7 @@ void within_batch(bvhgpu_tree* t, const T* points_dev, const T* max_dist_dev, si
     const bool mirror = t->exact_only && t->built && !t->unfolded && t->n >= 2;   // (see "Which array is walked" at the top)
     const bool unfolded = t->unfolded || t->n == 1 || mirror;   // a single-shape tree has one (leaf) entry and no navigator
     // the result object becomes an (empty) within result first: whatever fails below leaves it consistent
-    h->ctx = ctx; h->dtype = Traits<T>::dtype; h->flags = TRAVERSE_WITHIN; h->ah_leaf = 0; h->wi_count_only = count_only; h->n_rays = 0; h->total = 0;
-    h->stats = bvhgpu_traverse_stats{0, 0, 0, 0, 0};
-    h->pend_tree = nullptr; h->pend_rays = nullptr; h->pend_async = false;
-    h->pend_wide = false; h->pend_staged = false; h->pend_rec8 = false; h->pend_guide = false; h->pend_qwide = false;
+    rows_reset(h, ctx, Traits<T>::dtype, TRAVERSE_WITHIN, 0, count_only);
     char name[112];
     const char* tri = kind == 1 ? "true" : "false";
     const char* unf = unfolded ? "true" : "false";

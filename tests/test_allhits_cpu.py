@@ -49,7 +49,7 @@ def test_new_functions_in_every_layer():
         assert name in bound, f"{name} missing from _lib.SYMBOLS"
         assert hasattr(lib, name) and re.search(r" T %s\b" % name, nm), f"{name} not exported"
     blob = open(_lib.SO_PATH, "rb").read()
-    for kern in (b"k_allhits_count", b"k_allhits_fill", b"k_allhits_sort_row", b"k_allhits_scan_final"):
+    for kern in (b"k_allhits_count", b"k_allhits_fill", b"k_allhits_sort_row", b"k_rows_scan_final"):
         assert kern in blob, kern
     ffi = open(os.path.join(ROOT, "rust", "bvh-mi355x", "src", "ffi.rs")).read()
     lib_rs = open(os.path.join(ROOT, "rust", "bvh-mi355x", "src", "lib.rs")).read()

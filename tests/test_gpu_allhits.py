@@ -12,7 +12,7 @@ import allhits_ref as ar
 import khits_ref as kr
 import test_fp_extremes_queries_cpu as q
 from sphere_ref import cluster_rays, cluster_scene, list_hits, tmax_draw
-from test_allhits_cpu import long_pair_case, single_row_case
+from test_allhits_cpu import ROOT, long_pair_case, single_row_case
 from test_gpu_any_hit import _rb
 from test_khits_cpu import cluster_case, cube_case, pair_row_case, triangle_row_case
 
@@ -200,6 +200,39 @@ def test_allhits_ray_counts(eng, orc, ctx, dtype):
                 _check(flat, _dev_rays(eng, case["rays"][:n]), leaf, torch.from_numpy(tmax[:n].copy()).cuda(), True, want, (n, leaf, "device"))
     o, s, v = flat.allhits_batch(_rb(eng, case["rays"][:0]), "sphere")
     assert o.tolist() == [0] and s.shape == (0,) and v.shape == (0, 2)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_allhits_scan_second_round(eng, orc, ctx, dtype):
+    """256 * 1024 + 1 rays: 257 scan blocks, so the one-workgroup scan of the block sums runs a second round.  A small tree with short
+    rows; the batch repeats 64 distinct rays, so the definition is computed for 64 rows"""
+    import torch
+    boxes = orc.aligned_boxes().astype(dtype)
+    oflat = orc.flatten(orc.build(boxes).nodes)
+    rng = np.random.default_rng(45)
+    o = np.concatenate([rng.uniform(-12, 12, size=(64, 1)), rng.uniform(-0.45, 0.45, size=(64, 2))], axis=1)   # inside the row's cross-section
+    o[0, 0] = -12                                                                           # (ray 0, whose row is repeated at the end: all 21 boxes)
+    d = rng.normal(size=(64, 3))
+    d[::2] = np.array([1.0, 0, 0]) * np.where(np.arange(32) % 2, -1.0, 1.0)[:, None]      # every other ray along the row of boxes
+    base = orc.make_rays(o.astype(dtype), d.astype(dtype), dtype)
+    bt = np.asarray([np.inf, 0.5, 3, 10, -1, np.nan, 25, 1.5], dtype=dtype)[np.arange(64) % 8]
+    off, idx, ts, _ = orc.traverse_flat(oflat, boxes, base, want_t=True)
+    reps, n = 4096, 64 * 4096 + 1
+    assert n == 256 * 1024 + 1
+    rays, tmax = np.concatenate([np.tile(base, reps), base[:1]]), np.concatenate([np.tile(bt, reps), bt[:1]])
+    flat = eng.Bvh.from_aabbs(boxes, ctx).flatten()
+    lane_max = ar.engine_thresholds(ROOT)[0]
+    for sort in (True, False):
+        bo, bs, bv = ar.allhits_match(off, idx, ts, bt, sort)
+        first = int(bo[1])
+        lens = np.concatenate([np.tile(np.diff(bo.astype(np.int64)), reps), [first]])
+        want_o = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+        want = (want_o, np.concatenate([np.tile(bs, reps), bs[:first]]), np.concatenate([np.tile(bv, (reps, 1)), bv[:first]]))
+        assert 0 < first and 3 < lens.max() <= lane_max and (lens == 0).any() and len(want_o) == n + 1
+        if sort:                                                                            # rays and segment ends in HBM, then in host memory
+            _check(flat, _dev_rays(eng, rays), "box", torch.from_numpy(tmax.copy()).cuda(), sort, want, ("second round", sort))
+        else:
+            _check(flat, _rb(eng, rays), "box", tmax, sort, want, ("second round", sort))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

@@ -140,7 +140,7 @@ def test_new_functions_in_every_layer():
         assert hasattr(lib, name) and re.search(r" T %s\b" % name, nm), f"{name} not exported"
     assert _lib.WITHIN_LIST_ORDER == 1 and _lib.WITHIN_COUNT_ONLY == 2 and lib.bvhgpu_abi_version() == 7
     blob = open(_lib.SO_PATH, "rb").read()
-    for kern in (b"k_within_count", b"k_within_fill", b"k_within_sort_row", b"k_within_block_sums", b"k_within_scan_sums", b"k_within_scan_final"):
+    for kern in (b"k_within_count", b"k_within_fill", b"k_within_sort_row", b"k_rows_block_sums", b"k_rows_scan_sums", b"k_rows_scan_final"):
         assert kern in blob, kern
     ffi = open(os.path.join(ROOT, "rust", "bvh-mi355x", "src", "ffi.rs")).read()
     lib_rs = open(os.path.join(ROOT, "rust", "bvh-mi355x", "src", "lib.rs")).read()
@@ -151,7 +151,8 @@ def test_new_functions_in_every_layer():
     from bvh_amd.api import Bvh, _Hits, _TreeBase
     assert callable(getattr(_TreeBase, "within_batch", None)) and callable(getattr(_Hits, "fetch_within", None))
     assert Bvh.within_batch is not _TreeBase.within_batch                       # the flatten_in_place wrapper
-    assert "within.hip" in open(os.path.join(ROOT, "bvh_amd", "build_ext.py")).read()
+    build_py = open(os.path.join(ROOT, "bvh_amd", "build_ext.py")).read()
+    assert "within.hip" in build_py and "rows.hip" in build_py
 
 
 def test_header_states_the_definition():

@@ -249,7 +249,7 @@ def check(rc: int, ctx=None):
     if rc == OK:
         return
     lib = load()
-    msg = lib.bvhgpu_last_error(ctx).decode() if True else ""
+    msg = lib.bvhgpu_last_error(ctx).decode()
     if not msg:
         msg = lib.bvhgpu_status_string(rc).decode()
     raise BvhGpuError(rc, msg)

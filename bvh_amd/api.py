@@ -15,13 +15,13 @@ from __future__ import annotations
 import atexit
 import ctypes as C
 import weakref
-from typing import Iterable, List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import _lib
-from ._lib import (DEVICE, F32, F64, FLAT_F32, FLAT_F64, HOST, NODE_F32, NODE_F64, NONE, RAY_F32, RAY_F64,
-                   TRAVERSE_CLOSEST, TRAVERSE_COHERENT, TRAVERSE_FARTHEST_FIRST, TRAVERSE_NEAREST_FIRST, TRAVERSE_STATS, TRAVERSE_T_SLICE, TRAVERSE_TRIANGLES, BvhGpuError, check, ptr)
+from ._lib import (DEVICE, F32, FLAT_F32, FLAT_F64, HOST, NODE_F32, NODE_F64, NONE, RAY_F32, RAY_F64,
+                   TRAVERSE_CLOSEST, TRAVERSE_COHERENT, TRAVERSE_STATS, TRAVERSE_T_SLICE, TRAVERSE_TRIANGLES, BvhGpuError, check, ptr)
 
 
 def _sfx(dtype) -> str:
@@ -35,6 +35,36 @@ def _sfx(dtype) -> str:
 
 def _ray_dtype(s):
     return RAY_F32 if s == "f32" else RAY_F64
+
+
+_FT = {"f32": np.float32, "f64": np.float64}
+
+
+class _Typed:
+    """what follows from `sfx` ("f32" / "f64"), the scalar type of a tree or a ray batch"""
+    sfx: str
+
+    @property
+    def ft(self):
+        """the numpy scalar type"""
+        return _FT[self.sfx]
+
+
+def _is_torch_ft(t, ft) -> bool:
+    """is torch tensor `t` of the numpy scalar type `ft` (torch itself is not needed to tell)"""
+    return str(t.dtype) == "torch." + ft.__name__
+
+
+def _torch_ft(ft):
+    """the torch dtype outputs for the numpy scalar type `ft` are allocated in"""
+    import torch
+    return torch.float32 if np.dtype(ft) == np.float32 else torch.float64
+
+
+def _torch_sync(device) -> None:
+    """the engine works on its own stream: what torch has enqueued on `device` (the inputs, the outputs' memory) must be there"""
+    import torch
+    torch.cuda.current_stream(device).synchronize()
 
 
 # Native handles must be released while the HIP runtime is still alive: at interpreter shutdown the
@@ -59,8 +89,60 @@ def _shutdown():
 atexit.register(_shutdown)
 
 
+def _ray_flags(coherent: bool, first: bool = False) -> int:
+    return (TRAVERSE_COHERENT if coherent else 0) | (_lib.TRAVERSE_FIRST if first else 0)
+
+
 def _is_device_tensor(x) -> bool:
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda") and bool(x.is_cuda)
+
+
+def _rows_in(x, width: int, ft, what: str, check_tensor: bool = True, convert: bool = False, device: bool = True, exact: bool = True):
+    """The one way an input array reaches the C ABI: `x`, an array-like of rows of `width` scalars that must be in the tree's dtype `ft`
+    → (the object to keep alive over the call, its c_void_p, the row count, HOST or DEVICE).  A torch GPU tensor is used in place, anything
+    else becomes a contiguous numpy array.  Where the call sites differ, they say so:
+      check_tensor  a tensor of another dtype raises DTYPE_MISMATCH and a strided one is made contiguous; False: a tensor is taken as it
+                    is, its dtype unchecked (set_triangles, rebuild, refit, from_aabbs)
+      convert       a numpy array of another dtype is converted; False: it raises DTYPE_MISMATCH (lists and scalars are always converted)
+      device        False: host input only, a tensor is handed to numpy like any other object (nearest_batch)
+      exact         a size that is no multiple of `width` raises numpy's ValueError; False: the partial row is dropped (query_batch)"""
+    if device and _is_device_tensor(x):
+        if check_tensor:
+            if not _is_torch_ft(x, ft):
+                raise BvhGpuError(_lib.DTYPE_MISMATCH, f"{what} dtype differs from tree dtype")
+            x = x.contiguous()
+        return x, ptr(x.data_ptr()), x.numel() // width, DEVICE
+    if not convert and isinstance(x, np.ndarray) and x.dtype != ft:
+        raise BvhGpuError(_lib.DTYPE_MISMATCH, f"{what} dtype differs from tree dtype")
+    a = np.ascontiguousarray(x, dtype=ft)
+    a = a.reshape(-1, width) if exact else a.reshape(-1)
+    return a, ptr(a), a.size // width, HOST
+
+
+def _bytes_in(x):
+    """a scene blob's buffer as it is, a torch GPU tensor or a numpy array → (its c_void_p, DEVICE or HOST)"""
+    return (ptr(x.data_ptr()), DEVICE) if _is_device_tensor(x) else (ptr(x), HOST)
+
+
+def _side_in(v, main, n: int, mem: int, ft, what: str, of: str, scalar_ok: bool = False):
+    """The per-row side array of a batch (tmax of rays, max_dist of points): n values in the tree's dtype in the memory `mem` of the main
+    input `main` → (the object to keep alive, its c_void_p); None → (None, None).  scalar_ok: a scalar is the same value for every row."""
+    if v is None:
+        return None, None
+    if scalar_ok and not _is_device_tensor(v) and np.ndim(v) == 0:
+        if mem == DEVICE:
+            import torch
+            keep = torch.full((n,), float(v), dtype=main.dtype, device=main.device)
+            return keep, ptr(keep.data_ptr())
+        keep = np.full(n, v, dtype=ft)
+        return keep, ptr(keep)
+    if _is_device_tensor(v) != (mem == DEVICE):
+        raise BvhGpuError(_lib.INVALID_ARG, f"{what} is a GPU tensor but the {of} are in host memory" if mem == HOST else
+                          f"{what} is in host memory but the {of} are in HBM")
+    keep, p, m, _ = _rows_in(v, 1, ft, what)
+    if m != n:
+        raise BvhGpuError(_lib.INVALID_ARG, f"{what} has {m} values for {n} {of}")
+    return keep, p
 
 
 # ------------------------------------------------------------------------------------------------
@@ -298,7 +380,7 @@ class BHShape(Bounded):
 
 
 # ------------------------------------------------------------------------------------------------
-class RayBatch:
+class RayBatch(_Typed):
     """A batch of Ray<T,3> (ray_impl.rs:17-29) in host memory (structured array) or in HBM."""
 
     def __init__(self, n: int, dtype, host: Optional[np.ndarray] = None, device=None, device_ptr: int = 0):
@@ -350,7 +432,7 @@ def intersect_triangle_pairs(rays: "RayBatch", tris, ctx: Optional["Context"] = 
     """Ray::intersects_triangle (ray_impl.rs:154-213) for ray i against triangle i, on the GPU.
     tris: (n,3,3) or (n,9).  returns (n,3) = Intersection{distance,u,v}."""
     ctx = ctx or default_context()
-    ft = np.float32 if rays.sfx == "f32" else np.float64
+    ft = rays.ft
     t = np.ascontiguousarray(tris, dtype=ft).reshape(-1, 9)
     if len(t) != rays.n or rays.host is None:
         raise ValueError("one host triangle per host ray is required")
@@ -426,22 +508,30 @@ class _Hits:
 
     def wait(self) -> dict:
         """bvhgpu_hits_wait: complete an asynchronous batch; returns the stats dict of traverse_batch."""
-        lib = _lib.load()
-        check(lib.bvhgpu_hits_wait(self.h), self.ctx._h)
-        total = C.c_uint64()
-        st = _lib.TraverseStats()
-        check(lib.bvhgpu_hits_info(self.h, None, C.byref(total), C.byref(st)), self.ctx._h)
-        return dict(hits=int(st.hits), visited=int(st.visited), leaf_visits=int(st.leaf_visits),
-                    device_steps=int(st.device_steps), wave_steps=int(st.wave_steps), total=int(total.value))
+        check(_lib.load().bvhgpu_hits_wait(self.h), self.ctx._h)
+        total, sd = self._stats()
+        sd["total"] = total
+        return sd
 
     def info(self) -> dict:
         """stats of the completed batch (bvhgpu_hits_info)"""
-        lib = _lib.load()
-        total = C.c_uint64()
+        total, sd = self._stats()
+        sd["total"] = total
+        return sd
+
+    def _stats(self, want_total: bool = True):
+        """one bvhgpu_hits_info → (the hit total, or None when it is not asked for; the stats dict of the batch calls)"""
+        total = C.c_uint64() if want_total else None
         st = _lib.TraverseStats()
-        check(lib.bvhgpu_hits_info(self.h, None, C.byref(total), C.byref(st)), self.ctx._h)
-        return dict(hits=int(st.hits), visited=int(st.visited), leaf_visits=int(st.leaf_visits),
-                    device_steps=int(st.device_steps), wave_steps=int(st.wave_steps), total=int(total.value))
+        check(_lib.load().bvhgpu_hits_info(self.h, None, C.byref(total) if want_total else None, C.byref(st)), self.ctx._h)
+        return (int(total.value) if want_total else None), dict(hits=int(st.hits), visited=int(st.visited), leaf_visits=int(st.leaf_visits),
+                                                                device_steps=int(st.device_steps), wave_steps=int(st.wave_steps))
+
+    def _total(self) -> int:
+        """the hit total alone (bvhgpu_hits_info): what the CSR fetches size their outputs by"""
+        total = C.c_uint64()
+        check(_lib.load().bvhgpu_hits_info(self.h, None, C.byref(total), None), self.ctx._h)
+        return int(total.value)
 
     def walk_kernel(self) -> str:
         """bvhgpu_hits_walk_kernel: the kernel the completed batch was walked by, spelled as rocprofv3 prints it"""
@@ -454,97 +544,76 @@ class _Hits:
         check(_lib.load().bvhgpu_hits_walk_info(self.h, C.byref(f)), self.ctx._h)
         return int(f.value)
 
+    def _fetch_per_ray(self, entry: str, width: int, n_rays: int, dtype):
+        """bvhgpu_hits_fetch_<entry>: one record of `width` scalars and one shape per ray, copied to the host"""
+        vals = np.zeros((n_rays, width), dtype=dtype)
+        shape = np.zeros(n_rays, dtype=np.uint32)
+        check(getattr(_lib.load(), f"bvhgpu_hits_fetch_{entry}")(self.h, ptr(vals), ptr(shape), HOST), self.ctx._h)
+        return vals, shape
+
     def fetch_closest(self, n_rays: int, dtype=np.float32):
         """CLOSEST batches: (Intersection{distance,u,v}[n,3], shape[n]) of the completed batch, copied to the host"""
-        isect = np.zeros((n_rays, 3), dtype=dtype)
-        shape = np.zeros(n_rays, dtype=np.uint32)
-        check(_lib.load().bvhgpu_hits_fetch_closest(self.h, ptr(isect), ptr(shape), HOST), self.ctx._h)
-        return isect, shape
+        return self._fetch_per_ray("closest", 3, n_rays, dtype)
 
     def fetch_any(self, n_rays: int, dtype=np.float32):
         """any-hit batches: (Intersection{distance,u,v}[n,3], shape[n]) of the completed batch, copied to the host"""
-        isect = np.zeros((n_rays, 3), dtype=dtype)
-        shape = np.zeros(n_rays, dtype=np.uint32)
-        check(_lib.load().bvhgpu_hits_fetch_any(self.h, ptr(isect), ptr(shape), HOST), self.ctx._h)
-        return isect, shape
+        return self._fetch_per_ray("any", 3, n_rays, dtype)
 
     def fetch_box(self, n_rays: int, dtype=np.float32):
         """box batches: (slice{enter,exit}[n,2], shape[n]) of the completed batch, copied to the host"""
-        ts = np.zeros((n_rays, 2), dtype=dtype)
-        shape = np.zeros(n_rays, dtype=np.uint32)
-        check(_lib.load().bvhgpu_hits_fetch_box(self.h, ptr(ts), ptr(shape), HOST), self.ctx._h)
-        return ts, shape
+        return self._fetch_per_ray("box", 2, n_rays, dtype)
 
     def fetch_sphere(self, n_rays: int, dtype=np.float32):
         """sphere batches: (hit{distance,exit}[n,2], shape[n]) of the completed batch, copied to the host"""
-        ts = np.zeros((n_rays, 2), dtype=dtype)
-        shape = np.zeros(n_rays, dtype=np.uint32)
-        check(_lib.load().bvhgpu_hits_fetch_sphere(self.h, ptr(ts), ptr(shape), HOST), self.ctx._h)
-        return ts, shape
+        return self._fetch_per_ray("sphere", 2, n_rays, dtype)
 
     def fetch_triangles(self, dtype=np.float32):
         """TRIANGLES batches: Intersection{distance,u,v} of every candidate, CSR order"""
-        total = C.c_uint64()
-        check(_lib.load().bvhgpu_hits_info(self.h, None, C.byref(total), None), self.ctx._h)
-        isect = np.zeros((total.value, 3), dtype=dtype)
+        isect = np.zeros((self._total(), 3), dtype=dtype)
         check(_lib.load().bvhgpu_hits_fetch_triangles(self.h, ptr(isect), HOST), self.ctx._h)
         return isect
 
     def fetch(self, n_rays: int):
         """(offsets, indices) of the completed batch, copied to the host."""
-        lib = _lib.load()
-        total = C.c_uint64()
-        check(lib.bvhgpu_hits_info(self.h, None, C.byref(total), None), self.ctx._h)
         offsets = np.zeros(n_rays + 1, dtype=np.uint32)
-        indices = np.zeros(total.value, dtype=np.uint32)
-        check(lib.bvhgpu_hits_fetch(self.h, ptr(offsets), ptr(indices), None, HOST), self.ctx._h)
+        indices = np.zeros(self._total(), dtype=np.uint32)
+        check(_lib.load().bvhgpu_hits_fetch(self.h, ptr(offsets), ptr(indices), None, HOST), self.ctx._h)
         return offsets, indices
+
+    def _fetch_rows(self, entry: str, n: int, rows: int, vshape, dtype, device):
+        """bvhgpu_hits_fetch_<entry> of a CSR-rows batch: (offsets[n+1], shape[rows], vals[vshape]).  device None: copied to the host, offsets
+        and shape as uint32.  device: torch tensors there, filled by device-to-device copies — shape as torch.int32, offsets widened to
+        torch.int64 on the device.  With no rows the engine gets NULL for shape and vals."""
+        fn = getattr(_lib.load(), f"bvhgpu_hits_fetch_{entry}")
+        if device is not None:
+            import torch
+            off32 = torch.empty(n + 1, dtype=torch.int32, device=device)
+            shape = torch.empty(rows, dtype=torch.int32, device=device)
+            vals = torch.empty(vshape, dtype=_torch_ft(dtype), device=device)
+            _torch_sync(device)
+            check(fn(self.h, ptr(off32.data_ptr()), ptr(shape.data_ptr()) if rows else None, ptr(vals.data_ptr()) if rows else None, DEVICE),
+                  self.ctx._h)
+            return off32.to(torch.int64) & 0xFFFFFFFF, shape, vals
+        offsets = np.zeros(n + 1, dtype=np.uint32)
+        shape = np.zeros(rows, dtype=np.uint32)
+        vals = np.zeros(vshape, dtype=dtype)
+        check(fn(self.h, ptr(offsets), ptr(shape) if rows else None, ptr(vals) if rows else None, HOST), self.ctx._h)
+        return offsets, shape, vals
 
     def fetch_allhits(self, n_rays: int, leaf: str = "box", dtype=np.float32, device=None):
         """all-hits batches (bvhgpu_hits_fetch_allhits): (offsets[n+1], shape[total], vals[total, W]) of the completed batch.  device None:
         copied to the host, offsets and shape as uint32.  device: torch tensors there, filled by device-to-device copies — shape as
         torch.int32, offsets widened to torch.int64 on the device."""
-        lib = _lib.load()
-        total = C.c_uint64()
-        check(lib.bvhgpu_hits_info(self.h, None, C.byref(total), None), self.ctx._h)
-        total, w = int(total.value), _lib.LEAF_WIDTH[_lib.LEAF_KINDS[leaf]]
-        if device is not None:
-            import torch
-            off32 = torch.empty(n_rays + 1, dtype=torch.int32, device=device)
-            shape = torch.empty(total, dtype=torch.int32, device=device)
-            vals = torch.empty((total, w), dtype=torch.float32 if np.dtype(dtype) == np.float32 else torch.float64, device=device)
-            torch.cuda.current_stream(device).synchronize()
-            check(lib.bvhgpu_hits_fetch_allhits(self.h, ptr(off32.data_ptr()), ptr(shape.data_ptr()) if total else None,
-                                                ptr(vals.data_ptr()) if total else None, DEVICE), self.ctx._h)
-            return off32.to(torch.int64) & 0xFFFFFFFF, shape, vals
-        offsets = np.zeros(n_rays + 1, dtype=np.uint32)
-        shape = np.zeros(total, dtype=np.uint32)
-        vals = np.zeros((total, w), dtype=dtype)
-        check(lib.bvhgpu_hits_fetch_allhits(self.h, ptr(offsets), ptr(shape), ptr(vals), HOST), self.ctx._h)
-        return offsets, shape, vals
+        total = self._total()
+        return self._fetch_rows("allhits", n_rays, total, (total, _lib.LEAF_WIDTH[_lib.LEAF_KINDS[leaf]]), dtype, device)
 
     def fetch_within(self, n: int, dtype=np.float32, device=None, count_only: bool = False):
         """within batches (bvhgpu_hits_fetch_within): (offsets[n+1], shape[total], dist[total]) of the completed batch; a count-only batch
         has empty shape and dist.  device None: copied to the host, offsets and shape as uint32.  device: torch tensors there, filled by
         device-to-device copies — shape as torch.int32, offsets widened to torch.int64 on the device."""
-        lib = _lib.load()
-        total = C.c_uint64()
-        check(lib.bvhgpu_hits_info(self.h, None, C.byref(total), None), self.ctx._h)
-        rows = 0 if count_only else int(total.value)
-        if device is not None:
-            import torch
-            off32 = torch.empty(n + 1, dtype=torch.int32, device=device)
-            shape = torch.empty(rows, dtype=torch.int32, device=device)
-            dist = torch.empty(rows, dtype=torch.float32 if np.dtype(dtype) == np.float32 else torch.float64, device=device)
-            torch.cuda.current_stream(device).synchronize()
-            check(lib.bvhgpu_hits_fetch_within(self.h, ptr(off32.data_ptr()), ptr(shape.data_ptr()) if rows else None,
-                                               ptr(dist.data_ptr()) if rows else None, DEVICE), self.ctx._h)
-            return off32.to(torch.int64) & 0xFFFFFFFF, shape, dist
-        offsets = np.zeros(n + 1, dtype=np.uint32)
-        shape = np.zeros(rows, dtype=np.uint32)
-        dist = np.zeros(rows, dtype=dtype)
-        check(lib.bvhgpu_hits_fetch_within(self.h, ptr(offsets), ptr(shape) if rows else None, ptr(dist) if rows else None, HOST), self.ctx._h)
-        return offsets, shape, dist
+        total = self._total()
+        rows = 0 if count_only else total
+        return self._fetch_rows("within", n, rows, rows, dtype, device)
 
     def close(self):
         if getattr(self, "h", None) and not _closing:
@@ -561,7 +630,7 @@ class _Hits:
             pass
 
 
-class _TreeBase:
+class _TreeBase(_Typed):
     def __init__(self, ctx: Context, handle, sfx: str):
         self.ctx = ctx
         self._t = handle
@@ -594,6 +663,10 @@ class _TreeBase:
         check(_lib.load().bvhgpu_tree_info(self._t, C.byref(dt), C.byref(n), C.byref(nn), C.byref(nf)), self.ctx._h)
         return int(n.value), int(nn.value), int(nf.value)
 
+    def _ready(self) -> None:
+        """called first by traverse, query_batch, nearest_batch and knearest_batch, which walk the flat arrays: a Bvh flattens here, a
+        FlatBvh has nothing to do.  (khits_batch, allhits_batch and within_batch flatten in overrides on Bvh, which their tests pin.)"""
+
     # ---- traversal -------------------------------------------------------------------------
     def traverse_batch(self, rays: RayBatch, want_t: bool = False, stats: bool = False, fetch: bool = True,
                        coherent: bool = False, order: Optional[str] = None):
@@ -606,20 +679,14 @@ class _TreeBase:
         flags |= _lib.ORDER_FLAGS[order]
         fn = getattr(lib, f"bvhgpu_traverse_{self.sfx}")
         check(fn(self._t, rays._ptr(), rays.n, rays.mem, flags, C.byref(self._hits.h)), self.ctx._h)
-        total = C.c_uint64()
-        st = _lib.TraverseStats()
-        check(lib.bvhgpu_hits_info(self._hits.h, None, C.byref(total), C.byref(st)), self.ctx._h)
-        wk = C.c_uint()
-        check(lib.bvhgpu_hits_walk_info(self._hits.h, C.byref(wk)), self.ctx._h)
-        sd = dict(hits=int(st.hits), visited=int(st.visited), leaf_visits=int(st.leaf_visits),
-                  device_steps=int(st.device_steps), wave_steps=int(st.wave_steps), walk=int(wk.value),   # walk: _lib.WALK_* bits (diagnostic)
-                  kernel=self._hits.walk_kernel())                                                          # ... and the kernel's name
+        total, sd = self._hits._stats()
+        sd["walk"] = self._hits.walk_flags()        # _lib.WALK_* bits (diagnostic)
+        sd["kernel"] = self._hits.walk_kernel()     # ... and the kernel's name
         if not fetch:
             return None, None, None, sd
-        ft = np.float32 if self.sfx == "f32" else np.float64
         offsets = np.zeros(rays.n + 1, dtype=np.uint32)
-        indices = np.zeros(total.value, dtype=np.uint32)
-        ts = np.zeros((total.value, 2), dtype=ft) if want_t else None
+        indices = np.zeros(total, dtype=np.uint32)
+        ts = np.zeros((total, 2), dtype=self.ft) if want_t else None
         check(lib.bvhgpu_hits_fetch(self._hits.h, ptr(offsets), ptr(indices), ptr(ts), HOST), self.ctx._h)
         return offsets, indices, ts, sd
 
@@ -636,14 +703,8 @@ class _TreeBase:
     # ---- triangle stage -------------------------------------------------------------------
     def set_triangles(self, tris) -> None:
         """vertices of the shapes, (n,3,3) or (n,9) [a, b, c] (testbase.rs Triangle :316-323); numpy or torch GPU tensor."""
-        lib = _lib.load()
-        fn = getattr(lib, f"bvhgpu_tree_set_triangles_{self.sfx}")
-        if _is_device_tensor(tris):
-            check(fn(self._t, ptr(tris.data_ptr()), tris.numel() // 9, DEVICE), self.ctx._h)
-        else:
-            ft = np.float32 if self.sfx == "f32" else np.float64
-            a = np.ascontiguousarray(tris, dtype=ft).reshape(-1, 9)
-            check(fn(self._t, ptr(a), len(a), HOST), self.ctx._h)
+        _keep, p, n, mem = _rows_in(tris, 9, self.ft, "triangle", check_tensor=False, convert=True)
+        check(getattr(_lib.load(), f"bvhgpu_tree_set_triangles_{self.sfx}")(self._t, p, n, mem), self.ctx._h)
 
     def intersect_triangles(self, rays: RayBatch, stats: bool = False, coherent: bool = False, order: Optional[str] = None):
         """traverse + Ray::intersects_triangle on every returned shape (testbase.rs:826-836).
@@ -653,17 +714,12 @@ class _TreeBase:
         flags |= _lib.ORDER_FLAGS[order]
         check(getattr(lib, f"bvhgpu_traverse_{self.sfx}")(self._t, rays._ptr(), rays.n, rays.mem, flags,
                                                            C.byref(self._hits.h)), self.ctx._h)
-        total = C.c_uint64()
-        st = _lib.TraverseStats()
-        check(lib.bvhgpu_hits_info(self._hits.h, None, C.byref(total), C.byref(st)), self.ctx._h)
-        ft = np.float32 if self.sfx == "f32" else np.float64
+        total, sd = self._hits._stats()
         offsets = np.zeros(rays.n + 1, dtype=np.uint32)
-        indices = np.zeros(total.value, dtype=np.uint32)
-        isect = np.zeros((total.value, 3), dtype=ft)
+        indices = np.zeros(total, dtype=np.uint32)
+        isect = np.zeros((total, 3), dtype=self.ft)
         check(lib.bvhgpu_hits_fetch(self._hits.h, ptr(offsets), ptr(indices), None, HOST), self.ctx._h)
         check(lib.bvhgpu_hits_fetch_triangles(self._hits.h, ptr(isect), HOST), self.ctx._h)
-        sd = dict(hits=int(st.hits), visited=int(st.visited), leaf_visits=int(st.leaf_visits),
-                  device_steps=int(st.device_steps), wave_steps=int(st.wave_steps))
         return offsets, indices, isect, sd
 
     def closest_hits(self, rays: RayBatch, stats: bool = False, fetch: bool = True, coherent: bool = False,
@@ -675,41 +731,26 @@ class _TreeBase:
         flags |= _lib.ORDER_FLAGS[order]
         check(getattr(lib, f"bvhgpu_traverse_{self.sfx}")(self._t, rays._ptr(), rays.n, rays.mem, flags,
                                                            C.byref(self._hits.h)), self.ctx._h)
-        st = _lib.TraverseStats()
-        check(lib.bvhgpu_hits_info(self._hits.h, None, None, C.byref(st)), self.ctx._h)
-        sd = dict(hits=int(st.hits), visited=int(st.visited), leaf_visits=int(st.leaf_visits),
-                  device_steps=int(st.device_steps), wave_steps=int(st.wave_steps))
+        _, sd = self._hits._stats(want_total=False)
         if not fetch:
             return None, None, sd
-        ft = np.float32 if self.sfx == "f32" else np.float64
-        isect = np.zeros((rays.n, 3), dtype=ft)
-        shape = np.zeros(rays.n, dtype=np.uint32)
-        check(lib.bvhgpu_hits_fetch_closest(self._hits.h, ptr(isect), ptr(shape), HOST), self.ctx._h)
-        return isect, shape, sd
+        return self._hits.fetch_closest(rays.n, self.ft) + (sd,)
 
     def _tmax_arg(self, rays: RayBatch, tmax):
         """per-ray segment ends of any_hits / the box queries → (array kept alive, pointer or None): n values in the tree's dtype in the
         rays' memory — a numpy array for HOST rays, a torch GPU tensor for rays in HBM"""
-        ft = np.float32 if self.sfx == "f32" else np.float64
-        keep, tp = None, None
-        if tmax is not None:
-            if _is_device_tensor(tmax):
-                if rays.mem != DEVICE:
-                    raise BvhGpuError(_lib.INVALID_ARG, "tmax is a GPU tensor but the rays are in host memory")
-                if str(tmax.dtype) != ("torch.float32" if self.sfx == "f32" else "torch.float64"):
-                    raise BvhGpuError(_lib.DTYPE_MISMATCH, "tmax dtype differs from tree dtype")
-                keep = tmax.contiguous()
-                n, tp = keep.numel(), ptr(keep.data_ptr())
-            else:
-                if rays.mem != HOST:
-                    raise BvhGpuError(_lib.INVALID_ARG, "tmax is in host memory but the rays are in HBM")
-                if isinstance(tmax, np.ndarray) and tmax.dtype != ft:
-                    raise BvhGpuError(_lib.DTYPE_MISMATCH, "tmax dtype differs from tree dtype")
-                keep = np.ascontiguousarray(tmax, dtype=ft).reshape(-1)
-                n, tp = keep.size, ptr(keep)
-            if n != rays.n:
-                raise BvhGpuError(_lib.INVALID_ARG, f"tmax has {n} values for {rays.n} rays")
-        return keep, tp
+        return _side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
+
+    def _tmax_batch(self, entry: str, fetcher, rays: RayBatch, tmax, flags: int, fetch: bool):
+        """bvhgpu_traverse_<entry>_*, the ray batches with a per-ray tmax and one record per ray; `fetcher`: the _Hits.fetch_* of that entry"""
+        if rays.sfx != self.sfx:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
+        keep, tp = self._tmax_arg(rays, tmax)   # (keep: the array tp points into stays alive over the call)
+        fn = getattr(_lib.load(), f"bvhgpu_traverse_{entry}_{self.sfx}")
+        check(fn(self._t, rays._ptr(), tp, rays.n, rays.mem, flags, C.byref(self._hits.h)), self.ctx._h)
+        if not fetch:
+            return None, None
+        return fetcher(rays.n, self.ft)
 
     def any_hits(self, rays: RayBatch, tmax=None, fetch: bool = True, coherent: bool = False):
         """bvhgpu_traverse_any_*: occlusion of the segments o .. o + tmax[i]·d.  Per ray the FIRST shape of FlatBvh::traverse's list
@@ -717,16 +758,7 @@ class _TreeBase:
         (+inf, 0, 0) when there is none.  tmax: None (+inf for every ray), or n values in the tree's dtype in the rays' memory — a numpy
         array for HOST rays, a torch GPU tensor for rays in HBM.  Needs set_triangles.  returns (isect[n,3], shape[n]); fetch=False
         returns (None, None) and leaves the result on the tree's result object."""
-        if rays.sfx != self.sfx:
-            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
-        ft = np.float32 if self.sfx == "f32" else np.float64
-        keep, tp = self._tmax_arg(rays, tmax)   # (keep: the array tp points into stays alive over the call)
-        lib = _lib.load()
-        fn = getattr(lib, f"bvhgpu_traverse_any_{self.sfx}")
-        check(fn(self._t, rays._ptr(), tp, rays.n, rays.mem, TRAVERSE_COHERENT if coherent else 0, C.byref(self._hits.h)), self.ctx._h)
-        if not fetch:
-            return None, None
-        return self._hits.fetch_any(rays.n, ft)
+        return self._tmax_batch("any", self._hits.fetch_any, rays, tmax, _ray_flags(coherent), fetch)
 
     def occluded(self, rays: RayBatch, tmax=None) -> np.ndarray:
         """bool[n]: does segment i hit any triangle (any_hits(...) shape != NONE)"""
@@ -734,28 +766,17 @@ class _TreeBase:
         return shape != NONE
 
     # ---- ray queries against the shapes' own boxes (no triangles) ---------------------------
-    def _box_hits(self, rays: RayBatch, tmax, fetch: bool, coherent: bool, first: bool):
-        if rays.sfx != self.sfx:
-            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
-        keep, tp = self._tmax_arg(rays, tmax)   # (keep: the array tp points into stays alive over the call)
-        flags = (TRAVERSE_COHERENT if coherent else 0) | (_lib.TRAVERSE_FIRST if first else 0)
-        fn = getattr(_lib.load(), f"bvhgpu_traverse_box_{self.sfx}")
-        check(fn(self._t, rays._ptr(), tp, rays.n, rays.mem, flags, C.byref(self._hits.h)), self.ctx._h)
-        if not fetch:
-            return None, None
-        return self._hits.fetch_box(rays.n, np.float32 if self.sfx == "f32" else np.float64)
-
     def closest_box_hits(self, rays: RayBatch, tmax=None, fetch: bool = True, coherent: bool = False):
         """bvhgpu_traverse_box_*: per ray the shape of FlatBvh::traverse's list (flat_bvh.rs:396-431) whose own AABB the ray enters first,
         among those with enter < tmax[i] (strict; the first of the list on equal entries), with Ray::intersection_slice_for_aabb's
         (enter, exit) on that box; shape NONE and (+inf, 0) when there is none.  No triangles needed.  tmax as for any_hits.
         returns (slice[n,2], shape[n]); fetch=False returns (None, None) and leaves the result on the tree's result object."""
-        return self._box_hits(rays, tmax, fetch, coherent, False)
+        return self._tmax_batch("box", self._hits.fetch_box, rays, tmax, _ray_flags(coherent), fetch)
 
     def first_box_hits(self, rays: RayBatch, tmax=None, fetch: bool = True, coherent: bool = False):
         """bvhgpu_traverse_box_* with BVHGPU_TRAVERSE_FIRST: the FIRST shape of the ray's list with enter < tmax[i] instead of the
         nearest one (any-hit: every walk stops at it).  returns (slice[n,2], shape[n]) like closest_box_hits."""
-        return self._box_hits(rays, tmax, fetch, coherent, True)
+        return self._tmax_batch("box", self._hits.fetch_box, rays, tmax, _ray_flags(coherent, first=True), fetch)
 
     def box_occluded(self, rays: RayBatch, tmax=None) -> np.ndarray:
         """bool[n]: does ray i enter any shape's box before tmax[i] (first_box_hits(...) shape != NONE)"""
@@ -766,41 +787,20 @@ class _TreeBase:
     def set_spheres(self, spheres) -> None:
         """bvhgpu_tree_set_spheres_*: one sphere per shape, (n,4) [cx, cy, cz, r] in the tree's dtype; numpy or torch GPU tensor.  Independent
         of the AABBs the tree was built from (normally spheres_aabbs(spheres)); never validated."""
-        fn = getattr(_lib.load(), f"bvhgpu_tree_set_spheres_{self.sfx}")
-        if _is_device_tensor(spheres):
-            if str(spheres.dtype) != ("torch.float32" if self.sfx == "f32" else "torch.float64"):
-                raise BvhGpuError(_lib.DTYPE_MISMATCH, "sphere dtype differs from tree dtype")
-            keep = spheres.contiguous()
-            check(fn(self._t, ptr(keep.data_ptr()), keep.numel() // 4, DEVICE), self.ctx._h)
-        else:
-            ft = np.float32 if self.sfx == "f32" else np.float64
-            if isinstance(spheres, np.ndarray) and spheres.dtype != ft:
-                raise BvhGpuError(_lib.DTYPE_MISMATCH, "sphere dtype differs from tree dtype")
-            a = np.ascontiguousarray(spheres, dtype=ft).reshape(-1, 4)
-            check(fn(self._t, ptr(a), len(a), HOST), self.ctx._h)
-
-    def _sphere_hits(self, rays: RayBatch, tmax, fetch: bool, coherent: bool, first: bool):
-        if rays.sfx != self.sfx:
-            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
-        keep, tp = self._tmax_arg(rays, tmax)   # (keep: the array tp points into stays alive over the call)
-        flags = (TRAVERSE_COHERENT if coherent else 0) | (_lib.TRAVERSE_FIRST if first else 0)
-        fn = getattr(_lib.load(), f"bvhgpu_traverse_sphere_{self.sfx}")
-        check(fn(self._t, rays._ptr(), tp, rays.n, rays.mem, flags, C.byref(self._hits.h)), self.ctx._h)
-        if not fetch:
-            return None, None
-        return self._hits.fetch_sphere(rays.n, np.float32 if self.sfx == "f32" else np.float64)
+        _keep, p, n, mem = _rows_in(spheres, 4, self.ft, "sphere")
+        check(getattr(_lib.load(), f"bvhgpu_tree_set_spheres_{self.sfx}")(self._t, p, n, mem), self.ctx._h)
 
     def closest_sphere_hits(self, rays: RayBatch, tmax=None, fetch: bool = True, coherent: bool = False):
         """bvhgpu_traverse_sphere_*: per ray the shape of FlatBvh::traverse's list (flat_bvh.rs:396-431) whose sphere (set_spheres) the ray
         hits nearest, among those with distance < tmax[i] (strict; the first of the list on equal distances), with (distance, exit) on
         that sphere; shape NONE and (+inf, 0) when there is none.  Needs set_spheres, no triangles.  tmax as for any_hits.
         returns (hit[n,2], shape[n]); fetch=False returns (None, None) and leaves the result on the tree's result object."""
-        return self._sphere_hits(rays, tmax, fetch, coherent, False)
+        return self._tmax_batch("sphere", self._hits.fetch_sphere, rays, tmax, _ray_flags(coherent), fetch)
 
     def first_sphere_hits(self, rays: RayBatch, tmax=None, fetch: bool = True, coherent: bool = False):
         """bvhgpu_traverse_sphere_* with BVHGPU_TRAVERSE_FIRST: the FIRST shape of the ray's list whose sphere is hit with distance <
         tmax[i] instead of the nearest one (any-hit: every walk stops at it).  returns (hit[n,2], shape[n]) like closest_sphere_hits."""
-        return self._sphere_hits(rays, tmax, fetch, coherent, True)
+        return self._tmax_batch("sphere", self._hits.fetch_sphere, rays, tmax, _ray_flags(coherent, first=True), fetch)
 
     def sphere_occluded(self, rays: RayBatch, tmax=None) -> np.ndarray:
         """bool[n]: does ray i hit any shape's sphere before tmax[i] (first_sphere_hits(...) shape != NONE)"""
@@ -808,6 +808,26 @@ class _TreeBase:
         return shape != NONE
 
     # ---- multi-hit ray queries ---------------------------------------------------------------
+    def _leaf_kind(self, rays: RayBatch, leaf: str):
+        """what khits_batch and allhits_batch check alike → (BVHGPU_LEAF_* kind, the rays' torch device or None for HOST rays)"""
+        if rays.sfx != self.sfx:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
+        if leaf not in _lib.LEAF_KINDS:
+            raise BvhGpuError(_lib.INVALID_ARG, f"leaf must be one of {sorted(_lib.LEAF_KINDS)}")
+        return _lib.LEAF_KINDS[leaf], rays.device.device if rays.mem == DEVICE else None
+
+    def _alloc_out(self, device, ishape, fshape):
+        """the (shape, values) outputs a kernel writes in place → (shape, values, their two pointers).  device None: numpy, shape as uint32;
+        else torch tensors there, shape as torch.int32, and torch's stream is waited for."""
+        if device is None:
+            shape, vals = np.zeros(ishape, dtype=np.uint32), np.zeros(fshape, dtype=self.ft)
+            return shape, vals, ptr(shape), ptr(vals)
+        import torch
+        shape = torch.empty(ishape, dtype=torch.int32, device=device)
+        vals = torch.empty(fshape, dtype=_torch_ft(self.ft), device=device)
+        _torch_sync(device)
+        return shape, vals, ptr(shape.data_ptr()), ptr(vals.data_ptr())
+
     def khits_batch(self, rays: RayBatch, k: int, leaf: str = "box", tmax=None):
         """bvhgpu_traverse_khits_*: the k nearest hits of every ray.  Row i is the candidates of FlatBvh::traverse's list (flat_bvh.rs:396-431)
         — the members whose leaf-stage distance is < tmax[i], strict — in a stable ascending sort by distance (equal distances in list
@@ -816,28 +836,13 @@ class _TreeBase:
         returns (vals[n, k, W], shape[n, k]), W = 3 for triangles, else 2; slots beyond the number of candidates hold NONE and (+inf, 0[, 0]).
         HOST rays: numpy out, shape as uint32.  Rays in HBM: torch tensors on the same device, written by the kernel with no host round
         trip, shape as torch.int32 — so NONE reads as -1 there."""
-        if rays.sfx != self.sfx:
-            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
-        if leaf not in _lib.LEAF_KINDS:
-            raise BvhGpuError(_lib.INVALID_ARG, f"leaf must be one of {sorted(_lib.LEAF_KINDS)}")
-        kind = _lib.LEAF_KINDS[leaf]
-        w = _lib.LEAF_WIDTH[kind]
+        kind, dev = self._leaf_kind(rays, leaf)
         k = int(k)
         rows = k if 1 <= k <= _lib.KHITS_MAX_K else 0     # (out of range: the engine answers INVALID_ARG before it touches a buffer)
-        keep, tp = self._tmax_arg(rays, tmax)   # (keep: the array tp points into stays alive over the call)
+        _keep, tp = self._tmax_arg(rays, tmax)   # (_keep: the array tp points into stays alive over the call)
+        shape, vals, sp, vp = self._alloc_out(dev, (rays.n, rows), (rays.n, rows, _lib.LEAF_WIDTH[kind]))
         fn = getattr(_lib.load(), f"bvhgpu_traverse_khits_{self.sfx}")
-        if rays.mem == DEVICE:
-            import torch
-            dev = rays.device.device
-            shape = torch.empty((rays.n, rows), dtype=torch.int32, device=dev)
-            vals = torch.empty((rays.n, rows, w), dtype=torch.float32 if self.sfx == "f32" else torch.float64, device=dev)
-            torch.cuda.current_stream(dev).synchronize()   # the engine works on its own stream: the rays must be there
-            check(fn(self._t, rays._ptr(), tp, rays.n, DEVICE, kind, k & 0xFFFFFFFF, ptr(shape.data_ptr()), ptr(vals.data_ptr())), self.ctx._h)
-            return vals, shape
-        ft = np.float32 if self.sfx == "f32" else np.float64
-        shape = np.zeros((rays.n, rows), dtype=np.uint32)
-        vals = np.zeros((rays.n, rows, w), dtype=ft)
-        check(fn(self._t, rays._ptr(), tp, rays.n, HOST, kind, k & 0xFFFFFFFF, ptr(shape), ptr(vals)), self.ctx._h)
+        check(fn(self._t, rays._ptr(), tp, rays.n, rays.mem, kind, k & 0xFFFFFFFF, sp, vp), self.ctx._h)
         return vals, shape
 
     def allhits_batch(self, rays: RayBatch, leaf: str = "box", tmax=None, sort: bool = True):
@@ -847,84 +852,44 @@ class _TreeBase:
         returns (offsets[n+1], shape[total], vals[total, W]), W = 3 for triangles, else 2; no padding.  The first min(k, len) entries of a
         sorted row are khits_batch's row.  HOST rays: numpy out, offsets and shape as uint32.  Rays in HBM: torch tensors on the same
         device, shape as torch.int32, offsets as torch.int64."""
-        if rays.sfx != self.sfx:
-            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from tree dtype")
-        if leaf not in _lib.LEAF_KINDS:
-            raise BvhGpuError(_lib.INVALID_ARG, f"leaf must be one of {sorted(_lib.LEAF_KINDS)}")
-        keep, tp = self._tmax_arg(rays, tmax)   # (keep: the array tp points into stays alive over the call)
+        kind, dev = self._leaf_kind(rays, leaf)
+        _keep, tp = self._tmax_arg(rays, tmax)   # (_keep: the array tp points into stays alive over the call)
+        if dev is not None:
+            _torch_sync(dev)
         fn = getattr(_lib.load(), f"bvhgpu_traverse_allhits_{self.sfx}")
-        dev = None
-        if rays.mem == DEVICE:
-            import torch
-            dev = rays.device.device
-            torch.cuda.current_stream(dev).synchronize()   # the engine works on its own stream: the rays must be there
-        check(fn(self._t, rays._ptr(), tp, rays.n, rays.mem, _lib.LEAF_KINDS[leaf], 0 if sort else _lib.ALLHITS_LIST_ORDER, C.byref(self._hits.h)),
-              self.ctx._h)
-        return self._hits.fetch_allhits(rays.n, leaf, np.float32 if self.sfx == "f32" else np.float64, dev)
+        check(fn(self._t, rays._ptr(), tp, rays.n, rays.mem, kind, 0 if sort else _lib.ALLHITS_LIST_ORDER, C.byref(self._hits.h)), self.ctx._h)
+        return self._hits.fetch_allhits(rays.n, leaf, self.ft, dev)
 
     # ---- point query ---------------------------------------------------------------------
     def nearest_batch(self, points, triangles: bool = False):
         """<FlatBvh as BoundingHierarchy>::nearest_to (flat_bvh.rs:513-562) for many points.  Shape distance: the
         shape's own AABB (UnitBox, testbase.rs:101-105) or, with triangles=True, the closest point on the triangle
-        (testbase.rs:436-443; needs set_triangles).  returns (shape[n] u32 — NONE for an empty hierarchy, dist[n])"""
-        ft = np.float32 if self.sfx == "f32" else np.float64
-        p = np.ascontiguousarray(points, dtype=ft).reshape(-1, 3)
-        shape = np.zeros(len(p), dtype=np.uint32)
-        dist = np.zeros(len(p), dtype=ft)
+        (testbase.rs:436-443; needs set_triangles).  returns (shape[n] u32 — NONE for an empty hierarchy, dist[n]).
+        On a Bvh this is Bvh::nearest_to answered by the flat loop: the distance is the same as the recursive form's
+        (bvh_node.rs:327-374); on exact ties the two reference forms may name different shapes."""
+        self._ready()
+        _keep, pp, n, mem = _rows_in(points, 3, self.ft, "point", convert=True, device=False)
+        shape, dist, sp, dp = self._alloc_out(None, n, n)
         fn = getattr(_lib.load(), f"bvhgpu_nearest_{self.sfx}")
-        check(fn(self._t, ptr(p), len(p), HOST, 1 if triangles else 0, ptr(shape), ptr(dist)), self.ctx._h)
+        check(fn(self._t, pp, n, mem, 1 if triangles else 0, sp, dp), self.ctx._h)
         return shape, dist
+
+    def _points_in(self, points, max_dist):
+        """(n, 3) query points with their per-point limit (None, a scalar or n values in the points' memory) → (points kept alive, their
+        pointer, n, HOST or DEVICE, max_dist kept alive, its pointer or None)"""
+        p, pp, n, mem = _rows_in(points, 3, self.ft, "point")
+        m, mp = _side_in(max_dist, p, n, mem, self.ft, "max_dist", "points", scalar_ok=True)
+        return p, pp, n, mem, m, mp
 
     def _knearest(self, entry: str, points, k: int, triangles: bool, max_dist, with_limit: bool):
         """marshalling of knearest_batch (entry "knearest": no limit argument) and knearest_tree_batch ("knearest_tree": max_dist or NULL)"""
         fn = getattr(_lib.load(), f"bvhgpu_{entry}_{self.sfx}")
-        ft = np.float32 if self.sfx == "f32" else np.float64
         k = int(k)
         rows = k if 1 <= k <= _lib.KNN_MAX_K else 0       # (out of range: the engine answers INVALID_ARG before it touches a buffer)
-        kind = 1 if triangles else 0
-        scalar = max_dist is not None and not _is_device_tensor(max_dist) and np.ndim(max_dist) == 0
-        limit = (lambda mp: (mp,)) if with_limit else (lambda mp: ())   # (bvhgpu_knearest_* has no max_dist argument)
-        if _is_device_tensor(points):
-            import torch
-            if str(points.dtype) != ("torch.float32" if self.sfx == "f32" else "torch.float64"):
-                raise BvhGpuError(_lib.DTYPE_MISMATCH, "point dtype differs from tree dtype")
-            p = points.contiguous()
-            n = p.numel() // 3
-            m, mp = None, None
-            if scalar:
-                m = torch.full((n,), float(max_dist), dtype=p.dtype, device=p.device)
-            elif max_dist is not None:
-                if not _is_device_tensor(max_dist):
-                    raise BvhGpuError(_lib.INVALID_ARG, "max_dist is in host memory but the points are in HBM")
-                if max_dist.dtype != p.dtype:
-                    raise BvhGpuError(_lib.DTYPE_MISMATCH, "max_dist dtype differs from tree dtype")
-                m = max_dist.contiguous()
-            if m is not None:
-                if m.numel() != n:
-                    raise BvhGpuError(_lib.INVALID_ARG, f"max_dist has {m.numel()} values for {n} points")
-                mp = ptr(m.data_ptr())
-            shape = torch.empty((n, rows), dtype=torch.int32, device=p.device)
-            dist = torch.empty((n, rows), dtype=p.dtype, device=p.device)
-            torch.cuda.current_stream(p.device).synchronize()   # the engine works on its own stream: the points must be there
-            check(fn(self._t, ptr(p.data_ptr()), n, DEVICE, kind, k & 0xFFFFFFFF, *limit(mp), ptr(shape.data_ptr()), ptr(dist.data_ptr())), self.ctx._h)
-            return shape, dist
-        if isinstance(points, np.ndarray) and points.dtype != ft:
-            raise BvhGpuError(_lib.DTYPE_MISMATCH, "point dtype differs from tree dtype")
-        p = np.ascontiguousarray(points, dtype=ft).reshape(-1, 3)
-        m = None
-        if scalar:
-            m = np.full(len(p), max_dist, dtype=ft)
-        elif max_dist is not None:
-            if _is_device_tensor(max_dist):
-                raise BvhGpuError(_lib.INVALID_ARG, "max_dist is a GPU tensor but the points are in host memory")
-            if isinstance(max_dist, np.ndarray) and max_dist.dtype != ft:
-                raise BvhGpuError(_lib.DTYPE_MISMATCH, "max_dist dtype differs from tree dtype")
-            m = np.ascontiguousarray(max_dist, dtype=ft).reshape(-1)
-        if m is not None and m.size != len(p):
-            raise BvhGpuError(_lib.INVALID_ARG, f"max_dist has {m.size} values for {len(p)} points")
-        shape = np.zeros((len(p), rows), dtype=np.uint32)
-        dist = np.zeros((len(p), rows), dtype=ft)
-        check(fn(self._t, ptr(p), len(p), HOST, kind, k & 0xFFFFFFFF, *limit(ptr(m)), ptr(shape), ptr(dist)), self.ctx._h)
+        p, pp, n, mem, _m, mp = self._points_in(points, max_dist)   # (p, _m: what the pointers point into stays alive over the call)
+        shape, dist, sp, dp = self._alloc_out(p.device if mem == DEVICE else None, (n, rows), (n, rows))
+        limit = (mp,) if with_limit else ()   # (bvhgpu_knearest_* has no max_dist argument)
+        check(fn(self._t, pp, n, mem, 1 if triangles else 0, k & 0xFFFFFFFF, *limit, sp, dp), self.ctx._h)
         return shape, dist
 
     def knearest_batch(self, points, k: int, triangles: bool = False):
@@ -935,6 +900,7 @@ class _TreeBase:
         returns (shape[n, k], dist[n, k]): rows ascending in dist (a row that holds a NaN need not be sorted), equal distances in leaf
         pre-order; slots beyond the number of shapes hold NONE and +inf.  numpy in: numpy out, shape as uint32.  torch in: torch tensors on
         the same device, written by the kernel with no host round trip, shape as torch.int32 — so NONE reads as -1 there."""
+        self._ready()
         return self._knearest("knearest", points, k, triangles, None, False)
 
     def knearest_tree_batch(self, points, k: int, triangles: bool = False, max_dist=None):
@@ -959,47 +925,16 @@ class _TreeBase:
         every point) or n values in the points' memory.
         returns (offsets[n+1], shape[total], dist[total]); no padding.  numpy in: numpy out, offsets and shape as uint32.  torch in: torch
         tensors on the same device, shape as torch.int32, offsets as torch.int64."""
-        fn = getattr(_lib.load(), f"bvhgpu_within_{self.sfx}")
-        ft = np.float32 if self.sfx == "f32" else np.float64
-        kind = 1 if triangles else 0
         flags = (0 if sort else _lib.WITHIN_LIST_ORDER) | (_lib.WITHIN_COUNT_ONLY if count_only else 0)
         if max_dist is None:
             raise BvhGpuError(_lib.INVALID_ARG, "within_batch needs max_dist (a scalar or one value per point)")
-        scalar = not _is_device_tensor(max_dist) and np.ndim(max_dist) == 0
-        if _is_device_tensor(points):
-            import torch
-            if str(points.dtype) != ("torch.float32" if self.sfx == "f32" else "torch.float64"):
-                raise BvhGpuError(_lib.DTYPE_MISMATCH, "point dtype differs from tree dtype")
-            p = points.contiguous()
-            n = p.numel() // 3
-            if scalar:
-                m = torch.full((n,), float(max_dist), dtype=p.dtype, device=p.device)
-            else:
-                if not _is_device_tensor(max_dist):
-                    raise BvhGpuError(_lib.INVALID_ARG, "max_dist is in host memory but the points are in HBM")
-                if max_dist.dtype != p.dtype:
-                    raise BvhGpuError(_lib.DTYPE_MISMATCH, "max_dist dtype differs from tree dtype")
-                m = max_dist.contiguous()
-            if m.numel() != n:
-                raise BvhGpuError(_lib.INVALID_ARG, f"max_dist has {m.numel()} values for {n} points")
-            torch.cuda.current_stream(p.device).synchronize()   # the engine works on its own stream: the points must be there
-            check(fn(self._t, ptr(p.data_ptr()), ptr(m.data_ptr()), n, DEVICE, kind, flags, C.byref(self._hits.h)), self.ctx._h)
-            return self._hits.fetch_within(n, ft, p.device, count_only)
-        if isinstance(points, np.ndarray) and points.dtype != ft:
-            raise BvhGpuError(_lib.DTYPE_MISMATCH, "point dtype differs from tree dtype")
-        p = np.ascontiguousarray(points, dtype=ft).reshape(-1, 3)
-        if scalar:
-            m = np.full(len(p), max_dist, dtype=ft)
-        else:
-            if _is_device_tensor(max_dist):
-                raise BvhGpuError(_lib.INVALID_ARG, "max_dist is a GPU tensor but the points are in host memory")
-            if isinstance(max_dist, np.ndarray) and max_dist.dtype != ft:
-                raise BvhGpuError(_lib.DTYPE_MISMATCH, "max_dist dtype differs from tree dtype")
-            m = np.ascontiguousarray(max_dist, dtype=ft).reshape(-1)
-        if m.size != len(p):
-            raise BvhGpuError(_lib.INVALID_ARG, f"max_dist has {m.size} values for {len(p)} points")
-        check(fn(self._t, ptr(p), ptr(m), len(p), HOST, kind, flags, C.byref(self._hits.h)), self.ctx._h)
-        return self._hits.fetch_within(len(p), ft, None, count_only)
+        p, pp, n, mem, _m, mp = self._points_in(points, max_dist)   # (p, _m: what the pointers point into stays alive over the call)
+        dev = p.device if mem == DEVICE else None
+        if dev is not None:
+            _torch_sync(dev)
+        fn = getattr(_lib.load(), f"bvhgpu_within_{self.sfx}")
+        check(fn(self._t, pp, mp, n, mem, 1 if triangles else 0, flags, C.byref(self._hits.h)), self.ctx._h)
+        return self._hits.fetch_within(n, self.ft, dev, count_only)
 
     def nearest_to(self, query, shapes: Sequence, triangles: bool = False):
         """BoundingHierarchy::nearest_to (bounding_hierarchy.rs:262-336): Option<(&Shape, distance)>."""
@@ -1035,10 +970,11 @@ class _TreeBase:
     def traverse(self, query, shapes: Sequence) -> List:
         """BoundingHierarchy::traverse (bounding_hierarchy.rs:246-250): the shapes whose AABB `query` intersects, in the
         reference's order.  `query`: a Ray, an Aabb, a Ball / Sphere or a point (the crate's four IntersectsAabb types)."""
+        self._ready()
         if isinstance(query, Ray):
             _, idx, _, _ = self.traverse_batch(query._batch)
         else:
-            kind, row = _query_row(query, np.float32 if self.sfx == "f32" else np.float64)
+            kind, row = _query_row(query, self.ft)
             _, idx = self.query_batch(kind, row.reshape(1, -1))
         return [shapes[i] for i in idx.tolist()]
 
@@ -1049,28 +985,13 @@ class _TreeBase:
         (HOST) or a torch GPU tensor (DEVICE), or None with kind "aabb" for the tree's own shape AABBs (self_overlaps).
         returns (offsets[n+1], indices[total]) in the reference's per-query order; fetch=False returns (None, None) and leaves
         the result in HBM (hits_device)."""
+        self._ready()
         kind = {"aabb": _lib.QUERY_AABB, "point": _lib.QUERY_POINT, "ball": _lib.QUERY_BALL, "sphere": _lib.QUERY_BALL}.get(kind, kind)
-        lib = _lib.load()
-        fn = getattr(lib, f"bvhgpu_query_{self.sfx}")
-        ft = np.float32 if self.sfx == "f32" else np.float64
-        width = _lib.QUERY_WIDTH.get(kind, 1)
-        keep = None
         if queries is None:
-            n = self.info()[0]
-            qp, mem = None, HOST
-        elif _is_device_tensor(queries):
-            if str(queries.dtype) != ("torch.float32" if self.sfx == "f32" else "torch.float64"):
-                raise BvhGpuError(_lib.DTYPE_MISMATCH, "query dtype differs from tree dtype")
-            keep = queries.contiguous()
-            n = keep.numel() // width
-            qp, mem = ptr(keep.data_ptr()), DEVICE
+            _keep, qp, n, mem = None, None, self.info()[0], HOST
         else:
-            if isinstance(queries, np.ndarray) and queries.dtype != ft:
-                raise BvhGpuError(_lib.DTYPE_MISMATCH, "query dtype differs from tree dtype")
-            keep = np.ascontiguousarray(queries, dtype=ft).reshape(-1)
-            n = keep.size // width
-            qp, mem = ptr(keep), HOST
-        check(fn(self._t, kind, qp, n, mem, 0, C.byref(self._hits.h)), self.ctx._h)
+            _keep, qp, n, mem = _rows_in(queries, _lib.QUERY_WIDTH.get(kind, 1), self.ft, "query", exact=False)
+        check(getattr(_lib.load(), f"bvhgpu_query_{self.sfx}")(self._t, kind, qp, n, mem, 0, C.byref(self._hits.h)), self.ctx._h)
         if not fetch:
             return None, None
         return self._hits.fetch(n)
@@ -1092,10 +1013,8 @@ class _TreeBase:
 
     def scene_export(self, dst) -> None:
         """dst: torch uint8 tensor on the GPU (DEVICE) or a numpy uint8 array (HOST)."""
-        if _is_device_tensor(dst):
-            check(_lib.load().bvhgpu_scene_export(self._t, ptr(dst.data_ptr()), DEVICE), self.ctx._h)
-        else:
-            check(_lib.load().bvhgpu_scene_export(self._t, ptr(dst), HOST), self.ctx._h)
+        p, mem = _bytes_in(dst)
+        check(_lib.load().bvhgpu_scene_export(self._t, p, mem), self.ctx._h)
 
 
 class FlatBvh(_TreeBase):
@@ -1125,8 +1044,7 @@ class FlatBvh(_TreeBase):
         """Upload a FlatBvh produced elsewhere (e.g. by the Rust crate via flatten_custom)."""
         ctx = ctx or default_context()
         s = "f32" if flat.dtype == FLAT_F32 else "f64"
-        ft = np.float32 if s == "f32" else np.float64
-        sa = np.ascontiguousarray(shape_aabbs, dtype=ft).reshape(-1, 6)
+        sa = np.ascontiguousarray(shape_aabbs, dtype=_FT[s]).reshape(-1, 6)
         flat = np.ascontiguousarray(flat)
         h = C.c_void_p()
         fn = getattr(_lib.load(), f"bvhgpu_tree_from_flat_{s}")
@@ -1139,10 +1057,8 @@ class FlatBvh(_TreeBase):
         `reuse`: a FlatBvh from an earlier scene_import whose HBM is overwritten in place."""
         ctx = ctx or default_context()
         h = reuse._t if reuse is not None else C.c_void_p()
-        if _is_device_tensor(src):
-            check(_lib.load().bvhgpu_scene_import(ctx._h, ptr(src.data_ptr()), nbytes, DEVICE, C.byref(h)), ctx._h)
-        else:
-            check(_lib.load().bvhgpu_scene_import(ctx._h, ptr(src), nbytes, HOST, C.byref(h)), ctx._h)
+        p, mem = _bytes_in(src)
+        check(_lib.load().bvhgpu_scene_import(ctx._h, p, nbytes, mem, C.byref(h)), ctx._h)
         dt = C.c_int()
         check(_lib.load().bvhgpu_tree_info(h, C.byref(dt), None, None, None), ctx._h)
         if reuse is not None:
@@ -1164,29 +1080,21 @@ class Bvh(_TreeBase):
         if _is_device_tensor(aabbs):
             import torch  # only needed when the caller already uses torch
             s = "f32" if aabbs.dtype == torch.float32 else "f64"
-            n = aabbs.numel() // 6
-            check(getattr(lib, f"bvhgpu_build_{s}")(ctx._h, ptr(aabbs.data_ptr()), n, DEVICE, C.byref(h)), ctx._h)
         else:
-            a = np.asarray(aabbs)
-            if a.dtype not in (np.float32, np.float64):
-                a = a.astype(np.float32)
-            s = _sfx(a.dtype)
-            a = np.ascontiguousarray(a).reshape(-1, 6)
-            check(getattr(lib, f"bvhgpu_build_{s}")(ctx._h, ptr(a), len(a), HOST, C.byref(h)), ctx._h)
+            aabbs = np.asarray(aabbs)
+            if aabbs.dtype not in (np.float32, np.float64):
+                aabbs = aabbs.astype(np.float32)
+            s = _sfx(aabbs.dtype)
+        _keep, p, n, mem = _rows_in(aabbs, 6, _FT[s], "aabb", check_tensor=False)      # (the input's dtype is the tree's)
+        check(getattr(lib, f"bvhgpu_build_{s}")(ctx._h, p, n, mem, C.byref(h)), ctx._h)
         return Bvh(ctx, h, s)
 
     def rebuild(self, aabbs, flatten: bool = False) -> "Bvh":
         """Bvh::build again into the same device buffers (no allocation when n fits).  flatten=True: FlatBvh::build
         (flat_bvh.rs:328-331) — build + flatten in one call."""
-        lib = _lib.load()
-        fn = getattr(lib, f"bvhgpu_rebuild_flat_{self.sfx}" if flatten else f"bvhgpu_rebuild_{self.sfx}")
-        if _is_device_tensor(aabbs):
-            n = aabbs.numel() // 6
-            check(fn(self._t, ptr(aabbs.data_ptr()), n, DEVICE), self.ctx._h)
-        else:
-            ft = np.float32 if self.sfx == "f32" else np.float64
-            a = np.ascontiguousarray(aabbs, dtype=ft).reshape(-1, 6)
-            check(fn(self._t, ptr(a), len(a), HOST), self.ctx._h)
+        fn = getattr(_lib.load(), f"bvhgpu_rebuild_flat_{self.sfx}" if flatten else f"bvhgpu_rebuild_{self.sfx}")
+        _keep, p, n, mem = _rows_in(aabbs, 6, self.ft, "aabb", check_tensor=False, convert=True)
+        check(fn(self._t, p, n, mem), self.ctx._h)
         return self
 
     def rebuild_async(self, aabbs) -> "Bvh":
@@ -1209,7 +1117,7 @@ class Bvh(_TreeBase):
         aabbs (host array, n x 6): bvhgpu_build_traverse_host_* — the tree is rebuilt from them first, underneath the ray upload.
         od6: `origins` is ONE array n x 6 = [o xyz, d xyz] per ray (BVHGPU_TRAVERSE_RAYS_OD6: one transfer per chunk), directions None."""
         lib = _lib.load()
-        ft = np.float32 if self.sfx == "f32" else np.float64
+        ft = self.ft
         if od6:
             assert directions is None and origins.dtype == ft and origins.flags.c_contiguous and origins.size % 6 == 0
             n = origins.size // 6
@@ -1246,14 +1154,8 @@ class Bvh(_TreeBase):
         reproduced — rebuild() when the topology should follow the motion.  Input contract as for a build: with two or more
         shapes a NaN or ±inf component raises INVALID_ARG and leaves the tree exactly as it was; the call returns when that check
         has read the input (one host round trip)."""
-        lib = _lib.load()
-        fn = getattr(lib, f"bvhgpu_refit_{self.sfx}")
-        if _is_device_tensor(aabbs):
-            check(fn(self._t, ptr(aabbs.data_ptr()), aabbs.numel() // 6, DEVICE), self.ctx._h)
-        else:
-            ft = np.float32 if self.sfx == "f32" else np.float64
-            a = np.ascontiguousarray(aabbs, dtype=ft).reshape(-1, 6)
-            check(fn(self._t, ptr(a), len(a), HOST), self.ctx._h)
+        _keep, p, n, mem = _rows_in(aabbs, 6, self.ft, "aabb", check_tensor=False, convert=True)
+        check(getattr(_lib.load(), f"bvhgpu_refit_{self.sfx}")(self._t, p, n, mem), self.ctx._h)
         return self
 
     @staticmethod
@@ -1318,25 +1220,9 @@ class Bvh(_TreeBase):
     def flatten_in_place(self) -> None:
         check(_lib.load().bvhgpu_flatten(self._t), self.ctx._h)
 
-    def traverse(self, query, shapes: Sequence) -> List:
-        """Bvh::traverse (bvh_impl.rs:104-119): same hit list, same order as the flat traversal
-        (bvh_node.rs:288-319 visits the same boxes in the same order)."""
-        self.flatten_in_place()
-        return super().traverse(query, shapes)
-
-    def query_batch(self, kind, queries, fetch: bool = True):
-        self.flatten_in_place()
-        return super().query_batch(kind, queries, fetch)
-
-    def nearest_batch(self, points, triangles: bool = False):
-        """Bvh::nearest_to answered by the flat loop (flat_bvh.rs:513-562): the distance is the same as the
-        recursive form's (bvh_node.rs:327-374); on exact ties the two reference forms may name different shapes."""
-        self.flatten_in_place()
-        return super().nearest_batch(points, triangles)
-
-    def knearest_batch(self, points, k: int, triangles: bool = False):
-        self.flatten_in_place()
-        return super().knearest_batch(points, k, triangles)
+    # Bvh::traverse (bvh_impl.rs:104-119) and the other batch calls are answered by the flat walks: same hit list, same order
+    # (bvh_node.rs:288-319 visits the same boxes in the same order), so a Bvh flattens before each of them
+    _ready = flatten_in_place
 
     def khits_batch(self, rays: RayBatch, k: int, leaf: str = "box", tmax=None):
         self.flatten_in_place()

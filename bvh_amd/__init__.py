@@ -8,6 +8,7 @@ and testbase (the reference's scene and ray generators, used as synthetic inputs
 from ._lib import BvhGpuError, NONE, device_count  # noqa: F401
 from .api import (Aabb, Ball, BHShape, Bounded, Bvh, Context, FlatBvh, HostStep, Ray, RayBatch, Sphere,  # noqa: F401
                   default_context, pinned_array, spheres_aabbs)
+from .instances import Instances  # noqa: F401
 
-__all__ = ["Aabb", "Ball", "Sphere", "BHShape", "Bounded", "Bvh", "Context", "FlatBvh", "HostStep", "pinned_array", "Ray", "RayBatch", "BvhGpuError",
+__all__ = ["Aabb", "Ball", "Sphere", "BHShape", "Bounded", "Bvh", "Context", "FlatBvh", "HostStep", "Instances", "pinned_array", "Ray", "RayBatch", "BvhGpuError",
            "NONE", "device_count", "default_context", "spheres_aabbs"]

@@ -176,6 +176,15 @@ SYMBOLS = [
     ("bvhgpu_within_f32", _i, [_vp, _vp, _vp, _sz, _i, _i, _u, _pp]),
     ("bvhgpu_within_f64", _i, [_vp, _vp, _vp, _sz, _i, _i, _u, _pp]),
     ("bvhgpu_hits_fetch_within", _i, [_vp, _vp, _vp, _vp, _i]),
+    ("bvhgpu_instances_create_f32", _i, [_vp, _vp, _sz, _vp, _vp, _sz, _i, _pp]),
+    ("bvhgpu_instances_create_f64", _i, [_vp, _vp, _sz, _vp, _vp, _sz, _i, _pp]),
+    ("bvhgpu_instances_update_f32", _i, [_vp, _vp, _sz, _i]),
+    ("bvhgpu_instances_update_f64", _i, [_vp, _vp, _sz, _i]),
+    ("bvhgpu_instances_trace_f32", _i, [_vp, _vp, _vp, _sz, _i, _u, _vp, _vp, _vp]),
+    ("bvhgpu_instances_trace_f64", _i, [_vp, _vp, _vp, _sz, _i, _u, _vp, _vp, _vp]),
+    ("bvhgpu_instances_boxes", _i, [_vp, _vp, _i]),
+    ("bvhgpu_instances_info", _i, [_vp, C.POINTER(_i), C.POINTER(_sz), C.POINTER(_sz)]),
+    ("bvhgpu_instances_destroy", None, [_vp]),
     ("bvhgpu_enable_timing", _i, [_vp, _i]),
     ("bvhgpu_last_timings", _i, [_vp, C.POINTER(Timings)]),
     ("bvhgpu_obj_parse", _i, [C.c_char_p, _sz, C.POINTER(C.POINTER(C.c_float)), C.POINTER(_sz), _vp]),

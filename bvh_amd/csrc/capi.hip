@@ -922,6 +922,124 @@ int do_traverse_host(bvhgpu_tree* tree, const T* aabbs, size_t n_shapes, bool re
     });
 }
 
+// ---- instanced scenes: bvhgpu_instances_* (instances.hip) ------------------------------------------------------------------------------
+// The rules every member tree must pass, rule by rule over all members (the first broken rule wins); create and update share them.
+template <typename T> int instances_members_ok(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_trees) {
+    for (size_t k = 0; k < n_trees; k++) if (!trees[k]) return fail(ctx, BVHGPU_INVALID_ARG, "NULL member tree");
+    for (size_t k = 0; k < n_trees; k++)
+        if (trees[k]->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "member tree dtype differs from the instance set's");
+    for (size_t k = 0; k < n_trees; k++)
+        if (trees[k]->ctx != ctx) return fail(ctx, BVHGPU_INVALID_ARG, "member tree belongs to another context");
+    for (size_t k = 0; k < n_trees; k++) { const int rc = settle(trees[k]); if (rc != BVHGPU_OK) return rc; }
+    for (size_t k = 0; k < n_trees; k++)
+        if (!trees[k]->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "member tree is not flattened: call bvhgpu_flatten first");
+    for (size_t k = 0; k < n_trees; k++)
+        if (!trees[k]->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "instances need bvhgpu_tree_set_triangles on every member tree first");
+    return BVHGPU_OK;
+}
+// the pose in the caller's memory becomes the set's own copy and is committed (throws)
+template <typename T> void instances_pose(bvhgpu_instances* s, const T* xforms, int mem) {
+    bvhgpu_ctx* ctx = s->ctx;
+    s->committed = false;
+    const size_t bytes = s->n * 12 * sizeof(T);
+    if (bytes) {
+        s->xforms.reserve(bytes);
+        BVH_HIP(hipMemcpyAsync(s->xforms.p, xforms, bytes, mem == BVHGPU_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    }
+    instances_commit<T>(s);
+}
+template <typename T>
+int do_instances_create(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_trees, const uint32_t* tree_of, const T* xforms, size_t n, int mem,
+                        bvhgpu_instances** out) {
+    if (!ctx || !out) return fail(ctx, BVHGPU_INVALID_ARG, "ctx/out is NULL");
+    *out = nullptr;
+    if ((n_trees && !trees) || (n && (!tree_of || !xforms))) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    { const int rc = instances_members_ok<T>(ctx, trees, n_trees); if (rc != BVHGPU_OK) return rc; }
+    if (n > MAX_SHAPES || n_trees >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "too many instances for u32 flat indices");
+    bvhgpu_instances* s = nullptr;
+    const int rc = guarded(ctx, [&] {
+        use_device(ctx);
+        s = new bvhgpu_instances();
+        s->ctx = ctx; s->dtype = Traits<T>::dtype; s->n = n;
+        s->trees.assign(trees, trees + n_trees);
+        s->top = new bvhgpu_tree();
+        s->top->ctx = ctx; s->top->dtype = Traits<T>::dtype;
+        if (n) {   // the set's own copy of tree_of, and a look at it on the host
+            std::vector<uint32_t> of(n);
+            s->tree_of.reserve(n * 4);
+            BVH_HIP(hipMemcpyAsync(s->tree_of.p, tree_of, n * 4, mem == BVHGPU_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+            if (mem == BVHGPU_DEVICE) BVH_HIP(hipMemcpyAsync(of.data(), tree_of, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+            else std::memcpy(of.data(), tree_of, n * 4);
+            BVH_HIP(hipStreamSynchronize(ctx->stream));
+            for (size_t i = 0; i < n; i++)
+                if (of[i] >= n_trees) return fail(ctx, BVHGPU_INVALID_ARG, "tree_of[i] is not below n_trees");
+        }
+        instances_pose<T>(s, xforms, mem);
+        return (int)BVHGPU_OK;
+    });
+    if (rc != BVHGPU_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        if (s) { if (s->top) bvhgpu_tree_destroy(s->top); delete s; }
+        return rc;
+    }
+    *out = s;
+    return BVHGPU_OK;
+}
+template <typename T> int do_instances_update(bvhgpu_instances* s, const T* xforms, size_t n, int mem) {
+    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    bvhgpu_ctx* ctx = s->ctx;
+    if (n && !xforms) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from transform dtype");
+    { const int rc = instances_members_ok<T>(ctx, s->trees.data(), s->trees.size()); if (rc != BVHGPU_OK) return rc; }
+    if (n != s->n) return fail(ctx, BVHGPU_INVALID_ARG, "update: the number of instances differs from the set's");
+    const int rc = guarded(ctx, [&] { use_device(ctx); instances_pose<T>(s, xforms, mem); return (int)BVHGPU_OK; });
+    if (rc != BVHGPU_OK) (void)hipStreamSynchronize(ctx->stream);   // (the set stays uncommitted: instances_pose cleared the mark first)
+    return rc;
+}
+// do_khits' staging for rays: one layout (rays | tmax | vals | instance | shape), synchronous, and a refused call touches no buffer
+template <typename T>
+int do_instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, unsigned flags, T* out_vals,
+                       uint32_t* out_instance, uint32_t* out_shape) {
+    using Ray = typename Traits<T>::Ray;
+    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    bvhgpu_ctx* ctx = s->ctx;
+    if (n && (!rays || !out_vals || !out_instance || !out_shape)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from ray dtype");
+    if (flags & ~BVHGPU_TRAVERSE_FIRST) return fail(ctx, BVHGPU_INVALID_ARG, "instance trace flags: 0 or BVHGPU_TRAVERSE_FIRST");
+    if (!s->committed) return fail(ctx, BVHGPU_INVALID_ARG, "instances are not committed (the last commit failed): call bvhgpu_instances_update");
+    for (size_t k = 0; k < s->trees.size(); k++) {   // what the commit read of every member must still be what the member holds
+        const bvhgpu_tree* t = s->trees[k];
+        const bvhgpu_instances::Seen& c = s->seen[k];
+        if (t->trav.p != c.trav || t->aabbs.p != c.aabbs || t->tris.p != c.tris || t->n != c.n || t->n_trav != c.n_trav || t->gen != c.gen ||
+            !t->flattened || !t->has_tris || t->pending_build || t->pending_recv)
+            return fail(ctx, BVHGPU_INVALID_ARG, "instances are stale: call bvhgpu_instances_update");
+    }
+    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 rays in one batch");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        const Ray* rd = rays; const T* td = tmax; T* vd = out_vals; uint32_t *id = out_instance, *sd = out_shape;
+        const size_t rb = n * sizeof(Ray), tb = tmax ? n * sizeof(T) : 0, vb = n * 3 * sizeof(T), ib = n * 4;
+        if (mem == BVHGPU_HOST) {
+            ctx->upload.reserve(rb + tb + vb + 2 * ib + 64);
+            char* base = ctx->upload.as<char>();
+            if (rb) BVH_HIP(hipMemcpyAsync(base, rays, rb, hipMemcpyHostToDevice, ctx->stream));
+            if (tb) BVH_HIP(hipMemcpyAsync(base + rb, tmax, tb, hipMemcpyHostToDevice, ctx->stream));
+            rd = reinterpret_cast<const Ray*>(base); td = tb ? reinterpret_cast<const T*>(base + rb) : nullptr;
+            vd = reinterpret_cast<T*>(base + rb + tb); id = reinterpret_cast<uint32_t*>(base + rb + tb + vb); sd = id + n;
+        }
+        instances_trace<T>(s, rd, n ? td : nullptr, n, (flags & BVHGPU_TRAVERSE_FIRST) != 0, vd, id, sd);
+        if (mem == BVHGPU_HOST) {
+            copy_out(ctx, out_vals, vd, vb, BVHGPU_HOST); copy_out(ctx, out_instance, id, ib, BVHGPU_HOST); copy_out(ctx, out_shape, sd, ib, BVHGPU_HOST);
+        } else {
+            BVH_HIP(hipStreamSynchronize(ctx->stream));   // the rows are complete when the call returns, whichever stream reads them next
+        }
+        return (int)BVHGPU_OK;
+    });
+}
+
 }  // namespace
 
 namespace bvhgpu {
@@ -1627,6 +1745,51 @@ void bvhgpu_hits_destroy(bvhgpu_hits* h) {
     if (h->ctx) { (void)hipSetDevice(h->ctx->device); (void)hipStreamSynchronize(h->ctx->stream); }
     detach_waiter(h);   // an asynchronous batch that is never waited for: its tree forgets it
     delete h;
+}
+
+int bvhgpu_instances_create_f32(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_trees, const uint32_t* tree_of, const float* xforms, size_t n,
+                                int mem, bvhgpu_instances** out) {
+    return do_instances_create<float>(ctx, trees, n_trees, tree_of, xforms, n, mem, out);
+}
+int bvhgpu_instances_create_f64(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_trees, const uint32_t* tree_of, const double* xforms, size_t n,
+                                int mem, bvhgpu_instances** out) {
+    return do_instances_create<double>(ctx, trees, n_trees, tree_of, xforms, n, mem, out);
+}
+int bvhgpu_instances_update_f32(bvhgpu_instances* s, const float* xforms, size_t n, int mem) { return do_instances_update<float>(s, xforms, n, mem); }
+int bvhgpu_instances_update_f64(bvhgpu_instances* s, const double* xforms, size_t n, int mem) { return do_instances_update<double>(s, xforms, n, mem); }
+int bvhgpu_instances_trace_f32(bvhgpu_instances* s, const bvhgpu_ray_f32* rays, const float* tmax, size_t n_rays, int mem, unsigned flags,
+                               float* out_vals, uint32_t* out_instance, uint32_t* out_shape) {
+    return do_instances_trace<float>(s, rays, tmax, n_rays, mem, flags, out_vals, out_instance, out_shape);
+}
+int bvhgpu_instances_trace_f64(bvhgpu_instances* s, const bvhgpu_ray_f64* rays, const double* tmax, size_t n_rays, int mem, unsigned flags,
+                               double* out_vals, uint32_t* out_instance, uint32_t* out_shape) {
+    return do_instances_trace<double>(s, rays, tmax, n_rays, mem, flags, out_vals, out_instance, out_shape);
+}
+int bvhgpu_instances_boxes(bvhgpu_instances* s, void* out, int mem) {
+    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    bvhgpu_ctx* ctx = s->ctx;
+    if (s->n && !out) return fail(ctx, BVHGPU_INVALID_ARG, "out is NULL");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (!s->committed) return fail(ctx, BVHGPU_INVALID_ARG, "instances are not committed (the last commit failed): call bvhgpu_instances_update");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        copy_out(ctx, out, s->wboxes.p, s->n * 6 * (s->dtype == BVHGPU_F32 ? 4 : 8), mem);
+        return (int)BVHGPU_OK;
+    });
+}
+int bvhgpu_instances_info(const bvhgpu_instances* s, int* dtype, size_t* n_trees, size_t* n_instances) {
+    if (!s) return BVHGPU_INVALID_ARG;
+    if (dtype) *dtype = s->dtype;
+    if (n_trees) *n_trees = s->trees.size();
+    if (n_instances) *n_instances = s->n;
+    return BVHGPU_OK;
+}
+// frees what the set owns; the member trees are the caller's and may be gone already: they are not looked at
+void bvhgpu_instances_destroy(bvhgpu_instances* s) {
+    if (!s) return;
+    if (s->ctx) { (void)hipSetDevice(s->ctx->device); (void)hipStreamSynchronize(s->ctx->stream); }
+    if (s->top) bvhgpu_tree_destroy(s->top);
+    delete s;
 }
 
 int bvhgpu_enable_timing(bvhgpu_ctx* ctx, int on) {

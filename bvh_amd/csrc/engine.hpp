@@ -302,7 +302,34 @@ struct bvhgpu_hits {
     }
 };
 
+// an instance set (bvhgpu_instances_*, instances.hip): member trees (the caller's), instances (tree slot, 3x4 transform) and the
+// top-level tree over the instances' world boxes, which the set owns
+struct bvhgpu_instances {
+    bvhgpu_ctx* ctx = nullptr;
+    int dtype = BVHGPU_F32;
+    size_t n = 0;               // instances
+    bool committed = false;     // a pose is committed (the last create / update succeeded): trace may run
+    std::vector<bvhgpu_tree*> trees;   // the members: read by the commit and by trace's staleness check, NEVER by destroy
+    struct Seen { const void *trav, *aabbs, *tris; size_t n, n_trav; uint64_t gen; };
+    std::vector<Seen> seen;     // what the commit read of every member (trace refuses when a member no longer matches)
+    std::vector<unsigned char> table_host;   // host image of `table` (alive while its upload is in flight)
+    bvhgpu_tree* top = nullptr; // the top-level tree (built flat over `wboxes` by every commit)
+    bvhgpu::DevBuf tree_of;     // n u32
+    bvhgpu::DevBuf xforms;      // n x 12 T: the pose being committed
+    bvhgpu::DevBuf table;       // n_trees x InstTree<T>
+    bvhgpu::DevBuf bounds;      // n_trees x 6 T: B_t
+    bvhgpu::DevBuf recs;        // n x InstRec<T>: Y_i and the tree slot
+    bvhgpu::DevBuf wboxes;      // n x 6 T: W_i
+};
+
 namespace bvhgpu {
+
+// instances.hip: commit the pose in s->xforms (member tables, B_t, Y_i, W_i, the top-level build; throws Fail::NonFinite on a NaN / infinite
+// world box) and the two-level walk; everything in HBM, on the ctx's stream
+template <typename T> void instances_commit(bvhgpu_instances* s);
+template <typename T>
+void instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n_rays, bool first, T* out_vals_dev,
+                     uint32_t* out_instance_dev, uint32_t* out_shape_dev);
 
 // build.hip
 template <typename T> void build_tree(bvhgpu_tree* t, const T* aabbs_dev, size_t n, bool flatten_after);

@@ -1,0 +1,138 @@
+"""Instanced scenes over the C ABI (include/bvh_mi355x.h, bvhgpu_instances_*): ray queries over transformed copies of trees.
+
+An instance is (member tree, 3x4 object -> world transform); the set keeps a top-level tree over the instances' world boxes.  Everything
+that computes runs on the GPU; this file only marshals, through api._rows_in / api._side_in like every other batch call.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib, api
+from ._lib import DEVICE, NONE, BvhGpuError, check, ptr
+from .api import Context, RayBatch, _Typed
+
+
+class Instances(_Typed):
+    """bvhgpu_instances: `trees` (Bvh / FlatBvh objects of one context and dtype, with set_triangles done; kept referenced), `tree_of[i]`
+    the member of instance i, `transforms` n x 12 or n x 3 x 4 (row-major 3x4, object -> world) in the trees' dtype.  update() is the
+    re-pose and the re-sync: call it after moving instances and after any rebuild, refit or set_triangles of a member tree; a trace on a
+    set whose member was rebuilt since raises INVALID_ARG ("instances are stale")."""
+
+    def __init__(self, trees: Sequence, tree_of, transforms, ctx: Optional[Context] = None):
+        trees = list(trees)
+        self.trees = trees               # (the set borrows their device arrays)
+        self.ctx = ctx or (trees[0].ctx if trees else api.default_context())
+        f64 = isinstance(transforms, np.ndarray) and transforms.dtype == np.float64
+        self.sfx = trees[0].sfx if trees else ("f64" if f64 else "f32")   # (a set without members has no instances either)
+        self._s = None
+        for t in trees:
+            t._ready()                   # (a Bvh flattens here)
+        handles = (C.c_void_p * max(len(trees), 1))(*[t._t for t in trees])
+        _keep, xp, n, mem = api._rows_in(transforms, 12, self.ft, "transform")
+        of = self._tree_of_in(tree_of, n, mem, _keep)
+        h = C.c_void_p()
+        fn = getattr(_lib.load(), f"bvhgpu_instances_create_{self.sfx}")
+        check(fn(self.ctx._h, handles, len(trees), of[1], xp, n, mem, C.byref(h)), self.ctx._h)
+        self._s = h
+        self.n = n
+        self._counted = True
+        self.ctx._child_add()
+        api._live.add(self)
+
+    @staticmethod
+    def _tree_of_in(tree_of, n: int, mem: int, main):
+        """n u32 in the transforms' memory → (the object kept alive, its c_void_p)"""
+        if mem == DEVICE:   # 32-bit integers on the transforms' device (a host list is put there), then the one way in
+            import torch
+            tree_of = torch.as_tensor(tree_of, device=main.device).to(torch.int32).contiguous()
+            api._torch_sync(main.device)
+        elif api._is_device_tensor(tree_of):
+            raise BvhGpuError(_lib.INVALID_ARG, "tree_of is a GPU tensor but the transforms are in host memory")
+        keep, p, m, _ = api._rows_in(tree_of, 1, np.uint32, "tree_of", check_tensor=False, convert=True)
+        if m != n:
+            raise BvhGpuError(_lib.INVALID_ARG, f"tree_of has {m} values for {n} transforms")
+        return keep, p
+
+    def update(self, transforms) -> "Instances":
+        """bvhgpu_instances_update_*: commit a new pose (and whatever the member trees hold now).  A failed update (a NaN in a transform)
+        leaves the set uncommitted: every trace raises until an update succeeds."""
+        for t in self.trees:
+            t._ready()
+        _keep, xp, n, mem = api._rows_in(transforms, 12, self.ft, "transform")
+        if mem == DEVICE:
+            api._torch_sync(_keep.device)
+        check(getattr(_lib.load(), f"bvhgpu_instances_update_{self.sfx}")(self._s, xp, n, mem), self.ctx._h)
+        return self
+
+    def _trace(self, rays: RayBatch, tmax, flags: int):
+        if rays.sfx != self.sfx:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from the instance set's dtype")
+        _keep, tp = api._side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
+        n = rays.n
+        if rays.mem == DEVICE:
+            import torch
+            dev = rays.device.device
+            vals = torch.empty((n, 3), dtype=api._torch_ft(self.ft), device=dev)
+            inst = torch.empty((n,), dtype=torch.int32, device=dev)
+            shape = torch.empty((n,), dtype=torch.int32, device=dev)
+            api._torch_sync(dev)
+            vp, ip, sp = ptr(vals.data_ptr()), ptr(inst.data_ptr()), ptr(shape.data_ptr())
+        else:
+            vals, inst, shape = np.zeros((n, 3), dtype=self.ft), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+            vp, ip, sp = ptr(vals), ptr(inst), ptr(shape)
+        fn = getattr(_lib.load(), f"bvhgpu_instances_trace_{self.sfx}")
+        check(fn(self._s, rays._ptr(), tp, n, rays.mem, flags, vp, ip, sp), self.ctx._h)
+        return vals, inst, shape
+
+    def closest_hits(self, rays: RayBatch, tmax=None):
+        """per ray the nearest triangle hit over all instances with distance < tmax[i] (None: +inf): (vals[n,3] = Intersection{distance, u,
+        v} in the world ray's parameter, instance[n], shape[n] within that instance's tree); a miss is (+inf, 0, 0), NONE, NONE.  HOST rays:
+        numpy out, indices as uint32.  Rays in HBM: torch tensors on the same device, indices as torch.int32 (NONE reads as -1)."""
+        return self._trace(rays, tmax, 0)
+
+    def any_hits(self, rays: RayBatch, tmax=None):
+        """BVHGPU_TRAVERSE_FIRST: the FIRST candidate in walk order (instances in the top level's order, shapes in the member's order) with
+        distance < tmax[i]; returns what closest_hits returns."""
+        return self._trace(rays, tmax, _lib.TRAVERSE_FIRST)
+
+    def occluded(self, rays: RayBatch, tmax=None):
+        """bool[n]: does segment i hit any triangle of any instance"""
+        _, inst, _ = self.any_hits(rays, tmax)
+        return inst != (NONE if isinstance(inst, np.ndarray) else -1)
+
+    @property
+    def world_boxes(self) -> np.ndarray:
+        """W_i of the committed pose, (n, 6) [min xyz, max xyz]"""
+        out = np.zeros((self.n, 6), dtype=self.ft)
+        check(_lib.load().bvhgpu_instances_boxes(self._s, ptr(out), _lib.HOST), self.ctx._h)
+        return out
+
+    def info(self) -> Tuple[int, int]:
+        """(member trees, instances)"""
+        dt, nt, n = C.c_int(), C.c_size_t(), C.c_size_t()
+        check(_lib.load().bvhgpu_instances_info(self._s, C.byref(dt), C.byref(nt), C.byref(n)), self.ctx._h)
+        return int(nt.value), int(n.value)
+
+    def close(self):
+        if getattr(self, "_s", None):
+            if not api._closing:
+                _lib.load().bvhgpu_instances_destroy(self._s)   # (frees what the set owns; never looks at a member tree)
+        self._s = None
+        if getattr(self, "_counted", False):
+            self._counted = False
+            self.ctx._child_drop()
+
+    def __enter__(self) -> "Instances":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -685,6 +685,77 @@ int bvhgpu_within_f64(bvhgpu_tree *tree, const double *points, const double *max
                       bvhgpu_hits **hits);
 int bvhgpu_hits_fetch_within(bvhgpu_hits *hits, uint32_t *offsets, uint32_t *shape, void *dist, int mem);
 
+/* ---- instanced scenes: closest-hit and first-hit ray queries over transformed copies of trees — many copies of one mesh (a forest, a
+ * crowd) with the mesh built once, and rigid motion at the cost of rebuilding a tree over a few dozen object boxes while every object's own
+ * tree stays untouched.  Every operation below is rounded once in the set's dtype T, in the order written, with no contraction (the
+ * discipline of the triangle stage).
+ *  - Instance set.  n_trees member trees and n instances.  A member is a bvhgpu_tree of the set's context and dtype, flattened, with
+ *    triangles set.  Instance i is (tree_of[i], X_i).  X_i is 12 scalars, row-major 3x4 (m[k][j] = x[4k + j]), object -> world:
+ *        w[k] = ((m[k][0]*p[0] + m[k][1]*p[1]) + m[k][2]*p[2]) + m[k][3]
+ *  - Inverse Y_i (world -> object), computed on the device once per pose.  The nine cofactors are each a*b - c*d, two rounded products and
+ *    one subtraction:
+ *        C00 = m11*m22 - m12*m21    C01 = m12*m20 - m10*m22    C02 = m10*m21 - m11*m20
+ *        C10 = m02*m21 - m01*m22    C11 = m00*m22 - m02*m20    C12 = m01*m20 - m00*m21
+ *        C20 = m01*m12 - m02*m11    C21 = m02*m10 - m00*m12    C22 = m00*m11 - m01*m10
+ *        det = (m00*C00 + m01*C01) + m02*C02        r = 1/det        y[k][j] = C[j][k] * r   (j, k < 3)
+ *        y[k][3] = -(((y[k][0]*m03) + (y[k][1]*m13)) + y[k][2]*m23)
+ *    Nothing is validated: a singular matrix follows the arithmetic.
+ *  - Tree bounds B_t.  The component-wise min of the mins and max of the maxes over the member's shape AABBs as the tree holds them, with
+ *    -0 below +0.  The reduction is exact and order-free for NaN-free boxes; a tree built here cannot hold a NaN box.  For an uploaded tree
+ *    with a NaN box B_t is unspecified.
+ *  - World box W_i.  The min and max (again -0 below +0) over the 8 corners of B_tree_of[i], each mapped by the forward formula; bit k of
+ *    the corner number picks the max on axis k.
+ *  - Top level.  The tree bvhgpu_build_flat_* builds over W_0 .. W_{n-1}.  The builder's input check therefore refuses a NaN or infinite
+ *    world box with BVHGPU_INVALID_ARG (a NaN in a transform, a member without shapes).  n == 1 and n == 0 behave as they do for any tree.
+ *  - Ray j with tmax[j] (NULL: +inf).  I_j = FlatBvh::traverse(ray_j, W) over the top level, in its order.  For each instance i in I_j the
+ *    object-space ray r' is
+ *        o'[k] = ((y[k][0]*o[0] + y[k][1]*o[1]) + y[k][2]*o[2]) + y[k][3]
+ *        d'[k] = (y[k][0]*d[0] + y[k][1]*d[1]) + y[k][2]*d[2]                inv'[k] = 1/d'[k]
+ *    d' is NOT renormalised, so the parameter of an object-space hit is the world ray's parameter and distances compare across instances.
+ *    L' = FlatBvh::traverse(r', shapes of the member), in its order; for each s in L': isect = Ray::intersects_triangle(r', triangle s).
+ *  - Closest (flags 0).  Among all (i, s) in that double order the candidates are those with isect.distance < tmax[j], strict and in T.  The
+ *    winner is chosen by the rule BVHGPU_TRAVERSE_CLOSEST uses within one tree, carried across instances: strict <, the earlier candidate
+ *    keeps a tie.
+ *  - First (BVHGPU_TRAVERSE_FIRST).  The first (i, s) in that order with isect.distance < tmax[j].
+ *  - Output per ray: {distance, u, v}, the instance index and the shape index within that instance's tree.  A miss is {+inf, 0, 0},
+ *    BVHGPU_NONE, BVHGPU_NONE.
+ *  - No pruning.  No inner node and no instance is skipped because of tmax or of the best distance so far.
+ *  - Trees.  Every tree the binary walks accept as a member: built here, refitted, an uploaded FlatBvh, scene-imported, trees with empty
+ *    child bounds, with one shape.
+ * Memory.  `trees` is always a host array of handles.  In create / update `mem` covers `xforms` and `tree_of`; in trace it covers `rays`,
+ * `tmax` and the three outputs.  Every call is synchronous.
+ * Commit.  create and update both commit a pose: they read every member's arrays (completing a lazy flatten), counts and generation,
+ * compute B_t, Y_i and W_i and rebuild the top level.  update is the re-pose AND the re-sync: call it after moving instances and after any
+ * rebuild, refit or bvhgpu_tree_set_triangles of a member.  A commit that fails (a NaN or infinite world box) leaves the set uncommitted:
+ * trace and boxes return BVHGPU_INVALID_ARG until an update succeeds; a failed create returns no set.  A refused update (the rules below)
+ * changes nothing: the set keeps the pose it had.
+ * Stale sets.  trace compares every member's current arrays, counts and generation with the committed ones and refuses with
+ * BVHGPU_INVALID_ARG, "instances are stale: call bvhgpu_instances_update", when any differ — before anything is launched.  The check
+ * cannot see a refit, which keeps both the arrays and the generation: after a refit without an update, trace answers over the new member
+ * boxes inside the old world boxes.  The member trees must outlive every call on the set except bvhgpu_instances_destroy, which frees what
+ * the set owns and never looks at a member.
+ * Refused, touching no buffer, the first broken rule in this order: NULL arguments (ctx, out, the set, a needed array, a member);
+ * a `mem` that is neither BVHGPU_HOST nor BVHGPU_DEVICE; a member, or the call, of another dtype than the set's (BVHGPU_DTYPE_MISMATCH);
+ * a member of another context; what the settle of a member's asynchronous build returns; a member that is not flattened
+ * (BVHGPU_NOT_FLATTENED); a member without triangles; n > (2^32-2)/3 (BVHGPU_OVERFLOW); tree_of[i] >= n_trees; in update, n other than the
+ * set's n; in trace, a flag bit other than BVHGPU_TRAVERSE_FIRST, an uncommitted set, a stale set, n_rays >= 2^32-1 (BVHGPU_OVERFLOW).
+ * Everything not marked is BVHGPU_INVALID_ARG.  n_rays == 0 is fine.  n == 0 is fine: every ray misses.
+ * bvhgpu_instances_boxes: W_i of the committed pose, n x 6 T {min xyz, max xyz}, copied to `mem`. */
+typedef struct bvhgpu_instances bvhgpu_instances;
+int bvhgpu_instances_create_f32(bvhgpu_ctx *ctx, bvhgpu_tree *const *trees, size_t n_trees, const uint32_t *tree_of, const float *xforms, size_t n,
+                                int mem, bvhgpu_instances **out);
+int bvhgpu_instances_create_f64(bvhgpu_ctx *ctx, bvhgpu_tree *const *trees, size_t n_trees, const uint32_t *tree_of, const double *xforms, size_t n,
+                                int mem, bvhgpu_instances **out);
+int bvhgpu_instances_update_f32(bvhgpu_instances *s, const float *xforms, size_t n, int mem);
+int bvhgpu_instances_update_f64(bvhgpu_instances *s, const double *xforms, size_t n, int mem);
+int bvhgpu_instances_trace_f32(bvhgpu_instances *s, const bvhgpu_ray_f32 *rays, const float *tmax, size_t n_rays, int mem, unsigned flags,
+                               float *out_vals /* n x 3 */, uint32_t *out_instance, uint32_t *out_shape);
+int bvhgpu_instances_trace_f64(bvhgpu_instances *s, const bvhgpu_ray_f64 *rays, const double *tmax, size_t n_rays, int mem, unsigned flags,
+                               double *out_vals /* n x 3 */, uint32_t *out_instance, uint32_t *out_shape);
+int bvhgpu_instances_boxes(bvhgpu_instances *s, void *out, int mem);
+int bvhgpu_instances_info(const bvhgpu_instances *s, int *dtype, size_t *n_trees, size_t *n_instances);
+void bvhgpu_instances_destroy(bvhgpu_instances *s);
+
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */
 typedef struct { float build_ms, flatten_ms, traverse_kernel_ms, traverse_total_ms; } bvhgpu_timings;

@@ -57,6 +57,7 @@ pub const BVHGPU_QUERY_BALL: c_int = 3;
 #[repr(C)] pub struct bvhgpu_tree { _p: [u8; 0] }
 #[repr(C)] pub struct bvhgpu_hits { _p: [u8; 0] }
 #[repr(C)] pub struct bvhgpu_comm { _p: [u8; 0] }
+#[repr(C)] pub struct bvhgpu_instances { _p: [u8; 0] }
 
 /// POD image of `enum BvhNode<f32,3>` (src/bvh/bvh_node.rs:21-47); `shape == u32::MAX` ⇒ inner node
 #[repr(C)] #[derive(Clone, Copy, Debug, Default, PartialEq)]
@@ -208,6 +209,16 @@ extern "C" {
     pub fn bvhgpu_traverse_sphere_f32(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_traverse_sphere_f64(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_hits_fetch_sphere(h: *mut bvhgpu_hits, slice: *mut c_void, shape: *mut u32, mem: c_int) -> c_int;
+    // instanced scenes: a top-level tree over the world boxes of (member tree, 3x4 transform) pairs; closest / first hit per ray as {distance, u, v}, instance, shape
+    pub fn bvhgpu_instances_create_f32(ctx: *mut bvhgpu_ctx, trees: *const *mut bvhgpu_tree, n_trees: usize, tree_of: *const u32, xforms: *const f32, n: usize, mem: c_int, out: *mut *mut bvhgpu_instances) -> c_int;
+    pub fn bvhgpu_instances_create_f64(ctx: *mut bvhgpu_ctx, trees: *const *mut bvhgpu_tree, n_trees: usize, tree_of: *const u32, xforms: *const f64, n: usize, mem: c_int, out: *mut *mut bvhgpu_instances) -> c_int;
+    pub fn bvhgpu_instances_update_f32(s: *mut bvhgpu_instances, xforms: *const f32, n: usize, mem: c_int) -> c_int;
+    pub fn bvhgpu_instances_update_f64(s: *mut bvhgpu_instances, xforms: *const f64, n: usize, mem: c_int) -> c_int;
+    pub fn bvhgpu_instances_trace_f32(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, flags: c_uint, out_vals: *mut f32, out_instance: *mut u32, out_shape: *mut u32) -> c_int;
+    pub fn bvhgpu_instances_trace_f64(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, flags: c_uint, out_vals: *mut f64, out_instance: *mut u32, out_shape: *mut u32) -> c_int;
+    pub fn bvhgpu_instances_boxes(s: *mut bvhgpu_instances, out: *mut c_void, mem: c_int) -> c_int;
+    pub fn bvhgpu_instances_info(s: *const bvhgpu_instances, dtype: *mut c_int, n_trees: *mut usize, n_instances: *mut usize) -> c_int;
+    pub fn bvhgpu_instances_destroy(s: *mut bvhgpu_instances);
     // timing, scene ingest, tuning
     pub fn bvhgpu_enable_timing(ctx: *mut bvhgpu_ctx, on: c_int) -> c_int;
     pub fn bvhgpu_last_timings(ctx: *mut bvhgpu_ctx, out: *mut bvhgpu_timings) -> c_int;

@@ -787,6 +787,84 @@ impl<T: GpuScalar> Drop for GpuBvh<T> {
     }
 }
 
+/// Result of an instanced ray query (`GpuInstances::trace`): the `Intersection` in the world ray's parameter, the instance and the shape
+/// within that instance's tree; `instance == shape == u32::MAX` and `distance == +inf` when the ray hits nothing
+pub struct InstanceHit<T> {
+    pub intersection: Intersection<T>,
+    pub instance: u32,
+    pub shape: u32,
+}
+
+/// An instanced scene (`bvhgpu_instances_*`): transformed copies of member trees under a top-level tree over their world boxes.  The
+/// member trees are raw handles of ONE context (`GpuBvh::raw`, `upload_flat`), flattened and with triangles set; they are only borrowed
+/// and must outlive every call except the drop.  Transforms are row-major 3x4, object -> world.
+pub struct GpuInstances<T: GpuScalar> {
+    ctx: *mut ffi::bvhgpu_ctx,
+    set: *mut ffi::bvhgpu_instances,
+    n: usize,
+    _t: core::marker::PhantomData<T>,
+}
+
+impl<T: GpuScalar> GpuInstances<T> {
+    /// # Safety
+    /// `ctx` and every handle in `trees` are live handles of this library, and the trees were made on `ctx`.
+    pub unsafe fn new(ctx: *mut ffi::bvhgpu_ctx, trees: &[*mut ffi::bvhgpu_tree], tree_of: &[u32], xforms: &[[T; 12]]) -> GpuInstances<T> {
+        assert_eq!(tree_of.len(), xforms.len(), "one tree slot and one transform per instance");
+        let mut set = core::ptr::null_mut();
+        let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+            ffi::bvhgpu_instances_create_f32(ctx, trees.as_ptr(), trees.len(), tree_of.as_ptr(), xforms.as_ptr().cast(), xforms.len(), ffi::BVHGPU_HOST, &mut set)
+        } else {
+            ffi::bvhgpu_instances_create_f64(ctx, trees.as_ptr(), trees.len(), tree_of.as_ptr(), xforms.as_ptr().cast(), xforms.len(), ffi::BVHGPU_HOST, &mut set)
+        };
+        check(ctx, rc);
+        GpuInstances { ctx, set, n: xforms.len(), _t: core::marker::PhantomData }
+    }
+
+    /// The re-pose and the re-sync: after moving instances, and after any rebuild, refit or `set_triangles` of a member tree
+    pub fn update(&mut self, xforms: &[[T; 12]]) {
+        assert_eq!(xforms.len(), self.n, "one transform per instance");
+        let rc = unsafe {
+            if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_update_f32(self.set, xforms.as_ptr().cast(), xforms.len(), ffi::BVHGPU_HOST)
+            } else {
+                ffi::bvhgpu_instances_update_f64(self.set, xforms.as_ptr().cast(), xforms.len(), ffi::BVHGPU_HOST)
+            }
+        };
+        check(self.ctx, rc);
+    }
+
+    /// Per ray the nearest candidate over all instances (`first == false`) or the first one in walk order (`first == true`), among those
+    /// with `distance < tmax[j]` (`None`: +inf)
+    pub fn trace(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>, first: bool) -> Vec<InstanceHit<T>> {
+        if let Some(m) = tmax {
+            assert_eq!(m.len(), rays.len(), "tmax needs one value per ray");
+        }
+        let raw: Vec<T::RayC> = rays.iter().map(T::ray_to_ffi).collect();
+        let n = raw.len();
+        let mut vals = vec![T::default(); 3 * n];
+        let mut inst = vec![0u32; n];
+        let mut shape = vec![0u32; n];
+        let flags: c_uint = if first { ffi::BVHGPU_TRAVERSE_FIRST } else { 0 };
+        let rc = unsafe {
+            if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_trace_f32(self.set, raw.as_ptr().cast(), tmax.map_or(core::ptr::null(), |m| m.as_ptr().cast()), n, ffi::BVHGPU_HOST,
+                                                flags, vals.as_mut_ptr().cast(), inst.as_mut_ptr(), shape.as_mut_ptr())
+            } else {
+                ffi::bvhgpu_instances_trace_f64(self.set, raw.as_ptr().cast(), tmax.map_or(core::ptr::null(), |m| m.as_ptr().cast()), n, ffi::BVHGPU_HOST,
+                                                flags, vals.as_mut_ptr().cast(), inst.as_mut_ptr(), shape.as_mut_ptr())
+            }
+        };
+        check(self.ctx, rc);
+        (0..n).map(|j| InstanceHit { intersection: Intersection::new(vals[3 * j], vals[3 * j + 1], vals[3 * j + 2]), instance: inst[j], shape: shape[j] }).collect()
+    }
+}
+
+impl<T: GpuScalar> Drop for GpuInstances<T> {
+    fn drop(&mut self) {
+        unsafe { ffi::bvhgpu_instances_destroy(self.set) };   // (never looks at a member tree)
+    }
+}
+
 /// Traverse a crate-built `Bvh` on the GPU: `Bvh::flatten_custom` (src/flat_bvh.rs:240-251) lets the caller choose the node
 /// type, so the `#[repr(C)]` layout of the C ABI needs no change to the crate.
 pub fn upload_flat<T: GpuScalar>(bvh: &Bvh<T, 3>, shape_aabbs: &[[T; 6]], device: i32) -> (*mut ffi::bvhgpu_ctx, *mut ffi::bvhgpu_tree) {

@@ -9,6 +9,7 @@ from ._lib import BvhGpuError, NONE, device_count  # noqa: F401
 from .api import (Aabb, Ball, BHShape, Bounded, Bvh, Context, FlatBvh, HostStep, Ray, RayBatch, Sphere,  # noqa: F401
                   default_context, pinned_array, spheres_aabbs)
 from .instances import Instances  # noqa: F401
+from .region import aabb_planes, frustum_planes, region_batch  # noqa: F401
 
 __all__ = ["Aabb", "Ball", "Sphere", "BHShape", "Bounded", "Bvh", "Context", "FlatBvh", "HostStep", "Instances", "pinned_array", "Ray", "RayBatch", "BvhGpuError",
-           "NONE", "device_count", "default_context", "spheres_aabbs"]
+           "NONE", "device_count", "default_context", "spheres_aabbs", "aabb_planes", "frustum_planes", "region_batch"]

@@ -27,6 +27,9 @@ LEAF_WIDTH = {LEAF_BOX: 2, LEAF_TRIANGLE: 3, LEAF_SPHERE: 2}   # scalars per rec
 ALLHITS_LIST_ORDER = 1   # BVHGPU_ALLHITS_LIST_ORDER: rows of bvhgpu_traverse_allhits_* in list order, no sort pass
 WITHIN_LIST_ORDER = 1    # BVHGPU_WITHIN_LIST_ORDER: rows of bvhgpu_within_* in the order the loop met them, no sort pass
 WITHIN_COUNT_ONLY = 2    # BVHGPU_WITHIN_COUNT_ONLY: offsets and total only
+REGION_MAX_PLANES = 32   # BVHGPU_REGION_MAX_PLANES: most planes per region of bvhgpu_region_*
+REGION_COUNT_ONLY = 1    # BVHGPU_REGION_COUNT_ONLY: offsets and total only
+REGION_CLASSIFY = 2      # BVHGPU_REGION_CLASSIFY: one byte per reported shape, 1 = its AABB lies wholly inside
 TRAVERSE_T_SLICE = 1
 TRAVERSE_STATS = 2
 TRAVERSE_TRIANGLES = 4
@@ -176,6 +179,10 @@ SYMBOLS = [
     ("bvhgpu_within_f32", _i, [_vp, _vp, _vp, _sz, _i, _i, _u, _pp]),
     ("bvhgpu_within_f64", _i, [_vp, _vp, _vp, _sz, _i, _i, _u, _pp]),
     ("bvhgpu_hits_fetch_within", _i, [_vp, _vp, _vp, _vp, _i]),
+    ("bvhgpu_region_f32", _i, [_vp, _vp, _sz, C.c_uint32, _i, _u, _pp]),
+    ("bvhgpu_region_f64", _i, [_vp, _vp, _sz, C.c_uint32, _i, _u, _pp]),
+    ("bvhgpu_hits_fetch_region", _i, [_vp, _vp, _vp, _vp, _i]),
+    ("bvhgpu_hits_region_info", _i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("bvhgpu_instances_create_f32", _i, [_vp, _vp, _sz, _vp, _vp, _sz, _i, _pp]),
     ("bvhgpu_instances_create_f64", _i, [_vp, _vp, _sz, _vp, _vp, _sz, _i, _pp]),
     ("bvhgpu_instances_update_f32", _i, [_vp, _vp, _sz, _i]),

@@ -286,7 +286,7 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
     }
     if ((flags & BVHGPU_TRAVERSE_TRIANGLES) && (flags & BVHGPU_TRAVERSE_CLOSEST))
         return fail(ctx, BVHGPU_INVALID_ARG, "TRIANGLES and CLOSEST are alternatives");
-    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT | TRAVERSE_SPHERE_HIT | TRAVERSE_ALLHITS | TRAVERSE_WITHIN);   // (internal: only bvhgpu_traverse_any_* / _box_* / _sphere_* / _allhits_* and bvhgpu_within_* set them)
+    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT | TRAVERSE_SPHERE_HIT | TRAVERSE_ALLHITS | TRAVERSE_WITHIN | TRAVERSE_REGION);   // (internal: only bvhgpu_traverse_any_* / _box_* / _sphere_* / _allhits_*, bvhgpu_within_* and bvhgpu_region_* set them)
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
@@ -675,6 +675,42 @@ int do_within(bvhgpu_tree* t, const T* points, const T* max_dist, size_t n, int 
         const T* md = n ? static_cast<const T*>(h->pend_tmax) : nullptr;
         h->pend_tmax = nullptr;                    // (nothing replays this batch)
         within_batch<T>(t, dev, md, n, kind, flags, h);
+        return (int)BVHGPU_OK;
+    });
+}
+
+// ---- convex-region (plane-set) batches: bvhgpu_region_* ----------------------------------------------------------------------------------
+// do_within's shape with n x m planes in place of points and limits; the result goes to a result object (region.hip), whose buffers a
+// later batch of any kind reuses.  HOST planes are staged into the result object like host queries.  A refused call touches no buffer
+// and leaves *hits as it was.
+template <typename T>
+int do_region(bvhgpu_tree* t, const T* planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits** hits) {
+    if (!t) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL tree");
+    bvhgpu_ctx* ctx = t->ctx;
+    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
+    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
+    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
+    if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from plane dtype");
+    if (!t->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    if (m > BVHGPU_REGION_MAX_PLANES) return fail(ctx, BVHGPU_INVALID_ARG, "more than BVHGPU_REGION_MAX_PLANES planes per region");
+    if (n && m && !planes) return fail(ctx, BVHGPU_INVALID_ARG, "planes is NULL");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (flags & ~(BVHGPU_REGION_COUNT_ONLY | BVHGPU_REGION_CLASSIFY))
+        return fail(ctx, BVHGPU_INVALID_ARG, "region flags: BVHGPU_REGION_COUNT_ONLY and BVHGPU_REGION_CLASSIFY only");
+    if (t->exact_only && !t->built && !t->unfolded)
+        return fail(ctx, BVHGPU_INVALID_ARG, "an imported tree whose build had a split without SAH winner: its leaves' navigator boxes were folded away");
+    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 regions in one batch");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        bvhgpu_hits* h = batch_hits(hits);
+        const T* dev = planes;
+        const size_t bytes = n * m * 4 * sizeof(T);
+        if (mem == BVHGPU_HOST && bytes) {
+            h->qbuf.reserve(bytes);
+            BVH_HIP(hipMemcpyAsync(h->qbuf.p, planes, bytes, hipMemcpyHostToDevice, ctx->stream));
+            dev = h->qbuf.as<T>();
+        }
+        region_batch<T>(t, dev, n, m, flags, h);
         return (int)BVHGPU_OK;
     });
 }
@@ -1477,6 +1513,12 @@ int bvhgpu_within_f32(bvhgpu_tree* t, const float* points, const float* max_dist
 int bvhgpu_within_f64(bvhgpu_tree* t, const double* points, const double* max_dist, size_t n, int mem, int kind, unsigned flags, bvhgpu_hits** hits) {
     return do_within<double>(t, points, max_dist, n, mem, kind, flags, hits);
 }
+int bvhgpu_region_f32(bvhgpu_tree* t, const float* planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_region<float>(t, planes, n, m, mem, flags, hits);
+}
+int bvhgpu_region_f64(bvhgpu_tree* t, const double* planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_region<double>(t, planes, n, m, mem, flags, hits);
+}
 int bvhgpu_ray_triangle_pairs_f32(bvhgpu_ctx* ctx, const bvhgpu_ray_f32* rays, const float* tris, size_t n, int mem, float* out) {
     return do_pairs<float>(ctx, rays, tris, n, mem, out);
 }
@@ -1609,6 +1651,7 @@ int bvhgpu_hits_fetch_triangles(bvhgpu_hits* h, void* isect, int mem) {
     if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "a sphere-hit batch has no triangle values: use bvhgpu_hits_fetch_sphere");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
+    if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
     if (!(h->flags & BVHGPU_TRAVERSE_TRIANGLES)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_TRIANGLES");
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -1625,6 +1668,7 @@ static int fetch_per_ray(bvhgpu_hits* h, void* values, uint32_t* shape, int mem,
         return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
+    if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
     if (!(h->flags & kind_bit)) return fail(ctx, BVHGPU_INVALID_ARG, other_kind_msg);
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -1675,6 +1719,7 @@ int bvhgpu_hits_fetch(bvhgpu_hits* h, uint32_t* offsets, uint32_t* indices, void
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "an all-hits batch has a CSR of its own: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
+    if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
     if (tslice && !(h->flags & BVHGPU_TRAVERSE_T_SLICE)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_T_SLICE");
     if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR: use bvhgpu_hits_fetch_closest");
     if (h->flags & TRAVERSE_ANY_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR: use bvhgpu_hits_fetch_any");
@@ -1695,6 +1740,7 @@ int bvhgpu_hits_fetch_allhits(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
+    if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
     if (!(h->flags & TRAVERSE_ALLHITS)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_traverse_allhits_* batch");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
     return guarded(ctx, [&] {
@@ -1713,6 +1759,7 @@ int bvhgpu_hits_fetch_within(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape,
     if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
     if (!(h->flags & TRAVERSE_WITHIN)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_within_* batch");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
     return guarded(ctx, [&] {
@@ -1725,11 +1772,46 @@ int bvhgpu_hits_fetch_within(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape,
     });
 }
 
+// the CSR of a region batch: offsets (n + 1 u32), the shapes (total u32), the inside bytes (total, CLASSIFY batches); each may be NULL.  A
+// COUNT_ONLY batch has offsets only, whatever `total` says.  Every other kind of result is refused, each with its own message.
+int bvhgpu_hits_fetch_region(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape, void* inside, int mem) {
+    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = h->ctx;
+    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
+    if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
+    if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
+    if (h->flags & TRAVERSE_BOX_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_box_* batch: use bvhgpu_hits_fetch_box");
+    if (h->flags & TRAVERSE_ANY_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_any_* batch: use bvhgpu_hits_fetch_any");
+    if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a CLOSEST batch: use bvhgpu_hits_fetch_closest");
+    if (!(h->flags & TRAVERSE_REGION)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_region_* batch: use bvhgpu_hits_fetch");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (inside && !h->rg_classify) return fail(ctx, BVHGPU_INVALID_ARG, "the region batch was run without BVHGPU_REGION_CLASSIFY");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        const size_t rows = h->wi_count_only ? 0 : (size_t)h->total;
+        if (offsets) copy_out(ctx, offsets, h->rg_offsets.p, (h->n_rays + 1) * 4, mem);
+        if (shape && rows) copy_out(ctx, shape, h->indices.p, rows * 4, mem);
+        if (inside && rows) copy_out(ctx, inside, h->rg_inside.p, rows, mem);
+        return (int)BVHGPU_OK;
+    });
+}
+
+int bvhgpu_hits_region_info(const bvhgpu_hits* h, uint32_t* n_chunks, uint32_t* chunk_entries) {
+    if (!h) return BVHGPU_INVALID_ARG;
+    if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (!(h->flags & TRAVERSE_REGION)) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_region_* batch");
+    if (n_chunks) *n_chunks = h->rg_chunks;
+    if (chunk_entries) *chunk_entries = h->rg_chunk_entries;
+    return BVHGPU_OK;
+}
+
 int bvhgpu_hits_device(const bvhgpu_hits* h, const uint32_t** offsets, const uint32_t** indices, const void** tslice) {
     if (!h) return BVHGPU_INVALID_ARG;
     if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_ALLHITS) return fail(h->ctx, BVHGPU_INVALID_ARG, "an all-hits batch has a CSR of its own: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
+    if (h->flags & TRAVERSE_REGION) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
     if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(h->ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR");
     if (h->flags & TRAVERSE_ANY_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR");
     if (h->flags & TRAVERSE_BOX_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "a box-hit batch produces no CSR");

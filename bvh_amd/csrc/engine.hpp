@@ -51,6 +51,9 @@ constexpr unsigned TRAVERSE_ALLHITS = 1u << 28;
 // result objects of bvhgpu_within_* (within.hip): marked the same way; the only bit such a result carries.  (The caller flags end at
 // BVHGPU_TRAVERSE_FIRST = 1u << 10, and BVHGPU_WITHIN_* are never stored in bvhgpu_hits::flags.)
 constexpr unsigned TRAVERSE_WITHIN = 1u << 27;
+// result objects of bvhgpu_region_* (region.hip): marked the same way; the only bit such a result carries (BVHGPU_REGION_* are never
+// stored in bvhgpu_hits::flags)
+constexpr unsigned TRAVERSE_REGION = 1u << 26;
 
 }  // namespace bvhgpu
 
@@ -293,6 +296,13 @@ struct bvhgpu_hits {
     // within batches (bvhgpu_within_*, within.hip) reuse them: the CSR is `offsets` / `indices` (the shapes) / `ah_vals` (total T distances)
     bool wi_count_only = false;          // BVHGPU_WITHIN_COUNT_ONLY: `offsets` and `total` only, no shapes and no distances
     bvhgpu::DevBuf wi_unfold;            // the FlatNode array of a built tree with empty child bounds as an unfolded TravNode array (within.hip)
+    // region batches (bvhgpu_region_*, region.hip): `offsets` holds the scanned counts of the (region, chunk) units, `rg_offsets` the caller's
+    // n + 1 row offsets gathered from them; the CSR is `rg_offsets` / `indices` (the shapes) / `rg_inside` (total bytes, CLASSIFY).  HOST planes
+    // are staged in `qbuf`, a COUNT_ONLY batch sets wi_count_only, a tree with empty child bounds is mirrored into wi_unfold.
+    bvhgpu::DevBuf rg_offsets, rg_inside;
+    bvhgpu::DevBuf rg_anc;               // per chunk of the batch: its ancestor count, then REGION_ANC_MAX ancestor entries (rebuilt by every batch)
+    uint32_t rg_chunks = 0, rg_chunk_entries = 0;   // how the batch cut the entry array (bvhgpu_hits_region_info)
+    bool rg_classify = false;            // BVHGPU_REGION_CLASSIFY: `rg_inside` was written
     uint32_t replays = 0;               // times bvhgpu_hits_wait had to enqueue the asynchronous batch again
     int deferred_rc = 0;                // status of a completion that ran on behalf of another call (rebuild / destroy of the tree)
     std::string deferred_err;
@@ -401,6 +411,11 @@ void allhits_batch(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, cons
 // batch has more than 2^32-1 candidates (the result object then holds an empty within result).
 template <typename T>
 void within_batch(bvhgpu_tree* t, const T* points_dev, const T* max_dist_dev, size_t n, int kind, unsigned flags, bvhgpu_hits* h);
+// region.hip: every shape whose box passes the plane set of region i, in list order, as a CSR (bvhgpu_region_*); planes_dev: n x m x 4 T;
+// flags: BVHGPU_REGION_*.  Synchronous: h->rg_offsets / h->indices / h->rg_inside and h->total are complete on return.  Throws
+// Fail::Overflow when the batch reports more than 2^32-1 shapes (the result object then holds an empty region result).
+template <typename T>
+void region_batch(bvhgpu_tree* t, const T* planes_dev, size_t n, uint32_t m, unsigned flags, bvhgpu_hits* h);
 // rays.hip
 template <typename T>
 void ray_triangle_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays_dev, const T* tris_dev, size_t n, T* out_dev);

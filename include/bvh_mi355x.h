@@ -685,6 +685,64 @@ int bvhgpu_within_f64(bvhgpu_tree *tree, const double *points, const double *max
                       bvhgpu_hits **hits);
 int bvhgpu_hits_fetch_within(bvhgpu_hits *hits, uint32_t *offsets, uint32_t *shape, void *dist, int mem);
 
+/* ---- convex regions (plane sets): EVERY shape whose box passes a set of planes, per region, in list order, as a CSR — view-frustum
+ * culling, shadow-cascade slabs, a light's froxel, portals, selection prisms: "which shapes can this camera see".  Every operation below
+ * is rounded once in the tree's dtype T, in the order written, with no contraction.
+ *  - Batch.  n regions of m planes each, 0 <= m <= BVHGPU_REGION_MAX_PLANES, m uniform per batch.  `planes` is n x m x 4 T: (nx, ny, nz, d).
+ *    A point x is inside a plane when n.x + d >= 0: normals point inward and need not be normalised.  Nothing is validated.
+ *  - Test of a region against a box [lo, hi], for each plane in order:
+ *        p[k] = (n[k] >= 0) ? hi[k] : lo[k]      the corner farthest along the normal; -0 takes hi, a NaN component takes lo
+ *        s    = ((n0*p0 + n1*p1) + n2*p2) + d
+ *    The box passes iff s >= 0 holds for every plane; a NaN s is a miss.  m = 0 passes every box.  A padding plane (0, 0, 0, 0) passes
+ *    every box that has no infinite or NaN coordinate: that is how a caller mixes plane counts in one batch.  The test is the
+ *    conservative corner test of every culling system: it never loses a shape that touches the region, and it may keep one near an
+ *    edge of the region that does not; the caller refines where that matters.
+ *  - Row q is FlatBvh::traverse (flat_bvh.rs:396-431) with that test in place of intersects_aabb: an inner entry tests its box and goes
+ *    to entry_index on a pass and to exit_index otherwise; a leaf entry tests the shape's own AABB and reports the shape on a pass.
+ *    Rows are in that (pre-order) order, as a CSR without padding.
+ *  - BVHGPU_REGION_COUNT_ONLY: `offsets` and the total only.
+ *  - BVHGPU_REGION_CLASSIFY: also one byte per reported shape, 1 iff the shape's AABB lies wholly inside — the same sums with the
+ *    opposite corner, p'[k] = (n[k] >= 0) ? lo[k] : hi[k], give s' >= 0 for every plane — else 0.  A renderer skips finer tests for the 1s.
+ *    (Ignored together with COUNT_ONLY.)
+ *  - Fact 1.  On a tree whose inner boxes are exact joins (built or refitted here, no empty child bounds) the test is monotone in
+ *    floating point: p of a child is <= (for a negative normal component >=) p of its parent, and products and sums round
+ *    monotonically.  So the row equals "every shape whose own box passes, in leaf pre-order" — for inverted shape boxes too.
+ *  - Fact 2.  On a tree with empty child bounds (a split without SAH winner) the empty box gives -inf or NaN and is never entered (for
+ *    m > 0): the walk defines the row, not the brute-force set.
+ *  - Output.  offsets[n + 1]: exclusive prefix sums of the row lengths, u32, offsets[n] == total.  shape[total]: u32.  inside[total]:
+ *    bytes (CLASSIFY).
+ *  - Trees.  Built here, rebuilt, refitted, uploaded FlatBvhs, one shape, no shapes (all offsets 0), built trees with empty child
+ *    bounds.  A tree with empty child bounds that arrived by scene import or broadcast carries the folded array only, which would report
+ *    leaves the reference never reaches: BVHGPU_INVALID_ARG, as bvhgpu_query_* answers.
+ *    An uploaded array must be a pre-order array whose subtrees nest: an inner entry i owns the range [i, exit_i), and the exit of every
+ *    entry inside that range is at most exit_i.  bvhgpu_tree_from_flat checks entry == i + 1, exit > i and "at most two children", not the
+ *    nesting: the other walks follow the pointers one entry at a time and give FlatBvh::traverse's row on any array, whereas this one
+ *    skips to the largest exit of the entries that failed, which is the same row only where subtrees nest (every array FlatBvh::flatten
+ *    writes does).  On an array that does not, the call still ends (a step never goes backwards) and its rows are unspecified.
+ *  - Limits.  n < 2^32 - 1 and total <= 2^32 - 1, else BVHGPU_OVERFLOW (the total is summed in 64 bits before anything is sized by it).
+ *  - Working memory, in the result object: one u32 per (region, chunk) unit twice over (counts and their scan), n x n_chunks < n + 8192
+ *    units whatever the tree's size — about 8 (n + 8192) bytes, which grows with n and is not capped — and 260 bytes per chunk.
+ * The call is synchronous: the result object is complete on return.  HOST planes are staged into the result object.  *hits may be NULL
+ * or a result object of any kind, whose buffers are then reused.  bvhgpu_hits_info gives n and total; stats.hits == total.  The result is
+ * a kind of its own: _fetch / _fetch_triangles / _fetch_closest / _fetch_any / _fetch_box / _fetch_sphere / _fetch_allhits / _fetch_within /
+ * _device return BVHGPU_INVALID_ARG on it, and bvhgpu_hits_fetch_region on any other.
+ * Refused, touching no buffer and leaving *hits as it was, in this order: a NULL tree or a NULL `hits`; what the settle of the tree's
+ * asynchronous build returns; a result object that still holds an asynchronous batch; a tree of another dtype (BVHGPU_DTYPE_MISMATCH); a
+ * tree that is not flattened (BVHGPU_NOT_FLATTENED); m > BVHGPU_REGION_MAX_PLANES, a NULL `planes` with n * m > 0, a `mem` that is
+ * neither BVHGPU_HOST nor BVHGPU_DEVICE, a flag bit other than the two below, the imported tree above (BVHGPU_INVALID_ARG);
+ * n >= 2^32 - 1 (BVHGPU_OVERFLOW).
+ * bvhgpu_hits_fetch_region: offsets (n + 1 u32), shape (total u32) and inside (total bytes; NULL, or a CLASSIFY batch) copied to `mem`;
+ * each may be NULL.  A COUNT_ONLY batch has offsets only.
+ * bvhgpu_hits_region_info: how the batch was cut — a region is walked as n_chunks ranges of chunk_entries entries of the pre-order
+ * array, one wavefront each (both 0 for a batch without regions or a tree without shapes).  The rows do not depend on it. */
+#define BVHGPU_REGION_MAX_PLANES 32
+#define BVHGPU_REGION_COUNT_ONLY 1u /* offsets and the total only */
+#define BVHGPU_REGION_CLASSIFY 2u   /* one byte per reported shape: 1 = its AABB lies wholly inside the region */
+int bvhgpu_region_f32(bvhgpu_tree *tree, const float *planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits **hits);
+int bvhgpu_region_f64(bvhgpu_tree *tree, const double *planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits **hits);
+int bvhgpu_hits_fetch_region(bvhgpu_hits *hits, uint32_t *offsets, uint32_t *shape, void *inside, int mem);
+int bvhgpu_hits_region_info(const bvhgpu_hits *hits, uint32_t *n_chunks, uint32_t *chunk_entries);
+
 /* ---- instanced scenes: closest-hit and first-hit ray queries over transformed copies of trees — many copies of one mesh (a forest, a
  * crowd) with the mesh built once, and rigid motion at the cost of rebuilding a tree over a few dozen object boxes while every object's own
  * tree stays untouched.  Every operation below is rounded once in the set's dtype T, in the order written, with no contraction (the

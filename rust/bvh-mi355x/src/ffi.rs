@@ -10,6 +10,9 @@ pub const BVHGPU_KHITS_MAX_K: u32 = 64; // largest k of bvhgpu_traverse_khits_*
 pub const BVHGPU_ALLHITS_LIST_ORDER: c_uint = 1; // bvhgpu_traverse_allhits_*: rows in list order, no sort pass
 pub const BVHGPU_WITHIN_LIST_ORDER: c_uint = 1; // bvhgpu_within_*: rows in the order the loop met the candidates, no sort pass
 pub const BVHGPU_WITHIN_COUNT_ONLY: c_uint = 2; // bvhgpu_within_*: offsets (neighbour counts) and the total only
+pub const BVHGPU_REGION_MAX_PLANES: u32 = 32; // most planes per region of bvhgpu_region_*
+pub const BVHGPU_REGION_COUNT_ONLY: c_uint = 1; // bvhgpu_region_*: offsets and the total only
+pub const BVHGPU_REGION_CLASSIFY: c_uint = 2; // bvhgpu_region_*: one byte per reported shape, 1 = its AABB lies wholly inside
 pub const BVHGPU_LEAF_BOX: c_int = 0; // leaf stage of bvhgpu_traverse_khits_*: {enter, exit} on the shape's own AABB
 pub const BVHGPU_LEAF_TRIANGLE: c_int = 1; // ... Intersection{distance, u, v} (needs the triangles)
 pub const BVHGPU_LEAF_SPHERE: c_int = 2; // ... {distance, exit} (needs the spheres)
@@ -204,6 +207,11 @@ extern "C" {
     pub fn bvhgpu_within_f32(t: *mut bvhgpu_tree, points: *const f32, max_dist: *const f32, n: usize, mem: c_int, kind: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_within_f64(t: *mut bvhgpu_tree, points: *const f64, max_dist: *const f64, n: usize, mem: c_int, kind: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_hits_fetch_within(h: *mut bvhgpu_hits, offsets: *mut u32, shape: *mut u32, dist: *mut c_void, mem: c_int) -> c_int;
+    // every shape whose box passes the m planes of region i as a CSR in FlatBvh::traverse's order (planes: n x m x 4; offsets: n + 1, shape: total, inside: total bytes with BVHGPU_REGION_CLASSIFY; offsets only with BVHGPU_REGION_COUNT_ONLY)
+    pub fn bvhgpu_region_f32(t: *mut bvhgpu_tree, planes: *const f32, n: usize, m: u32, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_region_f64(t: *mut bvhgpu_tree, planes: *const f64, n: usize, m: u32, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_hits_fetch_region(h: *mut bvhgpu_hits, offsets: *mut u32, shape: *mut u32, inside: *mut c_void, mem: c_int) -> c_int;
+    pub fn bvhgpu_hits_region_info(h: *const bvhgpu_hits, n_chunks: *mut u32, chunk_entries: *mut u32) -> c_int;
     pub fn bvhgpu_tree_set_spheres_f32(t: *mut bvhgpu_tree, spheres: *const f32, n: usize, mem: c_int) -> c_int;
     pub fn bvhgpu_tree_set_spheres_f64(t: *mut bvhgpu_tree, spheres: *const f64, n: usize, mem: c_int) -> c_int;
     pub fn bvhgpu_traverse_sphere_f32(t: *mut bvhgpu_tree, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;

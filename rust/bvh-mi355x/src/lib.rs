@@ -105,6 +105,7 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
     unsafe fn traverse_allhits(t: *mut ffi::bvhgpu_tree, rays: *const Self::RayC, tmax: *const Self, n: usize, mem: c_int, leaf: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
     #[allow(clippy::too_many_arguments)]
     unsafe fn within(t: *mut ffi::bvhgpu_tree, points: *const Self, max_dist: *const Self, n: usize, mem: c_int, kind: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
+    unsafe fn region(t: *mut ffi::bvhgpu_tree, planes: *const Self, n: usize, m: u32, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int;
 
     fn node_to_crate(raw: &Self::Node) -> BvhNode<Self, 3>;
     fn flat_to_crate(raw: &Self::Flat) -> FlatNode<Self, 3>;
@@ -114,7 +115,7 @@ pub trait GpuScalar: BHValue + sealed::Sealed + Default + 'static {
 
 macro_rules! impl_gpu_scalar {
     ($t:ty, $dtype:expr, $node:ident, $flat:ident, $ray:ident, $build_flat:ident, $rebuild_flat:ident, $refit:ident, $traverse:ident,
-     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $traverse_box:ident, $set_spheres:ident, $traverse_sphere:ident, $knearest:ident, $knearest_tree:ident, $traverse_khits:ident, $traverse_allhits:ident, $within:ident,
+     $set_tris:ident, $from_flat:ident, $rebuild_async:ident, $traverse_host:ident, $build_traverse_host:ident, $query:ident, $traverse_any:ident, $traverse_box:ident, $set_spheres:ident, $traverse_sphere:ident, $knearest:ident, $knearest_tree:ident, $traverse_khits:ident, $traverse_allhits:ident, $within:ident, $region:ident,
      $flat_ctor:expr) => {
         impl GpuScalar for $t {
             type Node = ffi::$node;
@@ -178,6 +179,9 @@ macro_rules! impl_gpu_scalar {
             unsafe fn within(t: *mut ffi::bvhgpu_tree, points: *const $t, max_dist: *const $t, n: usize, mem: c_int, kind: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int {
                 ffi::$within(t, points, max_dist, n, mem, kind, flags, hits)
             }
+            unsafe fn region(t: *mut ffi::bvhgpu_tree, planes: *const $t, n: usize, m: u32, mem: c_int, flags: c_uint, hits: *mut *mut ffi::bvhgpu_hits) -> c_int {
+                ffi::$region(t, planes, n, m, mem, flags, hits)
+            }
             fn node_to_crate(r: &ffi::$node) -> BvhNode<$t, 3> {
                 if r.shape != ffi::BVHGPU_NONE {
                     BvhNode::Leaf { parent_index: r.parent as usize, shape_index: r.shape as usize }
@@ -216,11 +220,11 @@ macro_rules! impl_gpu_scalar {
 }
 impl_gpu_scalar!(f32, ffi::BVHGPU_F32, bvhgpu_node_f32, bvhgpu_flat_f32, bvhgpu_ray_f32, bvhgpu_build_flat_f32, bvhgpu_rebuild_flat_f32,
                  bvhgpu_refit_f32, bvhgpu_traverse_f32, bvhgpu_tree_set_triangles_f32, bvhgpu_tree_from_flat_f32,
-                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_traverse_box_f32, bvhgpu_tree_set_spheres_f32, bvhgpu_traverse_sphere_f32, bvhgpu_knearest_f32, bvhgpu_knearest_tree_f32, bvhgpu_traverse_khits_f32, bvhgpu_traverse_allhits_f32, bvhgpu_within_f32,
+                 bvhgpu_rebuild_flat_async_f32, bvhgpu_traverse_host_f32, bvhgpu_build_traverse_host_f32, bvhgpu_query_f32, bvhgpu_traverse_any_f32, bvhgpu_traverse_box_f32, bvhgpu_tree_set_spheres_f32, bvhgpu_traverse_sphere_f32, bvhgpu_knearest_f32, bvhgpu_knearest_tree_f32, bvhgpu_traverse_khits_f32, bvhgpu_traverse_allhits_f32, bvhgpu_within_f32, bvhgpu_region_f32,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f32 { min, max, entry, exit, shape });
 impl_gpu_scalar!(f64, ffi::BVHGPU_F64, bvhgpu_node_f64, bvhgpu_flat_f64, bvhgpu_ray_f64, bvhgpu_build_flat_f64, bvhgpu_rebuild_flat_f64,
                  bvhgpu_refit_f64, bvhgpu_traverse_f64, bvhgpu_tree_set_triangles_f64, bvhgpu_tree_from_flat_f64,
-                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_traverse_box_f64, bvhgpu_tree_set_spheres_f64, bvhgpu_traverse_sphere_f64, bvhgpu_knearest_f64, bvhgpu_knearest_tree_f64, bvhgpu_traverse_khits_f64, bvhgpu_traverse_allhits_f64, bvhgpu_within_f64,
+                 bvhgpu_rebuild_flat_async_f64, bvhgpu_traverse_host_f64, bvhgpu_build_traverse_host_f64, bvhgpu_query_f64, bvhgpu_traverse_any_f64, bvhgpu_traverse_box_f64, bvhgpu_tree_set_spheres_f64, bvhgpu_traverse_sphere_f64, bvhgpu_knearest_f64, bvhgpu_knearest_tree_f64, bvhgpu_traverse_khits_f64, bvhgpu_traverse_allhits_f64, bvhgpu_within_f64, bvhgpu_region_f64,
                  |min, max, entry, exit, shape| ffi::bvhgpu_flat_f64 { min, max, entry, exit, shape, _pad: 0 });
 
 fn aabb_to_6<T: GpuScalar>(b: &Aabb<T, 3>) -> [T; 6] {
@@ -663,6 +667,32 @@ impl<T: GpuScalar> GpuBvh<T> {
             ffi::bvhgpu_hits_destroy(hits);
         }
         (offsets, shape, dist)
+    }
+
+    /// The shapes whose box passes every plane of a convex region, per region, as a CSR (`bvhgpu_region_*`): `FlatBvh::traverse`
+    /// (src/flat_bvh.rs:396-431) with the corner test in place of `intersects_aabb`.  `planes`: `n * m` rows `[nx, ny, nz, d]`, a point `x`
+    /// is inside a plane when `n.x + d >= 0`; `m <= ffi::BVHGPU_REGION_MAX_PLANES` planes per region, rows of zeros are padding.  Returns
+    /// `(offsets, shape, inside)`: `n + 1` exclusive prefix sums, `total` shape indices in the order of `traverse`, and — with `classify`
+    /// (`ffi::BVHGPU_REGION_CLASSIFY`) — a byte per shape, 1 iff its AABB lies wholly inside.  `count_only`: the offsets alone.
+    pub fn region_query(&self, planes: &[[T; 4]], m: usize, classify: bool, count_only: bool) -> (Vec<u32>, Vec<u32>, Vec<u8>) {
+        let n = if m == 0 { 0 } else { planes.len() / m };
+        assert_eq!(n * m, planes.len(), "planes.len() must be a multiple of m");
+        let classify = classify && !count_only;
+        let flags = (if count_only { ffi::BVHGPU_REGION_COUNT_ONLY } else { 0 }) | (if classify { ffi::BVHGPU_REGION_CLASSIFY } else { 0 });
+        let mut hits = core::ptr::null_mut();
+        let mut offsets = vec![0u32; n + 1];
+        let (mut shape, mut inside) = (Vec::new(), Vec::new());
+        unsafe {
+            check(self.ctx, T::region(self.tree, planes.as_ptr().cast(), n, m as u32, ffi::BVHGPU_HOST, flags, &mut hits));
+            let mut total = 0u64;
+            check(self.ctx, ffi::bvhgpu_hits_info(hits, core::ptr::null_mut(), &mut total, core::ptr::null_mut()));
+            if !count_only { shape.resize(total as usize, 0u32); }
+            if classify { inside.resize(total as usize, 0u8); }
+            let inside_ptr = if classify { inside.as_mut_ptr() as *mut c_void } else { core::ptr::null_mut() };
+            check(self.ctx, ffi::bvhgpu_hits_fetch_region(hits, offsets.as_mut_ptr(), shape.as_mut_ptr(), inside_ptr, ffi::BVHGPU_HOST));
+            ffi::bvhgpu_hits_destroy(hits);
+        }
+        (offsets, shape, inside)
     }
 
     /// The `k` nearest shapes of every point (`bvhgpu_knearest_*`): the loop of `FlatBvh::nearest_to` (src/flat_bvh.rs:524-558) with a list of

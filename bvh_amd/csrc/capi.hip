@@ -1075,6 +1075,47 @@ int do_instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays,
         return (int)BVHGPU_OK;
     });
 }
+// do_region's shape over an instance set, behind do_instances_trace's commit and staleness rules.  HOST planes are staged in the result
+// object.  A refused call touches no buffer and leaves *hits as it was.
+template <typename T>
+int do_instances_region(bvhgpu_instances* s, const T* planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits** hits) {
+    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    bvhgpu_ctx* ctx = s->ctx;
+    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
+    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
+    if (m > BVHGPU_REGION_MAX_PLANES) return fail(ctx, BVHGPU_INVALID_ARG, "more than BVHGPU_REGION_MAX_PLANES planes per region");
+    if (n && m && !planes) return fail(ctx, BVHGPU_INVALID_ARG, "planes is NULL");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from plane dtype");
+    if (flags & ~(BVHGPU_REGION_COUNT_ONLY | BVHGPU_REGION_CLASSIFY | BVHGPU_REGION_INSTANCES_ONLY))
+        return fail(ctx, BVHGPU_INVALID_ARG, "instance region flags: BVHGPU_REGION_COUNT_ONLY, BVHGPU_REGION_CLASSIFY and BVHGPU_REGION_INSTANCES_ONLY only");
+    if (!s->committed) return fail(ctx, BVHGPU_INVALID_ARG, "instances are not committed (the last commit failed): call bvhgpu_instances_update");
+    for (size_t k = 0; k < s->trees.size(); k++) {   // what the commit read of every member must still be what the member holds
+        const bvhgpu_tree* t = s->trees[k];
+        const bvhgpu_instances::Seen& c = s->seen[k];
+        if (t->trav.p != c.trav || t->aabbs.p != c.aabbs || t->tris.p != c.tris || t->n != c.n || t->n_trav != c.n_trav || t->gen != c.gen ||
+            !t->flattened || !t->has_tris || t->pending_build || t->pending_recv)
+            return fail(ctx, BVHGPU_INVALID_ARG, "instances are stale: call bvhgpu_instances_update");
+    }
+    if (!(flags & BVHGPU_REGION_INSTANCES_ONLY))
+        for (const bvhgpu_tree* t : s->trees)
+            if (t->exact_only && !t->built && !t->unfolded)
+                return fail(ctx, BVHGPU_INVALID_ARG, "an imported member tree whose build had a split without SAH winner: its leaves' navigator boxes were folded away");
+    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 regions in one batch");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        bvhgpu_hits* h = batch_hits(hits);
+        const T* dev = planes;
+        const size_t bytes = n * m * 4 * sizeof(T);
+        if (mem == BVHGPU_HOST && bytes) {
+            h->qbuf.reserve(bytes);
+            BVH_HIP(hipMemcpyAsync(h->qbuf.p, planes, bytes, hipMemcpyHostToDevice, ctx->stream));
+            dev = h->qbuf.as<T>();
+        }
+        instances_region_batch<T>(s, dev, n, m, flags, h);
+        return (int)BVHGPU_OK;
+    });
+}
 
 }  // namespace
 
@@ -1785,12 +1826,44 @@ int bvhgpu_hits_fetch_region(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape,
     if (h->flags & TRAVERSE_ANY_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_any_* batch: use bvhgpu_hits_fetch_any");
     if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a CLOSEST batch: use bvhgpu_hits_fetch_closest");
     if (!(h->flags & TRAVERSE_REGION)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_region_* batch: use bvhgpu_hits_fetch");
+    if (h->rg_inst != REGION_INST_NONE)
+        return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_region_* batch: use bvhgpu_hits_fetch_instances_region");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
     if (inside && !h->rg_classify) return fail(ctx, BVHGPU_INVALID_ARG, "the region batch was run without BVHGPU_REGION_CLASSIFY");
     return guarded(ctx, [&] {
         use_device(ctx);
         const size_t rows = h->wi_count_only ? 0 : (size_t)h->total;
         if (offsets) copy_out(ctx, offsets, h->rg_offsets.p, (h->n_rays + 1) * 4, mem);
+        if (shape && rows) copy_out(ctx, shape, h->indices.p, rows * 4, mem);
+        if (inside && rows) copy_out(ctx, inside, h->rg_inside.p, rows, mem);
+        return (int)BVHGPU_OK;
+    });
+}
+
+// the CSR of a region batch over an instance set: offsets (n + 1 u32), the instances and the shapes (total u32 each; a batch with
+// BVHGPU_REGION_INSTANCES_ONLY has no shapes), the inside bytes (total, CLASSIFY batches); each may be NULL.  A COUNT_ONLY batch has offsets
+// only, whatever `total` says.  Every other kind of result is refused, a bvhgpu_region_* result included.
+int bvhgpu_hits_fetch_instances_region(bvhgpu_hits* h, uint32_t* offsets, uint32_t* instance, uint32_t* shape, void* inside, int mem) {
+    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = h->ctx;
+    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
+    if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
+    if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
+    if (h->flags & TRAVERSE_BOX_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_box_* batch: use bvhgpu_hits_fetch_box");
+    if (h->flags & TRAVERSE_ANY_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_any_* batch: use bvhgpu_hits_fetch_any");
+    if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a CLOSEST batch: use bvhgpu_hits_fetch_closest");
+    if (!(h->flags & TRAVERSE_REGION)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_instances_region_* batch: use bvhgpu_hits_fetch");
+    if (h->rg_inst == REGION_INST_NONE) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (inside && !h->rg_classify) return fail(ctx, BVHGPU_INVALID_ARG, "the region batch was run without BVHGPU_REGION_CLASSIFY");
+    if (shape && h->rg_inst == REGION_INST_ONLY) return fail(ctx, BVHGPU_INVALID_ARG, "the region batch was run with BVHGPU_REGION_INSTANCES_ONLY: it has no shapes");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        const size_t rows = h->wi_count_only ? 0 : (size_t)h->total;
+        const bool only = h->rg_inst == REGION_INST_ONLY;   // (stage 1's rows: the instances are where a region result keeps its shapes)
+        if (offsets) copy_out(ctx, offsets, h->rg_offsets.p, (h->n_rays + 1) * 4, mem);
+        if (instance && rows) copy_out(ctx, instance, only ? h->indices.p : h->rg_instance.p, rows * 4, mem);
         if (shape && rows) copy_out(ctx, shape, h->indices.p, rows * 4, mem);
         if (inside && rows) copy_out(ctx, inside, h->rg_inside.p, rows, mem);
         return (int)BVHGPU_OK;
@@ -1846,6 +1919,12 @@ int bvhgpu_instances_trace_f32(bvhgpu_instances* s, const bvhgpu_ray_f32* rays, 
 int bvhgpu_instances_trace_f64(bvhgpu_instances* s, const bvhgpu_ray_f64* rays, const double* tmax, size_t n_rays, int mem, unsigned flags,
                                double* out_vals, uint32_t* out_instance, uint32_t* out_shape) {
     return do_instances_trace<double>(s, rays, tmax, n_rays, mem, flags, out_vals, out_instance, out_shape);
+}
+int bvhgpu_instances_region_f32(bvhgpu_instances* s, const float* planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_instances_region<float>(s, planes, n, m, mem, flags, hits);
+}
+int bvhgpu_instances_region_f64(bvhgpu_instances* s, const double* planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_instances_region<double>(s, planes, n, m, mem, flags, hits);
 }
 int bvhgpu_instances_boxes(bvhgpu_instances* s, void* out, int mem) {
     if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");

@@ -54,6 +54,11 @@ constexpr unsigned TRAVERSE_WITHIN = 1u << 27;
 // result objects of bvhgpu_region_* (region.hip): marked the same way; the only bit such a result carries (BVHGPU_REGION_* are never
 // stored in bvhgpu_hits::flags)
 constexpr unsigned TRAVERSE_REGION = 1u << 26;
+// ... and within that kind, bvhgpu_hits::rg_inst tells a bvhgpu_instances_region_* result from a bvhgpu_region_* one (no further flag
+// bit: every other entry's mask stays as it is)
+constexpr int REGION_INST_NONE = 0;     // bvhgpu_region_*: rows of shapes
+constexpr int REGION_INST_SHAPES = 1;   // bvhgpu_instances_region_*: rows of (instance, shape)
+constexpr int REGION_INST_ONLY = 2;     // ... with BVHGPU_REGION_INSTANCES_ONLY: rows of instances (in `indices`)
 
 }  // namespace bvhgpu
 
@@ -303,6 +308,13 @@ struct bvhgpu_hits {
     bvhgpu::DevBuf rg_anc;               // per chunk of the batch: its ancestor count, then REGION_ANC_MAX ancestor entries (rebuilt by every batch)
     uint32_t rg_chunks = 0, rg_chunk_entries = 0;   // how the batch cut the entry array (bvhgpu_hits_region_info)
     bool rg_classify = false;            // BVHGPU_REGION_CLASSIFY: `rg_inside` was written
+    // region batches over an instance set (bvhgpu_instances_region_*, region.hip): the same CSR with `rg_instance` beside `indices`; the
+    // units are (pair, chunk), rg_chunks the uniform stride and rg_chunk_entries the largest member's chunk
+    int rg_inst = 0;                     // REGION_INST_*: which of the two entries made this region result (rows_reset: NONE)
+    bvhgpu::DevBuf rg_instance;          // total u32: the instance of every reported shape
+    bvhgpu::DevBuf rg_pairs;             // per (region, instance) pair: its region
+    bvhgpu::DevBuf rg_members;           // per member tree: region.hip RegionMember<T> (rebuilt by every batch, like the ancestor table)
+    std::vector<unsigned char> rg_members_host;   // its host image (alive while the upload is in flight)
     uint32_t replays = 0;               // times bvhgpu_hits_wait had to enqueue the asynchronous batch again
     int deferred_rc = 0;                // status of a completion that ran on behalf of another call (rebuild / destroy of the tree)
     std::string deferred_err;
@@ -330,6 +342,8 @@ struct bvhgpu_instances {
     bvhgpu::DevBuf bounds;      // n_trees x 6 T: B_t
     bvhgpu::DevBuf recs;        // n x InstRec<T>: Y_i and the tree slot
     bvhgpu::DevBuf wboxes;      // n x 6 T: W_i
+    bvhgpu_hits* rg_top = nullptr;   // bvhgpu_instances_region_*: the result object of stage 1 (the regions over `top`), made on first use
+    ~bvhgpu_instances() { delete rg_top; }   // (never holds an asynchronous batch; the caller has synchronised the stream)
 };
 
 namespace bvhgpu {
@@ -416,6 +430,11 @@ void within_batch(bvhgpu_tree* t, const T* points_dev, const T* max_dist_dev, si
 // Fail::Overflow when the batch reports more than 2^32-1 shapes (the result object then holds an empty region result).
 template <typename T>
 void region_batch(bvhgpu_tree* t, const T* planes_dev, size_t n, uint32_t m, unsigned flags, bvhgpu_hits* h);
+// region.hip: the same over a committed instance set (bvhgpu_instances_region_*): rows of (instance, shape) in h->rg_offsets / h->rg_instance /
+// h->indices / h->rg_inside, or with BVHGPU_REGION_INSTANCES_ONLY rows of instances in h->indices.  Synchronous; throws Fail::Overflow when the
+// batch has more than 2^32-1 (region, instance) pairs or reports more than 2^32-1 shapes (the result object then holds an empty result).
+template <typename T>
+void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, uint32_t m, unsigned flags, bvhgpu_hits* h);
 // rays.hip
 template <typename T>
 void ray_triangle_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays_dev, const T* tris_dev, size_t n, T* out_dev);

@@ -33,7 +33,12 @@
 // UNFOLDED rule for uploaded FlatBvhs and single-shape trees (a leaf entry tests the shape's AABB out of the shape array), and an unfolded
 // mirror of the FlatNode array (unfold.hpp) for a built tree with empty child bounds: below such a split the navigator boxes are
 // Aabb::empty(), whose sums are -inf or NaN — never entered — while the folded entry would test the shape's box.
+//
+// Regions over an instance set (bvhgpu_instances_region_*) live here as well, beside region_unit, which they call
+// unchanged: stage 1 is region_batch over the set's top level, stage 2 walks (pair, chunk) units with the planes re-expressed in the
+// pair's object frame (k_instances_region_walk below).
 #include <cstdio>
+#include <vector>
 
 #include "rows.hpp"
 #include "unfold.hpp"
@@ -219,6 +224,99 @@ __global__ __launch_bounds__(256) void k_region_offsets(const uint32_t* __restri
     if (q <= n) offsets[q] = unit_offsets[(size_t)q * n_chunks];
 }
 
+// ---- regions over an instance set (bvhgpu_instances_region_*; include/bvh_mi355x.h) -----------------------------------------
+// Stage 1 is region_batch over the set's top level with the world planes: its rows are the (region, instance) pairs.  Stage 2 walks every
+// pair's member with the planes re-expressed in the instance's object frame: the unit is (pair, chunk), unit u = pair u / nc_max, chunk
+// u % nc_max, where nc_max is the largest chunk count among the members — a uniform stride, so the schedule is rows.hip's again with no
+// further scan and no further host read; a unit whose chunk lies beyond its own member's array counts 0.
+
+// what the walk needs of a member, one record per member, made by every batch (instances.hip's InstTree is the ray walk's)
+template <typename T> struct RegionMember {
+    const TravNode<T>* nodes;   // the folded array, the uploaded array, or the unfolded mirror in the result object
+    const T* aabbs;             // n x 6: the shapes' own boxes (read by the unfolded rule)
+    uint32_t n_trav, unfolded;
+    uint32_t chunk_entries, n_chunks;
+    uint32_t anc_base;          // its first chunk in the batch's ancestor table
+    uint32_t _pad;
+};
+
+// pair p belongs to the region q with top_offsets[q] <= p < top_offsets[q + 1] (stage 1's rows; empty rows repeat an offset)
+__global__ __launch_bounds__(256) void k_instances_region_pairs(const uint32_t* __restrict__ top_offsets, uint32_t n, uint32_t n_pairs,
+                                                                uint32_t* __restrict__ pair_region) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;   // (no wrap: the grid is ceil(n_pairs / 256) and n_pairs <= 2^32 - 1)
+    if (p >= n_pairs) return;
+    uint32_t lo = 0, hi = n;   // top_offsets[lo] <= p < top_offsets[hi] throughout (top_offsets[0] == 0, top_offsets[n] == n_pairs)
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (top_offsets[mid] <= p) lo = mid; else hi = mid;
+    }
+    pair_region[p] = lo;
+}
+
+// a workgroup is one wave and takes the units blockIdx.x, blockIdx.x + gridDim.x, ...  The planes of the unit's region go to LDS in its
+// instance's object frame (lane j < m: plane j; the header's formula, from the FORWARD transform); then region_unit, on the member's array.
+// !FILL: out[u] = the unit's count.  FILL: out = the scanned counts; the unit writes shape_out and inst_out[out[u] .. out[u + 1])
+template <typename T, bool FILL, bool CLASSIFY>
+__global__ __launch_bounds__(64) void k_instances_region_walk(const RegionMember<T>* __restrict__ members, const uint32_t* __restrict__ tree_of,
+                                                              const T* __restrict__ xforms, const T* __restrict__ planes, uint32_t m,
+                                                              const uint32_t* __restrict__ pair_region, const uint32_t* __restrict__ pair_inst,
+                                                              uint32_t nc_max, size_t n_units, const uint32_t* __restrict__ anc_cnt,
+                                                              const uint32_t* __restrict__ anc, uint32_t* __restrict__ out, uint32_t* __restrict__ inst_out,
+                                                              uint32_t* __restrict__ shape_out, unsigned char* __restrict__ inside_out) {
+    __shared__ T pl[4 * BVHGPU_REGION_MAX_PLANES];
+    for (size_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+        uint32_t beg = 0, end = 0;
+        if (FILL) {
+            beg = out[u]; end = out[u + 1];
+            if (beg == end) continue;   // (uniform over the workgroup: nothing to write)
+        }
+        const uint32_t p = (uint32_t)(u / nc_max), c = (uint32_t)(u - (size_t)p * nc_max);
+        const uint32_t q = __builtin_amdgcn_readfirstlane(pair_region[p]), inst = __builtin_amdgcn_readfirstlane(pair_inst[p]);
+        const RegionMember<T>* mb = members + __builtin_amdgcn_readfirstlane(tree_of[inst]);
+        const uint32_t nc = __builtin_amdgcn_readfirstlane(mb->n_chunks);
+        if (c >= nc) {   // (uniform) the member's array ends in front of this chunk
+            if (!FILL && threadIdx.x == 0) out[u] = 0;
+            continue;
+        }
+        __syncthreads();   // (the previous unit's planes are no longer read)
+        if (threadIdx.x < m) {
+            const T* w = planes + ((size_t)q * m + threadIdx.x) * 4;
+            const T* x = xforms + 12 * (size_t)inst;
+            const T n0 = w[0], n1 = w[1], n2 = w[2], d = w[3];
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const T a = x[j] * n0, b = x[4 + j] * n1, cc = x[8 + j] * n2;
+                const T ab = a + b;
+                pl[4 * threadIdx.x + j] = ab + cc;
+            }
+            const T a = n0 * x[3], b = n1 * x[7], cc = n2 * x[11];
+            const T ab = a + b;
+            const T abc = ab + cc;
+            pl[4 * threadIdx.x + 3] = abc + d;
+        }
+        __syncthreads();
+        const uint32_t n_trav = __builtin_amdgcn_readfirstlane(mb->n_trav), ce = __builtin_amdgcn_readfirstlane(mb->chunk_entries);
+        const uint32_t ab0 = __builtin_amdgcn_readfirstlane(mb->anc_base);
+        const uint32_t* ac = anc_cnt + ab0;
+        const uint32_t* an = anc + (size_t)ab0 * REGION_ANC_MAX;
+        uint32_t cnt;
+        if (__builtin_amdgcn_readfirstlane(mb->unfolded) != 0u)   // (uniform: members of both rules meet in one launch)
+            cnt = region_unit<T, true, FILL, CLASSIFY>(mb->nodes, n_trav, mb->aabbs, pl, m, c, ce, ac, an, beg, end, shape_out, inside_out);
+        else
+            cnt = region_unit<T, false, FILL, CLASSIFY>(mb->nodes, n_trav, mb->aabbs, pl, m, c, ce, ac, an, beg, end, shape_out, inside_out);
+        if (!FILL && threadIdx.x == 0) out[u] = cnt;
+        if (FILL)
+            for (size_t k = (size_t)beg + threadIdx.x; k < end; k += 64) inst_out[k] = inst;   // the instance beside every shape of the unit
+    }
+}
+
+// the caller's offsets: row q starts where the first unit of its first pair starts; offsets[n] = the total
+__global__ __launch_bounds__(256) void k_instances_region_offsets(const uint32_t* __restrict__ unit_offsets, const uint32_t* __restrict__ top_offsets,
+                                                                  uint32_t n, uint32_t nc_max, uint32_t* __restrict__ offsets) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q <= n) offsets[q] = unit_offsets[(size_t)top_offsets[q] * nc_max];
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 template <typename T, bool UNFOLDED>
 static void region_launch(bvhgpu_tree* t, const TravNode<T>* nodes, uint32_t n_trav, const T* planes_dev, size_t n, uint32_t m, bool classify, bool count_only,
@@ -296,5 +394,125 @@ void region_batch(bvhgpu_tree* t, const T* planes_dev, size_t n, uint32_t m, uns
 }
 template void region_batch<float>(bvhgpu_tree*, const float*, size_t, uint32_t, unsigned, bvhgpu_hits*);
 template void region_batch<double>(bvhgpu_tree*, const double*, size_t, uint32_t, unsigned, bvhgpu_hits*);
+
+// the regions of a batch over a committed instance set (the caller has checked commit, staleness and the members' kinds)
+template <typename T>
+void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, uint32_t m, unsigned flags, bvhgpu_hits* h) {
+    bvhgpu_ctx* ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    const bool count_only = (flags & BVHGPU_REGION_COUNT_ONLY) != 0;
+    const bool classify = (flags & BVHGPU_REGION_CLASSIFY) != 0 && !count_only;
+    if (flags & BVHGPU_REGION_INSTANCES_ONLY) {   // stage 1 IS the answer: the top level's rows, straight into the caller's result object
+        try {
+            region_batch<T>(s->top, planes_dev, n, m, flags & (BVHGPU_REGION_COUNT_ONLY | BVHGPU_REGION_CLASSIFY), h);
+        } catch (...) {   // (the empty result it leaves is this entry's as well)
+            h->rg_inst = REGION_INST_ONLY;
+            throw;
+        }
+        h->rg_inst = REGION_INST_ONLY;
+        return;
+    }
+    // the result object becomes an (empty) instance-region result first: whatever fails below leaves it consistent
+    rows_reset(h, ctx, Traits<T>::dtype, TRAVERSE_REGION, 0, count_only);
+    h->rg_classify = classify; h->rg_chunks = 0; h->rg_chunk_entries = 0; h->rg_inst = REGION_INST_SHAPES;
+    char name[112];
+    std::snprintf(name, sizeof name, "bvhgpu::k_instances_region_walk<%s, %s, %s>", walk_type_name<T>(), count_only ? "false" : "true", classify ? "true" : "false");
+    h->walk_kernel = name;
+    h->rg_offsets.reserve((n + 1) * 4);
+    BVH_HIP(hipMemsetAsync(h->rg_offsets.p, 0, (n + 1) * 4, st));
+    // ---- stage 1, into the set's own result object (rows_reset clears the one it is given); synchronous, so P is known behind it
+    if (!s->rg_top) s->rg_top = new bvhgpu_hits();
+    bvhgpu_hits* top = s->rg_top;
+    region_batch<T>(s->top, planes_dev, n, m, 0u, top);
+    const size_t P = (size_t)top->total;   // (<= 2^32 - 1: region_batch throws Fail::Overflow beyond)
+    const size_t nt = s->trees.size();
+    // ---- the member table: which array, how it is cut for P pairs, where its ancestor rows and its mirror start
+    std::vector<RegionMember<T>> tbl(nt);
+    std::vector<size_t> mirror_at(nt, (size_t)-1);
+    size_t n_anc = 0, n_mirror = 0;
+    uint32_t nc_max = 0, ce_max = 0;
+    for (size_t k = 0; k < nt && P != 0; k++) {
+        bvhgpu_tree* t = s->trees[k];
+        RegionMember<T>& r = tbl[k];
+        r = RegionMember<T>{nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u};
+        if (t->n == 0) continue;   // (no instance of it has a finite world box: never looked up)
+        ensure_flat_arrays(t);
+        const bool mirror = t->exact_only && t->built && !t->unfolded && t->n >= 2;   // region_batch's rule, member by member
+        r.unfolded = (t->unfolded || t->n == 1 || mirror) ? 1u : 0u;
+        r.n_trav = (uint32_t)(mirror ? t->n_flat : t->n_trav);
+        r.nodes = t->trav.as<TravNode<T>>();
+        r.aabbs = t->aabbs.as<T>();
+        if (mirror) { mirror_at[k] = n_mirror; n_mirror += r.n_trav; }
+        r.chunk_entries = region_chunk_entries(P, r.n_trav);
+        r.n_chunks = (uint32_t)(((size_t)r.n_trav + r.chunk_entries - 1) / r.chunk_entries);
+        if (n_anc + r.n_chunks > 0xFFFFFFFFull) throw HipFail{hipErrorInvalidValue, nullptr, __LINE__, Fail::Overflow};
+        r.anc_base = (uint32_t)n_anc;
+        n_anc += r.n_chunks;
+        nc_max = r.n_chunks > nc_max ? r.n_chunks : nc_max;
+        ce_max = r.chunk_entries > ce_max ? r.chunk_entries : ce_max;
+    }
+    if (P != 0 && nc_max != 0) {
+        const size_t n_units = P * nc_max;   // (< P + REGION_UNITS_TARGET, and nc_max == 1 from P = REGION_UNITS_TARGET on: <= 2^32 - 1)
+        const dim3 grid((unsigned)(n_units < REGION_GRID_MAX ? n_units : REGION_GRID_MAX)), block(64);
+        h->offsets.reserve((n_units + 1) * 4);
+        h->rg_anc.reserve(n_anc * (1 + REGION_ANC_MAX) * 4);
+        h->rg_pairs.reserve(P * 4);
+        h->rg_members.reserve(nt * sizeof(RegionMember<T>));
+        if (n_mirror) h->wi_unfold.reserve(n_mirror * sizeof(TravNode<T>));
+        uint32_t* anc_cnt = h->rg_anc.as<uint32_t>();
+        uint32_t* anc = anc_cnt + n_anc;
+        for (size_t k = 0; k < nt; k++) {
+            RegionMember<T>& r = tbl[k];
+            if (r.n_chunks == 0) continue;
+            if (mirror_at[k] != (size_t)-1) {
+                TravNode<T>* dst = h->wi_unfold.as<TravNode<T>>() + mirror_at[k];
+                hipLaunchKernelGGL((k_within_unfold<T>), dim3((r.n_trav + 255) / 256), dim3(256), 0, st, s->trees[k]->flat.as<typename Traits<T>::Flat>(), r.n_trav, dst);
+                r.nodes = dst;
+            }
+            hipLaunchKernelGGL((k_region_ancestors<T>), dim3((r.n_chunks + 255) / 256), dim3(256), 0, st, r.nodes, r.chunk_entries, r.n_chunks,
+                               anc_cnt + r.anc_base, anc + (size_t)r.anc_base * REGION_ANC_MAX);
+        }
+        BVH_HIP(hipGetLastError());
+        h->rg_members_host.assign(reinterpret_cast<const unsigned char*>(tbl.data()), reinterpret_cast<const unsigned char*>(tbl.data() + nt));
+        BVH_HIP(hipMemcpyAsync(h->rg_members.p, h->rg_members_host.data(), nt * sizeof(RegionMember<T>), hipMemcpyHostToDevice, st));
+        const uint32_t* top_offsets = top->rg_offsets.as<uint32_t>();
+        const uint32_t* pair_inst = top->indices.as<uint32_t>();
+        uint32_t* pair_region = h->rg_pairs.as<uint32_t>();
+        hipLaunchKernelGGL(k_instances_region_pairs, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, top_offsets, (uint32_t)n, (uint32_t)P, pair_region);
+        const RegionMember<T>* members = h->rg_members.as<RegionMember<T>>();
+        const uint32_t* tree_of = s->tree_of.as<uint32_t>();
+        const T* xforms = s->xforms.as<T>();
+        uint32_t* counts = rows_begin(h, n_units, false);
+        hipLaunchKernelGGL((k_instances_region_walk<T, false, false>), grid, block, 0, st, members, tree_of, xforms, planes_dev, m, pair_region, pair_inst, nc_max,
+                           n_units, anc_cnt, anc, counts, (uint32_t*)nullptr, (uint32_t*)nullptr, (unsigned char*)nullptr);
+        BVH_HIP(hipGetLastError());
+        const RowsTotals rows = rows_scan(h, n_units, 0u, 0u);
+        h->rg_chunks = nc_max; h->rg_chunk_entries = ce_max;   // (behind the scan: a batch that overflowed leaves an empty result)
+        if (rows.total != 0) {
+            rows_offsets(h, n_units);
+            uint32_t* unit_offsets = h->offsets.as<uint32_t>();
+            hipLaunchKernelGGL(k_instances_region_offsets, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, st, unit_offsets, top_offsets, (uint32_t)n, nc_max,
+                               h->rg_offsets.as<uint32_t>());
+            if (!count_only) {
+                h->indices.reserve((size_t)rows.total * 4);
+                h->rg_instance.reserve((size_t)rows.total * 4);
+                if (classify) h->rg_inside.reserve((size_t)rows.total);
+                uint32_t* shape = h->indices.as<uint32_t>();
+                uint32_t* inst = h->rg_instance.as<uint32_t>();
+                if (classify) hipLaunchKernelGGL((k_instances_region_walk<T, true, true>), grid, block, 0, st, members, tree_of, xforms, planes_dev, m, pair_region,
+                                                 pair_inst, nc_max, n_units, anc_cnt, anc, unit_offsets, inst, shape, h->rg_inside.as<unsigned char>());
+                else hipLaunchKernelGGL((k_instances_region_walk<T, true, false>), grid, block, 0, st, members, tree_of, xforms, planes_dev, m, pair_region,
+                                        pair_inst, nc_max, n_units, anc_cnt, anc, unit_offsets, inst, shape, (unsigned char*)nullptr);
+            }
+            BVH_HIP(hipGetLastError());
+            h->total = rows.total;
+        }
+    }
+    BVH_HIP(hipStreamSynchronize(st));   // the result is complete when the call returns
+    h->n_rays = n;
+    h->stats.hits = h->total;
+}
+template void instances_region_batch<float>(bvhgpu_instances*, const float*, size_t, uint32_t, unsigned, bvhgpu_hits*);
+template void instances_region_batch<double>(bvhgpu_instances*, const double*, size_t, uint32_t, unsigned, bvhgpu_hits*);
 
 }  // namespace bvhgpu

@@ -32,6 +32,7 @@ void rows_offsets(bvhgpu_hits* h, size_t n);
 // leaves it consistent
 inline void rows_reset(bvhgpu_hits* h, bvhgpu_ctx* ctx, int dtype, unsigned flags, int ah_leaf, bool wi_count_only) {
     h->ctx = ctx; h->dtype = dtype; h->flags = flags; h->ah_leaf = ah_leaf; h->wi_count_only = wi_count_only; h->n_rays = 0; h->total = 0;
+    h->rg_inst = REGION_INST_NONE;
     h->stats = bvhgpu_traverse_stats{0, 0, 0, 0, 0};
     h->pend_tree = nullptr; h->pend_rays = nullptr; h->pend_async = false;
     h->pend_wide = false; h->pend_staged = false; h->pend_rec8 = false; h->pend_guide = false; h->pend_qwide = false;

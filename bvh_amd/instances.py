@@ -13,6 +13,7 @@ import numpy as np
 from . import _lib, api
 from ._lib import DEVICE, NONE, BvhGpuError, check, ptr
 from .api import Context, RayBatch, _Typed
+from .region import _plane_dims
 
 
 class Instances(_Typed):
@@ -103,6 +104,56 @@ class Instances(_Typed):
         _, inst, _ = self.any_hits(rays, tmax)
         return inst != (NONE if isinstance(inst, np.ndarray) else -1)
 
+    def region_batch(self, planes, classify: bool = False, count_only: bool = False, instances_only: bool = False) -> dict:
+        """bvhgpu_instances_region_*: per region of m WORLD-space planes (bvh_amd.frustum_planes / aabb_planes; (n, m, 4) in the set's
+        dtype, or (m, 4) for one region, m <= 32) the (instance, shape) pairs whose box passes, as a CSR: the instances whose world box
+        passes, in the top level's order, each walked with the planes re-expressed in its object frame.  classify: also `inside`, one byte
+        per pair, 1 iff the shape's box lies wholly inside.  count_only: offsets alone.  instances_only: the rows hold the instances
+        whose world box passes and no shapes (`inside`: the world box lies wholly inside).
+        returns {offsets[n+1], instance[total], shape[total] (not with instances_only), inside[total] (classify)}.  numpy in: numpy out,
+        offsets and indices as uint32, inside as uint8.  torch in: torch tensors on the same device, indices as torch.int32, offsets as
+        torch.int64, inside as torch.uint8."""
+        n, m = _plane_dims(planes)
+        keep, pp, _rows, mem = api._rows_in(planes, 4, self.ft, "plane")
+        classify = bool(classify) and not count_only
+        flags = ((_lib.REGION_COUNT_ONLY if count_only else 0) | (_lib.REGION_CLASSIFY if classify else 0) |
+                 (_lib.REGION_INSTANCES_ONLY if instances_only else 0))
+        dev = keep.device if mem == DEVICE else None
+        if dev is not None:
+            api._torch_sync(dev)
+        lib = _lib.load()
+        if getattr(self, "_hits", None) is None:
+            self._hits = api._Hits(self.ctx)     # (the set's own result object: its buffers are reused by every batch)
+        hits = self._hits
+        check(getattr(lib, f"bvhgpu_instances_region_{self.sfx}")(self._s, pp, n, m, mem, flags, C.byref(hits.h)), self.ctx._h)
+        rows = 0 if count_only else hits._total()
+        with_shape = not instances_only
+        if dev is not None:
+            import torch
+            off32 = torch.empty(n + 1, dtype=torch.int32, device=dev)
+            instance = torch.empty(rows, dtype=torch.int32, device=dev)
+            shape = torch.empty(rows, dtype=torch.int32, device=dev) if with_shape else None
+            inside = torch.empty(rows, dtype=torch.uint8, device=dev) if classify else None
+            api._torch_sync(dev)
+            check(lib.bvhgpu_hits_fetch_instances_region(hits.h, ptr(off32.data_ptr()), ptr(instance.data_ptr()) if rows else None,
+                                                         ptr(shape.data_ptr()) if with_shape and rows else None,
+                                                         ptr(inside.data_ptr()) if classify and rows else None, DEVICE), self.ctx._h)
+            offsets = off32.to(torch.int64) & 0xFFFFFFFF
+        else:
+            offsets = np.zeros(n + 1, dtype=np.uint32)
+            instance = np.zeros(rows, dtype=np.uint32)
+            shape = np.zeros(rows, dtype=np.uint32) if with_shape else None
+            inside = np.zeros(rows, dtype=np.uint8) if classify else None
+            check(lib.bvhgpu_hits_fetch_instances_region(hits.h, ptr(offsets), ptr(instance) if rows else None,
+                                                         ptr(shape) if with_shape and rows else None, ptr(inside) if classify and rows else None,
+                                                         _lib.HOST), self.ctx._h)
+        out = dict(offsets=offsets, instance=instance)
+        if with_shape:
+            out["shape"] = shape
+        if classify:
+            out["inside"] = inside
+        return out
+
     @property
     def world_boxes(self) -> np.ndarray:
         """W_i of the committed pose, (n, 6) [min xyz, max xyz]"""
@@ -117,6 +168,9 @@ class Instances(_Typed):
         return int(nt.value), int(n.value)
 
     def close(self):
+        if getattr(self, "_hits", None) is not None:
+            self._hits.close()
+            self._hits = None
         if getattr(self, "_s", None):
             if not api._closing:
                 _lib.load().bvhgpu_instances_destroy(self._s)   # (frees what the set owns; never looks at a member tree)

@@ -814,6 +814,57 @@ int bvhgpu_instances_boxes(bvhgpu_instances *s, void *out, int mem);
 int bvhgpu_instances_info(const bvhgpu_instances *s, int *dtype, size_t *n_trees, size_t *n_instances);
 void bvhgpu_instances_destroy(bvhgpu_instances *s);
 
+/* ---- convex regions over an instanced scene: per region every (instance, shape) whose box passes, as a CSR — "which instances, and which
+ * shapes inside them, can this camera see", without flattening the scene.  Every operation below is rounded once in the set's dtype T, in
+ * the order written, with no contraction.
+ *  - Batch.  bvhgpu_region_*'s: n regions of m <= BVHGPU_REGION_MAX_PLANES WORLD-space planes (nx, ny, nz, d), `planes` is n x m x 4 T, with
+ *    that entry's box test and its CLASSIFY test, unchanged.  The set is a committed bvhgpu_instances (X_i, W_i, the top level over W).
+ *  - Candidates.  I_q is row q of bvhgpu_region_* over the top level with the world planes: the instances whose W_i passes, in the top
+ *    level's list order.
+ *  - Object-space planes of region q in instance i, per plane, from the FORWARD transform X_i = m[k][j] (a plane transforms by the
+ *    transpose of the forward map, n.(M p + t) + d = (M^T n).p + (n.t + d): no inverse enters):
+ *        n'[j] = ((m[0][j]*n[0] + m[1][j]*n[1]) + m[2][j]*n[2])          j = 0, 1, 2
+ *        d'    = (((n[0]*m[0][3] + n[1]*m[1][3]) + n[2]*m[2][3]) + d)
+ *    A padding plane (0, 0, 0, 0) stays a padding plane for a finite X_i.  Nothing is validated.
+ *  - Row q.  For each i in I_q, in order: L' = row of bvhgpu_region_* over member tree_of[i] with the planes (n', d').  The row is the
+ *    concatenation of (i, s) for s in L'.  An instance that passes at the top and reports no shape contributes nothing.  The box test is
+ *    applied to the member's boxes in their own frame: conservative there, and tighter than a world-space box around a rotated shape.  The
+ *    world-box test and the object-space tests are separate roundings; neither is asserted to imply the other: the composition is the
+ *    definition.
+ *  - BVHGPU_REGION_COUNT_ONLY, BVHGPU_REGION_CLASSIFY: as for bvhgpu_region_*; the byte of (i, s) is 1 iff the opposite corner of s's box
+ *    passes every (n', d').
+ *  - BVHGPU_REGION_INSTANCES_ONLY: the row is I_q itself — instance indices, no shapes ("which objects do I draw").  With CLASSIFY the byte
+ *    is 1 iff W_i lies wholly inside the world planes.  bvhgpu_region_* refuses this bit.
+ *  - No pruning and no shortcut.  An instance whose W_i lies wholly inside is still walked and tested shape by shape.
+ *  - Members.  Served exactly where bvhgpu_region_* serves that tree: built, rebuilt and refitted trees, uploaded FlatBvhs, one-shape
+ *    trees, built trees with empty child bounds.  A member with empty child bounds that arrived by scene import or broadcast:
+ *    BVHGPU_INVALID_ARG from this call (not from create), unless BVHGPU_REGION_INSTANCES_ONLY is set, which reads no member.
+ *  - n == 0 instances, n == 0 regions and m == 0 (every instance, every shape) behave as bvhgpu_region_* does; so do a set of one instance
+ *    and a top level with empty child bounds (coincident world boxes).
+ *  - Staleness and commits.  bvhgpu_instances_trace_*'s rules: an uncommitted or a stale set is refused before anything is launched; a
+ *    refit of a member is invisible until bvhgpu_instances_update.
+ *  - Limits.  n < 2^32 - 1, the number of (region, instance) pairs P <= 2^32 - 1, total <= 2^32 - 1, else BVHGPU_OVERFLOW; each is summed
+ *    in 64 bits before anything is sized by it.
+ *  - Output.  offsets[n + 1] u32, instance[total] u32, shape[total] u32 (absent with INSTANCES_ONLY), inside[total] bytes (CLASSIFY).
+ *  - Working memory.  Stage 1 (the top level) runs into a result object the set owns.  Stage 2 walks (pair, chunk) units, one wavefront
+ *    each: member t is cut into nc_t <= ceil(8192 / P) chunks, the units are P x max_t nc_t < P + 8192 whatever the members' sizes —
+ *    one u32 per unit twice over, one u32 per pair, 260 bytes per chunk of every member, in the caller's result object.
+ * The call is synchronous: the result object is complete on return.  HOST planes are staged into the result object.  *hits may be NULL
+ * or a result object of any kind, whose buffers are then reused.  bvhgpu_hits_info gives n and total; stats.hits == total.  The result is
+ * a kind of its own: every _fetch_* above and _device return BVHGPU_INVALID_ARG on it, bvhgpu_hits_fetch_region included, and
+ * bvhgpu_hits_fetch_instances_region on any other, a bvhgpu_region_* result included.  bvhgpu_hits_region_info gives the chunks per pair
+ * (the uniform stride max_t nc_t) and the largest member's chunk_entries; with INSTANCES_ONLY, the top level's.
+ * Refused, touching no buffer and leaving *hits as it was, in this order: a NULL set or a NULL `hits`; a result object that still holds
+ * an asynchronous batch; m > BVHGPU_REGION_MAX_PLANES; a NULL `planes` with n * m > 0; a `mem` that is neither BVHGPU_HOST nor
+ * BVHGPU_DEVICE; a set of another dtype (BVHGPU_DTYPE_MISMATCH); a flag bit other than the three; an uncommitted set; a stale set; the
+ * imported member above; n >= 2^32 - 1 (BVHGPU_OVERFLOW).  Everything not marked is BVHGPU_INVALID_ARG.
+ * bvhgpu_hits_fetch_instances_region: offsets (n + 1 u32), instance and shape (total u32 each) and inside (total bytes; NULL, or a
+ * CLASSIFY batch) copied to `mem`; each may be NULL; `shape` must be NULL for an INSTANCES_ONLY batch.  A COUNT_ONLY batch has offsets only. */
+#define BVHGPU_REGION_INSTANCES_ONLY 4u /* bvhgpu_instances_region_*: rows of instances, no shapes */
+int bvhgpu_instances_region_f32(bvhgpu_instances *s, const float *planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits **hits);
+int bvhgpu_instances_region_f64(bvhgpu_instances *s, const double *planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits **hits);
+int bvhgpu_hits_fetch_instances_region(bvhgpu_hits *hits, uint32_t *offsets, uint32_t *instance, uint32_t *shape, void *inside, int mem);
+
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */
 typedef struct { float build_ms, flatten_ms, traverse_kernel_ms, traverse_total_ms; } bvhgpu_timings;

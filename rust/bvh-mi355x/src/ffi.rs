@@ -13,6 +13,7 @@ pub const BVHGPU_WITHIN_COUNT_ONLY: c_uint = 2; // bvhgpu_within_*: offsets (nei
 pub const BVHGPU_REGION_MAX_PLANES: u32 = 32; // most planes per region of bvhgpu_region_*
 pub const BVHGPU_REGION_COUNT_ONLY: c_uint = 1; // bvhgpu_region_*: offsets and the total only
 pub const BVHGPU_REGION_CLASSIFY: c_uint = 2; // bvhgpu_region_*: one byte per reported shape, 1 = its AABB lies wholly inside
+pub const BVHGPU_REGION_INSTANCES_ONLY: c_uint = 4; // bvhgpu_instances_region_*: rows of instances, no shapes
 pub const BVHGPU_LEAF_BOX: c_int = 0; // leaf stage of bvhgpu_traverse_khits_*: {enter, exit} on the shape's own AABB
 pub const BVHGPU_LEAF_TRIANGLE: c_int = 1; // ... Intersection{distance, u, v} (needs the triangles)
 pub const BVHGPU_LEAF_SPHERE: c_int = 2; // ... {distance, exit} (needs the spheres)
@@ -224,6 +225,10 @@ extern "C" {
     pub fn bvhgpu_instances_update_f64(s: *mut bvhgpu_instances, xforms: *const f64, n: usize, mem: c_int) -> c_int;
     pub fn bvhgpu_instances_trace_f32(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, flags: c_uint, out_vals: *mut f32, out_instance: *mut u32, out_shape: *mut u32) -> c_int;
     pub fn bvhgpu_instances_trace_f64(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, flags: c_uint, out_vals: *mut f64, out_instance: *mut u32, out_shape: *mut u32) -> c_int;
+    // every (instance, shape) whose box passes the m world-space planes of region i, the planes re-expressed in each instance's object frame (offsets: n + 1, instance / shape: total, inside: total bytes with BVHGPU_REGION_CLASSIFY; BVHGPU_REGION_INSTANCES_ONLY: the instances whose world box passes, no shapes)
+    pub fn bvhgpu_instances_region_f32(s: *mut bvhgpu_instances, planes: *const f32, n: usize, m: u32, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_instances_region_f64(s: *mut bvhgpu_instances, planes: *const f64, n: usize, m: u32, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_hits_fetch_instances_region(h: *mut bvhgpu_hits, offsets: *mut u32, instance: *mut u32, shape: *mut u32, inside: *mut c_void, mem: c_int) -> c_int;
     pub fn bvhgpu_instances_boxes(s: *mut bvhgpu_instances, out: *mut c_void, mem: c_int) -> c_int;
     pub fn bvhgpu_instances_info(s: *const bvhgpu_instances, dtype: *mut c_int, n_trees: *mut usize, n_instances: *mut usize) -> c_int;
     pub fn bvhgpu_instances_destroy(s: *mut bvhgpu_instances);

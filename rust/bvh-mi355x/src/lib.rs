@@ -887,6 +887,41 @@ impl<T: GpuScalar> GpuInstances<T> {
         check(self.ctx, rc);
         (0..n).map(|j| InstanceHit { intersection: Intersection::new(vals[3 * j], vals[3 * j + 1], vals[3 * j + 2]), instance: inst[j], shape: shape[j] }).collect()
     }
+
+    /// Per region of `m` world-space planes `[nx, ny, nz, d]` the `(instance, shape)` pairs whose box passes, as a CSR
+    /// (`bvhgpu_instances_region_*`): the instances whose world box passes, in the top level's order, each walked with the planes
+    /// re-expressed in its object frame.  Returns `(offsets, instance, shape, inside)`; `instances_only`
+    /// (`ffi::BVHGPU_REGION_INSTANCES_ONLY`): the instances alone, `shape` stays empty; `classify`: a byte per row entry, 1 iff the box
+    /// lies wholly inside; `count_only`: the offsets alone.
+    pub fn region_query(&self, planes: &[[T; 4]], m: usize, classify: bool, count_only: bool, instances_only: bool) -> (Vec<u32>, Vec<u32>, Vec<u32>, Vec<u8>) {
+        let n = if m == 0 { 0 } else { planes.len() / m };
+        assert_eq!(n * m, planes.len(), "planes.len() must be a multiple of m");
+        let classify = classify && !count_only;
+        let flags = (if count_only { ffi::BVHGPU_REGION_COUNT_ONLY } else { 0 }) | (if classify { ffi::BVHGPU_REGION_CLASSIFY } else { 0 })
+            | (if instances_only { ffi::BVHGPU_REGION_INSTANCES_ONLY } else { 0 });
+        let mut hits = core::ptr::null_mut();
+        let mut offsets = vec![0u32; n + 1];
+        let (mut instance, mut shape, mut inside) = (Vec::new(), Vec::new(), Vec::new());
+        unsafe {
+            let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_region_f32(self.set, planes.as_ptr().cast(), n, m as u32, ffi::BVHGPU_HOST, flags, &mut hits)
+            } else {
+                ffi::bvhgpu_instances_region_f64(self.set, planes.as_ptr().cast(), n, m as u32, ffi::BVHGPU_HOST, flags, &mut hits)
+            };
+            check(self.ctx, rc);
+            let mut total = 0u64;
+            check(self.ctx, ffi::bvhgpu_hits_info(hits, core::ptr::null_mut(), &mut total, core::ptr::null_mut()));
+            let rows = if count_only { 0 } else { total as usize };
+            instance.resize(rows, 0u32);
+            if !instances_only { shape.resize(rows, 0u32); }
+            if classify { inside.resize(rows, 0u8); }
+            let shape_ptr = if instances_only { core::ptr::null_mut() } else { shape.as_mut_ptr() };
+            let inside_ptr = if classify { inside.as_mut_ptr() as *mut c_void } else { core::ptr::null_mut() };
+            check(self.ctx, ffi::bvhgpu_hits_fetch_instances_region(hits, offsets.as_mut_ptr(), instance.as_mut_ptr(), shape_ptr, inside_ptr, ffi::BVHGPU_HOST));
+            ffi::bvhgpu_hits_destroy(hits);
+        }
+        (offsets, instance, shape, inside)
+    }
 }
 
 impl<T: GpuScalar> Drop for GpuInstances<T> {

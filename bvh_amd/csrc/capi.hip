@@ -286,7 +286,7 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
     }
     if ((flags & BVHGPU_TRAVERSE_TRIANGLES) && (flags & BVHGPU_TRAVERSE_CLOSEST))
         return fail(ctx, BVHGPU_INVALID_ARG, "TRIANGLES and CLOSEST are alternatives");
-    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT | TRAVERSE_SPHERE_HIT | TRAVERSE_ALLHITS | TRAVERSE_WITHIN | TRAVERSE_REGION);   // (internal: only bvhgpu_traverse_any_* / _box_* / _sphere_* / _allhits_*, bvhgpu_within_* and bvhgpu_region_* set them)
+    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT | TRAVERSE_SPHERE_HIT | TRAVERSE_ALLHITS | TRAVERSE_WITHIN | TRAVERSE_REGION | TRAVERSE_INST_ALLHITS);   // (internal: only bvhgpu_traverse_any_* / _box_* / _sphere_* / _allhits_*, bvhgpu_within_*, bvhgpu_region_* and bvhgpu_instances_allhits_* set them)
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
@@ -1034,6 +1034,19 @@ template <typename T> int do_instances_update(bvhgpu_instances* s, const T* xfor
     if (rc != BVHGPU_OK) (void)hipStreamSynchronize(ctx->stream);   // (the set stays uncommitted: instances_pose cleared the mark first)
     return rc;
 }
+// what every batch over a set asks before anything is launched: a committed pose, and members that are still what the commit read
+int instances_current(bvhgpu_instances* s) {
+    bvhgpu_ctx* ctx = s->ctx;
+    if (!s->committed) return fail(ctx, BVHGPU_INVALID_ARG, "instances are not committed (the last commit failed): call bvhgpu_instances_update");
+    for (size_t k = 0; k < s->trees.size(); k++) {   // what the commit read of every member must still be what the member holds
+        const bvhgpu_tree* t = s->trees[k];
+        const bvhgpu_instances::Seen& c = s->seen[k];
+        if (t->trav.p != c.trav || t->aabbs.p != c.aabbs || t->tris.p != c.tris || t->n != c.n || t->n_trav != c.n_trav || t->gen != c.gen ||
+            !t->flattened || !t->has_tris || t->pending_build || t->pending_recv)
+            return fail(ctx, BVHGPU_INVALID_ARG, "instances are stale: call bvhgpu_instances_update");
+    }
+    return BVHGPU_OK;
+}
 // do_khits' staging for rays: one layout (rays | tmax | vals | instance | shape), synchronous, and a refused call touches no buffer
 template <typename T>
 int do_instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, unsigned flags, T* out_vals,
@@ -1045,14 +1058,7 @@ int do_instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays,
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
     if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from ray dtype");
     if (flags & ~BVHGPU_TRAVERSE_FIRST) return fail(ctx, BVHGPU_INVALID_ARG, "instance trace flags: 0 or BVHGPU_TRAVERSE_FIRST");
-    if (!s->committed) return fail(ctx, BVHGPU_INVALID_ARG, "instances are not committed (the last commit failed): call bvhgpu_instances_update");
-    for (size_t k = 0; k < s->trees.size(); k++) {   // what the commit read of every member must still be what the member holds
-        const bvhgpu_tree* t = s->trees[k];
-        const bvhgpu_instances::Seen& c = s->seen[k];
-        if (t->trav.p != c.trav || t->aabbs.p != c.aabbs || t->tris.p != c.tris || t->n != c.n || t->n_trav != c.n_trav || t->gen != c.gen ||
-            !t->flattened || !t->has_tris || t->pending_build || t->pending_recv)
-            return fail(ctx, BVHGPU_INVALID_ARG, "instances are stale: call bvhgpu_instances_update");
-    }
+    { const int rc = instances_current(s); if (rc != BVHGPU_OK) return rc; }
     if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 rays in one batch");
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -1089,14 +1095,7 @@ int do_instances_region(bvhgpu_instances* s, const T* planes, size_t n, uint32_t
     if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from plane dtype");
     if (flags & ~(BVHGPU_REGION_COUNT_ONLY | BVHGPU_REGION_CLASSIFY | BVHGPU_REGION_INSTANCES_ONLY))
         return fail(ctx, BVHGPU_INVALID_ARG, "instance region flags: BVHGPU_REGION_COUNT_ONLY, BVHGPU_REGION_CLASSIFY and BVHGPU_REGION_INSTANCES_ONLY only");
-    if (!s->committed) return fail(ctx, BVHGPU_INVALID_ARG, "instances are not committed (the last commit failed): call bvhgpu_instances_update");
-    for (size_t k = 0; k < s->trees.size(); k++) {   // what the commit read of every member must still be what the member holds
-        const bvhgpu_tree* t = s->trees[k];
-        const bvhgpu_instances::Seen& c = s->seen[k];
-        if (t->trav.p != c.trav || t->aabbs.p != c.aabbs || t->tris.p != c.tris || t->n != c.n || t->n_trav != c.n_trav || t->gen != c.gen ||
-            !t->flattened || !t->has_tris || t->pending_build || t->pending_recv)
-            return fail(ctx, BVHGPU_INVALID_ARG, "instances are stale: call bvhgpu_instances_update");
-    }
+    { const int rc = instances_current(s); if (rc != BVHGPU_OK) return rc; }
     if (!(flags & BVHGPU_REGION_INSTANCES_ONLY))
         for (const bvhgpu_tree* t : s->trees)
             if (t->exact_only && !t->built && !t->unfolded)
@@ -1113,6 +1112,34 @@ int do_instances_region(bvhgpu_instances* s, const T* planes, size_t n, uint32_t
             dev = h->qbuf.as<T>();
         }
         instances_region_batch<T>(s, dev, n, m, flags, h);
+        return (int)BVHGPU_OK;
+    });
+}
+
+// do_allhits' shape over an instance set, behind do_instances_trace's commit and staleness rules; the result goes to a result object
+// (instances_allhits.hip), whose buffers a later batch of any kind reuses.  A refused call touches no buffer and leaves *hits as it was.
+template <typename T>
+int do_instances_allhits(bvhgpu_instances* s, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
+    using Ray = typename Traits<T>::Ray;
+    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    bvhgpu_ctx* ctx = s->ctx;
+    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
+    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
+    if (n && !rays) return fail(ctx, BVHGPU_INVALID_ARG, "rays is NULL");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from ray dtype");
+    if (flags & ~(BVHGPU_INSTANCES_ALLHITS_LIST_ORDER | BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY))
+        return fail(ctx, BVHGPU_INVALID_ARG, "instance all-hits flags: BVHGPU_INSTANCES_ALLHITS_LIST_ORDER and BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY only");
+    { const int rc = instances_current(s); if (rc != BVHGPU_OK) return rc; }
+    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 rays in one batch");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        bvhgpu_hits* h = batch_hits(hits);
+        const auto* dev = static_cast<const Ray*>(to_device(ctx, rays, n * sizeof(Ray), mem, ctx->upload));
+        stage_tmax<T>(ctx, h, tmax, n, mem);   // (a HOST tmax is staged as do_allhits stages it)
+        const T* td = n ? static_cast<const T*>(h->pend_tmax) : nullptr;
+        h->pend_tmax = nullptr;                // (nothing replays this batch)
+        instances_allhits_batch<T>(s, dev, td, n, flags, h);
         return (int)BVHGPU_OK;
     });
 }
@@ -1689,6 +1716,7 @@ int bvhgpu_hits_fetch_triangles(bvhgpu_hits* h, void* isect, int mem) {
     if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
     if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "a sphere-hit batch has no triangle values: use bvhgpu_hits_fetch_sphere");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
@@ -1705,6 +1733,7 @@ static int fetch_per_ray(bvhgpu_hits* h, void* values, uint32_t* shape, int mem,
     if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
     if ((h->flags & TRAVERSE_SPHERE_HIT) && kind_bit != TRAVERSE_SPHERE_HIT)
         return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
@@ -1758,6 +1787,7 @@ int bvhgpu_hits_fetch(bvhgpu_hits* h, uint32_t* offsets, uint32_t* indices, void
     if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "an all-hits batch has a CSR of its own: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
@@ -1780,6 +1810,7 @@ int bvhgpu_hits_fetch_allhits(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape
     if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
     if (!(h->flags & TRAVERSE_ALLHITS)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_traverse_allhits_* batch");
@@ -1800,6 +1831,7 @@ int bvhgpu_hits_fetch_within(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape,
     if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
     if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
     if (!(h->flags & TRAVERSE_WITHIN)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_within_* batch");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
@@ -1819,6 +1851,7 @@ int bvhgpu_hits_fetch_region(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape,
     if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
@@ -1847,6 +1880,7 @@ int bvhgpu_hits_fetch_instances_region(bvhgpu_hits* h, uint32_t* offsets, uint32
     if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
@@ -1870,6 +1904,26 @@ int bvhgpu_hits_fetch_instances_region(bvhgpu_hits* h, uint32_t* offsets, uint32
     });
 }
 
+// the CSR of an all-hits batch over an instance set: offsets (n_rays + 1 u32), the instances and the shapes (total u32 each), the records
+// (total x 3 T); each may be NULL.  A COUNT_ONLY batch has offsets only.  Every other kind of result is refused.
+int bvhgpu_hits_fetch_instances_allhits(bvhgpu_hits* h, uint32_t* offsets, uint32_t* instance, uint32_t* shape, void* vals, int mem) {
+    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = h->ctx;
+    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (!(h->flags & TRAVERSE_INST_ALLHITS)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_instances_allhits_* batch");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if ((instance || shape || vals) && h->wi_count_only)
+        return fail(ctx, BVHGPU_INVALID_ARG, "the batch was run with BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY: it has offsets only");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
+        if (instance && h->total) copy_out(ctx, instance, h->rg_instance.p, h->total * 4, mem);
+        if (shape && h->total) copy_out(ctx, shape, h->indices.p, h->total * 4, mem);
+        if (vals && h->total) copy_out(ctx, vals, h->ah_vals.p, h->total * 3 * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
+        return (int)BVHGPU_OK;
+    });
+}
+
 int bvhgpu_hits_region_info(const bvhgpu_hits* h, uint32_t* n_chunks, uint32_t* chunk_entries) {
     if (!h) return BVHGPU_INVALID_ARG;
     if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
@@ -1882,6 +1936,7 @@ int bvhgpu_hits_region_info(const bvhgpu_hits* h, uint32_t* n_chunks, uint32_t* 
 int bvhgpu_hits_device(const bvhgpu_hits* h, const uint32_t** offsets, const uint32_t** indices, const void** tslice) {
     if (!h) return BVHGPU_INVALID_ARG;
     if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
     if (h->flags & TRAVERSE_ALLHITS) return fail(h->ctx, BVHGPU_INVALID_ARG, "an all-hits batch has a CSR of its own: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (h->flags & TRAVERSE_REGION) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
@@ -1925,6 +1980,14 @@ int bvhgpu_instances_region_f32(bvhgpu_instances* s, const float* planes, size_t
 }
 int bvhgpu_instances_region_f64(bvhgpu_instances* s, const double* planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits** hits) {
     return do_instances_region<double>(s, planes, n, m, mem, flags, hits);
+}
+int bvhgpu_instances_allhits_f32(bvhgpu_instances* s, const bvhgpu_ray_f32* rays, const float* tmax, size_t n_rays, int mem, unsigned flags,
+                                 bvhgpu_hits** hits) {
+    return do_instances_allhits<float>(s, rays, tmax, n_rays, mem, flags, hits);
+}
+int bvhgpu_instances_allhits_f64(bvhgpu_instances* s, const bvhgpu_ray_f64* rays, const double* tmax, size_t n_rays, int mem, unsigned flags,
+                                 bvhgpu_hits** hits) {
+    return do_instances_allhits<double>(s, rays, tmax, n_rays, mem, flags, hits);
 }
 int bvhgpu_instances_boxes(bvhgpu_instances* s, void* out, int mem) {
     if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");

@@ -59,6 +59,9 @@ constexpr unsigned TRAVERSE_REGION = 1u << 26;
 constexpr int REGION_INST_NONE = 0;     // bvhgpu_region_*: rows of shapes
 constexpr int REGION_INST_SHAPES = 1;   // bvhgpu_instances_region_*: rows of (instance, shape)
 constexpr int REGION_INST_ONLY = 2;     // ... with BVHGPU_REGION_INSTANCES_ONLY: rows of instances (in `indices`)
+// result objects of bvhgpu_instances_allhits_* (instances_allhits.hip): marked like TRAVERSE_ALLHITS; the only bit such a result carries
+// (BVHGPU_INSTANCES_ALLHITS_* are never stored in bvhgpu_hits::flags)
+constexpr unsigned TRAVERSE_INST_ALLHITS = 1u << 25;
 
 }  // namespace bvhgpu
 
@@ -315,6 +318,9 @@ struct bvhgpu_hits {
     bvhgpu::DevBuf rg_pairs;             // per (region, instance) pair: its region
     bvhgpu::DevBuf rg_members;           // per member tree: region.hip RegionMember<T> (rebuilt by every batch, like the ancestor table)
     std::vector<unsigned char> rg_members_host;   // its host image (alive while the upload is in flight)
+    // all-hits batches over an instance set (bvhgpu_instances_allhits_*, instances_allhits.hip): the CSR is `offsets` / `rg_instance` / `indices`
+    // (the shapes) / `ah_vals` (total x 3 T); the scan runs in ah_counts / ah_sums / ah_work / ah_pos, a COUNT_ONLY batch sets wi_count_only
+    bvhgpu::DevBuf ia_list_shape;        // total u32: the shapes of the long rows of a sorted batch in the double order (the sort gathers from it)
     uint32_t replays = 0;               // times bvhgpu_hits_wait had to enqueue the asynchronous batch again
     int deferred_rc = 0;                // status of a completion that ran on behalf of another call (rebuild / destroy of the tree)
     std::string deferred_err;
@@ -435,6 +441,12 @@ void region_batch(bvhgpu_tree* t, const T* planes_dev, size_t n, uint32_t m, uns
 // batch has more than 2^32-1 (region, instance) pairs or reports more than 2^32-1 shapes (the result object then holds an empty result).
 template <typename T>
 void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, uint32_t m, unsigned flags, bvhgpu_hits* h);
+// instances_allhits.hip: every hit per ray over a committed instance set as a CSR (bvhgpu_instances_allhits_*); flags:
+// BVHGPU_INSTANCES_ALLHITS_*; tmax_dev: NULL or n segment ends.  Synchronous: h->offsets / h->rg_instance / h->indices / h->ah_vals and
+// h->total are complete on return.  Throws Fail::Overflow when the batch has more than 2^32-1 candidates (the result object then holds an
+// empty result of this kind).
+template <typename T>
+void instances_allhits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, unsigned flags, bvhgpu_hits* h);
 // rays.hip
 template <typename T>
 void ray_triangle_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays_dev, const T* tris_dev, size_t n, T* out_dev);

@@ -1,0 +1,297 @@
+// instances_allhits.hip — every hit of every ray over an instance set, in order, as a CSR (bvhgpu_instances_allhits_*; include/bvh_mi355x.h,
+// DESIGN.md §4m).
+//
+// The definition is the candidate table of bvhgpu_instances_trace_* (instances.hip) without the cut to one winner: ray j meets the pairs
+// (instance, shape) in the double order — the instances in the order of the top level's list, within each the shapes in the order of the
+// member's list — and (i, s) is a candidate iff its distance < tmax[j], strict, in T.  Row j is ALL candidates in a stable ascending sort by
+// distance, or with BVHGPU_INSTANCES_ALLHITS_LIST_ORDER in the double order.  A candidate's distance is never NaN (it passed a strict <), so
+// the sorted order is the total order on (distance, position in the double order): it is unique whatever produces it.  No pruning: both
+// walks visit the whole double order (§4e's inverted-box reason, §4j).
+//
+// The batch is rows.hip's schedule (count walk, scan, ONE host read, offsets, fill walk, a workgroup per long row); every walk is
+// k_instances_trace's loop, one ray per lane (instances_walk).  What this family puts into it:
+//   k_instances_allhits_count     counts[q] = the candidates of ray q
+//   k_instances_allhits_fill      A row of a sorted batch up to INST_ALLHITS_LANE_ROW_MAX is built by the lane's stable insertion (search from
+//                                 the back with the strict <) on its own region — the key of element e lives in vals[e * 3] — and the
+//                                 whole records are then computed again from the world ray and (instance, shape).  A LIST_ORDER row gets
+//                                 its records appended as the walk meets them.  A longer row of a sorted batch gets (distance, instance)
+//                                 appended in the double order, its shapes into a scratch row in the same order (and its positions, beyond
+//                                 INST_ALLHITS_LDS_ROW_MAX) and is left to
+//   k_instances_allhits_sort_row  rows_bitonic on the keys (distance, position) with the instance as payload, in LDS up to
+//                                 INST_ALLHITS_LDS_ROW_MAX elements, in place in global memory beyond; the shape of an element is gathered
+//                                 from the scratch row by its position; then the records of the row.
+// The row length is uniform per workgroup of k_instances_allhits_sort_row: every loop bound and every barrier there depends on it alone.
+#include <cstdio>
+
+#include "instances.hpp"
+#include "rows.hpp"
+#include "walk.hpp"
+
+namespace bvhgpu {
+
+// Thresholds: all-hits' (allhits.hip), taken over unmeasured for this family.  An element sorted in LDS is an f64 key, a
+// position and an instance — rows_lds_row_max_ok's 16 bytes: 32 KB a row in f64, 24 KB in f32; the shapes stay in global memory.
+constexpr uint32_t INST_ALLHITS_LANE_ROW_MAX = 32;
+constexpr uint32_t INST_ALLHITS_LDS_ROW_MAX = 2048;
+static_assert(rows_lds_row_max_ok(INST_ALLHITS_LDS_ROW_MAX), "a row sorted in LDS must fit a workgroup's LDS, padded to a power of two");
+
+// what both walks and the sort-row kernel read of the set
+template <typename T> struct InstScene {
+    const TravNode<T>* top;
+    uint32_t n_top;
+    const InstRec<T>* recs;
+    const InstTree<T>* tbl;
+};
+
+// {distance, u, v} of (inst, s) for the WORLD ray (o, d): the world ray in the instance's frame by k_instances_trace's sequence, then the
+// triangle test — the operands and the operations of the walk, hence its bits
+template <typename T>
+__device__ __forceinline__ void inst_record(const InstScene<T>& sc, const T o[3], const T d[3], uint32_t inst, uint32_t s, T v[3]) {
+    const InstRec<T> rec = load_rec<T>(sc.recs + inst);
+    const InstTree<T> t = sc.tbl[rec.tree];
+    T oo[3], dd[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { oo[k] = row4<T>(rec.y + 4 * k, o); dd[k] = row3<T>(rec.y + 4 * k, d); }
+    ray_triangle<T>(oo, dd, t.tris + 9 * (size_t)s, v);
+}
+
+// k_instances_trace's loop: one ray per lane, ONE loop; a lane is either in the top-level array with the world ray (inst == NONE) or in a
+// member's array with the object-space ray.  on_candidate(instance, shape, {distance, u, v}) for every pair of the double order whose
+// distance is below tm.  Every lane of the wave calls it (the slab test's variant is chosen per wave); a lane with !active walks nothing.
+template <typename T, typename F>
+__device__ __forceinline__ void instances_walk(const InstScene<T>& sc, const typename Traits<T>::Ray* __restrict__ rp, bool active, T tm, F&& on_candidate) {
+    T o[3] = {0, 0, 0}, d[3] = {0, 0, 0}, inv[3] = {0, 0, 0};
+    bool fin = true, wfin = true;   // the current ray / the world ray passes ray_is_finite (the NaN-free slab test is exact for it)
+    if (active) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) { o[k] = rp->o[k]; d[k] = rp->d[k]; inv[k] = rp->inv[k]; }
+        wfin = ray_is_finite<T>(o, inv);
+        fin = wfin;
+    }
+    const TravNode<T>* nodes = sc.top;
+    const T* tris = nullptr;
+    uint32_t i = 0, end = active ? sc.n_top : 0u, inst = NONE, top_next = 0;
+    while (true) {
+        const bool run = i < end;
+        if (!__any(run)) break;
+        const bool fast = !__any(run && !fin);   // wave-uniform
+        if (run) {
+            const NodeRegs<T> nd = load_node(nodes + i);
+            T t0, t1;
+            const bool hit = fast ? slab_hit_finite<T>(o, inv, nd.mn, nd.mx) : slab_hit<T>(o, inv, nd.mn, nd.mx, t0, t1);
+            const bool leaf = trav_is_leaf(nd.shape);
+            i = hit ? i + 1 : nd.exit;   // a leaf's exit IS i+1
+            if (hit && leaf) {
+                if (inst != NONE) {   // a triangle of the member: the pair (inst, shape)
+                    T v[3];
+                    ray_triangle<T>(o, d, tris + 9 * (size_t)nd.shape, v);
+                    if (v[0] < tm) on_candidate(inst, nd.shape, v);
+                } else {              // an instance's world box: into its tree with the ray in the object's frame
+                    top_next = i;
+                    inst = nd.shape;
+                    const InstRec<T> rec = load_rec<T>(sc.recs + inst);
+                    const InstTree<T> t = sc.tbl[rec.tree];
+                    T oo[3], dd[3];
+#pragma unroll
+                    for (int k = 0; k < 3; k++) { oo[k] = row4<T>(rec.y + 4 * k, o); dd[k] = row3<T>(rec.y + 4 * k, d); }
+#pragma unroll
+                    for (int k = 0; k < 3; k++) { o[k] = oo[k]; d[k] = dd[k]; inv[k] = (T)1 / dd[k]; }
+                    fin = ray_is_finite<T>(o, inv);
+                    nodes = t.trav; tris = t.tris; i = 0; end = t.n_trav;
+                }
+            }
+            if (inst != NONE && i >= end) {   // the member's array has ended: back to the top level, behind the leaf that sent the lane here
+#pragma unroll
+                for (int k = 0; k < 3; k++) { o[k] = rp->o[k]; d[k] = rp->d[k]; inv[k] = rp->inv[k]; }
+                fin = wfin;
+                nodes = sc.top; i = top_next; end = sc.n_top; inst = NONE;
+            }
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_instances_allhits_count(InstScene<T> sc, const typename Traits<T>::Ray* __restrict__ rays, const T* __restrict__ tmaxs,
+                                                                 uint32_t n, uint32_t* __restrict__ counts) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = q < n;
+    const T tm = active && tmaxs ? tmaxs[q] : Traits<T>::inf();
+    uint32_t cnt = 0;
+    instances_walk<T>(sc, rays + (active ? q : 0u), active, tm, [&](uint32_t, uint32_t, const T*) { cnt++; });
+    if (active) counts[q] = cnt;
+}
+
+// ---- the second walk ----------------------------------------------------------------------------------------------------------------
+// list_shape: NULL, or total u32 — the shapes of the long rows in the double order (a sorted batch that has long rows)
+// pos:        NULL, or total u32 — the positions of the rows beyond INST_ALLHITS_LDS_ROW_MAX (a sorted batch that has such rows)
+template <typename T, bool SORTED>
+__global__ __launch_bounds__(256) void k_instances_allhits_fill(InstScene<T> sc, const typename Traits<T>::Ray* __restrict__ rays, const T* __restrict__ tmaxs,
+                                                                uint32_t n, const uint32_t* __restrict__ offsets, uint32_t* __restrict__ instance,
+                                                                uint32_t* __restrict__ shape, T* __restrict__ vals, uint32_t* __restrict__ list_shape,
+                                                                uint32_t* __restrict__ pos) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t beg = q < n ? offsets[q] : 0u, len = q < n ? offsets[q + 1] - beg : 0u;
+    // (the count pass walked an empty row's ray: nothing to write.  Leaving it out can change the wave's `fast` choice against the count
+    // walk's — only ever towards slab_hit_finite, which is exact for every lane whose own ray is finite: the same candidates either way)
+    const bool active = len != 0;
+    const typename Traits<T>::Ray* rp = rays + (active ? q : 0u);
+    const T tm = active && tmaxs ? tmaxs[q] : Traits<T>::inf();
+    uint32_t* __restrict__ ri = instance + beg;
+    uint32_t* __restrict__ rs = shape + beg;
+    T* __restrict__ rv = vals + (size_t)beg * 3;
+    const bool insert = SORTED && len <= INST_ALLHITS_LANE_ROW_MAX;
+    const bool with_list = SORTED && !insert && list_shape != nullptr;
+    const bool with_pos = SORTED && pos != nullptr && len > INST_ALLHITS_LDS_ROW_MAX;
+    uint32_t cnt = 0;
+    instances_walk<T>(sc, rp, active, tm, [&](uint32_t inst, uint32_t s, const T* v) {
+        if (cnt >= len) return;   // (never: this walk is the count pass's; a lane stays inside its own region whatever happens)
+        if (insert) {
+            // ascending list: the first element e with dist < e is where a scan from the back stops, so search and shift are one loop
+            const T dist = v[0];
+            uint32_t hole = cnt;
+#pragma unroll 1
+            while (hole > 0) {
+                const T e = rv[(size_t)(hole - 1) * 3];
+                if (!(dist < e)) break;
+                rv[(size_t)hole * 3] = e;
+                ri[hole] = ri[hole - 1];
+                rs[hole] = rs[hole - 1];
+                hole--;
+            }
+            rv[(size_t)hole * 3] = dist;
+            ri[hole] = inst;
+            rs[hole] = s;
+        } else if (SORTED) {   // a long row: (distance, instance) and the shape in the double order for k_instances_allhits_sort_row
+            rv[(size_t)cnt * 3] = v[0];
+            ri[cnt] = inst;
+            if (with_list) list_shape[beg + cnt] = s;
+            if (with_pos) pos[beg + cnt] = cnt;
+        } else {               // the double order: the record as the walk meets it
+            ri[cnt] = inst;
+            rs[cnt] = s;
+            rv[(size_t)cnt * 3] = v[0]; rv[(size_t)cnt * 3 + 1] = v[1]; rv[(size_t)cnt * 3 + 2] = v[2];
+        }
+        cnt++;
+    });
+    if (insert && active) {
+        // the whole record of every element, computed again from the world ray and (instance, shape)
+        T o[3], d[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) { o[k] = rp->o[k]; d[k] = rp->d[k]; }
+#pragma unroll 1
+        for (uint32_t j = 0; j < cnt; j++) {
+            T v[3];
+            inst_record<T>(sc, o, d, ri[j], rs[j], v);
+            rv[(size_t)j * 3] = v[0]; rv[(size_t)j * 3 + 1] = v[1]; rv[(size_t)j * 3 + 2] = v[2];
+        }
+    }
+}
+
+// one workgroup per long row of a sorted batch
+template <typename T>
+__global__ __launch_bounds__(ROWS_SORT_THREADS) void k_instances_allhits_sort_row(InstScene<T> sc, const uint32_t* __restrict__ work,
+                                                                                 const typename Traits<T>::Ray* __restrict__ rays,
+                                                                                 const uint32_t* __restrict__ offsets, uint32_t* instance, uint32_t* shape,
+                                                                                 T* vals, const uint32_t* __restrict__ list_shape, uint32_t* pos) {
+    __shared__ T ld[INST_ALLHITS_LDS_ROW_MAX];
+    __shared__ uint32_t lp[INST_ALLHITS_LDS_ROW_MAX];
+    __shared__ uint32_t li[INST_ALLHITS_LDS_ROW_MAX];
+    const uint32_t q = work[blockIdx.x];
+    const uint32_t beg = offsets[q], len = offsets[q + 1] - beg;   // uniform over the workgroup
+    uint32_t P = 1;
+    while (P < len) P <<= 1;
+    uint32_t* ri = instance + beg;
+    uint32_t* rs = shape + beg;
+    T* rv = vals + (size_t)beg * 3;
+    const bool in_lds = len <= INST_ALLHITS_LDS_ROW_MAX;
+    if (in_lds) {
+        for (uint32_t e = threadIdx.x; e < len; e += ROWS_SORT_THREADS) { ld[e] = rv[(size_t)e * 3]; lp[e] = e; li[e] = ri[e]; }
+        __syncthreads();
+        rows_bitonic<T, false>(ld, 1u, lp, li, len, P);
+    } else {   // (the host passes the positions whenever a row is this long, and checks that it does)
+        __threadfence_block();
+        __syncthreads();
+        rows_bitonic<T, true>(rv, 3u, pos + beg, ri, len, P);
+    }
+    // the records of the row, from the world ray and the sorted (instance, shape) (the network ended with a barrier)
+    const typename Traits<T>::Ray* rp = rays + q;
+    T o[3], d[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { o[k] = rp->o[k]; d[k] = rp->d[k]; }
+    for (uint32_t e = threadIdx.x; e < len; e += ROWS_SORT_THREADS) {
+        const uint32_t p = in_lds ? lp[e] : pos[beg + e];
+        const uint32_t inst = in_lds ? li[e] : ri[e];
+        if (p >= len) continue;   // (the positions are a permutation of 0 .. len - 1: no read beyond the row's scratch whatever happens)
+        const uint32_t s = list_shape[beg + p];
+        T v[3];
+        inst_record<T>(sc, o, d, inst, s, v);
+        if (in_lds) ri[e] = inst;
+        rs[e] = s;
+        rv[(size_t)e * 3] = v[0]; rv[(size_t)e * 3 + 1] = v[1]; rv[(size_t)e * 3 + 2] = v[2];
+    }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+template <typename T>
+static void instances_allhits_launch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, bool sorted, bool count_only,
+                                     bvhgpu_hits* h) {
+    hipStream_t st = s->ctx->stream;
+    const InstScene<T> sc = {s->top->trav.as<TravNode<T>>(), (uint32_t)s->top->n_trav, s->recs.as<InstRec<T>>(), s->table.as<InstTree<T>>()};
+    const uint32_t n32 = (uint32_t)n;
+    const dim3 rgrid((unsigned)((n + 255) / 256)), block(256);
+    const bool rows_sorted = sorted && !count_only;
+    uint32_t* counts = rows_begin(h, n, rows_sorted);
+    uint32_t* offsets = h->offsets.as<uint32_t>();
+    hipLaunchKernelGGL((k_instances_allhits_count<T>), rgrid, block, 0, st, sc, rays_dev, tmax_dev, n32, counts);
+    const RowsTotals rows = rows_scan(h, n, rows_sorted ? INST_ALLHITS_LANE_ROW_MAX : 0u, INST_ALLHITS_LDS_ROW_MAX);
+    if (rows.total == 0) return;   // every row is empty
+    rows_offsets(h, n);
+    if (!count_only) {
+        const size_t total = (size_t)rows.total;
+        h->rg_instance.reserve(total * 4);
+        h->indices.reserve(total * 4);
+        h->ah_vals.reserve(total * 3 * sizeof(T));
+        uint32_t *list_shape = nullptr, *pos = nullptr;
+        if (rows.n_long) { h->ia_list_shape.reserve(total * 4); list_shape = h->ia_list_shape.as<uint32_t>(); }
+        if (rows.n_beyond_lds) { h->ah_pos.reserve(total * 4); pos = h->ah_pos.as<uint32_t>(); }
+        uint32_t* instance = h->rg_instance.as<uint32_t>();
+        uint32_t* shape = h->indices.as<uint32_t>();
+        T* vals = h->ah_vals.as<T>();
+        if (sorted) hipLaunchKernelGGL((k_instances_allhits_fill<T, true>), rgrid, block, 0, st, sc, rays_dev, tmax_dev, n32, offsets, instance, shape, vals,
+                                       list_shape, pos);
+        else hipLaunchKernelGGL((k_instances_allhits_fill<T, false>), rgrid, block, 0, st, sc, rays_dev, tmax_dev, n32, offsets, instance, shape, vals,
+                                list_shape, pos);
+        // the sort-row kernel reads both without a test of its own
+        if (sorted && ((rows.n_long && !list_shape) || (rows.n_beyond_lds && !pos))) throw HipFail{hipErrorInvalidValue, nullptr, __LINE__, Fail::None};
+        if (sorted && rows.n_long)
+            hipLaunchKernelGGL((k_instances_allhits_sort_row<T>), dim3(rows.n_long), dim3(ROWS_SORT_THREADS), 0, st, sc, h->ah_work.as<uint32_t>(), rays_dev,
+                               offsets, instance, shape, vals, list_shape, pos);
+    }
+    BVH_HIP(hipGetLastError());
+    h->total = rows.total;
+}
+
+template <typename T>
+void instances_allhits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, unsigned flags, bvhgpu_hits* h) {
+    bvhgpu_ctx* ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    const bool sorted = (flags & BVHGPU_INSTANCES_ALLHITS_LIST_ORDER) == 0;
+    const bool count_only = (flags & BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY) != 0;
+    // the result object becomes an (empty) result of this kind first: whatever fails below leaves it consistent
+    h->offsets.reserve((n + 1) * 4);
+    rows_reset(h, ctx, Traits<T>::dtype, TRAVERSE_INST_ALLHITS, BVHGPU_LEAF_TRIANGLE, count_only);
+    char name[96];
+    if (count_only) std::snprintf(name, sizeof name, "bvhgpu::k_instances_allhits_count<%s>", walk_type_name<T>());
+    else std::snprintf(name, sizeof name, "bvhgpu::k_instances_allhits_fill<%s, %s>", walk_type_name<T>(), sorted ? "true" : "false");
+    h->walk_kernel = name;
+    BVH_HIP(hipMemsetAsync(h->offsets.p, 0, 4, st));
+    if (n == 0 || s->n == 0) BVH_HIP(hipMemsetAsync(h->offsets.p, 0, (n + 1) * 4, st));   // no rays, or no instances: every row is empty
+    else instances_allhits_launch<T>(s, rays_dev, tmax_dev, n, sorted, count_only, h);
+    BVH_HIP(hipStreamSynchronize(st));   // the result is complete when the call returns
+    h->n_rays = n;
+    h->stats.hits = h->total;
+}
+template void instances_allhits_batch<float>(bvhgpu_instances*, const bvhgpu_ray_f32*, const float*, size_t, unsigned, bvhgpu_hits*);
+template void instances_allhits_batch<double>(bvhgpu_instances*, const bvhgpu_ray_f64*, const double*, size_t, unsigned, bvhgpu_hits*);
+
+}  // namespace bvhgpu

@@ -154,6 +154,49 @@ class Instances(_Typed):
             out["inside"] = inside
         return out
 
+    def allhits_batch(self, rays: RayBatch, tmax=None, sort: bool = True, count_only: bool = False) -> dict:
+        """bvhgpu_instances_allhits_*: per ray EVERY (instance, shape) whose triangle it hits with distance < tmax[i] (None: +inf), as a
+        CSR.  sort=True: each row ascending by distance, ties in walk order (instances in the top level's order, shapes in the member's
+        order) — its head is closest_hits' answer; sort=False: walk order, no sort pass — its head is any_hits' answer.  count_only:
+        offsets alone (the hit counts).
+        returns {offsets[n+1], instance[total], shape[total], vals[total, 3] = {distance, u, v}} (offsets only with count_only).  HOST rays:
+        numpy out, offsets and indices as uint32.  Rays in HBM: torch tensors on the same device, indices as torch.int32, offsets as
+        torch.int64."""
+        if rays.sfx != self.sfx:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from the instance set's dtype")
+        _keep, tp = api._side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
+        n = rays.n
+        flags = (0 if sort else _lib.INSTANCES_ALLHITS_LIST_ORDER) | (_lib.INSTANCES_ALLHITS_COUNT_ONLY if count_only else 0)
+        dev = rays.device.device if rays.mem == DEVICE else None
+        if dev is not None:
+            api._torch_sync(dev)
+        lib = _lib.load()
+        if getattr(self, "_hits", None) is None:
+            self._hits = api._Hits(self.ctx)     # (the set's own result object: its buffers are reused by every batch)
+        hits = self._hits
+        check(getattr(lib, f"bvhgpu_instances_allhits_{self.sfx}")(self._s, rays._ptr(), tp, n, rays.mem, flags, C.byref(hits.h)), self.ctx._h)
+        rows = 0 if count_only else hits._total()
+        if dev is not None:
+            import torch
+            off32 = torch.empty(n + 1, dtype=torch.int32, device=dev)
+            instance = torch.empty(rows, dtype=torch.int32, device=dev)
+            shape = torch.empty(rows, dtype=torch.int32, device=dev)
+            vals = torch.empty((rows, 3), dtype=api._torch_ft(self.ft), device=dev)
+            api._torch_sync(dev)
+            check(lib.bvhgpu_hits_fetch_instances_allhits(hits.h, ptr(off32.data_ptr()), ptr(instance.data_ptr()) if rows else None,
+                                                          ptr(shape.data_ptr()) if rows else None, ptr(vals.data_ptr()) if rows else None,
+                                                          DEVICE), self.ctx._h)
+            offsets = off32.to(torch.int64) & 0xFFFFFFFF
+        else:
+            offsets = np.zeros(n + 1, dtype=np.uint32)
+            instance, shape = np.zeros(rows, dtype=np.uint32), np.zeros(rows, dtype=np.uint32)
+            vals = np.zeros((rows, 3), dtype=self.ft)
+            check(lib.bvhgpu_hits_fetch_instances_allhits(hits.h, ptr(offsets), ptr(instance) if rows else None, ptr(shape) if rows else None,
+                                                          ptr(vals) if rows else None, _lib.HOST), self.ctx._h)
+        if count_only:
+            return dict(offsets=offsets)
+        return dict(offsets=offsets, instance=instance, shape=shape, vals=vals)
+
     @property
     def world_boxes(self) -> np.ndarray:
         """W_i of the committed pose, (n, 6) [min xyz, max xyz]"""

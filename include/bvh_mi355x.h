@@ -865,6 +865,49 @@ int bvhgpu_instances_region_f32(bvhgpu_instances *s, const float *planes, size_t
 int bvhgpu_instances_region_f64(bvhgpu_instances *s, const double *planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits **hits);
 int bvhgpu_hits_fetch_instances_region(bvhgpu_hits *hits, uint32_t *offsets, uint32_t *instance, uint32_t *shape, void *inside, int mem);
 
+/* ---- all hits over an instanced scene: per ray every (instance, shape) its segment crosses, in order, as a CSR — transmittance through
+ * all surfaces, order-independent transparency, inside/outside parity, full-waveform returns, without flattening the scene.
+ * Everything of bvhgpu_instances_trace_* stands unchanged: the committed set, Y_i, the object-space ray {Y o + y3, Y d, 1/(Y d)} (not
+ * renormalised), the double order — the instances in the order of FlatBvh::traverse(ray, W) over the top level, within each instance the
+ * shapes in the order of FlatBvh::traverse(r', member) — and isect = Ray::intersects_triangle(r', triangle s) per member of that list.
+ * Every operation is rounded once in the set's dtype T, in the order written, with no contraction.
+ *  - Candidate.  (i, s) is a candidate of ray j iff isect.distance < tmax[j], strict and in T.  A NULL tmax means +inf.  A miss (+inf) is
+ *    never a candidate; a NaN distance fails the strict comparison, so it is never a candidate; a NaN, zero or negative tmax admits
+ *    nothing.  So no key is ever NaN, and the sorted order below is a total order on (distance, position in the double order): it is
+ *    unique whatever algorithm produces it.
+ *  - Row j, default.  All candidates in a stable ascending sort by distance: equal distances stay in the double order.
+ *  - Row j with BVHGPU_INSTANCES_ALLHITS_LIST_ORDER.  The candidates in the double order, with no sort pass.
+ *  - BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY.  `offsets` only (the hit counts per ray); `total` is still reported.  Nothing else is produced
+ *    and the second walk does not run.
+ *  - Output.  offsets[n_rays + 1] u32 exclusive prefix sums, offsets[n_rays] == total; instance[total] u32; shape[total] u32, the shape
+ *    index within that instance's tree; vals[total x 3] T = {distance, u, v}, the distance in the world ray's parameter.  No padding.
+ *  - Consequences.  A non-empty default row starts with exactly what bvhgpu_instances_trace_* (flags 0) returns for that ray: closest is
+ *    strict < with the earlier candidate keeping a tie, which is the head of a stable sort.  A non-empty LIST_ORDER row starts with what
+ *    BVHGPU_TRAVERSE_FIRST returns.  A row is empty iff bvhgpu_instances_trace_* reports a miss for the ray (it is not occluded).
+ *  - No pruning.  Both walks visit the whole double order.
+ *  - Members, n == 0 instances (every row is empty), one instance, a top level with empty child bounds (coincident world boxes): served
+ *    exactly where bvhgpu_instances_trace_* serves them.  Staleness and commits: that entry's rules.
+ *  - Limits.  n_rays < 2^32 - 1 and total <= 2^32 - 1, else BVHGPU_OVERFLOW; the total is summed in 64 bits and checked before anything is
+ *    sized by it.  After such a refusal the result object holds an empty result of this kind.
+ * The call is synchronous: the result object is complete on return.  `mem` covers `rays` and `tmax`; HOST rays are staged.  *hits may be
+ * NULL or a result object of any kind, whose buffers are then reused.  bvhgpu_hits_info gives n_rays and total; stats.hits == total;
+ * bvhgpu_hits_wait returns BVHGPU_OK; bvhgpu_hits_walk_kernel names the fill kernel, or the count kernel of a COUNT_ONLY batch.  The
+ * result is a kind of its own: every _fetch_* above and _device return BVHGPU_INVALID_ARG on it, and
+ * bvhgpu_hits_fetch_instances_allhits on any other.
+ * Refused, touching no buffer and leaving *hits as it was, the first broken rule in this order: a NULL set or a NULL `hits`; a result
+ * object that still holds an asynchronous batch; a NULL `rays` with n_rays > 0; a `mem` that is neither BVHGPU_HOST nor BVHGPU_DEVICE; a
+ * set of another dtype (BVHGPU_DTYPE_MISMATCH); a flag bit other than the two; an uncommitted set; a stale set (the check and the message
+ * of bvhgpu_instances_trace_*); n_rays >= 2^32 - 1 (BVHGPU_OVERFLOW).  Everything not marked is BVHGPU_INVALID_ARG.
+ * bvhgpu_hits_fetch_instances_allhits: offsets (n_rays + 1 u32), instance and shape (total u32 each) and vals (total x 3 T) copied to
+ * `mem`; each may be NULL.  A COUNT_ONLY batch has offsets only: a non-NULL instance, shape or vals is BVHGPU_INVALID_ARG. */
+#define BVHGPU_INSTANCES_ALLHITS_LIST_ORDER 1u /* rows in the double order (top-level list, then member list) instead of sorted by distance */
+#define BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY 2u /* offsets (the hit counts) only: no instances, shapes or records */
+int bvhgpu_instances_allhits_f32(bvhgpu_instances *s, const bvhgpu_ray_f32 *rays, const float *tmax, size_t n_rays, int mem, unsigned flags,
+                                 bvhgpu_hits **hits);
+int bvhgpu_instances_allhits_f64(bvhgpu_instances *s, const bvhgpu_ray_f64 *rays, const double *tmax, size_t n_rays, int mem, unsigned flags,
+                                 bvhgpu_hits **hits);
+int bvhgpu_hits_fetch_instances_allhits(bvhgpu_hits *hits, uint32_t *offsets, uint32_t *instance, uint32_t *shape, void *vals, int mem);
+
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */
 typedef struct { float build_ms, flatten_ms, traverse_kernel_ms, traverse_total_ms; } bvhgpu_timings;

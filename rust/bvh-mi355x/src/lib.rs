@@ -922,6 +922,49 @@ impl<T: GpuScalar> GpuInstances<T> {
         }
         (offsets, instance, shape, inside)
     }
+
+    /// Per ray EVERY `(instance, shape)` whose triangle it hits with `distance < tmax[j]` (`None`: +inf), as a CSR
+    /// (`bvhgpu_instances_allhits_*`).  `sort`: each row ascending by distance, ties in walk order — its head is `trace(.., false)`'s
+    /// answer; otherwise walk order — its head is `trace(.., true)`'s.  Returns `(offsets, instance, shape, vals)`, `vals` holding
+    /// `{distance, u, v}` per entry; `count_only`: the offsets alone.
+    pub fn allhits(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>, sort: bool, count_only: bool) -> (Vec<u32>, Vec<u32>, Vec<u32>, Vec<T>) {
+        if let Some(m) = tmax {
+            assert_eq!(m.len(), rays.len(), "tmax needs one value per ray");
+        }
+        let raw: Vec<T::RayC> = rays.iter().map(T::ray_to_ffi).collect();
+        let n = raw.len();
+        let flags: c_uint = (if sort { 0 } else { ffi::BVHGPU_INSTANCES_ALLHITS_LIST_ORDER })
+            | (if count_only { ffi::BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY } else { 0 });
+        let mut hits = core::ptr::null_mut();
+        let mut offsets = vec![0u32; n + 1];
+        let (mut instance, mut shape, mut vals) = (Vec::new(), Vec::new(), Vec::new());
+        unsafe {
+            let tp = tmax.map_or(core::ptr::null(), |m| m.as_ptr());
+            let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_allhits_f32(self.set, raw.as_ptr().cast(), tp.cast(), n, ffi::BVHGPU_HOST, flags, &mut hits)
+            } else {
+                ffi::bvhgpu_instances_allhits_f64(self.set, raw.as_ptr().cast(), tp.cast(), n, ffi::BVHGPU_HOST, flags, &mut hits)
+            };
+            check(self.ctx, rc);   // (a refused batch made no result object)
+            let mut total = 0u64;
+            let mut rc = ffi::bvhgpu_hits_info(hits, core::ptr::null_mut(), &mut total, core::ptr::null_mut());
+            if rc == ffi::BVHGPU_OK {
+                let rows = if count_only { 0 } else { total as usize };
+                instance.resize(rows, 0u32);
+                shape.resize(rows, 0u32);
+                vals.resize(3 * rows, T::default());
+                let (ip, sp, vp) = if count_only {
+                    (core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut())
+                } else {
+                    (instance.as_mut_ptr(), shape.as_mut_ptr(), vals.as_mut_ptr() as *mut c_void)
+                };
+                rc = ffi::bvhgpu_hits_fetch_instances_allhits(hits, offsets.as_mut_ptr(), ip, sp, vp, ffi::BVHGPU_HOST);
+            }
+            ffi::bvhgpu_hits_destroy(hits);   // before the check, which panics on a failure
+            check(self.ctx, rc);
+        }
+        (offsets, instance, shape, vals)
+    }
 }
 
 impl<T: GpuScalar> Drop for GpuInstances<T> {

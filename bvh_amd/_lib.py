@@ -33,6 +33,8 @@ REGION_CLASSIFY = 2      # BVHGPU_REGION_CLASSIFY: one byte per reported shape, 
 REGION_INSTANCES_ONLY = 4   # BVHGPU_REGION_INSTANCES_ONLY (bvhgpu_instances_region_*): rows of instances, no shapes
 INSTANCES_ALLHITS_LIST_ORDER = 1   # BVHGPU_INSTANCES_ALLHITS_LIST_ORDER: rows in the double order instead of sorted by distance
 INSTANCES_ALLHITS_COUNT_ONLY = 2   # BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY: offsets and total only
+INSTANCES_WITHIN_LIST_ORDER = 1    # BVHGPU_INSTANCES_WITHIN_LIST_ORDER: rows in the double order instead of sorted by distance
+INSTANCES_WITHIN_COUNT_ONLY = 2    # BVHGPU_INSTANCES_WITHIN_COUNT_ONLY: offsets and total only
 TRAVERSE_T_SLICE = 1
 TRAVERSE_STATS = 2
 TRAVERSE_TRIANGLES = 4
@@ -198,6 +200,9 @@ SYMBOLS = [
     ("bvhgpu_instances_allhits_f32", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
     ("bvhgpu_instances_allhits_f64", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
     ("bvhgpu_hits_fetch_instances_allhits", _i, [_vp, _vp, _vp, _vp, _vp, _i]),
+    ("bvhgpu_instances_within_f32", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_instances_within_f64", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_hits_fetch_instances_within", _i, [_vp, _vp, _vp, _vp, _vp, _i]),
     ("bvhgpu_instances_boxes", _i, [_vp, _vp, _i]),
     ("bvhgpu_instances_info", _i, [_vp, C.POINTER(_i), C.POINTER(_sz), C.POINTER(_sz)]),
     ("bvhgpu_instances_destroy", None, [_vp]),

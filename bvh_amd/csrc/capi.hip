@@ -286,7 +286,7 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
     }
     if ((flags & BVHGPU_TRAVERSE_TRIANGLES) && (flags & BVHGPU_TRAVERSE_CLOSEST))
         return fail(ctx, BVHGPU_INVALID_ARG, "TRIANGLES and CLOSEST are alternatives");
-    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT | TRAVERSE_SPHERE_HIT | TRAVERSE_ALLHITS | TRAVERSE_WITHIN | TRAVERSE_REGION | TRAVERSE_INST_ALLHITS);   // (internal: only bvhgpu_traverse_any_* / _box_* / _sphere_* / _allhits_*, bvhgpu_within_*, bvhgpu_region_* and bvhgpu_instances_allhits_* set them)
+    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT | TRAVERSE_SPHERE_HIT | TRAVERSE_ALLHITS | TRAVERSE_WITHIN | TRAVERSE_REGION | TRAVERSE_INST_ALLHITS | TRAVERSE_INST_WITHIN);   // (internal: only bvhgpu_traverse_any_* / _box_* / _sphere_* / _allhits_*, bvhgpu_within_*, bvhgpu_region_*, bvhgpu_instances_allhits_* and bvhgpu_instances_within_* set them)
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
@@ -1144,6 +1144,38 @@ int do_instances_allhits(bvhgpu_instances* s, const typename Traits<T>::Ray* ray
     });
 }
 
+// do_within's shape over an instance set, behind do_instances_allhits' rules and do_instances_region's refusal of an imported member
+// whose navigator boxes were folded away; the result goes to a result object (instances_within.hip).  HOST points and limits are staged as
+// do_within stages them.  A refused call touches no buffer and leaves *hits as it was.
+template <typename T>
+int do_instances_within(bvhgpu_instances* s, const T* points, const T* max_dist, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
+    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    bvhgpu_ctx* ctx = s->ctx;
+    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
+    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
+    if (n && !points) return fail(ctx, BVHGPU_INVALID_ARG, "points is NULL");
+    if (n && !max_dist) return fail(ctx, BVHGPU_INVALID_ARG, "max_dist is NULL");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from point dtype");
+    if (flags & ~(BVHGPU_INSTANCES_WITHIN_LIST_ORDER | BVHGPU_INSTANCES_WITHIN_COUNT_ONLY))
+        return fail(ctx, BVHGPU_INVALID_ARG, "instance within flags: BVHGPU_INSTANCES_WITHIN_LIST_ORDER and BVHGPU_INSTANCES_WITHIN_COUNT_ONLY only");
+    { const int rc = instances_current(s); if (rc != BVHGPU_OK) return rc; }
+    for (const bvhgpu_tree* t : s->trees)
+        if (t->exact_only && !t->built && !t->unfolded)
+            return fail(ctx, BVHGPU_INVALID_ARG, "an imported member tree whose build had a split without SAH winner: its leaves' navigator boxes were folded away");
+    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 points in one batch");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        bvhgpu_hits* h = batch_hits(hits);
+        const auto* dev = static_cast<const T*>(to_device(ctx, points, n * 3 * sizeof(T), mem, ctx->upload));
+        stage_tmax<T>(ctx, h, max_dist, n, mem);   // (HOST limits are staged as do_within stages them)
+        const T* md = n ? static_cast<const T*>(h->pend_tmax) : nullptr;
+        h->pend_tmax = nullptr;                    // (nothing replays this batch)
+        instances_within_batch<T>(s, dev, md, n, flags, h);
+        return (int)BVHGPU_OK;
+    });
+}
+
 }  // namespace
 
 namespace bvhgpu {
@@ -1717,6 +1749,7 @@ int bvhgpu_hits_fetch_triangles(bvhgpu_hits* h, void* isect, int mem) {
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
+    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
     if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "a sphere-hit batch has no triangle values: use bvhgpu_hits_fetch_sphere");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
@@ -1734,6 +1767,7 @@ static int fetch_per_ray(bvhgpu_hits* h, void* values, uint32_t* shape, int mem,
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
+    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
     if ((h->flags & TRAVERSE_SPHERE_HIT) && kind_bit != TRAVERSE_SPHERE_HIT)
         return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
@@ -1788,6 +1822,7 @@ int bvhgpu_hits_fetch(bvhgpu_hits* h, uint32_t* offsets, uint32_t* indices, void
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
+    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "an all-hits batch has a CSR of its own: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
@@ -1811,6 +1846,7 @@ int bvhgpu_hits_fetch_allhits(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
+    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
     if (!(h->flags & TRAVERSE_ALLHITS)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_traverse_allhits_* batch");
@@ -1832,6 +1868,7 @@ int bvhgpu_hits_fetch_within(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape,
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
+    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
     if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
     if (!(h->flags & TRAVERSE_WITHIN)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_within_* batch");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
@@ -1852,6 +1889,7 @@ int bvhgpu_hits_fetch_region(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape,
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
+    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
@@ -1881,6 +1919,7 @@ int bvhgpu_hits_fetch_instances_region(bvhgpu_hits* h, uint32_t* offsets, uint32
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
+    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
     if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
@@ -1910,6 +1949,7 @@ int bvhgpu_hits_fetch_instances_allhits(bvhgpu_hits* h, uint32_t* offsets, uint3
     if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = h->ctx;
     if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
     if (!(h->flags & TRAVERSE_INST_ALLHITS)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_instances_allhits_* batch");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
     if ((instance || shape || vals) && h->wi_count_only)
@@ -1920,6 +1960,26 @@ int bvhgpu_hits_fetch_instances_allhits(bvhgpu_hits* h, uint32_t* offsets, uint3
         if (instance && h->total) copy_out(ctx, instance, h->rg_instance.p, h->total * 4, mem);
         if (shape && h->total) copy_out(ctx, shape, h->indices.p, h->total * 4, mem);
         if (vals && h->total) copy_out(ctx, vals, h->ah_vals.p, h->total * 3 * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
+        return (int)BVHGPU_OK;
+    });
+}
+
+// the CSR of a within batch over an instance set: offsets (n + 1 u32), the instances and the shapes (total u32 each), the distances
+// (total T); each may be NULL.  A COUNT_ONLY batch has offsets only.  Every other kind of result is refused.
+int bvhgpu_hits_fetch_instances_within(bvhgpu_hits* h, uint32_t* offsets, uint32_t* instance, uint32_t* shape, void* dist, int mem) {
+    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    bvhgpu_ctx* ctx = h->ctx;
+    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (!(h->flags & TRAVERSE_INST_WITHIN)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_instances_within_* batch");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if ((instance || shape || dist) && h->wi_count_only)
+        return fail(ctx, BVHGPU_INVALID_ARG, "the batch was run with BVHGPU_INSTANCES_WITHIN_COUNT_ONLY: it has offsets only");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
+        if (instance && h->total) copy_out(ctx, instance, h->rg_instance.p, h->total * 4, mem);
+        if (shape && h->total) copy_out(ctx, shape, h->indices.p, h->total * 4, mem);
+        if (dist && h->total) copy_out(ctx, dist, h->ah_vals.p, h->total * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
         return (int)BVHGPU_OK;
     });
 }
@@ -1937,6 +1997,7 @@ int bvhgpu_hits_device(const bvhgpu_hits* h, const uint32_t** offsets, const uin
     if (!h) return BVHGPU_INVALID_ARG;
     if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
     if (h->flags & TRAVERSE_INST_ALLHITS) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
+    if (h->flags & TRAVERSE_INST_WITHIN) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
     if (h->flags & TRAVERSE_ALLHITS) return fail(h->ctx, BVHGPU_INVALID_ARG, "an all-hits batch has a CSR of its own: use bvhgpu_hits_fetch_allhits");
     if (h->flags & TRAVERSE_WITHIN) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
     if (h->flags & TRAVERSE_REGION) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
@@ -1988,6 +2049,12 @@ int bvhgpu_instances_allhits_f32(bvhgpu_instances* s, const bvhgpu_ray_f32* rays
 int bvhgpu_instances_allhits_f64(bvhgpu_instances* s, const bvhgpu_ray_f64* rays, const double* tmax, size_t n_rays, int mem, unsigned flags,
                                  bvhgpu_hits** hits) {
     return do_instances_allhits<double>(s, rays, tmax, n_rays, mem, flags, hits);
+}
+int bvhgpu_instances_within_f32(bvhgpu_instances* s, const float* points, const float* max_dist, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_instances_within<float>(s, points, max_dist, n, mem, flags, hits);
+}
+int bvhgpu_instances_within_f64(bvhgpu_instances* s, const double* points, const double* max_dist, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_instances_within<double>(s, points, max_dist, n, mem, flags, hits);
 }
 int bvhgpu_instances_boxes(bvhgpu_instances* s, void* out, int mem) {
     if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");

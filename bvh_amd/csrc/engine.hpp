@@ -62,6 +62,9 @@ constexpr int REGION_INST_ONLY = 2;     // ... with BVHGPU_REGION_INSTANCES_ONLY
 // result objects of bvhgpu_instances_allhits_* (instances_allhits.hip): marked like TRAVERSE_ALLHITS; the only bit such a result carries
 // (BVHGPU_INSTANCES_ALLHITS_* are never stored in bvhgpu_hits::flags)
 constexpr unsigned TRAVERSE_INST_ALLHITS = 1u << 25;
+// result objects of bvhgpu_instances_within_* (instances_within.hip): marked like TRAVERSE_WITHIN; the only bit such a result carries
+// (BVHGPU_INSTANCES_WITHIN_* are never stored in bvhgpu_hits::flags)
+constexpr unsigned TRAVERSE_INST_WITHIN = 1u << 24;
 
 }  // namespace bvhgpu
 
@@ -321,6 +324,9 @@ struct bvhgpu_hits {
     // all-hits batches over an instance set (bvhgpu_instances_allhits_*, instances_allhits.hip): the CSR is `offsets` / `rg_instance` / `indices`
     // (the shapes) / `ah_vals` (total x 3 T); the scan runs in ah_counts / ah_sums / ah_work / ah_pos, a COUNT_ONLY batch sets wi_count_only
     bvhgpu::DevBuf ia_list_shape;        // total u32: the shapes of the long rows of a sorted batch in the double order (the sort gathers from it)
+    // within batches over an instance set (bvhgpu_instances_within_*, instances_within.hip): the CSR is `offsets` / `rg_instance` / `indices` (the
+    // shapes) / `ah_vals` (total T distances); the scan runs in ah_counts / ah_sums / ah_work / ah_pos, the long rows' shapes wait in ia_list_shape,
+    // a COUNT_ONLY batch sets wi_count_only; the per-batch array table lives in rg_members (instances_within.hip InstWithinArr<T>), the mirrors in wi_unfold
     uint32_t replays = 0;               // times bvhgpu_hits_wait had to enqueue the asynchronous batch again
     int deferred_rc = 0;                // status of a completion that ran on behalf of another call (rebuild / destroy of the tree)
     std::string deferred_err;
@@ -447,6 +453,12 @@ void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, 
 // empty result of this kind).
 template <typename T>
 void instances_allhits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, unsigned flags, bvhgpu_hits* h);
+// instances_within.hip: every (instance, shape) within max_dist_dev[i] of point i over a committed instance set as a CSR
+// (bvhgpu_instances_within_*); flags: BVHGPU_INSTANCES_WITHIN_*.  Synchronous: h->offsets / h->rg_instance / h->indices / h->ah_vals and h->total
+// are complete on return.  Throws Fail::Overflow when the batch has more than 2^32-1 candidates (the result object then holds an empty
+// result of this kind).
+template <typename T>
+void instances_within_batch(bvhgpu_instances* s, const T* points_dev, const T* max_dist_dev, size_t n, unsigned flags, bvhgpu_hits* h);
 // rays.hip
 template <typename T>
 void ray_triangle_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays_dev, const T* tris_dev, size_t n, T* out_dev);

@@ -197,6 +197,51 @@ class Instances(_Typed):
             return dict(offsets=offsets)
         return dict(offsets=offsets, instance=instance, shape=shape, vals=vals)
 
+    def within_batch(self, points, max_dist, sort: bool = True, count_only: bool = False) -> dict:
+        """bvhgpu_instances_within_*: per point EVERY (instance, shape) whose world-space triangle lies within max_dist[i] of it (<=, the
+        limit itself is inside; a negative or NaN limit gives an empty row, +inf keeps every pair whose distance is not NaN), as a CSR.
+        The distance is the true world distance to the transformed triangle, whatever the transform.  sort=True: each row ascending by
+        distance, ties in walk order (instances in the top level's order, shapes in the member's order); sort=False: walk order, no sort
+        pass.  count_only: offsets alone.
+        points: (n, 3) in the set's dtype — a numpy array (HOST) or a torch GPU tensor (DEVICE).  max_dist: a scalar (the same limit for
+        every point) or n values in the points' memory.
+        returns {offsets[n+1], instance[total], shape[total], dist[total]} (offsets only with count_only).  numpy in: numpy out, offsets
+        and indices as uint32.  Points in HBM: torch tensors on the same device, indices as torch.int32, offsets as torch.int64."""
+        if max_dist is None:
+            raise BvhGpuError(_lib.INVALID_ARG, "within_batch needs max_dist (a scalar or one value per point)")
+        keep, pp, n, mem = api._rows_in(points, 3, self.ft, "point")
+        _m, mp = api._side_in(max_dist, keep, n, mem, self.ft, "max_dist", "points", scalar_ok=True)
+        flags = (0 if sort else _lib.INSTANCES_WITHIN_LIST_ORDER) | (_lib.INSTANCES_WITHIN_COUNT_ONLY if count_only else 0)
+        dev = keep.device if mem == DEVICE else None
+        if dev is not None:
+            api._torch_sync(dev)
+        lib = _lib.load()
+        if getattr(self, "_hits", None) is None:
+            self._hits = api._Hits(self.ctx)     # (the set's own result object: its buffers are reused by every batch)
+        hits = self._hits
+        check(getattr(lib, f"bvhgpu_instances_within_{self.sfx}")(self._s, pp, mp, n, mem, flags, C.byref(hits.h)), self.ctx._h)
+        rows = 0 if count_only else hits._total()
+        if dev is not None:
+            import torch
+            off32 = torch.empty(n + 1, dtype=torch.int32, device=dev)
+            instance = torch.empty(rows, dtype=torch.int32, device=dev)
+            shape = torch.empty(rows, dtype=torch.int32, device=dev)
+            dist = torch.empty(rows, dtype=api._torch_ft(self.ft), device=dev)
+            api._torch_sync(dev)
+            check(lib.bvhgpu_hits_fetch_instances_within(hits.h, ptr(off32.data_ptr()), ptr(instance.data_ptr()) if rows else None,
+                                                         ptr(shape.data_ptr()) if rows else None, ptr(dist.data_ptr()) if rows else None,
+                                                         DEVICE), self.ctx._h)
+            offsets = off32.to(torch.int64) & 0xFFFFFFFF
+        else:
+            offsets = np.zeros(n + 1, dtype=np.uint32)
+            instance, shape = np.zeros(rows, dtype=np.uint32), np.zeros(rows, dtype=np.uint32)
+            dist = np.zeros(rows, dtype=self.ft)
+            check(lib.bvhgpu_hits_fetch_instances_within(hits.h, ptr(offsets), ptr(instance) if rows else None, ptr(shape) if rows else None,
+                                                         ptr(dist) if rows else None, _lib.HOST), self.ctx._h)
+        if count_only:
+            return dict(offsets=offsets)
+        return dict(offsets=offsets, instance=instance, shape=shape, dist=dist)
+
     @property
     def world_boxes(self) -> np.ndarray:
         """W_i of the committed pose, (n, 6) [min xyz, max xyz]"""

@@ -908,6 +908,69 @@ int bvhgpu_instances_allhits_f64(bvhgpu_instances *s, const bvhgpu_ray_f64 *rays
                                  bvhgpu_hits **hits);
 int bvhgpu_hits_fetch_instances_allhits(bvhgpu_hits *hits, uint32_t *offsets, uint32_t *instance, uint32_t *shape, void *vals, int mem);
 
+/* ---- radius search over an instanced scene: per query point every (instance, shape) whose WORLD-space triangle lies within max_dist of
+ * it, in order, as a CSR — contact candidates, proximity and clearance checks, density estimation, snapping, without flattening the scene.
+ * The set is the committed one of bvhgpu_instances_trace_*: X_i as uploaded, Y_i, the world boxes W_i and the top-level tree over W.
+ * All arithmetic is in the set's dtype T; every operation is rounded once, in the order written, with no contraction.
+ * Point p_j comes with m = max_dist[j]; r2 = m * m.  A negative or NaN m gives an empty row without a walk; -0.0 is the limit 0.
+ *   top level: <FlatBvh as BoundingHierarchy>::nearest_to's loop with a fixed limit (bvhgpu_within_* above) over the top level's FlatNode
+ *   array, with the world point:
+ *     non-leaf entry: md = aabb.min_distance_squared(p);  entry_index iff md <= r2, else exit_index
+ *     leaf entry (instance i): walk instance i, then exit_index
+ *   instance i (member t = tree_of[i]):
+ *     q[k] = ((Y_i[k][0]*p[0] + Y_i[k][1]*p[1]) + Y_i[k][2]*p[2]) + Y_i[k][3]                     the point in the object's frame
+ *     f[k] = (Y_i[k][0]*Y_i[k][0] + Y_i[k][1]*Y_i[k][1]) + Y_i[k][2]*Y_i[k][2];  F = (f[0] + f[1]) + f[2]    ||Y_i's 3x3 part||_F squared
+ *     r2o  = r2 * F                                                                                  the limit in the object's frame
+ *     the same loop over member t's FlatNode array with q and r2o:
+ *       non-leaf entry: md = aabb.min_distance_squared(q);  entry_index iff md <= r2o, else exit_index
+ *       leaf entry (shape s): w[v][k] = ((X_i[k][0]*tri_s[v][0] + X_i[k][1]*tri_s[v][1]) + X_i[k][2]*tri_s[v][2]) + X_i[k][3], v = a, b, c:
+ *                             the triangle in WORLD space;  d = <Triangle as PointDistance>::distance_squared(w, p);
+ *                             (i, s) is a candidate with key d iff d <= r2;  then exit_index
+ *  - The distance is the true world-space distance to the transformed triangle, meaningful under any affine X_i (distances do not
+ *    survive a non-uniform scale, so nothing is measured in the object's frame).  There is no box kind: a box under an affine map is not
+ *    a box, and a set needs bvhgpu_tree_set_triangles on every member anyway.
+ *  - The prune is conservative.  |p - (X v + x3)| = |X (q - v)| >= |q - v| / ||Y||_F, so every point of a world triangle within m of p
+ *    lies within m * ||Y||_F of q in the object's frame, and so does every box that contains it; W_i contains the world triangles.  In
+ *    exact arithmetic row j is therefore exactly {(i, s) : d(i, s) <= r2}.  In floating point the row is what the loop above yields: a
+ *    pair whose d lies within rounding of r2 may be decided by a box test, as for bvhgpu_within_*.  The threshold never moves, so the
+ *    candidate set does not depend on the order of the walk.
+ *  - Row j, default.  All candidates in a stable ascending sort by d; equal d stay in the order the loop met them: the double order, the
+ *    instances in the top level's list order, within each the shapes in the member's.  No key is NaN (a NaN d fails <=), so the order
+ *    is total and unique.
+ *  - Row j with BVHGPU_INSTANCES_WITHIN_LIST_ORDER.  The candidates in the double order, with no sort pass.
+ *  - BVHGPU_INSTANCES_WITHIN_COUNT_ONLY.  `offsets` only; `total` is still reported.  The second walk does not run.
+ *  - Output.  offsets[n + 1] u32 exclusive prefix sums, offsets[n] == total; instance[total] u32; shape[total] u32, the shape index
+ *    within that instance's tree; dist[total] T = sqrt(d).  No padding.
+ *  - Edge cases.  m = +inf keeps every pair whose distance is not NaN.  A NaN r2o (0 * inf) passes no box test of that instance.  NaN
+ *    and infinite points behave as bvhgpu_within_* describes for the box and the triangle distance.  Every walk terminates whatever
+ *    the values: the index only moves forward.
+ *  - Consequences.  An instance whose X is exactly the identity has Y = I and y3 = -0, so q = p and w = tri bit for bit, and F = 3: its
+ *    entries of a LIST_ORDER row hold the distances of bvhgpu_within_* (kind 1, LIST_ORDER) on the member itself, bit-equal, and its
+ *    shapes — identical wherever the single-tree prune (md <= r2) and this one (md <= 3 * r2) keep the same leaves.  A row is empty
+ *    iff no pair passes.
+ *  - Which arrays are walked: bvhgpu_instances_region_*'s rule, member by member, and the same rule for the top level (its build over
+ *    the world boxes can meet a split without SAH winner too: its empty child boxes are at distance 0 of every point, as in the
+ *    FlatNode array).  An imported member tree whose build had such a split is refused as there.
+ *  - Limits.  n < 2^32 - 1 and total <= 2^32 - 1, else BVHGPU_OVERFLOW; the total is summed in 64 bits and checked before anything is
+ *    sized by it.  After such a refusal the result object holds an empty result of this kind.
+ * The call is synchronous: the result object is complete on return.  `mem` covers `points` and `max_dist`; HOST input is staged.  *hits
+ * may be NULL or a result object of any kind, whose buffers are then reused.  bvhgpu_hits_info gives n and total; stats.hits == total;
+ * bvhgpu_hits_wait returns BVHGPU_OK; bvhgpu_hits_walk_kernel names the fill kernel, or the count kernel of a COUNT_ONLY batch.  The
+ * result is a kind of its own: every _fetch_* above and _device return BVHGPU_INVALID_ARG on it, and
+ * bvhgpu_hits_fetch_instances_within on any other.
+ * Refused, touching no buffer and leaving *hits as it was, the first broken rule in this order: a NULL set or a NULL `hits`; a result
+ * object that still holds an asynchronous batch; a NULL `points` with n > 0; a NULL `max_dist` with n > 0; a `mem` that is neither
+ * BVHGPU_HOST nor BVHGPU_DEVICE; a set of another dtype (BVHGPU_DTYPE_MISMATCH); a flag bit other than the two; an uncommitted set; a
+ * stale set (the check and the message of bvhgpu_instances_trace_*); the imported member above; n >= 2^32 - 1 (BVHGPU_OVERFLOW).
+ * Everything not marked is BVHGPU_INVALID_ARG.
+ * bvhgpu_hits_fetch_instances_within: offsets (n + 1 u32), instance and shape (total u32 each) and dist (total T) copied to `mem`; each
+ * may be NULL.  A COUNT_ONLY batch has offsets only: a non-NULL instance, shape or dist is BVHGPU_INVALID_ARG. */
+#define BVHGPU_INSTANCES_WITHIN_LIST_ORDER 1u /* rows in the double order (top-level list, then member list) instead of sorted by distance */
+#define BVHGPU_INSTANCES_WITHIN_COUNT_ONLY 2u /* offsets (the counts) only: no instances, shapes or distances */
+int bvhgpu_instances_within_f32(bvhgpu_instances *s, const float *points, const float *max_dist, size_t n, int mem, unsigned flags, bvhgpu_hits **hits);
+int bvhgpu_instances_within_f64(bvhgpu_instances *s, const double *points, const double *max_dist, size_t n, int mem, unsigned flags, bvhgpu_hits **hits);
+int bvhgpu_hits_fetch_instances_within(bvhgpu_hits *hits, uint32_t *offsets, uint32_t *instance, uint32_t *shape, void *dist, int mem);
+
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */
 typedef struct { float build_ms, flatten_ms, traverse_kernel_ms, traverse_total_ms; } bvhgpu_timings;

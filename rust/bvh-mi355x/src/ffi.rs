@@ -16,6 +16,8 @@ pub const BVHGPU_REGION_CLASSIFY: c_uint = 2; // bvhgpu_region_*: one byte per r
 pub const BVHGPU_REGION_INSTANCES_ONLY: c_uint = 4; // bvhgpu_instances_region_*: rows of instances, no shapes
 pub const BVHGPU_INSTANCES_ALLHITS_LIST_ORDER: c_uint = 1; // bvhgpu_instances_allhits_*: rows in the double order, no sort pass
 pub const BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY: c_uint = 2; // bvhgpu_instances_allhits_*: offsets (the hit counts) only
+pub const BVHGPU_INSTANCES_WITHIN_LIST_ORDER: c_uint = 1; // bvhgpu_instances_within_*: rows in the double order, no sort pass
+pub const BVHGPU_INSTANCES_WITHIN_COUNT_ONLY: c_uint = 2; // bvhgpu_instances_within_*: offsets (the counts) only
 pub const BVHGPU_LEAF_BOX: c_int = 0; // leaf stage of bvhgpu_traverse_khits_*: {enter, exit} on the shape's own AABB
 pub const BVHGPU_LEAF_TRIANGLE: c_int = 1; // ... Intersection{distance, u, v} (needs the triangles)
 pub const BVHGPU_LEAF_SPHERE: c_int = 2; // ... {distance, exit} (needs the spheres)
@@ -235,6 +237,10 @@ extern "C" {
     pub fn bvhgpu_instances_allhits_f32(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_instances_allhits_f64(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_hits_fetch_instances_allhits(h: *mut bvhgpu_hits, offsets: *mut u32, instance: *mut u32, shape: *mut u32, vals: *mut c_void, mem: c_int) -> c_int;
+    // every (instance, shape) whose world-space triangle lies within max_dist[i] of point i as a CSR (offsets: n + 1, instance / shape / dist: total; rows in ascending distance, or in the double order with BVHGPU_INSTANCES_WITHIN_LIST_ORDER; BVHGPU_INSTANCES_WITHIN_COUNT_ONLY: offsets alone)
+    pub fn bvhgpu_instances_within_f32(s: *mut bvhgpu_instances, points: *const f32, max_dist: *const f32, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_instances_within_f64(s: *mut bvhgpu_instances, points: *const f64, max_dist: *const f64, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_hits_fetch_instances_within(h: *mut bvhgpu_hits, offsets: *mut u32, instance: *mut u32, shape: *mut u32, dist: *mut c_void, mem: c_int) -> c_int;
     pub fn bvhgpu_instances_boxes(s: *mut bvhgpu_instances, out: *mut c_void, mem: c_int) -> c_int;
     pub fn bvhgpu_instances_info(s: *const bvhgpu_instances, dtype: *mut c_int, n_trees: *mut usize, n_instances: *mut usize) -> c_int;
     pub fn bvhgpu_instances_destroy(s: *mut bvhgpu_instances);

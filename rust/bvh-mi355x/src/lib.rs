@@ -965,6 +965,45 @@ impl<T: GpuScalar> GpuInstances<T> {
         }
         (offsets, instance, shape, vals)
     }
+
+    /// Per point EVERY `(instance, shape)` whose world-space triangle lies within `max_dist[j]` of it (`<=`; a negative or NaN limit gives
+    /// an empty row), as a CSR (`bvhgpu_instances_within_*`).  The distance is the true world distance to the transformed triangle,
+    /// whatever the transform.  `sort`: each row ascending by distance, ties in walk order; otherwise walk order.  Returns
+    /// `(offsets, instance, shape, dist)`, distances not squared; `count_only`: the offsets alone.
+    pub fn within_distance(&self, points: &[[T; 3]], max_dist: &[T], sort: bool, count_only: bool) -> (Vec<u32>, Vec<u32>, Vec<u32>, Vec<T>) {
+        assert_eq!(max_dist.len(), points.len(), "one max_dist per point");
+        let n = points.len();
+        let flags: c_uint = (if sort { 0 } else { ffi::BVHGPU_INSTANCES_WITHIN_LIST_ORDER })
+            | (if count_only { ffi::BVHGPU_INSTANCES_WITHIN_COUNT_ONLY } else { 0 });
+        let mut hits = core::ptr::null_mut();
+        let mut offsets = vec![0u32; n + 1];
+        let (mut instance, mut shape, mut dist) = (Vec::new(), Vec::new(), Vec::new());
+        unsafe {
+            let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_within_f32(self.set, points.as_ptr().cast(), max_dist.as_ptr().cast(), n, ffi::BVHGPU_HOST, flags, &mut hits)
+            } else {
+                ffi::bvhgpu_instances_within_f64(self.set, points.as_ptr().cast(), max_dist.as_ptr().cast(), n, ffi::BVHGPU_HOST, flags, &mut hits)
+            };
+            check(self.ctx, rc);   // (a refused batch made no result object)
+            let mut total = 0u64;
+            let mut rc = ffi::bvhgpu_hits_info(hits, core::ptr::null_mut(), &mut total, core::ptr::null_mut());
+            if rc == ffi::BVHGPU_OK {
+                let rows = if count_only { 0 } else { total as usize };
+                instance.resize(rows, 0u32);
+                shape.resize(rows, 0u32);
+                dist.resize(rows, T::default());
+                let (ip, sp, dp) = if count_only {
+                    (core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut())
+                } else {
+                    (instance.as_mut_ptr(), shape.as_mut_ptr(), dist.as_mut_ptr() as *mut c_void)
+                };
+                rc = ffi::bvhgpu_hits_fetch_instances_within(hits, offsets.as_mut_ptr(), ip, sp, dp, ffi::BVHGPU_HOST);
+            }
+            ffi::bvhgpu_hits_destroy(hits);   // before the check, which panics on a failure
+            check(self.ctx, rc);
+        }
+        (offsets, instance, shape, dist)
+    }
 }
 
 impl<T: GpuScalar> Drop for GpuInstances<T> {

@@ -1176,6 +1176,42 @@ int do_instances_within(bvhgpu_instances* s, const T* points, const T* max_dist,
     });
 }
 
+// do_points' rules and staging over an instance set, behind do_instances_within's: one layout (points | dist | instance | shape), no result
+// object, synchronous.  A refused call touches no buffer and leaves the set as it was.
+template <typename T>
+int do_instances_knearest(bvhgpu_instances* s, const T* points, size_t n, int mem, uint32_t k, uint32_t* out_instance, uint32_t* out_shape, T* out_dist) {
+    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    bvhgpu_ctx* ctx = s->ctx;
+    if (k == 0 || k > BVHGPU_INSTANCES_KNN_MAX_K) return fail(ctx, BVHGPU_INVALID_ARG, "k must be between 1 and BVHGPU_INSTANCES_KNN_MAX_K");
+    if (n && (!points || !out_instance || !out_shape || !out_dist)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from point dtype");
+    { const int rc = instances_current(s); if (rc != BVHGPU_OK) return rc; }   // (a member that lost its triangles is stale)
+    for (const bvhgpu_tree* t : s->trees)
+        if (t->exact_only && !t->built && !t->unfolded)
+            return fail(ctx, BVHGPU_INVALID_ARG, "an imported member tree whose build had a split without SAH winner: its leaves' navigator boxes were folded away");
+    if (n >= 0xFFFFFFFFull || n * (size_t)k >= 0x100000000ull) return fail(ctx, BVHGPU_OVERFLOW, "too many results (points x k) in one call");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        const T* pd = points; T* dd = out_dist; uint32_t *id = out_instance, *sd = out_shape;
+        const size_t pb = n * 3 * sizeof(T), db = n * k * sizeof(T), ib = n * k * 4;
+        if (mem == BVHGPU_HOST) {
+            ctx->upload.reserve(pb + db + 2 * ib + 64);
+            char* base = ctx->upload.as<char>();
+            if (pb) BVH_HIP(hipMemcpyAsync(base, points, pb, hipMemcpyHostToDevice, ctx->stream));
+            pd = reinterpret_cast<const T*>(base); dd = reinterpret_cast<T*>(base + pb);
+            id = reinterpret_cast<uint32_t*>(base + pb + db); sd = reinterpret_cast<uint32_t*>(base + pb + db + ib);
+        }
+        instances_knearest_batch<T>(s, pd, n, k, id, sd, dd);
+        if (mem == BVHGPU_HOST) {
+            copy_out(ctx, out_dist, dd, db, BVHGPU_HOST); copy_out(ctx, out_instance, id, ib, BVHGPU_HOST); copy_out(ctx, out_shape, sd, ib, BVHGPU_HOST);
+        } else {
+            BVH_HIP(hipStreamSynchronize(ctx->stream));   // the rows are complete when the call returns, whichever stream reads them next
+        }
+        return (int)BVHGPU_OK;
+    });
+}
+
 }  // namespace
 
 namespace bvhgpu {
@@ -2055,6 +2091,14 @@ int bvhgpu_instances_within_f32(bvhgpu_instances* s, const float* points, const 
 }
 int bvhgpu_instances_within_f64(bvhgpu_instances* s, const double* points, const double* max_dist, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
     return do_instances_within<double>(s, points, max_dist, n, mem, flags, hits);
+}
+int bvhgpu_instances_knearest_f32(bvhgpu_instances* s, const float* points, size_t n, int mem, uint32_t k, uint32_t* out_instance, uint32_t* out_shape,
+                                  float* out_dist) {
+    return do_instances_knearest<float>(s, points, n, mem, k, out_instance, out_shape, out_dist);
+}
+int bvhgpu_instances_knearest_f64(bvhgpu_instances* s, const double* points, size_t n, int mem, uint32_t k, uint32_t* out_instance, uint32_t* out_shape,
+                                  double* out_dist) {
+    return do_instances_knearest<double>(s, points, n, mem, k, out_instance, out_shape, out_dist);
 }
 int bvhgpu_instances_boxes(bvhgpu_instances* s, void* out, int mem) {
     if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");

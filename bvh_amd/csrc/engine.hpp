@@ -354,6 +354,11 @@ struct bvhgpu_instances {
     bvhgpu::DevBuf bounds;      // n_trees x 6 T: B_t
     bvhgpu::DevBuf recs;        // n x InstRec<T>: Y_i and the tree slot
     bvhgpu::DevBuf wboxes;      // n x 6 T: W_i
+    // bvhgpu_instances_knearest_* (instances_knn.hip): the array table of the set (instances_arrays.hpp InstWithinArr<T>, n_trees + 1 rows) and
+    // the unfolded mirrors it points to; made again by every call, the allocations kept between calls and freed with the set
+    bvhgpu::DevBuf kn_arrs;
+    bvhgpu::DevBuf kn_unfold;
+    std::vector<unsigned char> kn_arrs_host;   // host image of `kn_arrs` (alive while its upload is in flight)
     bvhgpu_hits* rg_top = nullptr;   // bvhgpu_instances_region_*: the result object of stage 1 (the regions over `top`), made on first use
     ~bvhgpu_instances() { delete rg_top; }   // (never holds an asynchronous batch; the caller has synchronised the stream)
 };
@@ -459,6 +464,11 @@ void instances_allhits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray*
 // result of this kind).
 template <typename T>
 void instances_within_batch(bvhgpu_instances* s, const T* points_dev, const T* max_dist_dev, size_t n, unsigned flags, bvhgpu_hits* h);
+// instances_knn.hip: the k nearest (instance, shape) pairs per point over a committed instance set (bvhgpu_instances_knearest_*); out_*: n x k,
+// a set without instances fills them with padding.  Enqueued on the ctx's stream; the array table and its mirrors live in the set.
+template <typename T>
+void instances_knearest_batch(bvhgpu_instances* s, const T* points_dev, size_t n, uint32_t k, uint32_t* out_instance_dev, uint32_t* out_shape_dev,
+                              T* out_dist_dev);
 // rays.hip
 template <typename T>
 void ray_triangle_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays_dev, const T* tris_dev, size_t n, T* out_dev);

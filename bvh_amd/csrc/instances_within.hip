@@ -30,7 +30,7 @@
 //                                its position; then sqrt.
 // The row length is uniform per workgroup of k_instances_within_sort_row: every loop bound and every barrier there depends on it alone.
 //
-// Which arrays are walked: region.hip's rule (RegionMember), array by array, in a table made by every batch (InstWithinArr; the last
+// Which arrays are walked: region.hip's rule (RegionMember), array by array, in a table made by every batch (instances_arrays.hpp InstWithinArr; the last
 // row is the top level's).  The folded `trav` array for a built tree (a leaf entry carries the shape's — the instance's — own box and
 // tests it), the UNFOLDED rule for an uploaded FlatBvh and a one-shape tree (a leaf entry is entered untested), and an unfolded mirror of
 // the FlatNode array (unfold.hpp) for a built tree with empty child bounds — the top level included, whose build over the world boxes
@@ -38,10 +38,9 @@
 #include <cstdio>
 #include <vector>
 
-#include "instances.hpp"
+#include "instances_arrays.hpp"
 #include "point_dist.hpp"
 #include "rows.hpp"
-#include "unfold.hpp"
 
 namespace bvhgpu {
 
@@ -50,13 +49,6 @@ namespace bvhgpu {
 constexpr uint32_t INST_WITHIN_LANE_ROW_MAX = 32;
 constexpr uint32_t INST_WITHIN_LDS_ROW_MAX = 2048;
 static_assert(rows_lds_row_max_ok(INST_WITHIN_LDS_ROW_MAX), "a row sorted in LDS must fit a workgroup's LDS, padded to a power of two");
-
-// one array of the batch: a member's, or (the table's last row) the top level's
-template <typename T> struct InstWithinArr {
-    const TravNode<T>* nodes;   // the folded array, the uploaded array, or the unfolded mirror in the result object
-    const T* tris;              // n x 9 (members)
-    uint32_t n_trav, unfolded;
-};
 
 // what the walks read of the set
 template <typename T> struct InstWithinScene {
@@ -296,37 +288,10 @@ void instances_within_batch(bvhgpu_instances* s, const T* points_dev, const T* m
     if (n == 0 || s->n == 0) {   // no points, or no instances: every row is empty
         BVH_HIP(hipMemsetAsync(h->offsets.p, 0, (n + 1) * 4, st));
     } else {
-        // ---- the table of the batch: which array of every member and of the top level, and where its mirror starts
+        // ---- the table of the batch: which array of every member and of the top level (instances_arrays.hpp), in the result object
         const size_t nt = s->trees.size();
-        std::vector<InstWithinArr<T>> tbl(nt + 1);
-        std::vector<size_t> mirror_at(nt + 1, (size_t)-1);
-        size_t n_mirror = 0;
-        for (size_t k = 0; k <= nt; k++) {
-            bvhgpu_tree* t = k < nt ? s->trees[k] : s->top;
-            InstWithinArr<T>& r = tbl[k];
-            r = InstWithinArr<T>{nullptr, nullptr, 0u, 0u};
-            if (t->n == 0) continue;   // (no instance of it has a finite world box: never looked up)
-            ensure_flat_arrays(t);
-            const bool mirror = t->exact_only && t->built && !t->unfolded && t->n >= 2;   // within_batch's rule, array by array
-            r.unfolded = (t->unfolded || t->n == 1 || mirror) ? 1u : 0u;
-            r.n_trav = (uint32_t)(mirror ? t->n_flat : t->n_trav);
-            r.nodes = t->trav.as<TravNode<T>>();
-            r.tris = t->tris.as<T>();
-            if (mirror) { mirror_at[k] = n_mirror; n_mirror += r.n_trav; }
-        }
-        if (n_mirror) h->wi_unfold.reserve(n_mirror * sizeof(TravNode<T>));
-        for (size_t k = 0; k <= nt; k++) {
-            if (mirror_at[k] == (size_t)-1) continue;
-            bvhgpu_tree* t = k < nt ? s->trees[k] : s->top;
-            TravNode<T>* dst = h->wi_unfold.as<TravNode<T>>() + mirror_at[k];
-            hipLaunchKernelGGL((k_within_unfold<T>), dim3((tbl[k].n_trav + 255) / 256), dim3(256), 0, st, t->flat.as<typename Traits<T>::Flat>(), tbl[k].n_trav, dst);
-            tbl[k].nodes = dst;
-        }
-        BVH_HIP(hipGetLastError());
-        h->rg_members.reserve((nt + 1) * sizeof(InstWithinArr<T>));
-        h->rg_members_host.assign(reinterpret_cast<const unsigned char*>(tbl.data()), reinterpret_cast<const unsigned char*>(tbl.data() + nt + 1));
-        BVH_HIP(hipMemcpyAsync(h->rg_members.p, h->rg_members_host.data(), (nt + 1) * sizeof(InstWithinArr<T>), hipMemcpyHostToDevice, st));
-        const InstWithinScene<T> sc = {h->rg_members.as<InstWithinArr<T>>(), s->recs.as<InstRec<T>>(), s->xforms.as<T>(), (uint32_t)nt};
+        const InstWithinArr<T>* arrs = instances_array_table<T>(s, h->wi_unfold, h->rg_members, h->rg_members_host);
+        const InstWithinScene<T> sc = {arrs, s->recs.as<InstRec<T>>(), s->xforms.as<T>(), (uint32_t)nt};
         instances_within_launch<T>(s, sc, points_dev, max_dist_dev, n, sorted, count_only, h);
     }
     BVH_HIP(hipStreamSynchronize(st));   // the result is complete when the call returns

@@ -242,6 +242,40 @@ class Instances(_Typed):
             return dict(offsets=offsets)
         return dict(offsets=offsets, instance=instance, shape=shape, dist=dist)
 
+    def knearest_batch(self, points, k: int):
+        """bvhgpu_instances_knearest_*: per point the k (instance, shape) pairs whose world-space triangles are nearest — bvhgpu_knearest_*'s
+        list and strict < over the two-level walk, the distance the true world distance to the transformed triangle.  Rows are ascending
+        in dist (a row that holds a NaN need not be sorted); equal distances stay in walk order (instances in the top level's order,
+        shapes in the member's order), and a tie at the k-th distance keeps the pairs met first.  1 <= k <= _lib.INSTANCES_KNN_MAX_K.
+        points: (n, 3) in the set's dtype — a numpy array (HOST) or a torch GPU tensor (DEVICE).
+        returns (instance[n, k], shape[n, k], dist[n, k]); slots beyond the number of pairs hold NONE, NONE and +inf.  numpy in: numpy
+        out, indices as uint32.  torch in: torch tensors on the same device, written by the kernel, indices as torch.int32 — so NONE
+        reads as -1 there."""
+        k = int(k)
+        rows = k if 1 <= k <= _lib.INSTANCES_KNN_MAX_K else 0   # (out of range: the engine answers INVALID_ARG before it touches a buffer)
+        keep, pp, n, mem = api._rows_in(points, 3, self.ft, "point")
+        if mem == DEVICE:
+            import torch
+            dev = keep.device
+            inst = torch.empty((n, rows), dtype=torch.int32, device=dev)
+            shape = torch.empty((n, rows), dtype=torch.int32, device=dev)
+            dist = torch.empty((n, rows), dtype=api._torch_ft(self.ft), device=dev)
+            api._torch_sync(dev)
+            ip, sp, dp = ptr(inst.data_ptr()), ptr(shape.data_ptr()), ptr(dist.data_ptr())
+        else:
+            inst, shape = np.zeros((n, rows), dtype=np.uint32), np.zeros((n, rows), dtype=np.uint32)
+            dist = np.zeros((n, rows), dtype=self.ft)
+            ip, sp, dp = ptr(inst), ptr(shape), ptr(dist)
+        fn = getattr(_lib.load(), f"bvhgpu_instances_knearest_{self.sfx}")
+        check(fn(self._s, pp, n, mem, k & 0xFFFFFFFF, ip, sp, dp), self.ctx._h)
+        return inst, shape, dist
+
+    def nearest_batch(self, points):
+        """knearest_batch with k = 1 and the last axis dropped: (instance[n], shape[n], dist[n]) — the reference's nearest_to over the
+        instanced scene; a set without instances gives NONE, NONE and +inf."""
+        inst, shape, dist = self.knearest_batch(points, 1)
+        return inst[:, 0], shape[:, 0], dist[:, 0]
+
     @property
     def world_boxes(self) -> np.ndarray:
         """W_i of the committed pose, (n, 6) [min xyz, max xyz]"""

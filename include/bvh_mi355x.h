@@ -971,6 +971,51 @@ int bvhgpu_instances_within_f32(bvhgpu_instances *s, const float *points, const 
 int bvhgpu_instances_within_f64(bvhgpu_instances *s, const double *points, const double *max_dist, size_t n, int mem, unsigned flags, bvhgpu_hits **hits);
 int bvhgpu_hits_fetch_instances_within(bvhgpu_hits *hits, uint32_t *offsets, uint32_t *instance, uint32_t *shape, void *dist, int mem);
 
+/* ---- k-nearest over an instanced scene: per query point the k (instance, shape) pairs whose WORLD-space triangles are nearest, ascending
+ * — distance fields, proximity and contact, snapping, without flattening the scene and without guessing a radius for
+ * bvhgpu_instances_within_*.  k = 1 is the reference's `nearest_to` over the scene.  The set is the committed one of
+ * bvhgpu_instances_trace_*.  All arithmetic is in the set's dtype T; every operation is rounded once, in the order written.
+ * Per point p a list L of at most k triples (d, instance, shape), ascending in d, the squared world distance in T.  full = len(L) == k,
+ * bound = L[last].d.  Every comparison is the strict < of T.  Insertion is bvhgpu_knearest_*'s: a full list drops its last element, and
+ * the new one goes in front of the first element e with d < e.d, else to the end.
+ *   top level (the FlatNode array over the world boxes, with p):
+ *     non-leaf entry: md = aabb.min_distance_squared(p);  entry_index iff !full || md < bound, else exit_index
+ *     leaf entry (instance i): walk instance i, then exit_index
+ *   instance i (member t = tree_of[i]), q[k] and F as for bvhgpu_instances_within_*:
+ *     member t's FlatNode array with q:
+ *       non-leaf entry: md = aabb.min_distance_squared(q);  entry_index iff !full || md < bound * F, else exit_index.  bound * F is ONE
+ *                       multiplication in T, made again whenever `bound` changes and on entry to the instance
+ *       leaf entry (shape s): w = the triangle in WORLD space and d = distance_squared(w, p) as for bvhgpu_instances_within_*;
+ *                             accepted iff !full || d < bound;  then exit_index
+ *  - Output row j, padded to k: out_instance[j*k + m], out_shape[j*k + m] and out_dist[j*k + m] = sqrt(L[m].d) for m < len(L); the other
+ *    slots hold BVHGPU_NONE, BVHGPU_NONE and +inf.
+ *  - The prune is conservative: |p - X v| >= |q - v| / ||Y||_F, so a member box with md >= bound * F holds no triangle with d < bound, and
+ *    a world box with md >= bound holds none either.  Acceptance is strict, so what a prune skips could not have been accepted (in exact
+ *    arithmetic; F exceeds the squared largest singular value of Y by the sum of the other two, which is the room rounding has for every
+ *    non-singular transform).  A row therefore equals the list built by offering EVERY (instance, shape) pair in the double order — the
+ *    instances in the top level's list order, within each the shapes in the member's — with no tree at all.
+ *  - Order and ties.  Equal distances stay in the double order.  A candidate equal to `bound` of a full list is refused, so a tie at the
+ *    k-th distance keeps the pairs met first.
+ *  - NaN behaves as in bvhgpu_knearest_*: a NaN d is accepted only while the list is not full, as `bound` of a full list it is never
+ *    replaced, and a NaN bound * F passes no box test.
+ *  - A set without instances gives all padding.  n = 0 is fine (NULL buffers too).
+ *  - Which arrays are walked: bvhgpu_instances_within_*'s rule; an imported member tree whose build had a split without SAH winner is
+ *    refused as there.  The table of arrays and the mirrors belong to the set and are freed by bvhgpu_instances_destroy.
+ *  - An identity instance of one tree gives that tree's own bvhgpu_knearest_* rows (kind 1): shapes and distances bit for bit.
+ * `mem` covers all four buffers.  The call runs on the context's stream and returns when the rows are complete; there is no result object.
+ * 1 <= k <= BVHGPU_INSTANCES_KNN_MAX_K: the lists of a workgroup live in LDS, k x (sizeof(T) + 8) bytes a lane — 64 lanes, k = 64 and f64 are
+ * exactly the 64 KB a launch gets.
+ * Refused, touching no buffer and leaving the set as it was, the first broken rule in this order: a NULL set; k = 0 or k >
+ * BVHGPU_INSTANCES_KNN_MAX_K; a NULL buffer with n > 0; a `mem` that is neither BVHGPU_HOST nor BVHGPU_DEVICE; a set of another dtype
+ * (BVHGPU_DTYPE_MISMATCH); an uncommitted set (the last update failed); a stale set (the check and the message of
+ * bvhgpu_instances_trace_*: "instances are stale" — a member that lost its triangles is stale); the imported member above; n >= 2^32 - 1
+ * or n * k >= 2^32 (BVHGPU_OVERFLOW).  Everything not marked is BVHGPU_INVALID_ARG. */
+#define BVHGPU_INSTANCES_KNN_MAX_K 64u /* 64 lanes x 64 slots x (8 + 4 + 4) bytes = 64 KB of LDS in f64 */
+int bvhgpu_instances_knearest_f32(bvhgpu_instances *s, const float *points, size_t n, int mem, uint32_t k,
+                                  uint32_t *out_instance, uint32_t *out_shape, float *out_dist);
+int bvhgpu_instances_knearest_f64(bvhgpu_instances *s, const double *points, size_t n, int mem, uint32_t k,
+                                  uint32_t *out_instance, uint32_t *out_shape, double *out_dist);
+
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */
 typedef struct { float build_ms, flatten_ms, traverse_kernel_ms, traverse_total_ms; } bvhgpu_timings;

@@ -6,6 +6,7 @@ use core::ffi::{c_char, c_int, c_uint, c_void};
 pub const BVHGPU_ABI_VERSION: c_int = 7;
 pub const BVHGPU_NONE: u32 = u32::MAX; // flat_bvh.rs:51-53
 pub const BVHGPU_KNN_MAX_K: u32 = 64; // largest k of bvhgpu_knearest_*
+pub const BVHGPU_INSTANCES_KNN_MAX_K: u32 = 64; // largest k of bvhgpu_instances_knearest_*
 pub const BVHGPU_KHITS_MAX_K: u32 = 64; // largest k of bvhgpu_traverse_khits_*
 pub const BVHGPU_ALLHITS_LIST_ORDER: c_uint = 1; // bvhgpu_traverse_allhits_*: rows in list order, no sort pass
 pub const BVHGPU_WITHIN_LIST_ORDER: c_uint = 1; // bvhgpu_within_*: rows in the order the loop met the candidates, no sort pass
@@ -241,6 +242,9 @@ extern "C" {
     pub fn bvhgpu_instances_within_f32(s: *mut bvhgpu_instances, points: *const f32, max_dist: *const f32, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_instances_within_f64(s: *mut bvhgpu_instances, points: *const f64, max_dist: *const f64, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_hits_fetch_instances_within(h: *mut bvhgpu_hits, offsets: *mut u32, instance: *mut u32, shape: *mut u32, dist: *mut c_void, mem: c_int) -> c_int;
+    // the k nearest (instance, shape) pairs per point over an instance set (out_*: n x k; padding = BVHGPU_NONE / BVHGPU_NONE / +inf; 1 <= k <= BVHGPU_INSTANCES_KNN_MAX_K; synchronous, no result object)
+    pub fn bvhgpu_instances_knearest_f32(s: *mut bvhgpu_instances, points: *const f32, n: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_dist: *mut f32) -> c_int;
+    pub fn bvhgpu_instances_knearest_f64(s: *mut bvhgpu_instances, points: *const f64, n: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_dist: *mut f64) -> c_int;
     pub fn bvhgpu_instances_boxes(s: *mut bvhgpu_instances, out: *mut c_void, mem: c_int) -> c_int;
     pub fn bvhgpu_instances_info(s: *const bvhgpu_instances, dtype: *mut c_int, n_trees: *mut usize, n_instances: *mut usize) -> c_int;
     pub fn bvhgpu_instances_destroy(s: *mut bvhgpu_instances);

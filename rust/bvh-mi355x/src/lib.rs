@@ -1004,6 +1004,29 @@ impl<T: GpuScalar> GpuInstances<T> {
         }
         (offsets, instance, shape, dist)
     }
+
+    /// Per point the `k` `(instance, shape)` pairs whose world-space triangles are nearest (`bvhgpu_instances_knearest_*`): `nearest_k`'s
+    /// list and strict `<` over the two-level walk, the distance the true world distance to the transformed triangle.  Returns row-major
+    /// `points.len() x k` arrays `(instance, shape, dist)`, distances not squared, ascending per row (a row that holds a NaN distance need
+    /// not be sorted); equal distances stay in walk order (instances in the top level's order, shapes in the member's order) and a tie
+    /// at the k-th distance keeps the pairs met first; slots beyond the number of pairs hold `u32::MAX`, `u32::MAX` and `+inf`.
+    /// `1 <= k <= ffi::BVHGPU_INSTANCES_KNN_MAX_K`; `k = 1` is `nearest_to` over the instanced scene.
+    pub fn knearest(&self, points: &[[T; 3]], k: usize) -> (Vec<u32>, Vec<u32>, Vec<T>) {
+        let k32 = u32::try_from(k).unwrap_or(u32::MAX);   // (out of range: the engine answers BVHGPU_INVALID_ARG and `check` panics with its message)
+        let slots = if (1..=ffi::BVHGPU_INSTANCES_KNN_MAX_K).contains(&k32) { points.len() * k } else { 0 };
+        let (mut instance, mut shape, mut dist) = (vec![0u32; slots], vec![0u32; slots], vec![T::default(); slots]);
+        unsafe {
+            let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_knearest_f32(self.set, points.as_ptr().cast(), points.len(), ffi::BVHGPU_HOST, k32, instance.as_mut_ptr(),
+                                                   shape.as_mut_ptr(), dist.as_mut_ptr().cast())
+            } else {
+                ffi::bvhgpu_instances_knearest_f64(self.set, points.as_ptr().cast(), points.len(), ffi::BVHGPU_HOST, k32, instance.as_mut_ptr(),
+                                                   shape.as_mut_ptr(), dist.as_mut_ptr().cast())
+            };
+            check(self.ctx, rc);
+        }
+        (instance, shape, dist)
+    }
 }
 
 impl<T: GpuScalar> Drop for GpuInstances<T> {

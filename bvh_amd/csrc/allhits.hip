@@ -178,56 +178,34 @@ __global__ __launch_bounds__(ROWS_SORT_THREADS) void k_allhits_sort_row(const ui
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 template <typename T, int LEAF>
 static void allhits_launch(bvhgpu_tree* t, const T* prims, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, bool sorted, bvhgpu_hits* h) {
-    constexpr uint32_t W = LeafVals<LEAF>::W;
     hipStream_t st = t->ctx->stream;
     const TravNode<T>* nodes = t->trav.as<TravNode<T>>();
     const uint32_t n_trav = (uint32_t)t->n_trav, n32 = (uint32_t)n;
     const dim3 rgrid((unsigned)((n + 255) / 256)), block(256);
-    uint32_t* counts = rows_begin(h, n, sorted);
-    uint32_t* offsets = h->offsets.as<uint32_t>();
-    hipLaunchKernelGGL((k_allhits_count<T, LEAF>), rgrid, block, 0, st, nodes, n_trav, prims, rays_dev, tmax_dev, n32, counts);
-    const RowsTotals rows = rows_scan(h, n, sorted ? ALLHITS_LANE_ROW_MAX : 0u, ALLHITS_LDS_ROW_MAX);
-    const unsigned long long total = rows.total;
-    if (total == 0) return;   // every row is empty
-    h->indices.reserve((size_t)total * 4);
-    h->ah_vals.reserve((size_t)total * W * sizeof(T));
-    uint32_t* pos = nullptr;
-    if (rows.n_beyond_lds) { h->ah_pos.reserve((size_t)total * 4); pos = h->ah_pos.as<uint32_t>(); }
-    uint32_t* shape = h->indices.as<uint32_t>();
-    T* vals = h->ah_vals.as<T>();
-    rows_offsets(h, n);
-    if (sorted) hipLaunchKernelGGL((k_allhits_fill<T, LEAF, true>), rgrid, block, 0, st, nodes, n_trav, prims, rays_dev, tmax_dev, n32, offsets, shape, vals, pos);
-    else hipLaunchKernelGGL((k_allhits_fill<T, LEAF, false>), rgrid, block, 0, st, nodes, n_trav, prims, rays_dev, tmax_dev, n32, offsets, shape, vals, pos);
-    if (sorted && rows.n_long)
-        hipLaunchKernelGGL((k_allhits_sort_row<T, LEAF>), dim3(rows.n_long), dim3(ROWS_SORT_THREADS), 0, st, h->ah_work.as<uint32_t>(), prims, rays_dev, offsets, shape,
-                           vals, pos);
-    BVH_HIP(hipGetLastError());
-    h->total = total;
+    const RowsPlan plan = {sorted, false, ALLHITS_LANE_ROW_MAX, ALLHITS_LDS_ROW_MAX, LeafVals<LEAF>::W * sizeof(T), false, false};
+    rows_run(h, n, plan,
+             [&](uint32_t* counts) { hipLaunchKernelGGL((k_allhits_count<T, LEAF>), rgrid, block, 0, st, nodes, n_trav, prims, rays_dev, tmax_dev, n32, counts); },
+             [&](const RowsOut& o, auto SORTED) {
+                 hipLaunchKernelGGL((k_allhits_fill<T, LEAF, decltype(SORTED)::value>), rgrid, block, 0, st, nodes, n_trav, prims, rays_dev, tmax_dev, n32, o.offsets,
+                                    o.shape, static_cast<T*>(o.vals), o.pos);
+             },
+             [&](const RowsOut& o, uint32_t n_long) {
+                 hipLaunchKernelGGL((k_allhits_sort_row<T, LEAF>), dim3(n_long), dim3(ROWS_SORT_THREADS), 0, st, o.work, prims, rays_dev, o.offsets, o.shape,
+                                    static_cast<T*>(o.vals), o.pos);
+             });
 }
 
 template <typename T>
 void allhits_batch(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, int leaf, unsigned flags, bvhgpu_hits* h) {
-    bvhgpu_ctx* ctx = t->ctx;
-    hipStream_t st = ctx->stream;
     const bool sorted = (flags & BVHGPU_ALLHITS_LIST_ORDER) == 0;
-    // the result object becomes an (empty) all-hits result first: whatever fails below leaves it consistent
-    h->offsets.reserve((n + 1) * 4);
-    rows_reset(h, ctx, Traits<T>::dtype, TRAVERSE_ALLHITS, leaf, false);
     char name[96];
     std::snprintf(name, sizeof name, "bvhgpu::k_allhits_fill<%s, %d, %s>", walk_type_name<T>(), leaf, sorted ? "true" : "false");
-    h->walk_kernel = name;
-    BVH_HIP(hipMemsetAsync(h->offsets.p, 0, 4, st));
-    if (n == 0 || t->n == 0) {   // no rays, or an empty hierarchy: every row is empty
-        BVH_HIP(hipMemsetAsync(h->offsets.p, 0, (n + 1) * 4, st));
-    } else {
+    rows_batch(h, t->ctx, Traits<T>::dtype, TRAVERSE_ALLHITS, leaf, false, n, t->n == 0, name, [&] {   // (empty: an empty hierarchy)
         ensure_flat_arrays(t);
         if (leaf == LEAF_TRIANGLE) allhits_launch<T, LEAF_TRIANGLE>(t, (const T*)t->tris.as<T>(), rays_dev, tmax_dev, n, sorted, h);
         else if (leaf == LEAF_SPHERE) allhits_launch<T, LEAF_SPHERE>(t, (const T*)t->spheres.as<T>(), rays_dev, tmax_dev, n, sorted, h);
         else allhits_launch<T, LEAF_BOX>(t, (const T*)t->aabbs.as<T>(), rays_dev, tmax_dev, n, sorted, h);
-    }
-    BVH_HIP(hipStreamSynchronize(st));   // the result is complete when the call returns
-    h->n_rays = n;
-    h->stats.hits = h->total;
+    });
 }
 template void allhits_batch<float>(bvhgpu_tree*, const bvhgpu_ray_f32*, const float*, size_t, int, unsigned, bvhgpu_hits*);
 template void allhits_batch<double>(bvhgpu_tree*, const bvhgpu_ray_f64*, const double*, size_t, int, unsigned, bvhgpu_hits*);

@@ -223,6 +223,54 @@ template <typename T> int new_build(bvhgpu_ctx* ctx, const T* aabbs, size_t n, i
     return BVHGPU_OK;
 }
 
+// ---- what kind of result a bvhgpu_hits holds ---------------------------------------------------------------------------------------------
+// One row per kind, in the enum's order: how the header spells the batches that make it, the accessor that reads it, and the internal
+// bits of bvhgpu_hits::flags that mark it (traverse_batch's walk-mode selectors and rows_reset's kinds; 0: the caller's flags alone).
+// A new family adds a row here and nothing to the accessors of the others.
+enum class HitsKind { Csr, Closest, Any, Box, Sphere, Allhits, Within, Region, InstRegion, InstAllhits, InstWithin };
+struct HitsKindRow { HitsKind kind; const char* entry; const char* reader; unsigned bits; };
+static constexpr HitsKindRow HITS_KINDS[] = {
+    {HitsKind::Csr, "bvhgpu_traverse_* / bvhgpu_query_* CSR", "bvhgpu_hits_fetch", 0},   // (options: T_SLICE, and TRIANGLES for bvhgpu_hits_fetch_triangles)
+    {HitsKind::Closest, "BVHGPU_TRAVERSE_CLOSEST", "bvhgpu_hits_fetch_closest", 0},
+    {HitsKind::Any, "bvhgpu_traverse_any_*", "bvhgpu_hits_fetch_any", TRAVERSE_ANY_HIT},
+    {HitsKind::Box, "bvhgpu_traverse_box_*", "bvhgpu_hits_fetch_box", TRAVERSE_BOX_HIT},
+    {HitsKind::Sphere, "bvhgpu_traverse_sphere_*", "bvhgpu_hits_fetch_sphere", TRAVERSE_SPHERE_HIT},
+    {HitsKind::Allhits, "bvhgpu_traverse_allhits_*", "bvhgpu_hits_fetch_allhits", TRAVERSE_ALLHITS},
+    {HitsKind::Within, "bvhgpu_within_*", "bvhgpu_hits_fetch_within", TRAVERSE_WITHIN},
+    {HitsKind::Region, "bvhgpu_region_*", "bvhgpu_hits_fetch_region", TRAVERSE_REGION},
+    // (its refusals name both region accessors: a caller who mixed the two region kinds up is told which one reads what)
+    {HitsKind::InstRegion, "bvhgpu_instances_region_*", "bvhgpu_hits_fetch_instances_region, not bvhgpu_hits_fetch_region", TRAVERSE_REGION},   // (options: shapes / INSTANCES_ONLY)
+    {HitsKind::InstAllhits, "bvhgpu_instances_allhits_*", "bvhgpu_hits_fetch_instances_allhits", TRAVERSE_INST_ALLHITS},
+    {HitsKind::InstWithin, "bvhgpu_instances_within_*", "bvhgpu_hits_fetch_instances_within", TRAVERSE_INST_WITHIN},
+};
+static constexpr unsigned hits_kind_bits() {
+    unsigned m = 0;
+    for (const HitsKindRow& r : HITS_KINDS) m |= r.bits;
+    return m;
+}
+static const HitsKindRow& hits_row(HitsKind k) { return HITS_KINDS[(int)k]; }
+static_assert(HITS_KINDS[(int)HitsKind::InstWithin].kind == HitsKind::InstWithin && sizeof(HITS_KINDS) / sizeof(HITS_KINDS[0]) == 11, "rows in the enum's order");
+
+// from what the object already stores: the internal bit, rg_inst within the region bit, else the caller's CLOSEST
+static HitsKind hits_kind(const bvhgpu_hits* h) {
+    for (const HitsKindRow& r : HITS_KINDS)
+        if (h->flags & r.bits) return r.bits != TRAVERSE_REGION ? r.kind : h->rg_inst == REGION_INST_NONE ? HitsKind::Region : HitsKind::InstRegion;
+    return (h->flags & BVHGPU_TRAVERSE_CLOSEST) ? HitsKind::Closest : HitsKind::Csr;
+}
+
+// What every accessor of a result object does first.  BVHGPU_OK: h holds a completed batch of the kind `want` (or `also`); every other
+// kind is refused with one message, which names the accessor that does read it.  copies: the accessor copies out of HBM, so it needs the ctx.
+static int hits_expect(const bvhgpu_hits* h, bool copies, HitsKind want, HitsKind also) {
+    if (!h || (copies && !h->ctx)) return BVHGPU_INVALID_ARG;
+    if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    const HitsKindRow& have = hits_row(hits_kind(h));
+    if (have.kind == want || have.kind == also) return BVHGPU_OK;
+    const std::string none = want == HitsKind::Closest ? std::string("traverse was run without BVHGPU_TRAVERSE_CLOSEST")
+                                                       : std::string("the result object holds no ") + hits_row(want).entry + " batch";
+    return fail(h->ctx, BVHGPU_INVALID_ARG, none + ": it holds a " + have.entry + " batch, use " + have.reader);
+}
+static int hits_expect(const bvhgpu_hits* h, bool copies, HitsKind want) { return hits_expect(h, copies, want, want); }
+
 // ---- result-object batches: bvhgpu_traverse_* / _traverse_async_* / _traverse_any_* / _traverse_box_* / _query_* ----------------------
 // What a family tests between batch_open and batch_refusal — its flags, `mem`, the wait for the tree's build — stays in the family:
 // the families differ there on purpose (an any-hit batch refuses bad flags before it settles the tree, a ray batch does not), and
@@ -286,7 +334,7 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
     }
     if ((flags & BVHGPU_TRAVERSE_TRIANGLES) && (flags & BVHGPU_TRAVERSE_CLOSEST))
         return fail(ctx, BVHGPU_INVALID_ARG, "TRIANGLES and CLOSEST are alternatives");
-    flags &= ~(TRAVERSE_ANY_HIT | TRAVERSE_BOX_HIT | TRAVERSE_SPHERE_HIT | TRAVERSE_ALLHITS | TRAVERSE_WITHIN | TRAVERSE_REGION | TRAVERSE_INST_ALLHITS | TRAVERSE_INST_WITHIN);   // (internal: only bvhgpu_traverse_any_* / _box_* / _sphere_* / _allhits_*, bvhgpu_within_*, bvhgpu_region_*, bvhgpu_instances_allhits_* and bvhgpu_instances_within_* set them)
+    flags &= ~hits_kind_bits();   // (internal: only the entries of the other kinds set them)
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
@@ -1781,15 +1829,8 @@ int bvhgpu_tree_set_spheres_f32(bvhgpu_tree* t, const float* spheres, size_t n, 
 int bvhgpu_tree_set_spheres_f64(bvhgpu_tree* t, const double* spheres, size_t n, int mem) { return set_spheres(t, spheres, n, mem, BVHGPU_F64); }
 
 int bvhgpu_hits_fetch_triangles(bvhgpu_hits* h, void* isect, int mem) {
-    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    { const int rc = hits_expect(h, true, HitsKind::Csr); if (rc != BVHGPU_OK) return rc; }
     bvhgpu_ctx* ctx = h->ctx;
-    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
-    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
-    if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "a sphere-hit batch has no triangle values: use bvhgpu_hits_fetch_sphere");
-    if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
-    if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
-    if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
     if (!(h->flags & BVHGPU_TRAVERSE_TRIANGLES)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_TRIANGLES");
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -1797,19 +1838,10 @@ int bvhgpu_hits_fetch_triangles(bvhgpu_hits* h, void* isect, int mem) {
         return (int)BVHGPU_OK;
     });
 }
-// one record per ray (`per_ray` scalars in h->closest, the shape in h->closest_prim) of a batch whose flags hold `kind_bit`
-static int fetch_per_ray(bvhgpu_hits* h, void* values, uint32_t* shape, int mem, unsigned kind_bit, const char* other_kind_msg, size_t per_ray) {
-    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+// one record per ray (`per_ray` scalars in h->closest, the shape in h->closest_prim) of a batch of the kind `kind`
+static int fetch_per_ray(bvhgpu_hits* h, void* values, uint32_t* shape, int mem, HitsKind kind, size_t per_ray) {
+    { const int rc = hits_expect(h, true, kind); if (rc != BVHGPU_OK) return rc; }
     bvhgpu_ctx* ctx = h->ctx;
-    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
-    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
-    if ((h->flags & TRAVERSE_SPHERE_HIT) && kind_bit != TRAVERSE_SPHERE_HIT)
-        return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
-    if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
-    if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
-    if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
-    if (!(h->flags & kind_bit)) return fail(ctx, BVHGPU_INVALID_ARG, other_kind_msg);
     return guarded(ctx, [&] {
         use_device(ctx);
         if (values && h->n_rays) copy_out(ctx, values, h->closest.p, h->n_rays * per_ray * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
@@ -1818,16 +1850,16 @@ static int fetch_per_ray(bvhgpu_hits* h, void* values, uint32_t* shape, int mem,
     });
 }
 int bvhgpu_hits_fetch_closest(bvhgpu_hits* h, void* isect, uint32_t* shape, int mem) {
-    return fetch_per_ray(h, isect, shape, mem, BVHGPU_TRAVERSE_CLOSEST, "traverse was run without BVHGPU_TRAVERSE_CLOSEST", 3);
+    return fetch_per_ray(h, isect, shape, mem, HitsKind::Closest, 3);
 }
 int bvhgpu_hits_fetch_any(bvhgpu_hits* h, void* isect, uint32_t* shape, int mem) {
-    return fetch_per_ray(h, isect, shape, mem, TRAVERSE_ANY_HIT, "the result object holds no bvhgpu_traverse_any_* batch", 3);
+    return fetch_per_ray(h, isect, shape, mem, HitsKind::Any, 3);
 }
 int bvhgpu_hits_fetch_box(bvhgpu_hits* h, void* slice, uint32_t* shape, int mem) {
-    return fetch_per_ray(h, slice, shape, mem, TRAVERSE_BOX_HIT, "the result object holds no bvhgpu_traverse_box_* batch", 2);
+    return fetch_per_ray(h, slice, shape, mem, HitsKind::Box, 2);
 }
 int bvhgpu_hits_fetch_sphere(bvhgpu_hits* h, void* slice, uint32_t* shape, int mem) {
-    return fetch_per_ray(h, slice, shape, mem, TRAVERSE_SPHERE_HIT, "the result object holds no bvhgpu_traverse_sphere_* batch", 2);
+    return fetch_per_ray(h, slice, shape, mem, HitsKind::Sphere, 2);
 }
 
 int bvhgpu_hits_info(const bvhgpu_hits* h, size_t* n_rays, uint64_t* total, bvhgpu_traverse_stats* stats) {
@@ -1854,19 +1886,9 @@ int bvhgpu_hits_walk_kernel(const bvhgpu_hits* h, char* name, size_t cap) {
 }
 
 int bvhgpu_hits_fetch(bvhgpu_hits* h, uint32_t* offsets, uint32_t* indices, void* tslice, int mem) {
-    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    { const int rc = hits_expect(h, true, HitsKind::Csr); if (rc != BVHGPU_OK) return rc; }
     bvhgpu_ctx* ctx = h->ctx;
-    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
-    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
-    if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "an all-hits batch has a CSR of its own: use bvhgpu_hits_fetch_allhits");
-    if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
-    if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
     if (tslice && !(h->flags & BVHGPU_TRAVERSE_T_SLICE)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_T_SLICE");
-    if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR: use bvhgpu_hits_fetch_closest");
-    if (h->flags & TRAVERSE_ANY_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR: use bvhgpu_hits_fetch_any");
-    if (h->flags & TRAVERSE_BOX_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "a box-hit batch produces no CSR: use bvhgpu_hits_fetch_box");
-    if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "a sphere-hit batch produces no CSR: use bvhgpu_hits_fetch_sphere");
     return guarded(ctx, [&] {
         use_device(ctx);
         if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
@@ -1878,21 +1900,15 @@ int bvhgpu_hits_fetch(bvhgpu_hits* h, uint32_t* offsets, uint32_t* indices, void
 
 // the CSR of an all-hits batch: offsets (n_rays + 1 u32), the shapes (total u32), the records (total x W T); each may be NULL
 int bvhgpu_hits_fetch_allhits(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape, void* vals, int mem) {
-    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    { const int rc = hits_expect(h, true, HitsKind::Allhits); if (rc != BVHGPU_OK) return rc; }
     bvhgpu_ctx* ctx = h->ctx;
-    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
-    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
-    if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
-    if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
-    if (!(h->flags & TRAVERSE_ALLHITS)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_traverse_allhits_* batch");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
     return guarded(ctx, [&] {
         use_device(ctx);
-        const size_t w = h->ah_leaf == BVHGPU_LEAF_TRIANGLE ? 3 : 2;
+        const size_t w = h->row_leaf == BVHGPU_LEAF_TRIANGLE ? 3 : 2;
         if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
         if (shape && h->total) copy_out(ctx, shape, h->indices.p, h->total * 4, mem);
-        if (vals && h->total) copy_out(ctx, vals, h->ah_vals.p, h->total * w * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
+        if (vals && h->total) copy_out(ctx, vals, h->row_vals.p, h->total * w * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
         return (int)BVHGPU_OK;
     });
 }
@@ -1900,46 +1916,29 @@ int bvhgpu_hits_fetch_allhits(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape
 // the CSR of a within batch: offsets (n + 1 u32), the shapes (total u32), the distances (total T); each may be NULL.  A COUNT_ONLY batch
 // has offsets only: its shapes and distances are empty, whatever `total` says.
 int bvhgpu_hits_fetch_within(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape, void* dist, int mem) {
-    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    { const int rc = hits_expect(h, true, HitsKind::Within); if (rc != BVHGPU_OK) return rc; }
     bvhgpu_ctx* ctx = h->ctx;
-    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
-    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
-    if (h->flags & TRAVERSE_REGION) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
-    if (!(h->flags & TRAVERSE_WITHIN)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_within_* batch");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
     return guarded(ctx, [&] {
         use_device(ctx);
-        const size_t rows = h->wi_count_only ? 0 : (size_t)h->total;
+        const size_t rows = h->count_only ? 0 : (size_t)h->total;
         if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
         if (shape && rows) copy_out(ctx, shape, h->indices.p, rows * 4, mem);
-        if (dist && rows) copy_out(ctx, dist, h->ah_vals.p, rows * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
+        if (dist && rows) copy_out(ctx, dist, h->row_vals.p, rows * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
         return (int)BVHGPU_OK;
     });
 }
 
 // the CSR of a region batch: offsets (n + 1 u32), the shapes (total u32), the inside bytes (total, CLASSIFY batches); each may be NULL.  A
-// COUNT_ONLY batch has offsets only, whatever `total` says.  Every other kind of result is refused, each with its own message.
+// COUNT_ONLY batch has offsets only, whatever `total` says.
 int bvhgpu_hits_fetch_region(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape, void* inside, int mem) {
-    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    { const int rc = hits_expect(h, true, HitsKind::Region); if (rc != BVHGPU_OK) return rc; }
     bvhgpu_ctx* ctx = h->ctx;
-    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
-    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
-    if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
-    if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
-    if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
-    if (h->flags & TRAVERSE_BOX_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_box_* batch: use bvhgpu_hits_fetch_box");
-    if (h->flags & TRAVERSE_ANY_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_any_* batch: use bvhgpu_hits_fetch_any");
-    if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a CLOSEST batch: use bvhgpu_hits_fetch_closest");
-    if (!(h->flags & TRAVERSE_REGION)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_region_* batch: use bvhgpu_hits_fetch");
-    if (h->rg_inst != REGION_INST_NONE)
-        return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_region_* batch: use bvhgpu_hits_fetch_instances_region");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
     if (inside && !h->rg_classify) return fail(ctx, BVHGPU_INVALID_ARG, "the region batch was run without BVHGPU_REGION_CLASSIFY");
     return guarded(ctx, [&] {
         use_device(ctx);
-        const size_t rows = h->wi_count_only ? 0 : (size_t)h->total;
+        const size_t rows = h->count_only ? 0 : (size_t)h->total;
         if (offsets) copy_out(ctx, offsets, h->rg_offsets.p, (h->n_rays + 1) * 4, mem);
         if (shape && rows) copy_out(ctx, shape, h->indices.p, rows * 4, mem);
         if (inside && rows) copy_out(ctx, inside, h->rg_inside.p, rows, mem);
@@ -1949,30 +1948,19 @@ int bvhgpu_hits_fetch_region(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape,
 
 // the CSR of a region batch over an instance set: offsets (n + 1 u32), the instances and the shapes (total u32 each; a batch with
 // BVHGPU_REGION_INSTANCES_ONLY has no shapes), the inside bytes (total, CLASSIFY batches); each may be NULL.  A COUNT_ONLY batch has offsets
-// only, whatever `total` says.  Every other kind of result is refused, a bvhgpu_region_* result included.
+// only, whatever `total` says.  A bvhgpu_region_* result is another kind.
 int bvhgpu_hits_fetch_instances_region(bvhgpu_hits* h, uint32_t* offsets, uint32_t* instance, uint32_t* shape, void* inside, int mem) {
-    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    { const int rc = hits_expect(h, true, HitsKind::InstRegion); if (rc != BVHGPU_OK) return rc; }
     bvhgpu_ctx* ctx = h->ctx;
-    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
-    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
-    if (h->flags & TRAVERSE_ALLHITS) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_allhits_* batch: use bvhgpu_hits_fetch_allhits");
-    if (h->flags & TRAVERSE_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
-    if (h->flags & TRAVERSE_SPHERE_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_sphere_* batch: use bvhgpu_hits_fetch_sphere");
-    if (h->flags & TRAVERSE_BOX_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_box_* batch: use bvhgpu_hits_fetch_box");
-    if (h->flags & TRAVERSE_ANY_HIT) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_traverse_any_* batch: use bvhgpu_hits_fetch_any");
-    if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a CLOSEST batch: use bvhgpu_hits_fetch_closest");
-    if (!(h->flags & TRAVERSE_REGION)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_instances_region_* batch: use bvhgpu_hits_fetch");
-    if (h->rg_inst == REGION_INST_NONE) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
     if (inside && !h->rg_classify) return fail(ctx, BVHGPU_INVALID_ARG, "the region batch was run without BVHGPU_REGION_CLASSIFY");
     if (shape && h->rg_inst == REGION_INST_ONLY) return fail(ctx, BVHGPU_INVALID_ARG, "the region batch was run with BVHGPU_REGION_INSTANCES_ONLY: it has no shapes");
     return guarded(ctx, [&] {
         use_device(ctx);
-        const size_t rows = h->wi_count_only ? 0 : (size_t)h->total;
+        const size_t rows = h->count_only ? 0 : (size_t)h->total;
         const bool only = h->rg_inst == REGION_INST_ONLY;   // (stage 1's rows: the instances are where a region result keeps its shapes)
         if (offsets) copy_out(ctx, offsets, h->rg_offsets.p, (h->n_rays + 1) * 4, mem);
-        if (instance && rows) copy_out(ctx, instance, only ? h->indices.p : h->rg_instance.p, rows * 4, mem);
+        if (instance && rows) copy_out(ctx, instance, only ? h->indices.p : h->row_instance.p, rows * 4, mem);
         if (shape && rows) copy_out(ctx, shape, h->indices.p, rows * 4, mem);
         if (inside && rows) copy_out(ctx, inside, h->rg_inside.p, rows, mem);
         return (int)BVHGPU_OK;
@@ -1980,67 +1968,50 @@ int bvhgpu_hits_fetch_instances_region(bvhgpu_hits* h, uint32_t* offsets, uint32
 }
 
 // the CSR of an all-hits batch over an instance set: offsets (n_rays + 1 u32), the instances and the shapes (total u32 each), the records
-// (total x 3 T); each may be NULL.  A COUNT_ONLY batch has offsets only.  Every other kind of result is refused.
+// (total x 3 T); each may be NULL.  A COUNT_ONLY batch has offsets only.
 int bvhgpu_hits_fetch_instances_allhits(bvhgpu_hits* h, uint32_t* offsets, uint32_t* instance, uint32_t* shape, void* vals, int mem) {
-    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    { const int rc = hits_expect(h, true, HitsKind::InstAllhits); if (rc != BVHGPU_OK) return rc; }
     bvhgpu_ctx* ctx = h->ctx;
-    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (h->flags & TRAVERSE_INST_WITHIN) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
-    if (!(h->flags & TRAVERSE_INST_ALLHITS)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_instances_allhits_* batch");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if ((instance || shape || vals) && h->wi_count_only)
+    if ((instance || shape || vals) && h->count_only)
         return fail(ctx, BVHGPU_INVALID_ARG, "the batch was run with BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY: it has offsets only");
     return guarded(ctx, [&] {
         use_device(ctx);
         if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
-        if (instance && h->total) copy_out(ctx, instance, h->rg_instance.p, h->total * 4, mem);
+        if (instance && h->total) copy_out(ctx, instance, h->row_instance.p, h->total * 4, mem);
         if (shape && h->total) copy_out(ctx, shape, h->indices.p, h->total * 4, mem);
-        if (vals && h->total) copy_out(ctx, vals, h->ah_vals.p, h->total * 3 * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
+        if (vals && h->total) copy_out(ctx, vals, h->row_vals.p, h->total * 3 * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
         return (int)BVHGPU_OK;
     });
 }
 
 // the CSR of a within batch over an instance set: offsets (n + 1 u32), the instances and the shapes (total u32 each), the distances
-// (total T); each may be NULL.  A COUNT_ONLY batch has offsets only.  Every other kind of result is refused.
+// (total T); each may be NULL.  A COUNT_ONLY batch has offsets only.
 int bvhgpu_hits_fetch_instances_within(bvhgpu_hits* h, uint32_t* offsets, uint32_t* instance, uint32_t* shape, void* dist, int mem) {
-    if (!h || !h->ctx) return BVHGPU_INVALID_ARG;
+    { const int rc = hits_expect(h, true, HitsKind::InstWithin); if (rc != BVHGPU_OK) return rc; }
     bvhgpu_ctx* ctx = h->ctx;
-    if (h->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (!(h->flags & TRAVERSE_INST_WITHIN)) return fail(ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_instances_within_* batch");
     if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if ((instance || shape || dist) && h->wi_count_only)
+    if ((instance || shape || dist) && h->count_only)
         return fail(ctx, BVHGPU_INVALID_ARG, "the batch was run with BVHGPU_INSTANCES_WITHIN_COUNT_ONLY: it has offsets only");
     return guarded(ctx, [&] {
         use_device(ctx);
         if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
-        if (instance && h->total) copy_out(ctx, instance, h->rg_instance.p, h->total * 4, mem);
+        if (instance && h->total) copy_out(ctx, instance, h->row_instance.p, h->total * 4, mem);
         if (shape && h->total) copy_out(ctx, shape, h->indices.p, h->total * 4, mem);
-        if (dist && h->total) copy_out(ctx, dist, h->ah_vals.p, h->total * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
+        if (dist && h->total) copy_out(ctx, dist, h->row_vals.p, h->total * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
         return (int)BVHGPU_OK;
     });
 }
 
 int bvhgpu_hits_region_info(const bvhgpu_hits* h, uint32_t* n_chunks, uint32_t* chunk_entries) {
-    if (!h) return BVHGPU_INVALID_ARG;
-    if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (!(h->flags & TRAVERSE_REGION)) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds no bvhgpu_region_* batch");
+    { const int rc = hits_expect(h, false, HitsKind::Region, HitsKind::InstRegion); if (rc != BVHGPU_OK) return rc; }
     if (n_chunks) *n_chunks = h->rg_chunks;
     if (chunk_entries) *chunk_entries = h->rg_chunk_entries;
     return BVHGPU_OK;
 }
 
 int bvhgpu_hits_device(const bvhgpu_hits* h, const uint32_t** offsets, const uint32_t** indices, const void** tslice) {
-    if (!h) return BVHGPU_INVALID_ARG;
-    if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
-    if (h->flags & TRAVERSE_INST_ALLHITS) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_allhits_* batch: use bvhgpu_hits_fetch_instances_allhits");
-    if (h->flags & TRAVERSE_INST_WITHIN) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_instances_within_* batch: use bvhgpu_hits_fetch_instances_within");
-    if (h->flags & TRAVERSE_ALLHITS) return fail(h->ctx, BVHGPU_INVALID_ARG, "an all-hits batch has a CSR of its own: use bvhgpu_hits_fetch_allhits");
-    if (h->flags & TRAVERSE_WITHIN) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_within_* batch: use bvhgpu_hits_fetch_within");
-    if (h->flags & TRAVERSE_REGION) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds a bvhgpu_region_* batch: use bvhgpu_hits_fetch_region");
-    if (h->flags & BVHGPU_TRAVERSE_CLOSEST) return fail(h->ctx, BVHGPU_INVALID_ARG, "CLOSEST produces no CSR");
-    if (h->flags & TRAVERSE_ANY_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "an any-hit batch produces no CSR");
-    if (h->flags & TRAVERSE_BOX_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "a box-hit batch produces no CSR");
-    if (h->flags & TRAVERSE_SPHERE_HIT) return fail(h->ctx, BVHGPU_INVALID_ARG, "a sphere-hit batch produces no CSR: use bvhgpu_hits_fetch_sphere");
+    { const int rc = hits_expect(h, false, HitsKind::Csr); if (rc != BVHGPU_OK) return rc; }
     if (offsets) *offsets = h->offsets.as<uint32_t>();
     if (indices) *indices = h->indices.as<uint32_t>();
     if (tslice) *tslice = (h->flags & BVHGPU_TRAVERSE_T_SLICE) ? h->tslice.p : nullptr;

@@ -299,34 +299,32 @@ struct bvhgpu_hits {
     bvhgpu::DevBuf any_key;              // n_rays u32: any-hit batches walked as items (walk.hpp WalkOut::any_key), all-ones between batches
     bool akey_clean = false;
     bvhgpu::DevBuf any_part;             // per workgroup of k_any_resolve: its occluded rays (k_any_publish adds them up)
-    // all-hits batches (bvhgpu_traverse_allhits_*, allhits.hip): the CSR is `offsets` / `indices` (the shapes) / `ah_vals` (total x W T)
-    int ah_leaf = 0;                     // BVHGPU_LEAF_* of the batch (W = 3 for triangles, else 2)
-    bvhgpu::DevBuf ah_vals;
-    bvhgpu::DevBuf ah_counts, ah_sums;   // n_rays u32 candidate counts; {total, long rows, rows beyond LDS} + a 64-bit sum per scan block
-    bvhgpu::DevBuf ah_work, ah_pos;      // the long rows of a sorted batch (ray ids); list positions of the rows sorted in global memory
-    // within batches (bvhgpu_within_*, within.hip) reuse them: the CSR is `offsets` / `indices` (the shapes) / `ah_vals` (total T distances)
-    bool wi_count_only = false;          // BVHGPU_WITHIN_COUNT_ONLY: `offsets` and `total` only, no shapes and no distances
-    bvhgpu::DevBuf wi_unfold;            // the FlatNode array of a built tree with empty child bounds as an unfolded TravNode array (within.hip)
-    // region batches (bvhgpu_region_*, region.hip): `offsets` holds the scanned counts of the (region, chunk) units, `rg_offsets` the caller's
-    // n + 1 row offsets gathered from them; the CSR is `rg_offsets` / `indices` (the shapes) / `rg_inside` (total bytes, CLASSIFY).  HOST planes
-    // are staged in `qbuf`, a COUNT_ONLY batch sets wi_count_only, a tree with empty child bounds is mirrored into wi_unfold.
+    // ---- results with one variable-length row per query, as a CSR (capi.hip hits_kind() tells which; rows.hpp has the schedule) --------
+    //   kind (entry point)                              offsets      instance       shape     values
+    //   all-hits            bvhgpu_traverse_allhits_*   offsets      -              indices   row_vals   total x W T (row_leaf: W = 3 / 2)
+    //   within              bvhgpu_within_*             offsets      -              indices   row_vals   total T distances
+    //   region              bvhgpu_region_*             rg_offsets   -              indices   rg_inside  total bytes (CLASSIFY)
+    //   instances-region    bvhgpu_instances_region_*   rg_offsets   row_instance   indices   rg_inside  (INSTANCES_ONLY: the instances in indices)
+    //   instances-all-hits  bvhgpu_instances_allhits_*  offsets      row_instance   indices   row_vals   total x 3 T
+    //   instances-within    bvhgpu_instances_within_*   offsets      row_instance   indices   row_vals   total T distances
+    // A region batch keeps the scanned counts of its (region, chunk) units in `offsets` and gathers the caller's n + 1 row offsets from
+    // them; its HOST planes are staged in `qbuf`.  Instances-region and instances-within make their per-batch member table in rg_members.
+    int row_leaf = 0;                    // all-hits: BVHGPU_LEAF_* of the batch
+    bool count_only = false;             // the batch ran with its family's COUNT_ONLY flag: `offsets` and `total` only
+    bvhgpu::DevBuf row_vals, row_instance;
+    bvhgpu::DevBuf rows_counts, rows_sums;   // the scan (rows.hip): n u32 candidate counts; {total, long rows, rows beyond LDS} + a 64-bit sum per scan block
+    bvhgpu::DevBuf rows_work, rows_pos;      // the long rows of a sorted batch (query ids); list positions of the rows sorted in global memory
+    bvhgpu::DevBuf row_list_shape;       // total u32: the shapes of the long rows of a sorted instances batch in the double order (the sort gathers from it)
+    bvhgpu::DevBuf unfold;               // FlatNode arrays of built trees with empty child bounds as unfolded TravNode arrays (unfold.hpp), made per batch
     bvhgpu::DevBuf rg_offsets, rg_inside;
     bvhgpu::DevBuf rg_anc;               // per chunk of the batch: its ancestor count, then REGION_ANC_MAX ancestor entries (rebuilt by every batch)
-    uint32_t rg_chunks = 0, rg_chunk_entries = 0;   // how the batch cut the entry array (bvhgpu_hits_region_info)
+    uint32_t rg_chunks = 0, rg_chunk_entries = 0;   // how the batch cut the entry array (bvhgpu_hits_region_info); instances: the uniform stride of the
+                                                    // (pair, chunk) units and the largest member's chunk
     bool rg_classify = false;            // BVHGPU_REGION_CLASSIFY: `rg_inside` was written
-    // region batches over an instance set (bvhgpu_instances_region_*, region.hip): the same CSR with `rg_instance` beside `indices`; the
-    // units are (pair, chunk), rg_chunks the uniform stride and rg_chunk_entries the largest member's chunk
     int rg_inst = 0;                     // REGION_INST_*: which of the two entries made this region result (rows_reset: NONE)
-    bvhgpu::DevBuf rg_instance;          // total u32: the instance of every reported shape
     bvhgpu::DevBuf rg_pairs;             // per (region, instance) pair: its region
-    bvhgpu::DevBuf rg_members;           // per member tree: region.hip RegionMember<T> (rebuilt by every batch, like the ancestor table)
+    bvhgpu::DevBuf rg_members;           // per member tree: region.hip RegionMember<T> / instances_arrays.hpp InstWithinArr<T> (rebuilt by every batch)
     std::vector<unsigned char> rg_members_host;   // its host image (alive while the upload is in flight)
-    // all-hits batches over an instance set (bvhgpu_instances_allhits_*, instances_allhits.hip): the CSR is `offsets` / `rg_instance` / `indices`
-    // (the shapes) / `ah_vals` (total x 3 T); the scan runs in ah_counts / ah_sums / ah_work / ah_pos, a COUNT_ONLY batch sets wi_count_only
-    bvhgpu::DevBuf ia_list_shape;        // total u32: the shapes of the long rows of a sorted batch in the double order (the sort gathers from it)
-    // within batches over an instance set (bvhgpu_instances_within_*, instances_within.hip): the CSR is `offsets` / `rg_instance` / `indices` (the
-    // shapes) / `ah_vals` (total T distances); the scan runs in ah_counts / ah_sums / ah_work / ah_pos, the long rows' shapes wait in ia_list_shape,
-    // a COUNT_ONLY batch sets wi_count_only; the per-batch array table lives in rg_members (instances_within.hip InstWithinArr<T>), the mirrors in wi_unfold
     uint32_t replays = 0;               // times bvhgpu_hits_wait had to enqueue the asynchronous batch again
     int deferred_rc = 0;                // status of a completion that ran on behalf of another call (rebuild / destroy of the tree)
     std::string deferred_err;
@@ -433,12 +431,12 @@ template <typename T>
 void khits_batch(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, int leaf, uint32_t k,
                  uint32_t* out_shape_dev, T* out_vals_dev);
 // allhits.hip: every hit per ray as a CSR (bvhgpu_traverse_allhits_*); leaf: BVHGPU_LEAF_*; flags: BVHGPU_ALLHITS_*; tmax_dev: NULL or n segment
-// ends.  Synchronous: h->offsets / h->indices / h->ah_vals and h->total are complete on return.  Throws Fail::Overflow when the batch has
+// ends.  Synchronous: h->offsets / h->indices / h->row_vals and h->total are complete on return.  Throws Fail::Overflow when the batch has
 // more than 2^32-1 candidates (the result object then holds an empty all-hits result).
 template <typename T>
 void allhits_batch(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, int leaf, unsigned flags, bvhgpu_hits* h);
 // within.hip: every shape within max_dist_dev[i] of point i as a CSR (bvhgpu_within_*); kind: 0 the shapes' AABBs, 1 their triangles; flags:
-// BVHGPU_WITHIN_*.  Synchronous: h->offsets / h->indices / h->ah_vals and h->total are complete on return.  Throws Fail::Overflow when the
+// BVHGPU_WITHIN_*.  Synchronous: h->offsets / h->indices / h->row_vals and h->total are complete on return.  Throws Fail::Overflow when the
 // batch has more than 2^32-1 candidates (the result object then holds an empty within result).
 template <typename T>
 void within_batch(bvhgpu_tree* t, const T* points_dev, const T* max_dist_dev, size_t n, int kind, unsigned flags, bvhgpu_hits* h);
@@ -447,19 +445,19 @@ void within_batch(bvhgpu_tree* t, const T* points_dev, const T* max_dist_dev, si
 // Fail::Overflow when the batch reports more than 2^32-1 shapes (the result object then holds an empty region result).
 template <typename T>
 void region_batch(bvhgpu_tree* t, const T* planes_dev, size_t n, uint32_t m, unsigned flags, bvhgpu_hits* h);
-// region.hip: the same over a committed instance set (bvhgpu_instances_region_*): rows of (instance, shape) in h->rg_offsets / h->rg_instance /
+// region.hip: the same over a committed instance set (bvhgpu_instances_region_*): rows of (instance, shape) in h->rg_offsets / h->row_instance /
 // h->indices / h->rg_inside, or with BVHGPU_REGION_INSTANCES_ONLY rows of instances in h->indices.  Synchronous; throws Fail::Overflow when the
 // batch has more than 2^32-1 (region, instance) pairs or reports more than 2^32-1 shapes (the result object then holds an empty result).
 template <typename T>
 void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, uint32_t m, unsigned flags, bvhgpu_hits* h);
 // instances_allhits.hip: every hit per ray over a committed instance set as a CSR (bvhgpu_instances_allhits_*); flags:
-// BVHGPU_INSTANCES_ALLHITS_*; tmax_dev: NULL or n segment ends.  Synchronous: h->offsets / h->rg_instance / h->indices / h->ah_vals and
+// BVHGPU_INSTANCES_ALLHITS_*; tmax_dev: NULL or n segment ends.  Synchronous: h->offsets / h->row_instance / h->indices / h->row_vals and
 // h->total are complete on return.  Throws Fail::Overflow when the batch has more than 2^32-1 candidates (the result object then holds an
 // empty result of this kind).
 template <typename T>
 void instances_allhits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, unsigned flags, bvhgpu_hits* h);
 // instances_within.hip: every (instance, shape) within max_dist_dev[i] of point i over a committed instance set as a CSR
-// (bvhgpu_instances_within_*); flags: BVHGPU_INSTANCES_WITHIN_*.  Synchronous: h->offsets / h->rg_instance / h->indices / h->ah_vals and h->total
+// (bvhgpu_instances_within_*); flags: BVHGPU_INSTANCES_WITHIN_*.  Synchronous: h->offsets / h->row_instance / h->indices / h->row_vals and h->total
 // are complete on return.  Throws Fail::Overflow when the batch has more than 2^32-1 candidates (the result object then holds an empty
 // result of this kind).
 template <typename T>

@@ -239,57 +239,28 @@ static void instances_allhits_launch(bvhgpu_instances* s, const typename Traits<
     const InstScene<T> sc = {s->top->trav.as<TravNode<T>>(), (uint32_t)s->top->n_trav, s->recs.as<InstRec<T>>(), s->table.as<InstTree<T>>()};
     const uint32_t n32 = (uint32_t)n;
     const dim3 rgrid((unsigned)((n + 255) / 256)), block(256);
-    const bool rows_sorted = sorted && !count_only;
-    uint32_t* counts = rows_begin(h, n, rows_sorted);
-    uint32_t* offsets = h->offsets.as<uint32_t>();
-    hipLaunchKernelGGL((k_instances_allhits_count<T>), rgrid, block, 0, st, sc, rays_dev, tmax_dev, n32, counts);
-    const RowsTotals rows = rows_scan(h, n, rows_sorted ? INST_ALLHITS_LANE_ROW_MAX : 0u, INST_ALLHITS_LDS_ROW_MAX);
-    if (rows.total == 0) return;   // every row is empty
-    rows_offsets(h, n);
-    if (!count_only) {
-        const size_t total = (size_t)rows.total;
-        h->rg_instance.reserve(total * 4);
-        h->indices.reserve(total * 4);
-        h->ah_vals.reserve(total * 3 * sizeof(T));
-        uint32_t *list_shape = nullptr, *pos = nullptr;
-        if (rows.n_long) { h->ia_list_shape.reserve(total * 4); list_shape = h->ia_list_shape.as<uint32_t>(); }
-        if (rows.n_beyond_lds) { h->ah_pos.reserve(total * 4); pos = h->ah_pos.as<uint32_t>(); }
-        uint32_t* instance = h->rg_instance.as<uint32_t>();
-        uint32_t* shape = h->indices.as<uint32_t>();
-        T* vals = h->ah_vals.as<T>();
-        if (sorted) hipLaunchKernelGGL((k_instances_allhits_fill<T, true>), rgrid, block, 0, st, sc, rays_dev, tmax_dev, n32, offsets, instance, shape, vals,
-                                       list_shape, pos);
-        else hipLaunchKernelGGL((k_instances_allhits_fill<T, false>), rgrid, block, 0, st, sc, rays_dev, tmax_dev, n32, offsets, instance, shape, vals,
-                                list_shape, pos);
-        // the sort-row kernel reads both without a test of its own
-        if (sorted && ((rows.n_long && !list_shape) || (rows.n_beyond_lds && !pos))) throw HipFail{hipErrorInvalidValue, nullptr, __LINE__, Fail::None};
-        if (sorted && rows.n_long)
-            hipLaunchKernelGGL((k_instances_allhits_sort_row<T>), dim3(rows.n_long), dim3(ROWS_SORT_THREADS), 0, st, sc, h->ah_work.as<uint32_t>(), rays_dev,
-                               offsets, instance, shape, vals, list_shape, pos);
-    }
-    BVH_HIP(hipGetLastError());
-    h->total = rows.total;
+    const RowsPlan plan = {sorted, count_only, INST_ALLHITS_LANE_ROW_MAX, INST_ALLHITS_LDS_ROW_MAX, 3 * sizeof(T), true, true};
+    rows_run(h, n, plan,
+             [&](uint32_t* counts) { hipLaunchKernelGGL((k_instances_allhits_count<T>), rgrid, block, 0, st, sc, rays_dev, tmax_dev, n32, counts); },
+             [&](const RowsOut& o, auto SORTED) {
+                 hipLaunchKernelGGL((k_instances_allhits_fill<T, decltype(SORTED)::value>), rgrid, block, 0, st, sc, rays_dev, tmax_dev, n32, o.offsets, o.instance,
+                                    o.shape, static_cast<T*>(o.vals), o.list_shape, o.pos);
+             },
+             [&](const RowsOut& o, uint32_t n_long) {
+                 hipLaunchKernelGGL((k_instances_allhits_sort_row<T>), dim3(n_long), dim3(ROWS_SORT_THREADS), 0, st, sc, o.work, rays_dev, o.offsets, o.instance,
+                                    o.shape, static_cast<T*>(o.vals), o.list_shape, o.pos);
+             });
 }
 
 template <typename T>
 void instances_allhits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, unsigned flags, bvhgpu_hits* h) {
-    bvhgpu_ctx* ctx = s->ctx;
-    hipStream_t st = ctx->stream;
     const bool sorted = (flags & BVHGPU_INSTANCES_ALLHITS_LIST_ORDER) == 0;
     const bool count_only = (flags & BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY) != 0;
-    // the result object becomes an (empty) result of this kind first: whatever fails below leaves it consistent
-    h->offsets.reserve((n + 1) * 4);
-    rows_reset(h, ctx, Traits<T>::dtype, TRAVERSE_INST_ALLHITS, BVHGPU_LEAF_TRIANGLE, count_only);
     char name[96];
     if (count_only) std::snprintf(name, sizeof name, "bvhgpu::k_instances_allhits_count<%s>", walk_type_name<T>());
     else std::snprintf(name, sizeof name, "bvhgpu::k_instances_allhits_fill<%s, %s>", walk_type_name<T>(), sorted ? "true" : "false");
-    h->walk_kernel = name;
-    BVH_HIP(hipMemsetAsync(h->offsets.p, 0, 4, st));
-    if (n == 0 || s->n == 0) BVH_HIP(hipMemsetAsync(h->offsets.p, 0, (n + 1) * 4, st));   // no rays, or no instances: every row is empty
-    else instances_allhits_launch<T>(s, rays_dev, tmax_dev, n, sorted, count_only, h);
-    BVH_HIP(hipStreamSynchronize(st));   // the result is complete when the call returns
-    h->n_rays = n;
-    h->stats.hits = h->total;
+    rows_batch(h, s->ctx, Traits<T>::dtype, TRAVERSE_INST_ALLHITS, BVHGPU_LEAF_TRIANGLE, count_only, n, s->n == 0, name,   // (empty: no instances)
+               [&] { instances_allhits_launch<T>(s, rays_dev, tmax_dev, n, sorted, count_only, h); });
 }
 template void instances_allhits_batch<float>(bvhgpu_instances*, const bvhgpu_ray_f32*, const float*, size_t, unsigned, bvhgpu_hits*);
 template void instances_allhits_batch<double>(bvhgpu_instances*, const bvhgpu_ray_f64*, const double*, size_t, unsigned, bvhgpu_hits*);

@@ -379,11 +379,11 @@ void region_batch(bvhgpu_tree* t, const T* planes_dev, size_t n, uint32_t m, uns
         uint32_t n_trav = (uint32_t)t->n_trav;
         if (mirror) {
             n_trav = (uint32_t)t->n_flat;
-            h->wi_unfold.reserve((size_t)n_trav * sizeof(TravNode<T>));
+            h->unfold.reserve((size_t)n_trav * sizeof(TravNode<T>));
             hipLaunchKernelGGL((k_within_unfold<T>), dim3((n_trav + 255) / 256), dim3(256), 0, st, t->flat.as<typename Traits<T>::Flat>(), n_trav,
-                               h->wi_unfold.as<TravNode<T>>());
+                               h->unfold.as<TravNode<T>>());
             BVH_HIP(hipGetLastError());
-            nodes = h->wi_unfold.as<TravNode<T>>();
+            nodes = h->unfold.as<TravNode<T>>();
         }
         if (unfolded) region_launch<T, true>(t, nodes, n_trav, planes_dev, n, m, classify, count_only, h);
         else region_launch<T, false>(t, nodes, n_trav, planes_dev, n, m, classify, count_only, h);
@@ -458,14 +458,14 @@ void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, 
         h->rg_anc.reserve(n_anc * (1 + REGION_ANC_MAX) * 4);
         h->rg_pairs.reserve(P * 4);
         h->rg_members.reserve(nt * sizeof(RegionMember<T>));
-        if (n_mirror) h->wi_unfold.reserve(n_mirror * sizeof(TravNode<T>));
+        if (n_mirror) h->unfold.reserve(n_mirror * sizeof(TravNode<T>));
         uint32_t* anc_cnt = h->rg_anc.as<uint32_t>();
         uint32_t* anc = anc_cnt + n_anc;
         for (size_t k = 0; k < nt; k++) {
             RegionMember<T>& r = tbl[k];
             if (r.n_chunks == 0) continue;
             if (mirror_at[k] != (size_t)-1) {
-                TravNode<T>* dst = h->wi_unfold.as<TravNode<T>>() + mirror_at[k];
+                TravNode<T>* dst = h->unfold.as<TravNode<T>>() + mirror_at[k];
                 hipLaunchKernelGGL((k_within_unfold<T>), dim3((r.n_trav + 255) / 256), dim3(256), 0, st, s->trees[k]->flat.as<typename Traits<T>::Flat>(), r.n_trav, dst);
                 r.nodes = dst;
             }
@@ -495,10 +495,10 @@ void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, 
                                h->rg_offsets.as<uint32_t>());
             if (!count_only) {
                 h->indices.reserve((size_t)rows.total * 4);
-                h->rg_instance.reserve((size_t)rows.total * 4);
+                h->row_instance.reserve((size_t)rows.total * 4);
                 if (classify) h->rg_inside.reserve((size_t)rows.total);
                 uint32_t* shape = h->indices.as<uint32_t>();
-                uint32_t* inst = h->rg_instance.as<uint32_t>();
+                uint32_t* inst = h->row_instance.as<uint32_t>();
                 if (classify) hipLaunchKernelGGL((k_instances_region_walk<T, true, true>), grid, block, 0, st, members, tree_of, xforms, planes_dev, m, pair_region,
                                                  pair_inst, nc_max, n_units, anc_cnt, anc, unit_offsets, inst, shape, h->rg_inside.as<unsigned char>());
                 else hipLaunchKernelGGL((k_instances_region_walk<T, true, false>), grid, block, 0, st, members, tree_of, xforms, planes_dev, m, pair_region,

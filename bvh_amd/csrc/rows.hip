@@ -1,5 +1,6 @@
-// rows.hip — the five-stage schedule of a batch whose result is one variable-length row per query, as a CSR (rows.hpp; its users are
-// allhits.hip and within.hip).  A family brings two walks, one query per lane, and the sort of its long rows:
+// rows.hip — the five-stage schedule of a batch whose result is one variable-length row per query, as a CSR (rows.hpp, whose rows_run puts
+// the stages in order for allhits.hip, within.hip, instances_allhits.hip and instances_within.hip: DESIGN.md §4h, §4i, §4m, §4n; region.hip's
+// two entries, §4k and §4l, use the scan alone).  A family brings two walks, one query per lane, and the sort of its long rows:
 //   k_<family>_count     counts[q] = the candidates of query q                                   (behind rows_begin)
 //   k_rows_block_sums    64-bit sum per block of ROWS_SCAN_BLOCK counts; the queries of a sorted batch whose rows are longer than the
 //                        family's lane_max are appended to the long-row worklist (any order), those above its lds_max counted
@@ -97,23 +98,23 @@ __global__ __launch_bounds__(256) void k_rows_scan_final(const uint32_t* __restr
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 static uint32_t rows_blocks(size_t n) { return (uint32_t)((n + ROWS_SCAN_BLOCK - 1) / ROWS_SCAN_BLOCK); }
-static unsigned long long* rows_sums(RowsMeta* meta) { return reinterpret_cast<unsigned long long*>(meta + 1); }
+static unsigned long long* sums_of(RowsMeta* meta) { return reinterpret_cast<unsigned long long*>(meta + 1); }
 
 uint32_t* rows_begin(bvhgpu_hits* h, size_t n, bool with_work) {
-    h->ah_counts.reserve(n * 4);
-    h->ah_sums.reserve(sizeof(RowsMeta) + (size_t)rows_blocks(n) * sizeof(unsigned long long));
-    if (with_work) h->ah_work.reserve(n * 4);
-    BVH_HIP(hipMemsetAsync(h->ah_sums.p, 0, sizeof(RowsMeta), h->ctx->stream));
-    return h->ah_counts.as<uint32_t>();
+    h->rows_counts.reserve(n * 4);
+    h->rows_sums.reserve(sizeof(RowsMeta) + (size_t)rows_blocks(n) * sizeof(unsigned long long));
+    if (with_work) h->rows_work.reserve(n * 4);
+    BVH_HIP(hipMemsetAsync(h->rows_sums.p, 0, sizeof(RowsMeta), h->ctx->stream));
+    return h->rows_counts.as<uint32_t>();
 }
 
 RowsTotals rows_scan(bvhgpu_hits* h, size_t n, uint32_t lane_max, uint32_t lds_max) {
     hipStream_t st = h->ctx->stream;
-    RowsMeta* meta = h->ah_sums.as<RowsMeta>();
+    RowsMeta* meta = h->rows_sums.as<RowsMeta>();
     const uint32_t nb = rows_blocks(n);
-    hipLaunchKernelGGL(k_rows_block_sums, dim3(nb), dim3(256), 0, st, h->ah_counts.as<uint32_t>(), (uint32_t)n, rows_sums(meta), meta,
-                       h->ah_work.as<uint32_t>(), lane_max, lds_max);
-    hipLaunchKernelGGL(k_rows_scan_sums, dim3(1), dim3(256), 0, st, rows_sums(meta), nb, meta);
+    hipLaunchKernelGGL(k_rows_block_sums, dim3(nb), dim3(256), 0, st, h->rows_counts.as<uint32_t>(), (uint32_t)n, sums_of(meta), meta,
+                       h->rows_work.as<uint32_t>(), lane_max, lds_max);
+    hipLaunchKernelGGL(k_rows_scan_sums, dim3(1), dim3(256), 0, st, sums_of(meta), nb, meta);
     BVH_HIP(hipGetLastError());
     RowsMeta* got = static_cast<RowsMeta*>(h->ctx->pinned);
     BVH_HIP(hipMemcpyAsync(got, meta, sizeof(RowsMeta), hipMemcpyDeviceToHost, st));
@@ -125,8 +126,8 @@ RowsTotals rows_scan(bvhgpu_hits* h, size_t n, uint32_t lane_max, uint32_t lds_m
 }
 
 void rows_offsets(bvhgpu_hits* h, size_t n) {
-    RowsMeta* meta = h->ah_sums.as<RowsMeta>();
-    hipLaunchKernelGGL(k_rows_scan_final, dim3(rows_blocks(n)), dim3(256), 0, h->ctx->stream, h->ah_counts.as<uint32_t>(), (uint32_t)n, rows_sums(meta),
+    RowsMeta* meta = h->rows_sums.as<RowsMeta>();
+    hipLaunchKernelGGL(k_rows_scan_final, dim3(rows_blocks(n)), dim3(256), 0, h->ctx->stream, h->rows_counts.as<uint32_t>(), (uint32_t)n, sums_of(meta),
                        meta, h->offsets.as<uint32_t>());
 }
 

@@ -203,71 +203,49 @@ static void within_launch(bvhgpu_tree* t, const TravNode<T>* nodes, uint32_t n_t
     const T* tris = t->tris.as<T>();
     const uint32_t n32 = (uint32_t)n;
     const dim3 pgrid((unsigned)((n + 255) / 256)), block(256);
-    const bool rows_sorted = sorted && !count_only;
-    uint32_t* counts = rows_begin(h, n, rows_sorted);
-    uint32_t* offsets = h->offsets.as<uint32_t>();
-    hipLaunchKernelGGL((k_within_count<T, TRIANGLE, UNFOLDED>), pgrid, block, 0, st, nodes, n_trav, aabbs, tris, points_dev, max_dist_dev, n32, counts);
-    const RowsTotals rows = rows_scan(h, n, rows_sorted ? WITHIN_LANE_ROW_MAX : 0u, WITHIN_LDS_ROW_MAX);
-    if (rows.total == 0) return;   // every row is empty
-    rows_offsets(h, n);
-    if (!count_only) {
-        h->indices.reserve((size_t)rows.total * 4);
-        h->ah_vals.reserve((size_t)rows.total * sizeof(T));
-        uint32_t* pos = nullptr;
-        if (rows.n_beyond_lds) { h->ah_pos.reserve((size_t)rows.total * 4); pos = h->ah_pos.as<uint32_t>(); }
-        uint32_t* shape = h->indices.as<uint32_t>();
-        T* dist = h->ah_vals.as<T>();
-        if (sorted) hipLaunchKernelGGL((k_within_fill<T, TRIANGLE, UNFOLDED, true>), pgrid, block, 0, st, nodes, n_trav, aabbs, tris, points_dev, max_dist_dev, n32,
-                                       offsets, shape, dist, pos);
-        else hipLaunchKernelGGL((k_within_fill<T, TRIANGLE, UNFOLDED, false>), pgrid, block, 0, st, nodes, n_trav, aabbs, tris, points_dev, max_dist_dev, n32,
-                                offsets, shape, dist, pos);
-        if (sorted && rows.n_long)
-            hipLaunchKernelGGL((k_within_sort_row<T>), dim3(rows.n_long), dim3(ROWS_SORT_THREADS), 0, st, h->ah_work.as<uint32_t>(), offsets, shape, dist, pos);
-    }
-    BVH_HIP(hipGetLastError());
-    h->total = rows.total;
+    const RowsPlan plan = {sorted, count_only, WITHIN_LANE_ROW_MAX, WITHIN_LDS_ROW_MAX, sizeof(T), false, false};
+    rows_run(h, n, plan,
+             [&](uint32_t* counts) {
+                 hipLaunchKernelGGL((k_within_count<T, TRIANGLE, UNFOLDED>), pgrid, block, 0, st, nodes, n_trav, aabbs, tris, points_dev, max_dist_dev, n32, counts);
+             },
+             [&](const RowsOut& o, auto SORTED) {
+                 hipLaunchKernelGGL((k_within_fill<T, TRIANGLE, UNFOLDED, decltype(SORTED)::value>), pgrid, block, 0, st, nodes, n_trav, aabbs, tris, points_dev,
+                                    max_dist_dev, n32, o.offsets, o.shape, static_cast<T*>(o.vals), o.pos);
+             },
+             [&](const RowsOut& o, uint32_t n_long) {
+                 hipLaunchKernelGGL((k_within_sort_row<T>), dim3(n_long), dim3(ROWS_SORT_THREADS), 0, st, o.work, o.offsets, o.shape, static_cast<T*>(o.vals), o.pos);
+             });
 }
 
 template <typename T>
 void within_batch(bvhgpu_tree* t, const T* points_dev, const T* max_dist_dev, size_t n, int kind, unsigned flags, bvhgpu_hits* h) {
-    bvhgpu_ctx* ctx = t->ctx;
-    hipStream_t st = ctx->stream;
     const bool count_only = (flags & BVHGPU_WITHIN_COUNT_ONLY) != 0;
     const bool sorted = (flags & BVHGPU_WITHIN_LIST_ORDER) == 0;
     const bool mirror = t->exact_only && t->built && !t->unfolded && t->n >= 2;   // (see "Which array is walked" at the top)
     const bool unfolded = t->unfolded || t->n == 1 || mirror;   // a single-shape tree has one (leaf) entry and no navigator
-    // the result object becomes an (empty) within result first: whatever fails below leaves it consistent
-    rows_reset(h, ctx, Traits<T>::dtype, TRAVERSE_WITHIN, 0, count_only);
     char name[112];
     const char* tri = kind == 1 ? "true" : "false";
     const char* unf = unfolded ? "true" : "false";
     if (count_only) std::snprintf(name, sizeof name, "bvhgpu::k_within_count<%s, %s, %s>", walk_type_name<T>(), tri, unf);
     else std::snprintf(name, sizeof name, "bvhgpu::k_within_fill<%s, %s, %s, %s>", walk_type_name<T>(), tri, unf, sorted ? "true" : "false");
-    h->walk_kernel = name;
-    h->offsets.reserve((n + 1) * 4);   // (behind the flags: a reserve that throws leaves an empty within result, never the old kind's flags over a new buffer)
-    BVH_HIP(hipMemsetAsync(h->offsets.p, 0, 4, st));
-    if (n == 0 || t->n == 0) {   // no points, or an empty hierarchy: every row is empty
-        BVH_HIP(hipMemsetAsync(h->offsets.p, 0, (n + 1) * 4, st));
-    } else {
+    rows_batch(h, t->ctx, Traits<T>::dtype, TRAVERSE_WITHIN, 0, count_only, n, t->n == 0, name, [&] {   // (empty: an empty hierarchy)
+        hipStream_t st = t->ctx->stream;
         ensure_flat_arrays(t);
         const TravNode<T>* nodes = t->trav.as<TravNode<T>>();
         uint32_t n_trav = (uint32_t)t->n_trav;
         if (mirror) {
             n_trav = (uint32_t)t->n_flat;
-            h->wi_unfold.reserve((size_t)n_trav * sizeof(TravNode<T>));
+            h->unfold.reserve((size_t)n_trav * sizeof(TravNode<T>));
             hipLaunchKernelGGL((k_within_unfold<T>), dim3((n_trav + 255) / 256), dim3(256), 0, st, t->flat.as<typename Traits<T>::Flat>(), n_trav,
-                               h->wi_unfold.as<TravNode<T>>());
+                               h->unfold.as<TravNode<T>>());
             BVH_HIP(hipGetLastError());
-            nodes = h->wi_unfold.as<TravNode<T>>();
+            nodes = h->unfold.as<TravNode<T>>();
         }
         if (kind == 1) { if (unfolded) within_launch<T, true, true>(t, nodes, n_trav, points_dev, max_dist_dev, n, sorted, count_only, h);
                          else within_launch<T, true, false>(t, nodes, n_trav, points_dev, max_dist_dev, n, sorted, count_only, h); }
         else { if (unfolded) within_launch<T, false, true>(t, nodes, n_trav, points_dev, max_dist_dev, n, sorted, count_only, h);
                else within_launch<T, false, false>(t, nodes, n_trav, points_dev, max_dist_dev, n, sorted, count_only, h); }
-    }
-    BVH_HIP(hipStreamSynchronize(st));   // the result is complete when the call returns
-    h->n_rays = n;
-    h->stats.hits = h->total;
+    });
 }
 template void within_batch<float>(bvhgpu_tree*, const float*, const float*, size_t, int, unsigned, bvhgpu_hits*);
 template void within_batch<double>(bvhgpu_tree*, const double*, const double*, size_t, int, unsigned, bvhgpu_hits*);

@@ -36,6 +36,7 @@ INSTANCES_ALLHITS_COUNT_ONLY = 2   # BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY: offset
 INSTANCES_WITHIN_LIST_ORDER = 1    # BVHGPU_INSTANCES_WITHIN_LIST_ORDER: rows in the double order instead of sorted by distance
 INSTANCES_WITHIN_COUNT_ONLY = 2    # BVHGPU_INSTANCES_WITHIN_COUNT_ONLY: offsets and total only
 INSTANCES_KNN_MAX_K = 64   # BVHGPU_INSTANCES_KNN_MAX_K: largest k of bvhgpu_instances_knearest_*
+INSTANCES_KHITS_MAX_K = 64   # BVHGPU_INSTANCES_KHITS_MAX_K: largest k of bvhgpu_instances_khits_*
 TRAVERSE_T_SLICE = 1
 TRAVERSE_STATS = 2
 TRAVERSE_TRIANGLES = 4
@@ -206,6 +207,8 @@ SYMBOLS = [
     ("bvhgpu_hits_fetch_instances_within", _i, [_vp, _vp, _vp, _vp, _vp, _i]),
     ("bvhgpu_instances_knearest_f32", _i, [_vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp]),
     ("bvhgpu_instances_knearest_f64", _i, [_vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp]),
+    ("bvhgpu_instances_khits_f32", _i, [_vp, _vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp]),
+    ("bvhgpu_instances_khits_f64", _i, [_vp, _vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp]),
     ("bvhgpu_instances_boxes", _i, [_vp, _vp, _i]),
     ("bvhgpu_instances_info", _i, [_vp, C.POINTER(_i), C.POINTER(_sz), C.POINTER(_sz)]),
     ("bvhgpu_instances_destroy", None, [_vp]),

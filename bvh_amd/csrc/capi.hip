@@ -1260,6 +1260,42 @@ int do_instances_knearest(bvhgpu_instances* s, const T* points, size_t n, int me
     });
 }
 
+// do_instances_trace's rules and staging with do_instances_knearest's k: one layout (rays | tmax | vals | instance | shape), no result
+// object, synchronous.  A refused call touches no buffer and leaves the set as it was.
+template <typename T>
+int do_instances_khits(bvhgpu_instances* s, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, uint32_t k, uint32_t* out_instance,
+                       uint32_t* out_shape, T* out_vals) {
+    using Ray = typename Traits<T>::Ray;
+    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    bvhgpu_ctx* ctx = s->ctx;
+    if (k == 0 || k > BVHGPU_INSTANCES_KHITS_MAX_K) return fail(ctx, BVHGPU_INVALID_ARG, "k must be between 1 and BVHGPU_INSTANCES_KHITS_MAX_K");
+    if (n && (!rays || !out_instance || !out_shape || !out_vals)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from ray dtype");
+    { const int rc = instances_current(s); if (rc != BVHGPU_OK) return rc; }
+    if (n >= 0xFFFFFFFFull || n * (size_t)k >= 0x100000000ull) return fail(ctx, BVHGPU_OVERFLOW, "too many results (rays x k) in one call");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        const Ray* rd = rays; const T* td = tmax; T* vd = out_vals; uint32_t *id = out_instance, *sd = out_shape;
+        const size_t rb = n * sizeof(Ray), tb = tmax ? n * sizeof(T) : 0, vb = n * k * 3 * sizeof(T), ib = n * k * 4;
+        if (mem == BVHGPU_HOST) {
+            ctx->upload.reserve(rb + tb + vb + 2 * ib + 64);
+            char* base = ctx->upload.as<char>();
+            if (rb) BVH_HIP(hipMemcpyAsync(base, rays, rb, hipMemcpyHostToDevice, ctx->stream));
+            if (tb) BVH_HIP(hipMemcpyAsync(base + rb, tmax, tb, hipMemcpyHostToDevice, ctx->stream));
+            rd = reinterpret_cast<const Ray*>(base); td = tb ? reinterpret_cast<const T*>(base + rb) : nullptr;
+            vd = reinterpret_cast<T*>(base + rb + tb); id = reinterpret_cast<uint32_t*>(base + rb + tb + vb); sd = reinterpret_cast<uint32_t*>(base + rb + tb + vb + ib);
+        }
+        instances_khits_batch<T>(s, rd, n ? td : nullptr, n, k, id, sd, vd);
+        if (mem == BVHGPU_HOST) {
+            copy_out(ctx, out_vals, vd, vb, BVHGPU_HOST); copy_out(ctx, out_instance, id, ib, BVHGPU_HOST); copy_out(ctx, out_shape, sd, ib, BVHGPU_HOST);
+        } else {
+            BVH_HIP(hipStreamSynchronize(ctx->stream));   // the rows are complete when the call returns, whichever stream reads them next
+        }
+        return (int)BVHGPU_OK;
+    });
+}
+
 }  // namespace
 
 namespace bvhgpu {
@@ -2070,6 +2106,14 @@ int bvhgpu_instances_knearest_f32(bvhgpu_instances* s, const float* points, size
 int bvhgpu_instances_knearest_f64(bvhgpu_instances* s, const double* points, size_t n, int mem, uint32_t k, uint32_t* out_instance, uint32_t* out_shape,
                                   double* out_dist) {
     return do_instances_knearest<double>(s, points, n, mem, k, out_instance, out_shape, out_dist);
+}
+int bvhgpu_instances_khits_f32(bvhgpu_instances* s, const bvhgpu_ray_f32* rays, const float* tmax, size_t n_rays, int mem, uint32_t k,
+                               uint32_t* out_instance, uint32_t* out_shape, float* out_vals) {
+    return do_instances_khits<float>(s, rays, tmax, n_rays, mem, k, out_instance, out_shape, out_vals);
+}
+int bvhgpu_instances_khits_f64(bvhgpu_instances* s, const bvhgpu_ray_f64* rays, const double* tmax, size_t n_rays, int mem, uint32_t k,
+                               uint32_t* out_instance, uint32_t* out_shape, double* out_vals) {
+    return do_instances_khits<double>(s, rays, tmax, n_rays, mem, k, out_instance, out_shape, out_vals);
 }
 int bvhgpu_instances_boxes(bvhgpu_instances* s, void* out, int mem) {
     if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");

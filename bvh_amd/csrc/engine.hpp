@@ -467,6 +467,11 @@ void instances_within_batch(bvhgpu_instances* s, const T* points_dev, const T* m
 template <typename T>
 void instances_knearest_batch(bvhgpu_instances* s, const T* points_dev, size_t n, uint32_t k, uint32_t* out_instance_dev, uint32_t* out_shape_dev,
                               T* out_dist_dev);
+// instances_khits.hip: the k nearest hits per ray over a committed instance set (bvhgpu_instances_khits_*); tmax_dev: NULL or n segment ends;
+// out_instance / out_shape: n x k, out_vals: n x k x 3; a set without instances fills them with padding.  Enqueued on the ctx's stream.
+template <typename T>
+void instances_khits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, uint32_t k,
+                           uint32_t* out_instance_dev, uint32_t* out_shape_dev, T* out_vals_dev);
 // rays.hip
 template <typename T>
 void ray_triangle_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays_dev, const T* tris_dev, size_t n, T* out_dev);

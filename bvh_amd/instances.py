@@ -197,6 +197,36 @@ class Instances(_Typed):
             return dict(offsets=offsets)
         return dict(offsets=offsets, instance=instance, shape=shape, vals=vals)
 
+    def khits_batch(self, rays: RayBatch, k: int, tmax=None):
+        """bvhgpu_instances_khits_*: per ray the k nearest (instance, shape) hits with distance < tmax[i] (None: +inf), ascending by
+        distance — the head of allhits_batch(sort=True)'s row, byte for byte, in fixed-width rows and one walk.  Equal distances stay in
+        walk order (instances in the top level's order, shapes in the member's order), and a tie at the k-th distance keeps the pairs met
+        first; k = 1 is closest_hits.  1 <= k <= _lib.INSTANCES_KHITS_MAX_K.
+        returns (instance[n, k], shape[n, k], vals[n, k, 3] = {distance, u, v}); slots beyond the number of hits hold NONE, NONE and
+        (+inf, 0, 0).  HOST rays: numpy out, indices as uint32.  Rays in HBM: torch tensors on the same device, written by the kernel,
+        indices as torch.int32 — so NONE reads as -1 there."""
+        if rays.sfx != self.sfx:
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from the instance set's dtype")
+        k = int(k)
+        rows = k if 1 <= k <= _lib.INSTANCES_KHITS_MAX_K else 0   # (out of range: the engine answers INVALID_ARG before it touches a buffer)
+        _keep, tp = api._side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
+        n = rays.n
+        if rays.mem == DEVICE:
+            import torch
+            dev = rays.device.device
+            inst = torch.empty((n, rows), dtype=torch.int32, device=dev)
+            shape = torch.empty((n, rows), dtype=torch.int32, device=dev)
+            vals = torch.empty((n, rows, 3), dtype=api._torch_ft(self.ft), device=dev)
+            api._torch_sync(dev)
+            ip, sp, vp = ptr(inst.data_ptr()), ptr(shape.data_ptr()), ptr(vals.data_ptr())
+        else:
+            inst, shape = np.zeros((n, rows), dtype=np.uint32), np.zeros((n, rows), dtype=np.uint32)
+            vals = np.zeros((n, rows, 3), dtype=self.ft)
+            ip, sp, vp = ptr(inst), ptr(shape), ptr(vals)
+        fn = getattr(_lib.load(), f"bvhgpu_instances_khits_{self.sfx}")
+        check(fn(self._s, rays._ptr(), tp, n, rays.mem, k & 0xFFFFFFFF, ip, sp, vp), self.ctx._h)
+        return inst, shape, vals
+
     def within_batch(self, points, max_dist, sort: bool = True, count_only: bool = False) -> dict:
         """bvhgpu_instances_within_*: per point EVERY (instance, shape) whose world-space triangle lies within max_dist[i] of it (<=, the
         limit itself is inside; a negative or NaN limit gives an empty row, +inf keeps every pair whose distance is not NaN), as a CSR.

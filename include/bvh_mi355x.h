@@ -1016,6 +1016,40 @@ int bvhgpu_instances_knearest_f32(bvhgpu_instances *s, const float *points, size
 int bvhgpu_instances_knearest_f64(bvhgpu_instances *s, const double *points, size_t n, int mem, uint32_t k,
                                   uint32_t *out_instance, uint32_t *out_shape, double *out_dist);
 
+/* ---- multi-hit ray queries over an instanced scene: the k nearest hits of every ray, in order, in fixed-width padded rows — depth
+ * peeling, transparency with a known layer budget, LiDAR multi-return, picking through a front surface — without flattening the scene
+ * and without fetching bvhgpu_instances_allhits_*'s whole CSR and cutting every row on the host.  bvhgpu_traverse_khits_* over the
+ * committed set of bvhgpu_instances_trace_*.  All arithmetic is in the set's dtype T; every operation is rounded once, in the order written.
+ *  - Candidates.  Ray j meets the pairs (instance, shape) in the double order of bvhgpu_instances_trace_*: the instances in the top level's
+ *    list order, within each the shapes in the member's list order.  The record {distance, u, v} of a pair comes from the object-frame
+ *    ray against the member's triangle, exactly as bvhgpu_instances_trace_* and bvhgpu_instances_allhits_* compute it.  A pair is a
+ *    candidate iff distance < tmax[j], strict, in T.  A NULL tmax means +inf for every ray.  A miss (+inf), or a NaN, zero or negative
+ *    tmax, admits nothing.
+ *  - Row j.  The candidates in a stable ascending sort by distance, cut to the first k.  Equal distances stay in the double order; a tie
+ *    at the k-th distance keeps the pairs met first.
+ *  - Padding.  Slots beyond the number of candidates hold BVHGPU_NONE, BVHGPU_NONE and {+inf, 0, 0}.
+ *  - Consequences.  Row j in front of its padding is the first min(k, len) entries of row j of bvhgpu_instances_allhits_* in its default
+ *    (sorted) order, byte for byte.  At k = 1 the row is bvhgpu_instances_trace_*'s closest hit.  Over one identity instance the shape
+ *    and vals columns equal bvhgpu_traverse_khits_* with BVHGPU_LEAF_TRIANGLE on the member.
+ *  - Incremental form, which the kernel runs: bvhgpu_traverse_khits_*'s list with the strict < of T.  While the list is not full every
+ *    candidate enters.  A full list accepts d iff d < L[k-1] and drops L[k-1].  An accepted d goes in front of the first element e with
+ *    d < e, else to the end.  A candidate's distance is never NaN (it passed a strict <), so rows are always sorted.
+ *  - No pruning.  The walk visits the whole double order, as trace and all-hits do.
+ *  - A set without instances, or whose top level is empty, gives rows that are all padding.  n_rays = 0 is fine (NULL buffers too).
+ * out_instance[j*k + m], out_shape[j*k + m] and out_vals[(j*k + m)*3 ..] are slot m of row j.  `mem` covers `rays`, `tmax` and the three
+ * outputs; HOST input is staged.  The call runs on the context's stream and returns when the rows are complete; there is no result object.
+ * 1 <= k <= BVHGPU_INSTANCES_KHITS_MAX_K: the lists of a workgroup live in LDS, k x (sizeof(T) + 8) bytes a lane.
+ * Refused on the host before anything is launched, touching no buffer and leaving the set as it was, the first broken rule in this
+ * order: a NULL set; k = 0 or k > BVHGPU_INSTANCES_KHITS_MAX_K; a NULL `rays` or output with n_rays > 0; a `mem` that is neither
+ * BVHGPU_HOST nor BVHGPU_DEVICE; a set of another dtype (BVHGPU_DTYPE_MISMATCH); an uncommitted set; a stale set (the check and the
+ * message of bvhgpu_instances_trace_*: "instances are stale"); n_rays >= 2^32 - 1 or n_rays * k >= 2^32 (BVHGPU_OVERFLOW).  Everything
+ * not marked is BVHGPU_INVALID_ARG. */
+#define BVHGPU_INSTANCES_KHITS_MAX_K 64u /* 64 lanes x 64 slots x (8 + 4 + 4) bytes = 64 KB of LDS in f64 */
+int bvhgpu_instances_khits_f32(bvhgpu_instances *s, const bvhgpu_ray_f32 *rays, const float *tmax, size_t n_rays, int mem, uint32_t k,
+                               uint32_t *out_instance /* n x k */, uint32_t *out_shape /* n x k */, float *out_vals /* n x k x 3 */);
+int bvhgpu_instances_khits_f64(bvhgpu_instances *s, const bvhgpu_ray_f64 *rays, const double *tmax, size_t n_rays, int mem, uint32_t k,
+                               uint32_t *out_instance /* n x k */, uint32_t *out_shape /* n x k */, double *out_vals /* n x k x 3 */);
+
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */
 typedef struct { float build_ms, flatten_ms, traverse_kernel_ms, traverse_total_ms; } bvhgpu_timings;

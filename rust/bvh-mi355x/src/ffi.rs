@@ -7,6 +7,7 @@ pub const BVHGPU_ABI_VERSION: c_int = 7;
 pub const BVHGPU_NONE: u32 = u32::MAX; // flat_bvh.rs:51-53
 pub const BVHGPU_KNN_MAX_K: u32 = 64; // largest k of bvhgpu_knearest_*
 pub const BVHGPU_INSTANCES_KNN_MAX_K: u32 = 64; // largest k of bvhgpu_instances_knearest_*
+pub const BVHGPU_INSTANCES_KHITS_MAX_K: u32 = 64; // largest k of bvhgpu_instances_khits_*
 pub const BVHGPU_KHITS_MAX_K: u32 = 64; // largest k of bvhgpu_traverse_khits_*
 pub const BVHGPU_ALLHITS_LIST_ORDER: c_uint = 1; // bvhgpu_traverse_allhits_*: rows in list order, no sort pass
 pub const BVHGPU_WITHIN_LIST_ORDER: c_uint = 1; // bvhgpu_within_*: rows in the order the loop met the candidates, no sort pass
@@ -245,6 +246,9 @@ extern "C" {
     // the k nearest (instance, shape) pairs per point over an instance set (out_*: n x k; padding = BVHGPU_NONE / BVHGPU_NONE / +inf; 1 <= k <= BVHGPU_INSTANCES_KNN_MAX_K; synchronous, no result object)
     pub fn bvhgpu_instances_knearest_f32(s: *mut bvhgpu_instances, points: *const f32, n: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_dist: *mut f32) -> c_int;
     pub fn bvhgpu_instances_knearest_f64(s: *mut bvhgpu_instances, points: *const f64, n: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_dist: *mut f64) -> c_int;
+    // the k nearest hits per ray over an instance set (out_instance / out_shape: n_rays x k, out_vals: n_rays x k x 3; padding = BVHGPU_NONE / BVHGPU_NONE / {+inf, 0, 0}; 1 <= k <= BVHGPU_INSTANCES_KHITS_MAX_K; synchronous, no result object)
+    pub fn bvhgpu_instances_khits_f32(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_vals: *mut f32) -> c_int;
+    pub fn bvhgpu_instances_khits_f64(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_vals: *mut f64) -> c_int;
     pub fn bvhgpu_instances_boxes(s: *mut bvhgpu_instances, out: *mut c_void, mem: c_int) -> c_int;
     pub fn bvhgpu_instances_info(s: *const bvhgpu_instances, dtype: *mut c_int, n_trees: *mut usize, n_instances: *mut usize) -> c_int;
     pub fn bvhgpu_instances_destroy(s: *mut bvhgpu_instances);

@@ -1027,6 +1027,34 @@ impl<T: GpuScalar> GpuInstances<T> {
         }
         (instance, shape, dist)
     }
+
+    /// Per ray the `k` nearest `(instance, shape)` hits with `distance < tmax[j]` (`None`: `+inf`), ascending (`bvhgpu_instances_khits_*`):
+    /// the head of `allhits`' sorted row, byte for byte, without the CSR.  Returns row-major `rays.len() x k` arrays `(instance, shape)` and
+    /// `rays.len() x k x 3` `vals` = `{distance, u, v}`; equal distances stay in walk order (instances in the top level's order, shapes in
+    /// the member's order) and a tie at the k-th distance keeps the pairs met first; slots beyond the number of hits hold `u32::MAX`,
+    /// `u32::MAX` and `{+inf, 0, 0}`.  `1 <= k <= ffi::BVHGPU_INSTANCES_KHITS_MAX_K`; `k = 1` is `closest_hits`.
+    pub fn khits(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>, k: usize) -> (Vec<u32>, Vec<u32>, Vec<T>) {
+        if let Some(m) = tmax {
+            assert_eq!(m.len(), rays.len(), "tmax needs one value per ray");
+        }
+        let raw: Vec<T::RayC> = rays.iter().map(T::ray_to_ffi).collect();
+        let n = raw.len();
+        let k32 = u32::try_from(k).unwrap_or(u32::MAX);   // (out of range: the engine answers BVHGPU_INVALID_ARG and `check` panics with its message)
+        let slots = if (1..=ffi::BVHGPU_INSTANCES_KHITS_MAX_K).contains(&k32) { n * k } else { 0 };
+        let (mut instance, mut shape, mut vals) = (vec![0u32; slots], vec![0u32; slots], vec![T::default(); 3 * slots]);
+        unsafe {
+            let tp = tmax.map_or(core::ptr::null(), |m| m.as_ptr());
+            let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_khits_f32(self.set, raw.as_ptr().cast(), tp.cast(), n, ffi::BVHGPU_HOST, k32, instance.as_mut_ptr(),
+                                                shape.as_mut_ptr(), vals.as_mut_ptr().cast())
+            } else {
+                ffi::bvhgpu_instances_khits_f64(self.set, raw.as_ptr().cast(), tp.cast(), n, ffi::BVHGPU_HOST, k32, instance.as_mut_ptr(),
+                                                shape.as_mut_ptr(), vals.as_mut_ptr().cast())
+            };
+            check(self.ctx, rc);
+        }
+        (instance, shape, vals)
+    }
 }
 
 impl<T: GpuScalar> Drop for GpuInstances<T> {

@@ -119,6 +119,36 @@ def _rows_in(x, width: int, ft, what: str, check_tensor: bool = True, convert: b
     return a, ptr(a), a.size // width, HOST
 
 
+def _out_cols(device, ft, *cols):
+    """The one way output arrays are made: one per column (shape, "index" | "float" | "byte").  device None: numpy arrays (uint32 / `ft` /
+    uint8).  Else torch tensors on that device (int32 — so NONE reads as -1 — / `ft` / uint8), and torch's stream is waited for: the engine
+    writes them on its own.  → (the arrays, their c_void_p's)"""
+    if device is None:
+        arrs = [np.zeros(shape, dtype={"index": np.uint32, "float": ft, "byte": np.uint8}[kind]) for shape, kind in cols]
+        return arrs, [ptr(a) for a in arrs]
+    import torch
+    dtypes = {"index": torch.int32, "float": _torch_ft(ft), "byte": torch.uint8}
+    arrs = [torch.empty(shape, dtype=dtypes[kind], device=device) for shape, kind in cols]
+    _torch_sync(device)
+    return arrs, [ptr(a.data_ptr()) for a in arrs]
+
+
+def _fetch_csr(entry: str, hits: "_Hits", n: int, rows: int, ft, device, *cols):
+    """The one way a CSR leaves a result object: bvhgpu_hits_fetch_<entry> of the completed batch in `hits` → [offsets[n+1], one array per
+    column].  A column is (shape, kind) as for _out_cols, or None for one this batch does not have: the engine gets NULL and the caller
+    None.  With no rows the engine gets NULL for every column.  device None: copied to the host, offsets as uint32.  Else device-to-device
+    copies into torch tensors there, and the offsets are widened to torch.int64 on the device."""
+    arrs, ptrs = _out_cols(device, ft, (n + 1, "index"), *[c for c in cols if c is not None])
+    made = iter(zip(arrs[1:], ptrs[1:]))
+    got = [next(made) if c is not None else (None, None) for c in cols]
+    fn = getattr(_lib.load(), f"bvhgpu_hits_fetch_{entry}")
+    check(fn(hits.h, ptrs[0], *[p if rows else None for _, p in got], HOST if device is None else DEVICE), hits.ctx._h)
+    if device is not None:
+        import torch
+        arrs[0] = arrs[0].to(torch.int64) & 0xFFFFFFFF
+    return [arrs[0]] + [a for a, _ in got]
+
+
 def _bytes_in(x):
     """a scene blob's buffer as it is, a torch GPU tensor or a numpy array → (its c_void_p, DEVICE or HOST)"""
     return (ptr(x.data_ptr()), DEVICE) if _is_device_tensor(x) else (ptr(x), HOST)
@@ -581,24 +611,8 @@ class _Hits:
         return offsets, indices
 
     def _fetch_rows(self, entry: str, n: int, rows: int, vshape, dtype, device):
-        """bvhgpu_hits_fetch_<entry> of a CSR-rows batch: (offsets[n+1], shape[rows], vals[vshape]).  device None: copied to the host, offsets
-        and shape as uint32.  device: torch tensors there, filled by device-to-device copies — shape as torch.int32, offsets widened to
-        torch.int64 on the device.  With no rows the engine gets NULL for shape and vals."""
-        fn = getattr(_lib.load(), f"bvhgpu_hits_fetch_{entry}")
-        if device is not None:
-            import torch
-            off32 = torch.empty(n + 1, dtype=torch.int32, device=device)
-            shape = torch.empty(rows, dtype=torch.int32, device=device)
-            vals = torch.empty(vshape, dtype=_torch_ft(dtype), device=device)
-            _torch_sync(device)
-            check(fn(self.h, ptr(off32.data_ptr()), ptr(shape.data_ptr()) if rows else None, ptr(vals.data_ptr()) if rows else None, DEVICE),
-                  self.ctx._h)
-            return off32.to(torch.int64) & 0xFFFFFFFF, shape, vals
-        offsets = np.zeros(n + 1, dtype=np.uint32)
-        shape = np.zeros(rows, dtype=np.uint32)
-        vals = np.zeros(vshape, dtype=dtype)
-        check(fn(self.h, ptr(offsets), ptr(shape) if rows else None, ptr(vals) if rows else None, HOST), self.ctx._h)
-        return offsets, shape, vals
+        """bvhgpu_hits_fetch_<entry> of a CSR-rows batch: (offsets[n+1], shape[rows], vals[vshape]), as _fetch_csr hands them over"""
+        return tuple(_fetch_csr(entry, self, n, rows, dtype, device, (rows, "index"), (vshape, "float")))
 
     def fetch_allhits(self, n_rays: int, leaf: str = "box", dtype=np.float32, device=None):
         """all-hits batches (bvhgpu_hits_fetch_allhits): (offsets[n+1], shape[total], vals[total, W]) of the completed batch.  device None:
@@ -817,16 +831,9 @@ class _TreeBase(_Typed):
         return _lib.LEAF_KINDS[leaf], rays.device.device if rays.mem == DEVICE else None
 
     def _alloc_out(self, device, ishape, fshape):
-        """the (shape, values) outputs a kernel writes in place → (shape, values, their two pointers).  device None: numpy, shape as uint32;
-        else torch tensors there, shape as torch.int32, and torch's stream is waited for."""
-        if device is None:
-            shape, vals = np.zeros(ishape, dtype=np.uint32), np.zeros(fshape, dtype=self.ft)
-            return shape, vals, ptr(shape), ptr(vals)
-        import torch
-        shape = torch.empty(ishape, dtype=torch.int32, device=device)
-        vals = torch.empty(fshape, dtype=_torch_ft(self.ft), device=device)
-        _torch_sync(device)
-        return shape, vals, ptr(shape.data_ptr()), ptr(vals.data_ptr())
+        """the (shape, values) outputs a kernel writes in place → (shape, values, their two pointers), as _out_cols makes them"""
+        (shape, vals), (sp, vp) = _out_cols(device, self.ft, (ishape, "index"), (fshape, "float"))
+        return shape, vals, sp, vp
 
     def khits_batch(self, rays: RayBatch, k: int, leaf: str = "box", tmax=None):
         """bvhgpu_traverse_khits_*: the k nearest hits of every ray.  Row i is the candidates of FlatBvh::traverse's list (flat_bvh.rs:396-431)

@@ -2,6 +2,7 @@
 // Every entry point catches everything, records a message on the ctx and returns a status code.
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 
 #include "engine.hpp"
@@ -51,6 +52,69 @@ template <typename F> int guarded(bvhgpu_ctx* ctx, F&& f) {
 
 void use_device(bvhgpu_ctx* ctx) { BVH_HIP(hipSetDevice(ctx->device)); }
 
+// ---- named rules ------------------------------------------------------------------------------------------------------------------------
+// Each refusal that more than one family gives, worded once: BVHGPU_OK (0) or the status, with the message recorded.  A front end is a
+// flat list of `if (const int rc = rule_...) return rc;` lines in ITS OWN order — which refusal wins when two apply is interface and
+// differs between the families on purpose; what is shared is what a rule says.  A new family lists the rules it needs and adds none.
+static_assert(BVHGPU_OK == 0, "a rule's status is tested as a truth value");
+int rule_mem(bvhgpu_ctx* ctx, int mem) {
+    return mem == BVHGPU_HOST || mem == BVHGPU_DEVICE ? (int)BVHGPU_OK : fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+}
+int rule_hits_arg(bvhgpu_ctx* ctx, bvhgpu_hits* const* hits) { return hits ? (int)BVHGPU_OK : fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL"); }
+int rule_hits_idle(bvhgpu_ctx* ctx, bvhgpu_hits* const* hits) {   // the result object a batch is about to fill
+    return *hits && (*hits)->pend_async ? fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first") : (int)BVHGPU_OK;
+}
+int rule_hits_complete(const bvhgpu_hits* h) {                    // the result object an accessor is about to read
+    return h->pend_async ? fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first") : (int)BVHGPU_OK;
+}
+int rule_batch_size(bvhgpu_ctx* ctx, size_t n, const char* plural) {   // offsets and NONE are u32
+    return n >= 0xFFFFFFFFull ? fail(ctx, BVHGPU_OVERFLOW, std::string("more than 2^32-2 ") + plural + " in one batch") : (int)BVHGPU_OK;
+}
+int rule_rows_size(bvhgpu_ctx* ctx, size_t n, uint32_t k, const char* msg) {   // n padded rows of k slots
+    return n >= 0xFFFFFFFFull || n * (size_t)k >= 0x100000000ull ? fail(ctx, BVHGPU_OVERFLOW, msg) : (int)BVHGPU_OK;
+}
+int rule_k(bvhgpu_ctx* ctx, uint32_t k, uint32_t max_k, const char* max_name) {
+    return k == 0 || k > max_k ? fail(ctx, BVHGPU_INVALID_ARG, std::string("k must be between 1 and ") + max_name) : (int)BVHGPU_OK;
+}
+int rule_flattened(const bvhgpu_tree* t) { return t->flattened ? (int)BVHGPU_OK : fail(t->ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first"); }
+int rule_leaf(bvhgpu_ctx* ctx, int leaf) {
+    return leaf == BVHGPU_LEAF_BOX || leaf == BVHGPU_LEAF_TRIANGLE || leaf == BVHGPU_LEAF_SPHERE
+               ? (int)BVHGPU_OK : fail(ctx, BVHGPU_INVALID_ARG, "leaf must be BVHGPU_LEAF_BOX, BVHGPU_LEAF_TRIANGLE or BVHGPU_LEAF_SPHERE");
+}
+int rule_leaf_array(const bvhgpu_tree* t, int leaf) {   // the per-shape array the leaf kind reads
+    if (leaf == BVHGPU_LEAF_TRIANGLE && !t->has_tris) return fail(t->ctx, BVHGPU_INVALID_ARG, "triangle hits need bvhgpu_tree_set_triangles first");
+    if (leaf == BVHGPU_LEAF_SPHERE && !t->has_spheres) return fail(t->ctx, BVHGPU_INVALID_ARG, "sphere hits need bvhgpu_tree_set_spheres first");
+    return BVHGPU_OK;
+}
+int rule_shape_kind(bvhgpu_ctx* ctx, int kind) {
+    return kind == 0 || kind == 1 ? (int)BVHGPU_OK : fail(ctx, BVHGPU_INVALID_ARG, "shape kind must be 0 (AABB) or 1 (triangle)");
+}
+int rule_kind_array(const bvhgpu_tree* t, int kind) {
+    return kind == 1 && !t->has_tris ? fail(t->ctx, BVHGPU_INVALID_ARG, "triangle distance needs bvhgpu_tree_set_triangles first") : (int)BVHGPU_OK;
+}
+// a walk that tests the leaves' navigator boxes cannot run on an imported tree that lost them — nor on a set with such a member
+bool folded_away(const bvhgpu_tree* t) { return t->exact_only && !t->built && !t->unfolded; }
+int rule_unfolded(const bvhgpu_tree* t) {
+    return folded_away(t) ? fail(t->ctx, BVHGPU_INVALID_ARG, "an imported tree whose build had a split without SAH winner: its leaves' navigator boxes were folded away") : (int)BVHGPU_OK;
+}
+int rule_members_unfolded(const bvhgpu_instances* s) {
+    for (const bvhgpu_tree* t : s->trees)
+        if (folded_away(t)) return fail(s->ctx, BVHGPU_INVALID_ARG, "an imported member tree whose build had a split without SAH winner: its leaves' navigator boxes were folded away");
+    return BVHGPU_OK;
+}
+int rule_planes(bvhgpu_ctx* ctx, const void* planes, size_t n, uint32_t m) {   // n regions of m planes
+    if (m > BVHGPU_REGION_MAX_PLANES) return fail(ctx, BVHGPU_INVALID_ARG, "more than BVHGPU_REGION_MAX_PLANES planes per region");
+    return n && m && !planes ? fail(ctx, BVHGPU_INVALID_ARG, "planes is NULL") : (int)BVHGPU_OK;
+}
+int no_tree() { return fail(nullptr, BVHGPU_INVALID_ARG, "NULL tree"); }
+int no_set() { return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set"); }
+template <typename T> int rule_tree_dtype(const bvhgpu_tree* t, const char* noun) {
+    return t->dtype != Traits<T>::dtype ? fail(t->ctx, BVHGPU_DTYPE_MISMATCH, std::string("tree dtype differs from ") + noun + " dtype") : (int)BVHGPU_OK;
+}
+template <typename T> int rule_set_dtype(const bvhgpu_instances* s, const char* noun) {
+    return s->dtype != Traits<T>::dtype ? fail(s->ctx, BVHGPU_DTYPE_MISMATCH, std::string("instance set dtype differs from ") + noun + " dtype") : (int)BVHGPU_OK;
+}
+
 // bring a caller buffer to HBM: returns a device pointer (either the caller's or the ctx staging copy)
 const void* to_device(bvhgpu_ctx* ctx, const void* p, size_t bytes, int mem, DevBuf& stage) {
     if (mem == BVHGPU_DEVICE || bytes == 0) return p;
@@ -65,6 +129,35 @@ void copy_out(bvhgpu_ctx* ctx, void* dst, const void* src_dev, size_t bytes, int
                            ctx->stream));
     BVH_HIP(hipStreamSynchronize(ctx->stream));
 }
+
+// ---- the row stage: inputs and outputs of a synchronous padded-row call (bvhgpu_nearest_* / _knearest* / _traverse_khits_* and the
+// bvhgpu_instances_trace / _knearest / _khits entries) -----------------------------------------------------------------------------------
+// The caller lists its input and output columns as (pointer, bytes); at<U>(i) is column i's device pointer, inputs first.  DEVICE: the
+// caller's own pointers.  HOST: every column gets a 16-byte-aligned place in ctx->upload (so each is aligned to its element, whatever the
+// order) and the inputs are copied in; a NULL column (no tmax, no max_dist) stays NULL.  finish() copies each HOST output out with its own
+// wait, or — DEVICE, where the family promises complete rows on return — waits for the stream.  A new padded-row family is a column list.
+struct Span { const void* p; size_t bytes; };
+class RowStage {
+    static constexpr size_t MAX_COLS = 6;
+    bvhgpu_ctx* ctx_; bool host_; size_t n_in_, n_ = 0;
+    Span col_[MAX_COLS]; void* dev_[MAX_COLS];
+  public:
+    RowStage(bvhgpu_ctx* ctx, int mem, std::initializer_list<Span> in, std::initializer_list<Span> out) : ctx_(ctx), host_(mem == BVHGPU_HOST), n_in_(in.size()) {
+        for (const Span& s : in) col_[n_++] = s;
+        for (const Span& s : out) col_[n_++] = s;
+        size_t off[MAX_COLS], need = 0;
+        for (size_t i = 0; i < n_; i++) { off[i] = need; need += (col_[i].bytes + 15) & ~(size_t)15; }
+        if (host_) ctx->upload.reserve(need + 64);
+        for (size_t i = 0; i < n_; i++) dev_[i] = !host_ ? const_cast<void*>(col_[i].p) : col_[i].p ? ctx->upload.as<char>() + off[i] : nullptr;
+        for (size_t i = 0; host_ && i < n_in_; i++)
+            if (col_[i].p && col_[i].bytes) BVH_HIP(hipMemcpyAsync(dev_[i], col_[i].p, col_[i].bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    template <typename U> U* at(size_t i) const { return static_cast<U*>(dev_[i]); }
+    void finish(bool sync_device) {
+        for (size_t i = n_in_; host_ && i < n_; i++) copy_out(ctx_, const_cast<void*>(col_[i].p), dev_[i], col_[i].bytes, BVHGPU_HOST);
+        if (!host_ && sync_device) BVH_HIP(hipStreamSynchronize(ctx_->stream));
+    }
+};
 
 // an asynchronous build may still be in flight: wait for it and finish / validate it (build.hip build_finalize); likewise a
 // broadcast that was received on the stream (comm.hip recv_finalize: its status header tells whether the root's tree was good)
@@ -262,7 +355,7 @@ static HitsKind hits_kind(const bvhgpu_hits* h) {
 // kind is refused with one message, which names the accessor that does read it.  copies: the accessor copies out of HBM, so it needs the ctx.
 static int hits_expect(const bvhgpu_hits* h, bool copies, HitsKind want, HitsKind also) {
     if (!h || (copies && !h->ctx)) return BVHGPU_INVALID_ARG;
-    if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (const int rc = rule_hits_complete(h)) return rc;
     const HitsKindRow& have = hits_row(hits_kind(h));
     if (have.kind == want || have.kind == also) return BVHGPU_OK;
     const std::string none = want == HitsKind::Closest ? std::string("traverse was run without BVHGPU_TRAVERSE_CLOSEST")
@@ -277,19 +370,17 @@ static int hits_expect(const bvhgpu_hits* h, bool copies, HitsKind want) { retur
 // which refusal a caller gets when two apply is part of the interface.
 int batch_open(bvhgpu_tree* tree, bvhgpu_hits** hits) {
     if (!tree) return BVHGPU_INVALID_ARG;
-    if (!hits) return fail(tree->ctx, BVHGPU_INVALID_ARG, "hits is NULL");
-    return BVHGPU_OK;
+    return rule_hits_arg(tree->ctx, hits);
 }
 // the refusals every family shares, in the order every family reports them (input_missing: the family's own test of its input pointer)
 template <typename T>
 int batch_refusal(bvhgpu_tree* tree, bvhgpu_hits* const* hits, const char* noun, const char* plural, bool input_missing, const char* missing_msg, size_t n) {
     bvhgpu_ctx* ctx = tree->ctx;
-    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
-    if (tree->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, std::string("tree dtype differs from ") + noun + " dtype");
-    if (!tree->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    if (const int rc = rule_hits_idle(ctx, hits)) return rc;
+    if (const int rc = rule_tree_dtype<T>(tree, noun)) return rc;
+    if (const int rc = rule_flattened(tree)) return rc;
     if (input_missing) return fail(ctx, BVHGPU_INVALID_ARG, missing_msg);
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, std::string("more than 2^32-2 ") + plural + " in one batch");
-    return BVHGPU_OK;
+    return rule_batch_size(ctx, n, plural);
 }
 // the caller's result object, made if there is none yet
 bvhgpu_hits* batch_hits(bvhgpu_hits** hits) {
@@ -299,26 +390,36 @@ bvhgpu_hits* batch_hits(bvhgpu_hits** hits) {
     h->pend_kind = 0; h->pend_queries = nullptr; h->pend_qwide = false;   // (the object may have held a query batch)
     return h;
 }
-// per-ray segment ends of an any-hit / box batch.  tmax == NULL: +inf for every ray.  HOST tmax is staged into the result object, so that
-// a replay (wide-walk stack overflow) reads it again.
+// ---- what a result-object family stages in the result object ----------------------------------------------------------------------------
+// The per-row side array (tmax of rays, max_dist of points) → its device pointer.  NULL stays NULL (+inf for every ray), DEVICE is used in
+// place, HOST values go into h->tmaxbuf.  The rows families (all-hits, within and their instanced forms) pass the pointer on and keep none.
+template <typename T> const T* stage_side(bvhgpu_ctx* ctx, bvhgpu_hits* h, const T* v, size_t n, int mem) {
+    if (!v || !n || mem != BVHGPU_HOST) return v;
+    h->tmaxbuf.reserve(n * sizeof(T));
+    BVH_HIP(hipMemcpyAsync(h->tmaxbuf.p, v, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    return h->tmaxbuf.as<T>();
+}
+// ... of an any-hit / box / sphere batch: kept in the result object, so that a replay (wide-walk stack overflow) reads it again
 template <typename T> void stage_tmax(bvhgpu_ctx* ctx, bvhgpu_hits* h, const T* tmax, size_t n_rays, int mem) {
-    const T* tmax_dev = tmax;
-    if (tmax && n_rays && mem == BVHGPU_HOST) {
-        h->tmaxbuf.reserve(n_rays * sizeof(T));
-        BVH_HIP(hipMemcpyAsync(h->tmaxbuf.p, tmax, n_rays * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-        tmax_dev = h->tmaxbuf.as<T>();
-    }
-    h->pend_tmax = tmax_dev;
+    h->pend_tmax = stage_side<T>(ctx, h, tmax, n_rays, mem);
+}
+// The main input of the families whose input is not rays or points (queries, planes) → its device pointer; HOST values go into h->qbuf
+// (a replay of a query batch reads them again).
+template <typename T> const T* stage_queries(bvhgpu_ctx* ctx, bvhgpu_hits* h, const T* q, size_t bytes, int mem) {
+    if (mem != BVHGPU_HOST || !bytes) return q;
+    h->qbuf.reserve(bytes);
+    BVH_HIP(hipMemcpyAsync(h->qbuf.p, q, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return h->qbuf.as<T>();
 }
 
 template <typename T>
 int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n_rays, int mem, unsigned flags,
                 bvhgpu_hits** hits, bool async = false) {
-    { const int rc = batch_open(tree, hits); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = batch_open(tree, hits)) return rc;
     bvhgpu_ctx* ctx = tree->ctx;
-    if (!async) { const int rc = settle(tree); if (rc != BVHGPU_OK) return rc; }
+    if (!async) { if (const int rc = settle(tree)) return rc; }
     else if (mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "asynchronous traversal takes rays that are resident in HBM");
-    { const int rc = batch_refusal<T>(tree, hits, "ray", "rays", n_rays && !rays, "rays is NULL", n_rays); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = batch_refusal<T>(tree, hits, "ray", "rays", n_rays && !rays, "rays is NULL", n_rays)) return rc;
     if ((flags & (BVHGPU_TRAVERSE_TRIANGLES | BVHGPU_TRAVERSE_CLOSEST)) && !tree->has_tris)
         return fail(ctx, BVHGPU_INVALID_ARG, "TRIANGLES / CLOSEST need bvhgpu_tree_set_triangles first");
     if ((flags & BVHGPU_TRAVERSE_T_SLICE) && (flags & (BVHGPU_TRAVERSE_TRIANGLES | BVHGPU_TRAVERSE_CLOSEST)))
@@ -362,12 +463,12 @@ int do_traverse(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, size_t n
 template <typename T>
 int do_traverse_tmax(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, const T* tmax, size_t n_rays, int mem, unsigned flags, bvhgpu_hits** hits,
                      unsigned allowed_flags, const char* flags_msg, unsigned kind_bit, const char* needs_msg) {   // needs_msg: the refusal when the kind's per-shape array (sphere hit: the spheres, else the triangles) is not set; NULL: none needed
-    { const int rc = batch_open(tree, hits); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = batch_open(tree, hits)) return rc;
     bvhgpu_ctx* ctx = tree->ctx;
     if (flags & ~allowed_flags) return fail(ctx, BVHGPU_INVALID_ARG, flags_msg);
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    { const int rc = settle(tree); if (rc != BVHGPU_OK) return rc; }
-    { const int rc = batch_refusal<T>(tree, hits, "ray", "rays", n_rays && !rays, "rays is NULL", n_rays); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = settle(tree)) return rc;
+    if (const int rc = batch_refusal<T>(tree, hits, "ray", "rays", n_rays && !rays, "rays is NULL", n_rays)) return rc;
     if (needs_msg && !(kind_bit == TRAVERSE_SPHERE_HIT ? tree->has_spheres : tree->has_tris)) return fail(ctx, BVHGPU_INVALID_ARG, needs_msg);
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -399,27 +500,21 @@ int do_traverse_sphere(bvhgpu_tree* tree, const typename Traits<T>::Ray* rays, c
 // bvhgpu_query_*: an AABB / point / ball batch (query.hip).  queries == NULL: the tree's own shape AABBs (self-overlap).
 template <typename T>
 int do_query(bvhgpu_tree* tree, int kind, const T* queries, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
-    { const int rc = batch_open(tree, hits); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = batch_open(tree, hits)) return rc;
     bvhgpu_ctx* ctx = tree->ctx;
     if (kind != BVHGPU_QUERY_AABB && kind != BVHGPU_QUERY_POINT && kind != BVHGPU_QUERY_BALL) return fail(ctx, BVHGPU_INVALID_ARG, "unknown query kind");
     if (flags != 0) return fail(ctx, BVHGPU_INVALID_ARG, "query flags are reserved (0)");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    { const int rc = settle(tree); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = settle(tree)) return rc;
     const bool self = queries == nullptr;
     { const int rc = batch_refusal<T>(tree, hits, "query", "queries", self && !(kind == BVHGPU_QUERY_AABB && n == tree->n),
                                       "queries is NULL: only BVHGPU_QUERY_AABB with n = the tree's shape count (self-overlap)", n); if (rc != BVHGPU_OK) return rc; }
-    if (tree->exact_only && !tree->built && !tree->unfolded)
-        return fail(ctx, BVHGPU_INVALID_ARG, "an imported tree whose build had a split without SAH winner: its leaves' navigator boxes were folded away");
+    if (const int rc = rule_unfolded(tree)) return rc;
     const size_t per = kind == BVHGPU_QUERY_AABB ? 6 : (kind == BVHGPU_QUERY_POINT ? 3 : 4);
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
-        const T* dev = self ? tree->aabbs.as<T>() : queries;
-        if (!self && mem == BVHGPU_HOST && n) {   // staged into the result object: a replay reads them again
-            h->qbuf.reserve(n * per * sizeof(T));
-            BVH_HIP(hipMemcpyAsync(h->qbuf.p, queries, n * per * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-            dev = h->qbuf.as<T>();
-        }
+        const T* dev = self ? tree->aabbs.as<T>() : stage_queries<T>(ctx, h, queries, n * per * sizeof(T), mem);
         query_batch<T>(tree, kind, dev, n, h);
         return (int)BVHGPU_OK;
     });
@@ -578,187 +673,145 @@ int do_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays, const T* tris
 }
 
 // ---- point batches: bvhgpu_nearest_* / bvhgpu_knearest_* / bvhgpu_knearest_tree_* --------------------------------------------------
-// One set of rules and one staging layout (points | max_dist | dist | shape); bvhgpu_nearest_* is k = 1 without limits, and only the
+// One set of rules and one row stage (points, max_dist → dist, shape); bvhgpu_nearest_* is k = 1 without limits, and only the
 // nearest-first descent takes max_dist.  That descent reads the BvhNode array (a tree built here, flattened or not); the other two walks
-// read the flattened arrays.
+// read the flattened arrays.  (A NULL tree is refused without a message here and with one by the later families: kept as it is.)
 enum class PointWalk { Nearest, KNearest, KNearestTree };
 template <typename T>
 int do_points(bvhgpu_tree* t, PointWalk walk, const T* points, size_t n, int mem, int kind, uint32_t k, const T* max_dist, uint32_t* out_shape, T* out_dist) {
     if (!t) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = t->ctx;
-    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
-    if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from point dtype");
+    if (const int rc = settle(t)) return rc;
+    if (const int rc = rule_tree_dtype<T>(t, "point")) return rc;
     if (walk == PointWalk::KNearestTree) {
         if (!t->built) return fail(ctx, BVHGPU_INVALID_ARG, "the nearest-first descent needs a tree that was built here (uploaded and imported trees carry no BvhNode array)");
-    } else if (!t->flattened) {
-        return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    } else if (const int rc = rule_flattened(t)) {
+        return rc;
     }
-    if (k == 0 || k > BVHGPU_KNN_MAX_K) return fail(ctx, BVHGPU_INVALID_ARG, "k must be between 1 and BVHGPU_KNN_MAX_K");
+    if (const int rc = rule_k(ctx, k, BVHGPU_KNN_MAX_K, "BVHGPU_KNN_MAX_K")) return rc;
     if (n && (!points || !out_shape || !out_dist)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
-    if (kind != 0 && kind != 1) return fail(ctx, BVHGPU_INVALID_ARG, "shape kind must be 0 (AABB) or 1 (triangle)");
-    if (kind == 1 && !t->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "triangle distance needs bvhgpu_tree_set_triangles first");
-    if (n >= 0xFFFFFFFFull || n * (size_t)k >= 0x100000000ull)
-        return fail(ctx, BVHGPU_OVERFLOW, walk == PointWalk::Nearest ? "too many points in one call" : "too many results (points x k) in one call");
+    if (const int rc = rule_shape_kind(ctx, kind)) return rc;
+    if (const int rc = rule_kind_array(t, kind)) return rc;
+    if (const int rc = rule_rows_size(ctx, n, k, walk == PointWalk::Nearest ? "too many points in one call" : "too many results (points x k) in one call")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
-        const T* pd = points; const T* md = max_dist; uint32_t* sd = out_shape; T* dd = out_dist;
-        const size_t pb = n * 3 * sizeof(T), mb = max_dist ? n * sizeof(T) : 0, sb = n * k * 4, db = n * k * sizeof(T);
-        if (mem == BVHGPU_HOST) {
-            ctx->upload.reserve(pb + mb + sb + db + 64);
-            char* base = ctx->upload.as<char>();
-            if (pb) BVH_HIP(hipMemcpyAsync(base, points, pb, hipMemcpyHostToDevice, ctx->stream));
-            if (mb) BVH_HIP(hipMemcpyAsync(base + pb, max_dist, mb, hipMemcpyHostToDevice, ctx->stream));
-            pd = reinterpret_cast<const T*>(base); md = max_dist ? reinterpret_cast<const T*>(base + pb) : nullptr;
-            dd = reinterpret_cast<T*>(base + pb + mb); sd = reinterpret_cast<uint32_t*>(base + pb + mb + db);
-        }
-        if (walk == PointWalk::KNearestTree) knearest_tree_batch<T>(t, pd, n, kind, k, md, sd, dd);
+        RowStage st(ctx, mem, {{points, n * 3 * sizeof(T)}, {max_dist, n * sizeof(T)}}, {{out_dist, n * k * sizeof(T)}, {out_shape, n * k * 4}});
+        const T* pd = st.at<const T>(0); T* dd = st.at<T>(2); uint32_t* sd = st.at<uint32_t>(3);
+        if (walk == PointWalk::KNearestTree) knearest_tree_batch<T>(t, pd, n, kind, k, st.at<const T>(1), sd, dd);
         else if (walk == PointWalk::KNearest) knearest_batch<T>(t, pd, n, kind, k, sd, dd);
         else if (t->n == 0) {   // empty hierarchy → None for every query (flat_bvh.rs:518-520)
             if (n) { BVH_HIP(hipMemsetAsync(sd, 0xFF, n * 4, ctx->stream)); BVH_HIP(hipMemsetAsync(dd, 0, n * sizeof(T), ctx->stream)); }
         } else {
             nearest_batch<T>(t, pd, n, kind, sd, dd);
         }
-        if (mem == BVHGPU_HOST) { copy_out(ctx, out_dist, dd, db, BVHGPU_HOST); copy_out(ctx, out_shape, sd, sb, BVHGPU_HOST); }
-        else if (walk != PointWalk::Nearest) BVH_HIP(hipStreamSynchronize(ctx->stream));   // k-nearest: the rows are complete when the call returns, whichever stream reads them next
+        st.finish(walk != PointWalk::Nearest);   // k-nearest in HBM: the rows are complete when the call returns, whichever stream reads them next
         return (int)BVHGPU_OK;
     });
 }
 
 // ---- multi-hit ray batches: bvhgpu_traverse_khits_* ----------------------------------------------------------------------------------
-// do_points' rules, order and staging for rays: one layout (rays | tmax | vals | shape), synchronous, and a refused call touches no buffer.
+// do_points' rules and order for rays, on the row stage (rays, tmax → vals, shape); synchronous, and a refused call touches no buffer.
 template <typename T>
 int do_khits(bvhgpu_tree* t, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, int leaf, uint32_t k, uint32_t* out_shape, T* out_vals) {
     using Ray = typename Traits<T>::Ray;
-    if (!t) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL tree");
+    if (!t) return no_tree();
     bvhgpu_ctx* ctx = t->ctx;
-    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
-    if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from ray dtype");
-    if (!t->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
-    if (k == 0 || k > BVHGPU_KHITS_MAX_K) return fail(ctx, BVHGPU_INVALID_ARG, "k must be between 1 and BVHGPU_KHITS_MAX_K");
+    if (const int rc = settle(t)) return rc;
+    if (const int rc = rule_tree_dtype<T>(t, "ray")) return rc;
+    if (const int rc = rule_flattened(t)) return rc;
+    if (const int rc = rule_k(ctx, k, BVHGPU_KHITS_MAX_K, "BVHGPU_KHITS_MAX_K")) return rc;
     if (n && (!rays || !out_shape || !out_vals)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if (leaf != BVHGPU_LEAF_BOX && leaf != BVHGPU_LEAF_TRIANGLE && leaf != BVHGPU_LEAF_SPHERE)
-        return fail(ctx, BVHGPU_INVALID_ARG, "leaf must be BVHGPU_LEAF_BOX, BVHGPU_LEAF_TRIANGLE or BVHGPU_LEAF_SPHERE");
-    if (leaf == BVHGPU_LEAF_TRIANGLE && !t->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "triangle hits need bvhgpu_tree_set_triangles first");
-    if (leaf == BVHGPU_LEAF_SPHERE && !t->has_spheres) return fail(ctx, BVHGPU_INVALID_ARG, "sphere hits need bvhgpu_tree_set_spheres first");
-    if (n >= 0xFFFFFFFFull || n * (size_t)k >= 0x100000000ull) return fail(ctx, BVHGPU_OVERFLOW, "too many results (rays x k) in one call");
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = rule_leaf(ctx, leaf)) return rc;
+    if (const int rc = rule_leaf_array(t, leaf)) return rc;
+    if (const int rc = rule_rows_size(ctx, n, k, "too many results (rays x k) in one call")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
-        const Ray* rd = rays; const T* td = tmax; uint32_t* sd = out_shape; T* vd = out_vals;
         const size_t w = leaf == BVHGPU_LEAF_TRIANGLE ? 3 : 2;
-        const size_t rb = n * sizeof(Ray), tb = tmax ? n * sizeof(T) : 0, vb = n * k * w * sizeof(T), sb = n * k * 4;
-        if (mem == BVHGPU_HOST) {
-            ctx->upload.reserve(rb + tb + vb + sb + 64);
-            char* base = ctx->upload.as<char>();
-            if (rb) BVH_HIP(hipMemcpyAsync(base, rays, rb, hipMemcpyHostToDevice, ctx->stream));
-            if (tb) BVH_HIP(hipMemcpyAsync(base + rb, tmax, tb, hipMemcpyHostToDevice, ctx->stream));
-            rd = reinterpret_cast<const Ray*>(base); td = tb ? reinterpret_cast<const T*>(base + rb) : nullptr;
-            vd = reinterpret_cast<T*>(base + rb + tb); sd = reinterpret_cast<uint32_t*>(base + rb + tb + vb);
-        }
-        khits_batch<T>(t, rd, n ? td : nullptr, n, leaf, k, sd, vd);
-        if (mem == BVHGPU_HOST) { copy_out(ctx, out_vals, vd, vb, BVHGPU_HOST); copy_out(ctx, out_shape, sd, sb, BVHGPU_HOST); }
-        else BVH_HIP(hipStreamSynchronize(ctx->stream));   // the rows are complete when the call returns, whichever stream reads them next
+        RowStage st(ctx, mem, {{rays, n * sizeof(Ray)}, {tmax, n * sizeof(T)}}, {{out_vals, n * k * w * sizeof(T)}, {out_shape, n * k * 4}});
+        khits_batch<T>(t, st.at<const Ray>(0), n ? st.at<const T>(1) : nullptr, n, leaf, k, st.at<uint32_t>(3), st.at<T>(2));
+        st.finish(true);   // in HBM too the rows are complete when the call returns, whichever stream reads them next
         return (int)BVHGPU_OK;
     });
 }
 
-// ---- all-hits ray batches: bvhgpu_traverse_allhits_* ----------------------------------------------------------------------------------
-// do_khits' rules and order; the result goes to a result object (allhits.hip), whose buffers a later batch of any kind reuses.  A refused
-// call touches no buffer and leaves *hits as it was.
+// ---- the rows families on a tree: bvhgpu_traverse_allhits_* / bvhgpu_within_* / bvhgpu_region_* -------------------------------------------
+// Each is its own rule list (the later ones were written in the earlier one's order, with their own inputs and flags), then: the main
+// input to HBM, the side array or the planes staged in the result object (stage_side / stage_queries), the family's batch (allhits.hip,
+// within.hip, region.hip).  The result goes to a result object, whose buffers a later batch of any kind reuses.  A refused call touches no
+// buffer and leaves *hits as it was.  (batch_open / batch_refusal do not fit: these families name a NULL tree, and they size the batch last.)
 template <typename T>
 int do_allhits(bvhgpu_tree* t, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, int leaf, unsigned flags, bvhgpu_hits** hits) {
     using Ray = typename Traits<T>::Ray;
-    if (!t) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL tree");
+    if (!t) return no_tree();
     bvhgpu_ctx* ctx = t->ctx;
-    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
-    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
-    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
-    if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from ray dtype");
-    if (!t->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    if (const int rc = rule_hits_arg(ctx, hits)) return rc;
+    if (const int rc = settle(t)) return rc;
+    if (const int rc = rule_hits_idle(ctx, hits)) return rc;
+    if (const int rc = rule_tree_dtype<T>(t, "ray")) return rc;
+    if (const int rc = rule_flattened(t)) return rc;
     if (n && !rays) return fail(ctx, BVHGPU_INVALID_ARG, "rays is NULL");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if (leaf != BVHGPU_LEAF_BOX && leaf != BVHGPU_LEAF_TRIANGLE && leaf != BVHGPU_LEAF_SPHERE)
-        return fail(ctx, BVHGPU_INVALID_ARG, "leaf must be BVHGPU_LEAF_BOX, BVHGPU_LEAF_TRIANGLE or BVHGPU_LEAF_SPHERE");
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = rule_leaf(ctx, leaf)) return rc;
     if (flags & ~BVHGPU_ALLHITS_LIST_ORDER) return fail(ctx, BVHGPU_INVALID_ARG, "all-hits flags: 0 or BVHGPU_ALLHITS_LIST_ORDER");
-    if (leaf == BVHGPU_LEAF_TRIANGLE && !t->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "triangle hits need bvhgpu_tree_set_triangles first");
-    if (leaf == BVHGPU_LEAF_SPHERE && !t->has_spheres) return fail(ctx, BVHGPU_INVALID_ARG, "sphere hits need bvhgpu_tree_set_spheres first");
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 rays in one batch");
+    if (const int rc = rule_leaf_array(t, leaf)) return rc;
+    if (const int rc = rule_batch_size(ctx, n, "rays")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
         const auto* dev = static_cast<const Ray*>(to_device(ctx, rays, n * sizeof(Ray), mem, ctx->upload));
-        stage_tmax<T>(ctx, h, tmax, n, mem);   // (a HOST tmax is staged as the box and sphere batches stage it)
-        const T* td = n ? static_cast<const T*>(h->pend_tmax) : nullptr;
-        h->pend_tmax = nullptr;                // (nothing replays this batch)
+        const T* td = n ? stage_side<T>(ctx, h, tmax, n, mem) : nullptr;
         allhits_batch<T>(t, dev, td, n, leaf, flags, h);
         return (int)BVHGPU_OK;
     });
 }
 
-// ---- radius-search point batches: bvhgpu_within_* ---------------------------------------------------------------------------------------
-// do_allhits' shape with points and limits in place of rays and tmax; the result goes to a result object (within.hip), whose buffers a
-// later batch of any kind reuses.  A refused call touches no buffer and leaves *hits as it was.
 template <typename T>
 int do_within(bvhgpu_tree* t, const T* points, const T* max_dist, size_t n, int mem, int kind, unsigned flags, bvhgpu_hits** hits) {
-    if (!t) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL tree");
+    if (!t) return no_tree();
     bvhgpu_ctx* ctx = t->ctx;
-    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
-    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
-    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
-    if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from point dtype");
-    if (!t->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
+    if (const int rc = rule_hits_arg(ctx, hits)) return rc;
+    if (const int rc = settle(t)) return rc;
+    if (const int rc = rule_hits_idle(ctx, hits)) return rc;
+    if (const int rc = rule_tree_dtype<T>(t, "point")) return rc;
+    if (const int rc = rule_flattened(t)) return rc;
     if (n && !points) return fail(ctx, BVHGPU_INVALID_ARG, "points is NULL");
     if (n && !max_dist) return fail(ctx, BVHGPU_INVALID_ARG, "max_dist is NULL");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if (kind != 0 && kind != 1) return fail(ctx, BVHGPU_INVALID_ARG, "shape kind must be 0 (AABB) or 1 (triangle)");
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = rule_shape_kind(ctx, kind)) return rc;
     if (flags & ~(BVHGPU_WITHIN_LIST_ORDER | BVHGPU_WITHIN_COUNT_ONLY))
         return fail(ctx, BVHGPU_INVALID_ARG, "within flags: BVHGPU_WITHIN_LIST_ORDER and BVHGPU_WITHIN_COUNT_ONLY only");
-    if (kind == 1 && !t->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "triangle distance needs bvhgpu_tree_set_triangles first");
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 points in one batch");
+    if (const int rc = rule_kind_array(t, kind)) return rc;
+    if (const int rc = rule_batch_size(ctx, n, "points")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
         const auto* dev = static_cast<const T*>(to_device(ctx, points, n * 3 * sizeof(T), mem, ctx->upload));
-        stage_tmax<T>(ctx, h, max_dist, n, mem);   // (HOST limits are staged as do_allhits stages tmax)
-        const T* md = n ? static_cast<const T*>(h->pend_tmax) : nullptr;
-        h->pend_tmax = nullptr;                    // (nothing replays this batch)
+        const T* md = n ? stage_side<T>(ctx, h, max_dist, n, mem) : nullptr;
         within_batch<T>(t, dev, md, n, kind, flags, h);
         return (int)BVHGPU_OK;
     });
 }
 
-// ---- convex-region (plane-set) batches: bvhgpu_region_* ----------------------------------------------------------------------------------
-// do_within's shape with n x m planes in place of points and limits; the result goes to a result object (region.hip), whose buffers a
-// later batch of any kind reuses.  HOST planes are staged into the result object like host queries.  A refused call touches no buffer
-// and leaves *hits as it was.
 template <typename T>
 int do_region(bvhgpu_tree* t, const T* planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits** hits) {
-    if (!t) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL tree");
+    if (!t) return no_tree();
     bvhgpu_ctx* ctx = t->ctx;
-    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
-    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
-    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
-    if (t->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "tree dtype differs from plane dtype");
-    if (!t->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
-    if (m > BVHGPU_REGION_MAX_PLANES) return fail(ctx, BVHGPU_INVALID_ARG, "more than BVHGPU_REGION_MAX_PLANES planes per region");
-    if (n && m && !planes) return fail(ctx, BVHGPU_INVALID_ARG, "planes is NULL");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (const int rc = rule_hits_arg(ctx, hits)) return rc;
+    if (const int rc = settle(t)) return rc;
+    if (const int rc = rule_hits_idle(ctx, hits)) return rc;
+    if (const int rc = rule_tree_dtype<T>(t, "plane")) return rc;
+    if (const int rc = rule_flattened(t)) return rc;
+    if (const int rc = rule_planes(ctx, planes, n, m)) return rc;
+    if (const int rc = rule_mem(ctx, mem)) return rc;
     if (flags & ~(BVHGPU_REGION_COUNT_ONLY | BVHGPU_REGION_CLASSIFY))
         return fail(ctx, BVHGPU_INVALID_ARG, "region flags: BVHGPU_REGION_COUNT_ONLY and BVHGPU_REGION_CLASSIFY only");
-    if (t->exact_only && !t->built && !t->unfolded)
-        return fail(ctx, BVHGPU_INVALID_ARG, "an imported tree whose build had a split without SAH winner: its leaves' navigator boxes were folded away");
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 regions in one batch");
+    if (const int rc = rule_unfolded(t)) return rc;
+    if (const int rc = rule_batch_size(ctx, n, "regions")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
-        const T* dev = planes;
-        const size_t bytes = n * m * 4 * sizeof(T);
-        if (mem == BVHGPU_HOST && bytes) {
-            h->qbuf.reserve(bytes);
-            BVH_HIP(hipMemcpyAsync(h->qbuf.p, planes, bytes, hipMemcpyHostToDevice, ctx->stream));
-            dev = h->qbuf.as<T>();
-        }
-        region_batch<T>(t, dev, n, m, flags, h);
+        region_batch<T>(t, stage_queries<T>(ctx, h, planes, n * m * 4 * sizeof(T), mem), n, m, flags, h);
         return (int)BVHGPU_OK;
     });
 }
@@ -1014,7 +1067,7 @@ template <typename T> int instances_members_ok(bvhgpu_ctx* ctx, bvhgpu_tree* con
         if (trees[k]->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "member tree dtype differs from the instance set's");
     for (size_t k = 0; k < n_trees; k++)
         if (trees[k]->ctx != ctx) return fail(ctx, BVHGPU_INVALID_ARG, "member tree belongs to another context");
-    for (size_t k = 0; k < n_trees; k++) { const int rc = settle(trees[k]); if (rc != BVHGPU_OK) return rc; }
+    for (size_t k = 0; k < n_trees; k++) if (const int rc = settle(trees[k])) return rc;
     for (size_t k = 0; k < n_trees; k++)
         if (!trees[k]->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "member tree is not flattened: call bvhgpu_flatten first");
     for (size_t k = 0; k < n_trees; k++)
@@ -1038,8 +1091,8 @@ int do_instances_create(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_tre
     if (!ctx || !out) return fail(ctx, BVHGPU_INVALID_ARG, "ctx/out is NULL");
     *out = nullptr;
     if ((n_trees && !trees) || (n && (!tree_of || !xforms))) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    { const int rc = instances_members_ok<T>(ctx, trees, n_trees); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = instances_members_ok<T>(ctx, trees, n_trees)) return rc;
     if (n > MAX_SHAPES || n_trees >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "too many instances for u32 flat indices");
     bvhgpu_instances* s = nullptr;
     const int rc = guarded(ctx, [&] {
@@ -1071,227 +1124,162 @@ int do_instances_create(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_tre
     return BVHGPU_OK;
 }
 template <typename T> int do_instances_update(bvhgpu_instances* s, const T* xforms, size_t n, int mem) {
-    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
     if (n && !xforms) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from transform dtype");
-    { const int rc = instances_members_ok<T>(ctx, s->trees.data(), s->trees.size()); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = rule_set_dtype<T>(s, "transform")) return rc;
+    if (const int rc = instances_members_ok<T>(ctx, s->trees.data(), s->trees.size())) return rc;
     if (n != s->n) return fail(ctx, BVHGPU_INVALID_ARG, "update: the number of instances differs from the set's");
     const int rc = guarded(ctx, [&] { use_device(ctx); instances_pose<T>(s, xforms, mem); return (int)BVHGPU_OK; });
     if (rc != BVHGPU_OK) (void)hipStreamSynchronize(ctx->stream);   // (the set stays uncommitted: instances_pose cleared the mark first)
     return rc;
 }
 // what every batch over a set asks before anything is launched: a committed pose, and members that are still what the commit read
+int rule_committed(const bvhgpu_instances* s) {
+    return s->committed ? (int)BVHGPU_OK : fail(s->ctx, BVHGPU_INVALID_ARG, "instances are not committed (the last commit failed): call bvhgpu_instances_update");
+}
 int instances_current(bvhgpu_instances* s) {
-    bvhgpu_ctx* ctx = s->ctx;
-    if (!s->committed) return fail(ctx, BVHGPU_INVALID_ARG, "instances are not committed (the last commit failed): call bvhgpu_instances_update");
+    if (const int rc = rule_committed(s)) return rc;
     for (size_t k = 0; k < s->trees.size(); k++) {   // what the commit read of every member must still be what the member holds
         const bvhgpu_tree* t = s->trees[k];
         const bvhgpu_instances::Seen& c = s->seen[k];
         if (t->trav.p != c.trav || t->aabbs.p != c.aabbs || t->tris.p != c.tris || t->n != c.n || t->n_trav != c.n_trav || t->gen != c.gen ||
             !t->flattened || !t->has_tris || t->pending_build || t->pending_recv)
-            return fail(ctx, BVHGPU_INVALID_ARG, "instances are stale: call bvhgpu_instances_update");
+            return fail(s->ctx, BVHGPU_INVALID_ARG, "instances are stale: call bvhgpu_instances_update");
     }
     return BVHGPU_OK;
 }
-// do_khits' staging for rays: one layout (rays | tmax | vals | instance | shape), synchronous, and a refused call touches no buffer
+// ---- batches over an instance set ---------------------------------------------------------------------------------------------------------
+// The padded-row entries (trace, knearest, khits: the row stage, no result object, synchronous) and the rows entries (region, allhits,
+// within: a result object, staged as their tree forms stage).  Every rule list ends with the commit and staleness rules, the refusal of an
+// imported member whose navigator boxes were folded away where the walk tests them, and the batch size; the k entries test k first.  A
+// refused call touches no buffer and leaves *hits and the set as they were.
 template <typename T>
 int do_instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, unsigned flags, T* out_vals,
                        uint32_t* out_instance, uint32_t* out_shape) {
     using Ray = typename Traits<T>::Ray;
-    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
     if (n && (!rays || !out_vals || !out_instance || !out_shape)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from ray dtype");
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = rule_set_dtype<T>(s, "ray")) return rc;
     if (flags & ~BVHGPU_TRAVERSE_FIRST) return fail(ctx, BVHGPU_INVALID_ARG, "instance trace flags: 0 or BVHGPU_TRAVERSE_FIRST");
-    { const int rc = instances_current(s); if (rc != BVHGPU_OK) return rc; }
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 rays in one batch");
+    if (const int rc = instances_current(s)) return rc;
+    if (const int rc = rule_batch_size(ctx, n, "rays")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
-        const Ray* rd = rays; const T* td = tmax; T* vd = out_vals; uint32_t *id = out_instance, *sd = out_shape;
-        const size_t rb = n * sizeof(Ray), tb = tmax ? n * sizeof(T) : 0, vb = n * 3 * sizeof(T), ib = n * 4;
-        if (mem == BVHGPU_HOST) {
-            ctx->upload.reserve(rb + tb + vb + 2 * ib + 64);
-            char* base = ctx->upload.as<char>();
-            if (rb) BVH_HIP(hipMemcpyAsync(base, rays, rb, hipMemcpyHostToDevice, ctx->stream));
-            if (tb) BVH_HIP(hipMemcpyAsync(base + rb, tmax, tb, hipMemcpyHostToDevice, ctx->stream));
-            rd = reinterpret_cast<const Ray*>(base); td = tb ? reinterpret_cast<const T*>(base + rb) : nullptr;
-            vd = reinterpret_cast<T*>(base + rb + tb); id = reinterpret_cast<uint32_t*>(base + rb + tb + vb); sd = id + n;
-        }
-        instances_trace<T>(s, rd, n ? td : nullptr, n, (flags & BVHGPU_TRAVERSE_FIRST) != 0, vd, id, sd);
-        if (mem == BVHGPU_HOST) {
-            copy_out(ctx, out_vals, vd, vb, BVHGPU_HOST); copy_out(ctx, out_instance, id, ib, BVHGPU_HOST); copy_out(ctx, out_shape, sd, ib, BVHGPU_HOST);
-        } else {
-            BVH_HIP(hipStreamSynchronize(ctx->stream));   // the rows are complete when the call returns, whichever stream reads them next
-        }
+        RowStage st(ctx, mem, {{rays, n * sizeof(Ray)}, {tmax, n * sizeof(T)}}, {{out_vals, n * 3 * sizeof(T)}, {out_instance, n * 4}, {out_shape, n * 4}});
+        instances_trace<T>(s, st.at<const Ray>(0), n ? st.at<const T>(1) : nullptr, n, (flags & BVHGPU_TRAVERSE_FIRST) != 0, st.at<T>(2), st.at<uint32_t>(3), st.at<uint32_t>(4));
+        st.finish(true);   // in HBM too the rows are complete when the call returns, whichever stream reads them next
         return (int)BVHGPU_OK;
     });
 }
-// do_region's shape over an instance set, behind do_instances_trace's commit and staleness rules.  HOST planes are staged in the result
-// object.  A refused call touches no buffer and leaves *hits as it was.
 template <typename T>
 int do_instances_region(bvhgpu_instances* s, const T* planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits** hits) {
-    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
-    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
-    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
-    if (m > BVHGPU_REGION_MAX_PLANES) return fail(ctx, BVHGPU_INVALID_ARG, "more than BVHGPU_REGION_MAX_PLANES planes per region");
-    if (n && m && !planes) return fail(ctx, BVHGPU_INVALID_ARG, "planes is NULL");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from plane dtype");
+    if (const int rc = rule_hits_arg(ctx, hits)) return rc;
+    if (const int rc = rule_hits_idle(ctx, hits)) return rc;
+    if (const int rc = rule_planes(ctx, planes, n, m)) return rc;
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = rule_set_dtype<T>(s, "plane")) return rc;
     if (flags & ~(BVHGPU_REGION_COUNT_ONLY | BVHGPU_REGION_CLASSIFY | BVHGPU_REGION_INSTANCES_ONLY))
         return fail(ctx, BVHGPU_INVALID_ARG, "instance region flags: BVHGPU_REGION_COUNT_ONLY, BVHGPU_REGION_CLASSIFY and BVHGPU_REGION_INSTANCES_ONLY only");
-    { const int rc = instances_current(s); if (rc != BVHGPU_OK) return rc; }
-    if (!(flags & BVHGPU_REGION_INSTANCES_ONLY))
-        for (const bvhgpu_tree* t : s->trees)
-            if (t->exact_only && !t->built && !t->unfolded)
-                return fail(ctx, BVHGPU_INVALID_ARG, "an imported member tree whose build had a split without SAH winner: its leaves' navigator boxes were folded away");
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 regions in one batch");
+    if (const int rc = instances_current(s)) return rc;
+    if (!(flags & BVHGPU_REGION_INSTANCES_ONLY))   // (the instances' world boxes alone: no member is walked)
+        if (const int rc = rule_members_unfolded(s)) return rc;
+    if (const int rc = rule_batch_size(ctx, n, "regions")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
-        const T* dev = planes;
-        const size_t bytes = n * m * 4 * sizeof(T);
-        if (mem == BVHGPU_HOST && bytes) {
-            h->qbuf.reserve(bytes);
-            BVH_HIP(hipMemcpyAsync(h->qbuf.p, planes, bytes, hipMemcpyHostToDevice, ctx->stream));
-            dev = h->qbuf.as<T>();
-        }
-        instances_region_batch<T>(s, dev, n, m, flags, h);
+        instances_region_batch<T>(s, stage_queries<T>(ctx, h, planes, n * m * 4 * sizeof(T), mem), n, m, flags, h);
         return (int)BVHGPU_OK;
     });
 }
-
-// do_allhits' shape over an instance set, behind do_instances_trace's commit and staleness rules; the result goes to a result object
-// (instances_allhits.hip), whose buffers a later batch of any kind reuses.  A refused call touches no buffer and leaves *hits as it was.
 template <typename T>
 int do_instances_allhits(bvhgpu_instances* s, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
     using Ray = typename Traits<T>::Ray;
-    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
-    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
-    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
+    if (const int rc = rule_hits_arg(ctx, hits)) return rc;
+    if (const int rc = rule_hits_idle(ctx, hits)) return rc;
     if (n && !rays) return fail(ctx, BVHGPU_INVALID_ARG, "rays is NULL");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from ray dtype");
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = rule_set_dtype<T>(s, "ray")) return rc;
     if (flags & ~(BVHGPU_INSTANCES_ALLHITS_LIST_ORDER | BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY))
         return fail(ctx, BVHGPU_INVALID_ARG, "instance all-hits flags: BVHGPU_INSTANCES_ALLHITS_LIST_ORDER and BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY only");
-    { const int rc = instances_current(s); if (rc != BVHGPU_OK) return rc; }
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 rays in one batch");
+    if (const int rc = instances_current(s)) return rc;
+    if (const int rc = rule_batch_size(ctx, n, "rays")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
         const auto* dev = static_cast<const Ray*>(to_device(ctx, rays, n * sizeof(Ray), mem, ctx->upload));
-        stage_tmax<T>(ctx, h, tmax, n, mem);   // (a HOST tmax is staged as do_allhits stages it)
-        const T* td = n ? static_cast<const T*>(h->pend_tmax) : nullptr;
-        h->pend_tmax = nullptr;                // (nothing replays this batch)
+        const T* td = n ? stage_side<T>(ctx, h, tmax, n, mem) : nullptr;
         instances_allhits_batch<T>(s, dev, td, n, flags, h);
         return (int)BVHGPU_OK;
     });
 }
-
-// do_within's shape over an instance set, behind do_instances_allhits' rules and do_instances_region's refusal of an imported member
-// whose navigator boxes were folded away; the result goes to a result object (instances_within.hip).  HOST points and limits are staged as
-// do_within stages them.  A refused call touches no buffer and leaves *hits as it was.
 template <typename T>
 int do_instances_within(bvhgpu_instances* s, const T* points, const T* max_dist, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
-    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
-    if (!hits) return fail(ctx, BVHGPU_INVALID_ARG, "hits is NULL");
-    if (*hits && (*hits)->pend_async) return fail(ctx, BVHGPU_INVALID_ARG, "the result object still holds an asynchronous batch: call bvhgpu_hits_wait first");
+    if (const int rc = rule_hits_arg(ctx, hits)) return rc;
+    if (const int rc = rule_hits_idle(ctx, hits)) return rc;
     if (n && !points) return fail(ctx, BVHGPU_INVALID_ARG, "points is NULL");
     if (n && !max_dist) return fail(ctx, BVHGPU_INVALID_ARG, "max_dist is NULL");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from point dtype");
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = rule_set_dtype<T>(s, "point")) return rc;
     if (flags & ~(BVHGPU_INSTANCES_WITHIN_LIST_ORDER | BVHGPU_INSTANCES_WITHIN_COUNT_ONLY))
         return fail(ctx, BVHGPU_INVALID_ARG, "instance within flags: BVHGPU_INSTANCES_WITHIN_LIST_ORDER and BVHGPU_INSTANCES_WITHIN_COUNT_ONLY only");
-    { const int rc = instances_current(s); if (rc != BVHGPU_OK) return rc; }
-    for (const bvhgpu_tree* t : s->trees)
-        if (t->exact_only && !t->built && !t->unfolded)
-            return fail(ctx, BVHGPU_INVALID_ARG, "an imported member tree whose build had a split without SAH winner: its leaves' navigator boxes were folded away");
-    if (n >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "more than 2^32-2 points in one batch");
+    if (const int rc = instances_current(s)) return rc;
+    if (const int rc = rule_members_unfolded(s)) return rc;
+    if (const int rc = rule_batch_size(ctx, n, "points")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
         const auto* dev = static_cast<const T*>(to_device(ctx, points, n * 3 * sizeof(T), mem, ctx->upload));
-        stage_tmax<T>(ctx, h, max_dist, n, mem);   // (HOST limits are staged as do_within stages them)
-        const T* md = n ? static_cast<const T*>(h->pend_tmax) : nullptr;
-        h->pend_tmax = nullptr;                    // (nothing replays this batch)
+        const T* md = n ? stage_side<T>(ctx, h, max_dist, n, mem) : nullptr;
         instances_within_batch<T>(s, dev, md, n, flags, h);
         return (int)BVHGPU_OK;
     });
 }
-
-// do_points' rules and staging over an instance set, behind do_instances_within's: one layout (points | dist | instance | shape), no result
-// object, synchronous.  A refused call touches no buffer and leaves the set as it was.
 template <typename T>
 int do_instances_knearest(bvhgpu_instances* s, const T* points, size_t n, int mem, uint32_t k, uint32_t* out_instance, uint32_t* out_shape, T* out_dist) {
-    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
-    if (k == 0 || k > BVHGPU_INSTANCES_KNN_MAX_K) return fail(ctx, BVHGPU_INVALID_ARG, "k must be between 1 and BVHGPU_INSTANCES_KNN_MAX_K");
+    if (const int rc = rule_k(ctx, k, BVHGPU_INSTANCES_KNN_MAX_K, "BVHGPU_INSTANCES_KNN_MAX_K")) return rc;
     if (n && (!points || !out_instance || !out_shape || !out_dist)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from point dtype");
-    { const int rc = instances_current(s); if (rc != BVHGPU_OK) return rc; }   // (a member that lost its triangles is stale)
-    for (const bvhgpu_tree* t : s->trees)
-        if (t->exact_only && !t->built && !t->unfolded)
-            return fail(ctx, BVHGPU_INVALID_ARG, "an imported member tree whose build had a split without SAH winner: its leaves' navigator boxes were folded away");
-    if (n >= 0xFFFFFFFFull || n * (size_t)k >= 0x100000000ull) return fail(ctx, BVHGPU_OVERFLOW, "too many results (points x k) in one call");
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = rule_set_dtype<T>(s, "point")) return rc;
+    if (const int rc = instances_current(s)) return rc;   // (a member that lost its triangles is stale)
+    if (const int rc = rule_members_unfolded(s)) return rc;
+    if (const int rc = rule_rows_size(ctx, n, k, "too many results (points x k) in one call")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
-        const T* pd = points; T* dd = out_dist; uint32_t *id = out_instance, *sd = out_shape;
-        const size_t pb = n * 3 * sizeof(T), db = n * k * sizeof(T), ib = n * k * 4;
-        if (mem == BVHGPU_HOST) {
-            ctx->upload.reserve(pb + db + 2 * ib + 64);
-            char* base = ctx->upload.as<char>();
-            if (pb) BVH_HIP(hipMemcpyAsync(base, points, pb, hipMemcpyHostToDevice, ctx->stream));
-            pd = reinterpret_cast<const T*>(base); dd = reinterpret_cast<T*>(base + pb);
-            id = reinterpret_cast<uint32_t*>(base + pb + db); sd = reinterpret_cast<uint32_t*>(base + pb + db + ib);
-        }
-        instances_knearest_batch<T>(s, pd, n, k, id, sd, dd);
-        if (mem == BVHGPU_HOST) {
-            copy_out(ctx, out_dist, dd, db, BVHGPU_HOST); copy_out(ctx, out_instance, id, ib, BVHGPU_HOST); copy_out(ctx, out_shape, sd, ib, BVHGPU_HOST);
-        } else {
-            BVH_HIP(hipStreamSynchronize(ctx->stream));   // the rows are complete when the call returns, whichever stream reads them next
-        }
+        RowStage st(ctx, mem, {{points, n * 3 * sizeof(T)}}, {{out_dist, n * k * sizeof(T)}, {out_instance, n * k * 4}, {out_shape, n * k * 4}});
+        instances_knearest_batch<T>(s, st.at<const T>(0), n, k, st.at<uint32_t>(2), st.at<uint32_t>(3), st.at<T>(1));
+        st.finish(true);   // in HBM too the rows are complete when the call returns, whichever stream reads them next
         return (int)BVHGPU_OK;
     });
 }
-
-// do_instances_trace's rules and staging with do_instances_knearest's k: one layout (rays | tmax | vals | instance | shape), no result
-// object, synchronous.  A refused call touches no buffer and leaves the set as it was.
 template <typename T>
 int do_instances_khits(bvhgpu_instances* s, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, uint32_t k, uint32_t* out_instance,
                        uint32_t* out_shape, T* out_vals) {
     using Ray = typename Traits<T>::Ray;
-    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
-    if (k == 0 || k > BVHGPU_INSTANCES_KHITS_MAX_K) return fail(ctx, BVHGPU_INVALID_ARG, "k must be between 1 and BVHGPU_INSTANCES_KHITS_MAX_K");
+    if (const int rc = rule_k(ctx, k, BVHGPU_INSTANCES_KHITS_MAX_K, "BVHGPU_INSTANCES_KHITS_MAX_K")) return rc;
     if (n && (!rays || !out_instance || !out_shape || !out_vals)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if (s->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "instance set dtype differs from ray dtype");
-    { const int rc = instances_current(s); if (rc != BVHGPU_OK) return rc; }
-    if (n >= 0xFFFFFFFFull || n * (size_t)k >= 0x100000000ull) return fail(ctx, BVHGPU_OVERFLOW, "too many results (rays x k) in one call");
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = rule_set_dtype<T>(s, "ray")) return rc;
+    if (const int rc = instances_current(s)) return rc;
+    if (const int rc = rule_rows_size(ctx, n, k, "too many results (rays x k) in one call")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
-        const Ray* rd = rays; const T* td = tmax; T* vd = out_vals; uint32_t *id = out_instance, *sd = out_shape;
-        const size_t rb = n * sizeof(Ray), tb = tmax ? n * sizeof(T) : 0, vb = n * k * 3 * sizeof(T), ib = n * k * 4;
-        if (mem == BVHGPU_HOST) {
-            ctx->upload.reserve(rb + tb + vb + 2 * ib + 64);
-            char* base = ctx->upload.as<char>();
-            if (rb) BVH_HIP(hipMemcpyAsync(base, rays, rb, hipMemcpyHostToDevice, ctx->stream));
-            if (tb) BVH_HIP(hipMemcpyAsync(base + rb, tmax, tb, hipMemcpyHostToDevice, ctx->stream));
-            rd = reinterpret_cast<const Ray*>(base); td = tb ? reinterpret_cast<const T*>(base + rb) : nullptr;
-            vd = reinterpret_cast<T*>(base + rb + tb); id = reinterpret_cast<uint32_t*>(base + rb + tb + vb); sd = reinterpret_cast<uint32_t*>(base + rb + tb + vb + ib);
-        }
-        instances_khits_batch<T>(s, rd, n ? td : nullptr, n, k, id, sd, vd);
-        if (mem == BVHGPU_HOST) {
-            copy_out(ctx, out_vals, vd, vb, BVHGPU_HOST); copy_out(ctx, out_instance, id, ib, BVHGPU_HOST); copy_out(ctx, out_shape, sd, ib, BVHGPU_HOST);
-        } else {
-            BVH_HIP(hipStreamSynchronize(ctx->stream));   // the rows are complete when the call returns, whichever stream reads them next
-        }
+        RowStage st(ctx, mem, {{rays, n * sizeof(Ray)}, {tmax, n * sizeof(T)}}, {{out_vals, n * k * 3 * sizeof(T)}, {out_instance, n * k * 4}, {out_shape, n * k * 4}});
+        instances_khits_batch<T>(s, st.at<const Ray>(0), n ? st.at<const T>(1) : nullptr, n, k, st.at<uint32_t>(3), st.at<uint32_t>(4), st.at<T>(2));
+        st.finish(true);   // in HBM too the rows are complete when the call returns, whichever stream reads them next
         return (int)BVHGPU_OK;
     });
 }
@@ -1498,7 +1486,7 @@ int bvhgpu_tree_info(const bvhgpu_tree* t, int* dtype, size_t* n_shapes, size_t*
 
 int bvhgpu_tree_nodes(bvhgpu_tree* t, void* out, int mem) {
     if (!t) return BVHGPU_INVALID_ARG;
-    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = settle(t)) return rc;
     if (!t->built) return fail(t->ctx, BVHGPU_INVALID_ARG, "tree has no node array (imported scene)");
     if (t->n_nodes && !out) return fail(t->ctx, BVHGPU_INVALID_ARG, "out is NULL");
     return guarded(t->ctx, [&] {
@@ -1511,7 +1499,7 @@ int bvhgpu_tree_nodes(bvhgpu_tree* t, void* out, int mem) {
 
 int bvhgpu_tree_shape_nodes(bvhgpu_tree* t, uint32_t* out, int mem) {
     if (!t) return BVHGPU_INVALID_ARG;
-    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = settle(t)) return rc;
     if (!t->built) return fail(t->ctx, BVHGPU_INVALID_ARG, "tree has no node array (imported scene)");
     if (t->n && !out) return fail(t->ctx, BVHGPU_INVALID_ARG, "out is NULL");
     return guarded(t->ctx, [&] {
@@ -1523,14 +1511,14 @@ int bvhgpu_tree_shape_nodes(bvhgpu_tree* t, uint32_t* out, int mem) {
 
 int bvhgpu_tree_build_levels(const bvhgpu_tree* t, int* levels) {
     if (!t || !levels) return BVHGPU_INVALID_ARG;
-    if (t->pending_build) { const int rc = settle(const_cast<bvhgpu_tree*>(t)); if (rc != BVHGPU_OK) return rc; }
+    if (t->pending_build) if (const int rc = settle(const_cast<bvhgpu_tree*>(t))) return rc;
     *levels = t->levels;
     return BVHGPU_OK;
 }
 
 int bvhgpu_flatten(bvhgpu_tree* t) {
     if (!t) return BVHGPU_INVALID_ARG;
-    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = settle(t)) return rc;
     if (!t->built) return fail(t->ctx, BVHGPU_INVALID_ARG, "tree has no node array (imported scene)");
     bvhgpu_ctx* ctx = t->ctx;
     return guarded(ctx, [&] {
@@ -1545,7 +1533,7 @@ int bvhgpu_flatten(bvhgpu_tree* t) {
 
 int bvhgpu_flat_nodes(bvhgpu_tree* t, void* out, int mem) {
     if (!t) return BVHGPU_INVALID_ARG;
-    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = settle(t)) return rc;
     if (!t->flattened || !t->built) return fail(t->ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
     if (t->n_flat && !out) return fail(t->ctx, BVHGPU_INVALID_ARG, "out is NULL");
     return guarded(t->ctx, [&] {
@@ -1586,7 +1574,7 @@ int bvhgpu_scene_nbytes(const bvhgpu_tree* t, size_t* nbytes) {
 
 int bvhgpu_scene_export(bvhgpu_tree* t, void* dst, int mem) {
     if (!t || !dst) return BVHGPU_INVALID_ARG;
-    { const int rc = settle(t); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = settle(t)) return rc;
     if (!t->flattened) return fail(t->ctx, BVHGPU_NOT_FLATTENED, "call bvhgpu_flatten first");
     bvhgpu_ctx* ctx = t->ctx;
     return guarded(ctx, [&] {
@@ -1818,54 +1806,43 @@ int bvhgpu_traverse_host_indices(bvhgpu_ctx* ctx, uint32_t* indices, size_t indi
     });
 }
 
-static int set_triangles(bvhgpu_tree* t, const void* verts, size_t n, int mem, int dtype) {
+// bvhgpu_tree_set_triangles_* / bvhgpu_tree_set_spheres_*: one record of `per` scalars per shape (3 vertices; {cx, cy, cz, r}) into a buffer
+// of the tree's own — a tree may hold triangles and spheres at once; nothing is validated.  Only the sphere setter tests `mem` (the
+// triangle setter, the older one, takes anything but BVHGPU_DEVICE for host memory: kept as it is).
+static int set_shape_array(bvhgpu_tree* t, const void* src, size_t n, int mem, int dtype, size_t per, DevBuf bvhgpu_tree::*buf, bool bvhgpu_tree::*has,
+                           const char* noun, const char* arg, bool test_mem) {
     if (!t) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = t->ctx;
-    if (t->dtype != dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "triangle dtype differs from tree dtype");
-    if (n != t->n) return fail(ctx, BVHGPU_INVALID_ARG, "one triangle per shape is required");
-    if (n && !verts) return fail(ctx, BVHGPU_INVALID_ARG, "verts is NULL");
+    if (t->dtype != dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, std::string(noun) + " dtype differs from tree dtype");
+    if (n != t->n) return fail(ctx, BVHGPU_INVALID_ARG, std::string("one ") + noun + " per shape is required");
+    if (n && !src) return fail(ctx, BVHGPU_INVALID_ARG, std::string(arg) + " is NULL");
+    if (test_mem) if (const int rc = rule_mem(ctx, mem)) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
-        const size_t bytes = n * 9 * (dtype == BVHGPU_F32 ? 4 : 8);
-        settle_waiters_impl(t);   // (a replay of a batch in flight must see the vertices it was enqueued with)
-        t->tris.reserve(bytes + 16);
+        const size_t bytes = n * per * (dtype == BVHGPU_F32 ? 4 : 8);
+        settle_waiters_impl(t);   // (a replay of a batch in flight must see the array it was enqueued with)
+        (t->*buf).reserve(bytes + 16);
         if (bytes) {
-            BVH_HIP(hipMemcpyAsync(t->tris.p, verts, bytes, mem == BVHGPU_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+            BVH_HIP(hipMemcpyAsync((t->*buf).p, src, bytes, mem == BVHGPU_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
             if (mem != BVHGPU_DEVICE) BVH_HIP(hipStreamSynchronize(ctx->stream));
         }
-        t->has_tris = true;
+        t->*has = true;
         return (int)BVHGPU_OK;
     });
+}
+static int set_triangles(bvhgpu_tree* t, const void* verts, size_t n, int mem, int dtype) {
+    return set_shape_array(t, verts, n, mem, dtype, 9, &bvhgpu_tree::tris, &bvhgpu_tree::has_tris, "triangle", "verts", false);
+}
+static int set_spheres(bvhgpu_tree* t, const void* spheres, size_t n, int mem, int dtype) {
+    return set_shape_array(t, spheres, n, mem, dtype, 4, &bvhgpu_tree::spheres, &bvhgpu_tree::has_spheres, "sphere", "spheres", true);
 }
 int bvhgpu_tree_set_triangles_f32(bvhgpu_tree* t, const float* verts, size_t n, int mem) { return set_triangles(t, verts, n, mem, BVHGPU_F32); }
 int bvhgpu_tree_set_triangles_f64(bvhgpu_tree* t, const double* verts, size_t n, int mem) { return set_triangles(t, verts, n, mem, BVHGPU_F64); }
-
-// one sphere {cx, cy, cz, r} per shape, in a buffer of its own (a tree may hold triangles and spheres at once); nothing is validated
-static int set_spheres(bvhgpu_tree* t, const void* spheres, size_t n, int mem, int dtype) {
-    if (!t) return BVHGPU_INVALID_ARG;
-    bvhgpu_ctx* ctx = t->ctx;
-    if (t->dtype != dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "sphere dtype differs from tree dtype");
-    if (n != t->n) return fail(ctx, BVHGPU_INVALID_ARG, "one sphere per shape is required");
-    if (n && !spheres) return fail(ctx, BVHGPU_INVALID_ARG, "spheres is NULL");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        const size_t bytes = n * 4 * (dtype == BVHGPU_F32 ? 4 : 8);
-        settle_waiters_impl(t);   // (a replay of a batch in flight must see the spheres it was enqueued with)
-        t->spheres.reserve(bytes + 16);
-        if (bytes) {
-            BVH_HIP(hipMemcpyAsync(t->spheres.p, spheres, bytes, mem == BVHGPU_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-            if (mem != BVHGPU_DEVICE) BVH_HIP(hipStreamSynchronize(ctx->stream));
-        }
-        t->has_spheres = true;
-        return (int)BVHGPU_OK;
-    });
-}
 int bvhgpu_tree_set_spheres_f32(bvhgpu_tree* t, const float* spheres, size_t n, int mem) { return set_spheres(t, spheres, n, mem, BVHGPU_F32); }
 int bvhgpu_tree_set_spheres_f64(bvhgpu_tree* t, const double* spheres, size_t n, int mem) { return set_spheres(t, spheres, n, mem, BVHGPU_F64); }
 
 int bvhgpu_hits_fetch_triangles(bvhgpu_hits* h, void* isect, int mem) {
-    { const int rc = hits_expect(h, true, HitsKind::Csr); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = hits_expect(h, true, HitsKind::Csr)) return rc;
     bvhgpu_ctx* ctx = h->ctx;
     if (!(h->flags & BVHGPU_TRAVERSE_TRIANGLES)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_TRIANGLES");
     return guarded(ctx, [&] {
@@ -1876,7 +1853,7 @@ int bvhgpu_hits_fetch_triangles(bvhgpu_hits* h, void* isect, int mem) {
 }
 // one record per ray (`per_ray` scalars in h->closest, the shape in h->closest_prim) of a batch of the kind `kind`
 static int fetch_per_ray(bvhgpu_hits* h, void* values, uint32_t* shape, int mem, HitsKind kind, size_t per_ray) {
-    { const int rc = hits_expect(h, true, kind); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = hits_expect(h, true, kind)) return rc;
     bvhgpu_ctx* ctx = h->ctx;
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -1900,7 +1877,7 @@ int bvhgpu_hits_fetch_sphere(bvhgpu_hits* h, void* slice, uint32_t* shape, int m
 
 int bvhgpu_hits_info(const bvhgpu_hits* h, size_t* n_rays, uint64_t* total, bvhgpu_traverse_stats* stats) {
     if (!h) return BVHGPU_INVALID_ARG;
-    if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (const int rc = rule_hits_complete(h)) return rc;
     if (n_rays) *n_rays = h->n_rays;
     if (total) *total = h->total;
     if (stats) *stats = h->stats;
@@ -1909,7 +1886,7 @@ int bvhgpu_hits_info(const bvhgpu_hits* h, size_t* n_rays, uint64_t* total, bvhg
 
 int bvhgpu_hits_walk_info(const bvhgpu_hits* h, unsigned* flags) {
     if (!h || !flags) return BVHGPU_INVALID_ARG;
-    if (h->pend_async) return fail(h->ctx, BVHGPU_INVALID_ARG, "the result object holds an asynchronous batch that has not been completed: call bvhgpu_hits_wait first");
+    if (const int rc = rule_hits_complete(h)) return rc;
     *flags = (h->pend_wide || h->pend_qwide ? BVHGPU_WALK_WIDE : 0u) | (h->pend_wide && h->pend_staged ? BVHGPU_WALK_STAGED : 0u) |
              (h->pend_wide && h->pend_rec8 ? BVHGPU_WALK_REC8 : 0u) | (h->pend_wide && h->pend_guide ? BVHGPU_WALK_F64_GUIDE : 0u);
     return BVHGPU_OK;
@@ -1921,133 +1898,85 @@ int bvhgpu_hits_walk_kernel(const bvhgpu_hits* h, char* name, size_t cap) {
     return BVHGPU_OK;
 }
 
+// ---- the CSR accessors: bvhgpu_hits_fetch and one per rows kind ------------------------------------------------------------------------------
+// An accessor is: the kind its result object must hold (csr_open: hits_expect, then `mem` — which bvhgpu_hits_fetch, the oldest, never
+// tested: kept), the kind's own refusals, and ONE csr_copy: the offsets buffer (n_rays + 1 u32) and up to four columns (destination,
+// source buffer, bytes per row) of `rows` rows — the batch's total, or none where a COUNT_ONLY batch hands out offsets alone.  Every
+// destination may be NULL.  A new rows kind adds a row to HITS_KINDS and an accessor of this shape.
+struct CsrCol { void* dst; const DevBuf* src; size_t row_bytes; };
+static int csr_open(const bvhgpu_hits* h, HitsKind kind, int mem) {
+    if (const int rc = hits_expect(h, true, kind)) return rc;
+    return rule_mem(h->ctx, mem);
+}
+static int csr_copy(bvhgpu_hits* h, int mem, uint32_t* offsets, const DevBuf& offsets_src, size_t rows, std::initializer_list<CsrCol> cols) {
+    bvhgpu_ctx* ctx = h->ctx;
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        if (offsets) copy_out(ctx, offsets, offsets_src.p, (h->n_rays + 1) * 4, mem);
+        for (const CsrCol& c : cols)
+            if (c.dst && rows) copy_out(ctx, c.dst, c.src->p, rows * c.row_bytes, mem);
+        return (int)BVHGPU_OK;
+    });
+}
+static size_t scalar_bytes(const bvhgpu_hits* h) { return h->dtype == BVHGPU_F32 ? 4 : 8; }
+static size_t rows_unless_count_only(const bvhgpu_hits* h) { return h->count_only ? 0 : (size_t)h->total; }   // (whatever `total` says)
+
 int bvhgpu_hits_fetch(bvhgpu_hits* h, uint32_t* offsets, uint32_t* indices, void* tslice, int mem) {
-    { const int rc = hits_expect(h, true, HitsKind::Csr); if (rc != BVHGPU_OK) return rc; }
-    bvhgpu_ctx* ctx = h->ctx;
-    if (tslice && !(h->flags & BVHGPU_TRAVERSE_T_SLICE)) return fail(ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_T_SLICE");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
-        if (indices && h->total) copy_out(ctx, indices, h->indices.p, h->total * 4, mem);
-        if (tslice && h->total) copy_out(ctx, tslice, h->tslice.p, h->total * 2 * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
-        return (int)BVHGPU_OK;
-    });
+    if (const int rc = hits_expect(h, true, HitsKind::Csr)) return rc;
+    if (tslice && !(h->flags & BVHGPU_TRAVERSE_T_SLICE)) return fail(h->ctx, BVHGPU_INVALID_ARG, "traverse was run without BVHGPU_TRAVERSE_T_SLICE");
+    return csr_copy(h, mem, offsets, h->offsets, h->total, {{indices, &h->indices, 4}, {tslice, &h->tslice, 2 * scalar_bytes(h)}});
 }
-
-// the CSR of an all-hits batch: offsets (n_rays + 1 u32), the shapes (total u32), the records (total x W T); each may be NULL
+// all-hits: the shapes (u32), the records (W x T)
 int bvhgpu_hits_fetch_allhits(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape, void* vals, int mem) {
-    { const int rc = hits_expect(h, true, HitsKind::Allhits); if (rc != BVHGPU_OK) return rc; }
-    bvhgpu_ctx* ctx = h->ctx;
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        const size_t w = h->row_leaf == BVHGPU_LEAF_TRIANGLE ? 3 : 2;
-        if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
-        if (shape && h->total) copy_out(ctx, shape, h->indices.p, h->total * 4, mem);
-        if (vals && h->total) copy_out(ctx, vals, h->row_vals.p, h->total * w * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
-        return (int)BVHGPU_OK;
-    });
+    if (const int rc = csr_open(h, HitsKind::Allhits, mem)) return rc;
+    const size_t w = h->row_leaf == BVHGPU_LEAF_TRIANGLE ? 3 : 2;
+    return csr_copy(h, mem, offsets, h->offsets, h->total, {{shape, &h->indices, 4}, {vals, &h->row_vals, w * scalar_bytes(h)}});
 }
-
-// the CSR of a within batch: offsets (n + 1 u32), the shapes (total u32), the distances (total T); each may be NULL.  A COUNT_ONLY batch
-// has offsets only: its shapes and distances are empty, whatever `total` says.
+// within: the shapes (u32), the distances (T); none of a COUNT_ONLY batch
 int bvhgpu_hits_fetch_within(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape, void* dist, int mem) {
-    { const int rc = hits_expect(h, true, HitsKind::Within); if (rc != BVHGPU_OK) return rc; }
-    bvhgpu_ctx* ctx = h->ctx;
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        const size_t rows = h->count_only ? 0 : (size_t)h->total;
-        if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
-        if (shape && rows) copy_out(ctx, shape, h->indices.p, rows * 4, mem);
-        if (dist && rows) copy_out(ctx, dist, h->row_vals.p, rows * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
-        return (int)BVHGPU_OK;
-    });
+    if (const int rc = csr_open(h, HitsKind::Within, mem)) return rc;
+    return csr_copy(h, mem, offsets, h->offsets, rows_unless_count_only(h), {{shape, &h->indices, 4}, {dist, &h->row_vals, scalar_bytes(h)}});
 }
-
-// the CSR of a region batch: offsets (n + 1 u32), the shapes (total u32), the inside bytes (total, CLASSIFY batches); each may be NULL.  A
-// COUNT_ONLY batch has offsets only, whatever `total` says.
+// region: offsets of its own, the shapes (u32), the inside bytes (CLASSIFY batches); none of a COUNT_ONLY batch
 int bvhgpu_hits_fetch_region(bvhgpu_hits* h, uint32_t* offsets, uint32_t* shape, void* inside, int mem) {
-    { const int rc = hits_expect(h, true, HitsKind::Region); if (rc != BVHGPU_OK) return rc; }
-    bvhgpu_ctx* ctx = h->ctx;
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if (inside && !h->rg_classify) return fail(ctx, BVHGPU_INVALID_ARG, "the region batch was run without BVHGPU_REGION_CLASSIFY");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        const size_t rows = h->count_only ? 0 : (size_t)h->total;
-        if (offsets) copy_out(ctx, offsets, h->rg_offsets.p, (h->n_rays + 1) * 4, mem);
-        if (shape && rows) copy_out(ctx, shape, h->indices.p, rows * 4, mem);
-        if (inside && rows) copy_out(ctx, inside, h->rg_inside.p, rows, mem);
-        return (int)BVHGPU_OK;
-    });
+    if (const int rc = csr_open(h, HitsKind::Region, mem)) return rc;
+    if (inside && !h->rg_classify) return fail(h->ctx, BVHGPU_INVALID_ARG, "the region batch was run without BVHGPU_REGION_CLASSIFY");
+    return csr_copy(h, mem, offsets, h->rg_offsets, rows_unless_count_only(h), {{shape, &h->indices, 4}, {inside, &h->rg_inside, 1}});
 }
-
-// the CSR of a region batch over an instance set: offsets (n + 1 u32), the instances and the shapes (total u32 each; a batch with
-// BVHGPU_REGION_INSTANCES_ONLY has no shapes), the inside bytes (total, CLASSIFY batches); each may be NULL.  A COUNT_ONLY batch has offsets
-// only, whatever `total` says.  A bvhgpu_region_* result is another kind.
+// region over an instance set (a bvhgpu_region_* result is another kind): the instances and the shapes (u32 each), the inside bytes.  A
+// batch with BVHGPU_REGION_INSTANCES_ONLY has no shapes, and its instances are stage 1's rows: where a region result keeps its shapes.
 int bvhgpu_hits_fetch_instances_region(bvhgpu_hits* h, uint32_t* offsets, uint32_t* instance, uint32_t* shape, void* inside, int mem) {
-    { const int rc = hits_expect(h, true, HitsKind::InstRegion); if (rc != BVHGPU_OK) return rc; }
-    bvhgpu_ctx* ctx = h->ctx;
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if (inside && !h->rg_classify) return fail(ctx, BVHGPU_INVALID_ARG, "the region batch was run without BVHGPU_REGION_CLASSIFY");
-    if (shape && h->rg_inst == REGION_INST_ONLY) return fail(ctx, BVHGPU_INVALID_ARG, "the region batch was run with BVHGPU_REGION_INSTANCES_ONLY: it has no shapes");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        const size_t rows = h->count_only ? 0 : (size_t)h->total;
-        const bool only = h->rg_inst == REGION_INST_ONLY;   // (stage 1's rows: the instances are where a region result keeps its shapes)
-        if (offsets) copy_out(ctx, offsets, h->rg_offsets.p, (h->n_rays + 1) * 4, mem);
-        if (instance && rows) copy_out(ctx, instance, only ? h->indices.p : h->row_instance.p, rows * 4, mem);
-        if (shape && rows) copy_out(ctx, shape, h->indices.p, rows * 4, mem);
-        if (inside && rows) copy_out(ctx, inside, h->rg_inside.p, rows, mem);
-        return (int)BVHGPU_OK;
-    });
+    if (const int rc = csr_open(h, HitsKind::InstRegion, mem)) return rc;
+    const bool only = h->rg_inst == REGION_INST_ONLY;
+    if (inside && !h->rg_classify) return fail(h->ctx, BVHGPU_INVALID_ARG, "the region batch was run without BVHGPU_REGION_CLASSIFY");
+    if (shape && only) return fail(h->ctx, BVHGPU_INVALID_ARG, "the region batch was run with BVHGPU_REGION_INSTANCES_ONLY: it has no shapes");
+    return csr_copy(h, mem, offsets, h->rg_offsets, rows_unless_count_only(h),
+                    {{instance, only ? &h->indices : &h->row_instance, 4}, {shape, &h->indices, 4}, {inside, &h->rg_inside, 1}});
 }
-
-// the CSR of an all-hits batch over an instance set: offsets (n_rays + 1 u32), the instances and the shapes (total u32 each), the records
-// (total x 3 T); each may be NULL.  A COUNT_ONLY batch has offsets only.
+// all-hits over an instance set: the instances and the shapes (u32 each), the records (3 x T).  A COUNT_ONLY batch refuses every column.
 int bvhgpu_hits_fetch_instances_allhits(bvhgpu_hits* h, uint32_t* offsets, uint32_t* instance, uint32_t* shape, void* vals, int mem) {
-    { const int rc = hits_expect(h, true, HitsKind::InstAllhits); if (rc != BVHGPU_OK) return rc; }
-    bvhgpu_ctx* ctx = h->ctx;
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (const int rc = csr_open(h, HitsKind::InstAllhits, mem)) return rc;
     if ((instance || shape || vals) && h->count_only)
-        return fail(ctx, BVHGPU_INVALID_ARG, "the batch was run with BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY: it has offsets only");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
-        if (instance && h->total) copy_out(ctx, instance, h->row_instance.p, h->total * 4, mem);
-        if (shape && h->total) copy_out(ctx, shape, h->indices.p, h->total * 4, mem);
-        if (vals && h->total) copy_out(ctx, vals, h->row_vals.p, h->total * 3 * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
-        return (int)BVHGPU_OK;
-    });
+        return fail(h->ctx, BVHGPU_INVALID_ARG, "the batch was run with BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY: it has offsets only");
+    return csr_copy(h, mem, offsets, h->offsets, h->total, {{instance, &h->row_instance, 4}, {shape, &h->indices, 4}, {vals, &h->row_vals, 3 * scalar_bytes(h)}});
 }
-
-// the CSR of a within batch over an instance set: offsets (n + 1 u32), the instances and the shapes (total u32 each), the distances
-// (total T); each may be NULL.  A COUNT_ONLY batch has offsets only.
+// within over an instance set: the instances and the shapes (u32 each), the distances (T).  A COUNT_ONLY batch refuses every column.
 int bvhgpu_hits_fetch_instances_within(bvhgpu_hits* h, uint32_t* offsets, uint32_t* instance, uint32_t* shape, void* dist, int mem) {
-    { const int rc = hits_expect(h, true, HitsKind::InstWithin); if (rc != BVHGPU_OK) return rc; }
-    bvhgpu_ctx* ctx = h->ctx;
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (const int rc = csr_open(h, HitsKind::InstWithin, mem)) return rc;
     if ((instance || shape || dist) && h->count_only)
-        return fail(ctx, BVHGPU_INVALID_ARG, "the batch was run with BVHGPU_INSTANCES_WITHIN_COUNT_ONLY: it has offsets only");
-    return guarded(ctx, [&] {
-        use_device(ctx);
-        if (offsets) copy_out(ctx, offsets, h->offsets.p, (h->n_rays + 1) * 4, mem);
-        if (instance && h->total) copy_out(ctx, instance, h->row_instance.p, h->total * 4, mem);
-        if (shape && h->total) copy_out(ctx, shape, h->indices.p, h->total * 4, mem);
-        if (dist && h->total) copy_out(ctx, dist, h->row_vals.p, h->total * (h->dtype == BVHGPU_F32 ? 4 : 8), mem);
-        return (int)BVHGPU_OK;
-    });
+        return fail(h->ctx, BVHGPU_INVALID_ARG, "the batch was run with BVHGPU_INSTANCES_WITHIN_COUNT_ONLY: it has offsets only");
+    return csr_copy(h, mem, offsets, h->offsets, h->total, {{instance, &h->row_instance, 4}, {shape, &h->indices, 4}, {dist, &h->row_vals, scalar_bytes(h)}});
 }
 
 int bvhgpu_hits_region_info(const bvhgpu_hits* h, uint32_t* n_chunks, uint32_t* chunk_entries) {
-    { const int rc = hits_expect(h, false, HitsKind::Region, HitsKind::InstRegion); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = hits_expect(h, false, HitsKind::Region, HitsKind::InstRegion)) return rc;
     if (n_chunks) *n_chunks = h->rg_chunks;
     if (chunk_entries) *chunk_entries = h->rg_chunk_entries;
     return BVHGPU_OK;
 }
 
 int bvhgpu_hits_device(const bvhgpu_hits* h, const uint32_t** offsets, const uint32_t** indices, const void** tslice) {
-    { const int rc = hits_expect(h, false, HitsKind::Csr); if (rc != BVHGPU_OK) return rc; }
+    if (const int rc = hits_expect(h, false, HitsKind::Csr)) return rc;
     if (offsets) *offsets = h->offsets.as<uint32_t>();
     if (indices) *indices = h->indices.as<uint32_t>();
     if (tslice) *tslice = (h->flags & BVHGPU_TRAVERSE_T_SLICE) ? h->tslice.p : nullptr;
@@ -2116,11 +2045,11 @@ int bvhgpu_instances_khits_f64(bvhgpu_instances* s, const bvhgpu_ray_f64* rays, 
     return do_instances_khits<double>(s, rays, tmax, n_rays, mem, k, out_instance, out_shape, out_vals);
 }
 int bvhgpu_instances_boxes(bvhgpu_instances* s, void* out, int mem) {
-    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "NULL instance set");
+    if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
     if (s->n && !out) return fail(ctx, BVHGPU_INVALID_ARG, "out is NULL");
-    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "mem must be BVHGPU_HOST or BVHGPU_DEVICE");
-    if (!s->committed) return fail(ctx, BVHGPU_INVALID_ARG, "instances are not committed (the last commit failed): call bvhgpu_instances_update");
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = rule_committed(s)) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
         copy_out(ctx, out, s->wboxes.p, s->n * 6 * (s->dtype == BVHGPU_F32 ? 4 : 8), mem);

@@ -68,25 +68,30 @@ class Instances(_Typed):
         check(getattr(_lib.load(), f"bvhgpu_instances_update_{self.sfx}")(self._s, xp, n, mem), self.ctx._h)
         return self
 
-    def _trace(self, rays: RayBatch, tmax, flags: int):
+    def _check_rays(self, rays: RayBatch) -> None:
         if rays.sfx != self.sfx:
             raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from the instance set's dtype")
+
+    def _csr(self, entry: str, args, n: int, dev, count_only: bool, *cols):
+        """one CSR batch into the set's own result object (made on first use: its buffers are reused by every batch) and its fetch:
+        bvhgpu_instances_<entry>_* with `args`, then api._fetch_csr with the columns given as (shape of one row, kind) or None"""
+        if dev is not None:
+            api._torch_sync(dev)
+        if getattr(self, "_hits", None) is None:
+            self._hits = api._Hits(self.ctx)
+        hits = self._hits
+        check(getattr(_lib.load(), f"bvhgpu_instances_{entry}_{self.sfx}")(self._s, *args, C.byref(hits.h)), self.ctx._h)
+        rows = 0 if count_only else hits._total()
+        return api._fetch_csr(f"instances_{entry}", hits, n, rows, self.ft, dev, *[c and ((rows,) + c[0], c[1]) for c in cols])
+
+    def _trace(self, rays: RayBatch, tmax, flags: int):
+        self._check_rays(rays)
         _keep, tp = api._side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
         n = rays.n
-        if rays.mem == DEVICE:
-            import torch
-            dev = rays.device.device
-            vals = torch.empty((n, 3), dtype=api._torch_ft(self.ft), device=dev)
-            inst = torch.empty((n,), dtype=torch.int32, device=dev)
-            shape = torch.empty((n,), dtype=torch.int32, device=dev)
-            api._torch_sync(dev)
-            vp, ip, sp = ptr(vals.data_ptr()), ptr(inst.data_ptr()), ptr(shape.data_ptr())
-        else:
-            vals, inst, shape = np.zeros((n, 3), dtype=self.ft), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
-            vp, ip, sp = ptr(vals), ptr(inst), ptr(shape)
+        out, (vp, ip, sp) = api._out_cols(rays.device.device if rays.mem == DEVICE else None, self.ft, ((n, 3), "float"), (n, "index"), (n, "index"))
         fn = getattr(_lib.load(), f"bvhgpu_instances_trace_{self.sfx}")
         check(fn(self._s, rays._ptr(), tp, n, rays.mem, flags, vp, ip, sp), self.ctx._h)
-        return vals, inst, shape
+        return tuple(out)
 
     def closest_hits(self, rays: RayBatch, tmax=None):
         """per ray the nearest triangle hit over all instances with distance < tmax[i] (None: +inf): (vals[n,3] = Intersection{distance, u,
@@ -118,37 +123,11 @@ class Instances(_Typed):
         classify = bool(classify) and not count_only
         flags = ((_lib.REGION_COUNT_ONLY if count_only else 0) | (_lib.REGION_CLASSIFY if classify else 0) |
                  (_lib.REGION_INSTANCES_ONLY if instances_only else 0))
-        dev = keep.device if mem == DEVICE else None
-        if dev is not None:
-            api._torch_sync(dev)
-        lib = _lib.load()
-        if getattr(self, "_hits", None) is None:
-            self._hits = api._Hits(self.ctx)     # (the set's own result object: its buffers are reused by every batch)
-        hits = self._hits
-        check(getattr(lib, f"bvhgpu_instances_region_{self.sfx}")(self._s, pp, n, m, mem, flags, C.byref(hits.h)), self.ctx._h)
-        rows = 0 if count_only else hits._total()
-        with_shape = not instances_only
-        if dev is not None:
-            import torch
-            off32 = torch.empty(n + 1, dtype=torch.int32, device=dev)
-            instance = torch.empty(rows, dtype=torch.int32, device=dev)
-            shape = torch.empty(rows, dtype=torch.int32, device=dev) if with_shape else None
-            inside = torch.empty(rows, dtype=torch.uint8, device=dev) if classify else None
-            api._torch_sync(dev)
-            check(lib.bvhgpu_hits_fetch_instances_region(hits.h, ptr(off32.data_ptr()), ptr(instance.data_ptr()) if rows else None,
-                                                         ptr(shape.data_ptr()) if with_shape and rows else None,
-                                                         ptr(inside.data_ptr()) if classify and rows else None, DEVICE), self.ctx._h)
-            offsets = off32.to(torch.int64) & 0xFFFFFFFF
-        else:
-            offsets = np.zeros(n + 1, dtype=np.uint32)
-            instance = np.zeros(rows, dtype=np.uint32)
-            shape = np.zeros(rows, dtype=np.uint32) if with_shape else None
-            inside = np.zeros(rows, dtype=np.uint8) if classify else None
-            check(lib.bvhgpu_hits_fetch_instances_region(hits.h, ptr(offsets), ptr(instance) if rows else None,
-                                                         ptr(shape) if with_shape and rows else None, ptr(inside) if classify and rows else None,
-                                                         _lib.HOST), self.ctx._h)
+        index, byte = ((), "index"), ((), "byte")
+        offsets, instance, shape, inside = self._csr("region", (pp, n, m, mem, flags), n, keep.device if mem == DEVICE else None, count_only,
+                                                     index, None if instances_only else index, byte if classify else None)
         out = dict(offsets=offsets, instance=instance)
-        if with_shape:
+        if not instances_only:
             out["shape"] = shape
         if classify:
             out["inside"] = inside
@@ -162,37 +141,12 @@ class Instances(_Typed):
         returns {offsets[n+1], instance[total], shape[total], vals[total, 3] = {distance, u, v}} (offsets only with count_only).  HOST rays:
         numpy out, offsets and indices as uint32.  Rays in HBM: torch tensors on the same device, indices as torch.int32, offsets as
         torch.int64."""
-        if rays.sfx != self.sfx:
-            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from the instance set's dtype")
+        self._check_rays(rays)
         _keep, tp = api._side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
-        n = rays.n
         flags = (0 if sort else _lib.INSTANCES_ALLHITS_LIST_ORDER) | (_lib.INSTANCES_ALLHITS_COUNT_ONLY if count_only else 0)
-        dev = rays.device.device if rays.mem == DEVICE else None
-        if dev is not None:
-            api._torch_sync(dev)
-        lib = _lib.load()
-        if getattr(self, "_hits", None) is None:
-            self._hits = api._Hits(self.ctx)     # (the set's own result object: its buffers are reused by every batch)
-        hits = self._hits
-        check(getattr(lib, f"bvhgpu_instances_allhits_{self.sfx}")(self._s, rays._ptr(), tp, n, rays.mem, flags, C.byref(hits.h)), self.ctx._h)
-        rows = 0 if count_only else hits._total()
-        if dev is not None:
-            import torch
-            off32 = torch.empty(n + 1, dtype=torch.int32, device=dev)
-            instance = torch.empty(rows, dtype=torch.int32, device=dev)
-            shape = torch.empty(rows, dtype=torch.int32, device=dev)
-            vals = torch.empty((rows, 3), dtype=api._torch_ft(self.ft), device=dev)
-            api._torch_sync(dev)
-            check(lib.bvhgpu_hits_fetch_instances_allhits(hits.h, ptr(off32.data_ptr()), ptr(instance.data_ptr()) if rows else None,
-                                                          ptr(shape.data_ptr()) if rows else None, ptr(vals.data_ptr()) if rows else None,
-                                                          DEVICE), self.ctx._h)
-            offsets = off32.to(torch.int64) & 0xFFFFFFFF
-        else:
-            offsets = np.zeros(n + 1, dtype=np.uint32)
-            instance, shape = np.zeros(rows, dtype=np.uint32), np.zeros(rows, dtype=np.uint32)
-            vals = np.zeros((rows, 3), dtype=self.ft)
-            check(lib.bvhgpu_hits_fetch_instances_allhits(hits.h, ptr(offsets), ptr(instance) if rows else None, ptr(shape) if rows else None,
-                                                          ptr(vals) if rows else None, _lib.HOST), self.ctx._h)
+        offsets, instance, shape, vals = self._csr("allhits", (rays._ptr(), tp, rays.n, rays.mem, flags), rays.n,
+                                                   rays.device.device if rays.mem == DEVICE else None, count_only,
+                                                   ((), "index"), ((), "index"), ((3,), "float"))
         if count_only:
             return dict(offsets=offsets)
         return dict(offsets=offsets, instance=instance, shape=shape, vals=vals)
@@ -205,27 +159,16 @@ class Instances(_Typed):
         returns (instance[n, k], shape[n, k], vals[n, k, 3] = {distance, u, v}); slots beyond the number of hits hold NONE, NONE and
         (+inf, 0, 0).  HOST rays: numpy out, indices as uint32.  Rays in HBM: torch tensors on the same device, written by the kernel,
         indices as torch.int32 — so NONE reads as -1 there."""
-        if rays.sfx != self.sfx:
-            raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from the instance set's dtype")
+        self._check_rays(rays)
         k = int(k)
         rows = k if 1 <= k <= _lib.INSTANCES_KHITS_MAX_K else 0   # (out of range: the engine answers INVALID_ARG before it touches a buffer)
         _keep, tp = api._side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
         n = rays.n
-        if rays.mem == DEVICE:
-            import torch
-            dev = rays.device.device
-            inst = torch.empty((n, rows), dtype=torch.int32, device=dev)
-            shape = torch.empty((n, rows), dtype=torch.int32, device=dev)
-            vals = torch.empty((n, rows, 3), dtype=api._torch_ft(self.ft), device=dev)
-            api._torch_sync(dev)
-            ip, sp, vp = ptr(inst.data_ptr()), ptr(shape.data_ptr()), ptr(vals.data_ptr())
-        else:
-            inst, shape = np.zeros((n, rows), dtype=np.uint32), np.zeros((n, rows), dtype=np.uint32)
-            vals = np.zeros((n, rows, 3), dtype=self.ft)
-            ip, sp, vp = ptr(inst), ptr(shape), ptr(vals)
+        out, (ip, sp, vp) = api._out_cols(rays.device.device if rays.mem == DEVICE else None, self.ft,
+                                          ((n, rows), "index"), ((n, rows), "index"), ((n, rows, 3), "float"))
         fn = getattr(_lib.load(), f"bvhgpu_instances_khits_{self.sfx}")
         check(fn(self._s, rays._ptr(), tp, n, rays.mem, k & 0xFFFFFFFF, ip, sp, vp), self.ctx._h)
-        return inst, shape, vals
+        return tuple(out)
 
     def within_batch(self, points, max_dist, sort: bool = True, count_only: bool = False) -> dict:
         """bvhgpu_instances_within_*: per point EVERY (instance, shape) whose world-space triangle lies within max_dist[i] of it (<=, the
@@ -242,32 +185,8 @@ class Instances(_Typed):
         keep, pp, n, mem = api._rows_in(points, 3, self.ft, "point")
         _m, mp = api._side_in(max_dist, keep, n, mem, self.ft, "max_dist", "points", scalar_ok=True)
         flags = (0 if sort else _lib.INSTANCES_WITHIN_LIST_ORDER) | (_lib.INSTANCES_WITHIN_COUNT_ONLY if count_only else 0)
-        dev = keep.device if mem == DEVICE else None
-        if dev is not None:
-            api._torch_sync(dev)
-        lib = _lib.load()
-        if getattr(self, "_hits", None) is None:
-            self._hits = api._Hits(self.ctx)     # (the set's own result object: its buffers are reused by every batch)
-        hits = self._hits
-        check(getattr(lib, f"bvhgpu_instances_within_{self.sfx}")(self._s, pp, mp, n, mem, flags, C.byref(hits.h)), self.ctx._h)
-        rows = 0 if count_only else hits._total()
-        if dev is not None:
-            import torch
-            off32 = torch.empty(n + 1, dtype=torch.int32, device=dev)
-            instance = torch.empty(rows, dtype=torch.int32, device=dev)
-            shape = torch.empty(rows, dtype=torch.int32, device=dev)
-            dist = torch.empty(rows, dtype=api._torch_ft(self.ft), device=dev)
-            api._torch_sync(dev)
-            check(lib.bvhgpu_hits_fetch_instances_within(hits.h, ptr(off32.data_ptr()), ptr(instance.data_ptr()) if rows else None,
-                                                         ptr(shape.data_ptr()) if rows else None, ptr(dist.data_ptr()) if rows else None,
-                                                         DEVICE), self.ctx._h)
-            offsets = off32.to(torch.int64) & 0xFFFFFFFF
-        else:
-            offsets = np.zeros(n + 1, dtype=np.uint32)
-            instance, shape = np.zeros(rows, dtype=np.uint32), np.zeros(rows, dtype=np.uint32)
-            dist = np.zeros(rows, dtype=self.ft)
-            check(lib.bvhgpu_hits_fetch_instances_within(hits.h, ptr(offsets), ptr(instance) if rows else None, ptr(shape) if rows else None,
-                                                         ptr(dist) if rows else None, _lib.HOST), self.ctx._h)
+        offsets, instance, shape, dist = self._csr("within", (pp, mp, n, mem, flags), n, keep.device if mem == DEVICE else None, count_only,
+                                                   ((), "index"), ((), "index"), ((), "float"))
         if count_only:
             return dict(offsets=offsets)
         return dict(offsets=offsets, instance=instance, shape=shape, dist=dist)
@@ -284,21 +203,10 @@ class Instances(_Typed):
         k = int(k)
         rows = k if 1 <= k <= _lib.INSTANCES_KNN_MAX_K else 0   # (out of range: the engine answers INVALID_ARG before it touches a buffer)
         keep, pp, n, mem = api._rows_in(points, 3, self.ft, "point")
-        if mem == DEVICE:
-            import torch
-            dev = keep.device
-            inst = torch.empty((n, rows), dtype=torch.int32, device=dev)
-            shape = torch.empty((n, rows), dtype=torch.int32, device=dev)
-            dist = torch.empty((n, rows), dtype=api._torch_ft(self.ft), device=dev)
-            api._torch_sync(dev)
-            ip, sp, dp = ptr(inst.data_ptr()), ptr(shape.data_ptr()), ptr(dist.data_ptr())
-        else:
-            inst, shape = np.zeros((n, rows), dtype=np.uint32), np.zeros((n, rows), dtype=np.uint32)
-            dist = np.zeros((n, rows), dtype=self.ft)
-            ip, sp, dp = ptr(inst), ptr(shape), ptr(dist)
+        out, (ip, sp, dp) = api._out_cols(keep.device if mem == DEVICE else None, self.ft, ((n, rows), "index"), ((n, rows), "index"), ((n, rows), "float"))
         fn = getattr(_lib.load(), f"bvhgpu_instances_knearest_{self.sfx}")
         check(fn(self._s, pp, n, mem, k & 0xFFFFFFFF, ip, sp, dp), self.ctx._h)
-        return inst, shape, dist
+        return tuple(out)
 
     def nearest_batch(self, points):
         """knearest_batch with k = 1 and the last axis dropped: (instance[n], shape[n], dist[n]) — the reference's nearest_to over the

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, api
-from ._lib import DEVICE, HOST, BvhGpuError, check, ptr
+from ._lib import DEVICE, BvhGpuError, check
 
 
 def frustum_planes(eye, look_at, up=(0.0, 1.0, 0.0), fov_y_deg: float = 60.0, aspect: float = 1.6, near: float = 0.1, far: float = 1000.0,
@@ -75,21 +75,7 @@ def region_batch(tree, planes, classify: bool = False, count_only: bool = False)
     nc, ce = C.c_uint32(), C.c_uint32()
     check(lib.bvhgpu_hits_region_info(hits.h, C.byref(nc), C.byref(ce)), tree.ctx._h)
     rows = 0 if count_only else hits._total()
-    if dev is not None:
-        import torch
-        off32 = torch.empty(n + 1, dtype=torch.int32, device=dev)
-        indices = torch.empty(rows, dtype=torch.int32, device=dev)
-        inside = torch.empty(rows, dtype=torch.uint8, device=dev) if classify else None
-        api._torch_sync(dev)
-        check(lib.bvhgpu_hits_fetch_region(hits.h, ptr(off32.data_ptr()), ptr(indices.data_ptr()) if rows else None,
-                                           ptr(inside.data_ptr()) if classify and rows else None, DEVICE), tree.ctx._h)
-        offsets = off32.to(torch.int64) & 0xFFFFFFFF
-    else:
-        offsets = np.zeros(n + 1, dtype=np.uint32)
-        indices = np.zeros(rows, dtype=np.uint32)
-        inside = np.zeros(rows, dtype=np.uint8) if classify else None
-        check(lib.bvhgpu_hits_fetch_region(hits.h, ptr(offsets), ptr(indices) if rows else None, ptr(inside) if classify and rows else None, HOST),
-              tree.ctx._h)
+    offsets, indices, inside = api._fetch_csr("region", hits, n, rows, tree.ft, dev, (rows, "index"), (rows, "byte") if classify else None)
     out = dict(offsets=offsets, indices=indices, chunks=int(nc.value), chunk_entries=int(ce.value))
     if classify:
         out["inside"] = inside

@@ -1,6 +1,7 @@
 """Which refusal a C entry point gives, with which message, and which one wins when two apply — for the batch entry points whose front
 ends capi.hip shares (bvhgpu_traverse_*, _traverse_async_*, _traverse_any_*, _traverse_box_*, _query_*, _nearest_*, _knearest_*,
-_knearest_tree_*, the per-ray fetches, _rebuild*/_refit_*).  The other suites assert refusal STATUSES; this one pins the message
+_knearest_tree_*, the per-ray fetches, _rebuild*/_refit_*), and the precedence alone for bvhgpu_traverse_sphere_* and bvhgpu_region_*,
+whose own suites assert each refusal by itself.  The other suites assert refusal STATUSES; this one pins the message
 and the precedence, through ctypes, so that arguments the Python layer would reject reach the C entry point.  After every refused call a
 valid call on the same tree and result object must still give the oracle's answer: a refusal leaves no half-set state.
 Not here: an uploaded tree given to bvhgpu_knearest_tree_* ("BvhNode" in the message) is asserted by test_gpu_knn_tree.test_errors, and
@@ -13,6 +14,7 @@ import pytest
 import knn_ref as kr
 import knn_tree_ref as ktr
 import query_ref as qr
+import region_ref as rr
 from test_box_hit_cpu import box_match
 from test_gpu_any_hit import first_match
 
@@ -32,6 +34,9 @@ FLATTEN_FIRST = "call bvhgpu_flatten first"
 K_MSG = "k must be between 1 and BVHGPU_KNN_MAX_K"
 KIND_MSG = "shape kind must be 0 (AABB) or 1 (triangle)"
 TRI_DIST = "triangle distance needs bvhgpu_tree_set_triangles first"
+SPHERE_FLAGS = "sphere-hit flags: BVHGPU_TRAVERSE_COHERENT and BVHGPU_TRAVERSE_FIRST only"
+PLANES_MAX, PLANE_DTYPE = "more than BVHGPU_REGION_MAX_PLANES planes per region", "tree dtype differs from plane dtype"
+M = 6                                                      # planes per region of the valid region call
 RAY_DTYPE, QUERY_DTYPE, POINT_DTYPE = "tree dtype differs from ray dtype", "tree dtype differs from query dtype", "tree dtype differs from point dtype"
 
 # (entry point, tree, arguments that differ from a valid call — None is a NULL pointer, expected status, expected part of bvhgpu_last_error)
@@ -130,6 +135,22 @@ PRECEDENCE = [
     ("nearest_f32", "f32", dict(points=None, kind=2), INVALID_ARG, "NULL argument"),                # NULL before kind
     ("nearest_f64", "f64", dict(kind=2, out_dist=None), INVALID_ARG, "NULL argument"),
     ("nearest_f32", "unflat", dict(points=None), NOT_FLATTENED, FLATTEN_FIRST),                     # flattened before NULL
+    # bvhgpu_traverse_sphere_*: the any-hit and box-hit order (no tree here has spheres: that rule is the last one)
+    ("traverse_sphere_f32", "f32", dict(flags=1, mem=7), INVALID_ARG, SPHERE_FLAGS),                # flags before mem
+    ("traverse_sphere_f32", "f32", dict(flags=1, hits=None), INVALID_ARG, "hits is NULL"),          # hits before flags
+    ("traverse_sphere_f32", "f64", dict(mem=7), INVALID_ARG, MEM_MSG),                              # mem before dtype
+    ("traverse_sphere_f64", "unflat", {}, DTYPE_MISMATCH, RAY_DTYPE),                               # dtype before flattened
+    ("traverse_sphere_f32", "unflat", dict(rays=None), NOT_FLATTENED, FLATTEN_FIRST),               # flattened before NULL rays
+    ("traverse_sphere_f32", "f32", dict(rays=None), INVALID_ARG, "rays is NULL"),                   # NULL rays before the spheres
+    ("traverse_sphere_f32", "f32", {}, INVALID_ARG, "sphere queries need bvhgpu_tree_set_spheres first"),
+    # bvhgpu_region_*: hits, dtype, flattened, the plane count, NULL planes, mem, flags
+    ("region_f32", "f64", dict(hits=None), INVALID_ARG, "hits is NULL"),                            # hits before dtype
+    ("region_f64", "unflat", {}, DTYPE_MISMATCH, PLANE_DTYPE),                                      # dtype before flattened
+    ("region_f32", "unflat", dict(m=33), NOT_FLATTENED, FLATTEN_FIRST),                             # flattened before the plane count
+    ("region_f32", "f32", dict(m=33, planes=None), INVALID_ARG, PLANES_MAX),                        # the plane count before NULL planes
+    ("region_f32", "f32", dict(planes=None, mem=7), INVALID_ARG, "planes is NULL"),                 # NULL planes before mem
+    ("region_f32", "f32", dict(mem=7, flags=4), INVALID_ARG, MEM_MSG),                              # mem before flags
+    ("region_f32", "f32", dict(flags=4), INVALID_ARG, "region flags: BVHGPU_REGION_COUNT_ONLY and BVHGPU_REGION_CLASSIFY only"),
 ]
 
 
@@ -137,7 +158,7 @@ class World:
     """three trees of 8 unit boxes on one ctx, 4 rays and 4 points per dtype, and the oracle's answers for them"""
 
     def __init__(self, eng, orc):
-        from bvh_amd import Context, _lib
+        from bvh_amd import Context, _lib, region
         self.lib, self.ptr = _lib.load(), _lib.ptr
         self.ctx = Context(0)
         boxes = np.array([[2 * i, 0, 0, 2 * i + 1, 1, 1] for i in range(8)], dtype=np.float64)
@@ -150,14 +171,15 @@ class World:
             a, p = boxes.astype(ft), points.astype(ft)
             rays = np.ascontiguousarray(orc.make_rays(origins, dirs, ft))
             tmax = np.full(N, 9.25, dtype=ft)
+            planes = np.ascontiguousarray(np.stack([region.aabb_planes(q - 1.5, q + 1.5, ft) for q in points]))   # (N, M, 4): a box about each point
             rays_dev = C.c_void_p()
             _lib.check(self.lib.bvhgpu_device_alloc(self.ctx._h, rays.nbytes, C.byref(rays_dev)), self.ctx._h)
             _lib.check(self.lib.bvhgpu_device_copy(self.ctx._h, rays_dev, DEVICE, self.ptr(rays), HOST, rays.nbytes), self.ctx._h)
-            self.inp[sfx] = dict(aabbs=a, rays=rays, rays_dev=rays_dev, tmax=tmax, points=p, tris=tris.astype(ft))
+            self.inp[sfx] = dict(aabbs=a, rays=rays, rays_dev=rays_dev, tmax=tmax, points=p, tris=tris.astype(ft), planes=planes)
             tree = orc.build(a)
             oflat = orc.flatten(tree.nodes)
             off, idx, ts, _ = orc.traverse_flat(oflat, a, rays, want_t=True)
-            ref = dict(csr=(off, idx), box=box_match(off, idx, ts, tmax, False), query=qr.walk(oflat, a, qr.POINT, p),
+            ref = dict(csr=(off, idx), box=box_match(off, idx, ts, tmax, False), query=qr.walk(oflat, a, qr.POINT, p), region=rr.walk(oflat, a, planes),
                        nearest=orc.nearest(oflat, a, p), knearest=kr.knearest(oflat, a, p, [K])[K],
                        knearest_tree=ktr.knearest_tree(tree.nodes, a, p, [K])[K])
             if sfx == "f32":
@@ -188,10 +210,12 @@ class World:
         if family in ("traverse", "traverse_async"):
             rays = g("rays", i["rays_dev"] if family == "traverse_async" else p(i["rays"]))
             args = (t, rays, n, g("mem", DEVICE if family == "traverse_async" else HOST), g("flags", 0), h)
-        elif family in ("traverse_any", "traverse_box"):
+        elif family in ("traverse_any", "traverse_box", "traverse_sphere"):
             args = (t, g("rays", p(i["rays"])), g("tmax", p(i["tmax"])), n, g("mem", HOST), g("flags", 0), h)
         elif family == "query":
             args = (t, g("kind", qr.POINT), g("queries", p(i["points"])), n, g("mem", HOST), g("flags", 0), h)
+        elif family == "region":
+            args = (t, g("planes", p(i["planes"])), n, g("m", M), g("mem", HOST), g("flags", 0), h)
         elif family in ("nearest", "knearest", "knearest_tree"):
             args = (t, g("points", p(i["points"])), n, HOST, g("kind", 0))
             args += {"nearest": (), "knearest": (g("k", K),), "knearest_tree": (g("k", K), None)}[family]
@@ -230,8 +254,8 @@ class World:
         if tree == "unflat":
             tree = "f32"                                        # no ray or query batch can run on that tree: the flattened f32 tree takes its place
         sfx = TREE_SFX[tree]
-        if family.startswith("re") or family == "traverse_async" or (family == "traverse_any" and tree != "f32"):
-            family = "traverse"                                 # (rebuild / refit refusals: the tree still answers; any-hit needs triangles)
+        if family.startswith(("rebuild", "refit")) or family in ("traverse_async", "traverse_sphere") or (family == "traverse_any" and tree != "f32"):
+            family = "traverse"                                 # (rebuild / refit refusals: the tree still answers; any-hit needs triangles, sphere hits spheres)
         assert self.call(f"{family}_{sfx}", tree, hits_of=hits_of) == OK, self.error()
         if family == "traverse":
             off, idx = self.fetch_csr(hits_of)
@@ -239,6 +263,11 @@ class World:
         elif family == "query":
             off, idx = self.fetch_csr(hits_of)
             assert off.tobytes() == self.ref[sfx]["query"][0].tobytes() and idx.tobytes() == self.ref[sfx]["query"][1].tobytes(), (entry, tree)
+        elif family == "region":
+            want = self.ref[sfx]["region"]
+            off, idx = np.zeros(N + 1, np.uint32), np.zeros(len(want[1]) + 1, np.uint32)
+            assert self.lib.bvhgpu_hits_fetch_region(self.hits(hits_of), self.ptr(off), self.ptr(idx), None, HOST) == OK, self.error()
+            assert off.tobytes() == want[0].tobytes() and idx[:-1].tobytes() == want[1].tobytes() and len(want[1]) > N, (entry, tree)
         else:
             kind = family.split("_")[1]
             vals, shape = self.fetch_rows(kind, hits_of, sfx)

@@ -283,6 +283,16 @@ def test_refusals(eng, orc, ctx):
         assert trace(r=rays64, f="f64", v=np.zeros((64, 3))) == DTYPE_MISMATCH and "dtype" in err()
         for flags in (1, 8, 16, 1024 | 16, 1 << 31):
             assert trace(flags=flags) == INVALID_ARG and "0 or BVHGPU_TRAVERSE_FIRST" in err()
+        # the order: an earlier rule wins over a later one (NULL argument, mem, dtype, flags, then the commit rule)
+        assert trace(r=None, mem=2, f="f64", flags=8) == INVALID_ARG and "NULL argument" in err()
+        assert trace(r=rays64, mem=2, f="f64", flags=8) == INVALID_ARG and "mem must be" in err()
+        assert trace(r=rays64, f="f64", flags=8) == DTYPE_MISMATCH and "dtype" in err()
+        bad = x.copy()
+        bad.reshape(-1)[0] = np.nan
+        assert lib.bvhgpu_instances_update_f32(h, ptr(bad), 2, HOST) == INVALID_ARG       # (a failed update: the set is uncommitted)
+        assert trace(flags=8) == INVALID_ARG and "0 or BVHGPU_TRAVERSE_FIRST" in err()
+        assert trace() == INVALID_ARG and "not committed" in err()
+        assert lib.bvhgpu_instances_update_f32(h, ptr(x), 2, HOST) == OK
         assert lib.bvhgpu_instances_boxes(h, None, HOST) == INVALID_ARG and "out is NULL" in err()
         assert lib.bvhgpu_instances_boxes(h, ptr(np.zeros((2, 6), dtype=np.float32)), 9) == INVALID_ARG and "mem must be" in err()
         assert trace(n=0, r=None, v=None, i=None, sh=None) == OK          # n_rays == 0 needs nothing

@@ -207,6 +207,8 @@ SYMBOLS = [
     ("bvhgpu_hits_fetch_instances_within", _i, [_vp, _vp, _vp, _vp, _vp, _i]),
     ("bvhgpu_instances_knearest_f32", _i, [_vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp]),
     ("bvhgpu_instances_knearest_f64", _i, [_vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp]),
+    ("bvhgpu_instances_knearest_tree_f32", _i, [_vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp, _vp]),
+    ("bvhgpu_instances_knearest_tree_f64", _i, [_vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp, _vp]),
     ("bvhgpu_instances_khits_f32", _i, [_vp, _vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp]),
     ("bvhgpu_instances_khits_f64", _i, [_vp, _vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp]),
     ("bvhgpu_instances_boxes", _i, [_vp, _vp, _i]),

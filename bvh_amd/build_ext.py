@@ -15,8 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libbvh_mi355x.so")
 SOURCES = ["capi.hip", "build.hip", "flatten.hip", "traverse.hip", "walk_binary.hip", "walk_ordered.hip", "walk_wide.hip", "csr.hip", "nearest.hip",
-           "rays.hip", "knn.hip", "knn_tree.hip", "khits.hip", "rows.hip", "allhits.hip", "within.hip", "region.hip", "instances.hip", "instances_allhits.hip", "instances_within.hip", "instances_knn.hip", "instances_khits.hip", "query.hip", "refit.hip", "comm.hip", "obj.cpp"]
-HEADERS = ["common.hpp", "engine.hpp", "walk.hpp", "point_dist.hpp", "rows.hpp", "instances.hpp", "instances_arrays.hpp", "unfold.hpp", "flatten_node.hpp", "obj.cpp", os.path.join("..", "..", "include", "bvh_mi355x.h")]
+           "rays.hip", "knn.hip", "knn_tree.hip", "khits.hip", "rows.hip", "allhits.hip", "within.hip", "region.hip", "instances.hip", "instances_allhits.hip", "instances_within.hip", "instances_knn.hip", "instances_knn_tree.hip", "instances_khits.hip", "query.hip", "refit.hip", "comm.hip", "obj.cpp"]
+HEADERS = ["common.hpp", "engine.hpp", "walk.hpp", "point_dist.hpp", "rows.hpp", "instances.hpp", "instances_arrays.hpp", "unfold.hpp", "tree_node.hpp", "flatten_node.hpp", "obj.cpp", os.path.join("..", "..", "include", "bvh_mi355x.h")]
 # -fno-slp-vectorize: ROCm 7.2's SLP vectoriser + gfx950 instruction selection crash (SIGSEGV in
 # constrainRegClass) on the integer-key min/max folds of sah_select(); packed v_pk_* VALU ops are no
 # gain for this code anyway (MI355X_MICROARCH.md, "packed f32 VALU ... an anti-lever").

@@ -1263,6 +1263,33 @@ int do_instances_knearest(bvhgpu_instances* s, const T* points, size_t n, int me
         return (int)BVHGPU_OK;
     });
 }
+// the nearest-first descent reads every member's BvhNode array: rule_members_unfolded's place in the order, another rule
+int rule_members_built(const bvhgpu_instances* s) {
+    for (const bvhgpu_tree* t : s->trees)
+        if (!t->built)
+            return fail(s->ctx, BVHGPU_INVALID_ARG, "the nearest-first descent needs the BvhNode array of every member tree: an uploaded, imported or broadcast member carries none (bvhgpu_instances_knearest_* takes such members)");
+    return BVHGPU_OK;
+}
+template <typename T>
+int do_instances_knearest_tree(bvhgpu_instances* s, const T* points, size_t n, int mem, uint32_t k, const T* max_dist, uint32_t* out_instance,
+                               uint32_t* out_shape, T* out_dist) {
+    if (!s) return no_set();
+    bvhgpu_ctx* ctx = s->ctx;
+    if (const int rc = rule_k(ctx, k, BVHGPU_INSTANCES_KNN_MAX_K, "BVHGPU_INSTANCES_KNN_MAX_K")) return rc;
+    if (n && (!points || !out_instance || !out_shape || !out_dist)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    if (const int rc = rule_set_dtype<T>(s, "point")) return rc;
+    if (const int rc = instances_current(s)) return rc;   // (a member that lost its triangles is stale)
+    if (const int rc = rule_members_built(s)) return rc;
+    if (const int rc = rule_rows_size(ctx, n, k, "too many results (points x k) in one call")) return rc;
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        RowStage st(ctx, mem, {{points, n * 3 * sizeof(T)}, {max_dist, n * sizeof(T)}}, {{out_dist, n * k * sizeof(T)}, {out_instance, n * k * 4}, {out_shape, n * k * 4}});
+        instances_knearest_tree_batch<T>(s, st.at<const T>(0), n, k, st.at<const T>(1), st.at<uint32_t>(3), st.at<uint32_t>(4), st.at<T>(2));
+        st.finish(true);   // in HBM too the rows are complete when the call returns, whichever stream reads them next
+        return (int)BVHGPU_OK;
+    });
+}
 template <typename T>
 int do_instances_khits(bvhgpu_instances* s, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, uint32_t k, uint32_t* out_instance,
                        uint32_t* out_shape, T* out_vals) {
@@ -2035,6 +2062,14 @@ int bvhgpu_instances_knearest_f32(bvhgpu_instances* s, const float* points, size
 int bvhgpu_instances_knearest_f64(bvhgpu_instances* s, const double* points, size_t n, int mem, uint32_t k, uint32_t* out_instance, uint32_t* out_shape,
                                   double* out_dist) {
     return do_instances_knearest<double>(s, points, n, mem, k, out_instance, out_shape, out_dist);
+}
+int bvhgpu_instances_knearest_tree_f32(bvhgpu_instances* s, const float* points, size_t n, int mem, uint32_t k, const float* max_dist,
+                                       uint32_t* out_instance, uint32_t* out_shape, float* out_dist) {
+    return do_instances_knearest_tree<float>(s, points, n, mem, k, max_dist, out_instance, out_shape, out_dist);
+}
+int bvhgpu_instances_knearest_tree_f64(bvhgpu_instances* s, const double* points, size_t n, int mem, uint32_t k, const double* max_dist,
+                                       uint32_t* out_instance, uint32_t* out_shape, double* out_dist) {
+    return do_instances_knearest_tree<double>(s, points, n, mem, k, max_dist, out_instance, out_shape, out_dist);
 }
 int bvhgpu_instances_khits_f32(bvhgpu_instances* s, const bvhgpu_ray_f32* rays, const float* tmax, size_t n_rays, int mem, uint32_t k,
                                uint32_t* out_instance, uint32_t* out_shape, float* out_vals) {

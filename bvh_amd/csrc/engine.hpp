@@ -357,6 +357,10 @@ struct bvhgpu_instances {
     bvhgpu::DevBuf kn_arrs;
     bvhgpu::DevBuf kn_unfold;
     std::vector<unsigned char> kn_arrs_host;   // host image of `kn_arrs` (alive while its upload is in flight)
+    // bvhgpu_instances_knearest_tree_* (instances_knn_tree.hip): per member its BvhNode image, node count and triangles (InstTreeMember<T>,
+    // n_trees rows); made again by every call, the allocation kept between calls and freed with the set
+    bvhgpu::DevBuf knt_members;
+    std::vector<unsigned char> knt_members_host;   // host image of `knt_members` (alive while its upload is in flight)
     bvhgpu_hits* rg_top = nullptr;   // bvhgpu_instances_region_*: the result object of stage 1 (the regions over `top`), made on first use
     ~bvhgpu_instances() { delete rg_top; }   // (never holds an asynchronous batch; the caller has synchronised the stream)
 };
@@ -467,6 +471,12 @@ void instances_within_batch(bvhgpu_instances* s, const T* points_dev, const T* m
 template <typename T>
 void instances_knearest_batch(bvhgpu_instances* s, const T* points_dev, size_t n, uint32_t k, uint32_t* out_instance_dev, uint32_t* out_shape_dev,
                               T* out_dist_dev);
+// instances_knn_tree.hip: the same rows found nearest child first over the BvhNode arrays of the top level and of the members
+// (bvhgpu_instances_knearest_tree_*); max_dist_dev: NULL or n limits; every member must have been built here.  Enqueued on the ctx's stream;
+// the member table lives in the set.
+template <typename T>
+void instances_knearest_tree_batch(bvhgpu_instances* s, const T* points_dev, size_t n, uint32_t k, const T* max_dist_dev, uint32_t* out_instance_dev,
+                                   uint32_t* out_shape_dev, T* out_dist_dev);
 // instances_khits.hip: the k nearest hits per ray over a committed instance set (bvhgpu_instances_khits_*); tmax_dev: NULL or n segment ends;
 // out_instance / out_shape: n x k, out_vals: n x k x 3; a set without instances fills them with padding.  Enqueued on the ctx's stream.
 template <typename T>

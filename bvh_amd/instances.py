@@ -16,7 +16,39 @@ from .api import Context, RayBatch, _Typed
 from .region import _plane_dims
 
 
-class Instances(_Typed):
+class InstancesTreeForm:
+    """The nearest-first ("tree form") point queries of an instance set, which Instances inherits: they read the BvhNode arrays of the top
+    level and of the members where every other entry of the set reads the flattened arrays.  Kept apart from Instances' own methods so
+    that the call recording of those (tests/golden/instances_calls.json) stays as it is; tests/test_instances_tree_marshal_cpu.py holds
+    these two to what they hand to the C ABI."""
+
+    def knearest_tree_batch(self, points, k: int, max_dist=None):
+        """bvhgpu_instances_knearest_tree_*: the rows of knearest_batch found nearest child first on both levels — the top-level BvhNode
+        array with the world point, every member's with the point in the object's frame — so the first pairs a point meets are near ones
+        and the bound that prunes is small from the start.  Equal distances stay in the order this walk meets them, which is not knearest_batch's: the two
+        may name different pairs at tied distances; their distances agree.
+        max_dist: None, a scalar (the same limit for every point) or n values in the points' memory — a numpy array for numpy points, a
+        torch GPU tensor for tensor points.  Nothing farther than max_dist[i] enters row i (d <= max_dist[i]^2); a negative or NaN limit
+        gives a row of padding, 0 keeps only distance 0.  Every member must have been built here (a Bvh's flatten(), not an uploaded
+        FlatBvh or an imported scene: those have no BvhNode array and raise INVALID_ARG; knearest_batch takes them).
+        points / k / returns: as knearest_batch."""
+        k = int(k)
+        rows = k if 1 <= k <= _lib.INSTANCES_KNN_MAX_K else 0   # (out of range: the engine answers INVALID_ARG before it touches a buffer)
+        keep, pp, n, mem = api._rows_in(points, 3, self.ft, "point")
+        _m, mp = api._side_in(max_dist, keep, n, mem, self.ft, "max_dist", "points", scalar_ok=True)
+        out, (ip, sp, dp) = api._out_cols(keep.device if mem == DEVICE else None, self.ft, ((n, rows), "index"), ((n, rows), "index"), ((n, rows), "float"))
+        fn = getattr(_lib.load(), f"bvhgpu_instances_knearest_tree_{self.sfx}")
+        check(fn(self._s, pp, n, mem, k & 0xFFFFFFFF, mp, ip, sp, dp), self.ctx._h)
+        return tuple(out)
+
+    def nearest_tree_batch(self, points, max_dist=None):
+        """knearest_tree_batch with k = 1 and the last axis dropped: (instance[n], shape[n], dist[n]); a point with nothing within its
+        limit, and a set without instances, give NONE, NONE and +inf."""
+        inst, shape, dist = self.knearest_tree_batch(points, 1, max_dist)
+        return inst[:, 0], shape[:, 0], dist[:, 0]
+
+
+class Instances(InstancesTreeForm, _Typed):
     """bvhgpu_instances: `trees` (Bvh / FlatBvh objects of one context and dtype, with set_triangles done; kept referenced), `tree_of[i]`
     the member of instance i, `transforms` n x 12 or n x 3 x 4 (row-major 3x4, object -> world) in the trees' dtype.  update() is the
     re-pose and the re-sync: call it after moving instances and after any rebuild, refit or set_triangles of a member tree; a trace on a

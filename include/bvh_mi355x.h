@@ -1016,6 +1016,64 @@ int bvhgpu_instances_knearest_f32(bvhgpu_instances *s, const float *points, size
 int bvhgpu_instances_knearest_f64(bvhgpu_instances *s, const double *points, size_t n, int mem, uint32_t k,
                                   uint32_t *out_instance, uint32_t *out_shape, double *out_dist);
 
+/* ---- k-nearest point queries over an instanced scene, nearest child first and with a search radius: the "tree form" of
+ * bvhgpu_instances_knearest_* (the "flat form"), as bvhgpu_knearest_tree_* is the tree form of bvhgpu_knearest_*.  The flat form walks
+ * both levels in list order and prunes nothing until a list is full; this one descends the BvhNode arrays of the top level and of the
+ * members nearest child first, so the first candidates a point meets are near ones, and it takes an optional limit per point.  The set is
+ * the committed one of bvhgpu_instances_trace_*.  All arithmetic is in the set's dtype T; every operation is rounded once, in the order
+ * written.
+ * For one query point p, L is a list of at most k triples (d, instance, shape); d is the squared WORLD distance in T.  full = len(L) == k,
+ * bound = L[last].d.  With a limit m = max_dist[j], r2 = m * m is one multiplication in T.  Insertion is bvhgpu_knearest_*'s: a full list
+ * drops its last element; the new one goes in front of the first e with d < e.d, else at the end.  Every comparison is T's <, > or <= as
+ * written; NaN behaves as in bvhgpu_knearest_* and bvhgpu_knearest_tree_*: a row that holds a NaN need not be sorted.
+ *   cmd(box, x)   = 0 if box.min[0] > box.max[0]      (a child of a split without SAH winner carries Aabb::empty(): nothing is known below it)
+ *                   else box.min_distance_squared(x)
+ *   admit_w(x)    = (max_dist == NULL || (m >= 0 && x <= r2))     && (!full || x < bound)       a leaf's d, world frame
+ *   admit_b(x, F) = (max_dist == NULL || (m >= 0 && x <= r2 * F)) && (!full || x < bound * F || bound * F == +inf)
+ *                   a child box: F = 1 at the top level (world frame: the products are r2 and bound themselves), F of the instance the walk
+ *                   is in below it (object frame).  A bound or a product that is +inf — a list that holds an infinite distance, or
+ *                   bound * F overflowing — says nothing about a box whose own distance overflowed as well, so it prunes nothing
+ *   top(node) over the BvhNode array of the top-level tree (the tree over the world boxes W), root = node 0, with p:
+ *     Leaf{shape = i}:  enter instance i
+ *     Node{l, l_aabb, r, r_aabb}:  c = [(l, cmd(l_aabb, p)), (r, cmd(r_aabb, p))];  if c[0].1 > c[1].1: swap   (strict >: ties and NaN keep left first)
+ *                                  for (idx, cd) in c: if admit_b(cd, 1): top(idx)  (the second test sees the list as the first subtree left it)
+ *   instance i (member t = tree_of[i]), bvhgpu_instances_knearest_*'s operation order:
+ *     q[c] = row4(Y_i[c], p);   F = (row3(Y_i[0],Y_i[0]) + row3(Y_i[1],Y_i[1])) + row3(Y_i[2],Y_i[2])
+ *     member(node) over member t's BvhNode array, root = node 0, with q:
+ *       Leaf{shape = s}:  w[v][c] = row4(X_i[c], tri_s[v]);  d = triangle_dist2(w, p)   (world triangle, world point: the flat form's leaf)
+ *                         if admit_w(d): insert (d, i, s)
+ *       Node{...}:        as above with cmd(., q) and admit_b(., F)
+ *  - r2 * F is ONE multiplication in T, made on entry to the instance.  bound * F is ONE multiplication in T, made on entry and whenever
+ *    `bound` changes.
+ *  - Output row j is the flat form's layout: out_instance[j*k + m], out_shape[j*k + m] and out_dist[j*k + m] = sqrt(L[m].d) for
+ *    m < len(L); the other slots hold BVHGPU_NONE, BVHGPU_NONE and +inf.
+ *  - A negative or NaN max_dist[j] gives a row of padding.  So do a set without instances and a member without shapes.  A limit of 0 keeps
+ *    only distance 0.  max_dist is NULL (no limit) or n values in the points' memory space.  n = 0 is fine (NULL buffers too).
+ *  - The prune is conservative by the flat form's argument, with <= for the radius: |p - X v| >= |q - v| / ||Y||_F, so a world triangle
+ *    with d <= r2 lies within sqrt(r2 * F) of q, and one with d < bound within sqrt(bound * F).  Acceptance into a full list is strict, so
+ *    what a prune skips could not have been accepted (in exact arithmetic).  Where bound * F overflows, admit_b's last clause switches the
+ *    box test off instead of comparing inf < inf: at coordinates near sqrt(max of T) the rows are still the nearest-first lists.
+ *  - Order and ties.  The order of a node's two children depends on the distances alone, never on the list.  Without prunes the walk
+ *    therefore visits all (instance, shape) pairs in one fixed order per point, the NEAREST-FIRST ORDER, and a row is the list built by
+ *    offering every pair in that order with no prune at all.  Ties stay in that order.  It is neither the flat form's double order nor
+ *    leaf pre-order: the flat and the tree form may name different pairs at tied distances.  Their distances agree.
+ *  - Members.  The descent reads the BvhNode array of every member, so every member must have been built here: an uploaded FlatBvh, an
+ *    imported or a broadcast member is refused (bvhgpu_instances_knearest_* takes such members).  The per-member table belongs to the set
+ *    and is freed by bvhgpu_instances_destroy.
+ *  - An identity instance of one tree gives that tree's own bvhgpu_knearest_tree_* distances (kind 1) bit for bit, and its shapes wherever a
+ *    row has no repeated distance (F = 3 there: the member's boxes are tested against wider limits, which may change the order ties are met in).
+ * `mem` covers all five buffers.  The call runs on the context's stream and returns when the rows are complete; there is no result object.
+ * 1 <= k <= BVHGPU_INSTANCES_KNN_MAX_K, the flat form's lists in LDS.
+ * Refused, touching no buffer and leaving the set as it was, the first broken rule in this order: a NULL set; k = 0 or k >
+ * BVHGPU_INSTANCES_KNN_MAX_K; a NULL points or output buffer with n > 0; a `mem` that is neither BVHGPU_HOST nor BVHGPU_DEVICE; a set of
+ * another dtype (BVHGPU_DTYPE_MISMATCH); an uncommitted set; a stale set (the check and the message of bvhgpu_instances_trace_*:
+ * "instances are stale"); a member that was not built here; n >= 2^32 - 1 or n * k >= 2^32 (BVHGPU_OVERFLOW).  Everything not marked is
+ * BVHGPU_INVALID_ARG. */
+int bvhgpu_instances_knearest_tree_f32(bvhgpu_instances *s, const float *points, size_t n, int mem, uint32_t k, const float *max_dist,
+                                       uint32_t *out_instance, uint32_t *out_shape, float *out_dist);
+int bvhgpu_instances_knearest_tree_f64(bvhgpu_instances *s, const double *points, size_t n, int mem, uint32_t k, const double *max_dist,
+                                       uint32_t *out_instance, uint32_t *out_shape, double *out_dist);
+
 /* ---- multi-hit ray queries over an instanced scene: the k nearest hits of every ray, in order, in fixed-width padded rows — depth
  * peeling, transparency with a known layer budget, LiDAR multi-return, picking through a front surface — without flattening the scene
  * and without fetching bvhgpu_instances_allhits_*'s whole CSR and cutting every row on the host.  bvhgpu_traverse_khits_* over the

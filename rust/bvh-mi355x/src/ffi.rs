@@ -246,6 +246,8 @@ extern "C" {
     // the k nearest (instance, shape) pairs per point over an instance set (out_*: n x k; padding = BVHGPU_NONE / BVHGPU_NONE / +inf; 1 <= k <= BVHGPU_INSTANCES_KNN_MAX_K; synchronous, no result object)
     pub fn bvhgpu_instances_knearest_f32(s: *mut bvhgpu_instances, points: *const f32, n: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_dist: *mut f32) -> c_int;
     pub fn bvhgpu_instances_knearest_f64(s: *mut bvhgpu_instances, points: *const f64, n: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_dist: *mut f64) -> c_int;
+    pub fn bvhgpu_instances_knearest_tree_f32(s: *mut bvhgpu_instances, points: *const f32, n: usize, mem: c_int, k: u32, max_dist: *const f32, out_instance: *mut u32, out_shape: *mut u32, out_dist: *mut f32) -> c_int;
+    pub fn bvhgpu_instances_knearest_tree_f64(s: *mut bvhgpu_instances, points: *const f64, n: usize, mem: c_int, k: u32, max_dist: *const f64, out_instance: *mut u32, out_shape: *mut u32, out_dist: *mut f64) -> c_int;
     // the k nearest hits per ray over an instance set (out_instance / out_shape: n_rays x k, out_vals: n_rays x k x 3; padding = BVHGPU_NONE / BVHGPU_NONE / {+inf, 0, 0}; 1 <= k <= BVHGPU_INSTANCES_KHITS_MAX_K; synchronous, no result object)
     pub fn bvhgpu_instances_khits_f32(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_vals: *mut f32) -> c_int;
     pub fn bvhgpu_instances_khits_f64(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_vals: *mut f64) -> c_int;

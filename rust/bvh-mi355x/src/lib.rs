@@ -1028,6 +1028,31 @@ impl<T: GpuScalar> GpuInstances<T> {
         (instance, shape, dist)
     }
 
+    /// The rows of `knearest` found nearest child first on both levels (`bvhgpu_instances_knearest_tree_*`), with an optional search radius
+    /// per point: nothing farther than `max_dist[j]` enters row `j` (`d <= max_dist[j]^2`); a negative or NaN limit gives a row of padding.
+    /// Equal distances stay in the order this walk meets them, which is not `knearest`'s: the two may name different pairs at tied
+    /// distances, their distances agree.  Every member tree must have been built here.  Returns and `k` as for `knearest`.
+    pub fn knearest_tree(&self, points: &[[T; 3]], k: usize, max_dist: Option<&[T]>) -> (Vec<u32>, Vec<u32>, Vec<T>) {
+        if let Some(m) = max_dist {
+            assert_eq!(m.len(), points.len(), "max_dist needs one value per point");
+        }
+        let k32 = u32::try_from(k).unwrap_or(u32::MAX);   // (out of range: the engine answers BVHGPU_INVALID_ARG and `check` panics with its message)
+        let slots = if (1..=ffi::BVHGPU_INSTANCES_KNN_MAX_K).contains(&k32) { points.len() * k } else { 0 };
+        let (mut instance, mut shape, mut dist) = (vec![0u32; slots], vec![0u32; slots], vec![T::default(); slots]);
+        unsafe {
+            let mp = max_dist.map_or(core::ptr::null(), |m| m.as_ptr());
+            let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_knearest_tree_f32(self.set, points.as_ptr().cast(), points.len(), ffi::BVHGPU_HOST, k32, mp.cast(),
+                                                        instance.as_mut_ptr(), shape.as_mut_ptr(), dist.as_mut_ptr().cast())
+            } else {
+                ffi::bvhgpu_instances_knearest_tree_f64(self.set, points.as_ptr().cast(), points.len(), ffi::BVHGPU_HOST, k32, mp.cast(),
+                                                        instance.as_mut_ptr(), shape.as_mut_ptr(), dist.as_mut_ptr().cast())
+            };
+            check(self.ctx, rc);
+        }
+        (instance, shape, dist)
+    }
+
     /// Per ray the `k` nearest `(instance, shape)` hits with `distance < tmax[j]` (`None`: `+inf`), ascending (`bvhgpu_instances_khits_*`):
     /// the head of `allhits`' sorted row, byte for byte, without the CSR.  Returns row-major `rays.len() x k` arrays `(instance, shape)` and
     /// `rays.len() x k x 3` `vals` = `{distance, u, v}`; equal distances stay in walk order (instances in the top level's order, shapes in

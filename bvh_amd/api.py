@@ -175,6 +175,46 @@ def _side_in(v, main, n: int, mem: int, ft, what: str, of: str, scalar_ok: bool 
     return keep, p
 
 
+def _mask_in(v, main, n: int, mem: int, what: str, of: str):
+    """The per-row 32-bit mask array of a batch (ray_mask of rays): n u32 in the memory `mem` of the main input `main` → (the object to keep
+    alive, its c_void_p); None → (None, None).  A Python int in [0, 2^32) is the same mask for every row.  HOST: numpy integers (or a
+    list of them), int32 taken by its bits, anything else by its value.  DEVICE: a torch.int32 tensor on the main input's device, its bits
+    taken as they are."""
+    if v is None:
+        return None, None
+    if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
+        v = int(v)
+        if not 0 <= v < 1 << 32:
+            raise BvhGpuError(_lib.INVALID_ARG, f"{what} must be in [0, 2^32), not {v}")
+        if mem == DEVICE:
+            import torch
+            keep = torch.full((n,), v - (1 << 32) if v >= 1 << 31 else v, dtype=torch.int32, device=main.device)
+            return keep, ptr(keep.data_ptr())
+        keep = np.full(n, v, dtype=np.uint32)
+        return keep, ptr(keep)
+    if _is_device_tensor(v) != (mem == DEVICE):
+        raise BvhGpuError(_lib.INVALID_ARG, f"{what} is a GPU tensor but the {of} are in host memory" if mem == HOST else
+                          f"{what} is in host memory but the {of} are in HBM")
+    if mem == DEVICE:
+        if str(v.dtype) != "torch.int32":
+            raise BvhGpuError(_lib.DTYPE_MISMATCH, f"{what} must be a torch.int32 tensor (its bits are the masks)")
+        v = v.contiguous()
+        if v.numel() != n:
+            raise BvhGpuError(_lib.INVALID_ARG, f"{what} has {v.numel()} values for {n} {of}")
+        return v, ptr(v.data_ptr())
+    a = np.asarray(v)
+    if a.size and a.dtype.kind not in "iu":
+        raise BvhGpuError(_lib.DTYPE_MISMATCH, f"{what} must be integers")
+    if a.dtype == np.int32:
+        a = a.view(np.uint32)
+    elif a.size and (int(a.min()) < 0 or int(a.max()) >= 1 << 32):
+        raise BvhGpuError(_lib.INVALID_ARG, f"{what} values must be in [0, 2^32)")
+    a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+    if a.size != n:
+        raise BvhGpuError(_lib.INVALID_ARG, f"{what} has {a.size} values for {n} {of}")
+    return a, ptr(a)
+
+
 # ------------------------------------------------------------------------------------------------
 class Context:
     """One GPU + one HIP stream + scratch (bvhgpu_ctx).  `stream` may be a raw hipStream_t

@@ -1102,6 +1102,10 @@ int do_instances_create(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_tre
         s->trees.assign(trees, trees + n_trees);
         s->top = new bvhgpu_tree();
         s->top->ctx = ctx; s->top->dtype = Traits<T>::dtype;
+        if (n) {   // every instance visible to every ray (bvhgpu_instances_set_masks)
+            s->masks.reserve(n * 4);
+            BVH_HIP(hipMemsetAsync(s->masks.p, 0xFF, n * 4, ctx->stream));
+        }
         if (n) {   // the set's own copy of tree_of, and a look at it on the host
             std::vector<uint32_t> of(n);
             s->tree_of.reserve(n * 4);
@@ -1155,9 +1159,11 @@ int instances_current(bvhgpu_instances* s) {
 // within: a result object, staged as their tree forms stage).  Every rule list ends with the commit and staleness rules, the refusal of an
 // imported member whose navigator boxes were folded away where the walk tests them, and the batch size; the k entries test k first.  A
 // refused call touches no buffer and leaves *hits and the set as they were.
+// The *_masked_* entries of trace, khits and allhits are the same functions with `masked`: the same rules in the same order, and ray_mask
+// (NULL: all ones) staged where the family stages tmax — a column of the row stage, or the result object's side buffer for all-hits.
 template <typename T>
 int do_instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, unsigned flags, T* out_vals,
-                       uint32_t* out_instance, uint32_t* out_shape) {
+                       uint32_t* out_instance, uint32_t* out_shape, bool masked = false, const uint32_t* ray_mask = nullptr) {
     using Ray = typename Traits<T>::Ray;
     if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
@@ -1169,8 +1175,10 @@ int do_instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays,
     if (const int rc = rule_batch_size(ctx, n, "rays")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
-        RowStage st(ctx, mem, {{rays, n * sizeof(Ray)}, {tmax, n * sizeof(T)}}, {{out_vals, n * 3 * sizeof(T)}, {out_instance, n * 4}, {out_shape, n * 4}});
-        instances_trace<T>(s, st.at<const Ray>(0), n ? st.at<const T>(1) : nullptr, n, (flags & BVHGPU_TRAVERSE_FIRST) != 0, st.at<T>(2), st.at<uint32_t>(3), st.at<uint32_t>(4));
+        RowStage st(ctx, mem, {{rays, n * sizeof(Ray)}, {tmax, n * sizeof(T)}, {masked ? ray_mask : nullptr, masked ? n * 4 : 0}},
+                    {{out_vals, n * 3 * sizeof(T)}, {out_instance, n * 4}, {out_shape, n * 4}});
+        instances_trace<T>(s, st.at<const Ray>(0), n ? st.at<const T>(1) : nullptr, n, (flags & BVHGPU_TRAVERSE_FIRST) != 0, st.at<T>(3), st.at<uint32_t>(4),
+                           st.at<uint32_t>(5), masked, n ? st.at<const uint32_t>(2) : nullptr);
         st.finish(true);   // in HBM too the rows are complete when the call returns, whichever stream reads them next
         return (int)BVHGPU_OK;
     });
@@ -1198,7 +1206,8 @@ int do_instances_region(bvhgpu_instances* s, const T* planes, size_t n, uint32_t
     });
 }
 template <typename T>
-int do_instances_allhits(bvhgpu_instances* s, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
+int do_instances_allhits(bvhgpu_instances* s, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, unsigned flags, bvhgpu_hits** hits,
+                         bool masked = false, const uint32_t* ray_mask = nullptr) {
     using Ray = typename Traits<T>::Ray;
     if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
@@ -1216,7 +1225,13 @@ int do_instances_allhits(bvhgpu_instances* s, const typename Traits<T>::Ray* ray
         bvhgpu_hits* h = batch_hits(hits);
         const auto* dev = static_cast<const Ray*>(to_device(ctx, rays, n * sizeof(Ray), mem, ctx->upload));
         const T* td = n ? stage_side<T>(ctx, h, tmax, n, mem) : nullptr;
-        instances_allhits_batch<T>(s, dev, td, n, flags, h);
+        const uint32_t* rm = masked && n ? ray_mask : nullptr;
+        if (rm && mem == BVHGPU_HOST) {   // (both walks of the batch read it: it stays in the result object like tmax)
+            h->maskbuf.reserve(n * 4);
+            BVH_HIP(hipMemcpyAsync(h->maskbuf.p, ray_mask, n * 4, hipMemcpyHostToDevice, ctx->stream));
+            rm = h->maskbuf.as<uint32_t>();
+        }
+        instances_allhits_batch<T>(s, dev, td, n, flags, h, masked, rm);
         return (int)BVHGPU_OK;
     });
 }
@@ -1292,7 +1307,7 @@ int do_instances_knearest_tree(bvhgpu_instances* s, const T* points, size_t n, i
 }
 template <typename T>
 int do_instances_khits(bvhgpu_instances* s, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, uint32_t k, uint32_t* out_instance,
-                       uint32_t* out_shape, T* out_vals) {
+                       uint32_t* out_shape, T* out_vals, bool masked = false, const uint32_t* ray_mask = nullptr) {
     using Ray = typename Traits<T>::Ray;
     if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
@@ -1304,8 +1319,10 @@ int do_instances_khits(bvhgpu_instances* s, const typename Traits<T>::Ray* rays,
     if (const int rc = rule_rows_size(ctx, n, k, "too many results (rays x k) in one call")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
-        RowStage st(ctx, mem, {{rays, n * sizeof(Ray)}, {tmax, n * sizeof(T)}}, {{out_vals, n * k * 3 * sizeof(T)}, {out_instance, n * k * 4}, {out_shape, n * k * 4}});
-        instances_khits_batch<T>(s, st.at<const Ray>(0), n ? st.at<const T>(1) : nullptr, n, k, st.at<uint32_t>(3), st.at<uint32_t>(4), st.at<T>(2));
+        RowStage st(ctx, mem, {{rays, n * sizeof(Ray)}, {tmax, n * sizeof(T)}, {masked ? ray_mask : nullptr, masked ? n * 4 : 0}},
+                    {{out_vals, n * k * 3 * sizeof(T)}, {out_instance, n * k * 4}, {out_shape, n * k * 4}});
+        instances_khits_batch<T>(s, st.at<const Ray>(0), n ? st.at<const T>(1) : nullptr, n, k, st.at<uint32_t>(4), st.at<uint32_t>(5), st.at<T>(3), masked,
+                                 n ? st.at<const uint32_t>(2) : nullptr);
         st.finish(true);   // in HBM too the rows are complete when the call returns, whichever stream reads them next
         return (int)BVHGPU_OK;
     });
@@ -2078,6 +2095,59 @@ int bvhgpu_instances_khits_f32(bvhgpu_instances* s, const bvhgpu_ray_f32* rays, 
 int bvhgpu_instances_khits_f64(bvhgpu_instances* s, const bvhgpu_ray_f64* rays, const double* tmax, size_t n_rays, int mem, uint32_t k,
                                uint32_t* out_instance, uint32_t* out_shape, double* out_vals) {
     return do_instances_khits<double>(s, rays, tmax, n_rays, mem, k, out_instance, out_shape, out_vals);
+}
+// ---- visibility masks: the set's n u32 and the three ray families that look at them ------------------------------------------
+// Not part of the pose: no commit, no look at `committed`, the top level untouched.  Synchronous: the masks are in place on return.
+int bvhgpu_instances_set_masks(bvhgpu_instances* s, const uint32_t* masks, size_t n, int mem) {
+    if (!s) return fail(nullptr, BVHGPU_INVALID_ARG, "set_masks: NULL instance set");
+    bvhgpu_ctx* ctx = s->ctx;
+    if (mem != BVHGPU_HOST && mem != BVHGPU_DEVICE) return fail(ctx, BVHGPU_INVALID_ARG, "set_masks: mem must be BVHGPU_HOST or BVHGPU_DEVICE");
+    if (n != s->n) return fail(ctx, BVHGPU_INVALID_ARG, "set_masks: the number of masks differs from the set's number of instances");
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        if (n) {
+            s->masks.reserve(n * 4);   // (create made it: never a new allocation)
+            if (masks) BVH_HIP(hipMemcpyAsync(s->masks.p, masks, n * 4, mem == BVHGPU_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+            else BVH_HIP(hipMemsetAsync(s->masks.p, 0xFF, n * 4, ctx->stream));
+        }
+        BVH_HIP(hipStreamSynchronize(ctx->stream));
+        return (int)BVHGPU_OK;
+    });
+}
+int bvhgpu_instances_masks(bvhgpu_instances* s, uint32_t* out, int mem) {
+    if (!s) return no_set();
+    bvhgpu_ctx* ctx = s->ctx;
+    if (s->n && !out) return fail(ctx, BVHGPU_INVALID_ARG, "out is NULL");
+    if (const int rc = rule_mem(ctx, mem)) return rc;
+    return guarded(ctx, [&] {
+        use_device(ctx);
+        copy_out(ctx, out, s->masks.p, s->n * 4, mem);
+        return (int)BVHGPU_OK;
+    });
+}
+int bvhgpu_instances_trace_masked_f32(bvhgpu_instances* s, const bvhgpu_ray_f32* rays, const float* tmax, const uint32_t* ray_mask, size_t n_rays, int mem,
+                                      unsigned flags, float* out_vals, uint32_t* out_instance, uint32_t* out_shape) {
+    return do_instances_trace<float>(s, rays, tmax, n_rays, mem, flags, out_vals, out_instance, out_shape, true, ray_mask);
+}
+int bvhgpu_instances_trace_masked_f64(bvhgpu_instances* s, const bvhgpu_ray_f64* rays, const double* tmax, const uint32_t* ray_mask, size_t n_rays, int mem,
+                                      unsigned flags, double* out_vals, uint32_t* out_instance, uint32_t* out_shape) {
+    return do_instances_trace<double>(s, rays, tmax, n_rays, mem, flags, out_vals, out_instance, out_shape, true, ray_mask);
+}
+int bvhgpu_instances_khits_masked_f32(bvhgpu_instances* s, const bvhgpu_ray_f32* rays, const float* tmax, const uint32_t* ray_mask, size_t n_rays, int mem,
+                                      uint32_t k, uint32_t* out_instance, uint32_t* out_shape, float* out_vals) {
+    return do_instances_khits<float>(s, rays, tmax, n_rays, mem, k, out_instance, out_shape, out_vals, true, ray_mask);
+}
+int bvhgpu_instances_khits_masked_f64(bvhgpu_instances* s, const bvhgpu_ray_f64* rays, const double* tmax, const uint32_t* ray_mask, size_t n_rays, int mem,
+                                      uint32_t k, uint32_t* out_instance, uint32_t* out_shape, double* out_vals) {
+    return do_instances_khits<double>(s, rays, tmax, n_rays, mem, k, out_instance, out_shape, out_vals, true, ray_mask);
+}
+int bvhgpu_instances_allhits_masked_f32(bvhgpu_instances* s, const bvhgpu_ray_f32* rays, const float* tmax, const uint32_t* ray_mask, size_t n_rays, int mem,
+                                        unsigned flags, bvhgpu_hits** hits) {
+    return do_instances_allhits<float>(s, rays, tmax, n_rays, mem, flags, hits, true, ray_mask);
+}
+int bvhgpu_instances_allhits_masked_f64(bvhgpu_instances* s, const bvhgpu_ray_f64* rays, const double* tmax, const uint32_t* ray_mask, size_t n_rays, int mem,
+                                        unsigned flags, bvhgpu_hits** hits) {
+    return do_instances_allhits<double>(s, rays, tmax, n_rays, mem, flags, hits, true, ray_mask);
 }
 int bvhgpu_instances_boxes(bvhgpu_instances* s, void* out, int mem) {
     if (!s) return no_set();

@@ -296,6 +296,7 @@ struct bvhgpu_hits {
     // any-hit, box and sphere batches (bvhgpu_traverse_any_* / _box_* / _sphere_*): per-ray segment ends in HBM (the caller's, or `tmaxbuf`; NULL = +inf), read by every replay
     const void* pend_tmax = nullptr;
     bvhgpu::DevBuf tmaxbuf;              // HOST tmax staged here
+    bvhgpu::DevBuf maskbuf;              // HOST ray_mask of bvhgpu_instances_allhits_masked_* staged here (the count walk and the fill walk read it)
     bvhgpu::DevBuf any_key;              // n_rays u32: any-hit batches walked as items (walk.hpp WalkOut::any_key), all-ones between batches
     bool akey_clean = false;
     bvhgpu::DevBuf any_part;             // per workgroup of k_any_resolve: its occluded rays (k_any_publish adds them up)
@@ -352,6 +353,8 @@ struct bvhgpu_instances {
     bvhgpu::DevBuf bounds;      // n_trees x 6 T: B_t
     bvhgpu::DevBuf recs;        // n x InstRec<T>: Y_i and the tree slot
     bvhgpu::DevBuf wboxes;      // n x 6 T: W_i
+    bvhgpu::DevBuf masks;       // n u32: the visibility masks (all ones from create; bvhgpu_instances_set_masks).  No part of the pose: no
+                                // commit reads or writes them, and only the *_masked_* entries look at them
     // bvhgpu_instances_knearest_* (instances_knn.hip): the array table of the set (instances_arrays.hpp InstWithinArr<T>, n_trees + 1 rows) and
     // the unfolded mirrors it points to; made again by every call, the allocations kept between calls and freed with the set
     bvhgpu::DevBuf kn_arrs;
@@ -368,11 +371,12 @@ struct bvhgpu_instances {
 namespace bvhgpu {
 
 // instances.hip: commit the pose in s->xforms (member tables, B_t, Y_i, W_i, the top-level build; throws Fail::NonFinite on a NaN / infinite
-// world box) and the two-level walk; everything in HBM, on the ctx's stream
+// world box) and the two-level walk; everything in HBM, on the ctx's stream.  masked (bvhgpu_instances_trace_masked_*): instance i is walked
+// for ray j iff s->masks[i] & ray_mask_dev[j] (NULL: all ones) is not 0; without it no mask is read
 template <typename T> void instances_commit(bvhgpu_instances* s);
 template <typename T>
 void instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n_rays, bool first, T* out_vals_dev,
-                     uint32_t* out_instance_dev, uint32_t* out_shape_dev);
+                     uint32_t* out_instance_dev, uint32_t* out_shape_dev, bool masked = false, const uint32_t* ray_mask_dev = nullptr);
 
 // build.hip
 template <typename T> void build_tree(bvhgpu_tree* t, const T* aabbs_dev, size_t n, bool flatten_after);
@@ -457,9 +461,10 @@ void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, 
 // instances_allhits.hip: every hit per ray over a committed instance set as a CSR (bvhgpu_instances_allhits_*); flags:
 // BVHGPU_INSTANCES_ALLHITS_*; tmax_dev: NULL or n segment ends.  Synchronous: h->offsets / h->row_instance / h->indices / h->row_vals and
 // h->total are complete on return.  Throws Fail::Overflow when the batch has more than 2^32-1 candidates (the result object then holds an
-// empty result of this kind).
+// empty result of this kind).  masked (bvhgpu_instances_allhits_masked_*): s->masks against ray_mask_dev, as for instances_trace.
 template <typename T>
-void instances_allhits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, unsigned flags, bvhgpu_hits* h);
+void instances_allhits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, unsigned flags, bvhgpu_hits* h,
+                             bool masked = false, const uint32_t* ray_mask_dev = nullptr);
 // instances_within.hip: every (instance, shape) within max_dist_dev[i] of point i over a committed instance set as a CSR
 // (bvhgpu_instances_within_*); flags: BVHGPU_INSTANCES_WITHIN_*.  Synchronous: h->offsets / h->row_instance / h->indices / h->row_vals and h->total
 // are complete on return.  Throws Fail::Overflow when the batch has more than 2^32-1 candidates (the result object then holds an empty
@@ -479,9 +484,11 @@ void instances_knearest_tree_batch(bvhgpu_instances* s, const T* points_dev, siz
                                    uint32_t* out_shape_dev, T* out_dist_dev);
 // instances_khits.hip: the k nearest hits per ray over a committed instance set (bvhgpu_instances_khits_*); tmax_dev: NULL or n segment ends;
 // out_instance / out_shape: n x k, out_vals: n x k x 3; a set without instances fills them with padding.  Enqueued on the ctx's stream.
+// masked (bvhgpu_instances_khits_masked_*): s->masks against ray_mask_dev, as for instances_trace.
 template <typename T>
 void instances_khits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, uint32_t k,
-                           uint32_t* out_instance_dev, uint32_t* out_shape_dev, T* out_vals_dev);
+                           uint32_t* out_instance_dev, uint32_t* out_shape_dev, T* out_vals_dev, bool masked = false,
+                           const uint32_t* ray_mask_dev = nullptr);
 // rays.hip
 template <typename T>
 void ray_triangle_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays_dev, const T* tris_dev, size_t n, T* out_dev);

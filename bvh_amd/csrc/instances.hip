@@ -4,7 +4,8 @@
 //   k_instances_prep<T, 1>   Y_i (the inverse transform) and W_i (the world box) of instance i (one lane per instance)
 //   k_instances_trace        one ray per lane over the top-level array; a top-level leaf sends the lane, with the ray re-expressed in the
 //                            object's frame, into that member's array — the same loop, another array — and the lane comes back to the
-//                            entry behind that leaf when the member's array ends
+//                            entry behind that leaf when the member's array ends.  MASKED (bvhgpu_instances_trace_masked_*, DESIGN.md
+//                            §4r): an instance whose mask shares no bit with the ray's is passed over at its top-level leaf
 // Node fetch, slab test and triangle test are walk.hpp's and common.hpp's, unchanged: that is what makes the bits those of the
 // single-tree walks.  Nothing is pruned.
 #include "instances.hpp"
@@ -109,14 +110,20 @@ __global__ __launch_bounds__(256) void k_instances_prep(const InstTree<T>* __res
 // the two-level walk: one ray per lane, ONE loop.  A lane's state is (array, index, end, ray): inst == NONE means the top-level array
 // and the world ray, otherwise member `inst`'s array and the object-space ray.  No loop is nested inside a top-level leaf, so the lanes of
 // a wave keep stepping together whatever level each of them is on.
+// MASKED: inst_mask is the set's n u32, ray_mask NULL (all ones) or n_rays u32; instance i is visible to the ray iff the two share a bit.  An
+// invisible instance costs its mask's load: no record, no re-expressed ray, no member node — the lane goes on at i + 1 in the top level.
+// Without MASKED neither pointer is read and the test is not compiled.
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool FIRST>
+template <typename T, bool FIRST, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_instances_trace(const TravNode<T>* __restrict__ top, uint32_t n_top, const InstRec<T>* __restrict__ recs,
                                                          const InstTree<T>* __restrict__ tbl, const typename Traits<T>::Ray* __restrict__ rays,
                                                          const T* __restrict__ tmax, uint32_t n_rays, T* __restrict__ out_vals,
-                                                         uint32_t* __restrict__ out_instance, uint32_t* __restrict__ out_shape) {
+                                                         uint32_t* __restrict__ out_instance, uint32_t* __restrict__ out_shape,
+                                                         const uint32_t* __restrict__ inst_mask, const uint32_t* __restrict__ ray_mask) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = r < n_rays;
+    uint32_t rmask = 0xFFFFFFFFu;
+    if constexpr (MASKED) { if (active && ray_mask) rmask = ray_mask[r]; }
     T o[3] = {0, 0, 0}, d[3] = {0, 0, 0}, inv[3] = {0, 0, 0};
     T best[3] = {Traits<T>::inf(), 0, 0};
     uint32_t best_inst = NONE, best_shape = NONE;
@@ -152,17 +159,21 @@ __global__ __launch_bounds__(256) void k_instances_trace(const TravNode<T>* __re
                         if (FIRST) { i = 0; end = 0; inst = NONE; }   // the ray is done
                     }
                 } else {              // an instance's world box: into its tree with the ray in the object's frame
-                    top_next = i;
-                    inst = nd.shape;
-                    const InstRec<T> rec = load_rec<T>(recs + inst);
-                    const InstTree<T> t = tbl[rec.tree];
-                    T oo[3], dd[3];
+                    bool visible = true;
+                    if constexpr (MASKED) visible = (inst_mask[nd.shape] & rmask) != 0u;   // (hidden: the lane stays here and goes on at i + 1)
+                    if (visible) {
+                        top_next = i;
+                        inst = nd.shape;
+                        const InstRec<T> rec = load_rec<T>(recs + inst);
+                        const InstTree<T> t = tbl[rec.tree];
+                        T oo[3], dd[3];
 #pragma unroll
-                    for (int k = 0; k < 3; k++) { oo[k] = row4<T>(rec.y + 4 * k, o); dd[k] = row3<T>(rec.y + 4 * k, d); }
+                        for (int k = 0; k < 3; k++) { oo[k] = row4<T>(rec.y + 4 * k, o); dd[k] = row3<T>(rec.y + 4 * k, d); }
 #pragma unroll
-                    for (int k = 0; k < 3; k++) { o[k] = oo[k]; d[k] = dd[k]; inv[k] = (T)1 / dd[k]; }
-                    fin = ray_is_finite<T>(o, inv);
-                    nodes = t.trav; tris = t.tris; i = 0; end = t.n_trav;
+                        for (int k = 0; k < 3; k++) { o[k] = oo[k]; d[k] = dd[k]; inv[k] = (T)1 / dd[k]; }
+                        fin = ray_is_finite<T>(o, inv);
+                        nodes = t.trav; tris = t.tris; i = 0; end = t.n_trav;
+                    }
                 }
             }
             if (inst != NONE && i >= end) {   // the member's array has ended: back to the top level, behind the leaf that sent the lane here
@@ -215,25 +226,30 @@ template <typename T> void instances_commit(bvhgpu_instances* s) {
     s->committed = true;
 }
 
+// masked: bvhgpu_instances_trace_masked_* — the set's masks against ray_mask_dev (NULL: all ones); otherwise ray_mask_dev is not looked at
 template <typename T>
 void instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n_rays, bool first, T* out_vals_dev,
-                     uint32_t* out_instance_dev, uint32_t* out_shape_dev) {
+                     uint32_t* out_instance_dev, uint32_t* out_shape_dev, bool masked, const uint32_t* ray_mask_dev) {
     if (!n_rays) return;
     hipStream_t st = s->ctx->stream;
     const bvhgpu_tree* top = s->top;
     const uint32_t n_top = s->n ? (uint32_t)top->n_trav : 0u;
     const dim3 grid((unsigned)((n_rays + 255) / 256)), block(256);
-#define INST_TRACE(F)                                                                                                                          \
-    hipLaunchKernelGGL((k_instances_trace<T, F>), grid, block, 0, st, top->trav.as<TravNode<T>>(), n_top, s->recs.as<InstRec<T>>(),        \
-                       s->table.as<InstTree<T>>(), rays_dev, tmax_dev, (uint32_t)n_rays, out_vals_dev, out_instance_dev, out_shape_dev)
-    if (first) INST_TRACE(true); else INST_TRACE(false);
+#define INST_TRACE(F, M)                                                                                                                       \
+    hipLaunchKernelGGL((k_instances_trace<T, F, M>), grid, block, 0, st, top->trav.as<TravNode<T>>(), n_top, s->recs.as<InstRec<T>>(),     \
+                       s->table.as<InstTree<T>>(), rays_dev, tmax_dev, (uint32_t)n_rays, out_vals_dev, out_instance_dev, out_shape_dev,       \
+                       M ? s->masks.as<uint32_t>() : nullptr, M ? ray_mask_dev : nullptr)
+    if (masked) { if (first) INST_TRACE(true, true); else INST_TRACE(false, true); }
+    else { if (first) INST_TRACE(true, false); else INST_TRACE(false, false); }
 #undef INST_TRACE
     BVH_HIP(hipGetLastError());
 }
 
 template void instances_commit<float>(bvhgpu_instances*);
 template void instances_commit<double>(bvhgpu_instances*);
-template void instances_trace<float>(bvhgpu_instances*, const bvhgpu_ray_f32*, const float*, size_t, bool, float*, uint32_t*, uint32_t*);
-template void instances_trace<double>(bvhgpu_instances*, const bvhgpu_ray_f64*, const double*, size_t, bool, double*, uint32_t*, uint32_t*);
+template void instances_trace<float>(bvhgpu_instances*, const bvhgpu_ray_f32*, const float*, size_t, bool, float*, uint32_t*, uint32_t*, bool,
+                                     const uint32_t*);
+template void instances_trace<double>(bvhgpu_instances*, const bvhgpu_ray_f64*, const double*, size_t, bool, double*, uint32_t*, uint32_t*, bool,
+                                      const uint32_t*);
 
 }  // namespace bvhgpu

@@ -21,6 +21,10 @@
 //                                 INST_ALLHITS_LDS_ROW_MAX elements, in place in global memory beyond; the shape of an element is gathered
 //                                 from the scratch row by its position; then the records of the row.
 // The row length is uniform per workgroup of k_instances_allhits_sort_row: every loop bound and every barrier there depends on it alone.
+//
+// MASKED (bvhgpu_instances_allhits_masked_*): instances_walk passes over an instance whose mask shares no bit with the ray's, at
+// its top-level leaf.  The count walk and the fill walk read the same two arrays and so take the same decision for every (ray, instance): the
+// offsets are what the fill writes.  k_instances_allhits_sort_row and inst_record only ever see pairs that are already in a row: no mask.
 #include <cstdio>
 
 #include "instances.hpp"
@@ -42,6 +46,11 @@ template <typename T> struct InstScene {
     const InstRec<T>* recs;
     const InstTree<T>* tbl;
 };
+// what a MASKED walk reads besides: the set's n u32, and NULL (all ones) or one u32 per ray.  Without MASKED neither is read.
+struct InstMasks {
+    const uint32_t* inst;
+    const uint32_t* ray;
+};
 
 // {distance, u, v} of (inst, s) for the WORLD ray (o, d): the world ray in the instance's frame by k_instances_trace's sequence, then the
 // triangle test — the operands and the operations of the walk, hence its bits
@@ -58,8 +67,11 @@ __device__ __forceinline__ void inst_record(const InstScene<T>& sc, const T o[3]
 // k_instances_trace's loop: one ray per lane, ONE loop; a lane is either in the top-level array with the world ray (inst == NONE) or in a
 // member's array with the object-space ray.  on_candidate(instance, shape, {distance, u, v}) for every pair of the double order whose
 // distance is below tm.  Every lane of the wave calls it (the slab test's variant is chosen per wave); a lane with !active walks nothing.
-template <typename T, typename F>
-__device__ __forceinline__ void instances_walk(const InstScene<T>& sc, const typename Traits<T>::Ray* __restrict__ rp, bool active, T tm, F&& on_candidate) {
+// MASKED: rmask is the ray's mask; an instance with (mk.inst[i] & rmask) == 0 is passed over at its leaf — no record, no re-expressed ray, no
+// member node — and the lane goes on at i + 1 in the top level.
+template <typename T, bool MASKED, typename F>
+__device__ __forceinline__ void instances_walk(const InstScene<T>& sc, const typename Traits<T>::Ray* __restrict__ rp, bool active, T tm,
+                                               const uint32_t* __restrict__ inst_mask, uint32_t rmask, F&& on_candidate) {
     T o[3] = {0, 0, 0}, d[3] = {0, 0, 0}, inv[3] = {0, 0, 0};
     bool fin = true, wfin = true;   // the current ray / the world ray passes ray_is_finite (the NaN-free slab test is exact for it)
     if (active) {
@@ -87,17 +99,21 @@ __device__ __forceinline__ void instances_walk(const InstScene<T>& sc, const typ
                     ray_triangle<T>(o, d, tris + 9 * (size_t)nd.shape, v);
                     if (v[0] < tm) on_candidate(inst, nd.shape, v);
                 } else {              // an instance's world box: into its tree with the ray in the object's frame
-                    top_next = i;
-                    inst = nd.shape;
-                    const InstRec<T> rec = load_rec<T>(sc.recs + inst);
-                    const InstTree<T> t = sc.tbl[rec.tree];
-                    T oo[3], dd[3];
+                    bool visible = true;
+                    if constexpr (MASKED) visible = (inst_mask[nd.shape] & rmask) != 0u;   // (hidden: the lane stays here and goes on at i + 1)
+                    if (visible) {
+                        top_next = i;
+                        inst = nd.shape;
+                        const InstRec<T> rec = load_rec<T>(sc.recs + inst);
+                        const InstTree<T> t = sc.tbl[rec.tree];
+                        T oo[3], dd[3];
 #pragma unroll
-                    for (int k = 0; k < 3; k++) { oo[k] = row4<T>(rec.y + 4 * k, o); dd[k] = row3<T>(rec.y + 4 * k, d); }
+                        for (int k = 0; k < 3; k++) { oo[k] = row4<T>(rec.y + 4 * k, o); dd[k] = row3<T>(rec.y + 4 * k, d); }
 #pragma unroll
-                    for (int k = 0; k < 3; k++) { o[k] = oo[k]; d[k] = dd[k]; inv[k] = (T)1 / dd[k]; }
-                    fin = ray_is_finite<T>(o, inv);
-                    nodes = t.trav; tris = t.tris; i = 0; end = t.n_trav;
+                        for (int k = 0; k < 3; k++) { o[k] = oo[k]; d[k] = dd[k]; inv[k] = (T)1 / dd[k]; }
+                        fin = ray_is_finite<T>(o, inv);
+                        nodes = t.trav; tris = t.tris; i = 0; end = t.n_trav;
+                    }
                 }
             }
             if (inst != NONE && i >= end) {   // the member's array has ended: back to the top level, behind the leaf that sent the lane here
@@ -110,25 +126,27 @@ __device__ __forceinline__ void instances_walk(const InstScene<T>& sc, const typ
     }
 }
 
-template <typename T>
+template <typename T, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_instances_allhits_count(InstScene<T> sc, const typename Traits<T>::Ray* __restrict__ rays, const T* __restrict__ tmaxs,
-                                                                 uint32_t n, uint32_t* __restrict__ counts) {
+                                                                 uint32_t n, uint32_t* __restrict__ counts, InstMasks mk) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = q < n;
     const T tm = active && tmaxs ? tmaxs[q] : Traits<T>::inf();
+    uint32_t rmask = 0xFFFFFFFFu;
+    if constexpr (MASKED) { if (active && mk.ray) rmask = mk.ray[q]; }
     uint32_t cnt = 0;
-    instances_walk<T>(sc, rays + (active ? q : 0u), active, tm, [&](uint32_t, uint32_t, const T*) { cnt++; });
+    instances_walk<T, MASKED>(sc, rays + (active ? q : 0u), active, tm, mk.inst, rmask, [&](uint32_t, uint32_t, const T*) { cnt++; });
     if (active) counts[q] = cnt;
 }
 
 // ---- the second walk ----------------------------------------------------------------------------------------------------------------
 // list_shape: NULL, or total u32 — the shapes of the long rows in the double order (a sorted batch that has long rows)
 // pos:        NULL, or total u32 — the positions of the rows beyond INST_ALLHITS_LDS_ROW_MAX (a sorted batch that has such rows)
-template <typename T, bool SORTED>
+template <typename T, bool SORTED, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_instances_allhits_fill(InstScene<T> sc, const typename Traits<T>::Ray* __restrict__ rays, const T* __restrict__ tmaxs,
                                                                 uint32_t n, const uint32_t* __restrict__ offsets, uint32_t* __restrict__ instance,
                                                                 uint32_t* __restrict__ shape, T* __restrict__ vals, uint32_t* __restrict__ list_shape,
-                                                                uint32_t* __restrict__ pos) {
+                                                                uint32_t* __restrict__ pos, InstMasks mk) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t beg = q < n ? offsets[q] : 0u, len = q < n ? offsets[q + 1] - beg : 0u;
     // (the count pass walked an empty row's ray: nothing to write.  Leaving it out can change the wave's `fast` choice against the count
@@ -142,8 +160,10 @@ __global__ __launch_bounds__(256) void k_instances_allhits_fill(InstScene<T> sc,
     const bool insert = SORTED && len <= INST_ALLHITS_LANE_ROW_MAX;
     const bool with_list = SORTED && !insert && list_shape != nullptr;
     const bool with_pos = SORTED && pos != nullptr && len > INST_ALLHITS_LDS_ROW_MAX;
+    uint32_t rmask = 0xFFFFFFFFu;
+    if constexpr (MASKED) { if (active && mk.ray) rmask = mk.ray[q]; }   // (the count walk's decision: the same two arrays)
     uint32_t cnt = 0;
-    instances_walk<T>(sc, rp, active, tm, [&](uint32_t inst, uint32_t s, const T* v) {
+    instances_walk<T, MASKED>(sc, rp, active, tm, mk.inst, rmask, [&](uint32_t inst, uint32_t s, const T* v) {
         if (cnt >= len) return;   // (never: this walk is the count pass's; a lane stays inside its own region whatever happens)
         if (insert) {
             // ascending list: the first element e with dist < e is where a scan from the back stops, so search and shift are one loop
@@ -232,19 +252,20 @@ __global__ __launch_bounds__(ROWS_SORT_THREADS) void k_instances_allhits_sort_ro
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool MASKED>
 static void instances_allhits_launch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, bool sorted, bool count_only,
-                                     bvhgpu_hits* h) {
+                                     bvhgpu_hits* h, const uint32_t* ray_mask_dev) {
     hipStream_t st = s->ctx->stream;
+    const InstMasks mk = {MASKED ? s->masks.as<uint32_t>() : nullptr, MASKED ? ray_mask_dev : nullptr};
     const InstScene<T> sc = {s->top->trav.as<TravNode<T>>(), (uint32_t)s->top->n_trav, s->recs.as<InstRec<T>>(), s->table.as<InstTree<T>>()};
     const uint32_t n32 = (uint32_t)n;
     const dim3 rgrid((unsigned)((n + 255) / 256)), block(256);
     const RowsPlan plan = {sorted, count_only, INST_ALLHITS_LANE_ROW_MAX, INST_ALLHITS_LDS_ROW_MAX, 3 * sizeof(T), true, true};
     rows_run(h, n, plan,
-             [&](uint32_t* counts) { hipLaunchKernelGGL((k_instances_allhits_count<T>), rgrid, block, 0, st, sc, rays_dev, tmax_dev, n32, counts); },
+             [&](uint32_t* counts) { hipLaunchKernelGGL((k_instances_allhits_count<T, MASKED>), rgrid, block, 0, st, sc, rays_dev, tmax_dev, n32, counts, mk); },
              [&](const RowsOut& o, auto SORTED) {
-                 hipLaunchKernelGGL((k_instances_allhits_fill<T, decltype(SORTED)::value>), rgrid, block, 0, st, sc, rays_dev, tmax_dev, n32, o.offsets, o.instance,
-                                    o.shape, static_cast<T*>(o.vals), o.list_shape, o.pos);
+                 hipLaunchKernelGGL((k_instances_allhits_fill<T, decltype(SORTED)::value, MASKED>), rgrid, block, 0, st, sc, rays_dev, tmax_dev, n32, o.offsets,
+                                    o.instance, o.shape, static_cast<T*>(o.vals), o.list_shape, o.pos, mk);
              },
              [&](const RowsOut& o, uint32_t n_long) {
                  hipLaunchKernelGGL((k_instances_allhits_sort_row<T>), dim3(n_long), dim3(ROWS_SORT_THREADS), 0, st, sc, o.work, rays_dev, o.offsets, o.instance,
@@ -252,17 +273,23 @@ static void instances_allhits_launch(bvhgpu_instances* s, const typename Traits<
              });
 }
 
+// masked: bvhgpu_instances_allhits_masked_* — the set's masks against ray_mask_dev (NULL: all ones); otherwise ray_mask_dev is not looked at
 template <typename T>
-void instances_allhits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, unsigned flags, bvhgpu_hits* h) {
+void instances_allhits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, unsigned flags, bvhgpu_hits* h,
+                             bool masked, const uint32_t* ray_mask_dev) {
     const bool sorted = (flags & BVHGPU_INSTANCES_ALLHITS_LIST_ORDER) == 0;
     const bool count_only = (flags & BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY) != 0;
     char name[96];
-    if (count_only) std::snprintf(name, sizeof name, "bvhgpu::k_instances_allhits_count<%s>", walk_type_name<T>());
-    else std::snprintf(name, sizeof name, "bvhgpu::k_instances_allhits_fill<%s, %s>", walk_type_name<T>(), sorted ? "true" : "false");
+    const char* m = masked ? "true" : "false";
+    if (count_only) std::snprintf(name, sizeof name, "bvhgpu::k_instances_allhits_count<%s, %s>", walk_type_name<T>(), m);
+    else std::snprintf(name, sizeof name, "bvhgpu::k_instances_allhits_fill<%s, %s, %s>", walk_type_name<T>(), sorted ? "true" : "false", m);
     rows_batch(h, s->ctx, Traits<T>::dtype, TRAVERSE_INST_ALLHITS, BVHGPU_LEAF_TRIANGLE, count_only, n, s->n == 0, name,   // (empty: no instances)
-               [&] { instances_allhits_launch<T>(s, rays_dev, tmax_dev, n, sorted, count_only, h); });
+               [&] {
+                   if (masked) instances_allhits_launch<T, true>(s, rays_dev, tmax_dev, n, sorted, count_only, h, ray_mask_dev);
+                   else instances_allhits_launch<T, false>(s, rays_dev, tmax_dev, n, sorted, count_only, h, nullptr);
+               });
 }
-template void instances_allhits_batch<float>(bvhgpu_instances*, const bvhgpu_ray_f32*, const float*, size_t, unsigned, bvhgpu_hits*);
-template void instances_allhits_batch<double>(bvhgpu_instances*, const bvhgpu_ray_f64*, const double*, size_t, unsigned, bvhgpu_hits*);
+template void instances_allhits_batch<float>(bvhgpu_instances*, const bvhgpu_ray_f32*, const float*, size_t, unsigned, bvhgpu_hits*, bool, const uint32_t*);
+template void instances_allhits_batch<double>(bvhgpu_instances*, const bvhgpu_ray_f64*, const double*, size_t, unsigned, bvhgpu_hits*, bool, const uint32_t*);
 
 }  // namespace bvhgpu

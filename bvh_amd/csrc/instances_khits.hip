@@ -16,6 +16,10 @@
 // its own column, only the walk's __any votes cross lanes: no barrier.  `len`, `full` and `bound` live in registers; the list is touched
 // only when a candidate is accepted.  Write-out: the whole record of every list element is computed again from the world ray and (instance,
 // shape) by inst_record's sequence — the device functions and the operands of bvhgpu_instances_allhits_*, hence its bits.
+//
+// MASKED (bvhgpu_instances_khits_masked_*): inst_mask is the set's n u32, ray_mask NULL (all ones) or one u32 per ray; an
+// instance whose mask shares no bit with the ray's is passed over at its top-level leaf — no record, no re-expressed ray, no member node —
+// and the lane goes on at i + 1.  The write-out sees only pairs that are in the list: no mask.  Without MASKED neither pointer is read.
 #include "instances.hpp"
 #include "walk.hpp"
 
@@ -39,10 +43,11 @@ template <typename T> struct InstKhitsScene {
     const InstTree<T>* tbl;
 };
 
-template <typename T>
+template <typename T, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_instances_khits(InstKhitsScene<T> sc, const typename Traits<T>::Ray* __restrict__ rays, const T* __restrict__ tmaxs,
                                                          uint32_t n, uint32_t k, uint32_t* __restrict__ out_instance, uint32_t* __restrict__ out_shape,
-                                                         T* __restrict__ out_vals) {
+                                                         T* __restrict__ out_vals, const uint32_t* __restrict__ inst_mask,
+                                                         const uint32_t* __restrict__ ray_mask) {
     extern __shared__ __align__(16) unsigned char ikh_lds[];
     const uint32_t block = blockDim.x;
     T* __restrict__ ld = reinterpret_cast<T*>(ikh_lds) + threadIdx.x;                                        // slot m: ld[m * block]
@@ -52,6 +57,8 @@ __global__ __launch_bounds__(256) void k_instances_khits(InstKhitsScene<T> sc, c
     const bool active = q < n;   // (a lane beyond the batch walks nothing and writes nothing, but takes part in the wave's votes)
     const typename Traits<T>::Ray* rp = rays + (active ? q : 0u);
     const T tm = active && tmaxs ? tmaxs[q] : Traits<T>::inf();
+    uint32_t rmask = 0xFFFFFFFFu;
+    if constexpr (MASKED) { if (active && ray_mask) rmask = ray_mask[q]; }
     T o[3] = {0, 0, 0}, d[3] = {0, 0, 0}, inv[3] = {0, 0, 0};
     bool fin = true, wfin = true;   // the current ray / the world ray passes ray_is_finite (the NaN-free slab test is exact for it)
     if (active) {
@@ -100,17 +107,21 @@ __global__ __launch_bounds__(256) void k_instances_khits(InstKhitsScene<T> sc, c
                         if (full) bound = ld[(k - 1) * block];
                     }
                 } else {              // an instance's world box: into its tree with the ray in the object's frame
-                    top_next = i;
-                    inst = nd.shape;
-                    const InstRec<T> rec = load_rec<T>(sc.recs + inst);
-                    const InstTree<T> t = sc.tbl[rec.tree];
-                    T oo[3], dd[3];
+                    bool visible = true;
+                    if constexpr (MASKED) visible = (inst_mask[nd.shape] & rmask) != 0u;   // (hidden: the lane stays here and goes on at i + 1)
+                    if (visible) {
+                        top_next = i;
+                        inst = nd.shape;
+                        const InstRec<T> rec = load_rec<T>(sc.recs + inst);
+                        const InstTree<T> t = sc.tbl[rec.tree];
+                        T oo[3], dd[3];
 #pragma unroll
-                    for (int c = 0; c < 3; c++) { oo[c] = row4<T>(rec.y + 4 * c, o); dd[c] = row3<T>(rec.y + 4 * c, d); }
+                        for (int c = 0; c < 3; c++) { oo[c] = row4<T>(rec.y + 4 * c, o); dd[c] = row3<T>(rec.y + 4 * c, d); }
 #pragma unroll
-                    for (int c = 0; c < 3; c++) { o[c] = oo[c]; d[c] = dd[c]; inv[c] = (T)1 / dd[c]; }
-                    fin = ray_is_finite<T>(o, inv);
-                    nodes = t.trav; tris = t.tris; i = 0; end = t.n_trav;
+                        for (int c = 0; c < 3; c++) { o[c] = oo[c]; d[c] = dd[c]; inv[c] = (T)1 / dd[c]; }
+                        fin = ray_is_finite<T>(o, inv);
+                        nodes = t.trav; tris = t.tris; i = 0; end = t.n_trav;
+                    }
                 }
             }
             if (inst != NONE && i >= end) {   // the member's array has ended: back to the top level, behind the leaf that sent the lane here
@@ -163,9 +174,10 @@ __global__ __launch_bounds__(256) void k_instances_khits_fill(uint32_t* __restri
 }
 
 // the rays of a batch over a committed instance set (the caller has checked commit, staleness and n x k < 2^32)
+// masked: bvhgpu_instances_khits_masked_* — the set's masks against ray_mask_dev (NULL: all ones); otherwise ray_mask_dev is not looked at
 template <typename T>
 void instances_khits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, uint32_t k,
-                           uint32_t* out_instance_dev, uint32_t* out_shape_dev, T* out_vals_dev) {
+                           uint32_t* out_instance_dev, uint32_t* out_shape_dev, T* out_vals_dev, bool masked, const uint32_t* ray_mask_dev) {
     if (!n) return;
     hipStream_t st = s->ctx->stream;
     if (s->n == 0 || s->top == nullptr || s->top->n_trav == 0) {   // no instance, or an empty top level: every row is padding
@@ -178,11 +190,18 @@ void instances_khits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* r
     const InstKhitsScene<T> sc = {s->top->trav.as<TravNode<T>>(), (uint32_t)s->top->n_trav, s->recs.as<InstRec<T>>(), s->table.as<InstTree<T>>()};
     const unsigned bs = instances_khits_block<T>(k);
     const size_t lds = (size_t)bs * k * (sizeof(T) + 8);
-    hipLaunchKernelGGL((k_instances_khits<T>), dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), lds, st, sc, rays_dev, tmax_dev, (uint32_t)n, k,
-                       out_instance_dev, out_shape_dev, out_vals_dev);
+    const dim3 grid((unsigned)((n + bs - 1) / bs)), block(bs);
+    if (masked)
+        hipLaunchKernelGGL((k_instances_khits<T, true>), grid, block, lds, st, sc, rays_dev, tmax_dev, (uint32_t)n, k, out_instance_dev, out_shape_dev,
+                           out_vals_dev, s->masks.as<uint32_t>(), ray_mask_dev);
+    else
+        hipLaunchKernelGGL((k_instances_khits<T, false>), grid, block, lds, st, sc, rays_dev, tmax_dev, (uint32_t)n, k, out_instance_dev, out_shape_dev,
+                           out_vals_dev, nullptr, nullptr);
     BVH_HIP(hipGetLastError());
 }
-template void instances_khits_batch<float>(bvhgpu_instances*, const bvhgpu_ray_f32*, const float*, size_t, uint32_t, uint32_t*, uint32_t*, float*);
-template void instances_khits_batch<double>(bvhgpu_instances*, const bvhgpu_ray_f64*, const double*, size_t, uint32_t, uint32_t*, uint32_t*, double*);
+template void instances_khits_batch<float>(bvhgpu_instances*, const bvhgpu_ray_f32*, const float*, size_t, uint32_t, uint32_t*, uint32_t*, float*, bool,
+                                           const uint32_t*);
+template void instances_khits_batch<double>(bvhgpu_instances*, const bvhgpu_ray_f64*, const double*, size_t, uint32_t, uint32_t*, uint32_t*, double*, bool,
+                                            const uint32_t*);
 
 }  // namespace bvhgpu

@@ -48,11 +48,99 @@ class InstancesTreeForm:
         return inst[:, 0], shape[:, 0], dist[:, 0]
 
 
-class Instances(InstancesTreeForm, _Typed):
+class InstancesMasks:
+    """Per-instance visibility masks (bvhgpu_instances_set_masks and the *_masked_* ray entries), which Instances inherits.  Every instance
+    i carries a 32-bit mask M[i] (all ones in a new set), a masked batch one 32-bit mask R[j] per ray, and instance i is visible to ray j
+    iff M[i] & R[j] != 0.  A masked method answers what its unmasked counterpart would over the set without the instances hidden from
+    that ray — same order of ties, same bits — and the walk passes over a hidden instance without entering its tree.  The masks are no
+    part of the pose: update() keeps them, setting them commits nothing.  Every other method of the set (closest_hits, any_hits, occluded,
+    khits_batch, allhits_batch and the point and region queries) ignores the masks: every instance is visible to it.
+    Kept apart from Instances' own methods so that the call recording of those (tests/golden/instances_calls.json) stays as it is;
+    tests/test_instances_masks_marshal_cpu.py holds these to what they hand to the C ABI.
+
+    ray_mask, everywhere: None (all ones for every ray), a Python int in [0, 2^32) (the same mask for every ray) or n values in the rays'
+    memory — numpy integers for HOST rays, a torch.int32 tensor on the rays' device for rays in HBM (its bits are the masks)."""
+
+    def set_masks(self, masks) -> "InstancesMasks":
+        """bvhgpu_instances_set_masks: one 32-bit mask per instance — numpy integers / a list (HOST) or a torch.int32 GPU tensor — or None
+        for all ones again.  In place when it returns; needs no update() and is allowed on a set whose last update failed."""
+        if masks is None:
+            mp, mem = None, _lib.HOST
+        elif api._is_device_tensor(masks):
+            keep, mp = api._mask_in(masks, masks, self.n, DEVICE, "masks", "instances")
+            mem = DEVICE
+            api._torch_sync(keep.device)
+        else:
+            keep, mp = api._mask_in(np.asarray(masks), None, self.n, _lib.HOST, "masks", "instances")
+            mem = _lib.HOST
+        check(_lib.load().bvhgpu_instances_set_masks(self._s, mp, self.n, mem), self.ctx._h)
+        return self
+
+    @property
+    def masks(self) -> np.ndarray:
+        """M, uint32[n]"""
+        out = np.zeros(self.n, dtype=np.uint32)
+        check(_lib.load().bvhgpu_instances_masks(self._s, ptr(out), _lib.HOST), self.ctx._h)
+        return out
+
+    def _trace_masked(self, rays: RayBatch, ray_mask, tmax, flags: int):
+        self._check_rays(rays)
+        _keep, tp = api._side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
+        _mk, mp = api._mask_in(ray_mask, rays.device, rays.n, rays.mem, "ray_mask", "rays")
+        n = rays.n
+        out, (vp, ip, sp) = api._out_cols(rays.device.device if rays.mem == DEVICE else None, self.ft, ((n, 3), "float"), (n, "index"), (n, "index"))
+        fn = getattr(_lib.load(), f"bvhgpu_instances_trace_masked_{self.sfx}")
+        check(fn(self._s, rays._ptr(), tp, mp, n, rays.mem, flags, vp, ip, sp), self.ctx._h)
+        return tuple(out)
+
+    def closest_hits_masked(self, rays: RayBatch, ray_mask, tmax=None):
+        """closest_hits over the instances visible to each ray; returns what closest_hits returns"""
+        return self._trace_masked(rays, ray_mask, tmax, 0)
+
+    def any_hits_masked(self, rays: RayBatch, ray_mask, tmax=None):
+        """any_hits over the instances visible to each ray: the first candidate in walk order that is left; returns what any_hits returns"""
+        return self._trace_masked(rays, ray_mask, tmax, _lib.TRAVERSE_FIRST)
+
+    def occluded_masked(self, rays: RayBatch, ray_mask, tmax=None):
+        """bool[n]: does segment i hit any triangle of any instance visible to ray i"""
+        _, inst, _ = self.any_hits_masked(rays, ray_mask, tmax)
+        return inst != (NONE if isinstance(inst, np.ndarray) else -1)
+
+    def khits_masked_batch(self, rays: RayBatch, k: int, ray_mask, tmax=None):
+        """bvhgpu_instances_khits_masked_*: khits_batch over the instances visible to each ray; k and the returns are khits_batch's"""
+        self._check_rays(rays)
+        k = int(k)
+        rows = k if 1 <= k <= _lib.INSTANCES_KHITS_MAX_K else 0   # (out of range: the engine answers INVALID_ARG before it touches a buffer)
+        _keep, tp = api._side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
+        _mk, mp = api._mask_in(ray_mask, rays.device, rays.n, rays.mem, "ray_mask", "rays")
+        n = rays.n
+        out, (ip, sp, vp) = api._out_cols(rays.device.device if rays.mem == DEVICE else None, self.ft,
+                                          ((n, rows), "index"), ((n, rows), "index"), ((n, rows, 3), "float"))
+        fn = getattr(_lib.load(), f"bvhgpu_instances_khits_masked_{self.sfx}")
+        check(fn(self._s, rays._ptr(), tp, mp, n, rays.mem, k & 0xFFFFFFFF, ip, sp, vp), self.ctx._h)
+        return tuple(out)
+
+    def allhits_masked_batch(self, rays: RayBatch, ray_mask, tmax=None, sort: bool = True, count_only: bool = False) -> dict:
+        """bvhgpu_instances_allhits_masked_*: allhits_batch over the instances visible to each ray; sort, count_only and the returns are
+        allhits_batch's"""
+        self._check_rays(rays)
+        _keep, tp = api._side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
+        _mk, mp = api._mask_in(ray_mask, rays.device, rays.n, rays.mem, "ray_mask", "rays")
+        flags = (0 if sort else _lib.INSTANCES_ALLHITS_LIST_ORDER) | (_lib.INSTANCES_ALLHITS_COUNT_ONLY if count_only else 0)
+        offsets, instance, shape, vals = self._csr("allhits_masked", (rays._ptr(), tp, mp, rays.n, rays.mem, flags), rays.n,
+                                                   rays.device.device if rays.mem == DEVICE else None, count_only,
+                                                   ((), "index"), ((), "index"), ((3,), "float"), fetch="instances_allhits")
+        if count_only:
+            return dict(offsets=offsets)
+        return dict(offsets=offsets, instance=instance, shape=shape, vals=vals)
+
+
+class Instances(InstancesTreeForm, InstancesMasks, _Typed):
     """bvhgpu_instances: `trees` (Bvh / FlatBvh objects of one context and dtype, with set_triangles done; kept referenced), `tree_of[i]`
     the member of instance i, `transforms` n x 12 or n x 3 x 4 (row-major 3x4, object -> world) in the trees' dtype.  update() is the
     re-pose and the re-sync: call it after moving instances and after any rebuild, refit or set_triangles of a member tree; a trace on a
-    set whose member was rebuilt since raises INVALID_ARG ("instances are stale")."""
+    set whose member was rebuilt since raises INVALID_ARG ("instances are stale").  The *_masked methods (InstancesMasks) see only the
+    instances whose mask shares a bit with the ray's; every other method ignores the masks."""
 
     def __init__(self, trees: Sequence, tree_of, transforms, ctx: Optional[Context] = None):
         trees = list(trees)
@@ -104,9 +192,10 @@ class Instances(InstancesTreeForm, _Typed):
         if rays.sfx != self.sfx:
             raise BvhGpuError(_lib.DTYPE_MISMATCH, "ray dtype differs from the instance set's dtype")
 
-    def _csr(self, entry: str, args, n: int, dev, count_only: bool, *cols):
+    def _csr(self, entry: str, args, n: int, dev, count_only: bool, *cols, fetch: Optional[str] = None):
         """one CSR batch into the set's own result object (made on first use: its buffers are reused by every batch) and its fetch:
-        bvhgpu_instances_<entry>_* with `args`, then api._fetch_csr with the columns given as (shape of one row, kind) or None"""
+        bvhgpu_instances_<entry>_* with `args`, then api._fetch_csr with the columns given as (shape of one row, kind) or None.  fetch:
+        the fetch entry of an <entry> whose result is of another entry's kind (allhits_masked: instances_allhits)"""
         if dev is not None:
             api._torch_sync(dev)
         if getattr(self, "_hits", None) is None:
@@ -114,7 +203,7 @@ class Instances(InstancesTreeForm, _Typed):
         hits = self._hits
         check(getattr(_lib.load(), f"bvhgpu_instances_{entry}_{self.sfx}")(self._s, *args, C.byref(hits.h)), self.ctx._h)
         rows = 0 if count_only else hits._total()
-        return api._fetch_csr(f"instances_{entry}", hits, n, rows, self.ft, dev, *[c and ((rows,) + c[0], c[1]) for c in cols])
+        return api._fetch_csr(fetch or f"instances_{entry}", hits, n, rows, self.ft, dev, *[c and ((rows,) + c[0], c[1]) for c in cols])
 
     def _trace(self, rays: RayBatch, tmax, flags: int):
         self._check_rays(rays)
@@ -128,16 +217,17 @@ class Instances(InstancesTreeForm, _Typed):
     def closest_hits(self, rays: RayBatch, tmax=None):
         """per ray the nearest triangle hit over all instances with distance < tmax[i] (None: +inf): (vals[n,3] = Intersection{distance, u,
         v} in the world ray's parameter, instance[n], shape[n] within that instance's tree); a miss is (+inf, 0, 0), NONE, NONE.  HOST rays:
-        numpy out, indices as uint32.  Rays in HBM: torch tensors on the same device, indices as torch.int32 (NONE reads as -1)."""
+        numpy out, indices as uint32.  Rays in HBM: torch tensors on the same device, indices as torch.int32 (NONE reads as -1).
+        Ignores the visibility masks (every instance is visible): closest_hits_masked looks at them."""
         return self._trace(rays, tmax, 0)
 
     def any_hits(self, rays: RayBatch, tmax=None):
         """BVHGPU_TRAVERSE_FIRST: the FIRST candidate in walk order (instances in the top level's order, shapes in the member's order) with
-        distance < tmax[i]; returns what closest_hits returns."""
+        distance < tmax[i]; returns what closest_hits returns.  Ignores the visibility masks (any_hits_masked looks at them)."""
         return self._trace(rays, tmax, _lib.TRAVERSE_FIRST)
 
     def occluded(self, rays: RayBatch, tmax=None):
-        """bool[n]: does segment i hit any triangle of any instance"""
+        """bool[n]: does segment i hit any triangle of any instance (visibility masks ignored: occluded_masked)"""
         _, inst, _ = self.any_hits(rays, tmax)
         return inst != (NONE if isinstance(inst, np.ndarray) else -1)
 
@@ -172,7 +262,7 @@ class Instances(InstancesTreeForm, _Typed):
         offsets alone (the hit counts).
         returns {offsets[n+1], instance[total], shape[total], vals[total, 3] = {distance, u, v}} (offsets only with count_only).  HOST rays:
         numpy out, offsets and indices as uint32.  Rays in HBM: torch tensors on the same device, indices as torch.int32, offsets as
-        torch.int64."""
+        torch.int64.  Ignores the visibility masks (allhits_masked_batch looks at them)."""
         self._check_rays(rays)
         _keep, tp = api._side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
         flags = (0 if sort else _lib.INSTANCES_ALLHITS_LIST_ORDER) | (_lib.INSTANCES_ALLHITS_COUNT_ONLY if count_only else 0)
@@ -190,7 +280,7 @@ class Instances(InstancesTreeForm, _Typed):
         first; k = 1 is closest_hits.  1 <= k <= _lib.INSTANCES_KHITS_MAX_K.
         returns (instance[n, k], shape[n, k], vals[n, k, 3] = {distance, u, v}); slots beyond the number of hits hold NONE, NONE and
         (+inf, 0, 0).  HOST rays: numpy out, indices as uint32.  Rays in HBM: torch tensors on the same device, written by the kernel,
-        indices as torch.int32 — so NONE reads as -1 there."""
+        indices as torch.int32 — so NONE reads as -1 there.  Ignores the visibility masks (khits_masked_batch looks at them)."""
         self._check_rays(rays)
         k = int(k)
         rows = k if 1 <= k <= _lib.INSTANCES_KHITS_MAX_K else 0   # (out of range: the engine answers INVALID_ARG before it touches a buffer)

@@ -1108,6 +1108,49 @@ int bvhgpu_instances_khits_f32(bvhgpu_instances *s, const bvhgpu_ray_f32 *rays, 
 int bvhgpu_instances_khits_f64(bvhgpu_instances *s, const bvhgpu_ray_f64 *rays, const double *tmax, size_t n_rays, int mem, uint32_t k,
                                uint32_t *out_instance /* n x k */, uint32_t *out_shape /* n x k */, double *out_vals /* n x k x 3 */);
 
+/* ---- per-instance visibility masks for the ray queries over an instanced scene: shadow rays that must not see the emitter, picking rays
+ * that see only selectable objects, one set serving several layers or LODs — without a set (a top level, an update per frame, an order of
+ * ties) per ray type and without filtering an all-hits CSR after the member walks of every hidden instance have been paid for.
+ *  - Every instance i of a set carries a 32-bit mask M[i].  A new set has M[i] = 0xFFFFFFFF for all i.
+ *  - A masked ray batch carries one 32-bit mask R[j] per ray.  A NULL `ray_mask` means 0xFFFFFFFF for every ray.
+ *  - Instance i is VISIBLE to ray j iff (M[i] & R[j]) != 0.
+ *  - The answer of a masked entry is the answer of the same unmasked entry computed over bvhgpu_instances_trace_*'s candidate table with
+ *    the rows of invisible instances removed.  That table is the double order: instances in the top level's list order, shapes in the
+ *    member's list order.
+ *  - Nothing else changes: the strict < against tmax; closest's strict < with the earlier candidate keeping a tie; first is the first
+ *    surviving candidate; a k-hits row is the stable ascending sort of the survivors cut to k, padded with BVHGPU_NONE and {+inf, 0, 0};
+ *    all-hits is sorted, list order or count only.
+ *  - A surviving candidate's bits are unchanged.  Its object-space ray is computed from the world ray and Y_i alone.
+ *  - The kernel skips an invisible instance at its top-level leaf.  It loads no record, re-expresses no ray and visits no member node.  The
+ *    lane stays in the top level and goes on at i + 1.  A hidden instance costs one 4-byte load.
+ *  - Still no pruning by distance.
+ *  - Masks are not part of the pose: bvhgpu_instances_update_* keeps them; setting them needs no commit and leaves the top level untouched;
+ *    setting them is allowed on a set whose last commit failed.
+ *  - The existing entries keep ignoring masks, so every instance is visible to them: bvhgpu_instances_trace_*, _khits_*, _allhits_*, and
+ *    the point and region families (_within_*, _knearest_*, _knearest_tree_*, _region_*).
+ * bvhgpu_instances_set_masks: `masks` is n u32 in `mem`, or NULL for all ones again; n must equal the set's number of instances.
+ * Synchronous: the masks are in place when it returns.  Refused with BVHGPU_INVALID_ARG, the set unchanged: a NULL set; a `mem` that is
+ * neither BVHGPU_HOST nor BVHGPU_DEVICE; an n that differs from the set's.
+ * bvhgpu_instances_masks: M, n u32, copied to `mem` (like bvhgpu_instances_boxes, but a set whose last commit failed answers too).
+ * The masked entries: `ray_mask` is n_rays u32 in the rays' memory, or NULL; every other argument, the flags and the range of k are the
+ * unmasked counterpart's.  Each makes the refusals of its counterpart, in the same order and with the same messages; a refused call
+ * touches no buffer.  An all-hits-masked result has the kind bvhgpu_instances_allhits_* produces and is read by
+ * bvhgpu_hits_fetch_instances_allhits. */
+int bvhgpu_instances_set_masks(bvhgpu_instances *s, const uint32_t *masks, size_t n, int mem);
+int bvhgpu_instances_masks(bvhgpu_instances *s, uint32_t *out, int mem);
+int bvhgpu_instances_trace_masked_f32(bvhgpu_instances *s, const bvhgpu_ray_f32 *rays, const float *tmax, const uint32_t *ray_mask, size_t n_rays,
+                                      int mem, unsigned flags, float *out_vals, uint32_t *out_instance, uint32_t *out_shape);
+int bvhgpu_instances_trace_masked_f64(bvhgpu_instances *s, const bvhgpu_ray_f64 *rays, const double *tmax, const uint32_t *ray_mask, size_t n_rays,
+                                      int mem, unsigned flags, double *out_vals, uint32_t *out_instance, uint32_t *out_shape);
+int bvhgpu_instances_khits_masked_f32(bvhgpu_instances *s, const bvhgpu_ray_f32 *rays, const float *tmax, const uint32_t *ray_mask, size_t n_rays,
+                                      int mem, uint32_t k, uint32_t *out_instance, uint32_t *out_shape, float *out_vals);
+int bvhgpu_instances_khits_masked_f64(bvhgpu_instances *s, const bvhgpu_ray_f64 *rays, const double *tmax, const uint32_t *ray_mask, size_t n_rays,
+                                      int mem, uint32_t k, uint32_t *out_instance, uint32_t *out_shape, double *out_vals);
+int bvhgpu_instances_allhits_masked_f32(bvhgpu_instances *s, const bvhgpu_ray_f32 *rays, const float *tmax, const uint32_t *ray_mask, size_t n_rays,
+                                        int mem, unsigned flags, bvhgpu_hits **hits);
+int bvhgpu_instances_allhits_masked_f64(bvhgpu_instances *s, const bvhgpu_ray_f64 *rays, const double *tmax, const uint32_t *ray_mask, size_t n_rays,
+                                        int mem, unsigned flags, bvhgpu_hits **hits);
+
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */
 typedef struct { float build_ms, flatten_ms, traverse_kernel_ms, traverse_total_ms; } bvhgpu_timings;

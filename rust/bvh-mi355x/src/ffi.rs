@@ -251,6 +251,14 @@ extern "C" {
     // the k nearest hits per ray over an instance set (out_instance / out_shape: n_rays x k, out_vals: n_rays x k x 3; padding = BVHGPU_NONE / BVHGPU_NONE / {+inf, 0, 0}; 1 <= k <= BVHGPU_INSTANCES_KHITS_MAX_K; synchronous, no result object)
     pub fn bvhgpu_instances_khits_f32(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_vals: *mut f32) -> c_int;
     pub fn bvhgpu_instances_khits_f64(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f64, tmax: *const f64, n_rays: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_vals: *mut f64) -> c_int;
+    pub fn bvhgpu_instances_set_masks(s: *mut bvhgpu_instances, masks: *const u32, n: usize, mem: c_int) -> c_int;
+    pub fn bvhgpu_instances_masks(s: *mut bvhgpu_instances, out: *mut u32, mem: c_int) -> c_int;
+    pub fn bvhgpu_instances_trace_masked_f32(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f32, tmax: *const f32, ray_mask: *const u32, n_rays: usize, mem: c_int, flags: c_uint, out_vals: *mut f32, out_instance: *mut u32, out_shape: *mut u32) -> c_int;
+    pub fn bvhgpu_instances_trace_masked_f64(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f64, tmax: *const f64, ray_mask: *const u32, n_rays: usize, mem: c_int, flags: c_uint, out_vals: *mut f64, out_instance: *mut u32, out_shape: *mut u32) -> c_int;
+    pub fn bvhgpu_instances_khits_masked_f32(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f32, tmax: *const f32, ray_mask: *const u32, n_rays: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_vals: *mut f32) -> c_int;
+    pub fn bvhgpu_instances_khits_masked_f64(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f64, tmax: *const f64, ray_mask: *const u32, n_rays: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_vals: *mut f64) -> c_int;
+    pub fn bvhgpu_instances_allhits_masked_f32(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f32, tmax: *const f32, ray_mask: *const u32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_instances_allhits_masked_f64(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f64, tmax: *const f64, ray_mask: *const u32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_instances_boxes(s: *mut bvhgpu_instances, out: *mut c_void, mem: c_int) -> c_int;
     pub fn bvhgpu_instances_info(s: *const bvhgpu_instances, dtype: *mut c_int, n_trees: *mut usize, n_instances: *mut usize) -> c_int;
     pub fn bvhgpu_instances_destroy(s: *mut bvhgpu_instances);

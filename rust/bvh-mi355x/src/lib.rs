@@ -1080,6 +1080,117 @@ impl<T: GpuScalar> GpuInstances<T> {
         }
         (instance, shape, vals)
     }
+
+    /// One 32-bit visibility mask per instance (`bvhgpu_instances_set_masks`), or `None` for all ones again — what a new set has.  Instance
+    /// `i` is visible to ray `j` of a `*_masked` call iff `masks[i] & ray_mask[j] != 0`.  No part of the pose: `update` keeps the masks,
+    /// setting them commits nothing.  `trace`, `khits`, `allhits` and the point and region queries ignore them.
+    pub fn set_masks(&mut self, masks: Option<&[u32]>) {
+        if let Some(m) = masks {
+            assert_eq!(m.len(), self.n, "one mask per instance");
+        }
+        let rc = unsafe { ffi::bvhgpu_instances_set_masks(self.set, masks.map_or(core::ptr::null(), |m| m.as_ptr()), self.n, ffi::BVHGPU_HOST) };
+        check(self.ctx, rc);
+    }
+
+    /// `trace` over the instances visible to each ray (`bvhgpu_instances_trace_masked_*`); `ray_mask`: one mask per ray, `None`: all ones
+    pub fn trace_masked(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>, ray_mask: Option<&[u32]>, first: bool) -> Vec<InstanceHit<T>> {
+        if let Some(m) = tmax {
+            assert_eq!(m.len(), rays.len(), "tmax needs one value per ray");
+        }
+        if let Some(m) = ray_mask {
+            assert_eq!(m.len(), rays.len(), "ray_mask needs one value per ray");
+        }
+        let raw: Vec<T::RayC> = rays.iter().map(T::ray_to_ffi).collect();
+        let n = raw.len();
+        let mut vals = vec![T::default(); 3 * n];
+        let mut inst = vec![0u32; n];
+        let mut shape = vec![0u32; n];
+        let flags: c_uint = if first { ffi::BVHGPU_TRAVERSE_FIRST } else { 0 };
+        let mp = ray_mask.map_or(core::ptr::null(), |m| m.as_ptr());
+        let rc = unsafe {
+            if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_trace_masked_f32(self.set, raw.as_ptr().cast(), tmax.map_or(core::ptr::null(), |m| m.as_ptr().cast()), mp, n,
+                                                       ffi::BVHGPU_HOST, flags, vals.as_mut_ptr().cast(), inst.as_mut_ptr(), shape.as_mut_ptr())
+            } else {
+                ffi::bvhgpu_instances_trace_masked_f64(self.set, raw.as_ptr().cast(), tmax.map_or(core::ptr::null(), |m| m.as_ptr().cast()), mp, n,
+                                                       ffi::BVHGPU_HOST, flags, vals.as_mut_ptr().cast(), inst.as_mut_ptr(), shape.as_mut_ptr())
+            }
+        };
+        check(self.ctx, rc);
+        (0..n).map(|j| InstanceHit { intersection: Intersection::new(vals[3 * j], vals[3 * j + 1], vals[3 * j + 2]), instance: inst[j], shape: shape[j] }).collect()
+    }
+
+    /// `khits` over the instances visible to each ray (`bvhgpu_instances_khits_masked_*`)
+    pub fn khits_masked(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>, ray_mask: Option<&[u32]>, k: usize) -> (Vec<u32>, Vec<u32>, Vec<T>) {
+        if let Some(m) = tmax {
+            assert_eq!(m.len(), rays.len(), "tmax needs one value per ray");
+        }
+        if let Some(m) = ray_mask {
+            assert_eq!(m.len(), rays.len(), "ray_mask needs one value per ray");
+        }
+        let raw: Vec<T::RayC> = rays.iter().map(T::ray_to_ffi).collect();
+        let n = raw.len();
+        let k32 = u32::try_from(k).unwrap_or(u32::MAX);   // (out of range: the engine answers BVHGPU_INVALID_ARG and `check` panics with its message)
+        let slots = if (1..=ffi::BVHGPU_INSTANCES_KHITS_MAX_K).contains(&k32) { n * k } else { 0 };
+        let (mut instance, mut shape, mut vals) = (vec![0u32; slots], vec![0u32; slots], vec![T::default(); 3 * slots]);
+        unsafe {
+            let tp = tmax.map_or(core::ptr::null(), |m| m.as_ptr());
+            let mp = ray_mask.map_or(core::ptr::null(), |m| m.as_ptr());
+            let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_khits_masked_f32(self.set, raw.as_ptr().cast(), tp.cast(), mp, n, ffi::BVHGPU_HOST, k32, instance.as_mut_ptr(),
+                                                       shape.as_mut_ptr(), vals.as_mut_ptr().cast())
+            } else {
+                ffi::bvhgpu_instances_khits_masked_f64(self.set, raw.as_ptr().cast(), tp.cast(), mp, n, ffi::BVHGPU_HOST, k32, instance.as_mut_ptr(),
+                                                       shape.as_mut_ptr(), vals.as_mut_ptr().cast())
+            };
+            check(self.ctx, rc);
+        }
+        (instance, shape, vals)
+    }
+
+    /// `allhits` over the instances visible to each ray (`bvhgpu_instances_allhits_masked_*`); the result is read like `allhits`' own
+    pub fn allhits_masked(&self, rays: &[Ray<T, 3>], tmax: Option<&[T]>, ray_mask: Option<&[u32]>, sort: bool, count_only: bool) -> (Vec<u32>, Vec<u32>, Vec<u32>, Vec<T>) {
+        if let Some(m) = tmax {
+            assert_eq!(m.len(), rays.len(), "tmax needs one value per ray");
+        }
+        if let Some(m) = ray_mask {
+            assert_eq!(m.len(), rays.len(), "ray_mask needs one value per ray");
+        }
+        let raw: Vec<T::RayC> = rays.iter().map(T::ray_to_ffi).collect();
+        let n = raw.len();
+        let flags: c_uint = (if sort { 0 } else { ffi::BVHGPU_INSTANCES_ALLHITS_LIST_ORDER })
+            | (if count_only { ffi::BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY } else { 0 });
+        let mut hits = core::ptr::null_mut();
+        let mut offsets = vec![0u32; n + 1];
+        let (mut instance, mut shape, mut vals) = (Vec::new(), Vec::new(), Vec::new());
+        unsafe {
+            let tp = tmax.map_or(core::ptr::null(), |m| m.as_ptr());
+            let mp = ray_mask.map_or(core::ptr::null(), |m| m.as_ptr());
+            let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_allhits_masked_f32(self.set, raw.as_ptr().cast(), tp.cast(), mp, n, ffi::BVHGPU_HOST, flags, &mut hits)
+            } else {
+                ffi::bvhgpu_instances_allhits_masked_f64(self.set, raw.as_ptr().cast(), tp.cast(), mp, n, ffi::BVHGPU_HOST, flags, &mut hits)
+            };
+            check(self.ctx, rc);   // (a refused batch made no result object)
+            let mut total = 0u64;
+            let mut rc = ffi::bvhgpu_hits_info(hits, core::ptr::null_mut(), &mut total, core::ptr::null_mut());
+            if rc == ffi::BVHGPU_OK {
+                let rows = if count_only { 0 } else { total as usize };
+                instance.resize(rows, 0u32);
+                shape.resize(rows, 0u32);
+                vals.resize(3 * rows, T::default());
+                let (ip, sp, vp) = if count_only {
+                    (core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut())
+                } else {
+                    (instance.as_mut_ptr(), shape.as_mut_ptr(), vals.as_mut_ptr() as *mut c_void)
+                };
+                rc = ffi::bvhgpu_hits_fetch_instances_allhits(hits, offsets.as_mut_ptr(), ip, sp, vp, ffi::BVHGPU_HOST);
+            }
+            ffi::bvhgpu_hits_destroy(hits);   // before the check, which panics on a failure
+            check(self.ctx, rc);
+        }
+        (offsets, instance, shape, vals)
+    }
 }
 
 impl<T: GpuScalar> Drop for GpuInstances<T> {

@@ -219,6 +219,14 @@ SYMBOLS = [
     ("bvhgpu_instances_khits_masked_f64", _i, [_vp, _vp, _vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp]),
     ("bvhgpu_instances_allhits_masked_f32", _i, [_vp, _vp, _vp, _vp, _sz, _i, _u, _pp]),
     ("bvhgpu_instances_allhits_masked_f64", _i, [_vp, _vp, _vp, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_instances_within_masked_f32", _i, [_vp, _vp, _vp, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_instances_within_masked_f64", _i, [_vp, _vp, _vp, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_instances_knearest_masked_f32", _i, [_vp, _vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp]),
+    ("bvhgpu_instances_knearest_masked_f64", _i, [_vp, _vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp]),
+    ("bvhgpu_instances_knearest_tree_masked_f32", _i, [_vp, _vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp, _vp]),
+    ("bvhgpu_instances_knearest_tree_masked_f64", _i, [_vp, _vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp, _vp]),
+    ("bvhgpu_instances_region_masked_f32", _i, [_vp, _vp, _vp, _sz, C.c_uint32, _i, _u, _pp]),
+    ("bvhgpu_instances_region_masked_f64", _i, [_vp, _vp, _vp, _sz, C.c_uint32, _i, _u, _pp]),
     ("bvhgpu_instances_boxes", _i, [_vp, _vp, _i]),
     ("bvhgpu_instances_info", _i, [_vp, C.POINTER(_i), C.POINTER(_sz), C.POINTER(_sz)]),
     ("bvhgpu_instances_destroy", None, [_vp]),

@@ -175,8 +175,14 @@ def _side_in(v, main, n: int, mem: int, ft, what: str, of: str, scalar_ok: bool 
     return keep, p
 
 
+def _needs(v, msg: str) -> None:
+    """an argument that has no default in the C ABI (max_dist of a within batch) must be given"""
+    if v is None:
+        raise BvhGpuError(_lib.INVALID_ARG, msg)
+
+
 def _mask_in(v, main, n: int, mem: int, what: str, of: str):
-    """The per-row 32-bit mask array of a batch (ray_mask of rays): n u32 in the memory `mem` of the main input `main` → (the object to keep
+    """The per-row 32-bit mask array of a batch (ray_mask of rays, point_mask of points, region_mask of regions): n u32 in the memory `mem` of the main input `main` → (the object to keep
     alive, its c_void_p); None → (None, None).  A Python int in [0, 2^32) is the same mask for every row.  HOST: numpy integers (or a
     list of them), int32 taken by its bits, anything else by its value.  DEVICE: a torch.int32 tensor on the main input's device, its bits
     taken as they are."""

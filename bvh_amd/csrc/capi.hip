@@ -1161,6 +1161,15 @@ int instances_current(bvhgpu_instances* s) {
 // refused call touches no buffer and leaves *hits and the set as they were.
 // The *_masked_* entries of trace, khits and allhits are the same functions with `masked`: the same rules in the same order, and ray_mask
 // (NULL: all ones) staged where the family stages tmax — a column of the row stage, or the result object's side buffer for all-hits.
+// Likewise the *_masked_* entries of within, knearest, knearest_tree and region with point_mask / region_mask: a column of the
+// row stage for the two padded-row families, the result object's mask buffer (stage_mask) for within and region.
+// a HOST mask array of a result-object family → its device pointer in h->maskbuf (every walk of the batch reads it); NULL and DEVICE as they are
+const uint32_t* stage_mask(bvhgpu_ctx* ctx, bvhgpu_hits* h, const uint32_t* mask, size_t n, int mem) {
+    if (!mask || !n || mem != BVHGPU_HOST) return n ? mask : nullptr;
+    h->maskbuf.reserve(n * 4);
+    BVH_HIP(hipMemcpyAsync(h->maskbuf.p, mask, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    return h->maskbuf.as<uint32_t>();
+}
 template <typename T>
 int do_instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays, const T* tmax, size_t n, int mem, unsigned flags, T* out_vals,
                        uint32_t* out_instance, uint32_t* out_shape, bool masked = false, const uint32_t* ray_mask = nullptr) {
@@ -1184,7 +1193,8 @@ int do_instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays,
     });
 }
 template <typename T>
-int do_instances_region(bvhgpu_instances* s, const T* planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits** hits) {
+int do_instances_region(bvhgpu_instances* s, const T* planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits** hits, bool masked = false,
+                        const uint32_t* region_mask = nullptr) {
     if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
     if (const int rc = rule_hits_arg(ctx, hits)) return rc;
@@ -1201,7 +1211,8 @@ int do_instances_region(bvhgpu_instances* s, const T* planes, size_t n, uint32_t
     return guarded(ctx, [&] {
         use_device(ctx);
         bvhgpu_hits* h = batch_hits(hits);
-        instances_region_batch<T>(s, stage_queries<T>(ctx, h, planes, n * m * 4 * sizeof(T), mem), n, m, flags, h);
+        const T* dev = stage_queries<T>(ctx, h, planes, n * m * 4 * sizeof(T), mem);
+        instances_region_batch<T>(s, dev, n, m, flags, h, masked, masked ? stage_mask(ctx, h, region_mask, n, mem) : nullptr);
         return (int)BVHGPU_OK;
     });
 }
@@ -1236,7 +1247,8 @@ int do_instances_allhits(bvhgpu_instances* s, const typename Traits<T>::Ray* ray
     });
 }
 template <typename T>
-int do_instances_within(bvhgpu_instances* s, const T* points, const T* max_dist, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
+int do_instances_within(bvhgpu_instances* s, const T* points, const T* max_dist, size_t n, int mem, unsigned flags, bvhgpu_hits** hits, bool masked = false,
+                        const uint32_t* point_mask = nullptr) {
     if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
     if (const int rc = rule_hits_arg(ctx, hits)) return rc;
@@ -1255,12 +1267,13 @@ int do_instances_within(bvhgpu_instances* s, const T* points, const T* max_dist,
         bvhgpu_hits* h = batch_hits(hits);
         const auto* dev = static_cast<const T*>(to_device(ctx, points, n * 3 * sizeof(T), mem, ctx->upload));
         const T* md = n ? stage_side<T>(ctx, h, max_dist, n, mem) : nullptr;
-        instances_within_batch<T>(s, dev, md, n, flags, h);
+        instances_within_batch<T>(s, dev, md, n, flags, h, masked, masked ? stage_mask(ctx, h, point_mask, n, mem) : nullptr);
         return (int)BVHGPU_OK;
     });
 }
 template <typename T>
-int do_instances_knearest(bvhgpu_instances* s, const T* points, size_t n, int mem, uint32_t k, uint32_t* out_instance, uint32_t* out_shape, T* out_dist) {
+int do_instances_knearest(bvhgpu_instances* s, const T* points, size_t n, int mem, uint32_t k, uint32_t* out_instance, uint32_t* out_shape, T* out_dist,
+                          bool masked = false, const uint32_t* point_mask = nullptr) {
     if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
     if (const int rc = rule_k(ctx, k, BVHGPU_INSTANCES_KNN_MAX_K, "BVHGPU_INSTANCES_KNN_MAX_K")) return rc;
@@ -1272,8 +1285,9 @@ int do_instances_knearest(bvhgpu_instances* s, const T* points, size_t n, int me
     if (const int rc = rule_rows_size(ctx, n, k, "too many results (points x k) in one call")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
-        RowStage st(ctx, mem, {{points, n * 3 * sizeof(T)}}, {{out_dist, n * k * sizeof(T)}, {out_instance, n * k * 4}, {out_shape, n * k * 4}});
-        instances_knearest_batch<T>(s, st.at<const T>(0), n, k, st.at<uint32_t>(2), st.at<uint32_t>(3), st.at<T>(1));
+        RowStage st(ctx, mem, {{points, n * 3 * sizeof(T)}, {masked ? point_mask : nullptr, masked ? n * 4 : 0}},
+                    {{out_dist, n * k * sizeof(T)}, {out_instance, n * k * 4}, {out_shape, n * k * 4}});
+        instances_knearest_batch<T>(s, st.at<const T>(0), n, k, st.at<uint32_t>(3), st.at<uint32_t>(4), st.at<T>(2), masked, n ? st.at<const uint32_t>(1) : nullptr);
         st.finish(true);   // in HBM too the rows are complete when the call returns, whichever stream reads them next
         return (int)BVHGPU_OK;
     });
@@ -1287,7 +1301,7 @@ int rule_members_built(const bvhgpu_instances* s) {
 }
 template <typename T>
 int do_instances_knearest_tree(bvhgpu_instances* s, const T* points, size_t n, int mem, uint32_t k, const T* max_dist, uint32_t* out_instance,
-                               uint32_t* out_shape, T* out_dist) {
+                               uint32_t* out_shape, T* out_dist, bool masked = false, const uint32_t* point_mask = nullptr) {
     if (!s) return no_set();
     bvhgpu_ctx* ctx = s->ctx;
     if (const int rc = rule_k(ctx, k, BVHGPU_INSTANCES_KNN_MAX_K, "BVHGPU_INSTANCES_KNN_MAX_K")) return rc;
@@ -1299,8 +1313,10 @@ int do_instances_knearest_tree(bvhgpu_instances* s, const T* points, size_t n, i
     if (const int rc = rule_rows_size(ctx, n, k, "too many results (points x k) in one call")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
-        RowStage st(ctx, mem, {{points, n * 3 * sizeof(T)}, {max_dist, n * sizeof(T)}}, {{out_dist, n * k * sizeof(T)}, {out_instance, n * k * 4}, {out_shape, n * k * 4}});
-        instances_knearest_tree_batch<T>(s, st.at<const T>(0), n, k, st.at<const T>(1), st.at<uint32_t>(3), st.at<uint32_t>(4), st.at<T>(2));
+        RowStage st(ctx, mem, {{points, n * 3 * sizeof(T)}, {max_dist, n * sizeof(T)}, {masked ? point_mask : nullptr, masked ? n * 4 : 0}},
+                    {{out_dist, n * k * sizeof(T)}, {out_instance, n * k * 4}, {out_shape, n * k * 4}});
+        instances_knearest_tree_batch<T>(s, st.at<const T>(0), n, k, st.at<const T>(1), st.at<uint32_t>(4), st.at<uint32_t>(5), st.at<T>(3), masked,
+                                         n ? st.at<const uint32_t>(2) : nullptr);
         st.finish(true);   // in HBM too the rows are complete when the call returns, whichever stream reads them next
         return (int)BVHGPU_OK;
     });
@@ -2148,6 +2164,38 @@ int bvhgpu_instances_allhits_masked_f32(bvhgpu_instances* s, const bvhgpu_ray_f3
 int bvhgpu_instances_allhits_masked_f64(bvhgpu_instances* s, const bvhgpu_ray_f64* rays, const double* tmax, const uint32_t* ray_mask, size_t n_rays, int mem,
                                         unsigned flags, bvhgpu_hits** hits) {
     return do_instances_allhits<double>(s, rays, tmax, n_rays, mem, flags, hits, true, ray_mask);
+}
+int bvhgpu_instances_within_masked_f32(bvhgpu_instances* s, const float* points, const float* max_dist, const uint32_t* point_mask, size_t n, int mem,
+                                       unsigned flags, bvhgpu_hits** hits) {
+    return do_instances_within<float>(s, points, max_dist, n, mem, flags, hits, true, point_mask);
+}
+int bvhgpu_instances_within_masked_f64(bvhgpu_instances* s, const double* points, const double* max_dist, const uint32_t* point_mask, size_t n, int mem,
+                                       unsigned flags, bvhgpu_hits** hits) {
+    return do_instances_within<double>(s, points, max_dist, n, mem, flags, hits, true, point_mask);
+}
+int bvhgpu_instances_knearest_masked_f32(bvhgpu_instances* s, const float* points, const uint32_t* point_mask, size_t n, int mem, uint32_t k,
+                                         uint32_t* out_instance, uint32_t* out_shape, float* out_dist) {
+    return do_instances_knearest<float>(s, points, n, mem, k, out_instance, out_shape, out_dist, true, point_mask);
+}
+int bvhgpu_instances_knearest_masked_f64(bvhgpu_instances* s, const double* points, const uint32_t* point_mask, size_t n, int mem, uint32_t k,
+                                         uint32_t* out_instance, uint32_t* out_shape, double* out_dist) {
+    return do_instances_knearest<double>(s, points, n, mem, k, out_instance, out_shape, out_dist, true, point_mask);
+}
+int bvhgpu_instances_knearest_tree_masked_f32(bvhgpu_instances* s, const float* points, const uint32_t* point_mask, size_t n, int mem, uint32_t k,
+                                              const float* max_dist, uint32_t* out_instance, uint32_t* out_shape, float* out_dist) {
+    return do_instances_knearest_tree<float>(s, points, n, mem, k, max_dist, out_instance, out_shape, out_dist, true, point_mask);
+}
+int bvhgpu_instances_knearest_tree_masked_f64(bvhgpu_instances* s, const double* points, const uint32_t* point_mask, size_t n, int mem, uint32_t k,
+                                              const double* max_dist, uint32_t* out_instance, uint32_t* out_shape, double* out_dist) {
+    return do_instances_knearest_tree<double>(s, points, n, mem, k, max_dist, out_instance, out_shape, out_dist, true, point_mask);
+}
+int bvhgpu_instances_region_masked_f32(bvhgpu_instances* s, const float* planes, const uint32_t* region_mask, size_t n, uint32_t m, int mem, unsigned flags,
+                                       bvhgpu_hits** hits) {
+    return do_instances_region<float>(s, planes, n, m, mem, flags, hits, true, region_mask);
+}
+int bvhgpu_instances_region_masked_f64(bvhgpu_instances* s, const double* planes, const uint32_t* region_mask, size_t n, uint32_t m, int mem, unsigned flags,
+                                       bvhgpu_hits** hits) {
+    return do_instances_region<double>(s, planes, n, m, mem, flags, hits, true, region_mask);
 }
 int bvhgpu_instances_boxes(bvhgpu_instances* s, void* out, int mem) {
     if (!s) return no_set();

@@ -296,7 +296,7 @@ struct bvhgpu_hits {
     // any-hit, box and sphere batches (bvhgpu_traverse_any_* / _box_* / _sphere_*): per-ray segment ends in HBM (the caller's, or `tmaxbuf`; NULL = +inf), read by every replay
     const void* pend_tmax = nullptr;
     bvhgpu::DevBuf tmaxbuf;              // HOST tmax staged here
-    bvhgpu::DevBuf maskbuf;              // HOST ray_mask of bvhgpu_instances_allhits_masked_* staged here (the count walk and the fill walk read it)
+    bvhgpu::DevBuf maskbuf;              // HOST ray_mask / point_mask / region_mask of the rows families' *_masked_* entries staged here (every walk of the batch reads it)
     bvhgpu::DevBuf any_key;              // n_rays u32: any-hit batches walked as items (walk.hpp WalkOut::any_key), all-ones between batches
     bool akey_clean = false;
     bvhgpu::DevBuf any_part;             // per workgroup of k_any_resolve: its occluded rays (k_any_publish adds them up)
@@ -456,8 +456,10 @@ void region_batch(bvhgpu_tree* t, const T* planes_dev, size_t n, uint32_t m, uns
 // region.hip: the same over a committed instance set (bvhgpu_instances_region_*): rows of (instance, shape) in h->rg_offsets / h->row_instance /
 // h->indices / h->rg_inside, or with BVHGPU_REGION_INSTANCES_ONLY rows of instances in h->indices.  Synchronous; throws Fail::Overflow when the
 // batch has more than 2^32-1 (region, instance) pairs or reports more than 2^32-1 shapes (the result object then holds an empty result).
+// masked (bvhgpu_instances_region_masked_*): I_q keeps the instances with s->masks[i] & region_mask_dev[q] (NULL: all ones) != 0.
 template <typename T>
-void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, uint32_t m, unsigned flags, bvhgpu_hits* h);
+void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, uint32_t m, unsigned flags, bvhgpu_hits* h, bool masked = false,
+                            const uint32_t* region_mask_dev = nullptr);
 // instances_allhits.hip: every hit per ray over a committed instance set as a CSR (bvhgpu_instances_allhits_*); flags:
 // BVHGPU_INSTANCES_ALLHITS_*; tmax_dev: NULL or n segment ends.  Synchronous: h->offsets / h->row_instance / h->indices / h->row_vals and
 // h->total are complete on return.  Throws Fail::Overflow when the batch has more than 2^32-1 candidates (the result object then holds an
@@ -469,19 +471,22 @@ void instances_allhits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray*
 // (bvhgpu_instances_within_*); flags: BVHGPU_INSTANCES_WITHIN_*.  Synchronous: h->offsets / h->row_instance / h->indices / h->row_vals and h->total
 // are complete on return.  Throws Fail::Overflow when the batch has more than 2^32-1 candidates (the result object then holds an empty
 // result of this kind).
+// masked (bvhgpu_instances_within_masked_*): s->masks against point_mask_dev (NULL: all ones), one mask per point.
 template <typename T>
-void instances_within_batch(bvhgpu_instances* s, const T* points_dev, const T* max_dist_dev, size_t n, unsigned flags, bvhgpu_hits* h);
+void instances_within_batch(bvhgpu_instances* s, const T* points_dev, const T* max_dist_dev, size_t n, unsigned flags, bvhgpu_hits* h, bool masked = false,
+                            const uint32_t* point_mask_dev = nullptr);
 // instances_knn.hip: the k nearest (instance, shape) pairs per point over a committed instance set (bvhgpu_instances_knearest_*); out_*: n x k,
 // a set without instances fills them with padding.  Enqueued on the ctx's stream; the array table and its mirrors live in the set.
 template <typename T>
 void instances_knearest_batch(bvhgpu_instances* s, const T* points_dev, size_t n, uint32_t k, uint32_t* out_instance_dev, uint32_t* out_shape_dev,
-                              T* out_dist_dev);
+                              T* out_dist_dev, bool masked = false, const uint32_t* point_mask_dev = nullptr);   // masked: bvhgpu_instances_knearest_masked_*
 // instances_knn_tree.hip: the same rows found nearest child first over the BvhNode arrays of the top level and of the members
 // (bvhgpu_instances_knearest_tree_*); max_dist_dev: NULL or n limits; every member must have been built here.  Enqueued on the ctx's stream;
 // the member table lives in the set.
 template <typename T>
 void instances_knearest_tree_batch(bvhgpu_instances* s, const T* points_dev, size_t n, uint32_t k, const T* max_dist_dev, uint32_t* out_instance_dev,
-                                   uint32_t* out_shape_dev, T* out_dist_dev);
+                                   uint32_t* out_shape_dev, T* out_dist_dev, bool masked = false,
+                                   const uint32_t* point_mask_dev = nullptr);   // masked: bvhgpu_instances_knearest_tree_masked_*
 // instances_khits.hip: the k nearest hits per ray over a committed instance set (bvhgpu_instances_khits_*); tmax_dev: NULL or n segment ends;
 // out_instance / out_shape: n x k, out_vals: n x k x 3; a set without instances fills them with padding.  Enqueued on the ctx's stream.
 // masked (bvhgpu_instances_khits_masked_*): s->masks against ray_mask_dev, as for instances_trace.

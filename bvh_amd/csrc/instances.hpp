@@ -21,6 +21,13 @@ template <typename T> struct __attribute__((aligned(16))) InstRec {
 };
 static_assert(sizeof(InstRec<float>) == 64 && sizeof(InstRec<double>) == 112, "instance record");
 
+// what a MASKED walk reads besides: the set's n u32, and NULL (all ones) or one u32 per row of the batch (a ray, a point, a region).
+// Without MASKED neither is read.
+struct InstMasks {
+    const uint32_t* inst;
+    const uint32_t* ray;
+};
+
 template <typename T> __device__ __forceinline__ InstRec<T> load_rec(const InstRec<T>* __restrict__ p) {
     constexpr int CHUNKS = (int)(sizeof(InstRec<T>) / 16);
     const uint4* q = reinterpret_cast<const uint4*>(p);

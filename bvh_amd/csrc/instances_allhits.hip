@@ -46,11 +46,6 @@ template <typename T> struct InstScene {
     const InstRec<T>* recs;
     const InstTree<T>* tbl;
 };
-// what a MASKED walk reads besides: the set's n u32, and NULL (all ones) or one u32 per ray.  Without MASKED neither is read.
-struct InstMasks {
-    const uint32_t* inst;
-    const uint32_t* ray;
-};
 
 // {distance, u, v} of (inst, s) for the WORLD ray (o, d): the world ray in the instance's frame by k_instances_trace's sequence, then the
 // triangle test — the operands and the operations of the walk, hence its bits

@@ -28,6 +28,11 @@
 // k, slot-major: slot m of lane l is element m x block + l of three arrays (distances, then instances, then shapes) — conflict-free, and a
 // lane only ever touches its own column, so the kernel has no barrier.  Block size: topk_block's rule for this element size
 // (instances_knn_block).  Which arrays are walked: instances_arrays.hpp's table, owned by the set and reused between calls.
+//
+// MASKED (bvhgpu_instances_knearest_masked_*): point j carries a mask P[j]; the walk passes over an instance whose mask shares
+// no bit with it, at its top-level leaf (one 4-byte load: no record, no X_i, no member table), so the list — and with it the bound that
+// prunes — only ever sees visible pairs: the row is the incremental list over the double order without the hidden instances' rows.  A point
+// whose mask is 0 does not walk: its row is padding.
 #include "instances_arrays.hpp"
 #include "point_dist.hpp"
 
@@ -51,10 +56,10 @@ template <typename T> struct InstKnnScene {
     uint32_t top;                   // the top level's row of `arrs`
 };
 
-template <typename T>
+template <typename T, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_instances_knearest(InstKnnScene<T> sc, const T* __restrict__ points, uint32_t n, uint32_t k,
                                                             uint32_t* __restrict__ out_instance, uint32_t* __restrict__ out_shape,
-                                                            T* __restrict__ out_dist) {
+                                                            T* __restrict__ out_dist, InstMasks mk) {
     extern __shared__ __align__(16) unsigned char iknn_lds[];
     const uint32_t block = blockDim.x;
     T* __restrict__ ld = reinterpret_cast<T*>(iknn_lds) + threadIdx.x;                                        // slot m: ld[m * block]
@@ -75,6 +80,11 @@ __global__ __launch_bounds__(256) void k_instances_knearest(InstKnnScene<T> sc, 
     T p[3] = {pw[0], pw[1], pw[2]};
     T xr[12] = {};           // X_i of the instance the lane is in
     uint32_t i = 0, end = top.n_trav, unfolded = top.unfolded, inst = NONE, top_next = 0;
+    uint32_t pmask = 0xFFFFFFFFu;
+    if constexpr (MASKED) {
+        if (mk.ray) pmask = mk.ray[q];
+        if (pmask == 0u) end = 0;   // (no instance is visible: no walk)
+    }
     while (i < end) {
         const NodeRegs<T> nd = load_node(nodes + i);
         const bool leaf = trav_is_leaf(nd.shape);
@@ -130,20 +140,24 @@ __global__ __launch_bounds__(256) void k_instances_knearest(InstKnnScene<T> sc, 
                     if (full) { bound = ld[(k - 1) * block]; lim = bound * fn; }
                 }
             } else {              // an instance: into its member with the point and the limit in the object's frame
-                top_next = i;
-                inst = nd.shape;
-                const InstRec<T> rec = load_rec<T>(sc.recs + inst);
-                const InstWithinArr<T> a = sc.arrs[rec.tree];
-                T f[3];
+                bool visible = true;
+                if constexpr (MASKED) visible = (mk.inst[nd.shape] & pmask) != 0u;   // (hidden: the lane stays here and goes on at nd.exit)
+                if (visible) {
+                    top_next = i;
+                    inst = nd.shape;
+                    const InstRec<T> rec = load_rec<T>(sc.recs + inst);
+                    const InstWithinArr<T> a = sc.arrs[rec.tree];
+                    T f[3];
 #pragma unroll
-                for (int c = 0; c < 3; c++) { p[c] = row4<T>(rec.y + 4 * c, pw); f[c] = row3<T>(rec.y + 4 * c, rec.y + 4 * c); }
-                const T f01 = f[0] + f[1];
-                fn = f01 + f[2];
-                lim = bound * fn;
-                const T* x = sc.xforms + 12 * (size_t)inst;
+                    for (int c = 0; c < 3; c++) { p[c] = row4<T>(rec.y + 4 * c, pw); f[c] = row3<T>(rec.y + 4 * c, rec.y + 4 * c); }
+                    const T f01 = f[0] + f[1];
+                    fn = f01 + f[2];
+                    lim = bound * fn;
+                    const T* x = sc.xforms + 12 * (size_t)inst;
 #pragma unroll
-                for (int c = 0; c < 12; c++) xr[c] = x[c];
-                nodes = a.nodes; tris = a.tris; i = 0; end = a.n_trav; unfolded = a.unfolded;
+                    for (int c = 0; c < 12; c++) xr[c] = x[c];
+                    nodes = a.nodes; tris = a.tris; i = 0; end = a.n_trav; unfolded = a.unfolded;
+                }
             }
         }
         if (inst != NONE && i >= end) {   // the member's array has ended: back to the top level, behind the leaf that sent the lane here
@@ -175,9 +189,10 @@ __global__ __launch_bounds__(256) void k_instances_knn_fill(uint32_t* __restrict
 }
 
 // the points of a batch over a committed instance set (the caller has checked commit, staleness, the members' kinds and n x k < 2^32)
+// masked: bvhgpu_instances_knearest_masked_* — the set's masks against point_mask_dev (NULL: all ones); otherwise point_mask_dev is not looked at
 template <typename T>
 void instances_knearest_batch(bvhgpu_instances* s, const T* points_dev, size_t n, uint32_t k, uint32_t* out_instance_dev, uint32_t* out_shape_dev,
-                              T* out_dist_dev) {
+                              T* out_dist_dev, bool masked, const uint32_t* point_mask_dev) {
     if (!n) return;
     hipStream_t st = s->ctx->stream;
     if (s->n == 0 || s->top == nullptr || s->top->n == 0) {   // no instance (with a finite world box): every row is padding
@@ -191,11 +206,17 @@ void instances_knearest_batch(bvhgpu_instances* s, const T* points_dev, size_t n
     const InstKnnScene<T> sc = {arrs, s->recs.as<InstRec<T>>(), s->xforms.as<T>(), (uint32_t)s->trees.size()};
     const unsigned bs = instances_knn_block<T>(k);
     const size_t lds = (size_t)bs * k * (sizeof(T) + 8);
-    hipLaunchKernelGGL((k_instances_knearest<T>), dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), lds, st, sc, points_dev, (uint32_t)n, k, out_instance_dev,
-                       out_shape_dev, out_dist_dev);
+    const dim3 grid((unsigned)((n + bs - 1) / bs));
+    if (masked) {
+        const InstMasks mk = {s->masks.as<uint32_t>(), point_mask_dev};
+        hipLaunchKernelGGL((k_instances_knearest<T, true>), grid, dim3(bs), lds, st, sc, points_dev, (uint32_t)n, k, out_instance_dev, out_shape_dev, out_dist_dev, mk);
+    } else {
+        hipLaunchKernelGGL((k_instances_knearest<T, false>), grid, dim3(bs), lds, st, sc, points_dev, (uint32_t)n, k, out_instance_dev, out_shape_dev, out_dist_dev,
+                           InstMasks{nullptr, nullptr});
+    }
     BVH_HIP(hipGetLastError());
 }
-template void instances_knearest_batch<float>(bvhgpu_instances*, const float*, size_t, uint32_t, uint32_t*, uint32_t*, float*);
-template void instances_knearest_batch<double>(bvhgpu_instances*, const double*, size_t, uint32_t, uint32_t*, uint32_t*, double*);
+template void instances_knearest_batch<float>(bvhgpu_instances*, const float*, size_t, uint32_t, uint32_t*, uint32_t*, float*, bool, const uint32_t*);
+template void instances_knearest_batch<double>(bvhgpu_instances*, const double*, size_t, uint32_t, uint32_t*, uint32_t*, double*, bool, const uint32_t*);
 
 }  // namespace bvhgpu

@@ -43,6 +43,11 @@
 // of a wave keep stepping together whatever level each is on.  X_i is read again at every member leaf rather than kept in twelve registers
 // (DESIGN.md §4q has the register counts of both choices).  The list is k_instances_knearest's: dynamic LDS, three slot-major arrays
 // (distances, instances, shapes), instances_knn_block's block rule, no barrier; the insertion is restated here as knn_tree.hip says it must.
+//
+// MASKED (bvhgpu_instances_knearest_tree_masked_*): point j carries a mask P[j].  The descent is over the SAME top-level array — the
+// top level of the whole set — and a top-level leaf whose instance shares no bit with P[j] contributes nothing: one 4-byte load, then it is
+// left exactly as a leaf whose member has no shapes is left (`next` stays NONE, the lane returns to the leaf's parent).  The list and the
+// bounds only ever see visible pairs.  A point whose mask is 0 does not walk: its row is padding.
 #include "engine.hpp"
 #include "instances.hpp"
 #include "point_dist.hpp"
@@ -73,12 +78,12 @@ template <typename T> __device__ __forceinline__ T child_min_dist2(const T mn[3]
     return mn[0] > mx[0] ? (T)0 : md;
 }
 
-template <typename T>
+template <typename T, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_instances_knearest_tree(const typename Traits<T>::Node* __restrict__ top, uint32_t n_top,
                                                                  const InstTreeMember<T>* __restrict__ members, const InstRec<T>* __restrict__ recs,
                                                                  const T* __restrict__ xforms, const T* __restrict__ points, uint32_t n, uint32_t k,
                                                                  const T* __restrict__ max_dist, uint32_t* __restrict__ out_instance,
-                                                                 uint32_t* __restrict__ out_shape, T* __restrict__ out_dist) {
+                                                                 uint32_t* __restrict__ out_shape, T* __restrict__ out_dist, InstMasks mk) {
     using Node = typename Traits<T>::Node;
     extern __shared__ __align__(16) unsigned char iknt_lds[];
     const uint32_t block = blockDim.x;
@@ -99,6 +104,11 @@ __global__ __launch_bounds__(256) void k_instances_knearest_tree(const typename 
         const T m = max_dist[q];
         r2 = m * m;
         walk = walk && m >= (T)0;                // a negative or NaN limit admits nothing
+    }
+    uint32_t pmask = 0xFFFFFFFFu;
+    if constexpr (MASKED) {
+        if (mk.ray) pmask = mk.ray[q];
+        walk = walk && pmask != 0u;                  // no instance is visible: no walk
     }
     T lim_r = r2;            // what a box test compares with: r2 and bound at the top level, r2 * fn and bound * fn inside an instance
     T lim_b = 0;
@@ -166,20 +176,24 @@ __global__ __launch_bounds__(256) void k_instances_knearest_tree(const typename 
                     if (full) { bound = ld[(k - 1) * block]; lim_b = bound * fn; }
                 }
             } else {              // an instance (its box was admitted, or it is record 0): into its member with the point and the limits in the object's frame
-                const InstRec<T> rec = load_rec<T>(recs + nd.shape);
-                const InstTreeMember<T> mb = members[rec.tree];
-                if (mb.n_nodes != 0u) {
-                    top_leaf = cur; top_parent = nd.parent;
-                    inst = nd.shape;
-                    T f[3];
+                bool visible = true;
+                if constexpr (MASKED) visible = (mk.inst[nd.shape] & pmask) != 0u;   // (hidden: `next` stays NONE, as for a member without shapes)
+                if (visible) {
+                    const InstRec<T> rec = load_rec<T>(recs + nd.shape);
+                    const InstTreeMember<T> mb = members[rec.tree];
+                    if (mb.n_nodes != 0u) {
+                        top_leaf = cur; top_parent = nd.parent;
+                        inst = nd.shape;
+                        T f[3];
 #pragma unroll
-                    for (int c = 0; c < 3; c++) { p[c] = row4<T>(rec.y + 4 * c, pw); f[c] = row3<T>(rec.y + 4 * c, rec.y + 4 * c); }
-                    const T f01 = f[0] + f[1];
-                    fn = f01 + f[2];
-                    lim_r = r2 * fn;
-                    lim_b = bound * fn;
-                    nodes = mb.nodes; tris = mb.tris; n_nodes = mb.n_nodes;
-                    next = 0;     // record 0 of the member's array, from above
+                        for (int c = 0; c < 3; c++) { p[c] = row4<T>(rec.y + 4 * c, pw); f[c] = row3<T>(rec.y + 4 * c, rec.y + 4 * c); }
+                        const T f01 = f[0] + f[1];
+                        fn = f01 + f[2];
+                        lim_r = r2 * fn;
+                        lim_b = bound * fn;
+                        nodes = mb.nodes; tris = mb.tris; n_nodes = mb.n_nodes;
+                        next = 0;     // record 0 of the member's array, from above
+                    }
                 }
             }
         } else {
@@ -216,14 +230,15 @@ __global__ __launch_bounds__(256) void k_instances_knearest_tree(const typename 
 
 // the points of a batch over a committed instance set (the caller has checked commit, staleness, that every member was built here and
 // n x k < 2^32); max_dist_dev: NULL or n limits
+// masked: bvhgpu_instances_knearest_tree_masked_* — the set's masks against point_mask_dev (NULL: all ones); otherwise point_mask_dev is not looked at
 template <typename T>
 void instances_knearest_tree_batch(bvhgpu_instances* s, const T* points_dev, size_t n, uint32_t k, const T* max_dist_dev, uint32_t* out_instance_dev,
-                                   uint32_t* out_shape_dev, T* out_dist_dev) {
+                                   uint32_t* out_shape_dev, T* out_dist_dev, bool masked, const uint32_t* point_mask_dev) {
     if (!n) return;
     using Node = typename Traits<T>::Node;
     hipStream_t st = s->ctx->stream;
     if (s->n == 0 || s->top == nullptr || s->top->n == 0) {   // no instance: every row is padding, written by the flat form's fill path
-        instances_knearest_batch<T>(s, points_dev, n, k, out_instance_dev, out_shape_dev, out_dist_dev);
+        instances_knearest_batch<T>(s, points_dev, n, k, out_instance_dev, out_shape_dev, out_dist_dev, false, nullptr);
         return;
     }
     // the member table: made again by every call (a member may have been rebuilt and the set updated), the allocation kept by the set
@@ -238,12 +253,22 @@ void instances_knearest_tree_batch(bvhgpu_instances* s, const T* points_dev, siz
     BVH_HIP(hipMemcpyAsync(s->knt_members.p, host, nt * sizeof(InstTreeMember<T>), hipMemcpyHostToDevice, st));
     const unsigned bs = instances_knn_tree_block<T>(k);
     const size_t lds = (size_t)bs * k * (sizeof(T) + 8);
-    hipLaunchKernelGGL((k_instances_knearest_tree<T>), dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), lds, st, s->top->nodes.as<Node>(),
-                       (uint32_t)s->top->n_nodes, s->knt_members.as<InstTreeMember<T>>(), s->recs.as<InstRec<T>>(), s->xforms.as<T>(), points_dev,
-                       (uint32_t)n, k, max_dist_dev, out_instance_dev, out_shape_dev, out_dist_dev);
+    const dim3 grid((unsigned)((n + bs - 1) / bs));
+    if (masked) {
+        const InstMasks mk = {s->masks.as<uint32_t>(), point_mask_dev};
+        hipLaunchKernelGGL((k_instances_knearest_tree<T, true>), grid, dim3(bs), lds, st, s->top->nodes.as<Node>(), (uint32_t)s->top->n_nodes,
+                           s->knt_members.as<InstTreeMember<T>>(), s->recs.as<InstRec<T>>(), s->xforms.as<T>(), points_dev, (uint32_t)n, k, max_dist_dev,
+                           out_instance_dev, out_shape_dev, out_dist_dev, mk);
+    } else {
+        hipLaunchKernelGGL((k_instances_knearest_tree<T, false>), grid, dim3(bs), lds, st, s->top->nodes.as<Node>(), (uint32_t)s->top->n_nodes,
+                           s->knt_members.as<InstTreeMember<T>>(), s->recs.as<InstRec<T>>(), s->xforms.as<T>(), points_dev, (uint32_t)n, k, max_dist_dev,
+                           out_instance_dev, out_shape_dev, out_dist_dev, InstMasks{nullptr, nullptr});
+    }
     BVH_HIP(hipGetLastError());
 }
-template void instances_knearest_tree_batch<float>(bvhgpu_instances*, const float*, size_t, uint32_t, const float*, uint32_t*, uint32_t*, float*);
-template void instances_knearest_tree_batch<double>(bvhgpu_instances*, const double*, size_t, uint32_t, const double*, uint32_t*, uint32_t*, double*);
+template void instances_knearest_tree_batch<float>(bvhgpu_instances*, const float*, size_t, uint32_t, const float*, uint32_t*, uint32_t*, float*, bool,
+                                                   const uint32_t*);
+template void instances_knearest_tree_batch<double>(bvhgpu_instances*, const double*, size_t, uint32_t, const double*, uint32_t*, uint32_t*, double*, bool,
+                                                    const uint32_t*);
 
 }  // namespace bvhgpu

@@ -35,6 +35,12 @@
 // tests it), the UNFOLDED rule for an uploaded FlatBvh and a one-shape tree (a leaf entry is entered untested), and an unfolded mirror of
 // the FlatNode array (unfold.hpp) for a built tree with empty child bounds — the top level included, whose build over the world boxes
 // can meet a split without SAH winner like any other.
+//
+// MASKED (bvhgpu_instances_within_masked_*): point j carries a mask P[j] and the walk passes over an instance whose mask shares
+// no bit with it, at its top-level leaf: one 4-byte load, no record, no X_i, no member table.  The candidate set does not depend on the
+// walk's order, so the row is the unmasked row without the hidden instances' pairs.  The count walk and the fill walk read the same two
+// arrays and so take the same decision for every (point, instance): the offsets are what the fill writes.  A point whose mask is 0 does not
+// walk.  k_instances_within_sort_row only ever sees pairs that are already in a row: no mask.
 #include <cstdio>
 #include <vector>
 
@@ -72,8 +78,10 @@ template <typename T> struct InstWithinPoint {
 // One point per lane, ONE loop.  on_candidate(instance, shape, d) for every pair the definition keeps, in the double order.  X_i is read
 // once on entry to an instance and carried through the member's walk: 6 (f64: 16) registers more across the loop than reading it again
 // at every accepted leaf, no scratch either way, and the faster of the two where it was timed (DESIGN.md §4n has both forms' figures).
-template <typename T, typename F>
-__device__ __forceinline__ void instances_within_walk(const InstWithinScene<T>& sc, const InstWithinPoint<T>& pt, F&& on_candidate) {
+// MASKED: pmask is the point's mask; an instance with (inst_mask[i] & pmask) == 0 is passed over at its leaf and the lane goes on in the top level.
+template <typename T, typename F, bool MASKED = false>
+__device__ __forceinline__ void instances_within_walk(const InstWithinScene<T>& sc, const InstWithinPoint<T>& pt, F&& on_candidate,
+                                                      const uint32_t* __restrict__ inst_mask = nullptr, uint32_t pmask = 0xFFFFFFFFu) {
     const InstWithinArr<T> top = sc.arrs[sc.top];
     const TravNode<T>* nodes = top.nodes;
     const T* tris = nullptr;
@@ -103,20 +111,24 @@ __device__ __forceinline__ void instances_within_walk(const InstWithinScene<T>& 
                 const T d = triangle_dist2<T>(w, pt.p);
                 if (d <= pt.r2) on_candidate(inst, nd.shape, d);
             } else {              // an instance: into its member with the point and the limit in the object's frame
-                top_next = i;
-                inst = nd.shape;
-                const InstRec<T> rec = load_rec<T>(sc.recs + inst);
-                const InstWithinArr<T> a = sc.arrs[rec.tree];
-                T f[3];
+                bool visible = true;
+                if constexpr (MASKED) visible = (inst_mask[nd.shape] & pmask) != 0u;   // (hidden: the lane stays here and goes on at nd.exit)
+                if (visible) {
+                    top_next = i;
+                    inst = nd.shape;
+                    const InstRec<T> rec = load_rec<T>(sc.recs + inst);
+                    const InstWithinArr<T> a = sc.arrs[rec.tree];
+                    T f[3];
 #pragma unroll
-                for (int k = 0; k < 3; k++) { p[k] = row4<T>(rec.y + 4 * k, pt.p); f[k] = row3<T>(rec.y + 4 * k, rec.y + 4 * k); }
-                const T f01 = f[0] + f[1];
-                const T fn = f01 + f[2];
-                lim = pt.r2 * fn;
-                const T* x = sc.xforms + 12 * (size_t)inst;
+                    for (int k = 0; k < 3; k++) { p[k] = row4<T>(rec.y + 4 * k, pt.p); f[k] = row3<T>(rec.y + 4 * k, rec.y + 4 * k); }
+                    const T f01 = f[0] + f[1];
+                    const T fn = f01 + f[2];
+                    lim = pt.r2 * fn;
+                    const T* x = sc.xforms + 12 * (size_t)inst;
 #pragma unroll
-                for (int k = 0; k < 12; k++) xr[k] = x[k];
-                nodes = a.nodes; tris = a.tris; i = 0; end = a.n_trav; unfolded = a.unfolded;
+                    for (int k = 0; k < 12; k++) xr[k] = x[k];
+                    nodes = a.nodes; tris = a.tris; i = 0; end = a.n_trav; unfolded = a.unfolded;
+                }
             }
         }
         if (inst != NONE && i >= end) {   // the member's array has ended: back to the top level, behind the leaf that sent the lane here
@@ -128,26 +140,32 @@ __device__ __forceinline__ void instances_within_walk(const InstWithinScene<T>& 
     }
 }
 
-template <typename T>
+template <typename T, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_instances_within_count(InstWithinScene<T> sc, const T* __restrict__ points, const T* __restrict__ max_dist, uint32_t n,
-                                                                uint32_t* __restrict__ counts) {
+                                                                uint32_t* __restrict__ counts, InstMasks mk) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
     InstWithinPoint<T> pt;
     pt.load(points, max_dist, q);
     uint32_t cnt = 0;
-    if (pt.walk) instances_within_walk<T>(sc, pt, [&](uint32_t, uint32_t, T) { cnt++; });
+    auto count = [&](uint32_t, uint32_t, T) { cnt++; };
+    if constexpr (MASKED) {
+        const uint32_t pmask = mk.ray ? mk.ray[q] : 0xFFFFFFFFu;
+        if (pt.walk && pmask != 0u) instances_within_walk<T, decltype(count)&, true>(sc, pt, count, mk.inst, pmask);
+    } else {
+        if (pt.walk) instances_within_walk<T>(sc, pt, count);
+    }
     counts[q] = cnt;
 }
 
 // ---- the second walk ----------------------------------------------------------------------------------------------------------------
 // list_shape: NULL, or total u32 — the shapes of the long rows in the double order (a sorted batch that has long rows)
 // pos:        NULL, or total u32 — the positions of the rows beyond INST_WITHIN_LDS_ROW_MAX (a sorted batch that has such rows)
-template <typename T, bool SORTED>
+template <typename T, bool SORTED, bool MASKED = false>
 __global__ __launch_bounds__(256) void k_instances_within_fill(InstWithinScene<T> sc, const T* __restrict__ points, const T* __restrict__ max_dist, uint32_t n,
                                                                const uint32_t* __restrict__ offsets, uint32_t* __restrict__ instance,
                                                                uint32_t* __restrict__ shape, T* __restrict__ dist, uint32_t* __restrict__ list_shape,
-                                                               uint32_t* __restrict__ pos) {
+                                                               uint32_t* __restrict__ pos, InstMasks mk) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
     const uint32_t beg = offsets[q], len = offsets[q + 1] - beg;
@@ -161,7 +179,7 @@ __global__ __launch_bounds__(256) void k_instances_within_fill(InstWithinScene<T
     const bool with_list = SORTED && !insert && list_shape != nullptr;
     const bool with_pos = SORTED && pos != nullptr && len > INST_WITHIN_LDS_ROW_MAX;
     uint32_t cnt = 0;
-    instances_within_walk<T>(sc, pt, [&](uint32_t inst, uint32_t s, T d) {
+    auto put = [&](uint32_t inst, uint32_t s, T d) {
         if (cnt >= len) return;   // (never: this walk is the count pass's; a lane stays inside its own region whatever happens)
         if (insert) {
             // ascending list: the first element e with d < e is where a scan from the back stops, so search and shift are one loop
@@ -189,7 +207,13 @@ __global__ __launch_bounds__(256) void k_instances_within_fill(InstWithinScene<T
             rs[cnt] = s;
         }
         cnt++;
-    });
+    };
+    if constexpr (MASKED) {   // (the count walk's decision: the same two arrays; a row with len != 0 has a mask that is not 0)
+        const uint32_t pmask = mk.ray ? mk.ray[q] : 0xFFFFFFFFu;
+        instances_within_walk<T, decltype(put)&, true>(sc, pt, put, mk.inst, pmask);
+    } else {
+        instances_within_walk<T>(sc, pt, put);
+    }
     if (insert) {
 #pragma unroll 1
         for (uint32_t j = 0; j < cnt; j++) rd[j] = sqrt(rd[j]);
@@ -232,18 +256,19 @@ __global__ __launch_bounds__(ROWS_SORT_THREADS) void k_instances_within_sort_row
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool MASKED>
 static void instances_within_launch(bvhgpu_instances* s, const InstWithinScene<T>& sc, const T* points_dev, const T* max_dist_dev, size_t n, bool sorted,
-                                    bool count_only, bvhgpu_hits* h) {
+                                    bool count_only, bvhgpu_hits* h, const uint32_t* point_mask_dev) {
     hipStream_t st = s->ctx->stream;
+    const InstMasks mk = {MASKED ? s->masks.as<uint32_t>() : nullptr, MASKED ? point_mask_dev : nullptr};
     const uint32_t n32 = (uint32_t)n;
     const dim3 pgrid((unsigned)((n + 255) / 256)), block(256);
     const RowsPlan plan = {sorted, count_only, INST_WITHIN_LANE_ROW_MAX, INST_WITHIN_LDS_ROW_MAX, sizeof(T), true, true};
     rows_run(h, n, plan,
-             [&](uint32_t* counts) { hipLaunchKernelGGL((k_instances_within_count<T>), pgrid, block, 0, st, sc, points_dev, max_dist_dev, n32, counts); },
+             [&](uint32_t* counts) { hipLaunchKernelGGL((k_instances_within_count<T, MASKED>), pgrid, block, 0, st, sc, points_dev, max_dist_dev, n32, counts, mk); },
              [&](const RowsOut& o, auto SORTED) {
-                 hipLaunchKernelGGL((k_instances_within_fill<T, decltype(SORTED)::value>), pgrid, block, 0, st, sc, points_dev, max_dist_dev, n32, o.offsets, o.instance,
-                                    o.shape, static_cast<T*>(o.vals), o.list_shape, o.pos);
+                 hipLaunchKernelGGL((k_instances_within_fill<T, decltype(SORTED)::value, MASKED>), pgrid, block, 0, st, sc, points_dev, max_dist_dev, n32, o.offsets,
+                                    o.instance, o.shape, static_cast<T*>(o.vals), o.list_shape, o.pos, mk);
              },
              [&](const RowsOut& o, uint32_t n_long) {
                  hipLaunchKernelGGL((k_instances_within_sort_row<T>), dim3(n_long), dim3(ROWS_SORT_THREADS), 0, st, o.work, o.offsets, o.instance, o.shape,
@@ -252,21 +277,25 @@ static void instances_within_launch(bvhgpu_instances* s, const InstWithinScene<T
 }
 
 // the points of a batch over a committed instance set (the caller has checked commit, staleness and the members' kinds)
+// masked: bvhgpu_instances_within_masked_* — the set's masks against point_mask_dev (NULL: all ones); otherwise point_mask_dev is not looked at
 template <typename T>
-void instances_within_batch(bvhgpu_instances* s, const T* points_dev, const T* max_dist_dev, size_t n, unsigned flags, bvhgpu_hits* h) {
+void instances_within_batch(bvhgpu_instances* s, const T* points_dev, const T* max_dist_dev, size_t n, unsigned flags, bvhgpu_hits* h, bool masked,
+                            const uint32_t* point_mask_dev) {
     const bool sorted = (flags & BVHGPU_INSTANCES_WITHIN_LIST_ORDER) == 0;
     const bool count_only = (flags & BVHGPU_INSTANCES_WITHIN_COUNT_ONLY) != 0;
     char name[96];
-    if (count_only) std::snprintf(name, sizeof name, "bvhgpu::k_instances_within_count<%s>", walk_type_name<T>());
-    else std::snprintf(name, sizeof name, "bvhgpu::k_instances_within_fill<%s, %s>", walk_type_name<T>(), sorted ? "true" : "false");
+    const char* m = masked ? ", true" : "";   // (the unmasked names are what they were)
+    if (count_only) std::snprintf(name, sizeof name, "bvhgpu::k_instances_within_count<%s%s>", walk_type_name<T>(), m);
+    else std::snprintf(name, sizeof name, "bvhgpu::k_instances_within_fill<%s, %s%s>", walk_type_name<T>(), sorted ? "true" : "false", m);
     rows_batch(h, s->ctx, Traits<T>::dtype, TRAVERSE_INST_WITHIN, 0, count_only, n, s->n == 0, name, [&] {   // (empty: no instances)
         // the table of the batch: which array of every member and of the top level (instances_arrays.hpp), in the result object
         const InstWithinArr<T>* arrs = instances_array_table<T>(s, h->unfold, h->rg_members, h->rg_members_host);
         const InstWithinScene<T> sc = {arrs, s->recs.as<InstRec<T>>(), s->xforms.as<T>(), (uint32_t)s->trees.size()};
-        instances_within_launch<T>(s, sc, points_dev, max_dist_dev, n, sorted, count_only, h);
+        if (masked) instances_within_launch<T, true>(s, sc, points_dev, max_dist_dev, n, sorted, count_only, h, point_mask_dev);
+        else instances_within_launch<T, false>(s, sc, points_dev, max_dist_dev, n, sorted, count_only, h, nullptr);
     });
 }
-template void instances_within_batch<float>(bvhgpu_instances*, const float*, const float*, size_t, unsigned, bvhgpu_hits*);
-template void instances_within_batch<double>(bvhgpu_instances*, const double*, const double*, size_t, unsigned, bvhgpu_hits*);
+template void instances_within_batch<float>(bvhgpu_instances*, const float*, const float*, size_t, unsigned, bvhgpu_hits*, bool, const uint32_t*);
+template void instances_within_batch<double>(bvhgpu_instances*, const double*, const double*, size_t, unsigned, bvhgpu_hits*, bool, const uint32_t*);
 
 }  // namespace bvhgpu

@@ -38,8 +38,10 @@
 // unchanged: stage 1 is region_batch over the set's top level, stage 2 walks (pair, chunk) units with the planes re-expressed in the
 // pair's object frame (k_instances_region_walk below).
 #include <cstdio>
+#include <type_traits>
 #include <vector>
 
+#include "instances.hpp"
 #include "rows.hpp"
 #include "unfold.hpp"
 #include "walk.hpp"
@@ -229,6 +231,12 @@ __global__ __launch_bounds__(256) void k_region_offsets(const uint32_t* __restri
 // pair's member with the planes re-expressed in the instance's object frame: the unit is (pair, chunk), unit u = pair u / nc_max, chunk
 // u % nc_max, where nc_max is the largest chunk count among the members — a uniform stride, so the schedule is rows.hip's again with no
 // further scan and no further host read; a unit whose chunk lies beyond its own member's array counts 0.
+// MASKED (bvhgpu_instances_region_masked_*): region q carries a mask P[q] and I_q keeps the instances of stage 1's row whose mask
+// shares a bit with it.  Stage 1 and the pairs are what they were; every unit of a hidden pair counts 0 — the wave learns (region, instance)
+// first, one 4-byte load and one register, in front of the plane transform — so the pair has no rows and the fill, which is the unmasked
+// fill walk, passes over its units by beg == end.  With
+// INSTANCES_ONLY stage 1 runs into the set's own result object and the pairs are the units (stride 1): k_instances_region_visible counts 1 or
+// 0, the same scan and offsets, and k_instances_region_keep writes the survivors with stage 1's inside byte.
 
 // what the walk needs of a member, one record per member, made by every batch (instances.hip's InstTree is the ray walk's)
 template <typename T> struct RegionMember {
@@ -256,13 +264,13 @@ __global__ __launch_bounds__(256) void k_instances_region_pairs(const uint32_t* 
 // a workgroup is one wave and takes the units blockIdx.x, blockIdx.x + gridDim.x, ...  The planes of the unit's region go to LDS in its
 // instance's object frame (lane j < m: plane j; the header's formula, from the FORWARD transform); then region_unit, on the member's array.
 // !FILL: out[u] = the unit's count.  FILL: out = the scanned counts; the unit writes shape_out and inst_out[out[u] .. out[u + 1])
-template <typename T, bool FILL, bool CLASSIFY>
+template <typename T, bool FILL, bool CLASSIFY, bool MASKED = false>
 __global__ __launch_bounds__(64) void k_instances_region_walk(const RegionMember<T>* __restrict__ members, const uint32_t* __restrict__ tree_of,
                                                               const T* __restrict__ xforms, const T* __restrict__ planes, uint32_t m,
                                                               const uint32_t* __restrict__ pair_region, const uint32_t* __restrict__ pair_inst,
                                                               uint32_t nc_max, size_t n_units, const uint32_t* __restrict__ anc_cnt,
                                                               const uint32_t* __restrict__ anc, uint32_t* __restrict__ out, uint32_t* __restrict__ inst_out,
-                                                              uint32_t* __restrict__ shape_out, unsigned char* __restrict__ inside_out) {
+                                                              uint32_t* __restrict__ shape_out, unsigned char* __restrict__ inside_out, InstMasks mk) {
     __shared__ T pl[4 * BVHGPU_REGION_MAX_PLANES];
     for (size_t u = blockIdx.x; u < n_units; u += gridDim.x) {
         uint32_t beg = 0, end = 0;
@@ -272,6 +280,14 @@ __global__ __launch_bounds__(64) void k_instances_region_walk(const RegionMember
         }
         const uint32_t p = (uint32_t)(u / nc_max), c = (uint32_t)(u - (size_t)p * nc_max);
         const uint32_t q = __builtin_amdgcn_readfirstlane(pair_region[p]), inst = __builtin_amdgcn_readfirstlane(pair_inst[p]);
+        static_assert(!(MASKED && FILL), "only the count walk looks at the masks: the fill passes over a hidden pair's units by beg == end");
+        if constexpr (MASKED) {   // (uniform) a hidden pair: every unit of it counts 0
+            const uint32_t pmask = mk.ray ? __builtin_amdgcn_readfirstlane(mk.ray[q]) : 0xFFFFFFFFu;
+            if ((__builtin_amdgcn_readfirstlane(mk.inst[inst]) & pmask) == 0u) {
+                if (threadIdx.x == 0) out[u] = 0;
+                continue;
+            }
+        }
         const RegionMember<T>* mb = members + __builtin_amdgcn_readfirstlane(tree_of[inst]);
         const uint32_t nc = __builtin_amdgcn_readfirstlane(mb->n_chunks);
         if (c >= nc) {   // (uniform) the member's array ends in front of this chunk
@@ -315,6 +331,26 @@ __global__ __launch_bounds__(256) void k_instances_region_offsets(const uint32_t
                                                                   uint32_t n, uint32_t nc_max, uint32_t* __restrict__ offsets) {
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q <= n) offsets[q] = unit_offsets[(size_t)top_offsets[q] * nc_max];
+}
+
+// MASKED with INSTANCES_ONLY: pair p (stage 1's row element p) is kept iff its instance is visible to its region
+__global__ __launch_bounds__(256) void k_instances_region_visible(const uint32_t* __restrict__ pair_region, const uint32_t* __restrict__ pair_inst,
+                                                                  uint32_t n_pairs, InstMasks mk, uint32_t* __restrict__ counts) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs) return;
+    const uint32_t pmask = mk.ray ? mk.ray[pair_region[p]] : 0xFFFFFFFFu;
+    counts[p] = (mk.inst[pair_inst[p]] & pmask) != 0u ? 1u : 0u;
+}
+// ... and a kept pair goes to its place in the scanned counts, with stage 1's inside byte (top_inside: NULL without CLASSIFY)
+__global__ __launch_bounds__(256) void k_instances_region_keep(const uint32_t* __restrict__ pair_offsets, const uint32_t* __restrict__ pair_inst,
+                                                               const unsigned char* __restrict__ top_inside, uint32_t n_pairs, uint32_t total,
+                                                               uint32_t* __restrict__ inst_out, unsigned char* __restrict__ inside_out) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pairs) return;
+    const uint32_t at = pair_offsets[p];
+    if (pair_offsets[p + 1] == at || at >= total) return;   // (hidden; never beyond the total: the offsets are the scan of these counts)
+    inst_out[at] = pair_inst[p];
+    if (top_inside) inside_out[at] = top_inside[p];
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
@@ -395,13 +431,72 @@ void region_batch(bvhgpu_tree* t, const T* planes_dev, size_t n, uint32_t m, uns
 template void region_batch<float>(bvhgpu_tree*, const float*, size_t, uint32_t, unsigned, bvhgpu_hits*);
 template void region_batch<double>(bvhgpu_tree*, const double*, size_t, uint32_t, unsigned, bvhgpu_hits*);
 
-// the regions of a batch over a committed instance set (the caller has checked commit, staleness and the members' kinds)
+// bvhgpu_instances_region_masked_* with BVHGPU_REGION_INSTANCES_ONLY: stage 1 into the set's own result object, then its pairs as units of one
+// — count 1 or 0, the scan with its ONE host read, the offsets at stride 1, the survivors with stage 1's inside byte
 template <typename T>
-void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, uint32_t m, unsigned flags, bvhgpu_hits* h) {
+static void instances_region_only_masked(bvhgpu_instances* s, const T* planes_dev, size_t n, uint32_t m, bool classify, bool count_only, bvhgpu_hits* h,
+                                         const uint32_t* region_mask_dev) {
+    bvhgpu_ctx* ctx = s->ctx;
+    hipStream_t st = ctx->stream;
+    rows_reset(h, ctx, Traits<T>::dtype, TRAVERSE_REGION, 0, count_only);
+    h->rg_classify = classify; h->rg_chunks = 0; h->rg_chunk_entries = 0; h->rg_inst = REGION_INST_ONLY;
+    h->walk_kernel = "bvhgpu::k_instances_region_visible";
+    h->rg_offsets.reserve((n + 1) * 4);
+    BVH_HIP(hipMemsetAsync(h->rg_offsets.p, 0, (n + 1) * 4, st));
+    if (!s->rg_top) s->rg_top = new bvhgpu_hits();
+    bvhgpu_hits* top = s->rg_top;
+    region_batch<T>(s->top, planes_dev, n, m, classify ? BVHGPU_REGION_CLASSIFY : 0u, top);   // (synchronous: P is known behind it)
+    const size_t P = (size_t)top->total;
+    if (P != 0) {
+        const InstMasks mk = {s->masks.as<uint32_t>(), region_mask_dev};
+        const dim3 pgrid((unsigned)((P + 255) / 256)), block(256);
+        h->offsets.reserve((P + 1) * 4);
+        h->rg_pairs.reserve(P * 4);
+        const uint32_t* top_offsets = top->rg_offsets.as<uint32_t>();
+        const uint32_t* pair_inst = top->indices.as<uint32_t>();
+        uint32_t* pair_region = h->rg_pairs.as<uint32_t>();
+        hipLaunchKernelGGL(k_instances_region_pairs, pgrid, block, 0, st, top_offsets, (uint32_t)n, (uint32_t)P, pair_region);
+        uint32_t* counts = rows_begin(h, P, false);
+        hipLaunchKernelGGL(k_instances_region_visible, pgrid, block, 0, st, pair_region, pair_inst, (uint32_t)P, mk, counts);
+        BVH_HIP(hipGetLastError());
+        const RowsTotals rows = rows_scan(h, P, 0u, 0u);
+        h->rg_chunks = top->rg_chunks; h->rg_chunk_entries = top->rg_chunk_entries;   // (how stage 1 cut the top level, as the unmasked form reports)
+        if (rows.total != 0) {
+            rows_offsets(h, P);
+            uint32_t* pair_offsets = h->offsets.as<uint32_t>();
+            hipLaunchKernelGGL(k_instances_region_offsets, dim3((unsigned)((n + 1 + 255) / 256)), block, 0, st, pair_offsets, top_offsets, (uint32_t)n, 1u,
+                               h->rg_offsets.as<uint32_t>());
+            if (!count_only) {
+                h->indices.reserve((size_t)rows.total * 4);
+                if (classify) h->rg_inside.reserve((size_t)rows.total);
+                hipLaunchKernelGGL(k_instances_region_keep, pgrid, block, 0, st, pair_offsets, pair_inst,
+                                   classify ? top->rg_inside.as<unsigned char>() : (const unsigned char*)nullptr, (uint32_t)P, (uint32_t)rows.total,
+                                   h->indices.as<uint32_t>(), classify ? h->rg_inside.as<unsigned char>() : (unsigned char*)nullptr);
+            }
+            BVH_HIP(hipGetLastError());
+            h->total = rows.total;
+        }
+    } else {
+        h->rg_chunks = top->rg_chunks; h->rg_chunk_entries = top->rg_chunk_entries;
+    }
+    BVH_HIP(hipStreamSynchronize(st));   // the result is complete when the call returns
+    h->n_rays = n;
+    h->stats.hits = h->total;
+}
+
+// the regions of a batch over a committed instance set (the caller has checked commit, staleness and the members' kinds)
+// masked: bvhgpu_instances_region_masked_* — the set's masks against region_mask_dev (NULL: all ones); otherwise region_mask_dev is not looked at
+template <typename T>
+void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, uint32_t m, unsigned flags, bvhgpu_hits* h, bool masked,
+                            const uint32_t* region_mask_dev) {
     bvhgpu_ctx* ctx = s->ctx;
     hipStream_t st = ctx->stream;
     const bool count_only = (flags & BVHGPU_REGION_COUNT_ONLY) != 0;
     const bool classify = (flags & BVHGPU_REGION_CLASSIFY) != 0 && !count_only;
+    if (masked && (flags & BVHGPU_REGION_INSTANCES_ONLY)) {
+        instances_region_only_masked<T>(s, planes_dev, n, m, classify, count_only, h, region_mask_dev);
+        return;
+    }
     if (flags & BVHGPU_REGION_INSTANCES_ONLY) {   // stage 1 IS the answer: the top level's rows, straight into the caller's result object
         try {
             region_batch<T>(s->top, planes_dev, n, m, flags & (BVHGPU_REGION_COUNT_ONLY | BVHGPU_REGION_CLASSIFY), h);
@@ -416,7 +511,9 @@ void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, 
     rows_reset(h, ctx, Traits<T>::dtype, TRAVERSE_REGION, 0, count_only);
     h->rg_classify = classify; h->rg_chunks = 0; h->rg_chunk_entries = 0; h->rg_inst = REGION_INST_SHAPES;
     char name[112];
-    std::snprintf(name, sizeof name, "bvhgpu::k_instances_region_walk<%s, %s, %s>", walk_type_name<T>(), count_only ? "false" : "true", classify ? "true" : "false");
+    // (the unmasked names are what they were; a masked batch names its count walk, the one launch that looks at the masks)
+    if (masked) std::snprintf(name, sizeof name, "bvhgpu::k_instances_region_walk<%s, false, false, true>", walk_type_name<T>());
+    else std::snprintf(name, sizeof name, "bvhgpu::k_instances_region_walk<%s, %s, %s>", walk_type_name<T>(), count_only ? "false" : "true", classify ? "true" : "false");
     h->walk_kernel = name;
     h->rg_offsets.reserve((n + 1) * 4);
     BVH_HIP(hipMemsetAsync(h->rg_offsets.p, 0, (n + 1) * 4, st));
@@ -483,8 +580,16 @@ void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, 
         const uint32_t* tree_of = s->tree_of.as<uint32_t>();
         const T* xforms = s->xforms.as<T>();
         uint32_t* counts = rows_begin(h, n_units, false);
-        hipLaunchKernelGGL((k_instances_region_walk<T, false, false>), grid, block, 0, st, members, tree_of, xforms, planes_dev, m, pair_region, pair_inst, nc_max,
-                           n_units, anc_cnt, anc, counts, (uint32_t*)nullptr, (uint32_t*)nullptr, (unsigned char*)nullptr);
+        const InstMasks mk = {masked ? s->masks.as<uint32_t>() : nullptr, masked ? region_mask_dev : nullptr};
+        // one launch of the walk: FILL, CLASSIFY and MASKED as types
+        auto walk = [&](auto FILL, auto CLASSIFY, auto MASKED, uint32_t* out, uint32_t* inst_out, uint32_t* shape_out, unsigned char* inside_out) {
+            hipLaunchKernelGGL((k_instances_region_walk<T, decltype(FILL)::value, decltype(CLASSIFY)::value, decltype(MASKED)::value>), grid, block, 0, st, members,
+                               tree_of, xforms, planes_dev, m, pair_region, pair_inst, nc_max, n_units, anc_cnt, anc, out, inst_out, shape_out, inside_out, mk);
+        };
+        using Yes = std::true_type;
+        using No = std::false_type;
+        if (masked) walk(No{}, No{}, Yes{}, counts, nullptr, nullptr, nullptr);
+        else walk(No{}, No{}, No{}, counts, nullptr, nullptr, nullptr);
         BVH_HIP(hipGetLastError());
         const RowsTotals rows = rows_scan(h, n_units, 0u, 0u);
         h->rg_chunks = nc_max; h->rg_chunk_entries = ce_max;   // (behind the scan: a batch that overflowed leaves an empty result)
@@ -499,10 +604,10 @@ void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, 
                 if (classify) h->rg_inside.reserve((size_t)rows.total);
                 uint32_t* shape = h->indices.as<uint32_t>();
                 uint32_t* inst = h->row_instance.as<uint32_t>();
-                if (classify) hipLaunchKernelGGL((k_instances_region_walk<T, true, true>), grid, block, 0, st, members, tree_of, xforms, planes_dev, m, pair_region,
-                                                 pair_inst, nc_max, n_units, anc_cnt, anc, unit_offsets, inst, shape, h->rg_inside.as<unsigned char>());
-                else hipLaunchKernelGGL((k_instances_region_walk<T, true, false>), grid, block, 0, st, members, tree_of, xforms, planes_dev, m, pair_region,
-                                        pair_inst, nc_max, n_units, anc_cnt, anc, unit_offsets, inst, shape, (unsigned char*)nullptr);
+                unsigned char* inside = classify ? h->rg_inside.as<unsigned char>() : nullptr;
+                // (masked too: every unit of a hidden pair has beg == end and is passed over before anything of it is read — no mask needed)
+                if (classify) walk(Yes{}, Yes{}, No{}, unit_offsets, inst, shape, inside);
+                else walk(Yes{}, No{}, No{}, unit_offsets, inst, shape, inside);
             }
             BVH_HIP(hipGetLastError());
             h->total = rows.total;
@@ -512,7 +617,7 @@ void instances_region_batch(bvhgpu_instances* s, const T* planes_dev, size_t n, 
     h->n_rays = n;
     h->stats.hits = h->total;
 }
-template void instances_region_batch<float>(bvhgpu_instances*, const float*, size_t, uint32_t, unsigned, bvhgpu_hits*);
-template void instances_region_batch<double>(bvhgpu_instances*, const double*, size_t, uint32_t, unsigned, bvhgpu_hits*);
+template void instances_region_batch<float>(bvhgpu_instances*, const float*, size_t, uint32_t, unsigned, bvhgpu_hits*, bool, const uint32_t*);
+template void instances_region_batch<double>(bvhgpu_instances*, const double*, size_t, uint32_t, unsigned, bvhgpu_hits*, bool, const uint32_t*);
 
 }  // namespace bvhgpu

@@ -54,7 +54,8 @@ class InstancesMasks:
     iff M[i] & R[j] != 0.  A masked method answers what its unmasked counterpart would over the set without the instances hidden from
     that ray — same order of ties, same bits — and the walk passes over a hidden instance without entering its tree.  The masks are no
     part of the pose: update() keeps them, setting them commits nothing.  Every other method of the set (closest_hits, any_hits, occluded,
-    khits_batch, allhits_batch and the point and region queries) ignores the masks: every instance is visible to it.
+    khits_batch, allhits_batch and the unmasked point and region queries) ignores the masks: every instance is visible to it; the point
+    and region queries have masked forms of their own in InstancesMaskedQueries.
     Kept apart from Instances' own methods so that the call recording of those (tests/golden/instances_calls.json) stays as it is;
     tests/test_instances_masks_marshal_cpu.py holds these to what they hand to the C ABI.
 
@@ -135,12 +136,97 @@ class InstancesMasks:
         return dict(offsets=offsets, instance=instance, shape=shape, vals=vals)
 
 
-class Instances(InstancesTreeForm, InstancesMasks, _Typed):
+class InstancesMaskedQueries:
+    """The point and region queries over the instances visible to each row (bvhgpu_instances_within_masked_*, _knearest_masked_*,
+    _knearest_tree_masked_*, _region_masked_*), which Instances inherits.  M[i] is InstancesMasks' instance mask; a masked point batch
+    carries one 32-bit mask per point, a masked region batch one per region, and instance i is visible to row j iff M[i] & mask[j] != 0.
+    Each method answers what its unmasked counterpart would over the set without the instances hidden from that row — same order of
+    ties, same bits, same outputs — and the walk passes over a hidden instance at its top-level leaf.  For k-nearest that is NOT a filter
+    of the unmasked row: the k slots go to visible pairs only.  The unmasked methods keep ignoring the masks.
+    Kept apart from Instances' own methods so that the call recording of those (tests/golden/instances_calls.json) stays as it is;
+    tests/test_instances_point_masks_marshal_cpu.py holds these to what they hand to the C ABI.
+
+    point_mask / region_mask, everywhere: None (all ones for every row), a Python int in [0, 2^32) (the same mask for every row) or n
+    values in the main input's memory — numpy integers for HOST input, a torch.int32 tensor on the input's device for input in HBM."""
+
+    def within_masked_batch(self, points, max_dist, point_mask, sort: bool = True, count_only: bool = False) -> dict:
+        """bvhgpu_instances_within_masked_*: within_batch over the instances visible to each point — its row without the hidden instances'
+        pairs; sort, count_only and the returns are within_batch's"""
+        api._needs(max_dist, "within_masked_batch needs max_dist (a scalar or one value per point)")
+        keep, pp, n, mem = api._rows_in(points, 3, self.ft, "point")
+        _m, mp = api._side_in(max_dist, keep, n, mem, self.ft, "max_dist", "points", scalar_ok=True)
+        _mk, kp = api._mask_in(point_mask, keep, n, mem, "point_mask", "points")
+        flags = (0 if sort else _lib.INSTANCES_WITHIN_LIST_ORDER) | (_lib.INSTANCES_WITHIN_COUNT_ONLY if count_only else 0)
+        offsets, instance, shape, dist = self._csr("within_masked", (pp, mp, kp, n, mem, flags), n, keep.device if mem == DEVICE else None, count_only,
+                                                   ((), "index"), ((), "index"), ((), "float"), fetch="instances_within")
+        if count_only:
+            return dict(offsets=offsets)
+        return dict(offsets=offsets, instance=instance, shape=shape, dist=dist)
+
+    def knearest_masked_batch(self, points, k: int, point_mask):
+        """bvhgpu_instances_knearest_masked_*: knearest_batch over the instances visible to each point — the first k of the stable ascending
+        sort of all VISIBLE pairs (a hidden pair takes no slot and moves no bound); k and the returns are knearest_batch's"""
+        k = int(k)
+        rows = k if 1 <= k <= _lib.INSTANCES_KNN_MAX_K else 0   # (out of range: the engine answers INVALID_ARG before it touches a buffer)
+        keep, pp, n, mem = api._rows_in(points, 3, self.ft, "point")
+        _mk, kp = api._mask_in(point_mask, keep, n, mem, "point_mask", "points")
+        out, (ip, sp, dp) = api._out_cols(keep.device if mem == DEVICE else None, self.ft, ((n, rows), "index"), ((n, rows), "index"), ((n, rows), "float"))
+        fn = getattr(_lib.load(), f"bvhgpu_instances_knearest_masked_{self.sfx}")
+        check(fn(self._s, pp, kp, n, mem, k & 0xFFFFFFFF, ip, sp, dp), self.ctx._h)
+        return tuple(out)
+
+    def nearest_masked_batch(self, points, point_mask):
+        """knearest_masked_batch with k = 1 and the last axis dropped: (instance[n], shape[n], dist[n]); a point that sees no instance gives
+        NONE, NONE and +inf"""
+        inst, shape, dist = self.knearest_masked_batch(points, 1, point_mask)
+        return inst[:, 0], shape[:, 0], dist[:, 0]
+
+    def knearest_tree_masked_batch(self, points, k: int, point_mask, max_dist=None):
+        """bvhgpu_instances_knearest_tree_masked_*: knearest_tree_batch's descent over the same top level, a hidden instance's leaf
+        contributing nothing; ties stay in that walk's order.  k, max_dist and the returns are knearest_tree_batch's"""
+        k = int(k)
+        rows = k if 1 <= k <= _lib.INSTANCES_KNN_MAX_K else 0   # (out of range: the engine answers INVALID_ARG before it touches a buffer)
+        keep, pp, n, mem = api._rows_in(points, 3, self.ft, "point")
+        _m, mp = api._side_in(max_dist, keep, n, mem, self.ft, "max_dist", "points", scalar_ok=True)
+        _mk, kp = api._mask_in(point_mask, keep, n, mem, "point_mask", "points")
+        out, (ip, sp, dp) = api._out_cols(keep.device if mem == DEVICE else None, self.ft, ((n, rows), "index"), ((n, rows), "index"), ((n, rows), "float"))
+        fn = getattr(_lib.load(), f"bvhgpu_instances_knearest_tree_masked_{self.sfx}")
+        check(fn(self._s, pp, kp, n, mem, k & 0xFFFFFFFF, mp, ip, sp, dp), self.ctx._h)
+        return tuple(out)
+
+    def nearest_tree_masked_batch(self, points, point_mask, max_dist=None):
+        """knearest_tree_masked_batch with k = 1 and the last axis dropped: (instance[n], shape[n], dist[n])"""
+        inst, shape, dist = self.knearest_tree_masked_batch(points, 1, point_mask, max_dist)
+        return inst[:, 0], shape[:, 0], dist[:, 0]
+
+    def region_masked_batch(self, planes, region_mask, classify: bool = False, count_only: bool = False, instances_only: bool = False) -> dict:
+        """bvhgpu_instances_region_masked_*: region_batch over the instances visible to each region (a camera's culling mask against the
+        objects' layers): the visible instances among those whose world box passes, in the top level's order, each walked as region_batch
+        walks it.  classify, count_only, instances_only and the returns are region_batch's"""
+        n, m = _plane_dims(planes)
+        keep, pp, _rows, mem = api._rows_in(planes, 4, self.ft, "plane")
+        _mk, kp = api._mask_in(region_mask, keep, n, mem, "region_mask", "regions")
+        classify = bool(classify) and not count_only
+        flags = ((_lib.REGION_COUNT_ONLY if count_only else 0) | (_lib.REGION_CLASSIFY if classify else 0) |
+                 (_lib.REGION_INSTANCES_ONLY if instances_only else 0))
+        index, byte = ((), "index"), ((), "byte")
+        offsets, instance, shape, inside = self._csr("region_masked", (pp, kp, n, m, mem, flags), n, keep.device if mem == DEVICE else None, count_only,
+                                                     index, None if instances_only else index, byte if classify else None, fetch="instances_region")
+        out = dict(offsets=offsets, instance=instance)
+        if not instances_only:
+            out["shape"] = shape
+        if classify:
+            out["inside"] = inside
+        return out
+
+
+class Instances(InstancesTreeForm, InstancesMasks, InstancesMaskedQueries, _Typed):
     """bvhgpu_instances: `trees` (Bvh / FlatBvh objects of one context and dtype, with set_triangles done; kept referenced), `tree_of[i]`
     the member of instance i, `transforms` n x 12 or n x 3 x 4 (row-major 3x4, object -> world) in the trees' dtype.  update() is the
     re-pose and the re-sync: call it after moving instances and after any rebuild, refit or set_triangles of a member tree; a trace on a
-    set whose member was rebuilt since raises INVALID_ARG ("instances are stale").  The *_masked methods (InstancesMasks) see only the
-    instances whose mask shares a bit with the ray's; every other method ignores the masks."""
+    set whose member was rebuilt since raises INVALID_ARG ("instances are stale").  The *_masked methods (InstancesMasks for rays,
+    InstancesMaskedQueries for points and regions) see only the instances whose mask shares a bit with the row's; every other method
+    ignores the masks."""
 
     def __init__(self, trees: Sequence, tree_of, transforms, ctx: Optional[Context] = None):
         trees = list(trees)

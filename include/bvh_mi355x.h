@@ -1151,6 +1151,50 @@ int bvhgpu_instances_allhits_masked_f32(bvhgpu_instances *s, const bvhgpu_ray_f3
 int bvhgpu_instances_allhits_masked_f64(bvhgpu_instances *s, const bvhgpu_ray_f64 *rays, const double *tmax, const uint32_t *ray_mask, size_t n_rays,
                                         int mem, unsigned flags, bvhgpu_hits **hits);
 
+/* ---- the same masks for the point and region queries over an instanced scene: the nearest selectable object, a proximity
+ * query that must not see the querying object's own instance, collision layers, frustum culling with a camera's layer mask.
+ *  - M[i] is the instance mask above: no new state; bvhgpu_instances_set_masks, _masks and _update_* are untouched.
+ *  - A masked point batch carries one u32 P[j] per point, a masked region batch one u32 P[q] per region.  A NULL `point_mask` /
+ *    `region_mask` means 0xFFFFFFFF for every row.  Instance i is VISIBLE to row j iff (M[i] & P[j]) != 0.
+ *  - within: row j is bvhgpu_instances_within_*'s row with the pairs of invisible instances removed (the candidate set does not depend on the
+ *    walk's order).  Sorted, LIST_ORDER and COUNT_ONLY as there; distances and the order of ties unchanged.
+ *  - knearest: bvhgpu_instances_knearest_*'s incremental list (strict <, the earlier pair keeps a tie) over the double order with the rows of
+ *    invisible instances removed; the bound that prunes comes from visible pairs only.  Row j is the first k of the stable ascending sort
+ *    of all VISIBLE pairs, padded with BVHGPU_NONE / +inf.  (Filtering an unmasked row afterwards is not this: its k slots may be spent on
+ *    hidden pairs.)
+ *  - knearest_tree: bvhgpu_instances_knearest_tree_*'s descent over the SAME top-level BvhNode array — the top level of the whole set.  A
+ *    top-level leaf whose instance is invisible contributes nothing and is left as a leaf whose member has no shapes is left.  Ties stay
+ *    in this walk's order; max_dist and its special values as there.
+ *  - region: I_q is the VISIBLE instances among those whose world box passes, in the top level's order; the object-space planes, the member
+ *    rows and the CLASSIFY bytes of the survivors are unchanged.  With BVHGPU_REGION_INSTANCES_ONLY the row is that I_q, with CLASSIFY the
+ *    surviving bytes.
+ *  - A surviving pair's bits are unchanged: every operand of its test comes from the point or region and from X_i / Y_i alone.  No pruning
+ *    beyond what each family already does.  A hidden instance costs one 4-byte load at its top-level leaf (region: per unit of its pair).
+ *  - The unmasked entries keep ignoring masks.
+ * `point_mask` is n u32 in the points' memory and `region_mask` n u32 in the planes' memory, or NULL; every other argument, the flags and
+ * the range of k are the unmasked counterpart's.  Each entry makes the refusals of its counterpart, in the same order and with the same
+ * messages; a refused call touches no buffer and leaves *hits as it was.  A result is of the counterpart's kind and is read by the
+ * counterpart's fetch entries (bvhgpu_hits_fetch_instances_within, bvhgpu_hits_fetch_instances_region).  bvhgpu_hits_walk_kernel on a
+ * masked within result names the masked fill (or count) kernel; on a masked region result it names the launch that looks at the masks —
+ * the count walk k_instances_region_walk<T, false, false, true>, or k_instances_region_visible with BVHGPU_REGION_INSTANCES_ONLY — not the
+ * kernel that writes the rows, which is the unmasked fill walk. */
+int bvhgpu_instances_within_masked_f32(bvhgpu_instances *s, const float *points, const float *max_dist, const uint32_t *point_mask, size_t n, int mem,
+                                       unsigned flags, bvhgpu_hits **hits);
+int bvhgpu_instances_within_masked_f64(bvhgpu_instances *s, const double *points, const double *max_dist, const uint32_t *point_mask, size_t n, int mem,
+                                       unsigned flags, bvhgpu_hits **hits);
+int bvhgpu_instances_knearest_masked_f32(bvhgpu_instances *s, const float *points, const uint32_t *point_mask, size_t n, int mem, uint32_t k,
+                                         uint32_t *out_instance /* n x k */, uint32_t *out_shape /* n x k */, float *out_dist /* n x k */);
+int bvhgpu_instances_knearest_masked_f64(bvhgpu_instances *s, const double *points, const uint32_t *point_mask, size_t n, int mem, uint32_t k,
+                                         uint32_t *out_instance /* n x k */, uint32_t *out_shape /* n x k */, double *out_dist /* n x k */);
+int bvhgpu_instances_knearest_tree_masked_f32(bvhgpu_instances *s, const float *points, const uint32_t *point_mask, size_t n, int mem, uint32_t k,
+                                              const float *max_dist, uint32_t *out_instance, uint32_t *out_shape, float *out_dist);
+int bvhgpu_instances_knearest_tree_masked_f64(bvhgpu_instances *s, const double *points, const uint32_t *point_mask, size_t n, int mem, uint32_t k,
+                                              const double *max_dist, uint32_t *out_instance, uint32_t *out_shape, double *out_dist);
+int bvhgpu_instances_region_masked_f32(bvhgpu_instances *s, const float *planes, const uint32_t *region_mask, size_t n, uint32_t m, int mem,
+                                       unsigned flags, bvhgpu_hits **hits);
+int bvhgpu_instances_region_masked_f64(bvhgpu_instances *s, const double *planes, const uint32_t *region_mask, size_t n, uint32_t m, int mem,
+                                       unsigned flags, bvhgpu_hits **hits);
+
 /* ---- timing hook used by bench.py: HIP-event time (ms) of the kernels of the last call of each
  * phase on this ctx's stream (build / flatten / traverse main kernel / traverse total). ---- */
 typedef struct { float build_ms, flatten_ms, traverse_kernel_ms, traverse_total_ms; } bvhgpu_timings;

@@ -259,6 +259,14 @@ extern "C" {
     pub fn bvhgpu_instances_khits_masked_f64(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f64, tmax: *const f64, ray_mask: *const u32, n_rays: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_vals: *mut f64) -> c_int;
     pub fn bvhgpu_instances_allhits_masked_f32(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f32, tmax: *const f32, ray_mask: *const u32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_instances_allhits_masked_f64(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f64, tmax: *const f64, ray_mask: *const u32, n_rays: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_instances_within_masked_f32(s: *mut bvhgpu_instances, points: *const f32, max_dist: *const f32, point_mask: *const u32, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_instances_within_masked_f64(s: *mut bvhgpu_instances, points: *const f64, max_dist: *const f64, point_mask: *const u32, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_instances_knearest_masked_f32(s: *mut bvhgpu_instances, points: *const f32, point_mask: *const u32, n: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_dist: *mut f32) -> c_int;
+    pub fn bvhgpu_instances_knearest_masked_f64(s: *mut bvhgpu_instances, points: *const f64, point_mask: *const u32, n: usize, mem: c_int, k: u32, out_instance: *mut u32, out_shape: *mut u32, out_dist: *mut f64) -> c_int;
+    pub fn bvhgpu_instances_knearest_tree_masked_f32(s: *mut bvhgpu_instances, points: *const f32, point_mask: *const u32, n: usize, mem: c_int, k: u32, max_dist: *const f32, out_instance: *mut u32, out_shape: *mut u32, out_dist: *mut f32) -> c_int;
+    pub fn bvhgpu_instances_knearest_tree_masked_f64(s: *mut bvhgpu_instances, points: *const f64, point_mask: *const u32, n: usize, mem: c_int, k: u32, max_dist: *const f64, out_instance: *mut u32, out_shape: *mut u32, out_dist: *mut f64) -> c_int;
+    pub fn bvhgpu_instances_region_masked_f32(s: *mut bvhgpu_instances, planes: *const f32, region_mask: *const u32, n: usize, m: u32, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_instances_region_masked_f64(s: *mut bvhgpu_instances, planes: *const f64, region_mask: *const u32, n: usize, m: u32, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_instances_boxes(s: *mut bvhgpu_instances, out: *mut c_void, mem: c_int) -> c_int;
     pub fn bvhgpu_instances_info(s: *const bvhgpu_instances, dtype: *mut c_int, n_trees: *mut usize, n_instances: *mut usize) -> c_int;
     pub fn bvhgpu_instances_destroy(s: *mut bvhgpu_instances);

@@ -1191,6 +1191,134 @@ impl<T: GpuScalar> GpuInstances<T> {
         }
         (offsets, instance, shape, vals)
     }
+
+    /// `within_distance` over the instances visible to each point (`bvhgpu_instances_within_masked_*`): instance `i` is visible to point `j`
+    /// iff `masks[i] & point_mask[j] != 0` (`None`: all ones).  Row `j` is `within_distance`'s row without the hidden instances' pairs.
+    pub fn within_masked(&self, points: &[[T; 3]], max_dist: &[T], point_mask: Option<&[u32]>, sort: bool, count_only: bool) -> (Vec<u32>, Vec<u32>, Vec<u32>, Vec<T>) {
+        assert_eq!(max_dist.len(), points.len(), "one max_dist per point");
+        if let Some(m) = point_mask {
+            assert_eq!(m.len(), points.len(), "point_mask needs one value per point");
+        }
+        let n = points.len();
+        let flags: c_uint = (if sort { 0 } else { ffi::BVHGPU_INSTANCES_WITHIN_LIST_ORDER })
+            | (if count_only { ffi::BVHGPU_INSTANCES_WITHIN_COUNT_ONLY } else { 0 });
+        let mut hits = core::ptr::null_mut();
+        let mut offsets = vec![0u32; n + 1];
+        let (mut instance, mut shape, mut dist) = (Vec::new(), Vec::new(), Vec::new());
+        unsafe {
+            let mp = point_mask.map_or(core::ptr::null(), |m| m.as_ptr());
+            let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_within_masked_f32(self.set, points.as_ptr().cast(), max_dist.as_ptr().cast(), mp, n, ffi::BVHGPU_HOST, flags, &mut hits)
+            } else {
+                ffi::bvhgpu_instances_within_masked_f64(self.set, points.as_ptr().cast(), max_dist.as_ptr().cast(), mp, n, ffi::BVHGPU_HOST, flags, &mut hits)
+            };
+            check(self.ctx, rc);   // (a refused batch made no result object)
+            let mut total = 0u64;
+            let mut rc = ffi::bvhgpu_hits_info(hits, core::ptr::null_mut(), &mut total, core::ptr::null_mut());
+            if rc == ffi::BVHGPU_OK {
+                let rows = if count_only { 0 } else { total as usize };
+                instance.resize(rows, 0u32);
+                shape.resize(rows, 0u32);
+                dist.resize(rows, T::default());
+                let (ip, sp, dp) = if count_only {
+                    (core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut())
+                } else {
+                    (instance.as_mut_ptr(), shape.as_mut_ptr(), dist.as_mut_ptr() as *mut c_void)
+                };
+                rc = ffi::bvhgpu_hits_fetch_instances_within(hits, offsets.as_mut_ptr(), ip, sp, dp, ffi::BVHGPU_HOST);
+            }
+            ffi::bvhgpu_hits_destroy(hits);   // before the check, which panics on a failure
+            check(self.ctx, rc);
+        }
+        (offsets, instance, shape, dist)
+    }
+
+    /// `knearest` over the instances visible to each point (`bvhgpu_instances_knearest_masked_*`): the first `k` of the stable ascending sort
+    /// of all VISIBLE pairs — a hidden pair takes no slot and moves no bound, which a filter of `knearest`'s row cannot give.
+    pub fn knearest_masked(&self, points: &[[T; 3]], point_mask: Option<&[u32]>, k: usize) -> (Vec<u32>, Vec<u32>, Vec<T>) {
+        if let Some(m) = point_mask {
+            assert_eq!(m.len(), points.len(), "point_mask needs one value per point");
+        }
+        let k32 = u32::try_from(k).unwrap_or(u32::MAX);   // (out of range: the engine answers BVHGPU_INVALID_ARG and `check` panics with its message)
+        let slots = if (1..=ffi::BVHGPU_INSTANCES_KNN_MAX_K).contains(&k32) { points.len() * k } else { 0 };
+        let (mut instance, mut shape, mut dist) = (vec![0u32; slots], vec![0u32; slots], vec![T::default(); slots]);
+        unsafe {
+            let mp = point_mask.map_or(core::ptr::null(), |m| m.as_ptr());
+            let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_knearest_masked_f32(self.set, points.as_ptr().cast(), mp, points.len(), ffi::BVHGPU_HOST, k32, instance.as_mut_ptr(),
+                                                          shape.as_mut_ptr(), dist.as_mut_ptr().cast())
+            } else {
+                ffi::bvhgpu_instances_knearest_masked_f64(self.set, points.as_ptr().cast(), mp, points.len(), ffi::BVHGPU_HOST, k32, instance.as_mut_ptr(),
+                                                          shape.as_mut_ptr(), dist.as_mut_ptr().cast())
+            };
+            check(self.ctx, rc);
+        }
+        (instance, shape, dist)
+    }
+
+    /// `knearest_tree` over the instances visible to each point (`bvhgpu_instances_knearest_tree_masked_*`): the same descent over the same
+    /// top level, a hidden instance's leaf contributing nothing; ties stay in that walk's order.
+    pub fn knearest_tree_masked(&self, points: &[[T; 3]], point_mask: Option<&[u32]>, k: usize, max_dist: Option<&[T]>) -> (Vec<u32>, Vec<u32>, Vec<T>) {
+        if let Some(m) = max_dist {
+            assert_eq!(m.len(), points.len(), "max_dist needs one value per point");
+        }
+        if let Some(m) = point_mask {
+            assert_eq!(m.len(), points.len(), "point_mask needs one value per point");
+        }
+        let k32 = u32::try_from(k).unwrap_or(u32::MAX);   // (out of range: the engine answers BVHGPU_INVALID_ARG and `check` panics with its message)
+        let slots = if (1..=ffi::BVHGPU_INSTANCES_KNN_MAX_K).contains(&k32) { points.len() * k } else { 0 };
+        let (mut instance, mut shape, mut dist) = (vec![0u32; slots], vec![0u32; slots], vec![T::default(); slots]);
+        unsafe {
+            let dp = max_dist.map_or(core::ptr::null(), |m| m.as_ptr());
+            let mp = point_mask.map_or(core::ptr::null(), |m| m.as_ptr());
+            let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_knearest_tree_masked_f32(self.set, points.as_ptr().cast(), mp, points.len(), ffi::BVHGPU_HOST, k32, dp.cast(),
+                                                               instance.as_mut_ptr(), shape.as_mut_ptr(), dist.as_mut_ptr().cast())
+            } else {
+                ffi::bvhgpu_instances_knearest_tree_masked_f64(self.set, points.as_ptr().cast(), mp, points.len(), ffi::BVHGPU_HOST, k32, dp.cast(),
+                                                               instance.as_mut_ptr(), shape.as_mut_ptr(), dist.as_mut_ptr().cast())
+            };
+            check(self.ctx, rc);
+        }
+        (instance, shape, dist)
+    }
+
+    /// `region_query` over the instances visible to each region (`bvhgpu_instances_region_masked_*`): a camera's culling mask against the
+    /// instances' layers.  `region_mask`: one mask per region, `None`: all ones; everything else as for `region_query`.
+    pub fn region_masked(&self, planes: &[[T; 4]], m: usize, region_mask: Option<&[u32]>, classify: bool, count_only: bool, instances_only: bool)
+                         -> (Vec<u32>, Vec<u32>, Vec<u32>, Vec<u8>) {
+        let n = if m == 0 { 0 } else { planes.len() / m };
+        assert_eq!(n * m, planes.len(), "planes.len() must be a multiple of m");
+        if let Some(r) = region_mask {
+            assert_eq!(r.len(), n, "region_mask needs one value per region");
+        }
+        let classify = classify && !count_only;
+        let flags = (if count_only { ffi::BVHGPU_REGION_COUNT_ONLY } else { 0 }) | (if classify { ffi::BVHGPU_REGION_CLASSIFY } else { 0 })
+            | (if instances_only { ffi::BVHGPU_REGION_INSTANCES_ONLY } else { 0 });
+        let mut hits = core::ptr::null_mut();
+        let mut offsets = vec![0u32; n + 1];
+        let (mut instance, mut shape, mut inside) = (Vec::new(), Vec::new(), Vec::new());
+        unsafe {
+            let mp = region_mask.map_or(core::ptr::null(), |r| r.as_ptr());
+            let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_instances_region_masked_f32(self.set, planes.as_ptr().cast(), mp, n, m as u32, ffi::BVHGPU_HOST, flags, &mut hits)
+            } else {
+                ffi::bvhgpu_instances_region_masked_f64(self.set, planes.as_ptr().cast(), mp, n, m as u32, ffi::BVHGPU_HOST, flags, &mut hits)
+            };
+            check(self.ctx, rc);
+            let mut total = 0u64;
+            check(self.ctx, ffi::bvhgpu_hits_info(hits, core::ptr::null_mut(), &mut total, core::ptr::null_mut()));
+            let rows = if count_only { 0 } else { total as usize };
+            instance.resize(rows, 0u32);
+            if !instances_only { shape.resize(rows, 0u32); }
+            if classify { inside.resize(rows, 0u8); }
+            let shape_ptr = if instances_only { core::ptr::null_mut() } else { shape.as_mut_ptr() };
+            let inside_ptr = if classify { inside.as_mut_ptr() as *mut c_void } else { core::ptr::null_mut() };
+            check(self.ctx, ffi::bvhgpu_hits_fetch_instances_region(hits, offsets.as_mut_ptr(), instance.as_mut_ptr(), shape_ptr, inside_ptr, ffi::BVHGPU_HOST));
+            ffi::bvhgpu_hits_destroy(hits);
+        }
+        (offsets, instance, shape, inside)
+    }
 }
 
 impl<T: GpuScalar> Drop for GpuInstances<T> {

@@ -21,7 +21,7 @@ HOST, DEVICE = 0, 1
 NONE = 0xFFFFFFFF
 KNN_MAX_K = 64   # BVHGPU_KNN_MAX_K: largest k of bvhgpu_knearest_*
 KHITS_MAX_K = 64   # BVHGPU_KHITS_MAX_K: largest k of bvhgpu_traverse_khits_*
-LEAF_BOX, LEAF_TRIANGLE, LEAF_SPHERE = 0, 1, 2   # BVHGPU_LEAF_*: the leaf stage of bvhgpu_traverse_khits_*
+LEAF_BOX, LEAF_TRIANGLE, LEAF_SPHERE = 0, 1, 2   # BVHGPU_LEAF_*: the leaf stage of bvhgpu_traverse_khits_* / _allhits_* and of an instance set
 LEAF_KINDS = {"box": LEAF_BOX, "triangle": LEAF_TRIANGLE, "sphere": LEAF_SPHERE}
 LEAF_WIDTH = {LEAF_BOX: 2, LEAF_TRIANGLE: 3, LEAF_SPHERE: 2}   # scalars per record
 ALLHITS_LIST_ORDER = 1   # BVHGPU_ALLHITS_LIST_ORDER: rows of bvhgpu_traverse_allhits_* in list order, no sort pass
@@ -192,6 +192,9 @@ SYMBOLS = [
     ("bvhgpu_hits_region_info", _i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("bvhgpu_instances_create_f32", _i, [_vp, _vp, _sz, _vp, _vp, _sz, _i, _pp]),
     ("bvhgpu_instances_create_f64", _i, [_vp, _vp, _sz, _vp, _vp, _sz, _i, _pp]),
+    ("bvhgpu_instances_create_leaf_f32", _i, [_vp, _vp, _sz, _vp, _vp, _sz, _i, _i, _pp]),
+    ("bvhgpu_instances_create_leaf_f64", _i, [_vp, _vp, _sz, _vp, _vp, _sz, _i, _i, _pp]),
+    ("bvhgpu_instances_leaf", _i, [_vp, C.POINTER(_i)]),
     ("bvhgpu_instances_update_f32", _i, [_vp, _vp, _sz, _i]),
     ("bvhgpu_instances_update_f64", _i, [_vp, _vp, _sz, _i]),
     ("bvhgpu_instances_trace_f32", _i, [_vp, _vp, _vp, _sz, _i, _u, _vp, _vp, _vp]),

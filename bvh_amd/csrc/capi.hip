@@ -1061,7 +1061,8 @@ int do_traverse_host(bvhgpu_tree* tree, const T* aabbs, size_t n_shapes, bool re
 
 // ---- instanced scenes: bvhgpu_instances_* (instances.hip) ------------------------------------------------------------------------------
 // The rules every member tree must pass, rule by rule over all members (the first broken rule wins); create and update share them.
-template <typename T> int instances_members_ok(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_trees) {
+// leaf: the set's kind — the per-shape array every member must hold (BVHGPU_LEAF_BOX: none besides its boxes)
+template <typename T> int instances_members_ok(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_trees, int leaf) {
     for (size_t k = 0; k < n_trees; k++) if (!trees[k]) return fail(ctx, BVHGPU_INVALID_ARG, "NULL member tree");
     for (size_t k = 0; k < n_trees; k++)
         if (trees[k]->dtype != Traits<T>::dtype) return fail(ctx, BVHGPU_DTYPE_MISMATCH, "member tree dtype differs from the instance set's");
@@ -1070,8 +1071,12 @@ template <typename T> int instances_members_ok(bvhgpu_ctx* ctx, bvhgpu_tree* con
     for (size_t k = 0; k < n_trees; k++) if (const int rc = settle(trees[k])) return rc;
     for (size_t k = 0; k < n_trees; k++)
         if (!trees[k]->flattened) return fail(ctx, BVHGPU_NOT_FLATTENED, "member tree is not flattened: call bvhgpu_flatten first");
-    for (size_t k = 0; k < n_trees; k++)
-        if (!trees[k]->has_tris) return fail(ctx, BVHGPU_INVALID_ARG, "instances need bvhgpu_tree_set_triangles on every member tree first");
+    for (size_t k = 0; k < n_trees; k++) {
+        if (leaf == BVHGPU_LEAF_TRIANGLE && !trees[k]->has_tris)
+            return fail(ctx, BVHGPU_INVALID_ARG, "instances need bvhgpu_tree_set_triangles on every member tree first");
+        if (leaf == BVHGPU_LEAF_SPHERE && !trees[k]->has_spheres)
+            return fail(ctx, BVHGPU_INVALID_ARG, "instances of sphere leaves need bvhgpu_tree_set_spheres on every member tree first");
+    }
     return BVHGPU_OK;
 }
 // the pose in the caller's memory becomes the set's own copy and is committed (throws)
@@ -1087,18 +1092,19 @@ template <typename T> void instances_pose(bvhgpu_instances* s, const T* xforms, 
 }
 template <typename T>
 int do_instances_create(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_trees, const uint32_t* tree_of, const T* xforms, size_t n, int mem,
-                        bvhgpu_instances** out) {
+                        int leaf, bvhgpu_instances** out) {
     if (!ctx || !out) return fail(ctx, BVHGPU_INVALID_ARG, "ctx/out is NULL");
     *out = nullptr;
     if ((n_trees && !trees) || (n && (!tree_of || !xforms))) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
     if (const int rc = rule_mem(ctx, mem)) return rc;
-    if (const int rc = instances_members_ok<T>(ctx, trees, n_trees)) return rc;
+    if (const int rc = rule_leaf(ctx, leaf)) return rc;
+    if (const int rc = instances_members_ok<T>(ctx, trees, n_trees, leaf)) return rc;
     if (n > MAX_SHAPES || n_trees >= 0xFFFFFFFFull) return fail(ctx, BVHGPU_OVERFLOW, "too many instances for u32 flat indices");
     bvhgpu_instances* s = nullptr;
     const int rc = guarded(ctx, [&] {
         use_device(ctx);
         s = new bvhgpu_instances();
-        s->ctx = ctx; s->dtype = Traits<T>::dtype; s->n = n;
+        s->ctx = ctx; s->dtype = Traits<T>::dtype; s->leaf = leaf; s->n = n;
         s->trees.assign(trees, trees + n_trees);
         s->top = new bvhgpu_tree();
         s->top->ctx = ctx; s->top->dtype = Traits<T>::dtype;
@@ -1133,13 +1139,19 @@ template <typename T> int do_instances_update(bvhgpu_instances* s, const T* xfor
     if (n && !xforms) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
     if (const int rc = rule_mem(ctx, mem)) return rc;
     if (const int rc = rule_set_dtype<T>(s, "transform")) return rc;
-    if (const int rc = instances_members_ok<T>(ctx, s->trees.data(), s->trees.size())) return rc;
+    if (const int rc = instances_members_ok<T>(ctx, s->trees.data(), s->trees.size(), s->leaf)) return rc;
     if (n != s->n) return fail(ctx, BVHGPU_INVALID_ARG, "update: the number of instances differs from the set's");
     const int rc = guarded(ctx, [&] { use_device(ctx); instances_pose<T>(s, xforms, mem); return (int)BVHGPU_OK; });
     if (rc != BVHGPU_OK) (void)hipStreamSynchronize(ctx->stream);   // (the set stays uncommitted: instances_pose cleared the mark first)
     return rc;
 }
 // what every batch over a set asks before anything is launched: a committed pose, and members that are still what the commit read
+size_t set_width(const bvhgpu_instances* s) { return s->leaf == BVHGPU_LEAF_TRIANGLE ? 3 : 2; }   // scalars per record of the set's ray families
+// the point families measure the distance to a member's triangles: a BOX or SPHERE set has none to measure
+int rule_set_triangles(const bvhgpu_instances* s) {
+    return s->leaf == BVHGPU_LEAF_TRIANGLE ? (int)BVHGPU_OK
+                                           : fail(s->ctx, BVHGPU_INVALID_ARG, "point queries measure triangle distance: the instance set was created with BVHGPU_LEAF_BOX or BVHGPU_LEAF_SPHERE");
+}
 int rule_committed(const bvhgpu_instances* s) {
     return s->committed ? (int)BVHGPU_OK : fail(s->ctx, BVHGPU_INVALID_ARG, "instances are not committed (the last commit failed): call bvhgpu_instances_update");
 }
@@ -1148,8 +1160,11 @@ int instances_current(bvhgpu_instances* s) {
     for (size_t k = 0; k < s->trees.size(); k++) {   // what the commit read of every member must still be what the member holds
         const bvhgpu_tree* t = s->trees[k];
         const bvhgpu_instances::Seen& c = s->seen[k];
-        if (t->trav.p != c.trav || t->aabbs.p != c.aabbs || t->tris.p != c.tris || t->n != c.n || t->n_trav != c.n_trav || t->gen != c.gen ||
-            !t->flattened || !t->has_tris || t->pending_build || t->pending_recv)
+        // the array of the set's kind: where it lives and whether the member still has it (a BOX set reads the boxes alone)
+        const void* prims = s->leaf == BVHGPU_LEAF_TRIANGLE ? t->tris.p : (s->leaf == BVHGPU_LEAF_SPHERE ? t->spheres.p : nullptr);
+        const bool has = s->leaf == BVHGPU_LEAF_TRIANGLE ? t->has_tris : (s->leaf == BVHGPU_LEAF_SPHERE ? t->has_spheres : true);
+        if (t->trav.p != c.trav || t->aabbs.p != c.aabbs || prims != c.prims || t->n != c.n || t->n_trav != c.n_trav || t->gen != c.gen ||
+            !t->flattened || !has || t->pending_build || t->pending_recv)
             return fail(s->ctx, BVHGPU_INVALID_ARG, "instances are stale: call bvhgpu_instances_update");
     }
     return BVHGPU_OK;
@@ -1185,7 +1200,7 @@ int do_instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays,
     return guarded(ctx, [&] {
         use_device(ctx);
         RowStage st(ctx, mem, {{rays, n * sizeof(Ray)}, {tmax, n * sizeof(T)}, {masked ? ray_mask : nullptr, masked ? n * 4 : 0}},
-                    {{out_vals, n * 3 * sizeof(T)}, {out_instance, n * 4}, {out_shape, n * 4}});
+                    {{out_vals, n * set_width(s) * sizeof(T)}, {out_instance, n * 4}, {out_shape, n * 4}});
         instances_trace<T>(s, st.at<const Ray>(0), n ? st.at<const T>(1) : nullptr, n, (flags & BVHGPU_TRAVERSE_FIRST) != 0, st.at<T>(3), st.at<uint32_t>(4),
                            st.at<uint32_t>(5), masked, n ? st.at<const uint32_t>(2) : nullptr);
         st.finish(true);   // in HBM too the rows are complete when the call returns, whichever stream reads them next
@@ -1257,6 +1272,7 @@ int do_instances_within(bvhgpu_instances* s, const T* points, const T* max_dist,
     if (n && !max_dist) return fail(ctx, BVHGPU_INVALID_ARG, "max_dist is NULL");
     if (const int rc = rule_mem(ctx, mem)) return rc;
     if (const int rc = rule_set_dtype<T>(s, "point")) return rc;
+    if (const int rc = rule_set_triangles(s)) return rc;
     if (flags & ~(BVHGPU_INSTANCES_WITHIN_LIST_ORDER | BVHGPU_INSTANCES_WITHIN_COUNT_ONLY))
         return fail(ctx, BVHGPU_INVALID_ARG, "instance within flags: BVHGPU_INSTANCES_WITHIN_LIST_ORDER and BVHGPU_INSTANCES_WITHIN_COUNT_ONLY only");
     if (const int rc = instances_current(s)) return rc;
@@ -1280,6 +1296,7 @@ int do_instances_knearest(bvhgpu_instances* s, const T* points, size_t n, int me
     if (n && (!points || !out_instance || !out_shape || !out_dist)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
     if (const int rc = rule_mem(ctx, mem)) return rc;
     if (const int rc = rule_set_dtype<T>(s, "point")) return rc;
+    if (const int rc = rule_set_triangles(s)) return rc;
     if (const int rc = instances_current(s)) return rc;   // (a member that lost its triangles is stale)
     if (const int rc = rule_members_unfolded(s)) return rc;
     if (const int rc = rule_rows_size(ctx, n, k, "too many results (points x k) in one call")) return rc;
@@ -1308,6 +1325,7 @@ int do_instances_knearest_tree(bvhgpu_instances* s, const T* points, size_t n, i
     if (n && (!points || !out_instance || !out_shape || !out_dist)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
     if (const int rc = rule_mem(ctx, mem)) return rc;
     if (const int rc = rule_set_dtype<T>(s, "point")) return rc;
+    if (const int rc = rule_set_triangles(s)) return rc;
     if (const int rc = instances_current(s)) return rc;   // (a member that lost its triangles is stale)
     if (const int rc = rule_members_built(s)) return rc;
     if (const int rc = rule_rows_size(ctx, n, k, "too many results (points x k) in one call")) return rc;
@@ -1336,7 +1354,7 @@ int do_instances_khits(bvhgpu_instances* s, const typename Traits<T>::Ray* rays,
     return guarded(ctx, [&] {
         use_device(ctx);
         RowStage st(ctx, mem, {{rays, n * sizeof(Ray)}, {tmax, n * sizeof(T)}, {masked ? ray_mask : nullptr, masked ? n * 4 : 0}},
-                    {{out_vals, n * k * 3 * sizeof(T)}, {out_instance, n * k * 4}, {out_shape, n * k * 4}});
+                    {{out_vals, n * k * set_width(s) * sizeof(T)}, {out_instance, n * k * 4}, {out_shape, n * k * 4}});
         instances_khits_batch<T>(s, st.at<const Ray>(0), n ? st.at<const T>(1) : nullptr, n, k, st.at<uint32_t>(4), st.at<uint32_t>(5), st.at<T>(3), masked,
                                  n ? st.at<const uint32_t>(2) : nullptr);
         st.finish(true);   // in HBM too the rows are complete when the call returns, whichever stream reads them next
@@ -2013,12 +2031,12 @@ int bvhgpu_hits_fetch_instances_region(bvhgpu_hits* h, uint32_t* offsets, uint32
     return csr_copy(h, mem, offsets, h->rg_offsets, rows_unless_count_only(h),
                     {{instance, only ? &h->indices : &h->row_instance, 4}, {shape, &h->indices, 4}, {inside, &h->rg_inside, 1}});
 }
-// all-hits over an instance set: the instances and the shapes (u32 each), the records (3 x T).  A COUNT_ONLY batch refuses every column.
+// all-hits over an instance set: the instances and the shapes (u32 each), the records (W x T by the set's leaf kind).  A COUNT_ONLY batch refuses every column.
 int bvhgpu_hits_fetch_instances_allhits(bvhgpu_hits* h, uint32_t* offsets, uint32_t* instance, uint32_t* shape, void* vals, int mem) {
     if (const int rc = csr_open(h, HitsKind::InstAllhits, mem)) return rc;
     if ((instance || shape || vals) && h->count_only)
         return fail(h->ctx, BVHGPU_INVALID_ARG, "the batch was run with BVHGPU_INSTANCES_ALLHITS_COUNT_ONLY: it has offsets only");
-    return csr_copy(h, mem, offsets, h->offsets, h->total, {{instance, &h->row_instance, 4}, {shape, &h->indices, 4}, {vals, &h->row_vals, 3 * scalar_bytes(h)}});
+    return csr_copy(h, mem, offsets, h->offsets, h->total, {{instance, &h->row_instance, 4}, {shape, &h->indices, 4}, {vals, &h->row_vals, (h->row_leaf == BVHGPU_LEAF_TRIANGLE ? 3 : 2) * scalar_bytes(h)}});
 }
 // within over an instance set: the instances and the shapes (u32 each), the distances (T).  A COUNT_ONLY batch refuses every column.
 int bvhgpu_hits_fetch_instances_within(bvhgpu_hits* h, uint32_t* offsets, uint32_t* instance, uint32_t* shape, void* dist, int mem) {
@@ -2052,11 +2070,24 @@ void bvhgpu_hits_destroy(bvhgpu_hits* h) {
 
 int bvhgpu_instances_create_f32(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_trees, const uint32_t* tree_of, const float* xforms, size_t n,
                                 int mem, bvhgpu_instances** out) {
-    return do_instances_create<float>(ctx, trees, n_trees, tree_of, xforms, n, mem, out);
+    return do_instances_create<float>(ctx, trees, n_trees, tree_of, xforms, n, mem, BVHGPU_LEAF_TRIANGLE, out);
 }
 int bvhgpu_instances_create_f64(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_trees, const uint32_t* tree_of, const double* xforms, size_t n,
                                 int mem, bvhgpu_instances** out) {
-    return do_instances_create<double>(ctx, trees, n_trees, tree_of, xforms, n, mem, out);
+    return do_instances_create<double>(ctx, trees, n_trees, tree_of, xforms, n, mem, BVHGPU_LEAF_TRIANGLE, out);
+}
+int bvhgpu_instances_create_leaf_f32(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_trees, const uint32_t* tree_of, const float* xforms, size_t n,
+                                     int mem, int leaf, bvhgpu_instances** out) {
+    return do_instances_create<float>(ctx, trees, n_trees, tree_of, xforms, n, mem, leaf, out);
+}
+int bvhgpu_instances_create_leaf_f64(bvhgpu_ctx* ctx, bvhgpu_tree* const* trees, size_t n_trees, const uint32_t* tree_of, const double* xforms, size_t n,
+                                     int mem, int leaf, bvhgpu_instances** out) {
+    return do_instances_create<double>(ctx, trees, n_trees, tree_of, xforms, n, mem, leaf, out);
+}
+int bvhgpu_instances_leaf(const bvhgpu_instances* s, int* leaf) {
+    if (!s) return no_set();
+    if (leaf) *leaf = s->leaf;
+    return BVHGPU_OK;
 }
 int bvhgpu_instances_update_f32(bvhgpu_instances* s, const float* xforms, size_t n, int mem) { return do_instances_update<float>(s, xforms, n, mem); }
 int bvhgpu_instances_update_f64(bvhgpu_instances* s, const double* xforms, size_t n, int mem) { return do_instances_update<double>(s, xforms, n, mem); }

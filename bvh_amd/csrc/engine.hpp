@@ -340,10 +340,11 @@ struct bvhgpu_hits {
 struct bvhgpu_instances {
     bvhgpu_ctx* ctx = nullptr;
     int dtype = BVHGPU_F32;
+    int leaf = BVHGPU_LEAF_TRIANGLE;   // the leaf stage of every ray family of the set, fixed at creation (bvhgpu_instances_create_leaf_*)
     size_t n = 0;               // instances
     bool committed = false;     // a pose is committed (the last create / update succeeded): trace may run
     std::vector<bvhgpu_tree*> trees;   // the members: read by the commit and by trace's staleness check, NEVER by destroy
-    struct Seen { const void *trav, *aabbs, *tris; size_t n, n_trav; uint64_t gen; };
+    struct Seen { const void *trav, *aabbs, *prims; size_t n, n_trav; uint64_t gen; };   // prims: tris / spheres by the set's kind, NULL for BOX
     std::vector<Seen> seen;     // what the commit read of every member (trace refuses when a member no longer matches)
     std::vector<unsigned char> table_host;   // host image of `table` (alive while its upload is in flight)
     bvhgpu_tree* top = nullptr; // the top-level tree (built flat over `wboxes` by every commit)

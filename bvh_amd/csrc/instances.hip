@@ -8,6 +8,9 @@
 //                            §4r): an instance whose mask shares no bit with the ray's is passed over at its top-level leaf
 // Node fetch, slab test and triangle test are walk.hpp's and common.hpp's, unchanged: that is what makes the bits those of the
 // single-tree walks.  Nothing is pruned.
+//   k_instances_trace_leaf   the same text for a set of BOX or SPHERE leaves (bvhgpu_instances_create_leaf_*): the leaf
+//                            stage is walk.hpp's leaf_record on the object-space ray, the record 2 scalars wide
+#ifndef INSTANCES_TRACE_KERNEL_TEXT
 #include "instances.hpp"
 #include "walk.hpp"
 
@@ -114,82 +117,26 @@ __global__ __launch_bounds__(256) void k_instances_prep(const InstTree<T>* __res
 // invisible instance costs its mask's load: no record, no re-expressed ray, no member node — the lane goes on at i + 1 in the top level.
 // Without MASKED neither pointer is read and the test is not compiled.
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool FIRST, bool MASKED = false>
-__global__ __launch_bounds__(256) void k_instances_trace(const TravNode<T>* __restrict__ top, uint32_t n_top, const InstRec<T>* __restrict__ recs,
-                                                         const InstTree<T>* __restrict__ tbl, const typename Traits<T>::Ray* __restrict__ rays,
-                                                         const T* __restrict__ tmax, uint32_t n_rays, T* __restrict__ out_vals,
-                                                         uint32_t* __restrict__ out_instance, uint32_t* __restrict__ out_shape,
-                                                         const uint32_t* __restrict__ inst_mask, const uint32_t* __restrict__ ray_mask) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = r < n_rays;
-    uint32_t rmask = 0xFFFFFFFFu;
-    if constexpr (MASKED) { if (active && ray_mask) rmask = ray_mask[r]; }
-    T o[3] = {0, 0, 0}, d[3] = {0, 0, 0}, inv[3] = {0, 0, 0};
-    T best[3] = {Traits<T>::inf(), 0, 0};
-    uint32_t best_inst = NONE, best_shape = NONE;
-    T tm = Traits<T>::inf();
-    bool fin = true, wfin = true;   // the current ray / the world ray passes ray_is_finite (the NaN-free slab test is exact for it)
-    if (active) {
-        const typename Traits<T>::Ray* rp = rays + r;
-#pragma unroll
-        for (int k = 0; k < 3; k++) { o[k] = rp->o[k]; d[k] = rp->d[k]; inv[k] = rp->inv[k]; }
-        if (tmax) tm = tmax[r];
-        wfin = ray_is_finite<T>(o, inv);
-        fin = wfin;
-    }
-    const TravNode<T>* nodes = top;
-    const T* tris = nullptr;
-    uint32_t i = 0, end = active ? n_top : 0u, inst = NONE, top_next = 0;
-    while (true) {
-        const bool run = i < end;
-        if (!__any(run)) break;
-        const bool fast = !__any(run && !fin);   // wave-uniform
-        if (run) {
-            const NodeRegs<T> nd = load_node(nodes + i);
-            T t0, t1;
-            const bool hit = fast ? slab_hit_finite<T>(o, inv, nd.mn, nd.mx) : slab_hit<T>(o, inv, nd.mn, nd.mx, t0, t1);
-            const bool leaf = trav_is_leaf(nd.shape);
-            i = hit ? i + 1 : nd.exit;   // a leaf's exit IS i+1
-            if (hit && leaf) {
-                if (inst != NONE) {   // a triangle of the member: candidate (inst, shape)
-                    T v[3];
-                    ray_triangle<T>(o, d, tris + 9 * (size_t)nd.shape, v);
-                    if (v[0] < tm && (FIRST || v[0] < best[0])) {   // strict: the earlier candidate keeps a tie
-                        best[0] = v[0]; best[1] = v[1]; best[2] = v[2]; best_inst = inst; best_shape = nd.shape;
-                        if (FIRST) { i = 0; end = 0; inst = NONE; }   // the ray is done
-                    }
-                } else {              // an instance's world box: into its tree with the ray in the object's frame
-                    bool visible = true;
-                    if constexpr (MASKED) visible = (inst_mask[nd.shape] & rmask) != 0u;   // (hidden: the lane stays here and goes on at i + 1)
-                    if (visible) {
-                        top_next = i;
-                        inst = nd.shape;
-                        const InstRec<T> rec = load_rec<T>(recs + inst);
-                        const InstTree<T> t = tbl[rec.tree];
-                        T oo[3], dd[3];
-#pragma unroll
-                        for (int k = 0; k < 3; k++) { oo[k] = row4<T>(rec.y + 4 * k, o); dd[k] = row3<T>(rec.y + 4 * k, d); }
-#pragma unroll
-                        for (int k = 0; k < 3; k++) { o[k] = oo[k]; d[k] = dd[k]; inv[k] = (T)1 / dd[k]; }
-                        fin = ray_is_finite<T>(o, inv);
-                        nodes = t.trav; tris = t.tris; i = 0; end = t.n_trav;
-                    }
-                }
-            }
-            if (inst != NONE && i >= end) {   // the member's array has ended: back to the top level, behind the leaf that sent the lane here
-                const typename Traits<T>::Ray* rp = rays + r;
-#pragma unroll
-                for (int k = 0; k < 3; k++) { o[k] = rp->o[k]; d[k] = rp->d[k]; inv[k] = rp->inv[k]; }
-                fin = wfin;
-                nodes = top; i = top_next; end = n_top; inst = NONE;
-            }
-        }
-    }
-    if (active) {
-        out_vals[3 * (size_t)r] = best[0]; out_vals[3 * (size_t)r + 1] = best[1]; out_vals[3 * (size_t)r + 2] = best[2];
-        out_instance[r] = best_inst; out_shape[r] = best_shape;
-    }
-}
+// The kernel text stands at the end of this file, behind INSTANCES_TRACE_KERNEL_TEXT, and is compiled twice by the two includes of this file below:
+// once under the kernels' own names with the TRIANGLE leaf stage — the same text under the same names and template heads as before a set had
+// a leaf kind, hence the same instructions — and once as the *_leaf kernels with a LEAF template argument for BOX and SPHERE sets
+// (DESIGN.md §4t).  INST_K(name): the kernel's name; INST_LEAF_TPARAM: the end of its template head; INST_LEAF_VALUE: its leaf kind.
+#define INSTANCES_TRACE_KERNEL_TEXT
+#define INST_K(name) name
+#define INST_LEAF_TPARAM
+#define INST_LEAF_VALUE LEAF_TRIANGLE
+#include "instances.hip"
+#undef INST_K
+#undef INST_LEAF_TPARAM
+#undef INST_LEAF_VALUE
+#define INST_K(name) name##_leaf
+#define INST_LEAF_TPARAM , int LEAF_ARG
+#define INST_LEAF_VALUE LEAF_ARG
+#include "instances.hip"
+#undef INST_K
+#undef INST_LEAF_TPARAM
+#undef INST_LEAF_VALUE
+#undef INSTANCES_TRACE_KERNEL_TEXT
 
 // ------------------------------------------------------------------------------------------------
 template <typename T> void instances_commit(bvhgpu_instances* s) {
@@ -204,8 +151,10 @@ template <typename T> void instances_commit(bvhgpu_instances* s) {
         bvhgpu_tree* t = s->trees[k];
         ensure_flat_arrays(t);   // (a lazy flatten owes the binary array)
         join_flat(t);
-        s->seen[k] = bvhgpu_instances::Seen{t->trav.p, t->aabbs.p, t->tris.p, t->n, t->n_trav, t->gen};
-        host[k] = InstTree<T>{t->trav.as<TravNode<T>>(), t->tris.as<T>(), t->aabbs.as<T>(), (uint32_t)t->n_trav, (uint32_t)t->n};
+        // the array the set's leaf kind reads: the staleness check (capi.hip instances_current) watches this one; a BOX set reads aabbs alone
+        const DevBuf* prims = s->leaf == BVHGPU_LEAF_TRIANGLE ? &t->tris : (s->leaf == BVHGPU_LEAF_SPHERE ? &t->spheres : &t->aabbs);
+        s->seen[k] = bvhgpu_instances::Seen{t->trav.p, t->aabbs.p, s->leaf == BVHGPU_LEAF_BOX ? nullptr : prims->p, t->n, t->n_trav, t->gen};
+        host[k] = InstTree<T>{t->trav.as<TravNode<T>>(), prims->as<T>(), t->aabbs.as<T>(), (uint32_t)t->n_trav, (uint32_t)t->n};
     }
     if (n && nt) {
         s->table.reserve(nt * sizeof(InstTree<T>));
@@ -235,13 +184,20 @@ void instances_trace(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_de
     const bvhgpu_tree* top = s->top;
     const uint32_t n_top = s->n ? (uint32_t)top->n_trav : 0u;
     const dim3 grid((unsigned)((n_rays + 255) / 256)), block(256);
-#define INST_TRACE(F, M)                                                                                                                       \
-    hipLaunchKernelGGL((k_instances_trace<T, F, M>), grid, block, 0, st, top->trav.as<TravNode<T>>(), n_top, s->recs.as<InstRec<T>>(),     \
+#define INST_TRACE_K(K, M)                                                                                                                     \
+    hipLaunchKernelGGL(K, grid, block, 0, st, top->trav.as<TravNode<T>>(), n_top, s->recs.as<InstRec<T>>(),                                    \
                        s->table.as<InstTree<T>>(), rays_dev, tmax_dev, (uint32_t)n_rays, out_vals_dev, out_instance_dev, out_shape_dev,       \
                        M ? s->masks.as<uint32_t>() : nullptr, M ? ray_mask_dev : nullptr)
+#define INST_TRACE(F, M)                                                                                                                       \
+    do {                                                                                                                                       \
+        if (s->leaf == BVHGPU_LEAF_TRIANGLE) INST_TRACE_K((k_instances_trace<T, F, M>), M);                                                    \
+        else if (s->leaf == BVHGPU_LEAF_SPHERE) INST_TRACE_K((k_instances_trace_leaf<T, F, M, LEAF_SPHERE>), M);                               \
+        else INST_TRACE_K((k_instances_trace_leaf<T, F, M, LEAF_BOX>), M);                                                                     \
+    } while (0)
     if (masked) { if (first) INST_TRACE(true, true); else INST_TRACE(false, true); }
     else { if (first) INST_TRACE(true, false); else INST_TRACE(false, false); }
 #undef INST_TRACE
+#undef INST_TRACE_K
     BVH_HIP(hipGetLastError());
 }
 
@@ -253,3 +209,88 @@ template void instances_trace<double>(bvhgpu_instances*, const bvhgpu_ray_f64*, 
                                       const uint32_t*);
 
 }  // namespace bvhgpu
+
+#else   // INSTANCES_TRACE_KERNEL_TEXT: the kernel text, inside namespace bvhgpu (see the includes of this file above)
+
+template <typename T, bool FIRST, bool MASKED INST_LEAF_TPARAM>
+__global__ __launch_bounds__(256) void INST_K(k_instances_trace)(const TravNode<T>* __restrict__ top, uint32_t n_top, const InstRec<T>* __restrict__ recs,
+                                                                 const InstTree<T>* __restrict__ tbl, const typename Traits<T>::Ray* __restrict__ rays,
+                                                                 const T* __restrict__ tmax, uint32_t n_rays, T* __restrict__ out_vals,
+                                                                 uint32_t* __restrict__ out_instance, uint32_t* __restrict__ out_shape,
+                                                                 const uint32_t* __restrict__ inst_mask, const uint32_t* __restrict__ ray_mask) {
+    constexpr int LEAF = INST_LEAF_VALUE;
+    constexpr uint32_t W = LeafVals<LEAF>::W;
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = r < n_rays;
+    uint32_t rmask = 0xFFFFFFFFu;
+    if constexpr (MASKED) { if (active && ray_mask) rmask = ray_mask[r]; }
+    T o[3] = {0, 0, 0}, d[3] = {0, 0, 0}, inv[3] = {0, 0, 0};
+    T best[3] = {Traits<T>::inf(), 0, 0};
+    uint32_t best_inst = NONE, best_shape = NONE;
+    T tm = Traits<T>::inf();
+    bool fin = true, wfin = true;   // the current ray / the world ray passes ray_is_finite (the NaN-free slab test is exact for it)
+    if (active) {
+        const typename Traits<T>::Ray* rp = rays + r;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { o[k] = rp->o[k]; d[k] = rp->d[k]; inv[k] = rp->inv[k]; }
+        if (tmax) tm = tmax[r];
+        wfin = ray_is_finite<T>(o, inv);
+        fin = wfin;
+    }
+    const TravNode<T>* nodes = top;
+    const T* prims = nullptr;
+    uint32_t i = 0, end = active ? n_top : 0u, inst = NONE, top_next = 0;
+    while (true) {
+        const bool run = i < end;
+        if (!__any(run)) break;
+        const bool fast = !__any(run && !fin);   // wave-uniform
+        if (run) {
+            const NodeRegs<T> nd = load_node(nodes + i);
+            T t0, t1;
+            const bool hit = fast ? slab_hit_finite<T>(o, inv, nd.mn, nd.mx) : slab_hit<T>(o, inv, nd.mn, nd.mx, t0, t1);
+            const bool leaf = trav_is_leaf(nd.shape);
+            i = hit ? i + 1 : nd.exit;   // a leaf's exit IS i+1
+            if (hit && leaf) {
+                if (inst != NONE) {   // a shape of the member: candidate (inst, shape), its record by the set's leaf kind
+                    T v[3];
+                    if constexpr (LEAF == LEAF_TRIANGLE) ray_triangle<T>(o, d, prims + 9 * (size_t)nd.shape, v);   // (leaf_record's triangle stage, spelt out)
+                    else leaf_record<T, LEAF>(o, d, inv, prims, nd.shape, v);
+                    if (v[0] < tm && (FIRST || v[0] < best[0])) {   // strict: the earlier candidate keeps a tie
+                        best[0] = v[0]; best[1] = v[1]; best[2] = v[2]; best_inst = inst; best_shape = nd.shape;
+                        if (FIRST) { i = 0; end = 0; inst = NONE; }   // the ray is done
+                    }
+                } else {              // an instance's world box: into its tree with the ray in the object's frame
+                    bool visible = true;
+                    if constexpr (MASKED) visible = (inst_mask[nd.shape] & rmask) != 0u;   // (hidden: the lane stays here and goes on at i + 1)
+                    if (visible) {
+                        top_next = i;
+                        inst = nd.shape;
+                        const InstRec<T> rec = load_rec<T>(recs + inst);
+                        const InstTree<T> t = tbl[rec.tree];
+                        T oo[3], dd[3];
+#pragma unroll
+                        for (int k = 0; k < 3; k++) { oo[k] = row4<T>(rec.y + 4 * k, o); dd[k] = row3<T>(rec.y + 4 * k, d); }
+#pragma unroll
+                        for (int k = 0; k < 3; k++) { o[k] = oo[k]; d[k] = dd[k]; inv[k] = (T)1 / dd[k]; }
+                        fin = ray_is_finite<T>(o, inv);
+                        nodes = t.trav; prims = t.prims; i = 0; end = t.n_trav;
+                    }
+                }
+            }
+            if (inst != NONE && i >= end) {   // the member's array has ended: back to the top level, behind the leaf that sent the lane here
+                const typename Traits<T>::Ray* rp = rays + r;
+#pragma unroll
+                for (int k = 0; k < 3; k++) { o[k] = rp->o[k]; d[k] = rp->d[k]; inv[k] = rp->inv[k]; }
+                fin = wfin;
+                nodes = top; i = top_next; end = n_top; inst = NONE;
+            }
+        }
+    }
+    if (active) {
+        if constexpr (W == 3) { out_vals[3 * (size_t)r] = best[0]; out_vals[3 * (size_t)r + 1] = best[1]; out_vals[3 * (size_t)r + 2] = best[2]; }
+        else { out_vals[2 * (size_t)r] = best[0]; out_vals[2 * (size_t)r + 1] = best[1]; }
+        out_instance[r] = best_inst; out_shape[r] = best_shape;
+    }
+}
+
+#endif   // INSTANCES_TRACE_KERNEL_TEXT

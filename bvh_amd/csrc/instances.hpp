@@ -9,7 +9,7 @@ namespace bvhgpu {
 // what the walk needs of a member tree, read once on entry to an instance
 template <typename T> struct InstTree {
     const TravNode<T>* trav;
-    const T* tris;     // n x 9
+    const T* prims;    // the array the set's leaf kind reads: aabbs (n x 6), tris (n x 9) or spheres (n x 4) — instances_commit
     const T* aabbs;    // n x 6 (k_instances_prep only)
     uint32_t n_trav, n;
 };

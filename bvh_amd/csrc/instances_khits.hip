@@ -20,6 +20,7 @@
 // MASKED (bvhgpu_instances_khits_masked_*): inst_mask is the set's n u32, ray_mask NULL (all ones) or one u32 per ray; an
 // instance whose mask shares no bit with the ray's is passed over at its top-level leaf — no record, no re-expressed ray, no member node —
 // and the lane goes on at i + 1.  The write-out sees only pairs that are in the list: no mask.  Without MASKED neither pointer is read.
+#ifndef INSTANCES_KHITS_KERNEL_TEXT
 #include "instances.hpp"
 #include "walk.hpp"
 
@@ -43,11 +44,102 @@ template <typename T> struct InstKhitsScene {
     const InstTree<T>* tbl;
 };
 
-template <typename T, bool MASKED = false>
-__global__ __launch_bounds__(256) void k_instances_khits(InstKhitsScene<T> sc, const typename Traits<T>::Ray* __restrict__ rays, const T* __restrict__ tmaxs,
-                                                         uint32_t n, uint32_t k, uint32_t* __restrict__ out_instance, uint32_t* __restrict__ out_shape,
-                                                         T* __restrict__ out_vals, const uint32_t* __restrict__ inst_mask,
-                                                         const uint32_t* __restrict__ ray_mask) {
+// The kernel text stands at the end of this file, behind INSTANCES_KHITS_KERNEL_TEXT, and is compiled twice by the two includes of this file below:
+// once under the kernels' own names with the TRIANGLE leaf stage — the same text under the same names and template heads as before a set had
+// a leaf kind, hence the same instructions — and once as the *_leaf kernels with a LEAF template argument for BOX and SPHERE sets
+// (DESIGN.md §4t).  INST_K(name): the kernel's name; INST_LEAF_TPARAM: the end of its template head; INST_LEAF_VALUE: its leaf kind.
+#define INSTANCES_KHITS_KERNEL_TEXT
+#define INST_K(name) name
+#define INST_LEAF_TPARAM
+#define INST_LEAF_VALUE LEAF_TRIANGLE
+#include "instances_khits.hip"
+#undef INST_K
+#undef INST_LEAF_TPARAM
+#undef INST_LEAF_VALUE
+#define INST_K(name) name##_leaf
+#define INST_LEAF_TPARAM , int LEAF_ARG
+#define INST_LEAF_VALUE LEAF_ARG
+#include "instances_khits.hip"
+#undef INST_K
+#undef INST_LEAF_TPARAM
+#undef INST_LEAF_VALUE
+#undef INSTANCES_KHITS_KERNEL_TEXT
+
+// a set without instances: every slot is padding (+inf is no byte pattern, so no memset)
+template <typename T>
+__global__ __launch_bounds__(256) void k_instances_khits_fill(uint32_t* __restrict__ out_instance, uint32_t* __restrict__ out_shape, T* __restrict__ out_vals,
+                                                              uint32_t total) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    out_instance[e] = NONE;
+    out_shape[e] = NONE;
+    T* v = out_vals + (size_t)e * 3;
+    v[0] = Traits<T>::inf(); v[1] = 0; v[2] = 0;
+}
+// ... of a BOX or SPHERE set: records 2 scalars wide
+template <typename T>
+__global__ __launch_bounds__(256) void k_instances_khits_fill2(uint32_t* __restrict__ out_instance, uint32_t* __restrict__ out_shape, T* __restrict__ out_vals,
+                                                               uint32_t total) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    out_instance[e] = NONE;
+    out_shape[e] = NONE;
+    T* v = out_vals + (size_t)e * 2;
+    v[0] = Traits<T>::inf(); v[1] = 0;
+}
+
+// the rays of a batch over a committed instance set (the caller has checked commit, staleness and n x k < 2^32)
+// masked: bvhgpu_instances_khits_masked_* — the set's masks against ray_mask_dev (NULL: all ones); otherwise ray_mask_dev is not looked at
+template <typename T>
+void instances_khits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, uint32_t k,
+                           uint32_t* out_instance_dev, uint32_t* out_shape_dev, T* out_vals_dev, bool masked, const uint32_t* ray_mask_dev) {
+    if (!n) return;
+    hipStream_t st = s->ctx->stream;
+    if (s->n == 0 || s->top == nullptr || s->top->n_trav == 0) {   // no instance, or an empty top level: every row is padding
+        const size_t total = n * k;
+        if (s->leaf == BVHGPU_LEAF_TRIANGLE)
+            hipLaunchKernelGGL((k_instances_khits_fill<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out_instance_dev, out_shape_dev,
+                               out_vals_dev, (uint32_t)total);
+        else
+            hipLaunchKernelGGL((k_instances_khits_fill2<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out_instance_dev, out_shape_dev,
+                               out_vals_dev, (uint32_t)total);
+        BVH_HIP(hipGetLastError());
+        return;
+    }
+    const InstKhitsScene<T> sc = {s->top->trav.as<TravNode<T>>(), (uint32_t)s->top->n_trav, s->recs.as<InstRec<T>>(), s->table.as<InstTree<T>>()};
+    const unsigned bs = instances_khits_block<T>(k);
+    const size_t lds = (size_t)bs * k * (sizeof(T) + 8);
+    const dim3 grid((unsigned)((n + bs - 1) / bs)), block(bs);
+#define INST_KHITS_K(K, M)                                                                                                             \
+    hipLaunchKernelGGL(K, grid, block, lds, st, sc, rays_dev, tmax_dev, (uint32_t)n, k, out_instance_dev, out_shape_dev, out_vals_dev, \
+                       M ? s->masks.as<uint32_t>() : nullptr, M ? ray_mask_dev : nullptr)
+#define INST_KHITS(M)                                                                                              \
+    do {                                                                                                           \
+        if (s->leaf == BVHGPU_LEAF_TRIANGLE) INST_KHITS_K((k_instances_khits<T, M>), M);                           \
+        else if (s->leaf == BVHGPU_LEAF_SPHERE) INST_KHITS_K((k_instances_khits_leaf<T, M, LEAF_SPHERE>), M);      \
+        else INST_KHITS_K((k_instances_khits_leaf<T, M, LEAF_BOX>), M);                                            \
+    } while (0)
+    if (masked) INST_KHITS(true); else INST_KHITS(false);
+#undef INST_KHITS
+#undef INST_KHITS_K
+    BVH_HIP(hipGetLastError());
+}
+template void instances_khits_batch<float>(bvhgpu_instances*, const bvhgpu_ray_f32*, const float*, size_t, uint32_t, uint32_t*, uint32_t*, float*, bool,
+                                           const uint32_t*);
+template void instances_khits_batch<double>(bvhgpu_instances*, const bvhgpu_ray_f64*, const double*, size_t, uint32_t, uint32_t*, uint32_t*, double*, bool,
+                                            const uint32_t*);
+
+}  // namespace bvhgpu
+
+#else   // INSTANCES_KHITS_KERNEL_TEXT: the kernel text, inside namespace bvhgpu (see the includes of this file above)
+
+template <typename T, bool MASKED INST_LEAF_TPARAM>
+__global__ __launch_bounds__(256) void INST_K(k_instances_khits)(InstKhitsScene<T> sc, const typename Traits<T>::Ray* __restrict__ rays,
+                                                                 const T* __restrict__ tmaxs, uint32_t n, uint32_t k, uint32_t* __restrict__ out_instance,
+                                                                 uint32_t* __restrict__ out_shape, T* __restrict__ out_vals,
+                                                                 const uint32_t* __restrict__ inst_mask, const uint32_t* __restrict__ ray_mask) {
+    constexpr int LEAF = INST_LEAF_VALUE;
+    constexpr uint32_t W = LeafVals<LEAF>::W;
     extern __shared__ __align__(16) unsigned char ikh_lds[];
     const uint32_t block = blockDim.x;
     T* __restrict__ ld = reinterpret_cast<T*>(ikh_lds) + threadIdx.x;                                        // slot m: ld[m * block]
@@ -71,7 +163,7 @@ __global__ __launch_bounds__(256) void k_instances_khits(InstKhitsScene<T> sc, c
     bool full = false;   // len == k
     T bound = 0;         // L[k - 1].distance of a full list
     const TravNode<T>* nodes = sc.top;
-    const T* tris = nullptr;
+    const T* prims = nullptr;
     uint32_t i = 0, end = active ? sc.n_top : 0u, inst = NONE, top_next = 0;
     while (true) {
         const bool run = i < end;
@@ -84,9 +176,10 @@ __global__ __launch_bounds__(256) void k_instances_khits(InstKhitsScene<T> sc, c
             const bool leaf = trav_is_leaf(nd.shape);
             i = hit ? i + 1 : nd.exit;   // a leaf's exit IS i+1
             if (hit && leaf) {
-                if (inst != NONE) {   // a triangle of the member: the pair (inst, shape)
+                if (inst != NONE) {   // a shape of the member: the pair (inst, shape), its record by the set's leaf kind
                     T v[3];
-                    ray_triangle<T>(o, d, tris + 9 * (size_t)nd.shape, v);
+                    if constexpr (LEAF == LEAF_TRIANGLE) ray_triangle<T>(o, d, prims + 9 * (size_t)nd.shape, v);   // (leaf_record's triangle stage, spelt out)
+                    else leaf_record<T, LEAF>(o, d, inv, prims, nd.shape, v);
                     const T dist = v[0];
                     if (dist < tm && (!full || dist < bound)) {
                         uint32_t hole = full ? k - 1 : len;   // a full list drops its last element
@@ -120,7 +213,7 @@ __global__ __launch_bounds__(256) void k_instances_khits(InstKhitsScene<T> sc, c
 #pragma unroll
                         for (int c = 0; c < 3; c++) { o[c] = oo[c]; d[c] = dd[c]; inv[c] = (T)1 / dd[c]; }
                         fin = ray_is_finite<T>(o, inv);
-                        nodes = t.trav; tris = t.tris; i = 0; end = t.n_trav;
+                        nodes = t.trav; prims = t.prims; i = 0; end = t.n_trav;
                     }
                 }
             }
@@ -139,7 +232,7 @@ __global__ __launch_bounds__(256) void k_instances_khits(InstKhitsScene<T> sc, c
     for (int c = 0; c < 3; c++) { o[c] = rp->o[c]; d[c] = rp->d[c]; }
     uint32_t* oi = out_instance + (size_t)q * k;
     uint32_t* os = out_shape + (size_t)q * k;
-    T* ov = out_vals + (size_t)q * k * 3;
+    T* ov = out_vals + (size_t)q * k * (W == 3 ? 3 : 2);
 #pragma unroll 1
     for (uint32_t m = 0; m < len; m++) {
         const uint32_t in = li[m * block], s = ls[m * block];
@@ -148,60 +241,27 @@ __global__ __launch_bounds__(256) void k_instances_khits(InstKhitsScene<T> sc, c
         T oo[3], dd[3], v[3];
 #pragma unroll
         for (int c = 0; c < 3; c++) { oo[c] = row4<T>(rec.y + 4 * c, o); dd[c] = row3<T>(rec.y + 4 * c, d); }
-        ray_triangle<T>(oo, dd, t.tris + 9 * (size_t)s, v);
+        if constexpr (LEAF == LEAF_TRIANGLE) {
+            ray_triangle<T>(oo, dd, t.prims + 9 * (size_t)s, v);
+        } else {
+            if (LEAF == LEAF_BOX) {   // (only the box stage reads the inverse: the walk's, from the object-space direction)
+#pragma unroll
+                for (int c = 0; c < 3; c++) inv[c] = (T)1 / dd[c];
+            }
+            leaf_record<T, LEAF>(oo, dd, inv, t.prims, s, v);
+        }
         oi[m] = in;
         os[m] = s;
-        ov[3 * m] = v[0]; ov[3 * m + 1] = v[1]; ov[3 * m + 2] = v[2];
+        if constexpr (W == 3) { ov[3 * m] = v[0]; ov[3 * m + 1] = v[1]; ov[3 * m + 2] = v[2]; }
+        else { ov[2 * m] = v[0]; ov[2 * m + 1] = v[1]; }
     }
 #pragma unroll 1
     for (uint32_t m = len; m < k; m++) {
         oi[m] = NONE;
         os[m] = NONE;
-        ov[3 * m] = Traits<T>::inf(); ov[3 * m + 1] = 0; ov[3 * m + 2] = 0;
+        if constexpr (W == 3) { ov[3 * m] = Traits<T>::inf(); ov[3 * m + 1] = 0; ov[3 * m + 2] = 0; }
+        else { ov[2 * m] = Traits<T>::inf(); ov[2 * m + 1] = 0; }
     }
 }
 
-// a set without instances: every slot is padding (+inf is no byte pattern, so no memset)
-template <typename T>
-__global__ __launch_bounds__(256) void k_instances_khits_fill(uint32_t* __restrict__ out_instance, uint32_t* __restrict__ out_shape, T* __restrict__ out_vals,
-                                                              uint32_t total) {
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= total) return;
-    out_instance[e] = NONE;
-    out_shape[e] = NONE;
-    T* v = out_vals + (size_t)e * 3;
-    v[0] = Traits<T>::inf(); v[1] = 0; v[2] = 0;
-}
-
-// the rays of a batch over a committed instance set (the caller has checked commit, staleness and n x k < 2^32)
-// masked: bvhgpu_instances_khits_masked_* — the set's masks against ray_mask_dev (NULL: all ones); otherwise ray_mask_dev is not looked at
-template <typename T>
-void instances_khits_batch(bvhgpu_instances* s, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, uint32_t k,
-                           uint32_t* out_instance_dev, uint32_t* out_shape_dev, T* out_vals_dev, bool masked, const uint32_t* ray_mask_dev) {
-    if (!n) return;
-    hipStream_t st = s->ctx->stream;
-    if (s->n == 0 || s->top == nullptr || s->top->n_trav == 0) {   // no instance, or an empty top level: every row is padding
-        const size_t total = n * k;
-        hipLaunchKernelGGL((k_instances_khits_fill<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out_instance_dev, out_shape_dev,
-                           out_vals_dev, (uint32_t)total);
-        BVH_HIP(hipGetLastError());
-        return;
-    }
-    const InstKhitsScene<T> sc = {s->top->trav.as<TravNode<T>>(), (uint32_t)s->top->n_trav, s->recs.as<InstRec<T>>(), s->table.as<InstTree<T>>()};
-    const unsigned bs = instances_khits_block<T>(k);
-    const size_t lds = (size_t)bs * k * (sizeof(T) + 8);
-    const dim3 grid((unsigned)((n + bs - 1) / bs)), block(bs);
-    if (masked)
-        hipLaunchKernelGGL((k_instances_khits<T, true>), grid, block, lds, st, sc, rays_dev, tmax_dev, (uint32_t)n, k, out_instance_dev, out_shape_dev,
-                           out_vals_dev, s->masks.as<uint32_t>(), ray_mask_dev);
-    else
-        hipLaunchKernelGGL((k_instances_khits<T, false>), grid, block, lds, st, sc, rays_dev, tmax_dev, (uint32_t)n, k, out_instance_dev, out_shape_dev,
-                           out_vals_dev, nullptr, nullptr);
-    BVH_HIP(hipGetLastError());
-}
-template void instances_khits_batch<float>(bvhgpu_instances*, const bvhgpu_ray_f32*, const float*, size_t, uint32_t, uint32_t*, uint32_t*, float*, bool,
-                                           const uint32_t*);
-template void instances_khits_batch<double>(bvhgpu_instances*, const bvhgpu_ray_f64*, const double*, size_t, uint32_t, uint32_t*, uint32_t*, double*, bool,
-                                            const uint32_t*);
-
-}  // namespace bvhgpu
+#endif   // INSTANCES_KHITS_KERNEL_TEXT

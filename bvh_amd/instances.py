@@ -89,7 +89,7 @@ class InstancesMasks:
         _keep, tp = api._side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
         _mk, mp = api._mask_in(ray_mask, rays.device, rays.n, rays.mem, "ray_mask", "rays")
         n = rays.n
-        out, (vp, ip, sp) = api._out_cols(rays.device.device if rays.mem == DEVICE else None, self.ft, ((n, 3), "float"), (n, "index"), (n, "index"))
+        out, (vp, ip, sp) = api._out_cols(rays.device.device if rays.mem == DEVICE else None, self.ft, ((n, _lib.LEAF_WIDTH[_lib.LEAF_KINDS[self.leaf]]), "float"), (n, "index"), (n, "index"))
         fn = getattr(_lib.load(), f"bvhgpu_instances_trace_masked_{self.sfx}")
         check(fn(self._s, rays._ptr(), tp, mp, n, rays.mem, flags, vp, ip, sp), self.ctx._h)
         return tuple(out)
@@ -116,7 +116,7 @@ class InstancesMasks:
         _mk, mp = api._mask_in(ray_mask, rays.device, rays.n, rays.mem, "ray_mask", "rays")
         n = rays.n
         out, (ip, sp, vp) = api._out_cols(rays.device.device if rays.mem == DEVICE else None, self.ft,
-                                          ((n, rows), "index"), ((n, rows), "index"), ((n, rows, 3), "float"))
+                                          ((n, rows), "index"), ((n, rows), "index"), ((n, rows, _lib.LEAF_WIDTH[_lib.LEAF_KINDS[self.leaf]]), "float"))
         fn = getattr(_lib.load(), f"bvhgpu_instances_khits_masked_{self.sfx}")
         check(fn(self._s, rays._ptr(), tp, mp, n, rays.mem, k & 0xFFFFFFFF, ip, sp, vp), self.ctx._h)
         return tuple(out)
@@ -130,7 +130,7 @@ class InstancesMasks:
         flags = (0 if sort else _lib.INSTANCES_ALLHITS_LIST_ORDER) | (_lib.INSTANCES_ALLHITS_COUNT_ONLY if count_only else 0)
         offsets, instance, shape, vals = self._csr("allhits_masked", (rays._ptr(), tp, mp, rays.n, rays.mem, flags), rays.n,
                                                    rays.device.device if rays.mem == DEVICE else None, count_only,
-                                                   ((), "index"), ((), "index"), ((3,), "float"), fetch="instances_allhits")
+                                                   ((), "index"), ((), "index"), ((_lib.LEAF_WIDTH[_lib.LEAF_KINDS[self.leaf]],), "float"), fetch="instances_allhits")
         if count_only:
             return dict(offsets=offsets)
         return dict(offsets=offsets, instance=instance, shape=shape, vals=vals)
@@ -222,13 +222,22 @@ class InstancesMaskedQueries:
 
 class Instances(InstancesTreeForm, InstancesMasks, InstancesMaskedQueries, _Typed):
     """bvhgpu_instances: `trees` (Bvh / FlatBvh objects of one context and dtype, with set_triangles done; kept referenced), `tree_of[i]`
-    the member of instance i, `transforms` n x 12 or n x 3 x 4 (row-major 3x4, object -> world) in the trees' dtype.  update() is the
+    the member of instance i, `transforms` n x 12 or n x 3 x 4 (row-major 3x4, object -> world) in the trees' dtype.
+    leaf: "triangle" (the default), "sphere" (the members need set_spheres instead: an instance's sphere is the ellipsoid its transform maps
+    it to) or "box" (the shapes' own boxes, as parallelepipeds; the members need neither).  Every ray query of the set — closest_hits,
+    any_hits, occluded, khits_batch, allhits_batch and their masked forms — answers with that kind's record: {distance, u, v} for triangles,
+    {enter, exit} for boxes and {distance, exit} for spheres, in the world ray's parameter, so `vals` is 3 or 2 wide
+    (_lib.LEAF_WIDTH).  region_batch serves every kind; the point queries measure triangle distance and raise INVALID_ARG on a box or sphere
+    set.  update() is the
     re-pose and the re-sync: call it after moving instances and after any rebuild, refit or set_triangles of a member tree; a trace on a
     set whose member was rebuilt since raises INVALID_ARG ("instances are stale").  The *_masked methods (InstancesMasks for rays,
     InstancesMaskedQueries for points and regions) see only the instances whose mask shares a bit with the row's; every other method
     ignores the masks."""
 
-    def __init__(self, trees: Sequence, tree_of, transforms, ctx: Optional[Context] = None):
+    def __init__(self, trees: Sequence, tree_of, transforms, ctx: Optional[Context] = None, leaf: str = "triangle"):
+        if leaf not in _lib.LEAF_KINDS:
+            raise ValueError(f"leaf must be one of {sorted(_lib.LEAF_KINDS)}, not {leaf!r}")
+        self.leaf = leaf                 # the leaf stage of every ray query of the set, fixed here
         trees = list(trees)
         self.trees = trees               # (the set borrows their device arrays)
         self.ctx = ctx or (trees[0].ctx if trees else api.default_context())
@@ -241,8 +250,12 @@ class Instances(InstancesTreeForm, InstancesMasks, InstancesMaskedQueries, _Type
         _keep, xp, n, mem = api._rows_in(transforms, 12, self.ft, "transform")
         of = self._tree_of_in(tree_of, n, mem, _keep)
         h = C.c_void_p()
-        fn = getattr(_lib.load(), f"bvhgpu_instances_create_{self.sfx}")
-        check(fn(self.ctx._h, handles, len(trees), of[1], xp, n, mem, C.byref(h)), self.ctx._h)
+        if leaf == "triangle":
+            fn = getattr(_lib.load(), f"bvhgpu_instances_create_{self.sfx}")
+            check(fn(self.ctx._h, handles, len(trees), of[1], xp, n, mem, C.byref(h)), self.ctx._h)
+        else:
+            fn = getattr(_lib.load(), f"bvhgpu_instances_create_leaf_{self.sfx}")
+            check(fn(self.ctx._h, handles, len(trees), of[1], xp, n, mem, _lib.LEAF_KINDS[leaf], C.byref(h)), self.ctx._h)
         self._s = h
         self.n = n
         self._counted = True
@@ -295,7 +308,7 @@ class Instances(InstancesTreeForm, InstancesMasks, InstancesMaskedQueries, _Type
         self._check_rays(rays)
         _keep, tp = api._side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
         n = rays.n
-        out, (vp, ip, sp) = api._out_cols(rays.device.device if rays.mem == DEVICE else None, self.ft, ((n, 3), "float"), (n, "index"), (n, "index"))
+        out, (vp, ip, sp) = api._out_cols(rays.device.device if rays.mem == DEVICE else None, self.ft, ((n, _lib.LEAF_WIDTH[_lib.LEAF_KINDS[self.leaf]]), "float"), (n, "index"), (n, "index"))
         fn = getattr(_lib.load(), f"bvhgpu_instances_trace_{self.sfx}")
         check(fn(self._s, rays._ptr(), tp, n, rays.mem, flags, vp, ip, sp), self.ctx._h)
         return tuple(out)
@@ -354,7 +367,7 @@ class Instances(InstancesTreeForm, InstancesMasks, InstancesMaskedQueries, _Type
         flags = (0 if sort else _lib.INSTANCES_ALLHITS_LIST_ORDER) | (_lib.INSTANCES_ALLHITS_COUNT_ONLY if count_only else 0)
         offsets, instance, shape, vals = self._csr("allhits", (rays._ptr(), tp, rays.n, rays.mem, flags), rays.n,
                                                    rays.device.device if rays.mem == DEVICE else None, count_only,
-                                                   ((), "index"), ((), "index"), ((3,), "float"))
+                                                   ((), "index"), ((), "index"), ((_lib.LEAF_WIDTH[_lib.LEAF_KINDS[self.leaf]],), "float"))
         if count_only:
             return dict(offsets=offsets)
         return dict(offsets=offsets, instance=instance, shape=shape, vals=vals)
@@ -373,7 +386,7 @@ class Instances(InstancesTreeForm, InstancesMasks, InstancesMaskedQueries, _Type
         _keep, tp = api._side_in(tmax, rays.device, rays.n, rays.mem, self.ft, "tmax", "rays")
         n = rays.n
         out, (ip, sp, vp) = api._out_cols(rays.device.device if rays.mem == DEVICE else None, self.ft,
-                                          ((n, rows), "index"), ((n, rows), "index"), ((n, rows, 3), "float"))
+                                          ((n, rows), "index"), ((n, rows), "index"), ((n, rows, _lib.LEAF_WIDTH[_lib.LEAF_KINDS[self.leaf]]), "float"))
         fn = getattr(_lib.load(), f"bvhgpu_instances_khits_{self.sfx}")
         check(fn(self._s, rays._ptr(), tp, n, rays.mem, k & 0xFFFFFFFF, ip, sp, vp), self.ctx._h)
         return tuple(out)

@@ -814,6 +814,41 @@ int bvhgpu_instances_boxes(bvhgpu_instances *s, void *out, int mem);
 int bvhgpu_instances_info(const bvhgpu_instances *s, int *dtype, size_t *n_trees, size_t *n_instances);
 void bvhgpu_instances_destroy(bvhgpu_instances *s);
 
+/* ---- instanced scenes of box and sphere shapes: a set has a LEAF KIND, fixed at creation, one of BVHGPU_LEAF_BOX, BVHGPU_LEAF_TRIANGLE
+ * and BVHGPU_LEAF_SPHERE.  Every ray family of the set — bvhgpu_instances_trace_*, _khits_*, _allhits_* and their _masked_* forms — answers
+ * with that kind's leaf stage.  bvhgpu_instances_create_* is bvhgpu_instances_create_leaf_* with BVHGPU_LEAF_TRIANGLE: for such a set every
+ * byte is what it was.  Every operation below is rounded once in the set's dtype T, in the order written, with no contraction.
+ *  - Everything up to and including the object-space ray r' = {Y o + y3, Y d, 1/(Y d)} is the block above, unchanged; so are the list
+ *    L' = FlatBvh::traverse(r', shapes of the member) and the double order of the candidates (i, s).
+ *  - The record of candidate (i, s), W scalars (3 for TRIANGLE, 2 otherwise), its first scalar the DISTANCE:
+ *      BVHGPU_LEAF_BOX       {enter, exit} of Ray::intersection_slice_for_aabb for r' on shape s's own AABB as the member holds it (its shape
+ *                            array — not the node box of the walked array, which a folded array or a tree with empty child bounds does not
+ *                            keep at the leaf); {+inf, 0} on a miss.
+ *      BVHGPU_LEAF_SPHERE    the sphere stage of bvhgpu_traverse_sphere_* on r' and the member's sphere s: {distance, exit}.  It divides by
+ *                            dot(d', d'), so it is exact for the direction that is not renormalised.
+ *      BVHGPU_LEAF_TRIANGLE  {distance, u, v} of Ray::intersects_triangle(r', triangle s), as above.
+ *    Because d' is not renormalised the two scalars of a BOX or SPHERE record are parameters of the WORLD ray.
+ *  - Closest / first / tmax, the k nearest hits and all hits apply to the distance by the rules of the blocks that define them for
+ *    triangles, word for word: strict <, the earlier candidate keeps a tie, tmax strict and in T.  A miss or a padding slot is
+ *    {+inf, 0[, 0]}, BVHGPU_NONE, BVHGPU_NONE.  No pruning.
+ *  - What is hit.  A sphere under an affine X_i is the ELLIPSOID X_i maps it to; a box is the PARALLELEPIPED X_i maps it to.  W_i stays the
+ *    image of the join of the member's shape AABBs: a sphere that reaches outside its shape's box is not covered there, exactly as
+ *    bvhgpu_traverse_sphere_* does not cover it on one tree.
+ *  - Output widths.  out_vals of trace is n x W, of khits n x k x W; bvhgpu_hits_fetch_instances_allhits copies total x W.
+ *  - Members.  TRIANGLE needs bvhgpu_tree_set_triangles_* on every member, SPHERE bvhgpu_tree_set_spheres_*, BOX neither.  An unknown `leaf`
+ *    is BVHGPU_INVALID_ARG, tested before the member rules.  update applies the set's own kind's rule.
+ *  - Stale sets.  The check watches the array the set's kind reads: a bvhgpu_tree_set_spheres_* that moves the buffer of a SPHERE set's
+ *    member makes the set stale until an update, and so does a rebuild to another shape count (which drops the spheres: update is refused
+ *    until they are set again).  A BOX set watches the boxes alone.
+ *  - bvhgpu_instances_region_* reads boxes only and serves every set.  The point families (within, knearest, knearest_tree and their masked
+ *    forms) measure triangle distance and refuse a BOX or SPHERE set with BVHGPU_INVALID_ARG, directly after the dtype rule.
+ * bvhgpu_instances_leaf: the set's kind. */
+int bvhgpu_instances_create_leaf_f32(bvhgpu_ctx *ctx, bvhgpu_tree *const *trees, size_t n_trees, const uint32_t *tree_of, const float *xforms,
+                                     size_t n, int mem, int leaf, bvhgpu_instances **out);
+int bvhgpu_instances_create_leaf_f64(bvhgpu_ctx *ctx, bvhgpu_tree *const *trees, size_t n_trees, const uint32_t *tree_of, const double *xforms,
+                                     size_t n, int mem, int leaf, bvhgpu_instances **out);
+int bvhgpu_instances_leaf(const bvhgpu_instances *s, int *leaf);
+
 /* ---- convex regions over an instanced scene: per region every (instance, shape) whose box passes, as a CSR — "which instances, and which
  * shapes inside them, can this camera see", without flattening the scene.  Every operation below is rounded once in the set's dtype T, in
  * the order written, with no contraction.
@@ -928,7 +963,8 @@ int bvhgpu_hits_fetch_instances_allhits(bvhgpu_hits *hits, uint32_t *offsets, ui
  *                             (i, s) is a candidate with key d iff d <= r2;  then exit_index
  *  - The distance is the true world-space distance to the transformed triangle, meaningful under any affine X_i (distances do not
  *    survive a non-uniform scale, so nothing is measured in the object's frame).  There is no box kind: a box under an affine map is not
- *    a box, and a set needs bvhgpu_tree_set_triangles on every member anyway.
+ *    a box, and the distance is a triangle's: a set created with BVHGPU_LEAF_BOX or BVHGPU_LEAF_SPHERE (bvhgpu_instances_create_leaf_*)
+ *    is refused with BVHGPU_INVALID_ARG, directly after the dtype rule.
  *  - The prune is conservative.  |p - (X v + x3)| = |X (q - v)| >= |q - v| / ||Y||_F, so every point of a world triangle within m of p
  *    lies within m * ||Y||_F of q in the object's frame, and so does every box that contains it; W_i contains the world triangles.  In
  *    exact arithmetic row j is therefore exactly {(i, s) : d(i, s) <= r2}.  In floating point the row is what the loop above yields: a

@@ -227,6 +227,9 @@ extern "C" {
     // instanced scenes: a top-level tree over the world boxes of (member tree, 3x4 transform) pairs; closest / first hit per ray as {distance, u, v}, instance, shape
     pub fn bvhgpu_instances_create_f32(ctx: *mut bvhgpu_ctx, trees: *const *mut bvhgpu_tree, n_trees: usize, tree_of: *const u32, xforms: *const f32, n: usize, mem: c_int, out: *mut *mut bvhgpu_instances) -> c_int;
     pub fn bvhgpu_instances_create_f64(ctx: *mut bvhgpu_ctx, trees: *const *mut bvhgpu_tree, n_trees: usize, tree_of: *const u32, xforms: *const f64, n: usize, mem: c_int, out: *mut *mut bvhgpu_instances) -> c_int;
+    pub fn bvhgpu_instances_create_leaf_f32(ctx: *mut bvhgpu_ctx, trees: *const *mut bvhgpu_tree, n_trees: usize, tree_of: *const u32, xforms: *const f32, n: usize, mem: c_int, leaf: c_int, out: *mut *mut bvhgpu_instances) -> c_int;
+    pub fn bvhgpu_instances_create_leaf_f64(ctx: *mut bvhgpu_ctx, trees: *const *mut bvhgpu_tree, n_trees: usize, tree_of: *const u32, xforms: *const f64, n: usize, mem: c_int, leaf: c_int, out: *mut *mut bvhgpu_instances) -> c_int;
+    pub fn bvhgpu_instances_leaf(s: *const bvhgpu_instances, leaf: *mut c_int) -> c_int;
     pub fn bvhgpu_instances_update_f32(s: *mut bvhgpu_instances, xforms: *const f32, n: usize, mem: c_int) -> c_int;
     pub fn bvhgpu_instances_update_f64(s: *mut bvhgpu_instances, xforms: *const f64, n: usize, mem: c_int) -> c_int;
     pub fn bvhgpu_instances_trace_f32(s: *mut bvhgpu_instances, rays: *const bvhgpu_ray_f32, tmax: *const f32, n_rays: usize, mem: c_int, flags: c_uint, out_vals: *mut f32, out_instance: *mut u32, out_shape: *mut u32) -> c_int;

@@ -850,6 +850,37 @@ impl<T: GpuScalar> GpuInstances<T> {
         GpuInstances { ctx, set, n: xforms.len(), _t: core::marker::PhantomData }
     }
 
+    /// `new` with a leaf kind, fixed for the set's life: `ffi::BVHGPU_LEAF_BOX` (the shapes' own boxes; the members need neither triangles
+    /// nor spheres), `ffi::BVHGPU_LEAF_TRIANGLE` (what `new` makes) or `ffi::BVHGPU_LEAF_SPHERE` (the members need `set_spheres`; an
+    /// instance's sphere is the ellipsoid its transform maps it to).  Every ray query of the set answers with that kind's record: two
+    /// scalars, `{enter, exit}` / `{distance, exit}`, for BOX and SPHERE.  `trace` and `trace_masked` return them as
+    /// `Intersection { distance, u: exit, v: 0 }`; the `vals` of the k-hits and all-hits methods are then 2 scalars per record.
+    /// # Safety
+    /// as `new`
+    pub unsafe fn new_with_leaf(ctx: *mut ffi::bvhgpu_ctx, trees: &[*mut ffi::bvhgpu_tree], tree_of: &[u32], xforms: &[[T; 12]], leaf: c_int) -> GpuInstances<T> {
+        assert_eq!(tree_of.len(), xforms.len(), "one tree slot and one transform per instance");
+        let mut set = core::ptr::null_mut();
+        let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+            ffi::bvhgpu_instances_create_leaf_f32(ctx, trees.as_ptr(), trees.len(), tree_of.as_ptr(), xforms.as_ptr().cast(), xforms.len(), ffi::BVHGPU_HOST, leaf, &mut set)
+        } else {
+            ffi::bvhgpu_instances_create_leaf_f64(ctx, trees.as_ptr(), trees.len(), tree_of.as_ptr(), xforms.as_ptr().cast(), xforms.len(), ffi::BVHGPU_HOST, leaf, &mut set)
+        };
+        check(ctx, rc);
+        GpuInstances { ctx, set, n: xforms.len(), _t: core::marker::PhantomData }
+    }
+
+    /// The set's leaf kind (`ffi::BVHGPU_LEAF_*`)
+    pub fn leaf(&self) -> c_int {
+        let mut leaf: c_int = ffi::BVHGPU_LEAF_TRIANGLE;
+        check(self.ctx, unsafe { ffi::bvhgpu_instances_leaf(self.set, &mut leaf) });
+        leaf
+    }
+
+    // scalars per record of the set's ray queries
+    fn width(&self) -> usize {
+        if self.leaf() == ffi::BVHGPU_LEAF_TRIANGLE { 3 } else { 2 }
+    }
+
     /// The re-pose and the re-sync: after moving instances, and after any rebuild, refit or `set_triangles` of a member tree
     pub fn update(&mut self, xforms: &[[T; 12]]) {
         assert_eq!(xforms.len(), self.n, "one transform per instance");
@@ -871,7 +902,8 @@ impl<T: GpuScalar> GpuInstances<T> {
         }
         let raw: Vec<T::RayC> = rays.iter().map(T::ray_to_ffi).collect();
         let n = raw.len();
-        let mut vals = vec![T::default(); 3 * n];
+        let w = self.width();
+        let mut vals = vec![T::default(); w * n];
         let mut inst = vec![0u32; n];
         let mut shape = vec![0u32; n];
         let flags: c_uint = if first { ffi::BVHGPU_TRAVERSE_FIRST } else { 0 };
@@ -885,7 +917,7 @@ impl<T: GpuScalar> GpuInstances<T> {
             }
         };
         check(self.ctx, rc);
-        (0..n).map(|j| InstanceHit { intersection: Intersection::new(vals[3 * j], vals[3 * j + 1], vals[3 * j + 2]), instance: inst[j], shape: shape[j] }).collect()
+        (0..n).map(|j| InstanceHit { intersection: Intersection::new(vals[w * j], vals[w * j + 1], if w == 3 { vals[w * j + 2] } else { T::default() }), instance: inst[j], shape: shape[j] }).collect()
     }
 
     /// Per region of `m` world-space planes `[nx, ny, nz, d]` the `(instance, shape)` pairs whose box passes, as a CSR
@@ -952,7 +984,7 @@ impl<T: GpuScalar> GpuInstances<T> {
                 let rows = if count_only { 0 } else { total as usize };
                 instance.resize(rows, 0u32);
                 shape.resize(rows, 0u32);
-                vals.resize(3 * rows, T::default());
+                vals.resize(self.width() * rows, T::default());
                 let (ip, sp, vp) = if count_only {
                     (core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut())
                 } else {
@@ -1066,7 +1098,7 @@ impl<T: GpuScalar> GpuInstances<T> {
         let n = raw.len();
         let k32 = u32::try_from(k).unwrap_or(u32::MAX);   // (out of range: the engine answers BVHGPU_INVALID_ARG and `check` panics with its message)
         let slots = if (1..=ffi::BVHGPU_INSTANCES_KHITS_MAX_K).contains(&k32) { n * k } else { 0 };
-        let (mut instance, mut shape, mut vals) = (vec![0u32; slots], vec![0u32; slots], vec![T::default(); 3 * slots]);
+        let (mut instance, mut shape, mut vals) = (vec![0u32; slots], vec![0u32; slots], vec![T::default(); self.width() * slots]);
         unsafe {
             let tp = tmax.map_or(core::ptr::null(), |m| m.as_ptr());
             let rc = if T::DTYPE == ffi::BVHGPU_F32 {
@@ -1102,7 +1134,8 @@ impl<T: GpuScalar> GpuInstances<T> {
         }
         let raw: Vec<T::RayC> = rays.iter().map(T::ray_to_ffi).collect();
         let n = raw.len();
-        let mut vals = vec![T::default(); 3 * n];
+        let w = self.width();
+        let mut vals = vec![T::default(); w * n];
         let mut inst = vec![0u32; n];
         let mut shape = vec![0u32; n];
         let flags: c_uint = if first { ffi::BVHGPU_TRAVERSE_FIRST } else { 0 };
@@ -1117,7 +1150,7 @@ impl<T: GpuScalar> GpuInstances<T> {
             }
         };
         check(self.ctx, rc);
-        (0..n).map(|j| InstanceHit { intersection: Intersection::new(vals[3 * j], vals[3 * j + 1], vals[3 * j + 2]), instance: inst[j], shape: shape[j] }).collect()
+        (0..n).map(|j| InstanceHit { intersection: Intersection::new(vals[w * j], vals[w * j + 1], if w == 3 { vals[w * j + 2] } else { T::default() }), instance: inst[j], shape: shape[j] }).collect()
     }
 
     /// `khits` over the instances visible to each ray (`bvhgpu_instances_khits_masked_*`)
@@ -1132,7 +1165,7 @@ impl<T: GpuScalar> GpuInstances<T> {
         let n = raw.len();
         let k32 = u32::try_from(k).unwrap_or(u32::MAX);   // (out of range: the engine answers BVHGPU_INVALID_ARG and `check` panics with its message)
         let slots = if (1..=ffi::BVHGPU_INSTANCES_KHITS_MAX_K).contains(&k32) { n * k } else { 0 };
-        let (mut instance, mut shape, mut vals) = (vec![0u32; slots], vec![0u32; slots], vec![T::default(); 3 * slots]);
+        let (mut instance, mut shape, mut vals) = (vec![0u32; slots], vec![0u32; slots], vec![T::default(); self.width() * slots]);
         unsafe {
             let tp = tmax.map_or(core::ptr::null(), |m| m.as_ptr());
             let mp = ray_mask.map_or(core::ptr::null(), |m| m.as_ptr());
@@ -1178,7 +1211,7 @@ impl<T: GpuScalar> GpuInstances<T> {
                 let rows = if count_only { 0 } else { total as usize };
                 instance.resize(rows, 0u32);
                 shape.resize(rows, 0u32);
-                vals.resize(3 * rows, T::default());
+                vals.resize(self.width() * rows, T::default());
                 let (ip, sp, vp) = if count_only {
                     (core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut())
                 } else {

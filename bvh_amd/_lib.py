@@ -185,6 +185,12 @@ SYMBOLS = [
     ("bvhgpu_hits_fetch_allhits", _i, [_vp, _vp, _vp, _vp, _i]),
     ("bvhgpu_within_f32", _i, [_vp, _vp, _vp, _sz, _i, _i, _u, _pp]),
     ("bvhgpu_within_f64", _i, [_vp, _vp, _vp, _sz, _i, _i, _u, _pp]),
+    ("bvhgpu_knearest_sphere_f32", _i, [_vp, _vp, _sz, _i, C.c_uint32, _vp, _vp]),
+    ("bvhgpu_knearest_sphere_f64", _i, [_vp, _vp, _sz, _i, C.c_uint32, _vp, _vp]),
+    ("bvhgpu_knearest_tree_sphere_f32", _i, [_vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp]),
+    ("bvhgpu_knearest_tree_sphere_f64", _i, [_vp, _vp, _sz, _i, C.c_uint32, _vp, _vp, _vp]),
+    ("bvhgpu_within_sphere_f32", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
+    ("bvhgpu_within_sphere_f64", _i, [_vp, _vp, _vp, _sz, _i, _u, _pp]),
     ("bvhgpu_hits_fetch_within", _i, [_vp, _vp, _vp, _vp, _i]),
     ("bvhgpu_region_f32", _i, [_vp, _vp, _sz, C.c_uint32, _i, _u, _pp]),
     ("bvhgpu_region_f64", _i, [_vp, _vp, _sz, C.c_uint32, _i, _u, _pp]),

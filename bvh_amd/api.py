@@ -690,7 +690,60 @@ class _Hits:
             pass
 
 
-class _TreeBase(_Typed):
+class _SpherePointQueries:
+    """The point families against the tree's spheres (set_spheres): bvhgpu_knearest_sphere_*, _knearest_tree_sphere_* and _within_sphere_*,
+    which _TreeBase inherits.  The shape distance is sqrt(d), d the squared distance from the point to the solid ball {cx, cy, cz, r}:
+    len = |p - c| rounded as dot3 and one sqrt, g = len - r, d = max(g, 0)^2 with a NaN kept (0 inside and on the ball; r is taken
+    literally).  Everything else — the loops, the strict comparisons, padding, memory rules, dtypes, returns — is knearest_batch's,
+    knearest_tree_batch's and within_batch's.  Nodes are pruned by their boxes: the rows are the k nearest / all within in the geometric
+    sense when every sphere lies inside its shape's box, as with spheres_aabbs.  A tree without spheres raises INVALID_ARG."""
+
+    def _knearest_sphere(self, entry: str, points, k: int, max_dist, with_limit: bool):
+        """_knearest's marshalling for the entries without a kind argument"""
+        fn = getattr(_lib.load(), f"bvhgpu_{entry}_{self.sfx}")
+        k = int(k)
+        rows = k if 1 <= k <= _lib.KNN_MAX_K else 0       # (out of range: the engine answers INVALID_ARG before it touches a buffer)
+        p, pp, n, mem, _m, mp = self._points_in(points, max_dist)   # (p, _m: what the pointers point into stays alive over the call)
+        shape, dist, sp, dp = self._alloc_out(p.device if mem == DEVICE else None, (n, rows), (n, rows))
+        limit = (mp,) if with_limit else ()
+        check(fn(self._t, pp, n, mem, k & 0xFFFFFFFF, *limit, sp, dp), self.ctx._h)
+        return shape, dist
+
+    def knearest_sphere_batch(self, points, k: int):
+        """bvhgpu_knearest_sphere_*: the k nearest spheres of every point, knearest_batch's loop and returns — (shape[n, k], dist[n, k]),
+        rows ascending, equal distances in leaf pre-order, padding NONE and +inf.  1 <= k <= _lib.KNN_MAX_K."""
+        self._ready()
+        return self._knearest_sphere("knearest_sphere", points, k, None, False)
+
+    def nearest_sphere_batch(self, points):
+        """knearest_sphere_batch with k = 1 and the last axis dropped: (shape[n], dist[n]); NONE and +inf for an empty hierarchy"""
+        shape, dist = self.knearest_sphere_batch(points, 1)
+        return shape[:, 0], dist[:, 0]
+
+    def knearest_tree_sphere_batch(self, points, k: int, max_dist=None):
+        """bvhgpu_knearest_tree_sphere_*: the same rows found nearest child first over the BvhNode array, knearest_tree_batch's descent,
+        max_dist (None, a scalar or n values in the points' memory) and returns.  The tree must have been built here; no flatten is
+        needed.  Ties stay in the order this walk meets them."""
+        return self._knearest_sphere("knearest_tree_sphere", points, k, max_dist, True)
+
+    def within_sphere_batch(self, points, max_dist, sort: bool = True, count_only: bool = False):
+        """bvhgpu_within_sphere_*: every sphere within max_dist[i] of point i (d <= max_dist[i]^2), as a CSR — within_batch's loop, flags
+        and returns: (offsets[n+1], shape[total], dist[total]), rows in a stable ascending sort by distance unless sort=False;
+        count_only=True gives the offsets alone."""
+        self._ready()
+        flags = (0 if sort else _lib.WITHIN_LIST_ORDER) | (_lib.WITHIN_COUNT_ONLY if count_only else 0)
+        if max_dist is None:
+            raise BvhGpuError(_lib.INVALID_ARG, "within_sphere_batch needs max_dist (a scalar or one value per point)")
+        p, pp, n, mem, _m, mp = self._points_in(points, max_dist)   # (p, _m: what the pointers point into stays alive over the call)
+        dev = p.device if mem == DEVICE else None
+        if dev is not None:
+            _torch_sync(dev)
+        fn = getattr(_lib.load(), f"bvhgpu_within_sphere_{self.sfx}")
+        check(fn(self._t, pp, mp, n, mem, flags, C.byref(self._hits.h)), self.ctx._h)
+        return self._hits.fetch_within(n, self.ft, dev, count_only)
+
+
+class _TreeBase(_SpherePointQueries, _Typed):
     def __init__(self, ctx: Context, handle, sfx: str):
         self.ctx = ctx
         self._t = handle

@@ -92,6 +92,9 @@ int rule_shape_kind(bvhgpu_ctx* ctx, int kind) {
 int rule_kind_array(const bvhgpu_tree* t, int kind) {
     return kind == 1 && !t->has_tris ? fail(t->ctx, BVHGPU_INVALID_ARG, "triangle distance needs bvhgpu_tree_set_triangles first") : (int)BVHGPU_OK;
 }
+int rule_sphere_array(const bvhgpu_tree* t) {   // the *_sphere_* point entries: rule_kind_array's place
+    return !t->has_spheres ? fail(t->ctx, BVHGPU_INVALID_ARG, "sphere distance needs bvhgpu_tree_set_spheres first") : (int)BVHGPU_OK;
+}
 // a walk that tests the leaves' navigator boxes cannot run on an imported tree that lost them — nor on a set with such a member
 bool folded_away(const bvhgpu_tree* t) { return t->exact_only && !t->built && !t->unfolded; }
 int rule_unfolded(const bvhgpu_tree* t) {
@@ -676,9 +679,12 @@ int do_pairs(bvhgpu_ctx* ctx, const typename Traits<T>::Ray* rays, const T* tris
 // One set of rules and one row stage (points, max_dist → dist, shape); bvhgpu_nearest_* is k = 1 without limits, and only the
 // nearest-first descent takes max_dist.  That descent reads the BvhNode array (a tree built here, flattened or not); the other two walks
 // read the flattened arrays.  (A NULL tree is refused without a message here and with one by the later families: kept as it is.)
+// sphere (bvhgpu_knearest_sphere_* / _knearest_tree_sphere_*): the shape distance is the sphere's, `kind` is not looked at, and the two kind
+// rules are replaced by rule_sphere_array.
 enum class PointWalk { Nearest, KNearest, KNearestTree };
 template <typename T>
-int do_points(bvhgpu_tree* t, PointWalk walk, const T* points, size_t n, int mem, int kind, uint32_t k, const T* max_dist, uint32_t* out_shape, T* out_dist) {
+int do_points(bvhgpu_tree* t, PointWalk walk, const T* points, size_t n, int mem, int kind, uint32_t k, const T* max_dist, uint32_t* out_shape, T* out_dist,
+              bool sphere = false) {
     if (!t) return BVHGPU_INVALID_ARG;
     bvhgpu_ctx* ctx = t->ctx;
     if (const int rc = settle(t)) return rc;
@@ -690,8 +696,13 @@ int do_points(bvhgpu_tree* t, PointWalk walk, const T* points, size_t n, int mem
     }
     if (const int rc = rule_k(ctx, k, BVHGPU_KNN_MAX_K, "BVHGPU_KNN_MAX_K")) return rc;
     if (n && (!points || !out_shape || !out_dist)) return fail(ctx, BVHGPU_INVALID_ARG, "NULL argument");
-    if (const int rc = rule_shape_kind(ctx, kind)) return rc;
-    if (const int rc = rule_kind_array(t, kind)) return rc;
+    if (sphere) {
+        if (const int rc = rule_sphere_array(t)) return rc;
+        kind = POINT_KIND_SPHERE;
+    } else {
+        if (const int rc = rule_shape_kind(ctx, kind)) return rc;
+        if (const int rc = rule_kind_array(t, kind)) return rc;
+    }
     if (const int rc = rule_rows_size(ctx, n, k, walk == PointWalk::Nearest ? "too many points in one call" : "too many results (points x k) in one call")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -767,7 +778,7 @@ int do_allhits(bvhgpu_tree* t, const typename Traits<T>::Ray* rays, const T* tma
 }
 
 template <typename T>
-int do_within(bvhgpu_tree* t, const T* points, const T* max_dist, size_t n, int mem, int kind, unsigned flags, bvhgpu_hits** hits) {
+int do_within(bvhgpu_tree* t, const T* points, const T* max_dist, size_t n, int mem, int kind, unsigned flags, bvhgpu_hits** hits, bool sphere = false) {
     if (!t) return no_tree();
     bvhgpu_ctx* ctx = t->ctx;
     if (const int rc = rule_hits_arg(ctx, hits)) return rc;
@@ -778,10 +789,11 @@ int do_within(bvhgpu_tree* t, const T* points, const T* max_dist, size_t n, int 
     if (n && !points) return fail(ctx, BVHGPU_INVALID_ARG, "points is NULL");
     if (n && !max_dist) return fail(ctx, BVHGPU_INVALID_ARG, "max_dist is NULL");
     if (const int rc = rule_mem(ctx, mem)) return rc;
-    if (const int rc = rule_shape_kind(ctx, kind)) return rc;
+    if (!sphere) { if (const int rc = rule_shape_kind(ctx, kind)) return rc; }   // (bvhgpu_within_sphere_*: no kind argument)
     if (flags & ~(BVHGPU_WITHIN_LIST_ORDER | BVHGPU_WITHIN_COUNT_ONLY))
         return fail(ctx, BVHGPU_INVALID_ARG, "within flags: BVHGPU_WITHIN_LIST_ORDER and BVHGPU_WITHIN_COUNT_ONLY only");
-    if (const int rc = rule_kind_array(t, kind)) return rc;
+    if (const int rc = sphere ? rule_sphere_array(t) : rule_kind_array(t, kind)) return rc;
+    if (sphere) kind = POINT_KIND_SPHERE;
     if (const int rc = rule_batch_size(ctx, n, "points")) return rc;
     return guarded(ctx, [&] {
         use_device(ctx);
@@ -1777,6 +1789,20 @@ int bvhgpu_knearest_tree_f64(bvhgpu_tree* t, const double* points, size_t n, int
                              uint32_t* out_shape, double* out_dist) {
     return do_points<double>(t, PointWalk::KNearestTree, points, n, mem, kind, k, max_dist, out_shape, out_dist);
 }
+int bvhgpu_knearest_sphere_f32(bvhgpu_tree* t, const float* points, size_t n, int mem, uint32_t k, uint32_t* out_shape, float* out_dist) {
+    return do_points<float>(t, PointWalk::KNearest, points, n, mem, 0, k, nullptr, out_shape, out_dist, true);
+}
+int bvhgpu_knearest_sphere_f64(bvhgpu_tree* t, const double* points, size_t n, int mem, uint32_t k, uint32_t* out_shape, double* out_dist) {
+    return do_points<double>(t, PointWalk::KNearest, points, n, mem, 0, k, nullptr, out_shape, out_dist, true);
+}
+int bvhgpu_knearest_tree_sphere_f32(bvhgpu_tree* t, const float* points, size_t n, int mem, uint32_t k, const float* max_dist, uint32_t* out_shape,
+                                    float* out_dist) {
+    return do_points<float>(t, PointWalk::KNearestTree, points, n, mem, 0, k, max_dist, out_shape, out_dist, true);
+}
+int bvhgpu_knearest_tree_sphere_f64(bvhgpu_tree* t, const double* points, size_t n, int mem, uint32_t k, const double* max_dist, uint32_t* out_shape,
+                                    double* out_dist) {
+    return do_points<double>(t, PointWalk::KNearestTree, points, n, mem, 0, k, max_dist, out_shape, out_dist, true);
+}
 int bvhgpu_traverse_khits_f32(bvhgpu_tree* t, const bvhgpu_ray_f32* rays, const float* tmax, size_t n_rays, int mem, int leaf, uint32_t k,
                               uint32_t* out_shape, float* out_vals) {
     return do_khits<float>(t, rays, tmax, n_rays, mem, leaf, k, out_shape, out_vals);
@@ -1798,6 +1824,12 @@ int bvhgpu_within_f32(bvhgpu_tree* t, const float* points, const float* max_dist
 }
 int bvhgpu_within_f64(bvhgpu_tree* t, const double* points, const double* max_dist, size_t n, int mem, int kind, unsigned flags, bvhgpu_hits** hits) {
     return do_within<double>(t, points, max_dist, n, mem, kind, flags, hits);
+}
+int bvhgpu_within_sphere_f32(bvhgpu_tree* t, const float* points, const float* max_dist, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_within<float>(t, points, max_dist, n, mem, 0, flags, hits, true);
+}
+int bvhgpu_within_sphere_f64(bvhgpu_tree* t, const double* points, const double* max_dist, size_t n, int mem, unsigned flags, bvhgpu_hits** hits) {
+    return do_within<double>(t, points, max_dist, n, mem, 0, flags, hits, true);
 }
 int bvhgpu_region_f32(bvhgpu_tree* t, const float* planes, size_t n, uint32_t m, int mem, unsigned flags, bvhgpu_hits** hits) {
     return do_region<float>(t, planes, n, m, mem, flags, hits);

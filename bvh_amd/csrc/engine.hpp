@@ -427,7 +427,10 @@ bool traverse_check(bvhgpu_hits* h);   // after a stream synchronise: false = en
 // nearest.hip
 template <typename T>
 void nearest_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint32_t* out_shape_dev, T* out_dist_dev);
-// knn.hip: the k nearest shapes per point (bvhgpu_knearest_*); out_*: n x k, an empty hierarchy fills them with padding
+// the shape distance of knearest_batch / knearest_tree_batch / within_batch: the public kinds 0 (the shape's AABB) and 1 (its triangle), and
+// the spheres of bvhgpu_tree_set_spheres, which the *_sphere_* entries select — no public kind value stands for it
+constexpr int POINT_KIND_SPHERE = 2;
+// knn.hip: the k nearest shapes per point (bvhgpu_knearest_* / _knearest_sphere_*); out_*: n x k, an empty hierarchy fills them with padding
 template <typename T>
 void knearest_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint32_t k, uint32_t* out_shape_dev, T* out_dist_dev);
 // knn_tree.hip: the same rows found nearest child first over the BvhNode array (bvhgpu_knearest_tree_*); max_dist_dev: NULL or n limits
@@ -444,7 +447,8 @@ void khits_batch(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, const 
 // more than 2^32-1 candidates (the result object then holds an empty all-hits result).
 template <typename T>
 void allhits_batch(bvhgpu_tree* t, const typename Traits<T>::Ray* rays_dev, const T* tmax_dev, size_t n, int leaf, unsigned flags, bvhgpu_hits* h);
-// within.hip: every shape within max_dist_dev[i] of point i as a CSR (bvhgpu_within_*); kind: 0 the shapes' AABBs, 1 their triangles; flags:
+// within.hip: every shape within max_dist_dev[i] of point i as a CSR (bvhgpu_within_* / _within_sphere_*); kind: 0 the shapes' AABBs, 1 their
+// triangles, POINT_KIND_SPHERE their spheres; flags:
 // BVHGPU_WITHIN_*.  Synchronous: h->offsets / h->indices / h->row_vals and h->total are complete on return.  Throws Fail::Overflow when the
 // batch has more than 2^32-1 candidates (the result object then holds an empty within result).
 template <typename T>

@@ -17,17 +17,89 @@
 // of two arrays (distances, then shapes).  A wave's access to one slot is 64 consecutive 4-byte (8-byte) words: conflict-free under both LDS
 // banking rules.  A lane only ever touches its own column, so the kernel has no barrier.
 // Block size: walk.hpp's topk_block.
+// Shape distance: kind 0 the shape's own box, kind 1 its triangle (bvhgpu_knearest_*), or its sphere (bvhgpu_knearest_sphere_*, point_dist.hpp's
+// sphere_dist2).  The nodes are pruned by their boxes whatever the kind, as the reference prunes any PointDistance shape by its
+// Aabb.  The sphere distance is not the box distance, so the array is chosen by kind 1's rule: UNFOLDED for t->unfolded || t->n == 1.
+#ifndef KNN_KERNEL_TEXT
 #include "point_dist.hpp"
 
 namespace bvhgpu {
 
 static_assert(topk_fits(BVHGPU_KNN_MAX_K), "the k-nearest lists of 64 lanes must fit a workgroup's LDS");
 
-template <typename T, bool TRIANGLE, bool UNFOLDED>
-__global__ __launch_bounds__(256) void k_knearest(const TravNode<T>* __restrict__ nodes, uint32_t n_trav,
-                                                  const T* __restrict__ shape_aabbs, const T* __restrict__ tris,
+// The kernel text stands at the end of this file, behind KNN_KERNEL_TEXT, and is compiled twice by the two includes of this file below
+// (DESIGN.md §4t's way, §4u): once as k_knearest<T, TRIANGLE, UNFOLDED> — the same text under the same name and template head as before
+// there was a sphere distance, hence the same instructions — and once as k_knearest_sphere<T, UNFOLDED>.  POINT_K(name): the kernel's
+// name; POINT_KIND_TPARAM: the kind's place in its template head; POINT_KIND_VALUE: its shape distance, 0 box, 1 triangle, 2 sphere.
+// `prims` is the array of that kind: the triangles (9 T per shape), the spheres (4 T per shape), not read for the box.
+#define KNN_KERNEL_TEXT
+#define POINT_K(name) name
+#define POINT_KIND_TPARAM bool TRIANGLE,
+#define POINT_KIND_VALUE (TRIANGLE ? 1 : 0)
+#include "knn.hip"
+#undef POINT_K
+#undef POINT_KIND_TPARAM
+#undef POINT_KIND_VALUE
+#define POINT_K(name) name##_sphere
+#define POINT_KIND_TPARAM
+#define POINT_KIND_VALUE 2
+#include "knn.hip"
+#undef POINT_K
+#undef POINT_KIND_TPARAM
+#undef POINT_KIND_VALUE
+#undef KNN_KERNEL_TEXT
+
+// an empty hierarchy: every slot is padding (+inf is no byte pattern, so no memset)
+template <typename T>
+__global__ __launch_bounds__(256) void k_knn_fill(uint32_t* __restrict__ out_shape, T* __restrict__ out_dist, uint32_t total) {
+    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    out_shape[e] = NONE;
+    out_dist[e] = (T)INFINITY;
+}
+
+template <typename T>
+void knearest_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint32_t k, uint32_t* out_shape_dev, T* out_dist_dev) {
+    if (!n) return;
+    hipStream_t st = t->ctx->stream;
+    if (t->n == 0) {
+        const size_t total = n * k;   // (the caller has checked n x k < 2^32)
+        hipLaunchKernelGGL((k_knn_fill<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out_shape_dev, out_dist_dev, (uint32_t)total);
+        BVH_HIP(hipGetLastError());
+        return;
+    }
+    const unsigned bs = topk_block<T>(k);
+    const dim3 grid((unsigned)((n + bs - 1) / bs)), block(bs);
+    const size_t lds = (size_t)bs * k * (sizeof(T) + 4);
+    ensure_flat_arrays(t);
+    const TravNode<T>* nodes = t->trav.as<TravNode<T>>();
+    const uint32_t n_trav = (uint32_t)t->n_trav;
+    const bool unfolded = t->unfolded || t->n == 1;   // a single-shape tree has one (leaf) entry and no navigator
+#define LAUNCH_KNEAREST_K(K, PRIMS) hipLaunchKernelGGL(K, grid, block, lds, st, nodes, n_trav, t->aabbs.as<T>(), PRIMS, points_dev, (uint32_t)n, k, \
+                                                      out_shape_dev, out_dist_dev)
+#define LAUNCH_KNEAREST(TRI, UNF) LAUNCH_KNEAREST_K((k_knearest<T, TRI, UNF>), t->tris.as<T>())
+    if (kind == POINT_KIND_SPHERE) {
+        if (unfolded) LAUNCH_KNEAREST_K((k_knearest_sphere<T, true>), t->spheres.as<T>());
+        else LAUNCH_KNEAREST_K((k_knearest_sphere<T, false>), t->spheres.as<T>());
+    } else if (kind == 1) { if (unfolded) LAUNCH_KNEAREST(true, true); else LAUNCH_KNEAREST(true, false); }
+    else { if (unfolded) LAUNCH_KNEAREST(false, true); else LAUNCH_KNEAREST(false, false); }
+#undef LAUNCH_KNEAREST
+#undef LAUNCH_KNEAREST_K
+    BVH_HIP(hipGetLastError());
+}
+template void knearest_batch<float>(bvhgpu_tree*, const float*, size_t, int, uint32_t, uint32_t*, float*);
+template void knearest_batch<double>(bvhgpu_tree*, const double*, size_t, int, uint32_t, uint32_t*, double*);
+
+}  // namespace bvhgpu
+
+#else   // KNN_KERNEL_TEXT: the kernel text, inside namespace bvhgpu (see the includes of this file above)
+
+template <typename T, POINT_KIND_TPARAM bool UNFOLDED>
+__global__ __launch_bounds__(256) void POINT_K(k_knearest)(const TravNode<T>* __restrict__ nodes, uint32_t n_trav,
+                                                  const T* __restrict__ shape_aabbs, const T* __restrict__ prims,
                                                   const T* __restrict__ points, uint32_t n, uint32_t k, uint32_t* __restrict__ out_shape,
                                                   T* __restrict__ out_dist) {
+    constexpr int KIND = POINT_KIND_VALUE;
     extern __shared__ __align__(16) unsigned char knn_lds[];
     const uint32_t block = blockDim.x;
     T* __restrict__ ld = reinterpret_cast<T*>(knn_lds) + threadIdx.x;                                        // slot j: ld[j * block]
@@ -51,7 +123,8 @@ __global__ __launch_bounds__(256) void k_knearest(const TravNode<T>* __restrict_
         if (leaf) {
             if (enter) {
                 T d;
-                if (TRIANGLE) d = triangle_dist2<T>(tris + 9 * (size_t)nd.shape, p);
+                if (KIND == 2) d = sphere_dist2<T>(prims + 4 * (size_t)nd.shape, p);
+                else if (KIND == 1) d = triangle_dist2<T>(prims + 9 * (size_t)nd.shape, p);
                 else {
                     const T* sb = shape_aabbs + 6 * (size_t)nd.shape;
                     const T mn[3] = {sb[0], sb[1], sb[2]}, mx[3] = {sb[3], sb[4], sb[5]};
@@ -103,40 +176,4 @@ __global__ __launch_bounds__(256) void k_knearest(const TravNode<T>* __restrict_
     for (uint32_t j = len; j < k; j++) { os[j] = NONE; od[j] = (T)INFINITY; }
 }
 
-// an empty hierarchy: every slot is padding (+inf is no byte pattern, so no memset)
-template <typename T>
-__global__ __launch_bounds__(256) void k_knn_fill(uint32_t* __restrict__ out_shape, T* __restrict__ out_dist, uint32_t total) {
-    const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= total) return;
-    out_shape[e] = NONE;
-    out_dist[e] = (T)INFINITY;
-}
-
-template <typename T>
-void knearest_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint32_t k, uint32_t* out_shape_dev, T* out_dist_dev) {
-    if (!n) return;
-    hipStream_t st = t->ctx->stream;
-    if (t->n == 0) {
-        const size_t total = n * k;   // (the caller has checked n x k < 2^32)
-        hipLaunchKernelGGL((k_knn_fill<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out_shape_dev, out_dist_dev, (uint32_t)total);
-        BVH_HIP(hipGetLastError());
-        return;
-    }
-    const unsigned bs = topk_block<T>(k);
-    const dim3 grid((unsigned)((n + bs - 1) / bs)), block(bs);
-    const size_t lds = (size_t)bs * k * (sizeof(T) + 4);
-    ensure_flat_arrays(t);
-    const TravNode<T>* nodes = t->trav.as<TravNode<T>>();
-    const uint32_t n_trav = (uint32_t)t->n_trav;
-    const bool unfolded = t->unfolded || t->n == 1;   // a single-shape tree has one (leaf) entry and no navigator
-#define LAUNCH_KNEAREST(TRI, UNF) hipLaunchKernelGGL((k_knearest<T, TRI, UNF>), grid, block, lds, st, nodes, n_trav, t->aabbs.as<T>(), \
-                                                     t->tris.as<T>(), points_dev, (uint32_t)n, k, out_shape_dev, out_dist_dev)
-    if (kind == 1) { if (unfolded) LAUNCH_KNEAREST(true, true); else LAUNCH_KNEAREST(true, false); }
-    else { if (unfolded) LAUNCH_KNEAREST(false, true); else LAUNCH_KNEAREST(false, false); }
-#undef LAUNCH_KNEAREST
-    BVH_HIP(hipGetLastError());
-}
-template void knearest_batch<float>(bvhgpu_tree*, const float*, size_t, int, uint32_t, uint32_t*, float*);
-template void knearest_batch<double>(bvhgpu_tree*, const double*, size_t, int, uint32_t, uint32_t*, double*);
-
-}  // namespace bvhgpu
+#endif   // KNN_KERNEL_TEXT

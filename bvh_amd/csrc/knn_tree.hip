@@ -27,6 +27,9 @@
 // no barrier.  The insertion below is a copy of k_knearest's (k_ray_khits holds a third, without the NaN branch).  Sharing it has been tried
 // twice; the second time as a __forceinline__ template taking ld, ls, block, k and references to len / full / has_nan / bound: it changed
 // the instruction text of 17 of the 22 kernels that hold the insertion and the register counts of several, so it stays restated.
+// Shape distance: kind 0 / 1 (bvhgpu_knearest_tree_*), or the shape's sphere (bvhgpu_knearest_tree_sphere_*, point_dist.hpp's sphere_dist2;
+// DESIGN.md §4u): only d at a leaf changes, the child boxes prune as before.
+#ifndef KNN_TREE_KERNEL_TEXT
 #include "point_dist.hpp"
 #include "tree_node.hpp"
 
@@ -34,12 +37,61 @@ namespace bvhgpu {
 
 static_assert(topk_fits(BVHGPU_KNN_MAX_K), "the k-nearest lists of 64 lanes must fit a workgroup's LDS");
 
-template <typename T, bool TRIANGLE>
-__global__ __launch_bounds__(256) void k_knearest_tree(const typename Traits<T>::Node* __restrict__ nodes, uint32_t n_nodes,
-                                                       const T* __restrict__ shape_aabbs, const T* __restrict__ tris,
+// The kernel text stands at the end of this file, behind KNN_TREE_KERNEL_TEXT, and is compiled twice by the two includes of this file
+// below (knn.hip's arrangement): as k_knearest_tree<T, TRIANGLE>, name, template head and instructions as they were, and
+// as k_knearest_tree_sphere<T>.  POINT_KIND_VALUE: 0 box, 1 triangle, 2 sphere; `prims` is the array of that kind.
+#define KNN_TREE_KERNEL_TEXT
+#define POINT_K(name) name
+#define POINT_KIND_TPARAM , bool TRIANGLE
+#define POINT_KIND_VALUE (TRIANGLE ? 1 : 0)
+#include "knn_tree.hip"
+#undef POINT_K
+#undef POINT_KIND_TPARAM
+#undef POINT_KIND_VALUE
+#define POINT_K(name) name##_sphere
+#define POINT_KIND_TPARAM
+#define POINT_KIND_VALUE 2
+#include "knn_tree.hip"
+#undef POINT_K
+#undef POINT_KIND_TPARAM
+#undef POINT_KIND_VALUE
+#undef KNN_TREE_KERNEL_TEXT
+
+template <typename T>
+void knearest_tree_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint32_t k, const T* max_dist_dev, uint32_t* out_shape_dev,
+                         T* out_dist_dev) {
+    if (!n) return;
+    using Node = typename Traits<T>::Node;
+    hipStream_t st = t->ctx->stream;
+    const unsigned bs = topk_block<T>(k);
+    const dim3 grid((unsigned)((n + bs - 1) / bs)), block(bs);
+    const size_t lds = (size_t)bs * k * (sizeof(T) + 4);
+    const uint32_t n_nodes = t->n ? (uint32_t)t->n_nodes : 0u;
+    if (kind == POINT_KIND_SPHERE)
+        hipLaunchKernelGGL((k_knearest_tree_sphere<T>), grid, block, lds, st, t->nodes.as<Node>(), n_nodes, t->aabbs.as<T>(), t->spheres.as<T>(),
+                           points_dev, (uint32_t)n, k, max_dist_dev, out_shape_dev, out_dist_dev);
+    else if (kind == 1)
+        hipLaunchKernelGGL((k_knearest_tree<T, true>), grid, block, lds, st, t->nodes.as<Node>(), n_nodes, t->aabbs.as<T>(), t->tris.as<T>(),
+                           points_dev, (uint32_t)n, k, max_dist_dev, out_shape_dev, out_dist_dev);
+    else
+        hipLaunchKernelGGL((k_knearest_tree<T, false>), grid, block, lds, st, t->nodes.as<Node>(), n_nodes, t->aabbs.as<T>(), t->tris.as<T>(),
+                           points_dev, (uint32_t)n, k, max_dist_dev, out_shape_dev, out_dist_dev);
+    BVH_HIP(hipGetLastError());
+}
+template void knearest_tree_batch<float>(bvhgpu_tree*, const float*, size_t, int, uint32_t, const float*, uint32_t*, float*);
+template void knearest_tree_batch<double>(bvhgpu_tree*, const double*, size_t, int, uint32_t, const double*, uint32_t*, double*);
+
+}  // namespace bvhgpu
+
+#else   // KNN_TREE_KERNEL_TEXT: the kernel text, inside namespace bvhgpu (see the includes of this file above)
+
+template <typename T POINT_KIND_TPARAM>
+__global__ __launch_bounds__(256) void POINT_K(k_knearest_tree)(const typename Traits<T>::Node* __restrict__ nodes, uint32_t n_nodes,
+                                                       const T* __restrict__ shape_aabbs, const T* __restrict__ prims,
                                                        const T* __restrict__ points, uint32_t n, uint32_t k,
                                                        const T* __restrict__ max_dist, uint32_t* __restrict__ out_shape,
                                                        T* __restrict__ out_dist) {
+    constexpr int KIND = POINT_KIND_VALUE;
     extern __shared__ __align__(16) unsigned char knn_tree_lds[];
     const uint32_t block = blockDim.x;
     T* __restrict__ ld = reinterpret_cast<T*>(knn_tree_lds) + threadIdx.x;                                   // slot j: ld[j * block]
@@ -67,7 +119,8 @@ __global__ __launch_bounds__(256) void k_knearest_tree(const typename Traits<T>:
         uint32_t next = NONE;
         if (nd.shape != NONE) {
             T d;
-            if (TRIANGLE) d = triangle_dist2<T>(tris + 9 * (size_t)nd.shape, p);
+            if (KIND == 2) d = sphere_dist2<T>(prims + 4 * (size_t)nd.shape, p);
+            else if (KIND == 1) d = triangle_dist2<T>(prims + 9 * (size_t)nd.shape, p);
             else {
                 const T* sb = shape_aabbs + 6 * (size_t)nd.shape;
                 const T mn[3] = {sb[0], sb[1], sb[2]}, mx[3] = {sb[3], sb[4], sb[5]};
@@ -130,25 +183,4 @@ __global__ __launch_bounds__(256) void k_knearest_tree(const typename Traits<T>:
     for (uint32_t j = len; j < k; j++) { os[j] = NONE; od[j] = (T)INFINITY; }
 }
 
-template <typename T>
-void knearest_tree_batch(bvhgpu_tree* t, const T* points_dev, size_t n, int kind, uint32_t k, const T* max_dist_dev, uint32_t* out_shape_dev,
-                         T* out_dist_dev) {
-    if (!n) return;
-    using Node = typename Traits<T>::Node;
-    hipStream_t st = t->ctx->stream;
-    const unsigned bs = topk_block<T>(k);
-    const dim3 grid((unsigned)((n + bs - 1) / bs)), block(bs);
-    const size_t lds = (size_t)bs * k * (sizeof(T) + 4);
-    const uint32_t n_nodes = t->n ? (uint32_t)t->n_nodes : 0u;
-    if (kind == 1)
-        hipLaunchKernelGGL((k_knearest_tree<T, true>), grid, block, lds, st, t->nodes.as<Node>(), n_nodes, t->aabbs.as<T>(), t->tris.as<T>(),
-                           points_dev, (uint32_t)n, k, max_dist_dev, out_shape_dev, out_dist_dev);
-    else
-        hipLaunchKernelGGL((k_knearest_tree<T, false>), grid, block, lds, st, t->nodes.as<Node>(), n_nodes, t->aabbs.as<T>(), t->tris.as<T>(),
-                           points_dev, (uint32_t)n, k, max_dist_dev, out_shape_dev, out_dist_dev);
-    BVH_HIP(hipGetLastError());
-}
-template void knearest_tree_batch<float>(bvhgpu_tree*, const float*, size_t, int, uint32_t, const float*, uint32_t*, float*);
-template void knearest_tree_batch<double>(bvhgpu_tree*, const double*, size_t, int, uint32_t, const double*, uint32_t*, double*);
-
-}  // namespace bvhgpu
+#endif   // KNN_TREE_KERNEL_TEXT

@@ -96,4 +96,29 @@ template <typename T> __device__ __forceinline__ T triangle_dist2(const T* __res
     return dot3<T>(diff, diff);
 }
 
+// The third shape distance (bvhgpu_knearest_sphere_* / _knearest_tree_sphere_* / _within_sphere_*): the squared distance
+// from p to the solid ball {cx, cy, cz, r} of bvhgpu_tree_set_spheres.  Every operation rounded once in T, in this order, no contraction:
+//   f[k] = p[k] - c[k];  s2 = dot3(f, f);  len = sqrt(s2) (correctly rounded);  g = len - r;  q = (g < 0) ? 0 : g;  d = q * q
+// A point inside or on the ball is at distance 0.  Nothing is special-cased:
+//   - a NaN in the sphere or the point gives d = NaN — NOT 0, unlike the box distance's max(0): `g < 0` is false for NaN and q keeps it.
+//     The families' NaN rules then apply (never a candidate of within; accepted by k-nearest only while the list is not full);
+//   - r is taken literally and never validated (as set_spheres says): a negative r adds |r|; r = +inf gives 0 unless len is +inf too,
+//     which gives NaN;
+//   - an s2 that overflows gives len = +inf and d = +inf.
+// Lists and thresholds hold d; output distances are sqrt(d), as for the other two kinds.  The walks still prune by the tree's boxes:
+// rows are "the k nearest" / "all within" in the geometric sense where every sphere lies inside its shape's box (spheres_aabbs);
+// a sphere that reaches outside its box can be pruned, as the ray walks can miss it.
+// `sphere` is 16-byte aligned (load_sphere, walk.hpp).
+template <typename T> __device__ __forceinline__ T sphere_dist2(const T* __restrict__ sphere, const T p[3]) {
+    T s[4], f[3];
+    load_sphere(sphere, s);
+#pragma unroll
+    for (int k = 0; k < 3; k++) f[k] = p[k] - s[k];
+    const T s2 = dot3<T>(f, f);
+    const T len = sqrt(s2);
+    const T g = len - s[3];
+    const T q = (g < (T)0) ? (T)0 : g;   // (keeps NaN)
+    return q * q;
+}
+
 }  // namespace bvhgpu

@@ -685,6 +685,47 @@ int bvhgpu_within_f64(bvhgpu_tree *tree, const double *points, const double *max
                       bvhgpu_hits **hits);
 int bvhgpu_hits_fetch_within(bvhgpu_hits *hits, uint32_t *offsets, uint32_t *shape, void *dist, int mem);
 
+/* ---- the point families against sphere shapes (ABI 7): the k nearest spheres of a point, and every sphere within max_dist of it.  A
+ * tree can carry one sphere {cx, cy, cz, r} per shape (bvhgpu_tree_set_spheres_*); these six entries are bvhgpu_knearest_*,
+ * bvhgpu_knearest_tree_* and bvhgpu_within_* word for word — the loop, the list, the strict comparisons, the NaN rules, the rows, the
+ * padding (BVHGPU_NONE, +inf), max_dist, the flags, the result object (of the within kind: bvhgpu_hits_fetch_within fetches it), the
+ * trees each accepts, the argument rules and their order — with one change: shape.distance_squared(p) at a leaf is the squared
+ * distance from p to the SOLID BALL, and there is no `kind` argument.
+ *   f[k] = p[k] - c[k]           k = 0, 1, 2
+ *   s2   = f[0]*f[0] + f[1]*f[1];  s2 = s2 + f[2]*f[2]       (three products, two sums, in this order)
+ *   len  = sqrt(s2)              correctly rounded
+ *   g    = len - r
+ *   q    = (g < 0) ? 0 : g       a point inside or on the ball is at distance 0; NaN stays NaN
+ *   d    = q * q
+ * Every operation is rounded once in T, in the order written, no contraction.  Lists and thresholds hold d; output distances are
+ * sqrt(d), as for kinds 0 and 1.  Deliberate consequences:
+ *  - A NaN in the sphere or the point gives d = NaN — not 0, unlike the box distance, whose max(0) turns NaN into 0.  The families' NaN
+ *    rules apply: never a candidate of within; accepted by the k-nearest forms only while the list is not full.
+ *  - r is taken literally and never validated, as bvhgpu_tree_set_spheres_* says: a negative r adds |r| to the distance; r = +inf gives
+ *    0 unless len is +inf too, which gives NaN.  An s2 that overflows gives d = +inf.
+ *  - Nodes are still pruned by their BOXES, exactly as the reference prunes any PointDistance shape by its Aabb: a subtree is entered
+ *    by the box rule of the unsuffixed entry.  A sphere that reaches outside its shape's box can therefore be pruned, as the ray entries
+ *    can miss it.  Rows are "the k nearest spheres" / "all spheres within max_dist" in the geometric sense where every sphere lies inside
+ *    its shape's box (boxes {c - r, c + r}, as the Python layer's spheres_aabbs makes them); in every case they are what the loop above produces.
+ *  - The sphere distance is not the box distance, so the array that is walked is chosen by kind 1's rule (bvhgpu_within_*, "Trees"):
+ *    the caveat about scene-imported trees with empty child bounds applies as for kind 1.
+ * Refused with BVHGPU_INVALID_ARG at the place the unsuffixed entry checks its kind's array: a tree without spheres (before the first
+ * bvhgpu_tree_set_spheres_*, or after a rebuild to another shape count dropped them).  The unsuffixed entries keep refusing kind 2. */
+int bvhgpu_knearest_sphere_f32(bvhgpu_tree *tree, const float *points, size_t n, int mem, uint32_t k,
+                               uint32_t *out_shape /* n x k */, float *out_dist /* n x k */);
+int bvhgpu_knearest_sphere_f64(bvhgpu_tree *tree, const double *points, size_t n, int mem, uint32_t k,
+                               uint32_t *out_shape /* n x k */, double *out_dist /* n x k */);
+int bvhgpu_knearest_tree_sphere_f32(bvhgpu_tree *tree, const float *points, size_t n, int mem, uint32_t k,
+                                    const float *max_dist /* NULL, or n values in the points' memory space */,
+                                    uint32_t *out_shape /* n x k */, float *out_dist /* n x k */);
+int bvhgpu_knearest_tree_sphere_f64(bvhgpu_tree *tree, const double *points, size_t n, int mem, uint32_t k,
+                                    const double *max_dist /* NULL, or n values in the points' memory space */,
+                                    uint32_t *out_shape /* n x k */, double *out_dist /* n x k */);
+int bvhgpu_within_sphere_f32(bvhgpu_tree *tree, const float *points, const float *max_dist, size_t n, int mem, unsigned flags,
+                             bvhgpu_hits **hits);
+int bvhgpu_within_sphere_f64(bvhgpu_tree *tree, const double *points, const double *max_dist, size_t n, int mem, unsigned flags,
+                             bvhgpu_hits **hits);
+
 /* ---- convex regions (plane sets): EVERY shape whose box passes a set of planes, per region, in list order, as a CSR — view-frustum
  * culling, shadow-cascade slabs, a light's froxel, portals, selection prisms: "which shapes can this camera see".  Every operation below
  * is rounded once in the tree's dtype T, in the order written, with no contraction.

@@ -213,6 +213,12 @@ extern "C" {
     // every shape within max_dist[i] of point i as a CSR (offsets: n + 1, shape: total, dist: total; no padding; rows in ascending distance, or in the loop's order with BVHGPU_WITHIN_LIST_ORDER; offsets only with BVHGPU_WITHIN_COUNT_ONLY)
     pub fn bvhgpu_within_f32(t: *mut bvhgpu_tree, points: *const f32, max_dist: *const f32, n: usize, mem: c_int, kind: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_within_f64(t: *mut bvhgpu_tree, points: *const f64, max_dist: *const f64, n: usize, mem: c_int, kind: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_knearest_sphere_f32(t: *mut bvhgpu_tree, points: *const f32, n: usize, mem: c_int, k: u32, out_shape: *mut u32, out_dist: *mut f32) -> c_int;
+    pub fn bvhgpu_knearest_sphere_f64(t: *mut bvhgpu_tree, points: *const f64, n: usize, mem: c_int, k: u32, out_shape: *mut u32, out_dist: *mut f64) -> c_int;
+    pub fn bvhgpu_knearest_tree_sphere_f32(t: *mut bvhgpu_tree, points: *const f32, n: usize, mem: c_int, k: u32, max_dist: *const f32, out_shape: *mut u32, out_dist: *mut f32) -> c_int;
+    pub fn bvhgpu_knearest_tree_sphere_f64(t: *mut bvhgpu_tree, points: *const f64, n: usize, mem: c_int, k: u32, max_dist: *const f64, out_shape: *mut u32, out_dist: *mut f64) -> c_int;
+    pub fn bvhgpu_within_sphere_f32(t: *mut bvhgpu_tree, points: *const f32, max_dist: *const f32, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
+    pub fn bvhgpu_within_sphere_f64(t: *mut bvhgpu_tree, points: *const f64, max_dist: *const f64, n: usize, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;
     pub fn bvhgpu_hits_fetch_within(h: *mut bvhgpu_hits, offsets: *mut u32, shape: *mut u32, dist: *mut c_void, mem: c_int) -> c_int;
     // every shape whose box passes the m planes of region i as a CSR in FlatBvh::traverse's order (planes: n x m x 4; offsets: n + 1, shape: total, inside: total bytes with BVHGPU_REGION_CLASSIFY; offsets only with BVHGPU_REGION_COUNT_ONLY)
     pub fn bvhgpu_region_f32(t: *mut bvhgpu_tree, planes: *const f32, n: usize, m: u32, mem: c_int, flags: c_uint, hits: *mut *mut bvhgpu_hits) -> c_int;

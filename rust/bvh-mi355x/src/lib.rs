@@ -732,6 +732,69 @@ impl<T: GpuScalar> GpuBvh<T> {
         (shape, dist)
     }
 
+    /// `nearest_k` against the tree's spheres (`set_spheres`; `bvhgpu_knearest_sphere_*`): the same loop, list and rows with the shape
+    /// distance of the solid ball — `len = |p - c|`, `g = len - r`, `d = max(g, 0)^2` with a NaN kept, every operation rounded once; a
+    /// point inside or on a ball is at distance 0.  Nodes are pruned by their boxes, so the rows are the `k` nearest spheres in the
+    /// geometric sense when every sphere lies inside its shape's box.  `k = 1` is the nearest sphere per point.
+    pub fn nearest_k_sphere(&self, points: &[[T; 3]], k: usize) -> (Vec<u32>, Vec<T>) {
+        self.nearest_k_sphere_rows(points, k, None, false)
+    }
+
+    /// `nearest_k_tree` against the tree's spheres (`bvhgpu_knearest_tree_sphere_*`): the nearest-child-first descent over the BvhNode
+    /// array with `nearest_k_sphere`'s distance; `max_dist` and ties as for `nearest_k_tree`.
+    pub fn nearest_k_tree_sphere(&self, points: &[[T; 3]], k: usize, max_dist: Option<&[T]>) -> (Vec<u32>, Vec<T>) {
+        if let Some(m) = max_dist {
+            assert_eq!(m.len(), points.len(), "max_dist needs one value per point");
+        }
+        self.nearest_k_sphere_rows(points, k, max_dist, true)
+    }
+
+    fn nearest_k_sphere_rows(&self, points: &[[T; 3]], k: usize, max_dist: Option<&[T]>, tree_form: bool) -> (Vec<u32>, Vec<T>) {
+        let k32 = u32::try_from(k).unwrap_or(u32::MAX);   // (out of range: the engine answers BVHGPU_INVALID_ARG and `check` panics with its message)
+        let slots = if (1..=ffi::BVHGPU_KNN_MAX_K).contains(&k32) { points.len() * k } else { 0 };
+        let mut shape = vec![0u32; slots];
+        let mut dist = vec![T::default(); slots];
+        unsafe {
+            let mp = max_dist.map_or(core::ptr::null(), |m| m.as_ptr());
+            let (pp, n, sp, dp) = (points.as_ptr(), points.len(), shape.as_mut_ptr(), dist.as_mut_ptr());
+            let rc = match (T::DTYPE == ffi::BVHGPU_F32, tree_form) {
+                (true, false) => ffi::bvhgpu_knearest_sphere_f32(self.tree, pp.cast(), n, ffi::BVHGPU_HOST, k32, sp, dp.cast()),
+                (false, false) => ffi::bvhgpu_knearest_sphere_f64(self.tree, pp.cast(), n, ffi::BVHGPU_HOST, k32, sp, dp.cast()),
+                (true, true) => ffi::bvhgpu_knearest_tree_sphere_f32(self.tree, pp.cast(), n, ffi::BVHGPU_HOST, k32, mp.cast(), sp, dp.cast()),
+                (false, true) => ffi::bvhgpu_knearest_tree_sphere_f64(self.tree, pp.cast(), n, ffi::BVHGPU_HOST, k32, mp.cast(), sp, dp.cast()),
+            };
+            check(self.ctx, rc);
+        }
+        (shape, dist)
+    }
+
+    /// `within_distance` against the tree's spheres (`bvhgpu_within_sphere_*`): every sphere within `max_dist[i]` of point i, with
+    /// `nearest_k_sphere`'s distance (`d <= max_dist[i]^2`; a NaN distance is never a candidate).  Flags and returns as for `within_distance`.
+    pub fn within_distance_sphere(&self, points: &[[T; 3]], max_dist: &[T], sort: bool, count_only: bool) -> (Vec<u32>, Vec<u32>, Vec<T>) {
+        assert_eq!(max_dist.len(), points.len(), "one max_dist per point");
+        let mut hits = core::ptr::null_mut();
+        let flags = (if sort { 0 } else { ffi::BVHGPU_WITHIN_LIST_ORDER }) | (if count_only { ffi::BVHGPU_WITHIN_COUNT_ONLY } else { 0 });
+        let mut offsets = vec![0u32; points.len() + 1];
+        let (mut shape, mut dist) = (Vec::new(), Vec::new());
+        unsafe {
+            let rc = if T::DTYPE == ffi::BVHGPU_F32 {
+                ffi::bvhgpu_within_sphere_f32(self.tree, points.as_ptr().cast(), max_dist.as_ptr().cast(), points.len(), ffi::BVHGPU_HOST, flags, &mut hits)
+            } else {
+                ffi::bvhgpu_within_sphere_f64(self.tree, points.as_ptr().cast(), max_dist.as_ptr().cast(), points.len(), ffi::BVHGPU_HOST, flags, &mut hits)
+            };
+            check(self.ctx, rc);
+            let mut total = 0u64;
+            check(self.ctx, ffi::bvhgpu_hits_info(hits, core::ptr::null_mut(), &mut total, core::ptr::null_mut()));
+            if !count_only {
+                shape.resize(total as usize, 0u32);
+                dist.resize(total as usize, T::default());
+            }
+            check(self.ctx, ffi::bvhgpu_hits_fetch_within(hits, offsets.as_mut_ptr(), shape.as_mut_ptr(), dist.as_mut_ptr() as *mut c_void, ffi::BVHGPU_HOST));
+            ffi::bvhgpu_hits_destroy(hits);
+        }
+        (offsets, shape, dist)
+    }
+
     /// Build again from new AABBs into the same device buffers (a frame loop: no allocation in the steady state)
     pub fn rebuild(&mut self, aabbs: &[[T; 6]]) {
         unsafe { check(self.ctx, T::rebuild_flat(self.tree, aabbs.as_ptr().cast(), aabbs.len(), ffi::BVHGPU_HOST)); }
